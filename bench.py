@@ -25,10 +25,16 @@ Prints ONE JSON line on rank 0 (contract in the task description), including
                    aligner's stream, inside the timed region), HBM traffic from the committed PMC profile;
   roofline_valu -- the resource that actually binds the kernel: vector-ALU issue (SQ counters from the
                    committed profile) and DP cells / s (live);
+and, with --full only (they take runs of their own; null otherwise),
   value_e2e     -- reads/s including host<->device transfers (upload + run + fetch of distinct batches,
                    two aligners on two host threads so that transfers overlap kernels); never `value`;
+  value_two_in_flight -- the same steps with two batches in flight (two aligners, two HIP streams);
   cpu_baseline  -- the CPU oracle (a port of the reference algorithm; the Rust reference cannot be
                    built here) timed on a bounded sample of the same reads on this box's host cores.
+
+--dump-outputs DIR writes what the last timed step computed (rank 0's batch) as DIR/<name>.npy: a fixed,
+seeded sample of its reads with their alignment counts, statuses, alignment records and op bytes (see
+dump_outputs).  The inputs are seeded, so two builds run with the same arguments can be compared file for file.
 """
 import argparse
 import json
@@ -104,6 +110,40 @@ def profile_entry(name, match):
     return j, None
 
 
+DUMP_READS = 32768      # reads in the sample --dump-outputs writes (all of them in a smaller batch)
+DUMP_ALNS = 100_000     # at most this many of their alignment records: 21 fields x 8 bytes each
+DUMP_OP_BYTES = 6 << 20  # at most this many of their op-stream bytes, 4 bytes each: ~43 MB in all at most
+
+
+def _ranges(starts, lens):
+    """the concatenation of [starts[i], starts[i] + lens[i]) over i, as one index array"""
+    starts, lens = np.asarray(starts, np.int64), np.asarray(lens, np.int64)
+    return np.repeat(starts - (np.cumsum(lens) - lens), lens) + np.arange(int(lens.sum()), dtype=np.int64)
+
+
+def dump_outputs(out_dir, g):
+    """g: the capi.BatchResult of one batch, what a caller of the timed path receives.  Writes, for a fixed sample of its
+    reads (seeded, in read order): reads (their indices), aln_count and read_status per read, aln_<field> per alignment
+    record of those reads (every field of thm_aln but padding), and ops, the op bytes of those records (genome range,
+    then transcript range, record by record).  float64, ops float32; integer values are exact in both."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = int(g.n_reads)
+    reads = np.arange(n) if n <= DUMP_READS else np.sort(np.random.default_rng(0).choice(n, DUMP_READS, replace=False))
+    off = g.offsets.astype(np.int64)
+    cnt = off[reads + 1] - off[reads]
+    status = np.zeros(len(reads), np.int32) if g.status is None else g.status[reads]
+    alns = g.alns[_ranges(off[reads], cnt)[:DUMP_ALNS]]
+    lens = np.stack([alns["ops_len"], alns["tx_ops_len"]], axis=1).ravel()
+    starts = np.stack([alns["ops_off"], alns["tx_ops_off"]], axis=1).ravel()
+    ops = g.ops[_ranges(starts, lens)[:DUMP_OP_BYTES]]
+    arrays = {"reads": reads, "aln_count": cnt, "read_status": status, "ops": ops.astype(np.float32)}
+    for f in alns.dtype.names:
+        if f != "pad_":
+            arrays["aln_" + f] = alns[f]
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, np.float32 if name == "ops" else np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -127,13 +167,19 @@ def main():
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
                     help="process-group backend; gloo + --one-device runs the N > 1 code path on a one-GPU box (tests)")
     ap.add_argument("--one-device", action="store_true", help="every rank on device 0 (tests of the N > 1 path on a one-GPU box)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the extra figures (value_e2e, value_two_in_flight): profiling passes")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the figures that take runs of their own: value_e2e, value_two_in_flight, cpu_baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full: skip value_e2e and value_two_in_flight")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--dump-digest", default=None,
                     help="write PATH.<rank>.json: SHA-256 of this rank's alignment records and op streams per batch (tests compare them "
                          "with the CPU oracle's for the same shard)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed (rank 0) as DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = 0 if args.one_device else int(os.environ.get("LOCAL_RANK", "0"))
@@ -279,6 +325,8 @@ def main():
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, aligners[(K - 1) % NB].fetch())
 
     # ---------------- the one collective: counter all-reduce ----------------
     cnt_local = np.zeros(capi.N_COUNTERS, np.uint64)
@@ -337,7 +385,7 @@ def main():
 
     # ---------------- PCIe-inclusive rate (not `value`): upload + run + fetch of distinct batches ----------------
     value_e2e = None
-    if not args.no_e2e and not strong and NB >= 2:
+    if args.full and not args.no_e2e and not strong and NB >= 2:
         n_thr = 2
         per_thread = max(2, K // 2)
 
@@ -368,7 +416,7 @@ def main():
     # ---------------- two batches in flight (not `value`): step i + 1 is launched (another aligner, another HIP stream)
     # before step i is waited for, so that the tail of one batch's extend kernel is filled by the other batch ----------------
     value_two_in_flight = None
-    if not args.no_e2e and NB >= 2 and not strong:
+    if args.full and not args.no_e2e and NB >= 2 and not strong:
         barrier()
         t1 = time.perf_counter()
         for i in range(K + 1):
@@ -387,7 +435,7 @@ def main():
 
     # ---------------- CPU baseline (rank 0, N = 1 only) ----------------
     cpu_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import pyoracle as orc
 
         bases, offsets = batches[0]

@@ -29,7 +29,7 @@ def _last_json(out):
 
 def test_bench_line_single_gpu():
     out = subprocess.run([sys.executable, "bench.py", "--reads-per-gpu", "60000", "--ref-len", "4000000", "--steps", "4", "--warmup", "1",
-                          "--cpu-seconds", "1"], cwd=ROOT, check=True, capture_output=True, timeout=900).stdout
+                          "--cpu-seconds", "1", "--full"], cwd=ROOT, check=True, capture_output=True, timeout=900).stdout
     d = _last_json(out)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline", "cpu_baseline"):
@@ -41,6 +41,34 @@ def test_bench_line_single_gpu():
     assert d["cpu_baseline"]["kind"] == "port" and d["cpu_baseline"]["cores"] >= 1
     assert d["value_e2e"]["value"] > 0 and d["value_two_in_flight"]["value"] > 0
     assert abs(d["value"] - 60000 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-3
+
+
+def test_bench_plain_run_dumps_the_last_step(tmp_path):
+    """without --full the line carries no extra figures; --dump-outputs writes the last timed step's result, which is the
+    CPU oracle's on that step's batch (5 steps over 4 batches: the last one is batch 0)"""
+    dump = tmp_path / "out"
+    out = subprocess.run([sys.executable, "bench.py", "--reads-per-gpu", "60000", "--ref-len", "4000000", "--steps", "5", "--warmup", "1",
+                          "--dump-outputs", str(dump)], cwd=ROOT, check=True, capture_output=True, timeout=900).stdout
+    d = _last_json(out)
+    assert d["steps"] == 5 and d["counters"]["reads"] == 5 * 60000 and d["ms_per_step"] > 0
+    assert d["cpu_baseline"] is None and d["value_e2e"] is None and d["value_two_in_flight"] is None
+    import types
+
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+    from oracle import pyoracle as orc
+    from thermite_amd import capi, synth
+
+    tables = synth.synth_reference(length=4000000)
+    bases, off, _ = synth.simulate_reads(tables, 60000, 91, sub_rate=0.01, indel_rate=0.001, stream=100)
+    r = orc.Index(tables, sa=capi.build_suffix_array(tables["text"])).align_batch(bases, off, capi.CI_OPTS, n_threads=16)
+    bench.dump_outputs(str(tmp_path / "oracle"), types.SimpleNamespace(n_reads=r.n, offsets=r.offsets, alns=r.alns, ops=r.ops, status=None))
+    names = sorted(os.listdir(tmp_path / "oracle"))
+    assert sorted(os.listdir(dump)) == names
+    for f in names:
+        assert np.array_equal(np.load(dump / f), np.load(tmp_path / "oracle" / f)), f
 
 
 def test_bench_two_ranks_sharded_stream(tmp_path):
