@@ -192,6 +192,45 @@ typedef struct thm_swg_view {
   const uint8_t* ops;
 } thm_swg_view;
 
+/* Result of one extend_left_right call (src/aligner.rs:352-407): bio's Alignment
+ * in the coordinates of the caller's reference sequence (ylen = its length) and
+ * read (xlen = its length).  The op stream is rev(left.operations) ++ Match x
+ * hit.len ++ right.operations (:388-394), Xclips included. */
+typedef struct thm_lr_aln {
+  uint64_t ystart;
+  uint64_t yend;
+  uint64_t ylen;
+  uint64_t ops_off;
+  int32_t score;
+  uint32_t xstart;
+  uint32_t xend;
+  uint32_t xlen;
+  uint32_t ops_len; /* bytes */
+  uint32_t pad_;
+} thm_lr_aln; /* 56 bytes */
+
+typedef struct thm_lr_view {
+  uint64_t n;
+  uint64_t n_op_bytes;
+  const thm_lr_aln* alns;
+  const uint8_t* ops;
+} thm_lr_view;
+
+/* Result of thm_align_seed_hits_batch: one GenomeAlignment per hit, in hit
+ * order, in the thm_aln record thm_batch_view uses (primary = 0).  Op streams
+ * lie back to back in hit order (gx ops, then tx ops of an exonic alignment).
+ * hit_status is NULL when every hit is THM_OK, else [n_hits] of THM_OK,
+ * THM_ERR_OUT_OF_CONTRACT or THM_ERR_UNSUPPORTED; the record of a failed hit
+ * is all zero and has no op bytes.  n_failed_hits counts those hits. */
+typedef struct thm_hits_view {
+  uint64_t n_hits;
+  uint64_t n_op_bytes;
+  const thm_aln* alns;
+  const uint8_t* ops;
+  uint64_t n_failed_hits;
+  const int32_t* hit_status;
+} thm_hits_view;
+
 /* Counters summed over a run; this is the vector the multi-GPU path
  * all-reduces (one ncclAllReduce of THM_N_COUNTERS u64). */
 enum {
@@ -321,6 +360,55 @@ int32_t thm_smems_batch(thm_aligner*, const uint8_t* bases, const uint64_t* offs
 int32_t thm_swg_extend_batch(thm_aligner*, const uint8_t* x_bases, const uint64_t* x_off, const uint8_t* y_bases,
                              const uint64_t* y_off, const uint32_t* band_width, const int32_t* x_drop,
                              uint32_t max_band_width, uint64_t n, thm_swg_view* out);
+
+/* extend_left_right (src/aligner.rs:352-407) for a batch of independent
+ * problems: problem i extends hits[i] (ref_idx relative to its reference
+ * sequence y_bases[y_off[i] .. y_off[i+1]), query_idx relative to its read
+ * x_bases[x_off[i] .. x_off[i+1])) to the right and, reversed, to the left,
+ * with SwgExtend::new(max_band_width) and the aligner's scoring.  Bases are
+ * taken as given (align_read upper-cases its read first, src/aligner.rs:125).
+ * The same THM_ERR_OUT_OF_CONTRACT rules as thm_swg_extend_batch, plus the
+ * slices that panic in the reference: query_idx + len > |read| (:356) and
+ * ref_idx + len > |ref| (:357).  A hit that is not an exact match is legal
+ * (the reference does not check it).  Op streams lie back to back in problem
+ * order. */
+int32_t thm_extend_left_right_batch(thm_aligner*, const uint8_t* x_bases, const uint64_t* x_off, const uint8_t* y_bases,
+                                    const uint64_t* y_off, const thm_mem* hits, const uint32_t* band_width,
+                                    const int32_t* x_drop, uint32_t max_band_width, uint64_t n, thm_lr_view* out);
+
+/* align_seed_hit (src/aligner.rs:198-314) for a batch of caller-chosen hits:
+ * extension in the genome window (:209-227) and in every transcript
+ * exon_to_tx.find yields (:229-258), lift_tx_to_gx, concat_to_chr_aln
+ * (:429-449) and the exonic / intronic / intergenic classification
+ * (:263-313), with primary = 0.  None of align_read's policy applies: no
+ * intron_mode check, no score filter, no band narrowing from hit to hit, no
+ * filter_overlapping (:143-187).  Reads are upper-cased and sanitised as
+ * thm_align_batch does (src/aligner.rs:125), so a hit thm_smems_batch returns
+ * aligns here exactly as it does inside thm_align_batch.
+ *
+ * hits[hit_off[r] .. hit_off[r+1]) are the hits of read r, in concatenated
+ * coordinates: the layout of thm_mems_view, so a thm_smems_batch result can be
+ * passed unchanged.  band_width / x_drop are per hit; max_band_width is the
+ * SwgExtend's (src/swg.rs:17-32).
+ *
+ * Per-hit outcomes (the other hits of the call are unaffected):
+ * THM_ERR_OUT_OF_CONTRACT for what panics in the reference -- a hit outside
+ * the text or crossing the end of its contig copy (the slices of :216-227),
+ * query_idx + len > |read|, band_width > max_band_width (src/swg.rs:32),
+ * x_drop < band_width, the lifts (src/txome.rs:102,154);
+ * THM_ERR_UNSUPPORTED for reads over 65535 bases and DP traces beyond the
+ * device-memory budget.  Call-level THM_ERR_INVALID_ARG: null pointers,
+ * non-monotone offsets, hit_off[n_reads] != n_hits.
+ *
+ * Counters: adds to THM_CNT_HITS, SWG_CALLS, DP_CELLS, DP_COLS, OP_BYTES and
+ * WINDOW_BYTES what the same hits add inside thm_align_batch (OP_BYTES: the
+ * bytes of every returned record).  The read-level counters (READS, ALIGNED,
+ * UNMAPPED, ALNS, EXONIC, INTRONIC, INTERGENIC, SMEMS) are left alone.
+ * The view stays valid until the next call of this function on the aligner. */
+int32_t thm_align_seed_hits_batch(thm_aligner*, const uint8_t* bases, const uint64_t* offsets, uint64_t n_reads,
+                                  const uint64_t* hit_off, const thm_mem* hits, uint64_t n_hits,
+                                  const uint32_t* band_width, const int32_t* x_drop, uint32_t max_band_width,
+                                  thm_hits_view* out);
 
 /* counters accumulated since the last reset (host copy) */
 int32_t thm_counters_get(thm_aligner*, uint64_t out[THM_N_COUNTERS]);

@@ -10,6 +10,8 @@
 //     Aligner::align_reads     <->  the loop of align_reads_from_file, src/aligner.rs:51-56, batched
 //     Aligner::all_smems       <->  Index::all_smems          src/index.rs:228
 //     Aligner::swg_extend      <->  SwgExtend::extend         src/swg.rs:31
+//     Aligner::extend_left_right <-> aligner::extend_left_right src/aligner.rs:352
+//     Aligner::align_seed_hits <->  aligner::align_seed_hit    src/aligner.rs:198, per hit of every read
 //     thermite::ThermiteAligner<->  wrapper::ThermiteAligner  src/wrapper.rs:20-123 (index file in, SAM records out)
 //     thermite::align_reads_from_file <-> aligner::align_reads_from_file  src/aligner.rs:22-120
 // Errors that are panics in the reference are exceptions here (never across the C ABI).
@@ -170,6 +172,60 @@ class Aligner {
     check(thm_swg_extend_batch(h_.get(), (const std::uint8_t*)x.data(), xo, (const std::uint8_t*)y.data(), yo, &band_width,
                                &x_drop, max_band_width, 1, &v));
     return SwgAlignment{v.alns[0].score, v.alns[0].xend, v.alns[0].yend, decode_ops(v.ops + v.alns[0].ops_off, v.alns[0].ops_len)};
+  }
+
+  // extend_left_right, src/aligner.rs:352-407: `hit` relative to `ref` and `read`
+  struct Alignment {  // bio::alignment::Alignment
+    std::int32_t score;
+    std::size_t ystart, xstart, yend, xend, ylen, xlen;
+    std::vector<AlignmentOperation> operations;
+  };
+  Alignment extend_left_right(const std::string& ref, const thm_mem& hit, const std::string& read, std::uint32_t band_width,
+                              std::int32_t x_drop, std::uint32_t max_band_width) {
+    const std::uint64_t xo[2] = {0, read.size()}, yo[2] = {0, ref.size()};
+    thm_lr_view v;
+    check(thm_extend_left_right_batch(h_.get(), (const std::uint8_t*)read.data(), xo, (const std::uint8_t*)ref.data(), yo, &hit,
+                                      &band_width, &x_drop, max_band_width, 1, &v));
+    const thm_lr_aln& a = v.alns[0];
+    return Alignment{a.score, a.ystart, a.xstart, a.yend, a.xend, a.ylen, a.xlen, decode_ops(v.ops + a.ops_off, a.ops_len)};
+  }
+
+  // align_seed_hit, src/aligner.rs:198-314, for every hit of every read: result[r][i] is hits_per_read[r][i]'s
+  // GenomeAlignment (primary false).  Throws on call-level errors; a hit whose status is not THM_OK has an all-zero
+  // record and no ops, its status in *status (hit order over all reads) when `status` is given.
+  std::vector<std::vector<GenomeAlignment>> align_seed_hits(const std::vector<std::string>& reads,
+                                                            const std::vector<std::vector<thm_mem>>& hits_per_read,
+                                                            const std::vector<std::uint32_t>& band_width,
+                                                            const std::vector<std::int32_t>& x_drop, std::uint32_t max_band_width,
+                                                            std::vector<std::int32_t>* status = nullptr) {
+    if (hits_per_read.size() != reads.size()) throw Error(THM_ERR_INVALID_ARG, "one hit list per read");
+    std::vector<std::uint8_t> bases;
+    std::vector<std::uint64_t> off{0}, hoff{0};
+    std::vector<thm_mem> hits;
+    for (std::size_t r = 0; r < reads.size(); r++) {
+      bases.insert(bases.end(), reads[r].begin(), reads[r].end());
+      off.push_back(bases.size());
+      hits.insert(hits.end(), hits_per_read[r].begin(), hits_per_read[r].end());
+      hoff.push_back(hits.size());
+    }
+    if (band_width.size() != hits.size() || x_drop.size() != hits.size()) throw Error(THM_ERR_INVALID_ARG, "one band and X-drop per hit");
+    thm_hits_view v;
+    check(thm_align_seed_hits_batch(h_.get(), bases.data(), off.data(), reads.size(), hoff.data(), hits.data(), hits.size(),
+                                    band_width.data(), x_drop.data(), max_band_width, &v));
+    if (status) status->assign(hits.size(), THM_OK);
+    std::vector<std::vector<GenomeAlignment>> out(reads.size());
+    for (std::size_t r = 0; r < reads.size(); r++)
+      for (std::uint64_t h = hoff[r]; h < hoff[r + 1]; h++) {
+        GenomeAlignment g;
+        g.rec = v.alns[h];
+        if (v.hit_status && status) (*status)[h] = v.hit_status[h];
+        if (!v.hit_status || v.hit_status[h] == THM_OK) {
+          g.operations = decode_ops(v.ops + g.rec.ops_off, g.rec.ops_len);
+          if (g.rec.aln_type == THM_ALN_EXONIC) g.tx_operations = decode_ops(v.ops + g.rec.tx_ops_off, g.rec.tx_ops_len);
+        }
+        out[r].push_back(std::move(g));
+      }
+    return out;
   }
   thm_aligner* get() { return h_.get(); }
   void set_opts(const AlignOpts& opts) {

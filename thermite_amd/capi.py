@@ -43,7 +43,10 @@ ALN_DT = np.dtype(
     ]
 )
 SWG_DT = np.dtype([("ops_off", "<u8"), ("ops_len", "<u4"), ("score", "<i4"), ("xend", "<u4"), ("yend", "<u4")])
-assert ALN_DT.itemsize == 112 and MEM_DT.itemsize == 16 and SWG_DT.itemsize == 24
+# thm_lr_aln: one extend_left_right result (bio Alignment), include/thermite.h
+LR_DT = np.dtype([("ystart", "<u8"), ("yend", "<u8"), ("ylen", "<u8"), ("ops_off", "<u8"), ("score", "<i4"),
+                  ("xstart", "<u4"), ("xend", "<u4"), ("xlen", "<u4"), ("ops_len", "<u4"), ("pad_", "<u4")])
+assert ALN_DT.itemsize == 112 and MEM_DT.itemsize == 16 and SWG_DT.itemsize == 24 and LR_DT.itemsize == 56
 
 N_COUNTERS = 16
 COUNTER_NAMES = ["reads", "aligned", "unmapped", "alns", "exonic", "intronic", "intergenic", "smems", "hits",
@@ -95,6 +98,15 @@ class SwgView(C.Structure):
     _fields_ = [("n", C.c_uint64), ("n_op_bytes", C.c_uint64), ("alns", C.c_void_p), ("ops", C.c_void_p)]
 
 
+class LrView(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("n_op_bytes", C.c_uint64), ("alns", C.c_void_p), ("ops", C.c_void_p)]
+
+
+class HitsView(C.Structure):
+    _fields_ = [("n_hits", C.c_uint64), ("n_op_bytes", C.c_uint64), ("alns", C.c_void_p), ("ops", C.c_void_p),
+                ("n_failed_hits", C.c_uint64), ("hit_status", C.c_void_p)]
+
+
 # every symbol include/thermite.h declares
 ABI_SYMBOLS = [
     "thm_index_create_in_memory", "thm_index_free", "thm_index_text_len", "thm_index_suffix_array",
@@ -104,6 +116,7 @@ ABI_SYMBOLS = [
     "thm_counters_reset", "thm_counters_device_ptr", "thm_timings_get", "thm_version", "thm_device_count",
     "thm_aligner_index", "thm_comm_unique_id", "thm_comm_create", "thm_comm_free", "thm_counters_allreduce",
     "thm_index_create_in_memory_ex", "thm_index_coord_bytes", "thm_index_suffix_array64", "thm_build_suffix_array64", "thm_build_suffix_array_gpu",
+    "thm_extend_left_right_batch", "thm_align_seed_hits_batch",
 ]
 # every symbol include/thermite_io.h declares
 IO_ABI_SYMBOLS = [
@@ -174,6 +187,10 @@ def lib():
     L.thm_swg_extend_batch.restype = i32
     L.thm_swg_extend_batch.argtypes = [vp, vp, vp, vp, vp, vp, vp, u32, u64, vp]
     L.thm_counters_get.restype = i32
+    L.thm_extend_left_right_batch.restype = i32
+    L.thm_extend_left_right_batch.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, u32, u64, vp]
+    L.thm_align_seed_hits_batch.restype = i32
+    L.thm_align_seed_hits_batch.argtypes = [vp, vp, vp, u64, vp, vp, u64, vp, vp, u32, vp]
     L.thm_counters_get.argtypes = [vp, vp]
     L.thm_counters_device_ptr.restype = vp
     L.thm_counters_device_ptr.argtypes = [vp]
@@ -532,6 +549,34 @@ class Aligner:
         self._chk(lib().thm_swg_extend_batch(self.h, _ptr(xb), _ptr(xo), _ptr(yb), _ptr(yo), _ptr(bw), _ptr(xd),
                                              max_bw, len(bw), C.byref(v)))
         return _copy(v.alns, v.n, SWG_DT), _copy(v.ops, v.n_op_bytes, np.uint8)
+
+    def extend_left_right_batch(self, x_bases, x_off, y_bases, y_off, hits, bw, xd, max_bw):
+        """extend_left_right (reference src/aligner.rs:352-407) per problem: read i = x_bases[x_off[i]:x_off[i+1]],
+        reference sequence i = y_bases[y_off[i]:y_off[i+1]], hits[i] (MEM_DT, relative to both).  Returns (LR_DT
+        records, op bytes); ops_off indexes the op bytes."""
+        xb, yb = _u8(x_bases), _u8(y_bases)
+        xo, yo = np.ascontiguousarray(x_off, "<u8"), np.ascontiguousarray(y_off, "<u8")
+        hits = np.ascontiguousarray(hits, MEM_DT)
+        bw, xd = np.ascontiguousarray(bw, "<u4"), np.ascontiguousarray(xd, "<i4")
+        v = LrView()
+        self._chk(lib().thm_extend_left_right_batch(self.h, _ptr(xb), _ptr(xo), _ptr(yb), _ptr(yo), _ptr(hits), _ptr(bw),
+                                                    _ptr(xd), max_bw, len(bw), C.byref(v)))
+        return _copy(v.alns, v.n, LR_DT), _copy(v.ops, v.n_op_bytes, np.uint8)
+
+    def align_seed_hits(self, bases, offsets, hit_off, hits, band_width, x_drop, max_band_width):
+        """align_seed_hit (reference src/aligner.rs:198-314) for each hit: hits[hit_off[r]:hit_off[r+1]] (MEM_DT,
+        concatenated coordinates) belong to read r -- a smems_batch result passes unchanged.  Returns (ALN_DT records in
+        hit order, op bytes, per-hit status int32 array: 0 = ok, ERR_OUT_OF_CONTRACT, ERR_UNSUPPORTED)."""
+        bases, offsets = _u8(bases), np.ascontiguousarray(offsets, "<u8")
+        hit_off, hits = np.ascontiguousarray(hit_off, "<u8"), np.ascontiguousarray(hits, MEM_DT)
+        bw, xd = np.ascontiguousarray(band_width, "<u4"), np.ascontiguousarray(x_drop, "<i4")
+        if not (len(hits) == len(bw) == len(xd)):
+            raise ThermiteError(ERR_INVALID_ARG, "hits, band_width and x_drop differ in length")
+        v = HitsView()
+        self._chk(lib().thm_align_seed_hits_batch(self.h, _ptr(bases), _ptr(offsets), len(offsets) - 1, _ptr(hit_off),
+                                                  _ptr(hits), len(hits), _ptr(bw), _ptr(xd), max_band_width, C.byref(v)))
+        status = (_copy(v.hit_status, v.n_hits, "<i4") if v.hit_status else np.zeros(int(v.n_hits), "<i4"))
+        return _copy(v.alns, v.n_hits, ALN_DT), _copy(v.ops, v.n_op_bytes, np.uint8), status
 
     def counters(self):
         out = np.zeros(N_COUNTERS, "<u8")

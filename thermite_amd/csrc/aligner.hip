@@ -217,7 +217,9 @@ void thm_aligner_free(thm_aligner* a) {
   DBuf* all[] = {&a->d_counters, &a->d_queue, &a->d_fault, &a->d_cursors, &a->b0, &a->b1, &a->b2, &a->b3, &a->b4,
                  &a->b5, &a->b6, &a->b7, &a->b8, &a->r_bases, &a->r_offsets, &a->r_san, &a->s_ms_end, &a->s_ms_lo, &a->s_ms_hi, &a->s_work_reads, &a->s_work_long, &a->s_work_cells, &a->s_work_counts, &a->s_fill_keys, &a->s_fill_perm, &a->s_fill_hist, &a->s_sel_scratch, &a->s_heavy, &a->s_slow, &a->s_team, &a->r_status, &a->e_slow, &a->e_recs, &a->e_wcnt, &a->t_memos, &a->t_recs, &a->t_dpops, &a->t_qlist, &a->t_act[0], &a->t_act[1], &a->t_ctl, &a->t_bail, &a->t_queue2, &a->t_trace, &a->t_ttrace, &a->t_hdr, &a->t_sums, &a->s_smems, &a->s_off, &a->s_cnt,
                  &a->s_hits, &a->s_cand_off, &a->scan_tmp, &a->e_cands, &a->e_heavy, &a->e_rel, &a->e_order, &a->e_ops, &a->e_nalns,
-                 &a->e_nalns64, &a->e_opbytes, &a->e_aln_off, &a->e_ops_off, &a->e_trace, &a->o_alns, &a->o_ops, &a->o_mems};
+                 &a->e_nalns64, &a->e_opbytes, &a->e_aln_off, &a->e_ops_off, &a->e_trace, &a->o_alns, &a->o_ops, &a->o_mems,
+                 &a->sh_bases, &a->sh_san, &a->sh_off, &a->sh_hits, &a->sh_read, &a->sh_bw, &a->sh_xd, &a->sh_list, &a->sh_out,
+                 &a->sh_status, &a->sh_ops, &a->sh_ctl, &a->sh_trace, &a->sh_slow};
   for (DBuf* b : all) b->release();
   for (int k = 0; k < 2; k++) {
     a->r_off[k].release();
@@ -382,6 +384,128 @@ int32_t thm_swg_extend_batch(thm_aligner* a, const uint8_t* x_bases, const uint6
   out->n = n;
   out->n_op_bytes = a->h_ops.size();
   out->alns = a->h_swg.data();
+  out->ops = a->h_ops.data();
+  return THM_OK;
+}
+
+// ------------------------------------------------- extend_left_right batch
+int32_t thm_extend_left_right_batch(thm_aligner* a, const uint8_t* x_bases, const uint64_t* x_off, const uint8_t* y_bases,
+                                    const uint64_t* y_off, const thm_mem* hits, const uint32_t* band_width,
+                                    const int32_t* x_drop, uint32_t max_band_width, uint64_t n, thm_lr_view* out) {
+  if (!a || !out || !x_off || !y_off || !hits || !band_width || !x_drop) return THM_ERR_INVALID_ARG;
+  memset(out, 0, sizeof(*out));
+  if (n == 0) return THM_OK;
+  if (n >= 0xFFFFFFFFull) return fail(a, THM_ERR_UNSUPPORTED, "more than 2^32-1 problems in one call");
+  if ((!x_bases && x_off[n] > 0) || (!y_bases && y_off[n] > 0)) return THM_ERR_INVALID_ARG;
+  HIPCHK(a, hipSetDevice(a->device));
+  uint32_t bw_max = 0, x_max = 0, y_max = 0;
+  std::vector<uint64_t> ops_off(n + 1, 0);
+  for (uint64_t i = 0; i < n; i++) {
+    if (x_off[i + 1] < x_off[i] || y_off[i + 1] < y_off[i]) return fail(a, THM_ERR_INVALID_ARG, "offsets not monotone");
+    const uint64_t xl = x_off[i + 1] - x_off[i], yl = y_off[i + 1] - y_off[i];
+    const thm_mem& h = hits[i];
+    if (band_width[i] > max_band_width)  // assert!, src/swg.rs:32
+      return fail(a, THM_ERR_OUT_OF_CONTRACT, "problem %llu: band_width %u > max_band_width %u (src/swg.rs:32)",
+                  (unsigned long long)i, band_width[i], max_band_width);
+    if (x_drop[i] < (int64_t)band_width[i])
+      return fail(a, THM_ERR_OUT_OF_CONTRACT, "problem %llu: x_drop < band_width is undefined in the reference",
+                  (unsigned long long)i);
+    if ((uint64_t)h.query_idx + h.len > xl)  // &read[hit.query_idx + hit.len..], src/aligner.rs:360
+      return fail(a, THM_ERR_OUT_OF_CONTRACT, "problem %llu: query_idx + len > read length (src/aligner.rs:360)",
+                  (unsigned long long)i);
+    if (h.ref_idx > yl || h.ref_idx + h.len > yl)  // &ref_seq[hit.ref_idx + hit.len..], src/aligner.rs:361
+      return fail(a, THM_ERR_OUT_OF_CONTRACT, "problem %llu: ref_idx + len > reference length (src/aligner.rs:361)",
+                  (unsigned long long)i);
+    if (xl > MAX_READ_LEN || band_width[i] > 2 * MAX_READ_LEN)
+      return fail(a, THM_ERR_UNSUPPORTED, "read longer than %u or band wider than +-%u", MAX_READ_LEN, 2 * MAX_READ_LEN);
+    // columns each side can reach: |x| + bw + 1
+    const uint64_t xr = xl - (h.query_idx + h.len), xlft = h.query_idx;
+    const uint64_t yr = std::min<uint64_t>(yl - (h.ref_idx + h.len), xr + band_width[i] + 1);
+    const uint64_t ylft = std::min<uint64_t>(std::min<uint64_t>(h.ref_idx, xl + band_width[i]), xlft + band_width[i] + 1);
+    bw_max = std::max(bw_max, band_width[i]);
+    x_max = std::max<uint32_t>(x_max, (uint32_t)std::max(xr, xlft));
+    y_max = std::max<uint32_t>(y_max, (uint32_t)std::max(yr, ylft));
+    ops_off[i + 1] = ops_off[i] + xr + yr + xlft + ylft + h.len + 16;
+  }
+  int cpl = (int)((2 * bw_max + 1 + 63) / 64);
+  ElrBatchParams p;
+  p.x_cap = (x_max + 15u) & ~15u;
+  p.y_cap = (y_max + 15u) & ~15u;
+  if (p.x_cap == 0) p.x_cap = 16;
+  if (p.y_cap == 0) p.y_cap = 16;
+  p.max_bw = bw_max;
+  p.scratch = nullptr;
+  p.scratch_per_wave = 0;
+  // bands over +-127 or problems beyond the LDS budget: the any-width kernel, chosen as thm_swg_extend_batch chooses it
+  if (cpl > 4 || elr_batch_lds_bytes(p, cpl) > EXTEND_LDS_LIMIT) cpl = 0;
+  const uint64_t xb_n = x_off[n], yb_n = y_off[n], pool = ops_off[n];
+  HIPCHK(a, a->b0.ensure(xb_n + 16));
+  HIPCHK(a, a->b1.ensure((n + 1) * 8));
+  HIPCHK(a, a->b2.ensure(yb_n + 16));
+  HIPCHK(a, a->b3.ensure((n + 1) * 8));
+  HIPCHK(a, a->b4.ensure(n * 4));
+  HIPCHK(a, a->b5.ensure(n * 4));
+  HIPCHK(a, a->b6.ensure((n + 1) * 8));
+  HIPCHK(a, a->b7.ensure(pool + 16));
+  HIPCHK(a, a->b8.ensure(n * sizeof(thm_lr_aln)));
+  HIPCHK(a, a->sh_hits.ensure(n * sizeof(thm_mem)));
+  hipStream_t s = a->stream;
+  if (xb_n) HIPCHK(a, hipMemcpyAsync(a->b0.p, x_bases, xb_n, hipMemcpyHostToDevice, s));
+  HIPCHK(a, hipMemcpyAsync(a->b1.p, x_off, (n + 1) * 8, hipMemcpyHostToDevice, s));
+  if (yb_n) HIPCHK(a, hipMemcpyAsync(a->b2.p, y_bases, yb_n, hipMemcpyHostToDevice, s));
+  HIPCHK(a, hipMemcpyAsync(a->b3.p, y_off, (n + 1) * 8, hipMemcpyHostToDevice, s));
+  HIPCHK(a, hipMemcpyAsync(a->b4.p, band_width, n * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(a, hipMemcpyAsync(a->b5.p, x_drop, n * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(a, hipMemcpyAsync(a->b6.p, ops_off.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
+  HIPCHK(a, hipMemcpyAsync(a->sh_hits.p, hits, n * sizeof(thm_mem), hipMemcpyHostToDevice, s));
+  int rc = reset_queue(a);
+  if (rc != THM_OK) return rc;
+  p.xb = a->b0.as<uint8_t>();
+  p.xo = a->b1.as<uint64_t>();
+  p.yb = a->b2.as<uint8_t>();
+  p.yo = a->b3.as<uint64_t>();
+  p.hits = a->sh_hits.as<thm_mem>();
+  p.bw = a->b4.as<uint32_t>();
+  p.xd = a->b5.as<int32_t>();
+  p.ops_off = a->b6.as<uint64_t>();
+  p.ops = a->b7.as<uint8_t>();
+  p.out = a->b8.as<thm_lr_aln>();
+  p.counters = a->d_counters.as<unsigned long long>();
+  p.queue = a->d_queue.as<unsigned int>();
+  p.fault = a->d_fault.as<int>();
+  p.n = n;
+  int n_blocks = grid_blocks(a, n, 4, 4);
+  if (cpl == 0) {
+    p.scratch_per_wave = (elr_batch_scratch_bytes(p) + 255) & ~255ull;
+    const uint64_t budget = 16ull << 30;
+    if (p.scratch_per_wave > budget) return fail(a, THM_ERR_UNSUPPORTED, "DP trace of %llu bytes per problem exceeds the device-memory budget",
+                                                 (unsigned long long)p.scratch_per_wave);
+    n_blocks = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)n_blocks, budget / p.scratch_per_wave / 4));
+    HIPCHK(a, a->e_slow.ensure((size_t)n_blocks * 4 * p.scratch_per_wave + 256));
+    p.scratch = a->e_slow.as<uint8_t>();
+  }
+  HIPCHK(a, launch_elr_batch(p, cpl, n_blocks, s));
+  std::vector<thm_lr_aln> raw(n);
+  std::vector<uint8_t> pool_h(pool);
+  int fault = 0;
+  HIPCHK(a, hipMemcpyAsync(raw.data(), a->b8.p, n * sizeof(thm_lr_aln), hipMemcpyDeviceToHost, s));
+  if (pool) HIPCHK(a, hipMemcpyAsync(pool_h.data(), a->b7.p, pool, hipMemcpyDeviceToHost, s));
+  HIPCHK(a, hipMemcpyAsync(&fault, a->d_fault.p, 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(a, hipStreamSynchronize(s));
+  if (fault) return fail(a, THM_ERR_INTERNAL, "inconsistent trace in elr_batch_kernel");
+  // canonical layout: op streams back to back in problem order
+  a->h_lr.resize(n);
+  a->h_ops.clear();
+  for (uint64_t i = 0; i < n; i++) {
+    thm_lr_aln r = raw[i];
+    const uint64_t off = a->h_ops.size();
+    a->h_ops.insert(a->h_ops.end(), pool_h.begin() + r.ops_off, pool_h.begin() + r.ops_off + r.ops_len);
+    r.ops_off = off;
+    a->h_lr[i] = r;
+  }
+  out->n = n;
+  out->n_op_bytes = a->h_ops.size();
+  out->alns = a->h_lr.data();
   out->ops = a->h_ops.data();
   return THM_OK;
 }

@@ -146,6 +146,12 @@ struct thm_aligner {
   std::vector<uint8_t> h_ops;
   std::vector<thm_mem> h_mems;
   std::vector<thm_swg_aln> h_swg;
+  std::vector<thm_lr_aln> h_lr;
+  // per-hit entry point (seed_hits.hip): device buffers and the host result its view points into
+  DBuf sh_bases, sh_san, sh_off, sh_hits, sh_read, sh_bw, sh_xd, sh_list, sh_out, sh_status, sh_ops, sh_ctl, sh_trace, sh_slow;
+  std::vector<thm_aln> h_hit_alns;
+  std::vector<int32_t> h_hit_status;
+  std::vector<uint8_t> h_hit_ops;
 };
 
 inline int fail(thm_aligner* a, int code, const char* fmt, ...) {

@@ -2002,7 +2002,355 @@ __global__ __launch_bounds__(256) void compact_heavy_copy_kernel(CompactParams p
   }
 }
 
+// ---- align_seed_hit for caller-chosen hits (thm_align_seed_hits_batch) ----
+// The wave context of this kernel is a type of its own, so that the helpers it shares with extend_kernel are
+// instantiated separately and extend_kernel's code does not change with it.
+template <bool GS_>
+struct HitCtxT : WctxT<GS_> {};
+
+// One hit per wavefront: align_seed_hit (src/aligner.rs:198-314) statement by statement, from the helpers extend_kernel
+// uses -- without align_read's loop around it (no band narrowing, no score filter, no intron_mode check, no
+// filter_overlapping) and without extend_kernel's reuse of the genome extensions for a transcript (an exact shortcut:
+// here every transcript target runs its two SwgExtend::extend calls).  CPL and the buffers as in extend_kernel.
+template <class C, int CPL>
+__global__ __launch_bounds__(256, 4) void seed_hit_kernel(SeedHitParamsT<C> p) {
+  typedef typename CoordTraits<C>::S S;
+  constexpr bool GS = (CPL == 0);
+  typedef HitCtxT<GS> Wctx;
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  const int lane = lane_id();
+  const int wave = bcast_first((int)(threadIdx.x >> 6));
+  const unsigned wave_global = blockIdx.x * (blockDim.x >> 6) + (unsigned)wave;
+  const ExtCaps caps = ext_caps(p.max_read_len, p.max_bw, CPL);
+  const uint32_t lcap = caps.lcap, wcap = caps.wcap, opcap = caps.opcap;
+  Wctx c;
+  if constexpr (GS) {
+    const SlowLayout sl = slow_layout(p.max_read_len, p.max_bw, p.mk_cap);
+    uint8_t* base = p.slow_scratch + (size_t)wave_global * p.slow_scratch_per_wave;
+    c.rd = base + sl.rd;
+    c.win = base + sl.win;
+    c.wing = base + sl.wing;
+    c.trace = nullptr;
+    c.trace_g = (unsigned long long*)(base + sl.trace);
+    c.pa = base + sl.pa;
+    c.pb = base + sl.pb;
+    c.pc = base + sl.pc;
+    c.mk_k = (int*)(base + sl.mk_k);
+    c.ycl = (uint32_t*)(base + sl.ycl);
+    c.dp = (int*)(base + sl.dp);
+    c.dp_stride = (int)sl.dp_stride;
+    c.mk_cap = (int)p.mk_cap;
+    c.ck = nullptr;
+  } else {
+    // the carve of extend_kernel (extend_lds_bytes sizes both); the candidate keys are not used here
+    const uint32_t per_wave = lcap + 2u * wcap + caps.trb + 3u * opcap + 8u * FAST_MAX_YCLIPS + (uint32_t)(KEYCAP * sizeof(CandKey));
+    uint8_t* base = smem + (size_t)wave * per_wave;
+    c.rd = base;
+    c.win = c.rd + lcap;
+    c.wing = c.win + wcap;
+    c.trace = (unsigned long long*)(c.wing + wcap);
+    c.trace_g = p.trace_scratch + (size_t)wave_global * ((size_t)(caps.ycols + 1u) * (CPL > 0 ? CPL : 1) * 2u);
+    c.pa = (uint8_t*)c.trace + caps.trb;
+    c.pb = c.pa + opcap;
+    c.pc = c.pb + opcap;
+    c.mk_k = (int*)(c.pc + opcap);
+    c.ycl = (uint32_t*)(c.mk_k + FAST_MAX_YCLIPS);
+    c.ck = nullptr;
+    c.dp = nullptr;
+    c.dp_stride = 0;
+    c.mk_cap = FAST_MAX_YCLIPS;
+  }
+  c.opcap = (int)opcap;
+  c.wcap = (int)wcap;
+  c.cells = c.cols = c.calls = c.winbytes = 0;
+  c.fault = 0;
+  c.pool_off = 0;
+  c.pool_left = 0;
+  const auto& ix = p.ix;
+  const uint64_t n_list = p.n_list_dev ? (uint64_t)uload(p.n_list_dev) : p.n_list;
+  unsigned long long k_hits = 0, k_cells = 0, k_cols = 0, k_calls = 0, k_win = 0, k_opb = 0;
+  int batch_fault = 0;
+
+  for (;;) {
+    unsigned g = 0;
+    if (lane == 0) g = atomicAdd(p.queue, 1u);
+    g = (unsigned)bcast_first((int)g);
+    if (g >= n_list) break;
+    const uint32_t hidx = uload(&p.list[g]);
+    const thm_mem hit = uload(&p.hits[hidx]);
+    const uint32_t rd_idx = uload(&p.hit_read[hidx]);
+    const uint64_t r0 = uload(&p.reads.offsets[rd_idx]);
+    const int L = (int)(uload(&p.reads.offsets[rd_idx + 1]) - r0);
+    c.L = L;
+    #pragma unroll 1
+    for (int t = lane; t < (int)lcap; t += 64) c.rd[t] = (t < L) ? p.reads.bases[r0 + t] : (uint8_t)0;
+    wsync(c);
+    const int bw = (int)uload(&p.bw[hidx]), xd = uload(&p.xd[hidx]);
+    const S hr = (S)hit.ref_idx;
+    const int q = (int)hit.query_idx, len = (int)hit.len;
+    const RefInfoT<C> ref = idx_to_ref<C>(ix, (C)hr);
+    const C qs = (C)hr, qe = (C)(hr + len);
+
+    // ---- genome window (:209-227): staged as extend_kernel stages it (unclamped, the text is padded) ----
+    const S rs = (S)ref.start;
+    const S seq_start = max((hr > L + bw) ? hr - (S)(L + bw) : (S)0, rs);
+    const S seq_end = min(hr + (S)(len + L + bw), (S)ref.end - 1);
+    const S gw_a = max(hr - (S)(L + bw), (S)0);
+    const S gw_b = min(hr + (S)(len + L + bw), (S)ix.n);
+    const unsigned gw_mis = (unsigned)((uintptr_t)(ix.text + gw_a) & 15u);
+    const int gw_n = (int)(gw_b - gw_a) + (int)gw_mis;
+    if (gw_n > c.wcap) {
+      c.fault |= FAULT_INTERNAL;
+    } else {
+      const uint4* gw_src = (const uint4*)(ix.text + gw_a - gw_mis);
+      uint4* wdst = (uint4*)c.wing;
+      #pragma unroll 1
+      for (int t2 = lane; t2 * 16 < gw_n; t2 += 64) wdst[t2] = gw_src[t2];
+    }
+    c.winbytes += (unsigned)(seq_end - seq_start);
+    wsync(c);
+    LrMemo gmemo, tmemo;
+    const PathT<S> gx = extend_lr<CPL, S>(c, c.wing, gw_a - (S)gw_mis, seq_start, seq_end, hr, q, len, bw, xd, c.pa, gmemo);
+
+    // ---- every transcript exon_to_tx.find yields (:229-258) ----
+    PathT<S> best = gx;
+    bool have_best = false;
+    uint32_t best_tx = 0, best_tlen = 0;
+    uint8_t* cur_buf = c.pb;
+    uint8_t* best_buf = c.pc;
+    GridQueryT<C, ExonEntryT<C>> eg;
+    grid_begin<C>(eg, ix.exon_grid_off, ix.exon_grid, qs, qe);
+    for (;;) {
+      uint32_t tx_idx = 0, ent_idx = 0;
+      if (!grid_next(eg, tx_idx, ent_idx)) break;
+      const ExonEntryT<C> ge = uload(&eg.ent[ent_idx]);
+      S xs, xe;
+      int exon_sum;
+      if (ge.prev_end <= qs) {
+        // lift_mem_to_tx (src/txome.rs:82-103): this exon is the first of its transcript that intersects the seed
+        xs = (S)ge.start;
+        xe = (S)ge.end;
+        exon_sum = (int)ge.txoff;
+      } else {
+        // first exon in transcript order that intersects, by looking at them all
+        const thm_tx tx = uload(&ix.txs[tx_idx]);
+        int fe = -1;
+        for (uint32_t e0 = 0; e0 < tx.n_exons && fe < 0; e0 += 64) {
+          const uint32_t e = e0 + (uint32_t)lane;
+          bool hit_e = false;
+          if (e < tx.n_exons) {
+            const thm_exon x = ix.exons[tx.exon_begin + e];
+            const C x0 = (C)x.start, x1 = (C)x.end;
+            hit_e = (qs >= x0 && qs < x1) || (x0 >= qs && x0 < qe);
+          }
+          const unsigned long long m = __ballot(hit_e);
+          if (m) fe = (int)e0 + __builtin_ctzll(m);
+        }
+        if (fe < 0) {  // unreachable!() in the reference
+          c.fault |= FAULT_CONTRACT;
+          continue;
+        }
+        const thm_exon x = uload(&ix.exons[tx.exon_begin + fe]);
+        exon_sum = (int)uload(&ix.exon_txoff[tx.exon_begin + fe]);
+        xs = (S)x.start;
+        xe = (S)x.end;
+      }
+      int tr_ = (int)((hr > xs) ? hr - xs : (S)0) + exon_sum;
+      const int start_offset = (int)((xs > hr) ? xs - hr : (S)0);
+      const int t_end = (int)(min(hr + (S)len, xe) - xs) + exon_sum;
+      int t_q = q + start_offset;
+      int t_len = t_end - tr_;
+      const int tlen = (int)ge.seq_len;
+      const int ws = (tr_ > L + bw) ? tr_ - (L + bw) : 0;
+      const int we = min(tlen, tr_ + t_len + L + bw + 1);
+      const int w0 = stage_window(c, c.win, ix.tx_seq + ge.seq_off, ws, we);
+      // extend_seed_match (src/aligner.rs:410-426): ballots of the first mismatch
+      {
+        int ext = 0;
+        for (bool done = false; !done;) {
+          const int tt = ext + lane;
+          const int rp = tr_ + t_len + tt;
+          const int qp = t_q + t_len + tt;
+          const bool ok = (rp < tlen) && (qp < L) && (c.win[rp - w0] == c.rd[qp]);
+          const unsigned long long bad = __ballot(!ok);
+          if (bad) {
+            ext += __builtin_ctzll(bad);
+            done = true;
+          } else {
+            ext += 64;
+          }
+        }
+        t_len += ext;
+        ext = 0;
+        for (bool done = false; !done;) {
+          const int tt = ext + lane + 1;
+          const int rp = tr_ - tt;
+          const int qp = t_q - tt;
+          const bool ok = (rp >= 0) && (qp >= 0) && (c.win[rp - w0] == c.rd[qp]);
+          const unsigned long long bad = __ballot(!ok);
+          if (bad) {
+            ext += __builtin_ctzll(bad);
+            done = true;
+          } else {
+            ext += 64;
+          }
+        }
+        tr_ -= ext;
+        t_q -= ext;
+        t_len += ext;
+      }
+      const PathT<S> pth = extend_lr<CPL, S>(c, c.win, (S)w0, (S)0, (S)tlen, (S)tr_, t_q, t_len, bw, xd, cur_buf, tmemo);
+      if (!have_best || pth.score > best.score) {  // strictly better (:249)
+        have_best = true;
+        best_tx = tx_idx;
+        best_tlen = ge.seq_len;
+        best = pth;
+        uint8_t* tmp = cur_buf;
+        cur_buf = best_buf;
+        best_buf = tmp;
+      }
+      if (pth.score >= L * MATCH_SCORE) break;  // cannot beat an exact match (:253-257)
+    }
+
+    // ---- exonic vs unspliced (:263-313) ----
+    const bool exonic = have_best && best.score >= gx.score;
+    int aln_type = THM_ALN_INTERGENIC;
+    uint32_t type_idx = THM_NO_IDX;
+    S cy0 = gx.ystart, cy1 = gx.yend;
+    const uint8_t* g_path = c.pa;
+    int g_n = gx.nops, g_ny = 0;
+    int sc = gx.score, xs_ = gx.xstart, xe_ = gx.xend;
+    if (exonic) {
+      // lift_tx_to_gx (src/txome.rs:110-160)
+      g_path = best_buf;
+      g_n = best.nops;
+      aln_type = THM_ALN_EXONIC;
+      type_idx = best_tx;
+      sc = best.score;
+      xs_ = best.xstart;
+      xe_ = best.xend;
+      g_ny = lift_markers<S>(c, ix, uload(&ix.txs[best_tx]), best_buf, best.nops, best.xend < L, (int)best.ystart, (int)best.yend,
+                             cy0, cy1);
+    } else {
+      // first interval gene_intervals.find yields (:283-288, :306)
+      GridQueryT<C, GridEntryT<C>> gg;
+      grid_begin<C>(gg, ix.gene_grid_off, ix.gene_grid, (C)cy0, (C)cy1);
+      uint32_t gene = 0, gene_ent = 0;
+      if (grid_next(gg, gene, gene_ent)) {
+        aln_type = THM_ALN_INTRONIC;
+        type_idx = gene;
+      }
+    }
+    if (c.fault & FAULT_RETRY) {
+      // more introns than this kernel's marker list holds: the any-width launch redoes the hit
+      c.fault &= ~(FAULT_RETRY | FAULT_CONTRACT);
+      if (lane == 0) {
+        const unsigned long long slot = atomicAdd(p.retry_count, 1ull);
+        p.retry[slot] = hidx;
+      }
+      c.cells = c.cols = c.calls = c.winbytes = 0;
+      continue;
+    }
+    if (c.fault & FAULT_CONTRACT) {
+      // a lift that panics in the reference: per-hit status, no record
+      c.fault &= ~FAULT_CONTRACT;
+      if (lane == 0) p.status[hidx] = THM_ERR_OUT_OF_CONTRACT;
+    } else {
+      // concat_to_chr_aln (:429-449)
+      const RefInfoT<C> cref = ((C)cy0 >= ref.start && (C)cy0 < ref.end) ? ref : idx_to_ref<C>(ix, (C)cy0);
+      uint64_t ch0, ch1;
+      bool rev;
+      if (cref.strand) {
+        ch0 = (uint64_t)((C)cy0 - cref.start);
+        ch1 = (uint64_t)((C)cy1 - cref.start);
+        rev = false;
+      } else {
+        ch0 = (uint64_t)(C)(cref.len - ((C)cy1 - cref.start));
+        ch1 = (uint64_t)(C)(cref.len - ((C)cy0 - cref.start));
+        rev = true;
+      }
+      int nb = 0, tnb = 0;
+      const unsigned long long off = emit_alignment(c, p, g_path, g_n, xs_, xe_, rev, g_ny, nb);
+      unsigned long long toff2 = 0;
+      if (exonic) toff2 = emit_alignment(c, p, best_buf, best.nops, best.xstart, best.xend, false, 0, tnb);
+      if (lane == 0) {
+        thm_aln a;
+        a.ystart = ch0;
+        a.yend = ch1;
+        a.ylen = (uint64_t)cref.len;
+        a.ops_off = off;
+        a.tx_ystart = exonic ? (uint64_t)best.ystart : 0;
+        a.tx_yend = exonic ? (uint64_t)best.yend : 0;
+        a.tx_ylen = exonic ? (uint64_t)best_tlen : 0;
+        a.tx_ops_off = exonic ? toff2 : 0;
+        a.score = sc;
+        a.ref_id = ref.id;
+        a.xstart = (uint32_t)xs_;
+        a.xend = (uint32_t)xe_;
+        a.xlen = (uint32_t)L;
+        a.ops_len = (uint32_t)nb;
+        a.tx_or_gene_idx = type_idx;
+        a.tx_score = exonic ? best.score : 0;
+        a.tx_xstart = exonic ? (uint32_t)best.xstart : 0;
+        a.tx_xend = exonic ? (uint32_t)best.xend : 0;
+        a.tx_ops_len = (uint32_t)tnb;
+        a.strand = ref.strand ? 1 : 0;
+        a.primary = 0;
+        a.aln_type = (uint8_t)aln_type;
+        a.pad_ = 0;
+        p.out[hidx] = a;
+        p.status[hidx] = THM_OK;
+      }
+      k_opb += (unsigned long long)(nb + tnb);
+    }
+    batch_fault |= c.fault;
+    c.fault = 0;
+    k_hits++;
+    k_cells += c.cells;
+    k_cols += c.cols;
+    k_calls += c.calls;
+    k_win += c.winbytes;
+    c.cells = c.cols = c.calls = c.winbytes = 0;
+    wsync(c);
+  }
+  batch_fault |= c.fault;
+  if (lane == 0) {
+    if (batch_fault & (FAULT_OPS_POOL | FAULT_INTERNAL)) atomicOr(p.fault, batch_fault & (FAULT_OPS_POOL | FAULT_INTERNAL));
+    if (k_hits) {
+      atomicAdd(&p.counters[THM_CNT_HITS], k_hits);
+      atomicAdd(&p.counters[THM_CNT_SWG_CALLS], k_calls);
+      atomicAdd(&p.counters[THM_CNT_DP_CELLS], k_cells);
+      atomicAdd(&p.counters[THM_CNT_DP_COLS], k_cols);
+      atomicAdd(&p.counters[THM_CNT_OP_BYTES], k_opb);
+      atomicAdd(&p.counters[THM_CNT_WINDOW_BYTES], k_win);
+    }
+  }
+}
+
 }  // namespace dev
+
+template <class C>
+static hipError_t launch_seed_hits_t(const SeedHitParamsT<C>& p, int cpl, int n_blocks, hipStream_t s) {
+  const size_t lds = cpl == 0 ? 0 : extend_lds_bytes(p.max_read_len, p.max_bw, cpl);
+  auto go = [&](auto kern) -> hipError_t {
+    if (lds > 48 * 1024) {
+      hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(256), lds, s, p);
+    return hipGetLastError();
+  };
+  switch (cpl) {
+    case 0: return go(dev::seed_hit_kernel<C, 0>);
+    case 1: return go(dev::seed_hit_kernel<C, 1>);
+    case 2: return go(dev::seed_hit_kernel<C, 2>);
+    case 3: return go(dev::seed_hit_kernel<C, 3>);
+    case 4: return go(dev::seed_hit_kernel<C, 4>);
+    default: return hipErrorInvalidValue;
+  }
+}
+hipError_t launch_seed_hits(const SeedHitParamsT<uint32_t>& p, int cpl, int n_blocks, hipStream_t s) { return launch_seed_hits_t(p, cpl, n_blocks, s); }
+hipError_t launch_seed_hits(const SeedHitParamsT<uint64_t>& p, int cpl, int n_blocks, hipStream_t s) { return launch_seed_hits_t(p, cpl, n_blocks, s); }
 
 size_t extend_lds_bytes(uint32_t max_read_len, uint32_t max_bw, int cpl) {
   const dev::ExtCaps k = dev::ext_caps(max_read_len, max_bw, cpl);

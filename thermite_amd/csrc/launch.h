@@ -37,6 +37,32 @@ size_t swg_batch_scratch_bytes(const SwgBatchParams& p);  // per wave, cpl == 0
 hipError_t launch_swg_batch(const SwgBatchParams& p, int cpl, int n_blocks, hipStream_t s);
 hipError_t launch_wave_prims(const int* in, int* out, hipStream_t s);
 
+// extend_left_right (reference src/aligner.rs:352-407) for a batch of independent problems (thm_extend_left_right_batch):
+// x = a read, y = a reference sequence, the hit relative to it; two SwgExtend::extend calls per problem
+struct ElrBatchParams {
+  const uint8_t* xb;
+  const uint64_t* xo;
+  const uint8_t* yb;
+  const uint64_t* yo;
+  const thm_mem* hits;
+  const uint32_t* bw;
+  const int32_t* xd;
+  const uint64_t* ops_off;  // per problem: start of its slot in the op pool
+  uint8_t* ops;
+  thm_lr_aln* out;
+  unsigned long long* counters;
+  unsigned int* queue;
+  int* fault;
+  uint64_t n;
+  uint32_t x_cap, y_cap;  // per-wave bytes for one side's x and y (multiples of 16)
+  uint8_t* scratch;       // cpl == 0: per-wave scratch in global memory
+  uint64_t scratch_per_wave;
+  uint32_t max_bw;
+};
+size_t elr_batch_lds_bytes(const ElrBatchParams& p, int cpl);
+size_t elr_batch_scratch_bytes(const ElrBatchParams& p);  // per wave, cpl == 0
+hipError_t launch_elr_batch(const ElrBatchParams& p, int cpl, int n_blocks, hipStream_t s);
+
 // ---- read-level pipeline ----
 struct ReadBatch {
   const uint8_t* bases;     // upper-cased, sanitised reads (bytes outside ACGTN -> 0), 128 B zero padding, device
@@ -466,6 +492,38 @@ struct CompactParams {
 hipError_t launch_compact(const CompactParams& p, hipStream_t s);
 // counters[k] += sum over rows of wave_counters[row][k]
 hipError_t launch_counters_reduce(const unsigned long long* wave_counters, uint32_t n_rows, unsigned long long* counters, hipStream_t s);
+
+// align_seed_hit (reference src/aligner.rs:198-314) for caller-chosen hits (thm_align_seed_hits_batch): one hit per
+// wavefront, no align_read policy around it.  One launch per band class, like the wave-per-read kernels: register-
+// resident cpl 1..4 (LDS carve of extend_lds_bytes) or the any-width kernel (slow_layout in global memory).
+template <class C>
+struct SeedHitParamsT {
+  DeviceIndexT<C> ix;
+  ReadBatch reads;             // sanitised, as for the read-level pipeline
+  const thm_mem* hits;         // [n_hits] concatenated-text coordinates
+  const uint32_t* hit_read;    // [n_hits] read of each hit
+  const uint32_t* bw;          // [n_hits]
+  const int32_t* xd;           // [n_hits]
+  const uint32_t* list;        // hits of this launch
+  uint64_t n_list;
+  const unsigned long long* n_list_dev;  // non-null: the list length is read here (any-width launch: its own hits + retries)
+  uint32_t* retry;             // register-resident launches: hits whose alignment crosses more introns than their marker
+  unsigned long long* retry_count;  // list holds, appended here (the any-width launch's list)
+  thm_aln* out;                // [n_hits], ops_off / tx_ops_off into cand_ops
+  int32_t* status;             // [n_hits]
+  uint8_t* cand_ops;
+  uint64_t cand_ops_cap;
+  unsigned long long* ops_cursor;
+  unsigned long long* counters;
+  unsigned int* queue;
+  int* fault;                  // FAULT_OPS_POOL: the host grows the op pool and replays; FAULT_INTERNAL
+  uint32_t max_read_len, max_bw, mk_cap;
+  unsigned long long* trace_scratch;  // cpl >= 2: [waves of the grid * extend_trace_scratch_bytes / 8]
+  uint8_t* slow_scratch;              // cpl == 0: [waves of the grid * slow_scratch_per_wave]
+  uint64_t slow_scratch_per_wave;
+};
+hipError_t launch_seed_hits(const SeedHitParamsT<uint32_t>& p, int cpl, int n_blocks, hipStream_t s);
+hipError_t launch_seed_hits(const SeedHitParamsT<uint64_t>& p, int cpl, int n_blocks, hipStream_t s);
 
 hipError_t launch_calib_gather(const uint8_t* table, uint64_t span, uint64_t n_threads, int pattern, unsigned long long* sink,
                                hipStream_t s);
