@@ -7,22 +7,12 @@ import pytest
 from oracle import pyoracle as orc
 from thermite_amd import capi, refdata, synth
 
-from gpu_common import assert_batch_equal
+from gpu_common import (COMPACT_HEAVY_N, TEAM_HITS, TEAM_MAX_HITS, World, assert_batch_equal, beyond_team_reads, beyond_team_reference,
+                        check_align, check_smems, ordinary_reads)
 
 pytestmark = pytest.mark.gpu
 
 TEST_OPTS = dict(min_seed_len=3, min_aln_score_percent=0.66, min_aln_score=0, multimap_score_range=1, intron_mode=False)
-
-
-class World:
-    def __init__(self, tables, wide=False):
-        self.t = tables
-        self.ix = capi.Index(tables, wide=wide)
-        assert self.ix.coord_bytes == (8 if wide else 4)
-        self.oix = orc.Index(tables, sa=self.ix.suffix_array())
-
-    def aligner(self, opts):
-        return capi.Aligner(self.ix, opts)
 
 
 # Every test of this file runs twice: on an index with 32-bit text positions and ranks (c32, the default for texts
@@ -53,38 +43,6 @@ def chrm(request, data_dir):
 @pytest.fixture(params=[False, True], ids=["c32", "c64"])
 def syn(request):
     return _world("syn", lambda: synth.synth_reference(length=400000, n_genes=40), request.param)
-
-
-def check_smems(w, bases, off, k):
-    a = w.aligner(dict(capi.DEFAULT_OPTS, min_seed_len=k))
-    g_off, g_mems = a.smems_batch(bases, off, k)
-    r = w.oix.all_smems(bases, off, k)
-    assert np.array_equal(g_off, r.offsets)
-    for f in ("ref_idx", "query_idx", "len"):
-        bad = np.nonzero(g_mems[f] != r.mems[f])[0]
-        assert len(bad) == 0, "%s differs at mem %d" % (f, bad[0])
-    a.close()
-
-
-def check_align(w, bases, off, opts, n_threads=8):
-    """Both device paths against the oracle: the problem-parallel path (kernels_tpr.hip: thread-per-read control
-    kernel + wave-per-request DP kernel; what it leaves goes to the wave-per-read kernels) and the wave-per-read
-    kernels alone."""
-    r = w.oix.align_batch(bases, off, opts, n_threads=n_threads)
-    assert r.counters[15] == 0, "oracle saw reads where the reference would panic"
-    g = None
-    for no_tpr in (False, True):
-        a = w.aligner(opts)
-        a.debug_set_flags(tpr=not no_tpr)
-        a.reset_counters()
-        g = a.align_batch(bases, off)
-        assert g.n_failed == 0 and g.status is None
-        assert_batch_equal(g, r)
-        c = a.counters()
-        assert np.array_equal(c[:10], r.counters[:10]) and c[12] == r.counters[12] and c[13] == r.counters[13], (no_tpr, c[:14], r.counters[:14])
-        assert c[10] <= r.counters[10] and c[11] <= r.counters[11], (no_tpr, c[:14], r.counters[:14])  # DP work: exact early exit computes fewer cells
-        a.close()
-    return g
 
 
 def test_config1_plumbing(test_ref, data_dir):
@@ -398,6 +356,9 @@ def heavy(request):
 
 
 def test_heavy_reads_thousands_of_hits(heavy):
+    """Reads from copies of an 8000-copy family among ordinary reads.  With the CI options the oracle's result exceeds
+    COMPACT_HEAVY_N = 8 final alignments per read by far (several hundred reads have more, the largest has thousands, and
+    reads with exactly 8 and 9 are present), so compact_kernel's layout path for many alignments is entered here."""
     rng = np.random.default_rng(3)
     pos = heavy.t["_copy_pos"]
     starts = pos[rng.integers(0, len(pos), 90)] + rng.integers(0, 300 - 91, 90)
@@ -412,9 +373,58 @@ def test_heavy_reads_thousands_of_hits(heavy):
     hits = np.diff(mo.astype(np.int64))
     assert hits.max() >= 2000 and (hits >= 256).sum() >= 3  # the team path is taken
     a.close()
-    check_align(heavy, b2, o2, capi.CI_OPTS)
+    r = heavy.oix.align_batch(b2, o2, capi.CI_OPTS, n_threads=8)
+    n_alns = np.diff(r.offsets.astype(np.int64))
+    assert n_alns.max() >= 1000 and (n_alns > COMPACT_HEAVY_N).sum() >= 100
+    assert (n_alns == COMPACT_HEAVY_N).any() and (n_alns == COMPACT_HEAVY_N + 1).any()
+    check_align(heavy, b2, o2, capi.CI_OPTS, ref=r)
     check_align(heavy, b2, o2, capi.DEFAULT_OPTS)
     check_align(heavy, b2, o2, dict(capi.CI_OPTS, multimap_score_range=6, min_seed_len=16))
+
+
+# ---------------------------------------------------------------------------------------------
+# more hits than the team kernel takes: plan_kernel (kernels_seed.hip) sends a read with more than TEAM_MAX_HITS = 60000
+# seed hits to the wave-per-read kernel's heavy list, where one wave walks all of them; the read's slice of the
+# candidate pool (cand_cap = 3 n + 1024 at first) forces the pool to grow
+@pytest.fixture(params=[False, True], ids=["c32", "c64"])
+def beyond(request):
+    def make():
+        t, info = beyond_team_reference()
+        t["_info"] = info
+        return t
+    return _world("beyond", make, request.param)
+
+
+def test_reads_beyond_the_team_capacity(beyond):
+    """Reads with exactly 60000 seed hits (the last the team kernel takes), 60001 and 60201 (the sequential walk of
+    the wave-per-read kernel), 1000 (team) and a few, in one batch; reads with exactly 8 final alignments (the last of
+    compact_kernel's common layout path), 9 (the first of its path for many alignments) and hundreds."""
+    rng = np.random.default_rng(2)
+    reads, kinds = beyond_team_reads(beyond.t["_info"], rng)
+    nk = len(kinds)
+    ob, oo = ordinary_reads(beyond.t, 1500, stream=2)
+    reads += [ob[oo[i]: oo[i + 1]] for i in range(1500)]
+    order = rng.permutation(len(reads))
+    where = np.argsort(order)[:nk]  # batch positions of the planted reads
+    b2, o2 = refdata.pack_reads([reads[i] for i in order])
+    a = beyond.aligner(capi.CI_OPTS)
+    mo, _ = a.smems_batch(b2, o2, 20)
+    a.close()
+    hits = np.diff(mo.astype(np.int64))
+    by_kind = {k: hits[where[[i for i in range(nk) if kinds[i] == k]]] for k in set(kinds)}
+    assert (by_kind["U40"] == TEAM_MAX_HITS).all() and (by_kind["U39"] == TEAM_MAX_HITS + 1).all()
+    assert (by_kind["U30"] > TEAM_MAX_HITS + 1).all()
+    assert ((by_kind["V"] >= TEAM_HITS) & (by_kind["V"] < TEAM_MAX_HITS)).all()
+    assert (hits > TEAM_MAX_HITS).sum() >= 2 and ((hits >= TEAM_HITS) & (hits <= TEAM_MAX_HITS)).sum() >= 2
+    assert hits.max() > 3 * len(hits) + 1024  # one read's candidates alone exceed the initial candidate pool
+    most = []
+    for opts in (capi.CI_OPTS, dict(capi.CI_OPTS, multimap_score_range=6)):
+        r = beyond.oix.align_batch(b2, o2, opts, n_threads=8)
+        n_alns = np.diff(r.offsets.astype(np.int64))
+        assert (n_alns == COMPACT_HEAVY_N).any() and (n_alns == COMPACT_HEAVY_N + 1).any()
+        most.append(int(n_alns.max()))
+        check_align(beyond, b2, o2, opts, ref=r)
+    assert most[1] >= 100, most  # (score range 6: hundreds of the 60000 places tie)
 
 
 @pytest.fixture(params=[False, True], ids=["c32", "c64"])

@@ -11,21 +11,11 @@ import pytest
 from oracle import pyoracle as orc
 from thermite_amd import capi, refdata, synth
 
-from gpu_common import mutate
+from gpu_common import World, assert_hits_equal, expected_batch, expected_hit, initial_band, mutate
 
 pytestmark = pytest.mark.gpu
 
 _ACGT = np.frombuffer(b"ACGT", np.uint8)
-ALN_EXONIC, ALN_INTRONIC, ALN_INTERGENIC = 0, 1, 2  # AlnType, include/thermite.h
-
-
-class World:
-    def __init__(self, tables, wide):
-        self.t = tables
-        self.ix = capi.Index(tables, wide=wide)
-        assert self.ix.coord_bytes == (8 if wide else 4)
-        self.oix = orc.Index(tables, sa=self.ix.suffix_array())
-        self.a = capi.Aligner(self.ix, capi.CI_OPTS)
 
 
 _worlds = {}
@@ -57,117 +47,6 @@ def syn(request):
 def chrm32(data_dir):
     return _world("chrm", lambda: refdata.load_reference(data_dir + "/GRCh38-2020-A-chrM.fasta", data_dir + "/GRCh38-2020-A-chrM.gtf"),
                   False)
-
-
-# ------------------------------------------------------------------ restatement of align_seed_hit
-def _idx_to_ref(refs, idx):  # Index::idx_to_ref, src/index.rs:287-290: refs.partition_point(|x| x.end_idx <= idx)
-    return int(np.searchsorted(refs["end_idx"], idx, side="right"))
-
-
-def _tx_exons(t, tx_idx):
-    tx = t["txs"][tx_idx]
-    ex = t["exons"][int(tx["exon_begin"]): int(tx["exon_begin"]) + int(tx["n_exons"])]
-    return [(int(e["start"]), int(e["end"]), int(tx_idx)) for e in ex]
-
-
-def _tx_seq(t, tx_idx):
-    tx = t["txs"][tx_idx]
-    return t["tx_seq"][int(tx["seq_off"]): int(tx["seq_off"]) + int(tx["seq_len"])]
-
-
-def _concat_to_chr(refs, ystart, yend, ops):  # src/aligner.rs:429-449
-    r = refs[_idx_to_ref(refs, ystart)]
-    s0, ln = int(r["start_idx"]), int(r["len"])
-    if r["strand"]:
-        return ystart - s0, yend - s0, ln, ops
-    return ln - (yend - s0), ln - (ystart - s0), ln, list(reversed(ops))
-
-
-def expected_hit(w, swg, read, hit, bw, xd):
-    """align_seed_hit, src/aligner.rs:198-314: one ALN_DT record (primary 0) and its op bytes (gx, then tx), or raises
-    RuntimeError where the reference panics in a lift."""
-    t, oix = w.t, w.oix
-    refs, text = t["refs"], t["text"]
-    L = len(read)
-    hr, q, ln = hit
-    k = _idx_to_ref(refs, hr)
-    ref = refs[k]
-    seq_start = max(max(hr - (L + bw), 0), int(ref["start_idx"]))
-    seq_end = min(hr + ln + L + bw, int(ref["end_idx"]) - 1)
-    g = swg.extend_left_right(text[seq_start:seq_end], (hr - seq_start, q, ln), read, bw, xd)
-    g["ystart"] += seq_start
-    g["yend"] += seq_start
-    best = None
-    for tx_idx in oix.exon_tree_find(hr, hr + ln):
-        exons = _tx_exons(t, tx_idx)
-        seq = _tx_seq(t, tx_idx)
-        seed = orc.lift_mem_to_tx((hr, q, ln), exons)
-        seed = orc.extend_seed_match(seq, seed, read)
-        a = swg.extend_left_right(seq, seed, read, bw, xd)
-        if best is None or a["score"] > best[1]["score"]:
-            best = (tx_idx, a)
-        if a["score"] >= L:
-            break
-    rec = np.zeros(1, capi.ALN_DT)[0]
-    rec["ref_id"], rec["strand"], rec["primary"], rec["xlen"] = k, ref["strand"], 0, L
-    if best is not None and best[1]["score"] >= g["score"]:
-        tx_idx, a = best
-        lifted = orc.lift_tx_to_gx(a["ops"], a["ystart"], a["yend"], _tx_exons(t, tx_idx))
-        ys, ye, ylen, ops = _concat_to_chr(refs, lifted["ystart"], lifted["yend"], lifted["ops"])
-        gx_bytes, tx_bytes = orc.encode_ops(ops), orc.encode_ops(a["ops"])
-        rec["aln_type"], rec["tx_or_gene_idx"] = ALN_EXONIC, tx_idx
-        rec["score"], rec["xstart"], rec["xend"] = a["score"], a["xstart"], a["xend"]
-        rec["tx_ystart"], rec["tx_yend"], rec["tx_ylen"] = a["ystart"], a["yend"], a["ylen"]
-        rec["tx_score"], rec["tx_xstart"], rec["tx_xend"], rec["tx_ops_len"] = a["score"], a["xstart"], a["xend"], len(tx_bytes)
-    else:
-        genes = oix.gene_tree_find(g["ystart"], g["yend"])
-        ys, ye, ylen, ops = _concat_to_chr(refs, g["ystart"], g["yend"], g["ops"])
-        gx_bytes, tx_bytes = orc.encode_ops(ops), b""
-        rec["aln_type"] = ALN_INTRONIC if genes else ALN_INTERGENIC
-        rec["tx_or_gene_idx"] = genes[0] if genes else 0xFFFFFFFF
-        rec["score"], rec["xstart"], rec["xend"] = g["score"], g["xstart"], g["xend"]
-    rec["ystart"], rec["yend"], rec["ylen"], rec["ops_len"] = ys, ye, ylen, len(gx_bytes)
-    return rec, gx_bytes + tx_bytes
-
-
-def expected_batch(w, bases, off, hit_off, hits, bw, xd, max_bw):
-    """records, op bytes (canonical layout) and statuses the restatement gives for every hit"""
-    swg = orc.Swg(max_bw)
-    recs = np.zeros(len(hits), capi.ALN_DT)
-    ops = bytearray()
-    status = np.zeros(len(hits), "<i4")
-    for r in range(len(off) - 1):
-        read = bytes(bases[off[r]: off[r + 1]]).upper()
-        for h in range(int(hit_off[r]), int(hit_off[r + 1])):
-            m = hits[h]
-            try:
-                rec, b = expected_hit(w, swg, read, (int(m["ref_idx"]), int(m["query_idx"]), int(m["len"])), int(bw[h]), int(xd[h]))
-            except RuntimeError:
-                status[h] = capi.ERR_OUT_OF_CONTRACT
-                continue
-            rec["ops_off"] = len(ops)
-            if rec["aln_type"] == ALN_EXONIC:
-                rec["tx_ops_off"] = len(ops) + rec["ops_len"]
-            ops += b
-            recs[h] = rec
-    return recs, np.frombuffer(bytes(ops), np.uint8), status
-
-
-def assert_hits_equal(got, exp, what=""):
-    g_alns, g_ops, g_st = got
-    e_alns, e_ops, e_st = exp
-    assert np.array_equal(g_st, e_st), (what, np.nonzero(g_st != e_st)[0][:10], g_st[g_st != e_st][:10], e_st[g_st != e_st][:10])
-    for f in capi.ALN_DT.names:
-        bad = np.nonzero(g_alns[f] != e_alns[f])[0]
-        if len(bad):
-            i = int(bad[0])
-            raise AssertionError("%s field %s differs at hit %d: gpu=%s expected=%s" % (what, f, i, g_alns[i], e_alns[i]))
-    assert np.array_equal(g_ops, e_ops), what + ": op streams differ"
-
-
-def initial_band(opts, L):  # align_read's initial band and X-drop, src/aligner.rs:130-138
-    ms = max(int(np.float32(opts["min_aln_score_percent"]) * np.float32(L)), opts["min_aln_score"])
-    return max(L - ms, 0) if ms >= 0 else L
 
 
 def _mutated_reads(rng, t, n, L):
