@@ -167,6 +167,40 @@ typedef struct thm_batch_view {
   const int32_t* read_status;
 } thm_batch_view;
 
+/* One alignment's run-length CIGARs and the counts every output format prints, computed on the device from the
+ * op streams.  Words are BAM-encoded, `len << 4 | code` with M=0 I=1 D=2 N=3 S=4: to_noodles_cigar,
+ * src/aln_writer.rs:279-323 -- Match and Subst both give M (:303-307), Xclip S, Yclip N; consecutive equal ops
+ * form a run, two clips are equal only if their lengths are, and a run of clips carries the clip's own length
+ * (:285-296, :309).  The transcript CIGAR of an exonic alignment (the TX:Z tag, :176-186) lies directly behind
+ * the genome CIGAR.  THM_DIGEST_LONG_RUN: a run of 2^28 or more (only an intron that long) does not fit a word;
+ * that stream has no words, its counts are valid. */
+#define THM_DIGEST_LONG_RUN 1u
+#define THM_DIGEST_MALFORMED 2u /* thm_cigar_encode_batch only: a kind above 5, or a clip cut by the end of the stream */
+typedef struct thm_aln_digest {
+  uint64_t cigar_off;   /* first word of the genome CIGAR in the view's word pool */
+  uint64_t ref_len;     /* reference bases the genome CIGAR consumes (M + D + N)  */
+  uint32_t n_cigar;     /* genome words; 0 for an empty op list (SAM prints "*")  */
+  uint32_t n_tx_cigar;  /* transcript words, directly behind; 0 unless exonic     */
+  uint32_t n_match;     /* PafEntry::num_match, src/aln_writer.rs:55-63           */
+  uint32_t n_subst;     /* nM, :160-168                                           */
+  uint32_t n_not_yclip; /* PafEntry::num_match_gap, :64-72                        */
+  uint32_t flags;       /* gx stream: bits 0-7, tx stream: the same bits << 8     */
+} thm_aln_digest;       /* 40 bytes */
+
+/* Host view of one aligned batch without its op pool: what the writer loop (src/aligner.rs:58-115) needs. */
+typedef struct thm_cigar_view {
+  uint64_t n_reads;
+  uint64_t n_alns;
+  uint64_t n_cigar_words;
+  const uint64_t* read_aln_off;  /* [n_reads+1] */
+  const thm_aln* alns;           /* as in thm_batch_view; the four ops_off/ops_len fields describe the
+                                    device pool, which this view does not carry */
+  const thm_aln_digest* digests; /* [n_alns] */
+  const uint32_t* cigar;         /* [n_cigar_words] */
+  uint64_t n_failed_reads;       /* as in thm_batch_view */
+  const int32_t* read_status;
+} thm_cigar_view;
+
 /* Result of thm_smems_batch: mems of read r in Index::all_smems order. */
 typedef struct thm_mems_view {
   uint64_t n_reads;
@@ -255,7 +289,9 @@ enum {
 
 /* per-stage device time of the last thm_batch_run, from HIP events recorded
  * on the aligner's stream */
-enum { THM_T_SEED = 0, THM_T_PLAN = 1, THM_T_EXTEND = 2, THM_T_COMPACT = 3, THM_T_TOTAL = 4, THM_N_TIMINGS = 8 };
+enum { THM_T_SEED = 0, THM_T_PLAN = 1, THM_T_EXTEND = 2, THM_T_COMPACT = 3, THM_T_TOTAL = 4,
+       THM_T_CIGAR = 5, /* the two CIGAR passes of the last thm_batch_fetch_cigars (not part of THM_T_TOTAL) */
+       THM_N_TIMINGS = 8 };
 
 typedef struct thm_index thm_index;
 typedef struct thm_aligner thm_aligner;
@@ -344,6 +380,25 @@ int32_t thm_batch_upload(thm_aligner*, const uint8_t* bases, const uint64_t* off
 int32_t thm_batch_run(thm_aligner*);
 int32_t thm_batch_sync(thm_aligner*);
 int32_t thm_batch_fetch(thm_aligner*, thm_batch_view* out);
+
+/* The result of thm_batch_run as run-length CIGARs (to_noodles_cigar, src/aln_writer.rs:279-323) and counts
+ * (PafEntry::new :47-72, nM :160-168) instead of op bytes: stands where thm_batch_fetch stands.  Syncs (pool-overflow
+ * replays included), runs two passes over the compacted op pool on the aligner's stream and copies offsets, records,
+ * digests, words and statuses; the op pool stays on the device.  Either fetch may follow the other for the same run,
+ * in any order, with equal records.  Results land in two pinned buffer sets of their own, used alternately: a
+ * thm_cigar_view stays valid until the second-next call on this aligner that returns one, and no thm_batch_view is
+ * invalidated.  Counters and the other timings of the run are untouched; THM_T_CIGAR is set. */
+int32_t thm_batch_fetch_cigars(thm_aligner*, thm_cigar_view* out);
+/* upload + run + the fetch above (aligner::align_read for a batch, src/aligner.rs:123-190) */
+int32_t thm_align_batch_cigars(thm_aligner*, const uint8_t* bases, const uint64_t* offsets, uint64_t n_reads,
+                               thm_cigar_view* out);
+/* to_noodles_cigar (src/aln_writer.rs:279-323) for `n` caller-supplied serialised op streams ops[off[i] .. off[i+1]):
+ * the operator-level surface of the CIGAR kernels.  One digest per stream: out->n_alns = n, n_reads = 0,
+ * read_aln_off = alns = NULL, n_tx_cigar = 0.  A malformed stream gets THM_DIGEST_MALFORMED, no words and zero
+ * counts; the other streams are unaffected.  THM_ERR_INVALID_ARG: null pointers, non-monotone offsets;
+ * THM_ERR_UNSUPPORTED: a stream of 2^32 bytes or more. */
+int32_t thm_cigar_encode_batch(thm_aligner*, const uint8_t* ops, const uint64_t* off, uint64_t n,
+                               thm_cigar_view* out);
 
 /* Index::all_smems (src/index.rs:228-255) for a batch: the seed-level parity
  * surface. */

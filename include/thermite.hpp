@@ -153,6 +153,51 @@ class Aligner {
   }
   std::vector<GenomeAlignment> align_read(const std::string& read) { return align_reads({read})[0]; }
 
+  // The same alignments with what the reference's writer derives from their op lists instead of the lists: the CIGAR
+  // of to_noodles_cigar (src/aln_writer.rs:279-323) as BAM words and as SAM text, the transcript CIGAR of the TX:Z
+  // tag, nM and PafEntry's counts (thm_aln_digest), all computed on the device.
+  struct CigarAlignment {
+    thm_aln rec;
+    thm_aln_digest digest;
+    std::vector<std::uint32_t> cigar, tx_cigar;  // BAM words: len << 4 | code (M I D N S = 0 1 2 3 4)
+    static std::string text(const std::vector<std::uint32_t>& words) {
+      if (words.empty()) return "*";
+      std::string s;
+      for (std::uint32_t w : words) s += std::to_string(w >> 4) + "MIDNSHP=X???????"[w & 15u];
+      return s;
+    }
+  };
+  std::vector<std::vector<CigarAlignment>> align_reads_cigars(const std::vector<std::string>& reads) {
+    std::vector<std::uint8_t> bases;
+    std::vector<std::uint64_t> off{0};
+    for (const auto& r : reads) {
+      bases.insert(bases.end(), r.begin(), r.end());
+      off.push_back(bases.size());
+    }
+    thm_cigar_view v;
+    check(thm_align_batch_cigars(h_.get(), bases.data(), off.data(), reads.size(), &v));
+    std::vector<std::vector<CigarAlignment>> out(reads.size());
+    for (std::uint64_t r = 0; r < v.n_reads; r++)
+      for (std::uint64_t a = v.read_aln_off[r]; a < v.read_aln_off[r + 1]; a++) {
+        CigarAlignment g;
+        g.rec = v.alns[a];
+        g.digest = v.digests[a];
+        const std::uint32_t* w = v.cigar + g.digest.cigar_off;
+        g.cigar.assign(w, w + g.digest.n_cigar);
+        g.tx_cigar.assign(w + g.digest.n_cigar, w + g.digest.n_cigar + g.digest.n_tx_cigar);
+        out[r].push_back(std::move(g));
+      }
+    return out;
+  }
+  // to_noodles_cigar for one serialised op stream (thm_cigar_encode_batch): its digest, words through *words
+  thm_aln_digest cigar_encode(const std::vector<std::uint8_t>& ops, std::vector<std::uint32_t>* words = nullptr) {
+    const std::uint64_t off[2] = {0, ops.size()};
+    thm_cigar_view v;
+    check(thm_cigar_encode_batch(h_.get(), ops.data(), off, 1, &v));
+    if (words) words->assign(v.cigar + v.digests[0].cigar_off, v.cigar + v.digests[0].cigar_off + v.digests[0].n_cigar);
+    return v.digests[0];
+  }
+
   std::vector<thm_mem> all_smems(const std::string& query, std::size_t min_seed_len) {
     const std::uint64_t off[2] = {0, query.size()};
     thm_mems_view v;

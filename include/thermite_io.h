@@ -118,6 +118,12 @@ int32_t thm_writer_trailer(thm_writer* w, thm_text* out);
  * BGZF blocks (records re-encoded in binary, bam::Writer::write_sam_record,
  * src/aligner.rs:69-76,98-108).  Text valid until the next call on `w`. */
 int32_t thm_writer_format_batch(thm_writer* w, const thm_read_batch* reads, const thm_batch_view* result, thm_text* out);
+/* The same records from a thm_cigar_view -- thm_batch_fetch_cigars / thm_align_batch_cigars for exactly these reads:
+ * byte for byte what thm_writer_format_batch gives for the full view of the same batch.  The CIGAR column and the
+ * TX:Z CIGAR (to_noodles_cigar, src/aln_writer.rs:279-323; :176-186) are printed from the words, BAM copies them; nM
+ * (:160-168), PafEntry's num_match / num_match_gap (:55-72) and the BAM bin come from the digest.  An alignment whose
+ * digest carries a flag (a run of 2^28 or more has no word) cannot be rendered: THM_ERR_INTERNAL. */
+int32_t thm_writer_format_batch_cigars(thm_writer* w, const thm_read_batch* reads, const thm_cigar_view* result, thm_text* out);
 
 /* ------------------------------------------------------ whole-file driver */
 

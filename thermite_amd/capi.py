@@ -46,13 +46,18 @@ SWG_DT = np.dtype([("ops_off", "<u8"), ("ops_len", "<u4"), ("score", "<i4"), ("x
 # thm_lr_aln: one extend_left_right result (bio Alignment), include/thermite.h
 LR_DT = np.dtype([("ystart", "<u8"), ("yend", "<u8"), ("ylen", "<u8"), ("ops_off", "<u8"), ("score", "<i4"),
                   ("xstart", "<u4"), ("xend", "<u4"), ("xlen", "<u4"), ("ops_len", "<u4"), ("pad_", "<u4")])
+# thm_aln_digest: run-length CIGAR and counts of one alignment, include/thermite.h
+DIGEST_DT = np.dtype([("cigar_off", "<u8"), ("ref_len", "<u8"), ("n_cigar", "<u4"), ("n_tx_cigar", "<u4"),
+                      ("n_match", "<u4"), ("n_subst", "<u4"), ("n_not_yclip", "<u4"), ("flags", "<u4")])
+DIGEST_LONG_RUN, DIGEST_MALFORMED = 1, 2
 assert ALN_DT.itemsize == 112 and MEM_DT.itemsize == 16 and SWG_DT.itemsize == 24 and LR_DT.itemsize == 56
+assert DIGEST_DT.itemsize == 40
 
 N_COUNTERS = 16
 COUNTER_NAMES = ["reads", "aligned", "unmapped", "alns", "exonic", "intronic", "intergenic", "smems", "hits",
                  "swg_calls", "dp_cells", "dp_cols", "op_bytes", "window_bytes"]
 N_TIMINGS = 8
-TIMING_NAMES = ["seed", "plan", "extend", "compact", "total"]
+TIMING_NAMES = ["seed", "plan", "extend", "compact", "total", "cigar"]
 
 OK, ERR_INVALID_ARG, ERR_NO_DEVICE, ERR_HIP, ERR_UNSUPPORTED, ERR_OUT_OF_CONTRACT, ERR_OOM, ERR_INTERNAL = (
     0, -1, -2, -3, -4, -5, -6, -7)
@@ -107,6 +112,21 @@ class HitsView(C.Structure):
                 ("n_failed_hits", C.c_uint64), ("hit_status", C.c_void_p)]
 
 
+class AlnDigest(C.Structure):
+    """thm_aln_digest"""
+
+    _fields_ = [("cigar_off", C.c_uint64), ("ref_len", C.c_uint64), ("n_cigar", C.c_uint32), ("n_tx_cigar", C.c_uint32),
+                ("n_match", C.c_uint32), ("n_subst", C.c_uint32), ("n_not_yclip", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class CigarView(C.Structure):
+    """thm_cigar_view"""
+
+    _fields_ = [("n_reads", C.c_uint64), ("n_alns", C.c_uint64), ("n_cigar_words", C.c_uint64),
+                ("read_aln_off", C.c_void_p), ("alns", C.c_void_p), ("digests", C.c_void_p), ("cigar", C.c_void_p),
+                ("n_failed_reads", C.c_uint64), ("read_status", C.c_void_p)]
+
+
 # every symbol include/thermite.h declares
 ABI_SYMBOLS = [
     "thm_index_create_in_memory", "thm_index_free", "thm_index_text_len", "thm_index_suffix_array",
@@ -117,6 +137,7 @@ ABI_SYMBOLS = [
     "thm_aligner_index", "thm_comm_unique_id", "thm_comm_create", "thm_comm_free", "thm_counters_allreduce",
     "thm_index_create_in_memory_ex", "thm_index_coord_bytes", "thm_index_suffix_array64", "thm_build_suffix_array64", "thm_build_suffix_array_gpu",
     "thm_extend_left_right_batch", "thm_align_seed_hits_batch",
+    "thm_batch_fetch_cigars", "thm_align_batch_cigars", "thm_cigar_encode_batch",
 ]
 # every symbol include/thermite_io.h declares
 IO_ABI_SYMBOLS = [
@@ -124,6 +145,7 @@ IO_ABI_SYMBOLS = [
     "thm_index_contig_name", "thm_index_tx_id", "thm_index_gene_id", "thm_index_gene_name", "thm_fastq_open",
     "thm_fastq_next_batch", "thm_fastq_close", "thm_writer_create", "thm_writer_free", "thm_writer_header",
     "thm_writer_format_batch", "thm_writer_trailer", "thm_align_files", "thm_align_files_multi",
+    "thm_writer_format_batch_cigars",
 ]
 ERR_IO, ERR_FORMAT = -8, -9
 FMT_PAF, FMT_SAM, FMT_BAM = 0, 1, 2
@@ -182,6 +204,12 @@ def lib():
         getattr(L, f).argtypes = [vp]
     L.thm_batch_fetch.restype = i32
     L.thm_batch_fetch.argtypes = [vp, vp]
+    L.thm_batch_fetch_cigars.restype = i32
+    L.thm_batch_fetch_cigars.argtypes = [vp, vp]
+    L.thm_align_batch_cigars.restype = i32
+    L.thm_align_batch_cigars.argtypes = [vp, vp, vp, u64, vp]
+    L.thm_cigar_encode_batch.restype = i32
+    L.thm_cigar_encode_batch.argtypes = [vp, vp, vp, u64, vp]
     L.thm_smems_batch.restype = i32
     L.thm_smems_batch.argtypes = [vp, vp, vp, u64, u64, vp]
     L.thm_swg_extend_batch.restype = i32
@@ -248,6 +276,8 @@ def lib():
     L.thm_writer_trailer.argtypes = [vp, vp]
     L.thm_writer_format_batch.restype = i32
     L.thm_writer_format_batch.argtypes = [vp, vp, vp, vp]
+    L.thm_writer_format_batch_cigars.restype = i32
+    L.thm_writer_format_batch_cigars.argtypes = [vp, vp, vp, vp]
     L.thm_align_files.restype = i32
     L.thm_align_files.argtypes = [vp, vp, u32, cp, i32, u64, u32, vp]
     L.thm_align_files_multi.restype = i32
@@ -480,6 +510,37 @@ class BatchResult:
         self.status = _copy(view.read_status, view.n_reads, "<i4", copy) if view.read_status else None
 
 
+class CigarResult:
+    """thm_cigar_view copied out, or (copy=False) numpy views of the aligner's pinned result set: records, one digest
+    (DIGEST_DT) per alignment and the pool of BAM-encoded CIGAR words; no op bytes.  For cigar_encode_batch there are
+    no reads and no records: one digest per stream."""
+
+    def __init__(self, view, copy=True):
+        self.n_reads = view.n_reads
+        self.offsets = _copy(view.read_aln_off, view.n_reads + 1, "<u8", copy) if view.read_aln_off else None
+        self.alns = _copy(view.alns, view.n_alns, ALN_DT, copy) if view.alns else None
+        self.digests = _copy(view.digests, view.n_alns, DIGEST_DT, copy)
+        self.cigar = _copy(view.cigar, view.n_cigar_words, "<u4", copy)
+        self.n_failed = view.n_failed_reads
+        self.status = _copy(view.read_status, view.n_reads, "<i4", copy) if view.read_status else None
+
+    @property
+    def nbytes(self):
+        """bytes the fetch moved to the host"""
+        return sum(a.nbytes for a in (self.offsets, self.alns, self.digests, self.cigar, self.status) if a is not None)
+
+    def words(self, i, tx=False):
+        """the genome (or transcript) CIGAR words of alignment i"""
+        d = self.digests[i]
+        o = int(d["cigar_off"]) + (int(d["n_cigar"]) if tx else 0)
+        return self.cigar[o: o + int(d["n_tx_cigar"] if tx else d["n_cigar"])]
+
+
+def cigar_text(words):
+    """BAM CIGAR words -> SAM text ('*' when there are none)"""
+    return "".join("%d%s" % (int(w) >> 4, "MIDNSHP=X"[int(w) & 15]) for w in words) or "*"
+
+
 class Aligner:
     """thm_aligner: mirrors the reference's per-thread aligner handle
     (ThermiteAligner, src/wrapper.rs:20-27; align_read, src/aligner.rs:123)."""
@@ -534,6 +595,25 @@ class Aligner:
         v = BatchView()
         self._chk(lib().thm_batch_fetch(self.h, C.byref(v)))
         return BatchResult(v, copy)
+
+    def fetch_cigars(self, copy=True):
+        """thm_batch_fetch_cigars: the run's records with digests and CIGAR words instead of op bytes"""
+        v = CigarView()
+        self._chk(lib().thm_batch_fetch_cigars(self.h, C.byref(v)))
+        return CigarResult(v, copy)
+
+    def align_batch_cigars(self, bases, offsets, copy=True):
+        bases, offsets = _u8(bases), np.ascontiguousarray(offsets, "<u8")
+        v = CigarView()
+        self._chk(lib().thm_align_batch_cigars(self.h, _ptr(bases), _ptr(offsets), len(offsets) - 1, C.byref(v)))
+        return CigarResult(v, copy)
+
+    def cigar_encode_batch(self, ops, off):
+        """thm_cigar_encode_batch: serialised op streams ops[off[i]:off[i+1]] -> CigarResult, one digest per stream"""
+        ops, off = _u8(ops), np.ascontiguousarray(off, "<u8")
+        v = CigarView()
+        self._chk(lib().thm_cigar_encode_batch(self.h, _ptr(ops), _ptr(off), len(off) - 1, C.byref(v)))
+        return CigarResult(v)
 
     def smems_batch(self, bases, offsets, min_seed_len):
         bases, offsets = _u8(bases), np.ascontiguousarray(offsets, "<u8")
@@ -782,6 +862,19 @@ class Writer:
                       _ptr(result.ops), 0, None)
         t = Text()
         rc = lib().thm_writer_format_batch(self.h, C.byref(rb), C.byref(v), C.byref(t))
+        if rc != 0:
+            raise ThermiteError(rc, _last_error())
+        return bytes(_copy(t.data, t.len, np.uint8))
+
+    def format_batch_cigars(self, batch, result):
+        """batch: dict as from FastqReader.next_batch; result: CigarResult -> bytes (what format_batch gives for the
+        full result of the same batch)"""
+        rb, keep = read_batch_struct(batch)
+        offs = np.ascontiguousarray(result.offsets, "<u8")
+        v = CigarView(len(offs) - 1, len(result.alns), len(result.cigar), _ptr(offs), _ptr(result.alns),
+                      _ptr(result.digests), _ptr(result.cigar), 0, None)
+        t = Text()
+        rc = lib().thm_writer_format_batch_cigars(self.h, C.byref(rb), C.byref(v), C.byref(t))
         if rc != 0:
             raise ThermiteError(rc, _last_error())
         return bytes(_copy(t.data, t.len, np.uint8))

@@ -219,14 +219,22 @@ void thm_aligner_free(thm_aligner* a) {
                  &a->s_hits, &a->s_cand_off, &a->scan_tmp, &a->e_cands, &a->e_heavy, &a->e_rel, &a->e_order, &a->e_ops, &a->e_nalns,
                  &a->e_nalns64, &a->e_opbytes, &a->e_aln_off, &a->e_ops_off, &a->e_trace, &a->o_alns, &a->o_ops, &a->o_mems,
                  &a->sh_bases, &a->sh_san, &a->sh_off, &a->sh_hits, &a->sh_read, &a->sh_bw, &a->sh_xd, &a->sh_list, &a->sh_out,
-                 &a->sh_status, &a->sh_ops, &a->sh_ctl, &a->sh_trace, &a->sh_slow};
+                 &a->sh_status, &a->sh_ops, &a->sh_ctl, &a->sh_trace, &a->sh_slow, &a->c_sums, &a->c_nwords, &a->c_woff,
+                 &a->c_scan_tmp, &a->c_flags, &a->c_dig, &a->c_words, &a->c_in_ops, &a->c_in_off};
   for (DBuf* b : all) b->release();
   for (int k = 0; k < 2; k++) {
     a->r_off[k].release();
     a->r_alns[k].release();
     a->r_ops[k].release();
     a->r_stat[k].release();
+    a->ch_off[k].release();
+    a->ch_alns[k].release();
+    a->ch_dig[k].release();
+    a->ch_words[k].release();
+    a->ch_stat[k].release();
   }
+  for (auto& e : a->ev_cig)
+    if (e) (void)hipEventDestroy(e);
   for (auto& e : a->ev)
     if (e) (void)hipEventDestroy(e);
   if (a->ev_fork) (void)hipEventDestroy(a->ev_fork);

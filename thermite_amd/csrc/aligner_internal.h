@@ -152,6 +152,15 @@ struct thm_aligner {
   std::vector<thm_aln> h_hit_alns;
   std::vector<int32_t> h_hit_status;
   std::vector<uint8_t> h_hit_ops;
+  // CIGAR entry points (cigar.hip): per-stream sums and word counts, their scan, digests and words on the device; the
+  // uploaded streams of thm_cigar_encode_batch; two pinned host sets of thm_batch_fetch_cigars, used alternately and
+  // apart from r_off .. r_stat, so that neither fetch invalidates the other's view
+  DBuf c_sums, c_nwords, c_woff, c_scan_tmp, c_flags, c_dig, c_words, c_in_ops, c_in_off;
+  HBuf ch_off[2], ch_alns[2], ch_dig[2], ch_words[2], ch_stat[2];
+  int c_cur = 0;
+  hipEvent_t ev_cig[4] = {nullptr, nullptr, nullptr, nullptr};  // created by the first call
+  std::vector<thm_aln_digest> h_cig_dig;
+  std::vector<uint32_t> h_cig_words;
 };
 
 inline int fail(thm_aligner* a, int code, const char* fmt, ...) {

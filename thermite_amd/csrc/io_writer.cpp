@@ -186,12 +186,45 @@ inline void put_maybe_empty(std::string& s, const uint8_t* p, size_t n) {
     s.append((const char*)p, n);
 }
 
+// CIGAR text of BAM words (thm_cigar_view: what put_cigar writes for the op stream they were made from)
+void put_cigar_words(std::string& s, const uint32_t* w, size_t n) {
+  if (n == 0) {
+    s.push_back('*');
+    return;
+  }
+  for (size_t i = 0; i < n; i++) {
+    put_u64(s, w[i] >> 4);
+    s.push_back("MIDNSHP=X???????"[w[i] & 15u]);
+  }
+}
+
+// A batch to render: its records with either the op pool (thm_batch_view) or digests and CIGAR words (thm_cigar_view).
 struct Ctx {
   const thm_index* ix;
   const thm_read_batch* reads;
-  const thm_batch_view* res;
   int format;
+  const uint64_t* read_aln_off;
+  const thm_aln* alns;
+  const uint8_t* ops;  // null: digests and words
+  uint64_t n_op_bytes;
+  const thm_aln_digest* digests;
+  const uint32_t* words;
+  uint64_t n_words;
 };
+
+// the digest of alignment `a` and its words, checked against the word pool and for streams that could not be encoded
+const thm_aln_digest* digest_of(const Ctx& c, uint64_t a, std::string& err) {
+  const thm_aln_digest& d = c.digests[a];
+  if (d.flags) {
+    err = (d.flags & (THM_DIGEST_MALFORMED | (THM_DIGEST_MALFORMED << 8))) ? "malformed op stream" : "a run of 2^28 or more has no CIGAR word";
+    return nullptr;
+  }
+  if (d.cigar_off > c.n_words || (uint64_t)d.n_cigar + d.n_tx_cigar > c.n_words - d.cigar_off) {
+    err = "CIGAR words out of range";
+    return nullptr;
+  }
+  return &d;
+}
 
 bool format_range(const Ctx& c, uint64_t r0, uint64_t r1, std::string& s, std::string& err) {
   const thm_index* ix = c.ix;
@@ -205,7 +238,7 @@ bool format_range(const Ctx& c, uint64_t r0, uint64_t r1, std::string& s, std::s
     // format_read_name: up to the first space (:344-349)
     size_t qn = name_len;
     if (const void* sp = memchr(name, ' ', name_len)) qn = (size_t)((const uint8_t*)sp - name);
-    const uint64_t a0 = c.res->read_aln_off[r], a1 = c.res->read_aln_off[r + 1];
+    const uint64_t a0 = c.read_aln_off[r], a1 = c.read_aln_off[r + 1];
     const uint64_t multimap = a1 - a0;
     if (multimap == 0) {
       if (c.format == THM_FMT_SAM) {  // unmapped_sam_record; PAF writes nothing (src/aligner.rs:58-81)
@@ -219,17 +252,24 @@ bool format_range(const Ctx& c, uint64_t r0, uint64_t r1, std::string& s, std::s
       continue;
     }
     for (uint64_t a = a0; a < a1; a++) {
-      const thm_aln& al = c.res->alns[a];
-      if (al.ref_id >= ix->refs.size() || al.ops_off + al.ops_len > c.res->n_op_bytes) {
+      const thm_aln& al = c.alns[a];
+      if (al.ref_id >= ix->refs.size() || (c.ops && al.ops_off + al.ops_len > c.n_op_bytes)) {
         err = "alignment record out of range";
         return false;
       }
       const thm_ref& ref = ix->refs[al.ref_id];
       const std::string& rname = ix->contig_names[ref.name_id];
-      const uint8_t* ops = c.res->ops + al.ops_off;
+      const uint8_t* ops = c.ops ? c.ops + al.ops_off : nullptr;
+      const thm_aln_digest* dg = nullptr;
       OpCounts cnt;
+      if (!c.ops) {
+        if (!(dg = digest_of(c, a, err))) return false;
+        cnt.n_match = dg->n_match;
+        cnt.n_subst = dg->n_subst;
+        cnt.n_not_yclip = dg->n_not_yclip;
+      }
       if (c.format == THM_FMT_PAF) {
-        if (!count_ops(ops, al.ops_len, cnt)) {
+        if (ops && !count_ops(ops, al.ops_len, cnt)) {
           err = "malformed op stream";
           return false;
         }
@@ -270,7 +310,9 @@ bool format_range(const Ctx& c, uint64_t r0, uint64_t r1, std::string& s, std::s
       s.push_back('\t');
       put_u64(s, multimapq(multimap));
       s.push_back('\t');
-      if (!put_cigar(s, ops, al.ops_len, &cnt)) {
+      if (dg) {
+        put_cigar_words(s, c.words + dg->cigar_off, dg->n_cigar);
+      } else if (!put_cigar(s, ops, al.ops_len, &cnt)) {
         err = "malformed op stream";
         return false;
       }
@@ -304,7 +346,7 @@ bool format_range(const Ctx& c, uint64_t r0, uint64_t r1, std::string& s, std::s
       put_u64(s, cnt.n_subst);
       if (al.aln_type == THM_ALN_EXONIC) {
         const uint32_t t = al.tx_or_gene_idx;
-        if (t >= ix->txs.size() || al.tx_ops_off + al.tx_ops_len > c.res->n_op_bytes) {
+        if (t >= ix->txs.size() || (c.ops && al.tx_ops_off + al.tx_ops_len > c.n_op_bytes)) {
           err = "transcript alignment out of range";
           return false;
         }
@@ -314,7 +356,9 @@ bool format_range(const Ctx& c, uint64_t r0, uint64_t r1, std::string& s, std::s
         s.append(",+");
         put_u64(s, al.tx_ystart);
         s.push_back(',');
-        if (!put_cigar(s, c.res->ops + al.tx_ops_off, al.tx_ops_len, nullptr)) {
+        if (dg) {
+          put_cigar_words(s, c.words + dg->cigar_off + dg->n_cigar, dg->n_tx_cigar);
+        } else if (!put_cigar(s, c.ops + al.tx_ops_off, al.tx_ops_len, nullptr)) {
           err = "malformed transcript op stream";
           return false;
         }
@@ -524,7 +568,7 @@ bool format_range_bam(const Ctx& c, const std::vector<int32_t>& sq_of_name, uint
       err = "read name longer than 254 bytes cannot be stored in BAM";
       return false;
     }
-    const uint64_t a0 = c.res->read_aln_off[r], a1 = c.res->read_aln_off[r + 1];
+    const uint64_t a0 = c.read_aln_off[r], a1 = c.read_aln_off[r + 1];
     const uint64_t multimap = a1 - a0;
     auto fixed = [&](int32_t ref_id, int32_t pos, uint32_t mapq, uint32_t bin, uint32_t n_cig, uint32_t flag) {
       // the 32 fixed bytes behind block_size in one append (little-endian host, like every other table of this library)
@@ -565,15 +609,32 @@ bool format_range_bam(const Ctx& c, const std::vector<int32_t>& sq_of_name, uint
       continue;
     }
     for (uint64_t a = a0; a < a1; a++) {
-      const thm_aln& al = c.res->alns[a];
-      if (al.ref_id >= ix->refs.size() || al.ops_off + al.ops_len > c.res->n_op_bytes) {
+      const thm_aln& al = c.alns[a];
+      if (al.ref_id >= ix->refs.size() || (c.ops && al.ops_off + al.ops_len > c.n_op_bytes)) {
         err = "alignment record out of range";
         return false;
       }
       const thm_ref& ref = ix->refs[al.ref_id];
       OpCounts cnt;
       uint64_t ref_len = 0;
-      if (!bam_cigar(cig, c.res->ops + al.ops_off, al.ops_len, &cnt, ref_len) || cig.size() > 0xffff) {
+      const thm_aln_digest* dg = nullptr;
+      const uint32_t* cig_words = nullptr;
+      size_t n_cig = 0;
+      if (!c.ops) {  // the words are BAM's own: copied
+        if (!(dg = digest_of(c, a, err))) return false;
+        cnt.n_subst = dg->n_subst;
+        ref_len = dg->ref_len;
+        cig_words = c.words + dg->cigar_off;
+        n_cig = dg->n_cigar;
+      } else {
+        if (!bam_cigar(cig, c.ops + al.ops_off, al.ops_len, &cnt, ref_len)) {
+          err = "malformed op stream";
+          return false;
+        }
+        cig_words = cig.data();
+        n_cig = cig.size();
+      }
+      if (n_cig > 0xffff) {
         err = "malformed op stream";
         return false;
       }
@@ -581,8 +642,8 @@ bool format_range_bam(const Ctx& c, const std::vector<int32_t>& sq_of_name, uint
       const size_t at = s.size();
       le32(s, 0);
       fixed(sq_of_name[ref.name_id], (int32_t)pos, multimapq(multimap), reg2bin(pos, pos + (int64_t)std::max<uint64_t>(ref_len, 1)),
-            (uint32_t)cig.size(), (al.strand ? 0u : 16u) | (al.primary ? 0u : 256u));
-      s.append((const char*)cig.data(), 4 * cig.size());
+            (uint32_t)n_cig, (al.strand ? 0u : 16u) | (al.primary ? 0u : 256u));
+      s.append((const char*)cig_words, 4 * n_cig);
       bam_seq_qual(s, seq, L, qual, QL, al.strand != 0);
       {  // the four integer tags through a small buffer (7 bytes each at most)
         std::string& t4 = tags;
@@ -595,7 +656,7 @@ bool format_range_bam(const Ctx& c, const std::vector<int32_t>& sq_of_name, uint
       }
       if (al.aln_type == THM_ALN_EXONIC) {
         const uint32_t t = al.tx_or_gene_idx;
-        if (t >= ix->txs.size() || al.tx_ops_off + al.tx_ops_len > c.res->n_op_bytes) {
+        if (t >= ix->txs.size() || (c.ops && al.tx_ops_off + al.tx_ops_len > c.n_op_bytes)) {
           err = "transcript alignment out of range";
           return false;
         }
@@ -604,7 +665,9 @@ bool format_range_bam(const Ctx& c, const std::vector<int32_t>& sq_of_name, uint
         txz += ",+";
         put_u64(txz, al.tx_ystart);
         txz.push_back(',');
-        if (!put_cigar(txz, c.res->ops + al.tx_ops_off, al.tx_ops_len, nullptr)) {
+        if (dg) {
+          put_cigar_words(txz, c.words + dg->cigar_off + dg->n_cigar, dg->n_tx_cigar);
+        } else if (!put_cigar(txz, c.ops + al.tx_ops_off, al.tx_ops_len, nullptr)) {
           err = "malformed transcript op stream";
           return false;
         }
@@ -692,20 +755,12 @@ bool bgzf_compress(const char* p, size_t n, std::string& out) {
   return ok;
 }
 
-}  // namespace
-
-namespace thm {
-
-int writer_format_chunks(thm_writer* w, const thm_read_batch* reads, const thm_batch_view* res,
-                         std::vector<const std::string*>& chunks) {
+// the reads of the batch in up to n_threads ranges, each rendered (and, for BAM, compressed) by its own thread
+int format_chunks(thm_writer* w, const Ctx& c, std::vector<const std::string*>& chunks) {
   chunks.clear();
-  if (!w || !reads || !res) return THM_ERR_INVALID_ARG;
-  if (reads->n_reads != res->n_reads) return fail(THM_ERR_INVALID_ARG, "thm_writer_format_batch: reads and results differ in n_reads");
-  if (reads->n_reads && (!reads->offsets || !reads->name_off || !reads->names || !res->read_aln_off)) return THM_ERR_INVALID_ARG;
-  const uint64_t n = reads->n_reads;
+  const uint64_t n = c.reads->n_reads;
   const unsigned T = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(w->n_threads, (n + 4095) / 4096));
   w->chunk.resize(std::max<size_t>(w->chunk.size(), T));
-  Ctx c{w->ix, reads, res, w->format};
   std::vector<std::string> errs(T);
   std::vector<char> ok(T, 1);
   if (w->format == THM_FMT_BAM) w->raw.resize(std::max<size_t>(w->raw.size(), T));
@@ -737,6 +792,32 @@ int writer_format_chunks(thm_writer* w, const thm_read_batch* reads, const thm_b
     if (!ok[t]) return fail(THM_ERR_INTERNAL, "thm_writer_format_batch: " + errs[t]);
   for (unsigned t = 0; t < T; t++) chunks.push_back(&w->chunk[t]);
   return THM_OK;
+}
+
+int join_chunks(thm_writer* w, const std::vector<const std::string*>& chunks, thm_text* out) {
+  size_t total = 0;
+  for (const std::string* c : chunks) total += c->size();
+  w->out.clear();
+  w->out.reserve(total);
+  for (const std::string* c : chunks) w->out += *c;
+  out->data = (const uint8_t*)w->out.data();
+  out->len = w->out.size();
+  return THM_OK;
+}
+
+}  // namespace
+
+namespace thm {
+
+int writer_format_chunks(thm_writer* w, const thm_read_batch* reads, const thm_batch_view* res,
+                         std::vector<const std::string*>& chunks) {
+  chunks.clear();
+  if (!w || !reads || !res) return THM_ERR_INVALID_ARG;
+  if (reads->n_reads != res->n_reads) return fail(THM_ERR_INVALID_ARG, "thm_writer_format_batch: reads and results differ in n_reads");
+  if (reads->n_reads && (!reads->offsets || !reads->name_off || !reads->names || !res->read_aln_off)) return THM_ERR_INVALID_ARG;
+  static const uint8_t no_ops = 0;  // (a batch without op bytes still renders from its op pool)
+  Ctx c{w->ix, reads, w->format, res->read_aln_off, res->alns, res->ops ? res->ops : &no_ops, res->n_op_bytes, nullptr, nullptr, 0};
+  return format_chunks(w, c, chunks);
 }
 
 }  // namespace thm
@@ -819,14 +900,23 @@ int32_t thm_writer_format_batch(thm_writer* w, const thm_read_batch* reads, cons
   std::vector<const std::string*> chunks;
   const int rc = thm::writer_format_chunks(w, reads, res, chunks);
   if (rc != THM_OK) return rc;
-  size_t total = 0;
-  for (const std::string* c : chunks) total += c->size();
-  w->out.clear();
-  w->out.reserve(total);
-  for (const std::string* c : chunks) w->out += *c;
-  out->data = (const uint8_t*)w->out.data();
-  out->len = w->out.size();
-  return THM_OK;
+  return join_chunks(w, chunks, out);
+}
+
+int32_t thm_writer_format_batch_cigars(thm_writer* w, const thm_read_batch* reads, const thm_cigar_view* res, thm_text* out) {
+  if (!out || !w || !reads || !res) return THM_ERR_INVALID_ARG;
+  out->data = nullptr;
+  out->len = 0;
+  if (reads->n_reads != res->n_reads) return fail(THM_ERR_INVALID_ARG, "thm_writer_format_batch_cigars: reads and results differ in n_reads");
+  if (reads->n_reads && (!reads->offsets || !reads->name_off || !reads->names || !res->read_aln_off)) return THM_ERR_INVALID_ARG;
+  if (res->n_alns && (!res->alns || !res->digests)) return THM_ERR_INVALID_ARG;
+  if (res->n_cigar_words && !res->cigar) return THM_ERR_INVALID_ARG;
+  if (reads->n_reads && res->read_aln_off[reads->n_reads] != res->n_alns) return fail(THM_ERR_INVALID_ARG, "thm_writer_format_batch_cigars: read_aln_off does not end at n_alns");
+  Ctx c{w->ix, reads, w->format, res->read_aln_off, res->alns, nullptr, 0, res->digests, res->cigar, res->n_cigar_words};
+  std::vector<const std::string*> chunks;
+  const int rc = format_chunks(w, c, chunks);
+  if (rc != THM_OK) return rc;
+  return join_chunks(w, chunks, out);
 }
 
 }  // extern "C"

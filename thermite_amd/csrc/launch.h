@@ -529,5 +529,32 @@ hipError_t launch_calib_gather(const uint8_t* table, uint64_t span, uint64_t n_t
                                hipStream_t s);
 hipError_t launch_widen_u32_to_u64(const uint32_t* in, uint64_t* out, uint64_t n, hipStream_t s);
 
+// Run-length CIGARs and summaries of serialised op streams (kernels_cigar.hip; thm_aln_digest), one stream per
+// wavefront.  With `alns` the launch covers 2 * n_alns streams -- stream 2i is the genome op stream of alns[i],
+// stream 2i + 1 its transcript op stream (empty unless exonic) -- and writes one digest per alignment; without, stream i
+// is ops[off[i] .. off[i+1]) and every stream gets a digest.  Count fills sums[] and n_words[] (a malformed stream,
+// or one outside the pool: no words, zero counts, THM_DIGEST_MALFORMED; a run of 2^28 or more: no words,
+// THM_DIGEST_LONG_RUN) and ORs the flags it met into *any_flags; the caller scans n_words into word_off
+// (launch_exclusive_scan_u64); emit writes words[] and digests[].
+struct CigarSum {
+  uint64_t ref_len;
+  uint32_t n_match, n_subst, n_not_yclip, flags;
+};
+struct CigarParams {
+  const uint8_t* ops;
+  uint64_t ops_bytes;  // size of the pool: no stream is read beyond it
+  uint64_t n_streams;
+  const thm_aln* alns;
+  const uint64_t* off;  // [n_streams + 1] when alns is null
+  CigarSum* sums;       // [n_streams]
+  uint64_t* n_words;    // [n_streams]
+  const uint64_t* word_off;  // [n_streams + 1], emit only
+  uint32_t* words;
+  thm_aln_digest* digests;
+  unsigned int* any_flags;
+};
+hipError_t launch_cigar_count(const CigarParams& p, int n_cu, hipStream_t s);
+hipError_t launch_cigar_emit(const CigarParams& p, int n_cu, hipStream_t s);
+
 }  // namespace thm
 #endif

@@ -1,11 +1,15 @@
 #!/usr/bin/env python3
 """Quick stage timing on the GPU box (tuning aid, not the benchmark):
-python tools_perf.py [ref_len] [n_reads] [opts]"""
+python tools/perf.py [ref_len] [n_reads] [opts] [--cigars]
+--cigars: on the resident batch, thm_batch_fetch against thm_batch_fetch_cigars -- milliseconds and bytes moved to the
+host by each, and the device time of the two CIGAR passes (THM_T_CIGAR)."""
 import sys, time
 import numpy as np
 sys.path.insert(0, __import__("os").path.dirname(__import__("os").path.dirname(__import__("os").path.abspath(__file__))))
 from thermite_amd import capi, synth
 
+cigars = "--cigars" in sys.argv
+sys.argv = [x for x in sys.argv if x != "--cigars"]
 ref_len = int(sys.argv[1]) if len(sys.argv) > 1 else 4000000
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 500000
 which = sys.argv[3] if len(sys.argv) > 3 else "both"
@@ -29,6 +33,25 @@ for name, opts in (("ci", capi.CI_OPTS), ("default", capi.DEFAULT_OPTS)):
     dt = (time.perf_counter() - t0) / K
     print("%-8s ref=%d n=%d  %.2f Mreads/s  wall %.2f ms  " % (name, ref_len, n, n / dt / 1e6, dt * 1e3) +
           " ".join("%s=%.2f" % kv for kv in acc.items()), flush=True)
+    if cigars:
+        K2 = 7
+        for fetch in (a.fetch, a.fetch_cigars, a.fetch, a.fetch_cigars):   # first round: buffers grow
+            ms = []
+            for _ in range(K2):
+                t0 = time.perf_counter()
+                r = fetch(copy=False)
+                ms.append((time.perf_counter() - t0) * 1e3)
+        for nm, fetch in (("fetch", a.fetch), ("fetch_cigars", a.fetch_cigars)):
+            ms = []
+            for _ in range(K2):
+                t0 = time.perf_counter()
+                r = fetch(copy=False)
+                ms.append((time.perf_counter() - t0) * 1e3)
+            nbytes = sum(x.nbytes for x in (r.offsets, r.alns, getattr(r, "ops", None), getattr(r, "digests", None),
+                                            getattr(r, "cigar", None), r.status) if x is not None)
+            extra = "" if nm == "fetch" else "  words %d  THM_T_CIGAR %.3f ms" % (len(r.cigar), a.timings()["cigar"])
+            print("         %-12s median %.2f ms (min %.2f max %.2f, %d calls)  %d bytes to the host  alns %d%s" % (
+                nm, float(np.median(ms)), min(ms), max(ms), K2, nbytes, len(r.alns), extra), flush=True)
     c = dict(zip(capi.COUNTER_NAMES, a.counters().tolist()))
     runs = K + 2
     print("         per read: smems %.2f hits %.2f swg_calls %.2f cols %.1f cells %.0f alns %.2f win_bytes %.0f" % tuple(
