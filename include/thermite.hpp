@@ -20,6 +20,7 @@
 
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -189,6 +190,47 @@ class Aligner {
       }
     return out;
   }
+  // The records of the writer loop (src/aligner.rs:54-116) for `reads`, BAM-encoded on the device (thm_align_batch_bam):
+  // result[r] holds the records of read r as byte strings, each beginning with its block_size -- one per alignment, or
+  // the unmapped record.  `quals` may be empty (no qualities: 0xff); flags: THM_BAM_NO_ANNOTATION_TAGS.
+  std::vector<std::vector<std::string>> align_reads_bam(const std::vector<std::string>& names, const std::vector<std::string>& reads,
+                                                        const std::vector<std::string>& quals, std::uint32_t flags = 0) {
+    if (names.size() != reads.size() || (!quals.empty() && quals.size() != reads.size()))
+      throw Error(THM_ERR_INVALID_ARG, "one name (and one quality string) per read");
+    std::vector<std::uint8_t> bases, q, nm;
+    std::vector<std::uint64_t> off{0}, noff{0};
+    for (std::size_t r = 0; r < reads.size(); r++) {
+      bases.insert(bases.end(), reads[r].begin(), reads[r].end());
+      off.push_back(bases.size());
+      nm.insert(nm.end(), names[r].begin(), names[r].end());
+      noff.push_back(nm.size());
+      if (!quals.empty()) {
+        if (quals[r].size() != reads[r].size()) throw Error(THM_ERR_INVALID_ARG, "quality string and read differ in length");
+        q.insert(q.end(), quals[r].begin(), quals[r].end());
+      }
+    }
+    const std::uint8_t none = 0;
+    thm_read_batch rb;
+    rb.n_reads = reads.size();
+    rb.n_bases = bases.size();
+    rb.bases = bases.empty() ? &none : bases.data();
+    rb.offsets = off.data();
+    rb.quals = quals.empty() ? nullptr : (q.empty() ? &none : q.data());
+    rb.names = nm.empty() ? &none : nm.data();
+    rb.name_off = noff.data();
+    thm_bam_view v;
+    check(thm_align_batch_bam(h_.get(), &rb, flags, &v));
+    std::vector<std::vector<std::string>> out(reads.size());
+    for (std::uint64_t r = 0; r < v.n_reads; r++)
+      for (std::uint64_t at = v.read_rec_off[r]; at < v.read_rec_off[r + 1];) {
+        std::uint32_t bs;
+        std::memcpy(&bs, v.data + at, 4);
+        out[r].emplace_back((const char*)v.data + at, (std::size_t)bs + 4);
+        at += (std::uint64_t)bs + 4;
+      }
+    return out;
+  }
+
   // to_noodles_cigar for one serialised op stream (thm_cigar_encode_batch): its digest, words through *words
   thm_aln_digest cigar_encode(const std::vector<std::uint8_t>& ops, std::vector<std::uint32_t>* words = nullptr) {
     const std::uint64_t off[2] = {0, ops.size()};
@@ -340,6 +382,15 @@ class ThermiteAligner {
     }
     return out;
   }
+  // The return shape of the reference's align_read (src/wrapper.rs:64-101,126-141): BAM-encoded records, the bytes a
+  // rust_htslib Record holds, encoded on the device, TX / GX / GN / RE removed (AS NH HI nM stay).  Each string begins
+  // with its block_size.  align_read_records_with_tags keeps the four tags.
+  std::vector<std::string> align_read_records(const std::string& name, const std::string& read, const std::string& qual) {
+    return records(name, read, qual, THM_BAM_NO_ANNOTATION_TAGS);
+  }
+  std::vector<std::string> align_read_records_with_tags(const std::string& name, const std::string& read, const std::string& qual) {
+    return records(name, read, qual, 0);
+  }
   std::vector<std::string> align_read_with_tags(const std::string& name, const std::string& read, const std::string& qual) {
     aligner_.set_opts(opts_);
     const std::uint64_t off[2] = {0, read.size()}, noff[2] = {0, name.size()};
@@ -382,6 +433,12 @@ class ThermiteAligner {
   const std::string& header_view() const { return header_; }  // SAM header text (a HeaderView in the reference)
 
  private:
+  std::vector<std::string> records(const std::string& name, const std::string& read, const std::string& qual, std::uint32_t flags) {
+    aligner_.set_opts(opts_);
+    std::vector<std::string> q;
+    if (qual.size() == read.size() && !qual.empty()) q.push_back(qual);  // as align_read_with_tags: otherwise none
+    return aligner_.align_reads_bam({name}, {read}, q, flags)[0];
+  }
   Index index_;
   Aligner aligner_;
   AlignOpts opts_;

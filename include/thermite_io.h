@@ -91,6 +91,42 @@ int32_t thm_fastq_open(const char* path, thm_fastq** out);
 int32_t thm_fastq_next_batch(thm_fastq* r, uint64_t max_reads, thm_read_batch* out);
 void thm_fastq_close(thm_fastq* r);
 
+/* ------------------------------------------------- BAM records from the device */
+
+/* The records of the writer loop (src/aligner.rs:54-116) for one aligned batch, BAM-encoded on the device
+ * (bam::Writer::write_sam_record, src/aligner.rs:69-76,98-108): back to back, each beginning with its block_size;
+ * no BAM header, no BGZF framing.  Byte for byte what thm_writer_format_batch encodes for a BAM writer before it
+ * deflates.  The records of read r are data[read_rec_off[r] .. read_rec_off[r+1]): one per alignment, or the unmapped
+ * record for a read without alignments (a failed read is one: n_failed_reads / read_status as in thm_batch_view). */
+typedef struct thm_bam_view {
+  uint64_t n_reads;
+  uint64_t n_records;
+  uint64_t n_bytes;
+  const uint8_t* data;          /* [n_bytes]   */
+  const uint64_t* read_rec_off; /* [n_reads+1] */
+  uint64_t n_failed_reads;
+  const int32_t* read_status;
+} thm_bam_view;
+
+/* drops the TX GX GN RE tags: what sam_noodles_to_htslib removes, src/wrapper.rs:134-139 (AS NH HI nM stay) */
+#define THM_BAM_NO_ANNOTATION_TAGS 1u
+
+/* thm_batch_upload plus the names and qualities (may be NULL) of the batch in device memory: what thm_batch_fetch_bam
+ * needs besides the run's results.  A batch uploaded by plain thm_batch_upload has no names. */
+int32_t thm_batch_upload_reads(thm_aligner* a, const thm_read_batch* reads);
+/* Stands where thm_batch_fetch / thm_batch_fetch_cigars stand after thm_batch_run: syncs (pool-overflow replays
+ * included), runs the CIGAR passes, a size pass, a scan and an emit pass on the aligner's stream and copies back the
+ * record bytes, the per-read byte offsets and the statuses only.  Any of the three fetches may follow the others for
+ * the same run, in any order.  Results land in two pinned buffer sets of their own, used alternately: a thm_bam_view
+ * stays valid until the second-next call on this aligner that returns one, and no other view is invalidated.
+ * Counters and the other timings are untouched; THM_T_BAM is set.  The index's name tables go to the device at the
+ * first call.  THM_ERR_INVALID_ARG: unknown bits in `flags`, a batch not uploaded by thm_batch_upload_reads, an index
+ * without names.  THM_ERR_INTERNAL, with the writer's messages: a QNAME (name up to the first space) over 254 bytes,
+ * more than 65535 CIGAR words, a run of 2^28 or more (THM_DIGEST_LONG_RUN). */
+int32_t thm_batch_fetch_bam(thm_aligner* a, uint32_t flags, thm_bam_view* out);
+/* upload_reads + run + the fetch above */
+int32_t thm_align_batch_bam(thm_aligner* a, const thm_read_batch* reads, uint32_t flags, thm_bam_view* out);
+
 /* -------------------------------------------------------- SAM / PAF writer */
 
 /* OutputFormat, src/aln_writer.rs:16-21 */
@@ -125,6 +161,12 @@ int32_t thm_writer_format_batch(thm_writer* w, const thm_read_batch* reads, cons
  * digest carries a flag (a run of 2^28 or more has no word) cannot be rendered: THM_ERR_INTERNAL. */
 int32_t thm_writer_format_batch_cigars(thm_writer* w, const thm_read_batch* reads, const thm_cigar_view* result, thm_text* out);
 
+/* BAM writers only: the records of a thm_bam_view as a run of complete BGZF blocks.  The bytes are cut into read
+ * ranges by read_rec_off over the writer's threads, as thm_writer_format_batch cuts the reads, and deflated by the
+ * same code (THM_BAM_LEVEL honoured): inflated, the output equals view->data.  THM_ERR_INVALID_ARG: another format,
+ * offsets that do not start at 0, descend or end elsewhere than n_bytes.  Text valid until the next call on `w`. */
+int32_t thm_writer_wrap_bam(thm_writer* w, const thm_bam_view* view, thm_text* out);
+
 /* ------------------------------------------------------ whole-file driver */
 
 typedef struct thm_run_stats {
@@ -142,7 +184,10 @@ typedef struct thm_run_stats {
 
 /* align_reads_from_file, src/aligner.rs:22-120: every record of every FASTQ in
  * order -> output_path ("-" = stdout).  Three overlapped stages (parse | GPU |
- * format+write) over batches of `batch_reads` reads (0 = 250 000). */
+ * format+write) over batches of `batch_reads` reads (0 = 250 000).
+ * THM_BAM_DEVICE=1 in the environment and THM_FMT_BAM: the records are encoded on the device
+ * (thm_batch_upload_reads / thm_batch_fetch_bam) and the formatting stage only deflates (thm_writer_wrap_bam);
+ * the file's inflated bytes are the same. */
 int32_t thm_align_files(thm_aligner* a, const char* const* fastq_paths, uint32_t n_paths, const char* output_path,
                         int32_t format, uint64_t batch_reads, uint32_t n_threads, thm_run_stats* stats);
 /* The same over several aligners -- one per GPU of the node, all over one index (the shape of ThermiteAligner: Clone +

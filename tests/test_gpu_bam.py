@@ -1,0 +1,339 @@
+"""-m gpu: BAM records encoded on the device (kernels_bam.hip, thm_batch_fetch_bam) against the oracle's writer
+(oracle/aln_writer.py: bam_stream) byte for byte, on the read sets tests/test_bam_host.py pins by the oracle alone;
+the annotation flag, the three fetches of one run in every order, the errors, the file driver with THM_BAM_DEVICE=1
+and the C++ face."""
+import gzip
+import itertools
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import bam_common as bc
+from gpu_common import World, assert_batch_equal
+from oracle import aln_writer as ow
+from thermite_amd import capi, refdata, synth
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+_worlds, _sets = {}, {}
+
+
+def _world(key, wide=False):
+    if (key, wide) not in _worlds:
+        _worlds[(key, wide)] = World(bc.tables(key), wide)
+    return _worlds[(key, wide)]
+
+
+def _set(name, wide=False):
+    """(world, read set, batch dict, oracle result, oracle record bytes, per-read byte offsets)"""
+    w = _world(bc.REF_OF[name], wide)
+    if name not in _sets:
+        rs = bc.read_set(name, w.t)
+        b = bc.batch_of(rs)
+        r = w.oix.align_batch(b["bases"], b["offsets"], rs["opts"], n_threads=8)
+        assert r.counters[15] == 0
+        _sets[name] = (rs, b, r) + bc.oracle_records(w.t, rs, r)
+    return (w,) + _sets[name]
+
+
+def _assert_records(g, data, off, what):
+    assert np.array_equal(g.read_rec_off, off), (what, "read_rec_off")
+    got = g.data.tobytes()
+    if got != data:
+        a, b = bc.split_records(got) if len(got) == len(data) else None, bc.split_records(data)
+        if a:
+            k = next(i for i in range(len(b)) if a[i] != b[i])
+            raise AssertionError("%s: record %d differs:\n device %r\n oracle %r" % (what, k, a[k], b[k]))
+        raise AssertionError("%s: %d bytes from the device, %d from the oracle" % (what, len(got), len(data)))
+    assert g.n_records == len(bc.split_records(data)) and g.n_reads == len(off) - 1
+
+
+# ------------------------------------------------------------------ byte equality
+@pytest.mark.parametrize("wide", [False, True], ids=["c32", "c64"])
+@pytest.mark.parametrize("name", bc.READ_SETS)
+def test_records_equal_the_oracles(name, wide):
+    w, rs, b, r, data, off = _set(name, wide)
+    for tpr in (True, False):   # the problem-parallel path in front, and the wave-per-read kernels alone
+        a = w.aligner(rs["opts"])
+        a.debug_set_flags(tpr=tpr)
+        a.upload_reads(b)
+        a.run()
+        g = a.fetch_bam()
+        assert g.n_failed == 0 and g.status is None
+        _assert_records(g, data, off, "%s tpr=%s" % (name, tpr))
+        assert a.timings()["bam"] > 0
+        assert [len(g.records(i)) for i in range(3)] == [max(int(r.offsets[i + 1] - r.offsets[i]), 1) for i in range(3)]
+        g2 = a.align_batch_bam(b)   # upload + run + fetch
+        _assert_records(g2, data, off, name + " align_batch_bam")
+        a.close()
+    if name == "test_query":
+        assert data == open(bc.GOLDEN_BIN, "rb").read()
+
+
+def test_both_emit_forms_give_the_same_bytes():
+    """the two forms of the emit kernel: the record staged in LDS and written out as aligned dwords (the default), and
+    byte stores (THM_BAM_EMIT=bytes, read once per aligner); records beyond the LDS slice (250-base reads, hundreds of
+    CIGAR words) take the byte path in either"""
+    old = os.environ.get("THM_BAM_EMIT")
+    try:
+        for form in ("dwords", "bytes"):
+            os.environ["THM_BAM_EMIT"] = form
+            for name in ("syn", "micro", "beyond", "test_query"):
+                w, rs, b, r, data, off = _set(name)
+                a = w.aligner(rs["opts"])
+                _assert_records(a.align_batch_bam(b), data, off, name + " " + form)
+                a.close()
+    finally:
+        if old is None:
+            os.environ.pop("THM_BAM_EMIT", None)
+        else:
+            os.environ["THM_BAM_EMIT"] = old
+
+
+@pytest.mark.parametrize("wide", [False, True], ids=["c32", "c64"])
+def test_failed_reads_get_the_unmapped_record(wide):
+    """a read beyond the build limit fails alone: statuses as thm_batch_fetch reports them, and its record is the
+    unmapped one the writer gives a read without alignments (expected records: the oracle's writer over the plain
+    fetch of the same run, which the other suites pin to the oracle's aligner)"""
+    w = _world("chrm", wide)
+    sb, so, _ = synth.simulate_reads(w.t, 200, 91, stream=101)
+    seqs = [bytes(sb[so[i]: so[i + 1]]) for i in range(200)]
+    seqs.insert(77, b"ACGT" * 17000)  # 68 000 bases
+    rs = dict(names=[b"f%d x" % i for i in range(201)], seqs=seqs, quals=[b"I" * len(s) for s in seqs], opts=capi.CI_OPTS)
+    a = w.aligner(capi.CI_OPTS)
+    a.upload_reads(bc.batch_of(rs))
+    a.run()
+    f = a.fetch()
+    g = a.fetch_bam()
+    assert f.n_failed == g.n_failed == 1 and np.array_equal(f.status, g.status) and g.status[77] == capi.ERR_UNSUPPORTED
+    data, off = bc.oracle_records(w.t, rs, f)
+    _assert_records(g, data, off, "batch with an over-long read")
+    rec = bc.parse_record(g.records(77)[0])
+    assert rec["flag"] == 4 and rec["l_seq"] == 68000 and rec["qname"] == b"f77"
+    a.close()
+
+
+def test_after_a_pool_overflow_replay():
+    w, rs, b, r, data, off = _set("syn")
+    a = w.aligner(rs["opts"])
+    before = a.debug_set_pool_caps(smem_cap=300, cand_cap=16, ops_cap=4096)
+    a.upload_reads(b)
+    a.run()
+    g = a.fetch_bam()   # the replay happens inside this call's sync
+    assert a.debug_set_pool_caps() > before, "the small pools did not overflow"
+    _assert_records(g, data, off, "after a pool-overflow replay")
+    assert_batch_equal(a.fetch(), r)
+    a.close()
+
+
+def test_empty_batch_and_a_batch_without_alignments():
+    w = _world("syn")
+    a = w.aligner(capi.CI_OPTS)
+    empty = dict(bases=np.zeros(0, np.uint8), offsets=np.zeros(1, "<u8"), quals=None, names=np.zeros(0, np.uint8), name_off=np.zeros(1, "<u8"))
+    g = a.align_batch_bam(empty)
+    assert g.n_reads == 0 and g.n_records == 0 and len(g.data) == 0 and g.read_rec_off.tolist() == [0]
+    rng = np.random.default_rng(5)
+    seqs = [bytes(np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, 60 + i % 5)]) for i in range(300)]
+    rs = dict(names=[b"n%d" % i for i in range(300)], seqs=seqs, quals=[b"#" * len(s) for s in seqs], opts=capi.CI_OPTS)
+    b = bc.batch_of(rs)
+    r = w.oix.align_batch(b["bases"], b["offsets"], capi.CI_OPTS, n_threads=8)
+    assert len(r.alns) == 0
+    data, off = bc.oracle_records(w.t, rs, r)
+    g = a.align_batch_bam(b)
+    _assert_records(g, data, off, "no read aligns")
+    assert g.n_records == 300
+    a.close()
+
+
+# ------------------------------------------------------------------ annotation flag
+@pytest.mark.parametrize("name", ["multi", "syn", "micro", "test_query"])
+def test_no_annotation_tags(name):
+    w, rs, b, r, data, off = _set(name)
+    stripped = bc.strip_annotation(data)
+    assert len(stripped) < len(data)
+    n_rec = np.maximum(np.diff(r.offsets.astype(np.int64)), 1)
+    lens = [len(x) for x in bc.split_records(stripped)]
+    off2 = np.concatenate([[0], np.cumsum(np.add.reduceat(lens, np.concatenate([[0], np.cumsum(n_rec)[:-1]])))]).astype("<u8")
+    a = w.aligner(rs["opts"])
+    g = a.align_batch_bam(b, flags=capi.BAM_NO_ANNOTATION_TAGS)
+    _assert_records(g, stripped, off2, name + " without annotation tags")
+    _assert_records(a.fetch_bam(), data, off, name + " with them, same run")
+    a.close()
+
+
+# ------------------------------------------------------------------ fetch order
+def test_the_three_fetches_in_every_order():
+    w, rs, b, r, data, off = _set("syn")
+    a = w.aligner(rs["opts"])
+    a.reset_counters()
+    a.upload_reads(b)
+    first_cig = None
+    for order in itertools.permutations(("fetch", "cigars", "bam")):
+        a.run()
+        a.sync()
+        t_run, c_run = a.timings(), a.counters()
+        views, kept = {}, {}
+        for what in order:
+            if what == "fetch":
+                v = a.fetch(copy=False)
+                kept[what] = (v.offsets.copy(), v.alns.copy(), v.ops.copy())
+            elif what == "cigars":
+                v = a.fetch_cigars(copy=False)
+                kept[what] = (v.offsets.copy(), v.alns.copy(), v.digests.copy(), v.cigar.copy())
+            else:
+                v = a.fetch_bam(copy=False)
+                kept[what] = (v.read_rec_off.copy(), v.data.copy())
+            views[what] = v
+        # every view is still valid after the other two fetches, and equal whatever the order
+        f, c, g = views["fetch"], views["cigars"], views["bam"]
+        assert all(np.array_equal(x, y) for x, y in zip((f.offsets, f.alns, f.ops), kept["fetch"])), order
+        assert all(np.array_equal(x, y) for x, y in zip((c.offsets, c.alns, c.digests, c.cigar), kept["cigars"])), order
+        assert all(np.array_equal(x, y) for x, y in zip((g.read_rec_off, g.data), kept["bam"])), order
+        assert_batch_equal(f, r)
+        _assert_records(g, data, off, "order %s" % (order,))
+        assert np.array_equal(c.alns, f.alns)
+        if first_cig is None:
+            first_cig = (c.digests.copy(), c.cigar.copy())
+        assert np.array_equal(c.digests, first_cig[0]) and np.array_equal(c.cigar, first_cig[1]), order
+        t2 = a.timings()
+        assert all(t2[k] == t_run[k] for k in ("seed", "plan", "extend", "compact", "total")) and t2["bam"] > 0 and t2["cigar"] > 0
+        assert np.array_equal(a.counters(), c_run)
+    # the two-set rule: a BAM view survives the next BAM fetch, and THM_T_CIGAR belongs to fetch_cigars alone
+    a.run()
+    a.fetch_cigars()
+    t_c = a.timings()["cigar"]
+    g1 = a.fetch_bam(copy=False)
+    k1 = g1.data.copy()
+    a.run()
+    g2 = a.fetch_bam(copy=False)
+    assert a.timings()["cigar"] == t_c
+    assert np.array_equal(g1.data, k1) and np.array_equal(g2.data, k1)
+    a.close()
+
+
+# ------------------------------------------------------------------ errors
+def test_errors():
+    w, rs, b, r, data, off = _set("multi")
+    a = w.aligner(rs["opts"])
+    a.upload(b["bases"], b["offsets"])   # plain upload: no names
+    a.run()
+    with pytest.raises(capi.ThermiteError) as e:
+        a.fetch_bam()
+    assert e.value.code == capi.ERR_INVALID_ARG and "thm_batch_upload_reads" in str(e.value)
+    assert_batch_equal(a.fetch(), r)     # the run itself is unharmed
+    a.upload_reads(b)
+    a.run()
+    for bad in (2, 0x80000000, 3):
+        with pytest.raises(capi.ThermiteError) as e:
+            a.fetch_bam(flags=bad)
+        assert e.value.code == capi.ERR_INVALID_ARG and "flag" in str(e.value)
+    _assert_records(a.fetch_bam(), data, off, "after the refused calls")
+    # a QNAME of 255 bytes fails the call with the writer's message; 254 bytes pass; what follows the space does not count
+    names = list(rs["names"])
+    names[5] = b"q" * 254 + b" " + b"c" * 300
+    ok = dict(rs, names=names)
+    g = a.align_batch_bam(bc.batch_of(ok))
+    assert bc.parse_record(g.records(5)[0])["qname"] == b"q" * 254
+    d_ok, o_ok = bc.oracle_records(w.t, ok, r)
+    _assert_records(g, d_ok, o_ok, "254-byte QNAME")
+    names[5] = b"q" * 255 + b" x"
+    with pytest.raises(capi.ThermiteError) as e:
+        a.align_batch_bam(bc.batch_of(dict(rs, names=names)))
+    assert e.value.code == capi.ERR_INTERNAL and "read name longer than 254 bytes cannot be stored in BAM" in str(e.value)
+    wr = capi.Writer(w.ix, capi.FMT_BAM)
+    with pytest.raises(capi.ThermiteError) as e2:   # the host writer's message for the same batch
+        wr.format_batch(bc.batch_of(dict(rs, names=names)), a.fetch())
+    assert str(e2.value).split(": ", 1)[1] == str(e.value).split(": ", 1)[1]
+    wr.close()
+    _assert_records(a.align_batch_bam(b), data, off, "the next batch after the failed one")
+    a.close()
+    # an index without names
+    t = {k: v for k, v in w.t.items() if k not in ("names", "tx_ids", "gene_ids", "gene_names")}
+    ix = capi.Index(t)
+    a = capi.Aligner(ix, rs["opts"])
+    a.upload_reads(b)
+    a.run()
+    with pytest.raises(capi.ThermiteError) as e:
+        a.fetch_bam()
+    assert e.value.code == capi.ERR_INVALID_ARG and "names" in str(e.value)
+    assert len(a.fetch().alns) == len(r.alns)
+    a.close()
+    ix.close()
+
+
+# ------------------------------------------------------------------ driver
+_DRIVER_CHILD = r"""
+import sys
+sys.path.insert(0, %r); sys.path.insert(0, %r)
+import bam_common as bc
+from thermite_amd import capi
+t = bc.tables("syn")
+ix = capi.Index(t)
+rs = bc.read_set("syn", t)
+for n_al in (1, 3):
+    als = [capi.Aligner(ix, rs["opts"]) for _ in range(n_al)]
+    for kind in ("fastq", "fastq.gz"):
+        st = capi.align_files(als, [sys.argv[1] + "/reads." + kind], "%%s/%%s.%%d.%%s.bam" %% (sys.argv[1], sys.argv[2], n_al, kind),
+                              capi.FMT_BAM, batch_reads=700, n_threads=4)
+        print("stats", n_al, kind, st["n_reads"], st["n_aligned_reads"], st["n_records"], st["n_batches"])
+    for a in als:
+        a.close()
+"""
+
+
+def test_file_driver_with_the_device_encoder(tmp_path):
+    """align_files(FMT_BAM) with THM_BAM_DEVICE=1 and without (a child process per setting: the switch is read from
+    the environment), plain and gzip FASTQ, one and three aligners: the inflated files are equal, and the oracle's"""
+    w, rs, b, r, data, off = _set("syn")
+    body = b"".join(b"@" + n + b"\n" + s + b"\n+\n" + q + b"\n" for n, s, q in zip(rs["names"], rs["seqs"], rs["quals"]))
+    (tmp_path / "reads.fastq").write_bytes(body)
+    (tmp_path / "reads.fastq.gz").write_bytes(gzip.compress(body, 6))
+    want = ow.bam_header_bytes(w.t) + data
+    stats = {}
+    for tag, switch in (("host", None), ("device", "1"), ("zero", "0")):
+        env = dict(os.environ)
+        env.pop("THM_BAM_DEVICE", None)
+        if switch is not None:
+            env["THM_BAM_DEVICE"] = switch
+        out = subprocess.run([sys.executable, "-c", _DRIVER_CHILD % (ROOT, os.path.join(ROOT, "tests")), str(tmp_path), tag],
+                             env=env, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-3000:]
+        stats[tag] = [ln for ln in out.stdout.splitlines() if ln.startswith("stats")]
+        assert len(stats[tag]) == 4
+    assert stats["host"] == stats["device"] == stats["zero"]   # reads, aligned reads, records, batches
+    n_aligned = int((np.diff(r.offsets.astype(np.int64)) > 0).sum())
+    assert stats["device"][0] == "stats 1 fastq %d %d %d %d" % (len(rs["seqs"]), n_aligned, len(bc.split_records(data)), -(-len(rs["seqs"]) // 700))
+    for n_al in (1, 3):
+        for kind in ("fastq", "fastq.gz"):
+            files = [open(tmp_path / ("%s.%d.%s.bam" % (tag, n_al, kind)), "rb").read() for tag in ("host", "device", "zero")]
+            assert ow.bgzf_decompress(files[1]) == want, (n_al, kind)
+            assert ow.bgzf_decompress(files[0]) == want and files[2] == files[0], (n_al, kind)
+
+
+# ------------------------------------------------------------------ C++
+def test_cpp_align_read_records(data_dir, tmp_path):
+    """ThermiteAligner::align_read_records (the reference's return shape: BAM-encoded records without TX GX GN RE) and
+    its _with_tags twin, one read per call, against the device records of the whole batch and the golden file"""
+    exe = tmp_path / "bam_main"
+    libdir = os.path.dirname(capi.SO_PATH)
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-I" + os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "tests", "cpp", "bam_main.cpp"), "-o", str(exe), "-L" + libdir,
+                           "-lthermite_amd", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"])
+    idx = tmp_path / "test_ref.thmidx"
+    ix = capi.Index.from_files(data_dir + "/test_ref.fasta", data_dir + "/test_ref.gtf")
+    ix.save(idx)
+    s_out, t_out = tmp_path / "stripped.bin", tmp_path / "tagged.bin"
+    out = subprocess.run([str(exe), str(idx), "3", "0", data_dir + "/test_query.fastq", str(s_out), str(t_out)], check=True, capture_output=True)
+    w, rs, b, r, data, off = _set("test_query")
+    a = capi.Aligner(ix, rs["opts"])
+    g = a.align_batch_bam(b)
+    gs = a.fetch_bam(flags=capi.BAM_NO_ANNOTATION_TAGS)
+    assert t_out.read_bytes() == g.data.tobytes() == open(bc.GOLDEN_BIN, "rb").read()
+    assert s_out.read_bytes() == gs.data.tobytes() == bc.strip_annotation(data)
+    assert b"records %d" % gs.n_records in out.stderr
+    a.close()
+    ix.close()

@@ -57,7 +57,7 @@ N_COUNTERS = 16
 COUNTER_NAMES = ["reads", "aligned", "unmapped", "alns", "exonic", "intronic", "intergenic", "smems", "hits",
                  "swg_calls", "dp_cells", "dp_cols", "op_bytes", "window_bytes"]
 N_TIMINGS = 8
-TIMING_NAMES = ["seed", "plan", "extend", "compact", "total", "cigar"]
+TIMING_NAMES = ["seed", "plan", "extend", "compact", "total", "cigar", "bam"]
 
 OK, ERR_INVALID_ARG, ERR_NO_DEVICE, ERR_HIP, ERR_UNSUPPORTED, ERR_OUT_OF_CONTRACT, ERR_OOM, ERR_INTERNAL = (
     0, -1, -2, -3, -4, -5, -6, -7)
@@ -127,6 +127,15 @@ class CigarView(C.Structure):
                 ("n_failed_reads", C.c_uint64), ("read_status", C.c_void_p)]
 
 
+class BamView(C.Structure):
+    """thm_bam_view (include/thermite_io.h)"""
+
+    _fields_ = [("n_reads", C.c_uint64), ("n_records", C.c_uint64), ("n_bytes", C.c_uint64), ("data", C.c_void_p),
+                ("read_rec_off", C.c_void_p), ("n_failed_reads", C.c_uint64), ("read_status", C.c_void_p)]
+
+
+BAM_NO_ANNOTATION_TAGS = 1
+
 # every symbol include/thermite.h declares
 ABI_SYMBOLS = [
     "thm_index_create_in_memory", "thm_index_free", "thm_index_text_len", "thm_index_suffix_array",
@@ -146,6 +155,7 @@ IO_ABI_SYMBOLS = [
     "thm_fastq_next_batch", "thm_fastq_close", "thm_writer_create", "thm_writer_free", "thm_writer_header",
     "thm_writer_format_batch", "thm_writer_trailer", "thm_align_files", "thm_align_files_multi",
     "thm_writer_format_batch_cigars",
+    "thm_batch_upload_reads", "thm_batch_fetch_bam", "thm_align_batch_bam", "thm_writer_wrap_bam",
 ]
 ERR_IO, ERR_FORMAT = -8, -9
 FMT_PAF, FMT_SAM, FMT_BAM = 0, 1, 2
@@ -278,6 +288,14 @@ def lib():
     L.thm_writer_format_batch.argtypes = [vp, vp, vp, vp]
     L.thm_writer_format_batch_cigars.restype = i32
     L.thm_writer_format_batch_cigars.argtypes = [vp, vp, vp, vp]
+    L.thm_batch_upload_reads.restype = i32
+    L.thm_batch_upload_reads.argtypes = [vp, vp]
+    L.thm_batch_fetch_bam.restype = i32
+    L.thm_batch_fetch_bam.argtypes = [vp, u32, vp]
+    L.thm_align_batch_bam.restype = i32
+    L.thm_align_batch_bam.argtypes = [vp, vp, u32, vp]
+    L.thm_writer_wrap_bam.restype = i32
+    L.thm_writer_wrap_bam.argtypes = [vp, vp, vp]
     L.thm_align_files.restype = i32
     L.thm_align_files.argtypes = [vp, vp, u32, cp, i32, u64, u32, vp]
     L.thm_align_files_multi.restype = i32
@@ -536,6 +554,34 @@ class CigarResult:
         return self.cigar[o: o + int(d["n_tx_cigar"] if tx else d["n_cigar"])]
 
 
+class BamResult:
+    """thm_bam_view copied out, or (copy=False) numpy views of the aligner's pinned result set: the BAM records of the
+    batch back to back (no header, no BGZF framing) and the byte offset of every read's first record."""
+
+    def __init__(self, view, copy=True):
+        self.n_reads = view.n_reads
+        self.n_records = view.n_records
+        self.data = _copy(view.data, view.n_bytes, np.uint8, copy)
+        self.read_rec_off = _copy(view.read_rec_off, view.n_reads + 1, "<u8", copy)
+        self.n_failed = view.n_failed_reads
+        self.status = _copy(view.read_status, view.n_reads, "<i4", copy) if view.read_status else None
+
+    @property
+    def nbytes(self):
+        """bytes the fetch moved to the host"""
+        return sum(a.nbytes for a in (self.data, self.read_rec_off, self.status) if a is not None)
+
+    def records(self, r):
+        """the records of read r as byte strings, each beginning with its block_size"""
+        b = self.data[int(self.read_rec_off[r]): int(self.read_rec_off[r + 1])].tobytes()
+        out, at = [], 0
+        while at < len(b):
+            n = 4 + int.from_bytes(b[at: at + 4], "little")
+            out.append(b[at: at + n])
+            at += n
+        return out
+
+
 def cigar_text(words):
     """BAM CIGAR words -> SAM text ('*' when there are none)"""
     return "".join("%d%s" % (int(w) >> 4, "MIDNSHP=X"[int(w) & 15]) for w in words) or "*"
@@ -607,6 +653,23 @@ class Aligner:
         v = CigarView()
         self._chk(lib().thm_align_batch_cigars(self.h, _ptr(bases), _ptr(offsets), len(offsets) - 1, C.byref(v)))
         return CigarResult(v, copy)
+
+    def upload_reads(self, batch):
+        """thm_batch_upload_reads: `batch` is a dict as from FastqReader.next_batch (quals may be None)"""
+        rb, keep = read_batch_struct(batch)
+        self._chk(lib().thm_batch_upload_reads(self.h, C.byref(rb)))
+
+    def fetch_bam(self, flags=0, copy=True):
+        """thm_batch_fetch_bam: the run's BAM records, encoded on the device"""
+        v = BamView()
+        self._chk(lib().thm_batch_fetch_bam(self.h, flags, C.byref(v)))
+        return BamResult(v, copy)
+
+    def align_batch_bam(self, batch, flags=0, copy=True):
+        rb, keep = read_batch_struct(batch)
+        v = BamView()
+        self._chk(lib().thm_align_batch_bam(self.h, C.byref(rb), flags, C.byref(v)))
+        return BamResult(v, copy)
 
     def cigar_encode_batch(self, ops, off):
         """thm_cigar_encode_batch: serialised op streams ops[off[i]:off[i+1]] -> CigarResult, one digest per stream"""
@@ -875,6 +938,17 @@ class Writer:
                       _ptr(result.digests), _ptr(result.cigar), 0, None)
         t = Text()
         rc = lib().thm_writer_format_batch_cigars(self.h, C.byref(rb), C.byref(v), C.byref(t))
+        if rc != 0:
+            raise ThermiteError(rc, _last_error())
+        return bytes(_copy(t.data, t.len, np.uint8))
+
+    def wrap_bam(self, result):
+        """thm_writer_wrap_bam: a BamResult (or anything with data / read_rec_off) -> complete BGZF blocks"""
+        data = _u8(result.data)
+        offs = np.ascontiguousarray(result.read_rec_off, "<u8")
+        v = BamView(len(offs) - 1, getattr(result, "n_records", 0), len(data), _ptr(data), _ptr(offs), 0, None)
+        t = Text()
+        rc = lib().thm_writer_wrap_bam(self.h, C.byref(v), C.byref(t))
         if rc != 0:
             raise ThermiteError(rc, _last_error())
         return bytes(_copy(t.data, t.len, np.uint8))

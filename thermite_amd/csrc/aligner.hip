@@ -220,7 +220,10 @@ void thm_aligner_free(thm_aligner* a) {
                  &a->e_nalns64, &a->e_opbytes, &a->e_aln_off, &a->e_ops_off, &a->e_trace, &a->o_alns, &a->o_ops, &a->o_mems,
                  &a->sh_bases, &a->sh_san, &a->sh_off, &a->sh_hits, &a->sh_read, &a->sh_bw, &a->sh_xd, &a->sh_list, &a->sh_out,
                  &a->sh_status, &a->sh_ops, &a->sh_ctl, &a->sh_trace, &a->sh_slow, &a->c_sums, &a->c_nwords, &a->c_woff,
-                 &a->c_scan_tmp, &a->c_flags, &a->c_dig, &a->c_words, &a->c_in_ops, &a->c_in_off};
+                 &a->c_scan_tmp, &a->c_flags, &a->c_dig, &a->c_words, &a->c_in_ops, &a->c_in_off,
+                 &a->bn_names, &a->bn_name_off, &a->bn_quals, &a->bt_tx_pool, &a->bt_tx_off, &a->bt_gid_pool, &a->bt_gid_off,
+                 &a->bt_gname_pool, &a->bt_gname_off, &a->bt_tx_gene, &a->bt_ref_sq, &a->bm_cnt, &a->bm_first, &a->bm_qn,
+                 &a->bm_rec_read, &a->bm_len, &a->bm_off, &a->bm_out, &a->bm_read_off, &a->bm_err, &a->bm_scan_tmp};
   for (DBuf* b : all) b->release();
   for (int k = 0; k < 2; k++) {
     a->r_off[k].release();
@@ -232,8 +235,13 @@ void thm_aligner_free(thm_aligner* a) {
     a->ch_dig[k].release();
     a->ch_words[k].release();
     a->ch_stat[k].release();
+    a->bh_data[k].release();
+    a->bh_off[k].release();
+    a->bh_stat[k].release();
   }
   for (auto& e : a->ev_cig)
+    if (e) (void)hipEventDestroy(e);
+  for (auto& e : a->ev_bam)
     if (e) (void)hipEventDestroy(e);
   for (auto& e : a->ev)
     if (e) (void)hipEventDestroy(e);

@@ -161,6 +161,18 @@ struct thm_aligner {
   hipEvent_t ev_cig[4] = {nullptr, nullptr, nullptr, nullptr};  // created by the first call
   std::vector<thm_aln_digest> h_cig_dig;
   std::vector<uint32_t> h_cig_words;
+  // BAM records on the device (bam.hip): names and qualities of the batch (thm_batch_upload_reads), the index's name
+  // tables (uploaded by the first thm_batch_fetch_bam), work arrays of the passes, the records, and two pinned host
+  // sets of their own, used alternately
+  DBuf bn_names, bn_name_off, bn_quals;
+  bool reads_named = false, reads_have_quals = false;  // thm_batch_upload clears reads_named
+  DBuf bt_tx_pool, bt_tx_off, bt_gid_pool, bt_gid_off, bt_gname_pool, bt_gname_off, bt_tx_gene, bt_ref_sq;
+  bool bam_tables = false;
+  DBuf bm_cnt, bm_first, bm_qn, bm_rec_read, bm_len, bm_off, bm_out, bm_read_off, bm_err, bm_scan_tmp;
+  HBuf bh_data[2], bh_off[2], bh_stat[2];
+  int b_cur = 0;
+  int bam_stage = -1;  // emit through LDS and dword stores (1) or byte stores (0); -1: not read from THM_BAM_EMIT yet
+  hipEvent_t ev_bam[4] = {nullptr, nullptr, nullptr, nullptr};  // created by the first call
 };
 
 inline int fail(thm_aligner* a, int code, const char* fmt, ...) {
@@ -182,6 +194,9 @@ inline int fail(thm_aligner* a, int code, const char* fmt, ...) {
                   #call, hipGetErrorString(e_), __FILE__, __LINE__);                                \
   } while (0)
 
+// cigar.hip: count -> scan -> emit over the streams of `p`; results in c_dig / c_words (synchronises the stream once)
+int run_cigar_passes(thm_aligner* a, thm::CigarParams p, uint64_t n_digests, uint64_t* n_words, unsigned* any_flags);
+int cigar_ensure_events(thm_aligner* a);
 int reset_queue(thm_aligner* a);
 int grid_blocks(const thm_aligner* a, uint64_t n_items, int waves_per_block, int blocks_per_cu);
 #endif

@@ -10,8 +10,6 @@
 
 using namespace thm;
 
-namespace {
-
 // count -> scan -> emit over `n_streams` streams of the pool `p.ops`; device results in c_dig / c_words, the number of
 // words and the flags met through *n_words / *any_flags (synchronises the stream once between the passes: the word pool
 // is sized by the count)
@@ -52,16 +50,18 @@ int run_cigar_passes(thm_aligner* a, CigarParams p, uint64_t n_digests, uint64_t
   return THM_OK;
 }
 
+int cigar_ensure_events(thm_aligner* a) {
+  for (auto& e : a->ev_cig)
+    if (!e) HIPCHK(a, hipEventCreate(&e));
+  return THM_OK;
+}
+
+namespace {
+
 void cigar_timing(thm_aligner* a) {  // after the stream has been synchronised
   float m1 = 0, m2 = 0;
   if (hipEventElapsedTime(&m1, a->ev_cig[0], a->ev_cig[1]) == hipSuccess && hipEventElapsedTime(&m2, a->ev_cig[2], a->ev_cig[3]) == hipSuccess)
     a->timings[THM_T_CIGAR] = m1 + m2;
-}
-
-int ensure_events(thm_aligner* a) {
-  for (auto& e : a->ev_cig)
-    if (!e) HIPCHK(a, hipEventCreate(&e));
-  return THM_OK;
 }
 
 }  // namespace
@@ -74,7 +74,7 @@ int32_t thm_batch_fetch_cigars(thm_aligner* a, thm_cigar_view* out) {
   int rc = thm_batch_sync(a);
   if (rc != THM_OK) return rc;
   HIPCHK(a, hipSetDevice(a->device));
-  rc = ensure_events(a);
+  rc = cigar_ensure_events(a);
   if (rc != THM_OK) return rc;
   const uint64_t n = a->n_reads;
   hipStream_t s = a->stream;
@@ -163,7 +163,7 @@ int32_t thm_cigar_encode_batch(thm_aligner* a, const uint8_t* ops, const uint64_
     if (off[i + 1] - off[i] >= (1ull << 32)) return fail(a, THM_ERR_UNSUPPORTED, "stream %llu has 2^32 bytes or more", (unsigned long long)i);
   }
   HIPCHK(a, hipSetDevice(a->device));
-  int rc = ensure_events(a);
+  int rc = cigar_ensure_events(a);
   if (rc != THM_OK) return rc;
   hipStream_t s = a->stream;
   // the pool is uploaded from off[0] on; the offsets travel relative to it

@@ -49,6 +49,7 @@ struct Slot {
   bool parsed = false;  // `reads` already holds the batch (sequential parser: FASTA, odd inputs)
   thm::HostBatch reads;
   thm_batch_view res;  // into the pinned result buffers of the aligner that ran it (two sets per aligner, used alternately)
+  thm_bam_view bam;    // ... or, with THM_BAM_DEVICE=1, the BAM records encoded on the device (likewise two sets)
   bool aligned = false;
 };
 
@@ -225,6 +226,9 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
   for (uint32_t i = 0; i < n_aligners; i++)
     if (!aligners[i]) return THM_ERR_INVALID_ARG;
   if (batch_reads == 0) batch_reads = 250000;
+  // THM_BAM_DEVICE=1: BAM records are encoded on the device (thm_batch_fetch_bam) and only deflated here
+  const char* bam_dev_env = getenv("THM_BAM_DEVICE");
+  const bool bam_device = format == THM_FMT_BAM && bam_dev_env && !strcmp(bam_dev_env, "1");
   const thm_index* ix = thm_aligner_index(aligners[0]);
   for (uint32_t i = 1; i < n_aligners; i++)
     if (thm_aligner_index(aligners[i]) != ix) {
@@ -511,7 +515,7 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
           const auto t0 = Clock::now();
           const thm_read_batch rb = s->reads.view();
           int grc = sh.step([&] {
-            int g2 = thm_batch_upload(a, rb.bases, rb.offsets, rb.n_reads);
+            int g2 = bam_device ? thm_batch_upload_reads(a, &rb) : thm_batch_upload(a, rb.bases, rb.offsets, rb.n_reads);
             if (g2 == THM_OK) g2 = thm_batch_run(a);
             if (g2 == THM_OK) g2 = thm_batch_sync(a);
             return g2;
@@ -524,17 +528,19 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
             done_cv.wait(g, [&] { return n_written > must || sh.failed(); });
           }
           const auto t2 = Clock::now();
-          if (grc == THM_OK) grc = sh.step([&] { return thm_batch_fetch(a, &s->res); });
-          if (grc == THM_OK && s->res.n_failed_reads) {
+          if (grc == THM_OK) grc = sh.step([&] { return bam_device ? thm_batch_fetch_bam(a, 0, &s->bam) : thm_batch_fetch(a, &s->res); });
+          const uint64_t n_res = bam_device ? s->bam.n_reads : s->res.n_reads;
+          const int32_t* res_status = bam_device ? s->bam.read_status : s->res.read_status;
+          if (grc == THM_OK && (bam_device ? s->bam.n_failed_reads : s->res.n_failed_reads)) {
             // the reference aligns every read or panics; a read this build cannot take fails the run, by name
             uint64_t bad = 0;
-            while (bad < s->res.n_reads && s->res.read_status[bad] == THM_OK) bad++;
+            while (bad < n_res && res_status[bad] == THM_OK) bad++;
             const thm_read_batch v = s->reads.view();
             std::string name((const char*)v.names + v.name_off[bad], (size_t)(v.name_off[bad + 1] - v.name_off[bad]));
-            sh.set(s->res.read_status[bad], "read " + name + (s->res.read_status[bad] == THM_ERR_UNSUPPORTED
-                                                                   ? ": longer than 65535 bases, or its DP trace exceeds the device-memory budget"
-                                                                   : ": hits a condition that panics in the reference (lift_mem_to_tx / lift_tx_to_gx)"));
-            grc = s->res.read_status[bad];
+            sh.set(res_status[bad], "read " + name + (res_status[bad] == THM_ERR_UNSUPPORTED
+                                                           ? ": longer than 65535 bases, or its DP trace exceeds the device-memory budget"
+                                                           : ": hits a condition that panics in the reference (lift_mem_to_tx / lift_tx_to_gx)"));
+            grc = res_status[bad];
           }
           if (grc != THM_OK) {
             sh.set(grc, thm_last_error(a));
@@ -546,7 +552,7 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
           std::lock_guard<std::mutex> g(st_mu);
           st.gpu_s += secs(t0, t1) + secs(t2, Clock::now());
           if (grc == THM_OK) {
-            st.n_reads += s->res.n_reads;
+            st.n_reads += n_res;
             st.n_batches += 1;
           }
         }
@@ -648,7 +654,10 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
         const thm_read_batch rb = s->reads.view();
         const thm_batch_view& v = s->res;
         WriteJob& j = jobs[k];
-        const int wrc = sh.step([&] { return thm::writer_format_chunks(ws[k], &rb, &v, j.chunks); });
+        const thm_bam_view& bv = s->bam;
+        const int wrc = sh.step([&] {
+          return bam_device ? thm::writer_wrap_bam_chunks(ws[k], &bv, j.chunks) : thm::writer_format_chunks(ws[k], &rb, &v, j.chunks);
+        });
         st.format_s += secs(t0, Clock::now());
         if (wrc != THM_OK) {
           sh.set(wrc, thm_last_error(nullptr));
@@ -659,10 +668,16 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
             file_off += j.chunks[c]->size();
             st.n_output_bytes += j.chunks[c]->size();
           }
-          for (uint64_t r = 0; r < v.n_reads; r++) {
-            const uint64_t kk = v.read_aln_off[r + 1] - v.read_aln_off[r];
-            st.n_aligned_reads += kk != 0;
-            st.n_records += kk ? kk : (format == THM_FMT_PAF ? 0 : 1);
+          if (bam_device) {
+            // a read is unmapped when its first record carries flag 4 (bytes 18 .. 19 of the record)
+            for (uint64_t r = 0; r < bv.n_reads; r++) st.n_aligned_reads += !(bv.data[bv.read_rec_off[r] + 18] & 4);
+            st.n_records += bv.n_records;
+          } else {
+            for (uint64_t r = 0; r < v.n_reads; r++) {
+              const uint64_t kk = v.read_aln_off[r + 1] - v.read_aln_off[r];
+              st.n_aligned_reads += kk != 0;
+              st.n_records += kk ? kk : (format == THM_FMT_PAF ? 0 : 1);
+            }
           }
           j.s = s;
           j.seq = next;

@@ -94,5 +94,12 @@ size_t deflate_block(const uint8_t* in, size_t n, uint8_t* out, DeflateScratch& 
 int writer_format_chunks(thm_writer* w, const thm_read_batch* reads, const thm_batch_view* res,
                          std::vector<const std::string*>& chunks);
 
+// thm_writer_wrap_bam without the final concatenation (chunks as above)
+int writer_wrap_bam_chunks(thm_writer* w, const thm_bam_view* view, std::vector<const std::string*>& chunks);
+
+// contig name_id -> index of its @SQ line (the BAM refID), build_sam_header's order (src/aln_writer.rs:256-276);
+// `sq`: the lines' (name, length), when asked for
+std::vector<int32_t> sq_of_name(const thm_index* ix, std::vector<std::pair<std::string, uint64_t>>* sq);
+
 }  // namespace thm
 #endif

@@ -809,6 +809,60 @@ int join_chunks(thm_writer* w, const std::vector<const std::string*>& chunks, th
 
 namespace thm {
 
+// build_sam_header (:256-276): the reference sequences are collected into a map keyed by name,
+// so the forward and reverse Ref of a contig share one @SQ line (first-seen order)
+std::vector<int32_t> sq_of_name(const thm_index* ix, std::vector<std::pair<std::string, uint64_t>>* sq_out) {
+  std::vector<std::pair<std::string, uint64_t>> sq;
+  std::vector<int32_t> of(ix->contig_names.size(), -1);
+  for (const thm_ref& r : ix->refs) {
+    if (r.name_id >= of.size() || of[r.name_id] >= 0) continue;
+    int32_t k = -1;
+    for (size_t i = 0; i < sq.size(); i++)
+      if (sq[i].first == ix->contig_names[r.name_id]) k = (int32_t)i;  // same name under another id: same @SQ
+    if (k < 0) {
+      k = (int32_t)sq.size();
+      sq.emplace_back(ix->contig_names[r.name_id], r.len);
+    }
+    of[r.name_id] = k;
+  }
+  if (sq_out) sq_out->swap(sq);
+  return of;
+}
+
+// the records of the view in the read ranges format_chunks cuts, each deflated into complete BGZF blocks by its thread
+int writer_wrap_bam_chunks(thm_writer* w, const thm_bam_view* v, std::vector<const std::string*>& chunks) {
+  chunks.clear();
+  if (!w || !v) return THM_ERR_INVALID_ARG;
+  if (w->format != THM_FMT_BAM) return fail(THM_ERR_INVALID_ARG, "thm_writer_wrap_bam: not a BAM writer");
+  const uint64_t n = v->n_reads;
+  if (!v->read_rec_off || (v->n_bytes && !v->data)) return fail(THM_ERR_INVALID_ARG, "thm_writer_wrap_bam: null data or offsets");
+  if (v->read_rec_off[0] != 0 || v->read_rec_off[n] != v->n_bytes)
+    return fail(THM_ERR_INVALID_ARG, "thm_writer_wrap_bam: read_rec_off does not run from 0 to n_bytes");
+  for (uint64_t r = 0; r < n; r++)
+    if (v->read_rec_off[r + 1] < v->read_rec_off[r]) return fail(THM_ERR_INVALID_ARG, "thm_writer_wrap_bam: read_rec_off descends");
+  const unsigned T = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(w->n_threads, (n + 4095) / 4096));
+  w->chunk.resize(std::max<size_t>(w->chunk.size(), T));
+  std::vector<char> ok(T, 1);
+  auto work = [&](unsigned t) {
+    std::string& s = w->chunk[t];
+    s.clear();
+    const uint64_t b0 = v->read_rec_off[n * t / T], b1 = v->read_rec_off[n * (t + 1) / T];
+    if (b1 > b0 && !bgzf_compress((const char*)v->data + b0, (size_t)(b1 - b0), s)) ok[t] = 0;
+  };
+  if (T == 1) {
+    work(0);
+  } else {
+    std::vector<std::thread> th;
+    for (unsigned t = 1; t < T; t++) th.emplace_back(work, t);
+    work(0);
+    for (auto& x : th) x.join();
+  }
+  for (unsigned t = 0; t < T; t++)
+    if (!ok[t]) return fail(THM_ERR_INTERNAL, "thm_writer_wrap_bam: BGZF compression failed");
+  for (unsigned t = 0; t < T; t++) chunks.push_back(&w->chunk[t]);
+  return THM_OK;
+}
+
 int writer_format_chunks(thm_writer* w, const thm_read_batch* reads, const thm_batch_view* res,
                          std::vector<const std::string*>& chunks) {
   chunks.clear();
@@ -837,21 +891,8 @@ int32_t thm_writer_create(const thm_index* ix, int32_t format, uint32_t n_thread
   unsigned t = n_threads ? n_threads : std::min(16u, std::thread::hardware_concurrency());
   w->n_threads = std::max(1u, std::min(t, 32u));
   if (format == THM_FMT_SAM || format == THM_FMT_BAM) {
-    // build_sam_header (:256-276): the reference sequences are collected into a map keyed by name,
-    // so the forward and reverse Ref of a contig share one @SQ line (first-seen order)
     std::vector<std::pair<std::string, uint64_t>> sq;
-    w->sq_of_name.assign(ix->contig_names.size(), -1);
-    for (const thm_ref& r : ix->refs) {
-      if (w->sq_of_name[r.name_id] >= 0) continue;
-      int32_t k = -1;
-      for (size_t i = 0; i < sq.size(); i++)
-        if (sq[i].first == ix->contig_names[r.name_id]) k = (int32_t)i;  // same name under another id: same @SQ
-      if (k < 0) {
-        k = (int32_t)sq.size();
-        sq.emplace_back(ix->contig_names[r.name_id], r.len);
-      }
-      w->sq_of_name[r.name_id] = k;
-    }
+    w->sq_of_name = thm::sq_of_name(ix, &sq);
     std::string text;
     for (const auto& q : sq) text += "@SQ\tSN:" + q.first + "\tLN:" + std::to_string(q.second) + "\n";
     text += "@PG\tID:thermite\n";
@@ -899,6 +940,16 @@ int32_t thm_writer_format_batch(thm_writer* w, const thm_read_batch* reads, cons
   if (!out) return THM_ERR_INVALID_ARG;
   std::vector<const std::string*> chunks;
   const int rc = thm::writer_format_chunks(w, reads, res, chunks);
+  if (rc != THM_OK) return rc;
+  return join_chunks(w, chunks, out);
+}
+
+int32_t thm_writer_wrap_bam(thm_writer* w, const thm_bam_view* view, thm_text* out) {
+  if (!out) return THM_ERR_INVALID_ARG;
+  out->data = nullptr;
+  out->len = 0;
+  std::vector<const std::string*> chunks;
+  const int rc = thm::writer_wrap_bam_chunks(w, view, chunks);
   if (rc != THM_OK) return rc;
   return join_chunks(w, chunks, out);
 }

@@ -556,5 +556,47 @@ struct CigarParams {
 hipError_t launch_cigar_count(const CigarParams& p, int n_cu, hipStream_t s);
 hipError_t launch_cigar_emit(const CigarParams& p, int n_cu, hipStream_t s);
 
+// ---- BAM records on the device (kernels_bam.hip; host side bam.hip) ----
+// prep (per read: record count, QNAME length) -> scan -> size (per record: its read, its bytes) -> scan -> emit (one
+// wavefront per record) -> offsets (per read: first byte).  `err` collects the conditions that fail the call.
+constexpr uint32_t THM_BAM_FLAG_NO_ANNOTATION = 1u;  // THM_BAM_NO_ANNOTATION_TAGS, include/thermite_io.h
+constexpr unsigned BAM_ERR_QNAME = 1u, BAM_ERR_CIGAR_WORDS = 2u, BAM_ERR_DIGEST_FLAGS = 4u, BAM_ERR_RANGE = 8u;
+struct BamParams {
+  uint64_t n_reads, n_rec;
+  uint32_t flags;
+  uint32_t n_refs, n_txs, n_genes;
+  // the batch: raw reads, qualities (null: none), names
+  const uint8_t* bases;
+  const uint64_t* offsets;
+  const uint8_t* quals;
+  const uint8_t* names;
+  const uint64_t* name_off;
+  // the run: compacted records, their digests and CIGAR words
+  const uint64_t* aln_off;
+  const thm_aln* alns;
+  const thm_aln_digest* digests;
+  const uint32_t* words;
+  uint64_t n_words;
+  // the index's names: string pools with offsets, gene of every transcript, @SQ index (BAM refID) of every ref
+  const uint8_t *tx_pool, *gid_pool, *gname_pool;
+  const uint32_t *tx_off, *gid_off, *gname_off;
+  const uint32_t* tx_gene;
+  const int32_t* ref_sq;
+  // work and results
+  uint64_t* rec_cnt;          // [n_reads]      prep
+  const uint64_t* rec_first;  // [n_reads + 1]  scan of rec_cnt
+  uint32_t* qn;               // [n_reads]      prep
+  uint32_t* rec_read;         // [n_rec]        size
+  uint64_t* rec_len;          // [n_rec]        size
+  const uint64_t* rec_off;    // [n_rec + 1]    scan of rec_len
+  uint8_t* out;               // [rec_off[n_rec]]
+  uint64_t* read_rec_off;     // [n_reads + 1]
+  unsigned int* err;
+};
+hipError_t launch_bam_prep(const BamParams& p, hipStream_t s);
+hipError_t launch_bam_size(const BamParams& p, hipStream_t s);
+hipError_t launch_bam_emit(const BamParams& p, bool stage, int n_cu, hipStream_t s);
+hipError_t launch_bam_offsets(const BamParams& p, hipStream_t s);
+
 }  // namespace thm
 #endif

@@ -627,6 +627,7 @@ int32_t thm_batch_upload(thm_aligner* a, const uint8_t* bases, const uint64_t* o
   if (!a || !offsets || (!bases && n_reads && offsets[n_reads] > 0)) return THM_ERR_INVALID_ARG;
   HIPCHK(a, hipSetDevice(a->device));
   a->uploaded = a->ran = a->synced = false;
+  a->reads_named = false;  // (thm_batch_upload_reads sets it)
   if (n_reads >= 0xFFFFFFF0ull) return fail(a, THM_ERR_UNSUPPORTED, "more than 2^32-16 reads in one batch");
   if (offsets[0] != 0) return fail(a, THM_ERR_INVALID_ARG, "offsets[0] must be 0");
   // the lengths present in the batch (usually one or a handful): histogram by sorting the distinct ones

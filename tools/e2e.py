@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """End-to-end file throughput on the GPU box (tuning aid, not the benchmark):
-FASTQ on disk -> thm_align_files -> SAM / PAF.   python tools_e2e.py [ref_len] [n_reads] [threads]"""
+FASTQ on disk -> thm_align_files -> SAM / PAF.   python tools_e2e.py [ref_len] [n_reads] [threads] [rep]
+--bam-device[=RUNS]: only FASTQ -> BAM and .fastq.gz -> BAM, each RUNS times (default 4) with THM_BAM_DEVICE off and on
+in turn (the driver reads the switch at every call), in one session."""
 import os, sys, time
+BAM_RUNS = 0
+for arg in list(sys.argv[1:]):
+    if arg.startswith("--bam-device"):
+        BAM_RUNS = int(arg.split("=")[1]) if "=" in arg else 4
+        sys.argv.remove(arg)
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from thermite_amd import capi, synth
@@ -39,7 +46,7 @@ with open(big, "wb") as f:
         f.write(one)
     del one
 print("plain input: %d reads, %.1f MB" % (n * REP, os.path.getsize(big) / 1e6), flush=True)
-for fmt, name in ((capi.FMT_SAM, "sam"), (capi.FMT_PAF, "paf")):
+for fmt, name in (() if BAM_RUNS else ((capi.FMT_SAM, "sam"), (capi.FMT_PAF, "paf"))):
     for rep in range(2):
         out = "/tmp/thm_e2e_out.%s" % name
         st = capi.align_files(a, [big], out, fmt, batch_reads=250000, n_threads=threads)
@@ -81,17 +88,35 @@ def digest(path):
     return h.hexdigest()
 
 
-paf_of_plain = digest("/tmp/thm_e2e_out.paf")  # (the last plain run wrote PAF of the REP-copy file)
+paf_of_plain = None if BAM_RUNS else digest("/tmp/thm_e2e_out.paf")  # (the last plain run wrote PAF of the REP-copy file)
 
 
-def run(tag, paths, fmt, out):
-    for rep in range(2):
+def run(tag, paths, fmt, out, reps=2):
+    for rep in range(reps):
         st = capi.align_files(a, paths, out, fmt, batch_reads=250000, n_threads=threads)
         print("%s run %d: %.2f Mreads/s wall %.2fs | parse+inflate %.2fs gpu %.2fs format %.2fs write %.2fs | %.0f MB out" % (
             tag, rep, st["n_reads"] / st["wall_s"] / 1e6, st["wall_s"], st["parse_s"], st["gpu_s"], st["format_s"], st["write_s"],
             st["n_output_bytes"] / 1e6), flush=True)
 
 
+if BAM_RUNS:
+    os.environ.pop("THM_BAM_DEVICE", None)
+    run("warm-up: bam from plain fastq, host encoder", [big], capi.FMT_BAM, "/tmp/thm_e2e_out.bam", 1)
+    sums = {}
+    for k in range(BAM_RUNS):
+        for dev in ("0", "1"):
+            os.environ["THM_BAM_DEVICE"] = dev
+            what = "device encoder" if dev == "1" else "host encoder"
+            run("bam from plain fastq, %s, round %d" % (what, k), [big], capi.FMT_BAM, "/tmp/thm_e2e_out.%s.bam" % dev, 1)
+            run("bam from two .gz, %s, round %d" % (what, k), [gz, gz2], capi.FMT_BAM, "/tmp/thm_e2e_out.gz%s.bam" % dev, 1)
+    same = digest("/tmp/thm_e2e_out.0.bam") == digest("/tmp/thm_e2e_out.1.bam") and digest("/tmp/thm_e2e_out.gz0.bam") == digest("/tmp/thm_e2e_out.gz1.bam")
+    print("BAM files of the two encoders are %s" % ("IDENTICAL" if same else "DIFFERENT"), flush=True)
+    a.close()
+    for f in (path, big, gz, gz2, "/tmp/thm_e2e_out.bam", "/tmp/thm_e2e_out.0.bam", "/tmp/thm_e2e_out.1.bam", "/tmp/thm_e2e_out.gz0.bam", "/tmp/thm_e2e_out.gz1.bam"):
+        if os.path.exists(f):
+            os.remove(f)
+    assert same
+    sys.exit(0)
 run("paf from one .gz", [gz], capi.FMT_PAF, "/tmp/thm_e2e_out.paf")
 # the .gz holds the same records as the plain file (REP members of the same reads): same PAF, byte for byte
 same = digest("/tmp/thm_e2e_out.paf") == paf_of_plain

@@ -1,15 +1,21 @@
 #!/usr/bin/env python3
 """Quick stage timing on the GPU box (tuning aid, not the benchmark):
-python tools/perf.py [ref_len] [n_reads] [opts] [--cigars]
+python tools/perf.py [ref_len] [n_reads] [opts] [--cigars] [--bam]
 --cigars: on the resident batch, thm_batch_fetch against thm_batch_fetch_cigars -- milliseconds and bytes moved to the
-host by each, and the device time of the two CIGAR passes (THM_T_CIGAR)."""
+host by each, and the device time of the two CIGAR passes (THM_T_CIGAR).
+--bam: on the resident batch, thm_batch_fetch_bam with both forms of the emit kernel (THM_BAM_EMIT) -- milliseconds,
+bytes, THM_T_BAM -- beside thm_batch_fetch plus the host's record encoding of the same batch (thm_writer_format_batch
+at THM_BAM_LEVEL=0 minus thm_writer_wrap_bam of the same records: stored blocks, so the difference is the encoding)."""
 import sys, time
 import numpy as np
 sys.path.insert(0, __import__("os").path.dirname(__import__("os").path.dirname(__import__("os").path.abspath(__file__))))
 from thermite_amd import capi, synth
 
 cigars = "--cigars" in sys.argv
-sys.argv = [x for x in sys.argv if x != "--cigars"]
+bam = "--bam" in sys.argv
+sys.argv = [x for x in sys.argv if x not in ("--cigars", "--bam")]
+if bam:
+    __import__("os").environ["THM_BAM_LEVEL"] = "0"  # (read once, by the first BGZF block of the process)
 ref_len = int(sys.argv[1]) if len(sys.argv) > 1 else 4000000
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 500000
 which = sys.argv[3] if len(sys.argv) > 3 else "both"
@@ -52,6 +58,53 @@ for name, opts in (("ci", capi.CI_OPTS), ("default", capi.DEFAULT_OPTS)):
             extra = "" if nm == "fetch" else "  words %d  THM_T_CIGAR %.3f ms" % (len(r.cigar), a.timings()["cigar"])
             print("         %-12s median %.2f ms (min %.2f max %.2f, %d calls)  %d bytes to the host  alns %d%s" % (
                 nm, float(np.median(ms)), min(ms), max(ms), K2, nbytes, len(r.alns), extra), flush=True)
+    if bam:
+        import os
+        K2 = 7
+        names = [b"SYN:%d 1:N:0:ACGT" % i for i in range(n)]
+        batch = dict(bases=bases, offsets=off, quals=np.full(len(bases), ord("F"), np.uint8), names=np.frombuffer(b"".join(names), np.uint8),
+                     name_off=np.cumsum([0] + [len(x) for x in names]).astype("<u8"))
+
+        def med(f):
+            ms = []
+            for _ in range(K2):
+                t0 = time.perf_counter()
+                r = f()
+                ms.append((time.perf_counter() - t0) * 1e3)
+            return r, float(np.median(ms)), min(ms), max(ms)
+
+        recs = None
+        for form in ("bytes", "dwords", "bytes", "dwords"):   # first round: buffers grow
+            os.environ["THM_BAM_EMIT"] = form
+            b = capi.Aligner(ix, opts)
+            b.upload_reads(batch)
+            b.run(); b.sync()
+            b.fetch_bam(copy=False)
+            tb = []
+            for _ in range(K2):
+                b.fetch_bam(copy=False)
+                tb.append(b.timings()["bam"])
+            g, m, lo, hi = med(lambda: b.fetch_bam(copy=False))
+            print("         fetch_bam[%-6s] median %.2f ms (min %.2f max %.2f)  %d bytes to the host  records %d  THM_T_BAM median %.3f ms (min %.3f max %.3f)" % (
+                form, m, lo, hi, g.nbytes, g.n_records, float(np.median(tb)), min(tb), max(tb)), flush=True)
+            recs = capi.BamResult.__new__(capi.BamResult)
+            recs.data, recs.read_rec_off, recs.n_records = g.data.copy(), g.read_rec_off.copy(), g.n_records
+            f, m, lo, hi = med(lambda: b.fetch(copy=False))
+            full = (f.offsets.copy(), f.alns.copy(), f.ops.copy())
+            print("         fetch          median %.2f ms (min %.2f max %.2f)  %d bytes to the host" % (m, lo, hi, sum(x.nbytes for x in full)), flush=True)
+            b.close()
+        os.environ.pop("THM_BAM_EMIT", None)
+        res = capi.BatchResult.__new__(capi.BatchResult)
+        res.offsets, res.alns, res.ops = full
+        for threads in (16, 1):
+            w = capi.Writer(ix, capi.FMT_BAM, n_threads=threads)
+            w.format_batch(batch, res)
+            o1, m1, lo1, hi1 = med(lambda: w.format_batch(batch, res))
+            o2, m2, lo2, hi2 = med(lambda: w.wrap_bam(recs))
+            print("         host, %2d threads: format_batch (encode + stored blocks) median %.2f ms (min %.2f max %.2f); wrap_bam (stored blocks only) "
+                  "median %.2f ms (min %.2f max %.2f); encoding = %.2f ms; outputs %s" % (threads, m1, lo1, hi1, m2, lo2, hi2, m1 - m2,
+                                                                                         "equal" if o1 == o2 else "DIFFER"), flush=True)
+            w.close()
     c = dict(zip(capi.COUNTER_NAMES, a.counters().tolist()))
     runs = K + 2
     print("         per read: smems %.2f hits %.2f swg_calls %.2f cols %.1f cells %.0f alns %.2f win_bytes %.0f" % tuple(
