@@ -103,6 +103,12 @@ def check_smems(w, bases, off, k):
     a.close()
 
 
+def assert_counters_match(c, rc, what=""):
+    """device counters against the oracle's after one batch"""
+    assert np.array_equal(c[:10], rc[:10]) and c[12] == rc[12] and c[13] == rc[13], (what, c[:14], rc[:14])
+    assert c[10] <= rc[10] and c[11] <= rc[11], (what, c[:14], rc[:14])  # DP work: exact early exit computes fewer cells
+
+
 def check_align(w, bases, off, opts, n_threads=8, pool_caps=None, ref=None):
     """Both device paths against the oracle: the problem-parallel path (kernels_tpr.hip: thread-per-read control
     kernel + wave-per-request DP kernel; what it leaves goes to the wave-per-read kernels) and the wave-per-read
@@ -121,9 +127,7 @@ def check_align(w, bases, off, opts, n_threads=8, pool_caps=None, ref=None):
             assert a.debug_set_pool_caps() > replays, "the small pools did not overflow: %r" % (pool_caps,)
         assert g.n_failed == 0 and g.status is None
         assert_batch_equal(g, r)
-        c = a.counters()
-        assert np.array_equal(c[:10], r.counters[:10]) and c[12] == r.counters[12] and c[13] == r.counters[13], (no_tpr, c[:14], r.counters[:14])
-        assert c[10] <= r.counters[10] and c[11] <= r.counters[11], (no_tpr, c[:14], r.counters[:14])  # DP work: exact early exit computes fewer cells
+        assert_counters_match(a.counters(), r.counters, no_tpr)
         a.close()
     return g
 

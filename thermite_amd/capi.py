@@ -313,6 +313,9 @@ def lib():
         L.thm_debug_set_band_clip.argtypes = [vp, C.c_uint32]
         L.thm_debug_tpr_stats.restype = i32
         L.thm_debug_tpr_stats.argtypes = [vp, vp]
+    if hasattr(L, "thm_debug_knobs"):
+        L.thm_debug_knobs.restype = i32
+        L.thm_debug_knobs.argtypes = [vp, vp]
     if hasattr(L, "thm_debug_calib_gather"):
         L.thm_debug_calib_gather.restype = i32
         L.thm_debug_calib_gather.argtypes = [vp, i32, u64, vp]
@@ -767,6 +770,12 @@ class Aligner:
         self._chk(lib().thm_debug_tpr_stats(self.h, _ptr(out)))
         return out
 
+    def debug_knobs(self):
+        """what the run-time knobs resolved to in this process: the 16 words of thm_debug_knobs (knobs_dict names them)"""
+        out = np.zeros(16, "<u4")
+        self._chk(lib().thm_debug_knobs(self.h, _ptr(out)))
+        return out
+
     def debug_calib_gather(self, pattern, n_threads):
         """profiling hook: a gather of known size (see tools/calib_fetch.py); returns the bytes requested"""
         b = C.c_uint64()
@@ -786,6 +795,17 @@ class Aligner:
 
     def __del__(self):
         self.close()
+
+
+KNOB_NAMES = {0: "seed_fill", 1: "compact_k", 2: "hit_gl", 11: "team_div_per_cu", 12: "swg_bpc", 13: "use_tpr", 14: "tpr_rounds",
+              15: "n_cu"}
+
+
+def knobs_dict(raw):
+    """the 16 words of thm_debug_knobs by name"""
+    d = {name: int(raw[i]) for i, name in KNOB_NAMES.items()}
+    d["ext_minw"] = {(cpl, bool(wide)): int(raw[3 + 2 * (cpl - 1) + wide]) for cpl in (1, 2, 3, 4) for wide in (0, 1)}
+    return d
 
 
 def comm_unique_id():

@@ -24,6 +24,16 @@ const char* global_error_cstr();
 }
 using namespace thm;
 
+// tuning knob THM_SWG_BPC = 1..8: resident workgroups per CU of swg_batch_kernel
+static int swg_blocks_per_cu() {
+  static const int v = [] {
+    const char* e = getenv("THM_SWG_BPC");
+    const int v = e ? atoi(e) : 4;
+    return (v >= 1 && v <= 8) ? v : 4;
+  }();
+  return v;
+}
+
 template <class T>
 static hipError_t upload(DBuf& b, const std::vector<T>& v, hipStream_t s) {
   size_t bytes = std::max<size_t>(v.size() * sizeof(T), 16);
@@ -363,11 +373,7 @@ int32_t thm_swg_extend_batch(thm_aligner* a, const uint8_t* x_bases, const uint6
   p.queue = a->d_queue.as<unsigned int>();
   p.fault = a->d_fault.as<int>();
   p.n = n;
-  static const int bpc = [] {  // tuning knob: resident workgroups per CU
-    const char* e = getenv("THM_SWG_BPC");
-    const int v = e ? atoi(e) : 4;
-    return (v >= 1 && v <= 8) ? v : 4;
-  }();
+  const int bpc = swg_blocks_per_cu();
   int n_blocks = grid_blocks(a, n, 4, bpc);
   if (cpl == 0) {
     p.scratch_per_wave = (swg_batch_scratch_bytes(p) + 255) & ~255ull;
@@ -584,6 +590,25 @@ int32_t thm_debug_tpr_stats(thm_aligner* a, uint64_t stats[32]) {
   stats[17] = c[TPRC_Q_CUR];  // class 0: thread-per-problem kernel
   for (int k = 0; k < 4; k++) stats[18 + k] = c[TPRC_Q_CUR + 1 + k];
   stats[22] = c[TPRC_N_ACT + a->tpr_rounds + 1];
+  return THM_OK;
+}
+// test hook: what the run-time knobs of INTEGRATION.md section 6 resolved to in this process, as the launches will use
+// them -- [0] THM_SEED_FILL mode, [1] THM_COMPACT_K, [2] THM_HIT_GL lanes per hit, [3 + 2 * (cpl - 1) + wide] waves per
+// SIMD of the wave-per-read extend kernel for cpl = 1..4 cells per lane and 32- / 64-bit coordinates (THM_EXT_MINW,
+// THM_EXT_MINW_CPL3, THM_EXT_MINW_WIDE), [11] THM_TEAM_DIV_PER_CU, [12] THM_SWG_BPC, [13] this aligner's use_tpr,
+// [14] its tpr_rounds, [15] its n_cu
+int32_t thm_debug_knobs(thm_aligner* a, uint32_t out[16]) {
+  if (!a || !out) return THM_ERR_INVALID_ARG;
+  out[0] = seed_fill_mode();
+  out[1] = (uint32_t)compact_k();
+  out[2] = (uint32_t)hit_gl();
+  for (int cpl = 1; cpl <= 4; cpl++)
+    for (int wide = 0; wide < 2; wide++) out[3 + 2 * (cpl - 1) + wide] = (uint32_t)extend_waves_per_simd(cpl, wide != 0);
+  out[11] = team_div_per_cu();
+  out[12] = (uint32_t)swg_blocks_per_cu();
+  out[13] = a->use_tpr ? 1u : 0u;
+  out[14] = (uint32_t)a->tpr_rounds;
+  out[15] = (uint32_t)a->n_cu;
   return THM_OK;
 }
 

@@ -199,4 +199,7 @@ int run_cigar_passes(thm_aligner* a, thm::CigarParams p, uint64_t n_digests, uin
 int cigar_ensure_events(thm_aligner* a);
 int reset_queue(thm_aligner* a);
 int grid_blocks(const thm_aligner* a, uint64_t n_items, int waves_per_block, int blocks_per_cu);
+// pipeline.hip: what THM_SEED_FILL and THM_TEAM_DIV_PER_CU resolved to (read once per process)
+uint32_t seed_fill_mode();
+unsigned team_div_per_cu();
 #endif

@@ -2372,28 +2372,40 @@ constexpr int EXT_MINW_CPL34 = 4;  // default register budget of the three- and 
 // waves per SIMD the wave-per-read kernel chosen for (cpl, coordinate width) is compiled for = workgroups of 4 waves
 // that fit a CU; the host launches no more than that (a workgroup beyond it starts when the first ones leave, finds
 // the work counters dry and only delays the end of the launch)
-int extend_waves_per_simd(int cpl, bool wide) {
-  static const int minw_env = [] {
+static int ext_minw_env() {  // THM_EXT_MINW = 4..8 (0: unset); which of them a kernel has: extend_waves_per_simd
+  static const int v = [] {
     const char* e = getenv("THM_EXT_MINW");
     const int v = e ? atoi(e) : 0;
     return (v >= 4 && v <= 8) ? v : 0;
   }();
+  return v;
+}
+static int ext_minw_cpl3_env() {  // THM_EXT_MINW_CPL3 = 3 | 4 | 5 | 6 (0: unset)
+  static const int v = [] {
+    const char* e = getenv("THM_EXT_MINW_CPL3");
+    const int v = e ? atoi(e) : 0;
+    return (v >= 3 && v <= 6) ? v : 0;
+  }();
+  return v;
+}
+static int ext_minw_wide_env() {  // THM_EXT_MINW_WIDE = 4 | 5 (0: unset)
+  static const int v = [] {
+    const char* e = getenv("THM_EXT_MINW_WIDE");
+    const int v = e ? atoi(e) : 0;
+    return (v == 4 || v == 5) ? v : 0;
+  }();
+  return v;
+}
+int extend_waves_per_simd(int cpl, bool wide) {
+  const int minw_env = ext_minw_env();
   if (cpl == 0) return 2;
   if (cpl > 2) {
     // three and four cells per lane (bands beyond +-63: BASELINE config 5's +-64): tuning knob THM_EXT_MINW_CPL3 = 3 | 4 | 5 | 6
-    static const int v34 = [] {
-      const char* e = getenv("THM_EXT_MINW_CPL3");
-      const int v = e ? atoi(e) : 0;
-      return (v >= 3 && v <= 6) ? v : 0;
-    }();
+    const int v34 = ext_minw_cpl3_env();
     return (v34 && !wide) ? v34 : EXT_MINW_CPL34;
   }
   if (wide) {
-    static const int wide_env = [] {
-      const char* e = getenv("THM_EXT_MINW_WIDE");
-      const int v = e ? atoi(e) : 0;
-      return (v == 4 || v == 5) ? v : 0;
-    }();
+    const int wide_env = ext_minw_wide_env();
     return wide_env ? wide_env : 5;
   }
   if (minw_env) {
@@ -2479,6 +2491,16 @@ hipError_t launch_counters_reduce(const unsigned long long* wave_counters, uint3
   return hipGetLastError();
 }
 
+// reads in flight per 16-lane group of the compact kernel: 2 unless THM_COMPACT_K = 1 | 4 says otherwise (tuning)
+int compact_k() {
+  static const int v = [] {
+    const char* e = getenv("THM_COMPACT_K");
+    const int v = e ? atoi(e) : 2;
+    return v == 1 || v == 2 || v == 4 ? v : 2;
+  }();
+  return v;
+}
+
 hipError_t launch_compact(const CompactParams& p, hipStream_t s) {
   static const unsigned n_cu = [] {
     int dev = 0, cu = 256;
@@ -2488,11 +2510,7 @@ hipError_t launch_compact(const CompactParams& p, hipStream_t s) {
   // 8 workgroups of 256 threads fill a CU's wave slots
   const unsigned blocks = (unsigned)std::min<uint64_t>((p.n_reads + 15) / 16, (uint64_t)n_cu * 8);
   if (blocks == 0) return hipSuccess;
-  static const int k_reads = [] {
-    const char* e = getenv("THM_COMPACT_K");
-    const int v = e ? atoi(e) : 2;
-    return v == 1 || v == 2 || v == 4 ? v : 2;
-  }();
+  const int k_reads = compact_k();
   if (k_reads == 1)
     hipLaunchKernelGGL(dev::compact_kernel<1>, dim3(blocks), dim3(256), 0, s, p);
   else if (k_reads == 2)

@@ -510,7 +510,7 @@ hipError_t launch_hit_summaries_gl(const HitParamsT<uint64_t>& p, int n_blocks, 
   hipError_t launch_hit_summaries_gl##n(const HitParamsT<uint32_t>& p, int n_blocks, hipStream_t s); \
   hipError_t launch_hit_summaries_gl##n(const HitParamsT<uint64_t>& p, int n_blocks, hipStream_t s);
 HIT_DECL(1) HIT_DECL(2) HIT_DECL(8)
-static int hit_gl() {
+int hit_gl() {
   static const int v = [] {
     const char* e = getenv("THM_HIT_GL");
     const int x = e ? atoi(e) : 0;

@@ -282,6 +282,8 @@ struct ExtendParamsT {
 };
 size_t extend_lds_bytes(uint32_t max_read_len, uint32_t max_bw, int cpl);
 int extend_waves_per_simd(int cpl, bool wide);
+int compact_k();  // compact_kernel<K> that launch_compact runs (THM_COMPACT_K)
+int hit_gl();     // lanes per hit of the hit-summary kernel that launch_hit_summaries runs (THM_HIT_GL)
 size_t extend_trace_scratch_bytes(uint32_t max_read_len, uint32_t max_bw, int cpl);
 size_t extend_slow_scratch_bytes(uint32_t max_read_len, uint32_t max_bw, uint32_t mk_cap);  // per wave
 constexpr size_t EXTEND_LDS_LIMIT = 160 * 1024;  // gfx950: one workgroup may take the whole LDS of its CU

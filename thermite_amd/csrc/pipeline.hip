@@ -24,6 +24,25 @@
 
 using namespace thm;
 
+// THM_SEED_FILL = 0 | 1 | 2: which form of the seed kernels' fill pass runs (launch_seed)
+uint32_t seed_fill_mode() {
+  static const uint32_t v = [] {
+    const char* e = getenv("THM_SEED_FILL");
+    const int v = e ? atoi(e) : 0;
+    return (uint32_t)(v >= 0 && v <= 2 ? v : 0);
+  }();
+  return v;
+}
+// THM_TEAM_DIV_PER_CU (tuning knob): TEAM_DIV_PER_CU of the plan kernel's team threshold (launch.h)
+unsigned team_div_per_cu() {
+  static const unsigned v = [] {
+    const char* e = getenv("THM_TEAM_DIV_PER_CU");
+    const int v = e ? atoi(e) : 0;
+    return v > 0 ? (unsigned)v : TEAM_DIV_PER_CU;
+  }();
+  return v;
+}
+
 namespace {
 
 // bw0(L) of reference src/aligner.rs:130-138; non-decreasing in L
@@ -137,11 +156,7 @@ int enqueue_seed_t(thm_aligner* a, uint32_t min_seed_len) {
   sp.fault = a->d_fault.as<int>();
   sp.sel_scratch = nullptr;
   sp.sel_scratch_per_wave = 0;
-  static const uint32_t fill_mode = [] {
-    const char* e = getenv("THM_SEED_FILL");
-    const int v = e ? atoi(e) : 0;
-    return (uint32_t)(v >= 0 && v <= 2 ? v : 0);
-  }();
+  const uint32_t fill_mode = seed_fill_mode();
   sp.fill_mode = fill_mode;
   sp.fill_keys = nullptr;
   sp.fill_perm = nullptr;
@@ -533,14 +548,7 @@ int enqueue_run(thm_aligner* a) {
     pp.team_ok = (cpl_f <= 2 && team_fits_lds(extend_lds_bytes(cls.fast_len, cls.fast_bw, cpl_f))) ? 1u : 0u;
   }
   pp.total_hits = a->s_cand_off.as<uint64_t>() + n;
-  {
-    static const unsigned div_env = [] {
-      const char* e = getenv("THM_TEAM_DIV_PER_CU");  // tuning knob
-      const int v = e ? atoi(e) : 0;
-      return v > 0 ? (unsigned)v : TEAM_DIV_PER_CU;
-    }();
-    pp.team_div = div_env * (uint32_t)std::max(a->n_cu, 1);
-  }
+  pp.team_div = team_div_per_cu() * (uint32_t)std::max(a->n_cu, 1);
   pp.tpr_max_hits = (a->use_tpr && std::max(1, (int)((2 * cls.fast_bw + 1 + 63) / 64)) <= 4) ? TPR_MAX_HITS : 0u;
   pp.counts = a->s_work_counts.as<unsigned long long>();
   pp.read_status = a->r_status.as<int32_t>();
