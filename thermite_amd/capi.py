@@ -313,6 +313,9 @@ def lib():
         L.thm_debug_set_band_clip.argtypes = [vp, C.c_uint32]
         L.thm_debug_tpr_stats.restype = i32
         L.thm_debug_tpr_stats.argtypes = [vp, vp]
+    if hasattr(L, "thm_debug_seed_stats"):
+        L.thm_debug_seed_stats.restype = i32
+        L.thm_debug_seed_stats.argtypes = [vp, vp]
     if hasattr(L, "thm_debug_knobs"):
         L.thm_debug_knobs.restype = i32
         L.thm_debug_knobs.argtypes = [vp, vp]
@@ -755,10 +758,21 @@ class Aligner:
         self._chk(lib().thm_debug_set_pool_caps(self.h, smem_cap, cand_cap, ops_cap, C.byref(n)))
         return n.value
 
-    def debug_set_flags(self, tpr=None, rounds=0):
+    def debug_set_flags(self, tpr=None, rounds=0, seed_infer=None, seed_stats=None):
         """test / tuning hook: tpr = False: every read takes the wave-per-read kernels, True: the problem-parallel path
-        in front of them (None: keep); rounds = its request rounds (1..8, 0: keep)"""
-        self._chk(lib().thm_debug_set_flags(self.h, (0 if tpr is None else (2 if tpr else 1)) | (int(rounds) << 8)))
+        in front of them (None: keep); rounds = its request rounds (1..8, 0: keep); seed_infer = False: no seed probe
+        is decided from its table entry and a neighbouring match (bit 2 of the word; True: bit 4, on again);
+        seed_stats = True: the seed kernels count their probes for debug_seed_stats (bit 3; False: bit 5).  None: keep."""
+        word = (0 if tpr is None else (2 if tpr else 1)) | (int(rounds) << 8)
+        word |= 0 if seed_infer is None else (16 if seed_infer else 4)
+        word |= 0 if seed_stats is None else (8 if seed_stats else 32)
+        self._chk(lib().thm_debug_set_flags(self.h, word))
+
+    def debug_seed_stats(self):
+        """the last batch's seed probes (thm_debug_seed_stats): (decided from the table entry alone, run in full)"""
+        out = np.zeros(2, "<u8")
+        self._chk(lib().thm_debug_seed_stats(self.h, _ptr(out)))
+        return int(out[0]), int(out[1])
 
     def debug_set_band_clip(self, max_bw=None):
         """test hook: the register-resident kernels pretend to hold bands up to max_bw only (None: off)"""

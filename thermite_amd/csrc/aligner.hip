@@ -567,6 +567,24 @@ int32_t thm_debug_set_flags(thm_aligner* a, uint32_t flags) {
   if (flags & 2u) a->use_tpr = true;
   const int r = (int)((flags >> 8) & 15u);
   if (r >= 1 && r <= TPR_MAX_ROUNDS) a->tpr_rounds = r;
+  // bit 2: the seed probes are never decided from the table entry and a neighbouring match, and store every interval
+  // (kernels_seed.hip; for A/B runs), bit 4: they are again; bit 3: the seed kernels count their probes for
+  // thm_debug_seed_stats, bit 5: they stop counting.  Neither bit of a pair: keep, as with bits 0 and 1.
+  if (flags & 4u) a->dbg_seed_noinfer = true;
+  if (flags & 16u) a->dbg_seed_noinfer = false;
+  if (flags & 8u) a->dbg_seed_stats = true;
+  if (flags & 32u) a->dbg_seed_stats = false;
+  return THM_OK;
+}
+// thm_debug_seed_stats: the last batch's seed stage, counted when bit 3 of thm_debug_set_flags is set (else zeros) --
+// [0] probes decided from the k-mer table entry alone, [1] probes run in full (position 0 of every read included)
+int32_t thm_debug_seed_stats(thm_aligner* a, uint64_t stats[2]) {
+  if (!a || !stats) return THM_ERR_INVALID_ARG;
+  stats[0] = stats[1] = 0;
+  if (!a->s_work_counts.p || a->s_work_counts.cap < 128) return THM_OK;
+  HIPCHK(a, hipSetDevice(a->device));
+  HIPCHK(a, hipStreamSynchronize(a->stream));
+  HIPCHK(a, hipMemcpy(stats, a->s_work_counts.as<unsigned long long>() + 8, 16, hipMemcpyDeviceToHost));
   return THM_OK;
 }
 // test hook: the register-resident kernels pretend their class holds bands up to `max_bw` only (max_bw + 1 is stored; 0 turns

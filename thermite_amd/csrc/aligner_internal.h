@@ -131,6 +131,9 @@ struct thm_aligner {
   // test hook (thm_debug_set_pool_caps): initial pool sizes instead of the heuristics, to force the grow-and-replay path
   uint64_t dbg_smem_cap = 0, dbg_cand_cap = 0, dbg_ops_cap = 0;
   uint32_t dbg_band_clip = 0;  // test hook (thm_debug_set_band_clip): pretend the fast class holds bands up to this only (0: off)
+  // test / tuning hook (thm_debug_set_flags bits 2, 3): seed probes never decided from the table entry and a neighbouring
+  // match; seed probes counted (thm_debug_seed_stats)
+  bool dbg_seed_noinfer = false, dbg_seed_stats = false;
   uint32_t n_replays = 0;  // pool-overflow replays since the aligner was created
   bool ran = false, synced = false;
   hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};

@@ -108,8 +108,11 @@ __device__ __forceinline__ int lcp_cmp(const uint8_t* tp, const uint8_t* q, int 
 //   4. larger intervals (repeats): lower bound of the whole query tail by binary
 //      search, the better of the two neighbours of the insertion point gives the
 //      match length, two more binary searches give the interval.
+// `known_end` (0: none) is E[a] = a + MS[a] of some position a < pos of the same read with MS[a] >= k, as an earlier
+// probe stored it.  Returns true when the table entry and that end decided the probe (no suffix-array or text read).
 template <class C>
-__device__ void ms_search(const DeviceIndexT<C>& ix, const uint8_t* rd, int L, int pos, int k, int& out_d, C& out_lo, C& out_hi) {
+__device__ bool ms_search(const DeviceIndexT<C>& ix, const uint8_t* rd, int L, int pos, int k, int known_end, int& out_d, C& out_lo,
+                          C& out_hi) {
   C lo = 0, hi = (C)ix.n;
   int d = 0;
   const int kt = (int)ix.kt;
@@ -127,6 +130,29 @@ __device__ void ms_search(const DeviceIndexT<C>& ix, const uint8_t* rd, int L, i
       lo = e.lo;
       hi = e.hi;
       d = kt;
+      // Shortcut: a single suffix in the bucket and a left neighbour whose match reaches past the kt-mer.
+      // Let a < pos be the neighbour, E = known_end = a + MS[a], and pos + kt <= E.  "Match" below is what
+      // lcp_cmp computes: byte equality of the sanitised read with the text, never past the read's end L.
+      //   * rd[a..E) occurs in the text at some t, so rd[pos..E) occurs at s = t + (pos - a), and that occurrence
+      //     starts with the kt-mer rd[pos..pos+kt): s is a suffix of the bucket.  The bucket holds one suffix, so
+      //     s is that suffix, MS[pos] >= E - pos, and t = s - (pos - a) is the ONLY occurrence of rd[a..E).
+      //   * A longer match from pos would again start with the kt-mer, hence at s, and would need text[s + E - pos]
+      //     == rd[E] with E < L.  That byte is text[t + E - a], and MS[a] is the maximum over all occurrences of
+      //     rd[a..E) -- t alone -- so the neighbour's match stopped at E because E == L, or because rd[E] !=
+      //     text[t + E - a].  The second covers every way a match can stop inside the read: a substitution; a read
+      //     byte outside ACGTN (sanitised to 0, which no text byte equals); a read N against a text base; and a
+      //     '$' (contig end) or an N run of the text against a read base or N ('$' never occurs in a sanitised
+      //     read, and N == N is a match for the neighbour and for this position alike).  In each case the
+      //     same two bytes face each other here, so the match from pos stops at E too.
+      // Hence MS[pos] = E - pos exactly and the interval is the bucket, which is what the sz == 1 path below
+      // returns (it never changes lo / hi).  Every other case (two or more suffixes, an empty entry, no hint, a
+      // hint that ends inside the kt-mer, kt > k, a byte outside ACGT in the kt-mer) takes the full path.
+      if (known_end != 0 && hi - lo == 1 && pos + kt <= known_end) {
+        out_d = known_end - pos;
+        out_lo = lo;
+        out_hi = hi;
+        return true;
+      }
     }
   }
   if (lo < hi && pos + d < L) {
@@ -221,6 +247,7 @@ __device__ void ms_search(const DeviceIndexT<C>& ix, const uint8_t* rd, int L, i
   out_d = (lo < hi) ? d : 0;
   out_lo = lo;
   out_hi = hi;
+  return false;
 }
 
 // upper-case + sanitise the batch once (reference src/aligner.rs:125); both the
@@ -261,6 +288,12 @@ __global__ void sanitize_kernel(const uint8_t* in, uint8_t* out, uint64_t n, uin
 //                      inside has that end too (and MS >= k), so nothing starts there and
 //                      the end is recorded without probing; other cells go on a work list.
 //   seed_fill_kernel   the inner positions of listed cells: the cells around a jump of E.
+// For reads of at most SHORT_READ_MAX bases the grid and cells steps are one launch (seed_grid_cells_kernel).
+// A probe behind position 0 is told the end of a match further left in its read (the match from position 0 for the
+// grid, the nearest grid point with a match for the fill): where that match covers the probe's kt-mer and the table
+// holds a single suffix for it, the probe is decided without reading the suffix array or the text (ms_search), and
+// the interval of a probe is stored only where an SMEM can start (probe_store).  SEED_INFER in p.flags; off: every
+// probe runs in full and stores everything.
 // The work lists keep the probing launches dense (whole waves of real probes).  The per-position
 // arrays are ragged: the row of read r starts at slot ms_row(offsets[r], r) (launch.h).
 constexpr int PROBE_STRIDE = 8;
@@ -286,12 +319,70 @@ __device__ __forceinline__ void block_append(bool flag, unsigned long long value
   __syncthreads();
 }
 
+// SEED_STATS: a workgroup's probe counts (decided from the table entry alone / run in full) are gathered in LDS, a
+// ballot and popcount per wavefront, and added to work_counts[8], [9] with one atomic per counter and workgroup.  Every thread calls _begin and _end, under a
+// branch on p.flags (uniform for the launch); nothing is counted, and no register is held, when the bit is clear.
+__device__ __forceinline__ unsigned* seed_stats_lds() {
+  __shared__ unsigned s_cnt[2];
+  return s_cnt;
+}
+__device__ __forceinline__ void seed_stats_begin() {
+  unsigned* c = seed_stats_lds();
+  if (threadIdx.x == 0) c[0] = c[1] = 0;
+  __syncthreads();
+}
+// the probes of the lanes that are here together: one pair of LDS adds per wavefront
+__device__ __forceinline__ void seed_stats_note(bool decided) {
+  const unsigned long long here = __ballot(1), dec = __ballot(decided);
+  if (lane_id() == (int)__builtin_ctzll(here)) {
+    unsigned* c = seed_stats_lds();
+    if (dec) atomicAdd(&c[0], (unsigned)__popcll(dec));
+    if (here & ~dec) atomicAdd(&c[1], (unsigned)__popcll(here & ~dec));
+  }
+}
+template <class C>
+__device__ __forceinline__ void seed_stats_end(const SeedParamsT<C>& p) {
+  unsigned* c = seed_stats_lds();
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    if (c[0]) atomicAdd(&p.work_counts[8], (unsigned long long)c[0]);
+    if (c[1]) atomicAdd(&p.work_counts[9], (unsigned long long)c[1]);
+  }
+}
+
+// One probe behind position 0: search, store the end, and store the interval only where a selection kernel can read
+// it.  Both selection kernels take ms_lo / ms_hi of a position only where an SMEM starts: stored end e > 0 and
+// e > stored end of pos - 1.  With a hint (the true end E[a] of a position a < pos, see ms_search) that needs e > hint:
+// E never decreases, so E[pos - 1] >= hint; if e == hint then E[pos - 1] == e, MS[pos - 1] = MS[pos] + 1 >= k, the
+// end stored for pos - 1 is e as well and nothing starts at pos.  Without a hint the interval is always stored.
+// (seed_select_kernel loads ms_lo / ms_hi of a whole row into registers before it knows the starts: the words of
+// positions skipped here are stale or never written, inside the buffer, and must stay unused except at a start.)
+// Returns the stored end; `decided`: the table entry and the hint answered the probe.
+template <class C>
+__device__ __forceinline__ int probe_store(const SeedParamsT<C>& p, const uint8_t* rd, int L, int pos, uint64_t item0, int hint,
+                                           bool& decided) {
+  const int k = (int)p.min_seed_len;
+  int d = 0;
+  C lo = 0, hi = 0;
+  decided = ms_search(p.ix, rd, L, pos, k, hint, d, lo, hi);
+  if (p.flags & SEED_STATS) seed_stats_note(decided);
+  const int e = (d >= k) ? pos + d : 0;
+  const uint64_t item = item0 + (uint64_t)pos;
+  p.ms_end[item] = (uint16_t)e;
+  if (hint == 0 || e > hint) {
+    p.ms_lo[item] = lo;
+    p.ms_hi[item] = hi;
+  }
+  return e;
+}
+
 template <class C>
 __global__ __launch_bounds__(256) void seed_first_kernel(SeedParamsT<C> p) {
   const uint64_t read = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   const int lane = lane_id();
   const bool active = read < p.reads.n_reads;
   const int k = (int)p.min_seed_len;
+  if (p.flags & SEED_STATS) seed_stats_begin();
   int d = 0, L = 0;
   C lo = 0, hi = 0;
   bool too_long = false;
@@ -301,13 +392,17 @@ __global__ __launch_bounds__(256) void seed_first_kernel(SeedParamsT<C> p) {
     too_long = Lfull > MAX_READ_LEN;
     L = too_long ? 0 : (int)Lfull;
     if (too_long) p.read_status[read] = THM_ERR_UNSUPPORTED;
-    if (k <= L) ms_search(p.ix, p.reads.bases + r0, L, 0, k, d, lo, hi);
+    if (k <= L) (void)ms_search(p.ix, p.reads.bases + r0, L, 0, k, 0, d, lo, hi);
     if (L > 0) {
       const uint64_t item = ms_row(r0, read);
       p.ms_end[item] = (uint16_t)((d >= k) ? d : 0);
       p.ms_lo[item] = lo;
       p.ms_hi[item] = hi;
     }
+  }
+  if (p.flags & SEED_STATS) {
+    if (active && k <= L) seed_stats_note(false);
+    seed_stats_end(p);
   }
   const bool covered = active && d >= k && d == L;
   // reads that are not finished here: more positions to probe, or (a single position) left to the selection kernels
@@ -358,23 +453,73 @@ __global__ __launch_bounds__(256) void seed_grid_kernel(SeedParamsT<C> p, const 
                                                         const unsigned long long* count, uint32_t G) {
   const uint64_t tid = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   const uint64_t wi = tid / G;
-  if (wi >= *count) return;
-  const uint64_t read = list[wi];
-  const int g = (int)(tid - wi * G);
-  const uint64_t r0 = p.reads.offsets[read];
-  const int L = (int)(p.reads.offsets[read + 1] - r0);
-  const int k = (int)p.min_seed_len;
-  const int npos = L - k + 1;  // >= 1 for listed reads
-  const int pos = (g + 1 == (int)G) ? npos - 1 : g * PROBE_STRIDE;
-  // position 0 was probed by seed_first_kernel; the last position is probed once (by the extra slot)
-  if (pos <= 0 || pos >= npos || (g + 1 != (int)G && pos == npos - 1)) return;
-  int d = 0;
-  C lo = 0, hi = 0;
-  ms_search(p.ix, p.reads.bases + r0, L, pos, k, d, lo, hi);
-  const uint64_t item = ms_row(r0, read) + (uint64_t)pos;
-  p.ms_end[item] = (uint16_t)((d >= k) ? pos + d : 0);
-  p.ms_lo[item] = lo;
-  p.ms_hi[item] = hi;
+  if (p.flags & SEED_STATS) seed_stats_begin();
+  if (wi < *count) {
+    const uint64_t read = list[wi];
+    const int g = (int)(tid - wi * G);
+    const uint64_t r0 = p.reads.offsets[read];
+    const int L = (int)(p.reads.offsets[read + 1] - r0);
+    const int k = (int)p.min_seed_len;
+    const int npos = L - k + 1;  // >= 1 for listed reads
+    const int pos = (g + 1 == (int)G) ? npos - 1 : g * PROBE_STRIDE;
+    // position 0 was probed by seed_first_kernel; the last position is probed once (by the extra slot)
+    if (!(pos <= 0 || pos >= npos || (g + 1 != (int)G && pos == npos - 1))) {
+      const uint64_t item0 = ms_row(r0, read);
+      const int hint = (p.flags & SEED_INFER) ? (int)p.ms_end[item0] : 0;  // the match from position 0
+      bool decided;
+      (void)probe_store(p, p.reads.bases + r0, L, pos, item0, hint, decided);
+    }
+  }
+  if (p.flags & SEED_STATS) seed_stats_end(p);
+}
+
+// seed_grid_kernel and seed_cells_kernel in one launch, for the short class (G <= 256): a workgroup takes 256 / G
+// whole reads (its surplus threads idle), so the ends a cell needs are those of two threads of the same workgroup and
+// pass through LDS instead of a second launch re-reading list, offsets and the row of ends.  Slot g of a read probes
+// like seed_grid_kernel's thread; behind the barrier slot c < G - 1 classifies cell c like seed_cells_kernel's.
+template <class C>
+__global__ __launch_bounds__(256) void seed_grid_cells_kernel(SeedParamsT<C> p, const unsigned long long* list,
+                                                              const unsigned long long* count, uint32_t G) {
+  __shared__ uint16_t s_end[256];
+  const unsigned per = 256u / G;             // reads per workgroup
+  const unsigned rl = threadIdx.x / G;       // read of the workgroup
+  const int g = (int)(threadIdx.x - rl * G); // its slot
+  const uint64_t wi = (uint64_t)blockIdx.x * per + rl;
+  const bool live = rl < per && wi < *count;
+  if (p.flags & SEED_STATS) seed_stats_begin();
+  uint64_t read = 0, item0 = 0;
+  int npos = 0, e = 0;
+  if (live) {
+    read = list[wi];
+    const uint64_t r0 = p.reads.offsets[read];
+    const int L = (int)(p.reads.offsets[read + 1] - r0);
+    npos = L - (int)p.min_seed_len + 1;  // >= 1 for listed reads
+    item0 = ms_row(r0, read);
+    const int pos = (g + 1 == (int)G) ? npos - 1 : g * PROBE_STRIDE;
+    const int e0 = p.ms_end[item0];  // the match from position 0 (seed_first_kernel): slot 0's end, everybody's hint
+    if (pos <= 0) {
+      e = e0;
+    } else if (pos < npos && !(g + 1 != (int)G && pos == npos - 1)) {
+      bool decided;
+      e = probe_store(p, p.reads.bases + r0, L, pos, item0, (p.flags & SEED_INFER) ? e0 : 0, decided);
+    }
+  }
+  s_end[threadIdx.x] = (uint16_t)e;
+  __syncthreads();
+  bool todo = false;
+  if (live && g + 1 < (int)G) {  // cell g: positions a .. b, both probed (a by this thread, b by slot g + 1 or the last slot)
+    const int a = g * PROBE_STRIDE, b = min(a + PROBE_STRIDE, npos - 1);
+    if (b - a > 1) {  // the cell has inner positions
+      const int ea = e, eb = s_end[rl * G + (unsigned)(b == npos - 1 ? (int)G - 1 : g + 1)];
+      if (ea != 0 && ea == eb) {
+        for (int q = a + 1; q < b; q++) p.ms_end[item0 + (uint64_t)q] = (uint16_t)ea;  // same end: nothing starts here
+      } else {
+        todo = true;
+      }
+    }
+  }
+  block_append(todo, (read << 16) | (unsigned long long)g, p.work_cells, &p.work_counts[1]);
+  if (p.flags & SEED_STATS) seed_stats_end(p);
 }
 
 template <class C>
@@ -419,27 +564,46 @@ __device__ __forceinline__ bool fill_item(const SeedParamsT<C>& p, uint64_t tid,
   pos = c * PROBE_STRIDE + j;
   return pos < min(c * PROBE_STRIDE + PROBE_STRIDE, npos - 1);
 }
+// The hint of a fill probe: the stored end of the nearest grid point at or left of the cell's left end that has one
+// (all in the read's row of ends, written by the launches before).  One substitution leaves at most k positions with
+// MS < k, i.e. ceil(k / 8) + 1 grid points in a row with a stored end of 0: behind that many there is no hint.  The
+// row is read four grid points at a time with the loads in flight together.
+template <class C>
+__device__ __forceinline__ int fill_hint(const SeedParamsT<C>& p, uint64_t item0, int pos) {
+  const int steps = ((int)p.min_seed_len + PROBE_STRIDE - 1) / PROBE_STRIDE + 1;
+  int a = pos & ~(PROBE_STRIDE - 1);
+  for (int s0 = 0; s0 < steps && a >= 0; s0 += 4, a -= 4 * PROBE_STRIDE) {
+    int e[4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const int at = a - u * PROBE_STRIDE;
+      e[u] = (at >= 0 && s0 + u < steps) ? (int)p.ms_end[item0 + (uint64_t)at] : 0;
+    }
+#pragma unroll
+    for (int u = 0; u < 4; u++)
+      if (e[u] != 0) return e[u];
+  }
+  return 0;
+}
 template <class C>
 __device__ __forceinline__ void fill_probe(const SeedParamsT<C>& p, uint64_t read, int pos, uint64_t r0, int L) {
-  const int k = (int)p.min_seed_len;
-  int d = 0;
-  C lo = 0, hi = 0;
-  ms_search(p.ix, p.reads.bases + r0, L, pos, k, d, lo, hi);
-  const uint64_t item = ms_row(r0, read) + (uint64_t)pos;
-  p.ms_end[item] = (uint16_t)((d >= k) ? pos + d : 0);
-  p.ms_lo[item] = lo;
-  p.ms_hi[item] = hi;
+  const uint64_t item0 = ms_row(r0, read);
+  const int hint = (p.flags & SEED_INFER) ? fill_hint(p, item0, pos) : 0;
+  bool decided;
+  (void)probe_store(p, p.reads.bases + r0, L, pos, item0, hint, decided);
 }
 
 template <class C>
 __global__ __launch_bounds__(256) void seed_fill_kernel(SeedParamsT<C> p) {
   const uint64_t total = p.work_counts[1] * PROBE_STRIDE;
   const uint64_t step = (uint64_t)gridDim.x * 256;  // (the worst-case grid covers every slot: one pass)
+  if (p.flags & SEED_STATS) seed_stats_begin();
   for (uint64_t tid = (uint64_t)blockIdx.x * 256 + threadIdx.x; tid < total; tid += step) {
     uint64_t read, r0;
     int pos, L;
     if (fill_item(p, tid, read, pos, r0, L)) fill_probe(p, read, pos, r0, L);
   }
+  if (p.flags & SEED_STATS) seed_stats_end(p);
 }
 
 // ---- the probes in bucket order (fill_mode 2) ----
@@ -505,12 +669,14 @@ template <class C>
 __global__ __launch_bounds__(256) void seed_fill_bucketed_kernel(SeedParamsT<C> p) {
   const uint64_t total = p.fill_hist[2 * (FILL_BUCKETS + 1)];
   const uint64_t step = (uint64_t)gridDim.x * 256;
+  if (p.flags & SEED_STATS) seed_stats_begin();
   for (uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x; s < total; s += step) {
     const uint64_t tid = p.fill_perm[s];
     uint64_t read, r0;
     int pos, L;
     if (fill_item(p, tid, read, pos, r0, L)) fill_probe(p, read, pos, r0, L);
   }
+  if (p.flags & SEED_STATS) seed_stats_end(p);
 }
 
 // per read: SMEM selection and ordering, one read per wavefront.  The per-read lists (one entry per
@@ -931,15 +1097,24 @@ static hipError_t launch_seed_t(const SeedParamsT<C>& p, int n_blocks, hipStream
     uint32_t max_len;
     const unsigned long long* list;
     const unsigned long long* count;
-  } cls[2] = {{n_short, p.max_len_short, p.work_short, p.work_counts + 0}, {p.n_long, p.max_len_long, p.work_long, p.work_counts + 4}};
+    bool fused;  // grid and cells in one launch
+  } cls[2] = {{n_short, p.max_len_short, p.work_short, p.work_counts + 0, true},
+              {p.n_long, p.max_len_long, p.work_long, p.work_counts + 4, false}};
   uint64_t fill_cells = 0;
   for (const Cls& c : cls) {
     if (c.n == 0 || c.max_len < k + 1) continue;  // a single position was probed by seed_first_kernel
     const uint64_t NC = cells_of(c.max_len), G = NC + 1;
-    hipLaunchKernelGGL(dev::seed_grid_kernel<C>, blocks(c.n * G), dim3(256), 0, s, p, c.list, c.count, (uint32_t)G);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(dev::seed_cells_kernel<C>, blocks(c.n * NC), dim3(256), 0, s, p, c.list, c.count, (uint32_t)NC);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (c.fused && G <= 256) {  // (always for the short class: at most SHORT_READ_MAX positions) whole reads per workgroup
+      const uint64_t per = 256 / G;
+      hipLaunchKernelGGL(dev::seed_grid_cells_kernel<C>, dim3((unsigned)((c.n + per - 1) / per)), dim3(256), 0, s, p, c.list, c.count,
+                         (uint32_t)G);
+      if ((e = hipGetLastError()) != hipSuccess) return e;
+    } else {
+      hipLaunchKernelGGL(dev::seed_grid_kernel<C>, blocks(c.n * G), dim3(256), 0, s, p, c.list, c.count, (uint32_t)G);
+      if ((e = hipGetLastError()) != hipSuccess) return e;
+      hipLaunchKernelGGL(dev::seed_cells_kernel<C>, blocks(c.n * NC), dim3(256), 0, s, p, c.list, c.count, (uint32_t)NC);
+      if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
     fill_cells += c.n * NC;
   }
   if (fill_cells) {

@@ -95,7 +95,10 @@ struct SeedParamsT {
   unsigned long long* work_short;   // [n_reads] short reads that need more than the probe at position 0
   unsigned long long* work_long;    // [n_long] long reads, the same
   unsigned long long* work_cells;   // [cells] (read << 16 | cell) of grid cells to probe
-  unsigned long long* work_counts;  // [8] list lengths: 0 short, 1 cells, 2 heavy, 3 select overflow, 4 long, 5 slow; zeroed before launch
+  unsigned long long* work_counts;  // [16] list lengths: 0 short, 1 cells, 2 heavy, 3 select overflow, 4 long, 5 slow; with
+                                    // SEED_STATS 8 = probes decided from the table entry alone, 9 = probes run in full;
+                                    // zeroed before launch
+  uint32_t flags;                   // SEED_INFER | SEED_STATS
   SmemT<C>* smems;             // pool
   uint64_t smem_cap;           // pool capacity (entries)
   unsigned long long* cursor;  // bump allocator head (entries), zeroed before launch
@@ -116,6 +119,10 @@ struct SeedParamsT {
   uint32_t* fill_perm;     // [fill slots] probes in bucket order
   unsigned int* fill_hist; // [FILL_BUCKETS] counts, [FILL_BUCKETS] cursors, [1] total; zeroed before launch
 };
+// SeedParamsT::flags.  SEED_INFER: a probe may be decided by its table entry and a match further left in the read, and
+// stores its interval only where an SMEM can start (kernels_seed.hip; thm_debug_set_flags bit 2 clears it, bit 4 sets it again).
+// SEED_STATS: the probing kernels count their probes into work_counts[8], [9] (thm_debug_set_flags bit 3; bit 5 ends it).
+constexpr uint32_t SEED_INFER = 1u, SEED_STATS = 2u;
 constexpr int FILL_KEY_BASES = 7;
 constexpr unsigned FILL_BUCKETS = 1u << (2 * FILL_KEY_BASES);  // + one bucket for k-mers with a byte outside ACGT
 size_t seed_select_lds_bytes(uint32_t max_read_len);         // per workgroup (4 waves)

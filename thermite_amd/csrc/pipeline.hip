@@ -122,8 +122,8 @@ int enqueue_seed_t(thm_aligner* a, uint32_t min_seed_len) {
   HIPCHK(a, a->s_work_reads.ensure((n + 1) * 8));
   HIPCHK(a, a->s_work_long.ensure((n_long + 1) * 8));
   HIPCHK(a, a->s_work_cells.ensure((std::max(cells, n) + 1) * 8));
-  HIPCHK(a, a->s_work_counts.ensure(64));
-  HIPCHK(a, hipMemsetAsync(a->s_work_counts.p, 0, 64, s));
+  HIPCHK(a, a->s_work_counts.ensure(128));
+  HIPCHK(a, hipMemsetAsync(a->s_work_counts.p, 0, 128, s));
   int rc = reset_queue(a);
   if (rc != THM_OK) return rc;
   HIPCHK(a, hipMemsetAsync(a->d_cursors.p, 0, 64, s));
@@ -144,6 +144,7 @@ int enqueue_seed_t(thm_aligner* a, uint32_t min_seed_len) {
   sp.work_long = a->s_work_long.as<unsigned long long>();
   sp.work_cells = a->s_work_cells.as<unsigned long long>();
   sp.work_counts = a->s_work_counts.as<unsigned long long>();
+  sp.flags = (a->dbg_seed_noinfer ? 0u : SEED_INFER) | (a->dbg_seed_stats ? SEED_STATS : 0u);
   sp.smems = a->s_smems.as<SmemT<C>>();
   sp.smem_cap = a->smem_cap;
   sp.cursor = a->d_cursors.as<unsigned long long>();
