@@ -205,10 +205,18 @@ int32_t thm_aligner_create(const thm_index* ix, const thm_align_opts* opts, int3
       hipEventCreateWithFlags(&a->ev_fork, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&a->ev_join, hipEventDisableTiming) != hipSuccess)
     return bail(fail(nullptr, THM_ERR_HIP, "second stream / events: creation failed"));
-  if (a->d_counters.ensure(THM_N_COUNTERS * 8 * 3) != hipSuccess || a->d_queue.ensure(thm::QUEUE_BYTES) != hipSuccess ||
-      a->d_fault.ensure(64) != hipSuccess || a->d_cursors.ensure(64) != hipSuccess)
+  if (a->d_counters.ensure(THM_N_COUNTERS * 8 * 3) != hipSuccess || a->d_ctl.ensure(thm_aligner::CTL_BYTES) != hipSuccess)
     return bail(fail(nullptr, THM_ERR_OOM, "scratch allocation failed"));
+  {
+    uint8_t* ctl = a->d_ctl.as<uint8_t>();
+    a->s_work_counts = {ctl + thm_aligner::CTL_WORK_COUNTS, 128};
+    a->d_cursors = {ctl + thm_aligner::CTL_CURSORS, 64};
+    a->d_fault = {ctl + thm_aligner::CTL_FAULT, 64};
+    a->d_queue = {ctl + thm_aligner::CTL_QUEUE, thm::QUEUE_BYTES};
+    a->d_queue_ext = {ctl + thm_aligner::CTL_QUEUE_EXT, thm::QUEUE_BYTES};
+  }
   (void)hipMemsetAsync(a->d_counters.p, 0, THM_N_COUNTERS * 8 * 3, a->stream);
+  (void)hipMemsetAsync(a->d_ctl.p, 0, thm_aligner::CTL_BYTES, a->stream);
   int rc = get_dev_copy(a);
   if (rc != THM_OK) return bail(rc);
   rc = thm_aligner_set_opts(a, opts);
@@ -224,10 +232,10 @@ void thm_aligner_free(thm_aligner* a) {
   if (a->stream2) (void)hipStreamSynchronize(a->stream2);
   if (a->stream3) (void)hipStreamSynchronize(a->stream3);
   if (a->stream4) (void)hipStreamSynchronize(a->stream4);
-  DBuf* all[] = {&a->d_counters, &a->d_queue, &a->d_fault, &a->d_cursors, &a->b0, &a->b1, &a->b2, &a->b3, &a->b4,
-                 &a->b5, &a->b6, &a->b7, &a->b8, &a->r_bases, &a->r_offsets, &a->r_san, &a->s_ms_end, &a->s_ms_lo, &a->s_ms_hi, &a->s_work_reads, &a->s_work_long, &a->s_work_cells, &a->s_work_counts, &a->s_fill_keys, &a->s_fill_perm, &a->s_fill_hist, &a->s_sel_scratch, &a->s_heavy, &a->s_slow, &a->s_team, &a->r_status, &a->e_slow, &a->e_recs, &a->e_wcnt, &a->t_memos, &a->t_recs, &a->t_dpops, &a->t_qlist, &a->t_act[0], &a->t_act[1], &a->t_ctl, &a->t_bail, &a->t_queue2, &a->t_trace, &a->t_ttrace, &a->t_hdr, &a->t_sums, &a->s_smems, &a->s_off, &a->s_cnt,
+  DBuf* all[] = {&a->d_counters, &a->d_ctl, &a->b0, &a->b1, &a->b2, &a->b3, &a->b4,
+                 &a->b5, &a->b6, &a->b7, &a->b8, &a->r_bases, &a->r_offsets, &a->r_san, &a->s_ms_end, &a->s_ms_lo, &a->s_ms_hi, &a->s_work_reads, &a->s_work_long, &a->s_work_cells, &a->s_fill_keys, &a->s_fill_perm, &a->s_fill_hist, &a->s_sel_scratch, &a->s_heavy, &a->s_slow, &a->s_team, &a->r_status, &a->e_slow, &a->e_recs, &a->e_wcnt, &a->t_memos, &a->t_recs, &a->t_dpops, &a->t_qlist, &a->t_act[0], &a->t_act[1], &a->t_ctl, &a->t_bail, &a->t_queue2, &a->t_trace, &a->t_ttrace, &a->t_hdr, &a->t_sums, &a->s_smems, &a->s_off, &a->s_cnt,
                  &a->s_hits, &a->s_cand_off, &a->scan_tmp, &a->e_cands, &a->e_heavy, &a->e_rel, &a->e_order, &a->e_ops, &a->e_nalns,
-                 &a->e_nalns64, &a->e_opbytes, &a->e_aln_off, &a->e_ops_off, &a->e_trace, &a->o_alns, &a->o_ops, &a->o_mems,
+                 &a->e_opbytes, &a->e_aln_off, &a->e_ops_off, &a->e_trace, &a->o_alns, &a->o_ops, &a->o_mems,
                  &a->sh_bases, &a->sh_san, &a->sh_off, &a->sh_hits, &a->sh_read, &a->sh_bw, &a->sh_xd, &a->sh_list, &a->sh_out,
                  &a->sh_status, &a->sh_ops, &a->sh_ctl, &a->sh_trace, &a->sh_slow, &a->c_sums, &a->c_nwords, &a->c_woff,
                  &a->c_scan_tmp, &a->c_flags, &a->c_dig, &a->c_words, &a->c_in_ops, &a->c_in_off,

@@ -36,6 +36,16 @@ struct DBuf {
   }
 };
 
+// a fixed part of another DBuf (the control block's words): same accessors, nothing to grow or free
+struct DView {
+  void* p = nullptr;
+  size_t cap = 0;
+  template <class T>
+  T* as() const {
+    return (T*)p;
+  }
+};
+
 // grow-only pinned host buffer (results land here: D2H at full PCIe rate, no value-initialisation)
 struct HBuf {
   void* p = nullptr;
@@ -96,7 +106,17 @@ struct thm_aligner {
   thm_align_opts opts;
   std::string err;
 
-  DBuf d_counters, d_queue, d_fault, d_cursors;  // cursors: [0] smem pool head, [1] op pool head (u64 each)
+  DBuf d_counters;
+  // Control block: every word a run of the read-level pipeline wants zeroed when it starts, side by side, so that the
+  // run's first kernel zeroes them in one go (launch.h, RunResetParams).  The views below are its parts.
+  DBuf d_ctl;
+  static constexpr size_t CTL_WORK_COUNTS = 0, CTL_CURSORS = 128, CTL_FAULT = 192, CTL_QUEUE = 256,
+                          CTL_QUEUE_EXT = CTL_QUEUE + thm::QUEUE_BYTES, CTL_BYTES = CTL_QUEUE_EXT + thm::QUEUE_BYTES;
+  static_assert(CTL_BYTES % 16 == 0 && thm::QUEUE_BYTES % 16 == 0, "the block is zeroed 16 bytes at a time");
+  DView d_queue;      // work counters of the seed stage's selection kernel and of the operator-level calls
+  DView d_queue_ext;  // ... of the extend stage: its own words, so that one reset serves both stages of a run
+  DView d_fault, d_cursors;  // cursors: [0] smem pool head, [1] op pool head (u64 each)
+  DView s_work_counts;       // list lengths of the seed stage and of the plan kernel (16 u64)
   DBuf b0, b1, b2, b3, b4, b5, b6, b7, b8;       // operator-level scratch
 
   // ---- read-level pipeline ----
@@ -111,11 +131,15 @@ struct thm_aligner {
   bool uploaded = false;
   // seeds
   DBuf s_smems, s_off, s_cnt, s_hits, s_cand_off, scan_tmp, s_ms_end, s_ms_lo, s_ms_hi, s_work_reads, s_work_long, s_work_cells,
-      s_work_counts, s_sel_scratch, s_heavy, s_slow, s_team, s_fill_keys, s_fill_perm, s_fill_hist;
+      s_sel_scratch, s_heavy, s_slow, s_team, s_fill_keys, s_fill_perm, s_fill_hist;
   uint64_t smem_cap = 0;
   // extension
   DBuf e_heavy, e_rel;  // compact stage: lists of reads with many alignments, op offsets of their alignments
-  DBuf e_cands, e_order, e_ops, e_nalns, e_nalns64, e_opbytes, e_aln_off, e_ops_off, e_trace, e_slow, e_recs, e_wcnt;
+  DBuf e_cands, e_order, e_ops, e_nalns, e_opbytes, e_aln_off, e_ops_off, e_trace, e_slow, e_recs, e_wcnt;
+  // e_wcnt (the waves' counter rows) is zero from end to end between runs: launch_counters_reduce zeroes what it read, so
+  // only a new allocation is zeroed by the host.  The capacity that is known clean (0 while a run's launches are being
+  // enqueued: an enqueue that fails half way leaves rows nobody reduced)
+  size_t wcnt_clean_cap = 0;
   // Extension problems as the unit of wavefront work (kernels_tpr.hip: thread-per-read control kernel + wave-per-request
   // DP kernel, in rounds), ahead of the wave-per-read kernels, which take what is left.  THM_TPR=0 or
   // thm_debug_set_flags turn it off (every read then takes the wave-per-read path); THM_TPR_ROUNDS = 1..8.

@@ -1784,19 +1784,40 @@ __global__ __launch_bounds__(TEAM > 0 ? 64 * TEAM : 256, TEAM > 0 ? 1 : MINW) vo
   }
 }
 
-// counters[k] += sum of wave_counters[row][k] (the rows the extend kernels' waves left; zeroed before the launches)
-__global__ __launch_bounds__(1024) void counters_reduce_kernel(const unsigned long long* rows, uint32_t n_rows, unsigned long long* counters) {
-  __shared__ unsigned long long part[64][THM_N_COUNTERS];
+// counters[k] += sum of wave_counters[row][k] (the rows the extend kernels' waves left), and every row that held
+// something is zeroed again: the rows are clean when the next run starts, whatever its number of rows.  A workgroup
+// takes REDUCE_GROUPS rows at a time (a row is one 128-byte line), sums them in LDS and adds its sums with one atomic
+// per counter (the sums are integers: the order of the workgroups does not show).
+constexpr int REDUCE_GROUPS = 64, REDUCE_MAX_BLOCKS = 32;
+__global__ __launch_bounds__(REDUCE_GROUPS * THM_N_COUNTERS) void counters_reduce_kernel(unsigned long long* rows, uint32_t n_rows,
+                                                                                       unsigned long long* counters) {
+  __shared__ unsigned long long part[REDUCE_GROUPS][THM_N_COUNTERS];
   static_assert(THM_N_COUNTERS == 16, "one thread per counter and row group");
   const int k = (int)(threadIdx.x & 15u), g = (int)(threadIdx.x >> 4);
+  const uint32_t step = gridDim.x * REDUCE_GROUPS;
   unsigned long long sum = 0;
-  for (uint32_t r = (uint32_t)g; r < n_rows; r += 64) sum += rows[(size_t)r * THM_N_COUNTERS + k];
+  // four rows in flight per thread (the stores would otherwise order the loads behind them)
+  for (uint32_t r0 = blockIdx.x * REDUCE_GROUPS + (uint32_t)g; r0 < n_rows; r0 += 4 * step) {
+    unsigned long long v[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const uint64_t r = (uint64_t)r0 + (uint64_t)j * step;
+      v[j] = r < n_rows ? rows[r * THM_N_COUNTERS + k] : 0ull;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      if (v[j]) {
+        sum += v[j];
+        rows[((uint64_t)r0 + (uint64_t)j * step) * THM_N_COUNTERS + k] = 0;
+      }
+    }
+  }
   part[g][k] = sum;
   __syncthreads();
   if (g == 0) {
     unsigned long long t = 0;
-    for (int i = 0; i < 64; i++) t += part[i][k];
-    if (t) counters[k] += t;
+    for (int i = 0; i < REDUCE_GROUPS; i++) t += part[i][k];
+    if (t) atomicAdd(&counters[k], t);
   }
 }
 
@@ -2485,9 +2506,11 @@ static hipError_t launch_extend_t(const ExtendParamsT<C>& p, int cpl, int n_bloc
 hipError_t launch_extend(const ExtendParamsT<uint32_t>& p, int cpl, int n_blocks, hipStream_t s, bool team) { return launch_extend_t(p, cpl, n_blocks, s, team); }
 hipError_t launch_extend(const ExtendParamsT<uint64_t>& p, int cpl, int n_blocks, hipStream_t s, bool team) { return launch_extend_t(p, cpl, n_blocks, s, team); }
 
-hipError_t launch_counters_reduce(const unsigned long long* wave_counters, uint32_t n_rows, unsigned long long* counters, hipStream_t s) {
+hipError_t launch_counters_reduce(unsigned long long* wave_counters, uint32_t n_rows, unsigned long long* counters, hipStream_t s) {
   if (n_rows == 0) return hipSuccess;
-  hipLaunchKernelGGL(dev::counters_reduce_kernel, dim3(1), dim3(1024), 0, s, wave_counters, n_rows, counters);
+  const unsigned blocks = std::min<unsigned>((n_rows + dev::REDUCE_GROUPS - 1) / dev::REDUCE_GROUPS, dev::REDUCE_MAX_BLOCKS);
+  hipLaunchKernelGGL(dev::counters_reduce_kernel, dim3(blocks), dim3(dev::REDUCE_GROUPS * THM_N_COUNTERS), 0, s, wave_counters, n_rows,
+                     counters);
   return hipGetLastError();
 }
 

@@ -252,9 +252,8 @@ __device__ bool ms_search(const DeviceIndexT<C>& ix, const uint8_t* rd, int L, i
 
 // upper-case + sanitise the batch once (reference src/aligner.rs:125); both the
 // probe kernel and the extend kernel read this copy
-__global__ void sanitize_kernel(const uint8_t* in, uint8_t* out, uint64_t n, uint64_t n_padded) {
+__device__ __forceinline__ void sanitize16(const uint8_t* in, uint8_t* out, uint64_t n, uint64_t n_padded, uint64_t i) {
   // 16 bytes per thread (both buffers come from hipMalloc and are padded past n_padded)
-  const uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * 16;
   if (i >= n_padded) return;
   uint4 v = make_uint4(0, 0, 0, 0);
   if (i < n) v = *(const uint4*)(in + i);  // may read up to 15 bytes past n: inside the allocation's slack
@@ -271,6 +270,20 @@ __global__ void sanitize_kernel(const uint8_t* in, uint8_t* out, uint64_t n, uin
     w[j] = r;
   }
   *(uint4*)(out + i) = make_uint4(w[0], w[1], w[2], w[3]);
+}
+__global__ void sanitize_kernel(const uint8_t* in, uint8_t* out, uint64_t n, uint64_t n_padded) {
+  sanitize16(in, out, n, n_padded, ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * 16);
+}
+// ... and, as the first kernel of a run of the read-level pipeline, everything that run wants zeroed (launch.h,
+// RunResetParams): one launch instead of a memset per buffer
+__global__ void sanitize_reset_kernel(const uint8_t* in, uint8_t* out, uint64_t n, uint64_t n_padded, RunResetParams rp) {
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint4 zero = make_uint4(0, 0, 0, 0);
+  if (t < rp.status_vec4) rp.status[t] = zero;
+  if (t < rp.ctl_vec4) rp.ctl[t] = zero;
+  if (t < THM_N_COUNTERS) rp.counters[THM_N_COUNTERS + t] = rp.counters[t];
+  if (t == 0) *rp.san_head = zero;
+  sanitize16(in, out, n, n_padded, t * 16);
 }
 
 // Matching statistics by probing fewer and fewer positions.  E[i] = i + MS[i], the end of
@@ -986,15 +999,21 @@ __global__ __launch_bounds__(256) void seed_select_thread_kernel(SeedParamsT<C> 
   }
 }
 
-// After the seed stage: the extend stage's lists.  Reads of the fast class with many seed hits (longest
-// jobs first), reads of the slow class (band or length beyond the register-resident kernels), and the
-// status of reads no kernel takes.
-__global__ __launch_bounds__(256) void plan_kernel(PlanParams p) {
+// After the seed stage, one thread per read:
+//   - the extend stage's lists: reads of the fast class with many seed hits (longest jobs first), reads of the slow
+//     class (band or length beyond the register-resident kernels), and the status of reads no kernel takes;
+//   - one record per read for the extend kernel (launch.h, ReadRecT);
+//   - the last phase of the scan of the hit counts: read_cand_off[] arrives as prefixes within tiles of SCAN_TILE reads
+//     and leaves as the final offsets (the compact kernel reads them).  A read's slice is read_hits[r] long, so no
+//     thread needs its neighbour's offset.
+template <class C>
+__global__ __launch_bounds__(256) void plan_pack_kernel(PlanParams p, PackParamsT<C> q) {
   const uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   const bool active = r < p.n_reads;
-  uint64_t L = 0, hits = 0;
+  uint64_t b0 = 0, L = 0, hits = 0;
   if (active) {
-    L = p.offsets[r + 1] - p.offsets[r];
+    b0 = p.offsets[r];
+    L = p.offsets[r + 1] - b0;
     hits = p.read_hits[r];
   }
   const bool fast = active && L <= p.fast_max_len;
@@ -1012,33 +1031,27 @@ __global__ __launch_bounds__(256) void plan_kernel(PlanParams p) {
   block_append(fast && !team && hits >= (p.tpr_max_hits ? (uint64_t)p.tpr_max_hits : (uint64_t)HEAVY_HITS), r, p.heavy, &p.counts[2]);
   block_append(slow, r, p.slow, &p.counts[5]);
   block_append(team, r, p.team, &p.counts[7]);
-}
-
-// One record per read for the extend kernel (launch.h, ReadRecT): thread per read
-template <class C>
-__global__ __launch_bounds__(256) void pack_reads_kernel(PackParamsT<C> p) {
-  const uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  if (r >= p.n_reads) return;
+  if (!active) return;
   ReadRecT<C> rec;
-  const uint64_t b0 = p.offsets[r], L = p.offsets[r + 1] - b0;
   rec.base_off = b0;
   rec.len = L > 0xFFFFFFFEull ? 0xFFFFFFFFu : (uint32_t)L;
-  rec.smem_off = p.read_smem_off[r];
-  rec.smem_cnt = p.read_smem_cnt[r];
-  const uint64_t c0 = p.read_cand_off[r], nh = p.read_cand_off[r + 1] - c0;
+  rec.smem_off = q.read_smem_off[r];
+  rec.smem_cnt = q.read_smem_cnt[r];
+  const uint64_t c0 = q.read_cand_off[r] + q.tile_offs[r / SCAN_TILE];
+  q.read_cand_off[r] = c0;
   rec.cand_off = c0;
-  rec.n_hits = nh > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)nh;
+  rec.n_hits = hits > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)hits;
   rec.qpos0 = rec.len0 = 0;
   rec.lo0 = rec.hi0 = rec.sa0 = 0;
-  if (rec.smem_cnt > 0 && *p.fault_seed == 0) {  // after a pool overflow the runs are incomplete (the batch is replayed)
-    const SmemT<C> sm = p.smems[rec.smem_off];
+  if (rec.smem_cnt > 0 && *q.fault_seed == 0) {  // after a pool overflow the runs are incomplete (the batch is replayed)
+    const SmemT<C> sm = q.smems[rec.smem_off];
     rec.qpos0 = sm.qpos;
     rec.len0 = sm.len;
     rec.lo0 = sm.lo;
     rec.hi0 = sm.hi;
-    if (sm.hi > sm.lo) rec.sa0 = p.sa[sm.hi - 1];
+    if (sm.hi > sm.lo) rec.sa0 = q.sa[sm.hi - 1];
   }
-  p.recs[r] = rec;
+  q.recs[r] = rec;
 }
 
 // Mem list of Index::all_smems for thm_smems_batch: one wave per read
@@ -1074,6 +1087,12 @@ size_t seed_select_lds_bytes(uint32_t max_read_len) { return 4 * seed_select_scr
 hipError_t launch_sanitize(const uint8_t* in, uint8_t* out, uint64_t n, uint64_t n_padded, hipStream_t s) {
   if (n_padded == 0) return hipSuccess;
   hipLaunchKernelGGL(dev::sanitize_kernel, dim3((unsigned)((n_padded / 16 + 255) / 256 + 1)), dim3(256), 0, s, in, out, n, n_padded);
+  return hipGetLastError();
+}
+
+hipError_t launch_sanitize_reset(const uint8_t* in, uint8_t* out, uint64_t n, uint64_t n_padded, const RunResetParams& rp, hipStream_t s) {
+  const uint64_t threads = std::max<uint64_t>(std::max<uint64_t>(n_padded / 16 + 1, rp.status_vec4), std::max<uint64_t>(rp.ctl_vec4, THM_N_COUNTERS));
+  hipLaunchKernelGGL(dev::sanitize_reset_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, in, out, n, n_padded, rp);
   return hipGetLastError();
 }
 
@@ -1161,20 +1180,14 @@ static hipError_t launch_seed_t(const SeedParamsT<C>& p, int n_blocks, hipStream
 hipError_t launch_seed(const SeedParamsT<uint32_t>& p, int n_blocks, hipStream_t s) { return launch_seed_t(p, n_blocks, s); }
 hipError_t launch_seed(const SeedParamsT<uint64_t>& p, int n_blocks, hipStream_t s) { return launch_seed_t(p, n_blocks, s); }
 
-hipError_t launch_plan(const PlanParams& p, hipStream_t s) {
-  if (p.n_reads == 0) return hipSuccess;
-  hipLaunchKernelGGL(dev::plan_kernel, dim3((unsigned)((p.n_reads + 255) / 256)), dim3(256), 0, s, p);
-  return hipGetLastError();
-}
-
 template <class C>
-static hipError_t launch_pack_reads_t(const PackParamsT<C>& p, hipStream_t s) {
-  if (p.n_reads == 0) return hipSuccess;
-  hipLaunchKernelGGL(dev::pack_reads_kernel<C>, dim3((unsigned)((p.n_reads + 255) / 256)), dim3(256), 0, s, p);
+static hipError_t launch_plan_pack_t(const PlanParams& pl, const PackParamsT<C>& pk, hipStream_t s) {
+  if (pl.n_reads == 0) return hipSuccess;
+  hipLaunchKernelGGL(dev::plan_pack_kernel<C>, dim3((unsigned)((pl.n_reads + 255) / 256)), dim3(256), 0, s, pl, pk);
   return hipGetLastError();
 }
-hipError_t launch_pack_reads(const PackParamsT<uint32_t>& p, hipStream_t s) { return launch_pack_reads_t(p, s); }
-hipError_t launch_pack_reads(const PackParamsT<uint64_t>& p, hipStream_t s) { return launch_pack_reads_t(p, s); }
+hipError_t launch_plan_pack(const PlanParams& pl, const PackParamsT<uint32_t>& pk, hipStream_t s) { return launch_plan_pack_t(pl, pk, s); }
+hipError_t launch_plan_pack(const PlanParams& pl, const PackParamsT<uint64_t>& pk, hipStream_t s) { return launch_plan_pack_t(pl, pk, s); }
 
 template <class C>
 static hipError_t launch_expand_t(const ExpandParamsT<C>& p, hipStream_t s) {

@@ -1,5 +1,5 @@
 // kernels_util.hip -- small plumbing kernels: exclusive prefix sums that turn
-// per-read counts into offsets (count -> scan -> fill), u32 -> u64 widening.
+// per-read counts into offsets (count -> scan -> fill).
 #include <hip/hip_runtime.h>
 
 #include "launch.h"
@@ -9,7 +9,7 @@ namespace dev {
 
 constexpr int SCAN_THREADS = 256;
 constexpr int SCAN_ITEMS = 8;
-constexpr int SCAN_TILE = SCAN_THREADS * SCAN_ITEMS;
+static_assert(SCAN_TILE == SCAN_THREADS * SCAN_ITEMS, "launch.h: SCAN_TILE");
 
 // exclusive scan of `v` over the block (256 threads); returns the thread's prefix, total in *tot
 __device__ uint64_t block_excl_scan(uint64_t v, uint64_t* sh, uint64_t* tot) {
@@ -72,9 +72,64 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_add_kernel(uint64_t* out, u
     if (base + k < n) out[base + k] += add;
 }
 
-__global__ void widen_kernel(const uint32_t* in, uint64_t* out, uint64_t n) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = in[i];
+// Two arrays in one pass (alignment counts, u32, and op bytes, u64): the tile sums of `a` in tile_sums[0 .. tiles), those
+// of `b` behind them
+__global__ __launch_bounds__(SCAN_THREADS) void scan2_tiles_kernel(const uint32_t* in_a, const uint64_t* in_b, uint64_t* out_a,
+                                                                   uint64_t* out_b, uint64_t n, uint64_t* tile_sums) {
+  __shared__ uint64_t sh[SCAN_THREADS];
+  const uint64_t base = (uint64_t)blockIdx.x * SCAN_TILE + (uint64_t)threadIdx.x * SCAN_ITEMS;
+  uint64_t va[SCAN_ITEMS], vb[SCAN_ITEMS], sa = 0, sb = 0;
+#pragma unroll
+  for (int k = 0; k < SCAN_ITEMS; k++) {
+    va[k] = (base + k < n) ? (uint64_t)in_a[base + k] : 0;
+    vb[k] = (base + k < n) ? in_b[base + k] : 0;
+    sa += va[k];
+    sb += vb[k];
+  }
+  uint64_t tot_a, tot_b;
+  uint64_t pre_a = block_excl_scan(sa, sh, &tot_a);
+  uint64_t pre_b = block_excl_scan(sb, sh, &tot_b);
+#pragma unroll
+  for (int k = 0; k < SCAN_ITEMS; k++) {
+    if (base + k < n) {
+      out_a[base + k] = pre_a;
+      out_b[base + k] = pre_b;
+    }
+    pre_a += va[k];
+    pre_b += vb[k];
+  }
+  if (threadIdx.x == 0) {
+    tile_sums[blockIdx.x] = tot_a;
+    tile_sums[gridDim.x + blockIdx.x] = tot_b;
+  }
+}
+
+// two blocks: block 0 scans the tile sums of `a`, block 1 those of `b`
+__global__ __launch_bounds__(SCAN_THREADS) void scan2_sums_kernel(uint64_t* tile_sums, uint64_t n_tiles, uint64_t* total_a,
+                                                                  uint64_t* total_b) {
+  __shared__ uint64_t sh[SCAN_THREADS];
+  uint64_t* sums = tile_sums + (uint64_t)blockIdx.x * n_tiles;
+  uint64_t carry = 0;
+  for (uint64_t b0 = 0; b0 < n_tiles; b0 += SCAN_THREADS) {
+    const uint64_t i = b0 + threadIdx.x;
+    const uint64_t v = (i < n_tiles) ? sums[i] : 0;
+    uint64_t tot;
+    const uint64_t pre = block_excl_scan(v, sh, &tot);
+    if (i < n_tiles) sums[i] = carry + pre;
+    carry += tot;
+  }
+  if (threadIdx.x == 0) *(blockIdx.x ? total_b : total_a) = carry;
+}
+
+__global__ __launch_bounds__(SCAN_THREADS) void scan2_add_kernel(uint64_t* out_a, uint64_t* out_b, uint64_t n, const uint64_t* tile_offs) {
+  const uint64_t base = (uint64_t)blockIdx.x * SCAN_TILE + (uint64_t)threadIdx.x * SCAN_ITEMS;
+  const uint64_t add_a = tile_offs[blockIdx.x], add_b = tile_offs[gridDim.x + blockIdx.x];
+#pragma unroll
+  for (int k = 0; k < SCAN_ITEMS; k++)
+    if (base + k < n) {
+      out_a[base + k] += add_a;
+      out_b[base + k] += add_b;
+    }
 }
 
 // Calibration of the memory-side counters (rocprofv3 FETCH_SIZE) on a gather of known size in the access patterns
@@ -120,21 +175,36 @@ hipError_t launch_calib_gather(const uint8_t* table, uint64_t span, uint64_t n_t
   return hipGetLastError();
 }
 
-size_t scan_tmp_entries(uint64_t n) { return (size_t)((n + dev::SCAN_TILE - 1) / dev::SCAN_TILE) + 1; }
+size_t scan_tmp_entries(uint64_t n) { return (size_t)((n + SCAN_TILE - 1) / SCAN_TILE) + 1; }
 
 // out has n+1 entries: out[i] = sum(in[0..i)), out[n] = total
 hipError_t launch_exclusive_scan_u64(const uint64_t* in, uint64_t* out, uint64_t n, uint64_t* tmp, hipStream_t s) {
   if (n == 0) return hipMemsetAsync(out, 0, 8, s);
-  const uint64_t tiles = (n + dev::SCAN_TILE - 1) / dev::SCAN_TILE;
+  const uint64_t tiles = (n + SCAN_TILE - 1) / SCAN_TILE;
   hipLaunchKernelGGL(dev::scan_tiles_kernel, dim3((unsigned)tiles), dim3(dev::SCAN_THREADS), 0, s, in, out, n, tmp);
   hipLaunchKernelGGL(dev::scan_sums_kernel, dim3(1), dim3(dev::SCAN_THREADS), 0, s, tmp, tiles, out + n);
   hipLaunchKernelGGL(dev::scan_add_kernel, dim3((unsigned)tiles), dim3(dev::SCAN_THREADS), 0, s, out, n, tmp);
   return hipGetLastError();
 }
 
-hipError_t launch_widen_u32_to_u64(const uint32_t* in, uint64_t* out, uint64_t n, hipStream_t s) {
-  if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(dev::widen_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, in, out, n);
+hipError_t launch_scan_tiles_sums_u64(const uint64_t* in, uint64_t* out, uint64_t n, uint64_t* tmp, hipStream_t s) {
+  if (n == 0) return hipMemsetAsync(out, 0, 8, s);
+  const uint64_t tiles = (n + SCAN_TILE - 1) / SCAN_TILE;
+  hipLaunchKernelGGL(dev::scan_tiles_kernel, dim3((unsigned)tiles), dim3(dev::SCAN_THREADS), 0, s, in, out, n, tmp);
+  hipLaunchKernelGGL(dev::scan_sums_kernel, dim3(1), dim3(dev::SCAN_THREADS), 0, s, tmp, tiles, out + n);
+  return hipGetLastError();
+}
+
+hipError_t launch_exclusive_scan2(const uint32_t* in_a, const uint64_t* in_b, uint64_t* out_a, uint64_t* out_b, uint64_t n,
+                                  uint64_t* tmp, hipStream_t s) {
+  if (n == 0) {
+    hipError_t e = hipMemsetAsync(out_a, 0, 8, s);
+    return e != hipSuccess ? e : hipMemsetAsync(out_b, 0, 8, s);
+  }
+  const uint64_t tiles = (n + SCAN_TILE - 1) / SCAN_TILE;
+  hipLaunchKernelGGL(dev::scan2_tiles_kernel, dim3((unsigned)tiles), dim3(dev::SCAN_THREADS), 0, s, in_a, in_b, out_a, out_b, n, tmp);
+  hipLaunchKernelGGL(dev::scan2_sums_kernel, dim3(2), dim3(dev::SCAN_THREADS), 0, s, tmp, tiles, out_a + n, out_b + n);
+  hipLaunchKernelGGL(dev::scan2_add_kernel, dim3((unsigned)tiles), dim3(dev::SCAN_THREADS), 0, s, out_a, out_b, n, tmp);
   return hipGetLastError();
 }
 

@@ -132,6 +132,19 @@ hipError_t launch_seed(const SeedParamsT<uint32_t>& p, int n_blocks, hipStream_t
 hipError_t launch_seed(const SeedParamsT<uint64_t>& p, int n_blocks, hipStream_t s);
 hipError_t launch_sanitize(const uint8_t* in, uint8_t* out, uint64_t n, uint64_t n_padded, hipStream_t s);
 
+// What a run of the read-level pipeline zeroes before its first kernel, done by the sanitising launch itself
+// (launch_sanitize_reset): the aligner's control block, the per-read statuses and the 16 bytes in front of the
+// sanitised reads; the counters are copied to their snapshot row on the way (a replay restores them from there).
+struct RunResetParams {
+  uint4* ctl;          // control block (aligner_internal.h, CTL_*), ctl_vec4 x 16 bytes
+  uint32_t ctl_vec4;
+  uint4* status;       // r_status, status_vec4 x 16 bytes (>= n_reads + 1 words; the buffer's slack takes the rounding)
+  uint64_t status_vec4;
+  uint4* san_head;     // the 16 bytes in front of `out`
+  unsigned long long* counters;  // [THM_N_COUNTERS] -> [THM_N_COUNTERS .. 2 THM_N_COUNTERS)
+};
+hipError_t launch_sanitize_reset(const uint8_t* in, uint8_t* out, uint64_t n, uint64_t n_padded, const RunResetParams& rp, hipStream_t s);
+
 // After the seed stage: list the reads of the fast class with >= HEAVY_HITS hits (heavy[0 .. counts[2])), the reads
 // of the slow class (slow[0 .. counts[5])), and give reads beyond every class their status.
 struct PlanParams {
@@ -153,11 +166,10 @@ struct PlanParams {
   uint32_t* read_n_alns;       // zeroed for unsupported reads
   uint64_t* read_op_bytes;
 };
-hipError_t launch_plan(const PlanParams& p, hipStream_t s);
 
 // Everything the extend kernel needs to start on a read, in one 64-byte record (one scalar load instead of a chain of
 // dependent ones: offsets, SMEM run, candidate slice, first SMEM, its first suffix-array entry).  Written by
-// pack_reads_kernel after the seed stage and the hit-count scan.
+// plan_pack_kernel after the seed stage and the hit-count scan.
 template <class C>
 struct ReadRecT {
   uint64_t base_off;   // first base of the read in the sanitised batch
@@ -179,12 +191,15 @@ struct PackParamsT {
   const SmemT<C>* smems;
   const uint64_t* read_smem_off;
   const uint32_t* read_smem_cnt;
-  const uint64_t* read_cand_off;  // [n_reads + 1]
+  uint64_t* read_cand_off;        // [n_reads + 1]: tile-local prefixes of read_hits on entry (launch_scan_tiles_sums_u64),
+                                  // the final offsets on exit ([n_reads], the total, is final already)
+  const uint64_t* tile_offs;      // [tiles of SCAN_TILE reads] offset of each tile
   const int* fault_seed;
   ReadRecT<C>* recs;
 };
-hipError_t launch_pack_reads(const PackParamsT<uint32_t>& p, hipStream_t s);
-hipError_t launch_pack_reads(const PackParamsT<uint64_t>& p, hipStream_t s);
+// plan + pack in one thread-per-read launch, which also finishes the scan of the hit counts (its add phase)
+hipError_t launch_plan_pack(const PlanParams& pl, const PackParamsT<uint32_t>& pk, hipStream_t s);
+hipError_t launch_plan_pack(const PlanParams& pl, const PackParamsT<uint64_t>& pk, hipStream_t s);
 
 // expand SMEMs into Mem lists (thm_smems_batch)
 template <class C>
@@ -204,6 +219,14 @@ hipError_t launch_expand(const ExpandParamsT<uint64_t>& p, hipStream_t s);
 hipError_t launch_exclusive_scan_u64(const uint64_t* in, uint64_t* out, uint64_t n, uint64_t* block_tmp,
                                      hipStream_t s);
 size_t scan_tmp_entries(uint64_t n);
+constexpr unsigned SCAN_TILE = 2048;  // entries per workgroup of the scan kernels
+// The first two phases of that scan only: out[i] = prefix within i's tile of SCAN_TILE entries, block_tmp[t] = offset of
+// tile t, out[n] = total.  The caller's next kernel adds block_tmp[i / SCAN_TILE] itself (plan_pack_kernel).
+hipError_t launch_scan_tiles_sums_u64(const uint64_t* in, uint64_t* out, uint64_t n, uint64_t* block_tmp, hipStream_t s);
+// Two arrays in one pass: out_a = exclusive scan of in_a (u32 counts), out_b = of in_b, n+1 entries each;
+// block_tmp holds 2 * scan_tmp_entries(n) words.
+hipError_t launch_exclusive_scan2(const uint32_t* in_a, const uint64_t* in_b, uint64_t* out_a, uint64_t* out_b, uint64_t n,
+                                  uint64_t* block_tmp, hipStream_t s);
 
 // candidate alignment as the extend kernel stores it (device scratch)
 struct Cand {
@@ -271,7 +294,8 @@ struct ExtendParamsT {
   unsigned long long* n_contract;   // reads that ended with THM_ERR_OUT_OF_CONTRACT (tells the host to fetch the statuses)
   unsigned long long* counters;
   // [waves of this launch][THM_N_COUNTERS]: every wave leaves its counts in its own row (plain stores) and
-  // launch_counters_reduce adds the rows to `counters` afterwards.  (Twelve atomics per wave on one cache line, 61 000 per
+  // launch_counters_reduce adds the rows to `counters` afterwards and zeroes them again (a wave without work writes
+  // nothing: its row must be zero when the launch starts).  (Twelve atomics per wave on one cache line, 61 000 per
   // launch at ~88 M/s, all at the end of the launch when the waves leave: 0.17 ms of a 4 ms launch.)
   unsigned long long* wave_counters;
   unsigned int* queue;
@@ -499,8 +523,8 @@ struct CompactParams {
   uint64_t heavy_cap;
 };
 hipError_t launch_compact(const CompactParams& p, hipStream_t s);
-// counters[k] += sum over rows of wave_counters[row][k]
-hipError_t launch_counters_reduce(const unsigned long long* wave_counters, uint32_t n_rows, unsigned long long* counters, hipStream_t s);
+// counters[k] += sum over rows of wave_counters[row][k]; every row read is left zeroed for the next run
+hipError_t launch_counters_reduce(unsigned long long* wave_counters, uint32_t n_rows, unsigned long long* counters, hipStream_t s);
 
 // align_seed_hit (reference src/aligner.rs:198-314) for caller-chosen hits (thm_align_seed_hits_batch): one hit per
 // wavefront, no align_read policy around it.  One launch per band class, like the wave-per-read kernels: register-
@@ -536,7 +560,6 @@ hipError_t launch_seed_hits(const SeedHitParamsT<uint64_t>& p, int cpl, int n_bl
 
 hipError_t launch_calib_gather(const uint8_t* table, uint64_t span, uint64_t n_threads, int pattern, unsigned long long* sink,
                                hipStream_t s);
-hipError_t launch_widen_u32_to_u64(const uint32_t* in, uint64_t* out, uint64_t n, hipStream_t s);
 
 // Run-length CIGARs and summaries of serialised op streams (kernels_cigar.hip; thm_aln_digest), one stream per
 // wavefront.  With `alns` the launch covers 2 * n_alns streams -- stream 2i is the genome op stream of alns[i],

@@ -4,8 +4,8 @@
 //
 // One batch = count -> scan -> fill on the device:
 //   seed kernels    SMEMs per read (pool + per-read run), hit counts
-//   plan kernel     lists: reads with many hits (longest jobs first), reads of the slow class
-//   scan            hit counts -> per-read slice of the candidate array
+//   scan            hit counts -> per-read slice of the candidate array (its last phase is the plan kernel's)
+//   plan kernel     lists: reads with many hits (longest jobs first), reads of the slow class; a record per read
 //   extend kernel   align_read per read; accepted alignments into the slice,
 //                   op streams into a bump-allocated pool; final order list.
 //                   Reads whose band or length exceeds what the register-resident kernel
@@ -76,17 +76,18 @@ const DeviceIndexT<uint64_t>& dev_view<uint64_t>(const thm_aligner* a) {
   return a->dix->view64;
 }
 
+// finish_scan: the hit-count scan runs to its end here (thm_smems_batch); a full run leaves its last phase to
+// plan_pack_kernel
 template <class C>
-int enqueue_seed_t(thm_aligner* a, uint32_t min_seed_len) {
+int enqueue_seed_t(thm_aligner* a, uint32_t min_seed_len, bool finish_scan) {
   const uint64_t n = a->n_reads;
   hipStream_t s = a->stream;
   HIPCHK(a, a->s_off.ensure((n + 1) * 8));
   HIPCHK(a, a->s_cnt.ensure((n + 1) * 4));
   HIPCHK(a, a->s_hits.ensure((n + 1) * 8));
   HIPCHK(a, a->s_cand_off.ensure((n + 2) * 8));
-  HIPCHK(a, a->scan_tmp.ensure(scan_tmp_entries(n + 1) * 8 + 64));
-  HIPCHK(a, a->r_status.ensure((n + 1) * 4));
-  HIPCHK(a, hipMemsetAsync(a->r_status.p, 0, (n + 1) * 4, s));
+  HIPCHK(a, a->scan_tmp.ensure(2 * scan_tmp_entries(n + 1) * 8 + 64));  // (twice: the two-array scan of the output offsets)
+  HIPCHK(a, a->r_status.ensure((n + 1) * 4 + 16));
   // typical: 1-2 SMEMs per read; waves take the pool in 256-entry slices, hence the fixed slack
   const uint64_t smem_min = a->dbg_smem_cap ? a->dbg_smem_cap : n * 4 + (4u << 20);
   if (a->smem_cap < smem_min) a->smem_cap = smem_min;
@@ -95,8 +96,19 @@ int enqueue_seed_t(thm_aligner* a, uint32_t min_seed_len) {
   // to_ascii_uppercase (src/aligner.rs:125) + sanitising, once per run for both kernels
   // (16 bytes in front: a left extension is read in whole 8-byte words that may begin a few bytes before the first read)
   HIPCHK(a, a->r_san.ensure(a->n_bases + 256 + 16));
-  HIPCHK(a, hipMemsetAsync(a->r_san.p, 0, 16, s));
-  HIPCHK(a, launch_sanitize(a->r_bases.as<uint8_t>(), a->r_san.as<uint8_t>() + 16, a->n_bases, a->n_bases + 128, s));
+  // The same launch starts the run: control block (list counts, cursors, fault words, the queue words of both
+  // stages), per-read statuses and the 16 bytes in front zeroed, counters copied to their snapshot row (as they stood
+  // before this attempt, so that a replay after a pool overflow does not count twice).
+  {
+    RunResetParams rp;
+    rp.ctl = a->d_ctl.as<uint4>();
+    rp.ctl_vec4 = (uint32_t)(thm_aligner::CTL_BYTES / 16);
+    rp.status = a->r_status.as<uint4>();
+    rp.status_vec4 = ((n + 1) * 4 + 15) / 16;
+    rp.san_head = a->r_san.as<uint4>();
+    rp.counters = a->d_counters.as<unsigned long long>();
+    HIPCHK(a, launch_sanitize_reset(a->r_bases.as<uint8_t>(), a->r_san.as<uint8_t>() + 16, a->n_bases, a->n_bases + 128, rp, s));
+  }
   // length classes of the seed stage (launch.h): short reads take the byte-per-position paths
   uint64_t n_long = 0;
   uint32_t max_short = 0, max_long = 0;
@@ -122,11 +134,6 @@ int enqueue_seed_t(thm_aligner* a, uint32_t min_seed_len) {
   HIPCHK(a, a->s_work_reads.ensure((n + 1) * 8));
   HIPCHK(a, a->s_work_long.ensure((n_long + 1) * 8));
   HIPCHK(a, a->s_work_cells.ensure((std::max(cells, n) + 1) * 8));
-  HIPCHK(a, a->s_work_counts.ensure(128));
-  HIPCHK(a, hipMemsetAsync(a->s_work_counts.p, 0, 128, s));
-  int rc = reset_queue(a);
-  if (rc != THM_OK) return rc;
-  HIPCHK(a, hipMemsetAsync(a->d_cursors.p, 0, 64, s));
   const int n_blocks = blocks_for(a, n, std::min(seed_select_lds_bytes(std::max(max_short, 1u)), SEED_SELECT_LDS_LIMIT));
   SeedParamsT<C> sp;
   sp.ix = dev_view<C>(a);
@@ -181,13 +188,34 @@ int enqueue_seed_t(thm_aligner* a, uint32_t min_seed_len) {
   }
   HIPCHK(a, launch_seed(sp, n_blocks, s));
   // hit counts -> offsets of each read's slice (also the Mem offsets of thm_smems_batch)
-  HIPCHK(a, launch_exclusive_scan_u64(a->s_hits.as<uint64_t>(), a->s_cand_off.as<uint64_t>(), n,
-                                      a->scan_tmp.as<uint64_t>(), s));
+  if (finish_scan)
+    HIPCHK(a, launch_exclusive_scan_u64(a->s_hits.as<uint64_t>(), a->s_cand_off.as<uint64_t>(), n, a->scan_tmp.as<uint64_t>(), s));
+  else
+    HIPCHK(a, launch_scan_tiles_sums_u64(a->s_hits.as<uint64_t>(), a->s_cand_off.as<uint64_t>(), n, a->scan_tmp.as<uint64_t>(), s));
   return THM_OK;
 }
 
-int enqueue_seed(thm_aligner* a, uint32_t min_seed_len) {
-  return a->dix->wide ? enqueue_seed_t<uint64_t>(a, min_seed_len) : enqueue_seed_t<uint32_t>(a, min_seed_len);
+int enqueue_seed(thm_aligner* a, uint32_t min_seed_len, bool finish_scan) {
+  return a->dix->wide ? enqueue_seed_t<uint64_t>(a, min_seed_len, finish_scan) : enqueue_seed_t<uint32_t>(a, min_seed_len, finish_scan);
+}
+
+// the extend stage's lists and the per-read records, one launch (kernels_seed.hip, plan_pack_kernel)
+template <class C>
+int enqueue_plan_pack_t(thm_aligner* a, const PlanParams& pp) {
+  HIPCHK(a, a->e_recs.ensure((a->n_reads + 1) * sizeof(ReadRecT<C>)));
+  PackParamsT<C> pk;
+  pk.sa = dev_view<C>(a).sa;
+  pk.offsets = a->r_offsets.as<uint64_t>();
+  pk.n_reads = a->n_reads;
+  pk.smems = a->s_smems.as<SmemT<C>>();
+  pk.read_smem_off = a->s_off.as<uint64_t>();
+  pk.read_smem_cnt = a->s_cnt.as<uint32_t>();
+  pk.read_cand_off = a->s_cand_off.as<uint64_t>();
+  pk.tile_offs = a->scan_tmp.as<uint64_t>();
+  pk.fault_seed = a->d_fault.as<int>();
+  pk.recs = a->e_recs.as<ReadRecT<C>>();
+  HIPCHK(a, launch_plan_pack(pp, pk, a->stream));
+  return THM_OK;
 }
 
 // Length classes of the extend stage for the current options.  Band and buffer sizes grow with the read
@@ -234,21 +262,7 @@ int enqueue_extend_t(thm_aligner* a, const ExtClasses& cls, uint32_t mk_cap_slow
   ep.reads.n_reads = n;
   ep.opts = a->opts;
   ep.smems = a->s_smems.as<SmemT<C>>();
-  // one record per read (offsets, SMEM run, candidate slice, first SMEM and its first occurrence)
-  HIPCHK(a, a->e_recs.ensure((n + 1) * sizeof(ReadRecT<C>)));
-  {
-    PackParamsT<C> pk;
-    pk.sa = ep.ix.sa;
-    pk.offsets = a->r_offsets.as<uint64_t>();
-    pk.n_reads = n;
-    pk.smems = ep.smems;
-    pk.read_smem_off = a->s_off.as<uint64_t>();
-    pk.read_smem_cnt = a->s_cnt.as<uint32_t>();
-    pk.read_cand_off = a->s_cand_off.as<uint64_t>();
-    pk.fault_seed = a->d_fault.as<int>();
-    pk.recs = a->e_recs.as<ReadRecT<C>>();
-    HIPCHK(a, launch_pack_reads(pk, s));
-  }
+  // one record per read (offsets, SMEM run, candidate slice, first SMEM and its first occurrence): enqueue_plan_pack_t
   ep.read_recs = a->e_recs.as<ReadRecT<C>>();
   ep.heavy = a->s_heavy.as<unsigned long long>();
   ep.heavy_count = a->s_work_counts.as<unsigned long long>() + 2;
@@ -268,7 +282,7 @@ int enqueue_extend_t(thm_aligner* a, const ExtClasses& cls, uint32_t mk_cap_slow
   ep.retry_count = a->s_work_counts.as<unsigned long long>() + 5;
   ep.n_contract = a->s_work_counts.as<unsigned long long>() + 6;
   ep.counters = a->d_counters.as<unsigned long long>();
-  ep.queue = a->d_queue.as<unsigned int>();
+  ep.queue = a->d_queue_ext.as<unsigned int>();  // (not the seed stage's words: both sets were zeroed when the run began)
   ep.fault = a->d_fault.as<int>() + 1;
   ep.fault_seed = a->d_fault.as<int>();
   ep.prof = a->d_counters.as<unsigned long long>() + 2 * THM_N_COUNTERS;
@@ -326,8 +340,11 @@ int enqueue_extend_t(thm_aligner* a, const ExtClasses& cls, uint32_t mk_cap_slow
   const int bail_blocks = tpr ? std::min(ext_blocks, a->n_cu) : 0;
   const uint64_t tpr_rows = (uint64_t)ctl_blocks + (uint64_t)bail_blocks * 4;
   const uint64_t n_rows = main_rows + team_rows + slow_waves + tpr_rows;
+  // The rows are zero from one run to the next (launch_counters_reduce zeroes what it read, and no launch writes past
+  // its run's n_rows): only a new allocation is zeroed here -- or the rows of an enqueue that failed half way.
   HIPCHK(a, a->e_wcnt.ensure(n_rows * THM_N_COUNTERS * 8 + 64));
-  HIPCHK(a, hipMemsetAsync(a->e_wcnt.p, 0, n_rows * THM_N_COUNTERS * 8, s));
+  if (a->wcnt_clean_cap != a->e_wcnt.cap) HIPCHK(a, hipMemsetAsync(a->e_wcnt.p, 0, a->e_wcnt.cap, s));
+  a->wcnt_clean_cap = 0;
   ep.wave_counters = a->e_wcnt.as<unsigned long long>();
   ep.skip_scan = 0;
   if (tpr) {
@@ -492,17 +509,16 @@ int enqueue_extend_t(thm_aligner* a, const ExtClasses& cls, uint32_t mk_cap_slow
     HIPCHK(a, launch_extend(ep, 0, blocks, s));
   }
   HIPCHK(a, launch_counters_reduce(a->e_wcnt.as<unsigned long long>(), (uint32_t)n_rows, a->d_counters.as<unsigned long long>(), s));
+  a->wcnt_clean_cap = a->e_wcnt.cap;
   return THM_OK;
 }
 
 int enqueue_run(thm_aligner* a) {
   const uint64_t n = a->n_reads;
   hipStream_t s = a->stream;
-  // counters as they stood before this attempt, so that a replay after a pool overflow does not count twice
-  HIPCHK(a, hipMemcpyAsync(a->d_counters.as<uint8_t>() + THM_N_COUNTERS * 8, a->d_counters.p, THM_N_COUNTERS * 8,
-                           hipMemcpyDeviceToDevice, s));
   HIPCHK(a, hipEventRecord(a->ev[0], s));
-  int rc = enqueue_seed(a, (uint32_t)a->opts.min_seed_len);
+  // (the seed stage's first kernel zeroes the run's control words and takes the counter snapshot)
+  int rc = enqueue_seed(a, (uint32_t)a->opts.min_seed_len, false);
   if (rc != THM_OK) return rc;
   HIPCHK(a, hipEventRecord(a->ev[1], s));
 
@@ -517,7 +533,6 @@ int enqueue_run(thm_aligner* a) {
   HIPCHK(a, a->e_rel.ensure(a->cand_cap * 4));
   HIPCHK(a, a->e_ops.ensure(a->cand_ops_cap + 64));
   HIPCHK(a, a->e_nalns.ensure((n + 1) * 4));
-  HIPCHK(a, a->e_nalns64.ensure((n + 1) * 8));
   HIPCHK(a, a->e_opbytes.ensure((n + 1) * 8));
   HIPCHK(a, a->e_aln_off.ensure((n + 2) * 8));
   HIPCHK(a, a->e_ops_off.ensure((n + 2) * 8));
@@ -526,7 +541,6 @@ int enqueue_run(thm_aligner* a) {
   HIPCHK(a, a->s_heavy.ensure((n + 1) * 8));
   HIPCHK(a, a->s_slow.ensure((n + 1) * 8));
   HIPCHK(a, a->s_team.ensure((n + 1) * 8));
-  HIPCHK(a, hipMemsetAsync(a->d_queue.p, 0, thm::QUEUE_BYTES, s));
 
   // length classes for the current options; lists for the extend stage
   const uint32_t mk_cap_slow = std::max<uint32_t>(a->ix->max_tx_exons, 1);
@@ -555,7 +569,8 @@ int enqueue_run(thm_aligner* a) {
   pp.read_status = a->r_status.as<int32_t>();
   pp.read_n_alns = a->e_nalns.as<uint32_t>();
   pp.read_op_bytes = a->e_opbytes.as<uint64_t>();
-  HIPCHK(a, launch_plan(pp, s));
+  rc = a->dix->wide ? enqueue_plan_pack_t<uint64_t>(a, pp) : enqueue_plan_pack_t<uint32_t>(a, pp);
+  if (rc != THM_OK) return rc;
   HIPCHK(a, hipEventRecord(a->ev[2], s));
 
   rc = a->dix->wide ? enqueue_extend_t<uint64_t>(a, cls, mk_cap_slow, retry_possible)
@@ -563,11 +578,8 @@ int enqueue_run(thm_aligner* a) {
   if (rc != THM_OK) return rc;
   HIPCHK(a, hipEventRecord(a->ev[3], s));
 
-  HIPCHK(a, launch_widen_u32_to_u64(a->e_nalns.as<uint32_t>(), a->e_nalns64.as<uint64_t>(), n, s));
-  HIPCHK(a, launch_exclusive_scan_u64(a->e_nalns64.as<uint64_t>(), a->e_aln_off.as<uint64_t>(), n,
-                                      a->scan_tmp.as<uint64_t>(), s));
-  HIPCHK(a, launch_exclusive_scan_u64(a->e_opbytes.as<uint64_t>(), a->e_ops_off.as<uint64_t>(), n,
-                                      a->scan_tmp.as<uint64_t>(), s));
+  HIPCHK(a, launch_exclusive_scan2(a->e_nalns.as<uint32_t>(), a->e_opbytes.as<uint64_t>(), a->e_aln_off.as<uint64_t>(),
+                                   a->e_ops_off.as<uint64_t>(), n, a->scan_tmp.as<uint64_t>(), s));
   CompactParams cp;
   cp.n_reads = n;
   cp.read_cand_off = a->s_cand_off.as<uint64_t>();
@@ -803,13 +815,11 @@ int32_t thm_smems_batch(thm_aligner* a, const uint8_t* bases, const uint64_t* of
   hipStream_t s = a->stream;
   RunStatus st;
   for (int attempt = 0;; attempt++) {
-    if (attempt == 0)
-      HIPCHK(a, hipMemcpyAsync(a->d_counters.as<uint8_t>() + THM_N_COUNTERS * 8, a->d_counters.p, THM_N_COUNTERS * 8,
-                               hipMemcpyDeviceToDevice, s));
-    else
+    // (the counters' snapshot is taken by the seed stage's first kernel; a replay starts from it)
+    if (attempt > 0)
       HIPCHK(a, hipMemcpyAsync(a->d_counters.p, a->d_counters.as<uint8_t>() + THM_N_COUNTERS * 8, THM_N_COUNTERS * 8,
                                hipMemcpyDeviceToDevice, s));
-    rc = enqueue_seed(a, (uint32_t)min_seed_len);
+    rc = enqueue_seed(a, (uint32_t)min_seed_len, true);
     if (rc != THM_OK) return rc;
     rc = read_status(a, &st);
     if (rc != THM_OK) return rc;
