@@ -292,6 +292,7 @@ enum {
 enum { THM_T_SEED = 0, THM_T_PLAN = 1, THM_T_EXTEND = 2, THM_T_COMPACT = 3, THM_T_TOTAL = 4,
        THM_T_CIGAR = 5, /* the two CIGAR passes of the last thm_batch_fetch_cigars (not part of THM_T_TOTAL) */
        THM_T_BAM = 6,   /* the size and emit passes of the last BAM fetch, thermite_io.h (likewise)    */
+       THM_T_BGZF = 7,  /* deflate, scan and compaction of the last BGZF fetch, thermite_io.h (likewise) */
        THM_N_TIMINGS = 8 };
 
 typedef struct thm_index thm_index;

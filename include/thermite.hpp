@@ -190,34 +190,46 @@ class Aligner {
       }
     return out;
   }
+  // names, reads and qualities (may be empty: none) back to back, as thm_read_batch wants them
+  struct ReadPack {
+    std::vector<std::uint8_t> bases, q, nm;
+    std::vector<std::uint64_t> off{0}, noff{0};
+    bool has_quals;
+    ReadPack(const std::vector<std::string>& names, const std::vector<std::string>& reads, const std::vector<std::string>& quals)
+        : has_quals(!quals.empty()) {
+      if (names.size() != reads.size() || (!quals.empty() && quals.size() != reads.size()))
+        throw Error(THM_ERR_INVALID_ARG, "one name (and one quality string) per read");
+      for (std::size_t r = 0; r < reads.size(); r++) {
+        bases.insert(bases.end(), reads[r].begin(), reads[r].end());
+        off.push_back(bases.size());
+        nm.insert(nm.end(), names[r].begin(), names[r].end());
+        noff.push_back(nm.size());
+        if (!quals.empty()) {
+          if (quals[r].size() != reads[r].size()) throw Error(THM_ERR_INVALID_ARG, "quality string and read differ in length");
+          q.insert(q.end(), quals[r].begin(), quals[r].end());
+        }
+      }
+    }
+    thm_read_batch view() const {
+      static const std::uint8_t none = 0;
+      thm_read_batch rb;
+      rb.n_reads = off.size() - 1;
+      rb.n_bases = bases.size();
+      rb.bases = bases.empty() ? &none : bases.data();
+      rb.offsets = off.data();
+      rb.quals = !has_quals ? nullptr : (q.empty() ? &none : q.data());
+      rb.names = nm.empty() ? &none : nm.data();
+      rb.name_off = noff.data();
+      return rb;
+    }
+  };
   // The records of the writer loop (src/aligner.rs:54-116) for `reads`, BAM-encoded on the device (thm_align_batch_bam):
   // result[r] holds the records of read r as byte strings, each beginning with its block_size -- one per alignment, or
   // the unmapped record.  `quals` may be empty (no qualities: 0xff); flags: THM_BAM_NO_ANNOTATION_TAGS.
   std::vector<std::vector<std::string>> align_reads_bam(const std::vector<std::string>& names, const std::vector<std::string>& reads,
                                                         const std::vector<std::string>& quals, std::uint32_t flags = 0) {
-    if (names.size() != reads.size() || (!quals.empty() && quals.size() != reads.size()))
-      throw Error(THM_ERR_INVALID_ARG, "one name (and one quality string) per read");
-    std::vector<std::uint8_t> bases, q, nm;
-    std::vector<std::uint64_t> off{0}, noff{0};
-    for (std::size_t r = 0; r < reads.size(); r++) {
-      bases.insert(bases.end(), reads[r].begin(), reads[r].end());
-      off.push_back(bases.size());
-      nm.insert(nm.end(), names[r].begin(), names[r].end());
-      noff.push_back(nm.size());
-      if (!quals.empty()) {
-        if (quals[r].size() != reads[r].size()) throw Error(THM_ERR_INVALID_ARG, "quality string and read differ in length");
-        q.insert(q.end(), quals[r].begin(), quals[r].end());
-      }
-    }
-    const std::uint8_t none = 0;
-    thm_read_batch rb;
-    rb.n_reads = reads.size();
-    rb.n_bases = bases.size();
-    rb.bases = bases.empty() ? &none : bases.data();
-    rb.offsets = off.data();
-    rb.quals = quals.empty() ? nullptr : (q.empty() ? &none : q.data());
-    rb.names = nm.empty() ? &none : nm.data();
-    rb.name_off = noff.data();
+    const ReadPack pack(names, reads, quals);
+    const thm_read_batch rb = pack.view();
     thm_bam_view v;
     check(thm_align_batch_bam(h_.get(), &rb, flags, &v));
     std::vector<std::vector<std::string>> out(reads.size());
@@ -228,6 +240,27 @@ class Aligner {
         out[r].emplace_back((const char*)v.data + at, (std::size_t)bs + 4);
         at += (std::uint64_t)bs + 4;
       }
+    return out;
+  }
+
+  // The same records as complete BGZF members, encoded and deflated on the device (thm_align_batch_bgzf): no BAM header
+  // and no end-of-file block -- Writer::header() + data + Writer::trailer() is a valid .bam file.
+  struct BgzfBlocks {
+    std::string data;                      // the members back to back
+    std::vector<std::uint64_t> block_off;  // [n_blocks + 1]
+    std::uint64_t n_records = 0, n_raw_bytes = 0;
+  };
+  BgzfBlocks align_reads_bgzf(const std::vector<std::string>& names, const std::vector<std::string>& reads,
+                              const std::vector<std::string>& quals, std::uint32_t flags = 0) {
+    const ReadPack pack(names, reads, quals);
+    const thm_read_batch rb = pack.view();
+    thm_bgzf_view v;
+    check(thm_align_batch_bgzf(h_.get(), &rb, flags, &v));
+    BgzfBlocks out;
+    out.data.assign((const char*)v.data, (std::size_t)v.n_bytes);
+    out.block_off.assign(v.block_off, v.block_off + v.n_blocks + 1);
+    out.n_records = v.n_records;
+    out.n_raw_bytes = v.n_raw_bytes;
     return out;
   }
 

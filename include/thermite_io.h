@@ -127,6 +127,34 @@ int32_t thm_batch_fetch_bam(thm_aligner* a, uint32_t flags, thm_bam_view* out);
 /* upload_reads + run + the fetch above */
 int32_t thm_align_batch_bam(thm_aligner* a, const thm_read_batch* reads, uint32_t flags, thm_bam_view* out);
 
+/* ------------------------------------------------- BGZF blocks from the device */
+
+/* The same records, BGZF-compressed on the device: the byte stream of a thm_bam_view cut every 0xff00 bytes (as the
+ * host writer cuts it; a cut may fall inside a record) and every block deflated there into a complete BGZF member --
+ * the 18-byte header with the BC subfield, one raw DEFLATE stream (a dynamic-Huffman block over an LZ77 parse, or a
+ * stored block when that is not larger), CRC-32 and ISIZE.  Member b is data[block_off[b] .. block_off[b+1]).  No BAM
+ * header and no end-of-file block: thm_writer_header + data + thm_writer_trailer is a valid .bam file.  Inflated, the
+ * members give the data of the thm_bam_view of the same run and flags, n_raw_bytes long; no records: n_blocks == 0.
+ * The bytes depend on the input bytes only: the same records compress to the same members on every call and aligner. */
+typedef struct thm_bgzf_view {
+  uint64_t n_reads, n_records;
+  uint64_t n_raw_bytes;          /* what the blocks inflate to: thm_bam_view.n_bytes of the same run */
+  uint64_t n_blocks, n_bytes;
+  const uint8_t* data;           /* [n_bytes]: n_blocks complete BGZF members, back to back */
+  const uint64_t* block_off;     /* [n_blocks+1] */
+  uint64_t n_failed_reads;
+  const int32_t* read_status;
+} thm_bgzf_view;
+/* Stands where thm_batch_fetch_bam stands and takes its flags, preconditions and errors (same codes and messages, which
+ * name thm_batch_fetch_bam: it is that call's record passes that report them); failed reads as there.  Any of the four
+ * fetches may follow the others for the same run, in any order.  Only the members, their offsets and the statuses are
+ * copied back, into two pinned buffer sets of their own, used alternately: a thm_bgzf_view stays valid until the
+ * second-next call on this aligner that returns one, and no other view is invalidated.  Counters and the other
+ * timings are untouched; THM_T_BGZF is set.  THM_BAM_LEVEL does not apply. */
+int32_t thm_batch_fetch_bgzf(thm_aligner* a, uint32_t flags, thm_bgzf_view* out);
+/* upload_reads + run + the fetch above */
+int32_t thm_align_batch_bgzf(thm_aligner* a, const thm_read_batch* reads, uint32_t flags, thm_bgzf_view* out);
+
 /* -------------------------------------------------------- SAM / PAF writer */
 
 /* OutputFormat, src/aln_writer.rs:16-21 */
@@ -187,7 +215,10 @@ typedef struct thm_run_stats {
  * format+write) over batches of `batch_reads` reads (0 = 250 000).
  * THM_BAM_DEVICE=1 in the environment and THM_FMT_BAM: the records are encoded on the device
  * (thm_batch_upload_reads / thm_batch_fetch_bam) and the formatting stage only deflates (thm_writer_wrap_bam);
- * the file's inflated bytes are the same. */
+ * the file's inflated bytes are the same.
+ * THM_BAM_DEVICE=2 and THM_FMT_BAM: the records are encoded and BGZF-compressed on the device (thm_batch_fetch_bgzf)
+ * and the formatting stage only passes the members on; the file's inflated bytes are the same again, the compressed
+ * ones are the device encoder's (THM_BAM_LEVEL does not apply), and n_output_bytes counts them. */
 int32_t thm_align_files(thm_aligner* a, const char* const* fastq_paths, uint32_t n_paths, const char* output_path,
                         int32_t format, uint64_t batch_reads, uint32_t n_threads, thm_run_stats* stats);
 /* The same over several aligners -- one per GPU of the node, all over one index (the shape of ThermiteAligner: Clone +

@@ -57,7 +57,7 @@ N_COUNTERS = 16
 COUNTER_NAMES = ["reads", "aligned", "unmapped", "alns", "exonic", "intronic", "intergenic", "smems", "hits",
                  "swg_calls", "dp_cells", "dp_cols", "op_bytes", "window_bytes"]
 N_TIMINGS = 8
-TIMING_NAMES = ["seed", "plan", "extend", "compact", "total", "cigar", "bam"]
+TIMING_NAMES = ["seed", "plan", "extend", "compact", "total", "cigar", "bam", "bgzf"]
 
 OK, ERR_INVALID_ARG, ERR_NO_DEVICE, ERR_HIP, ERR_UNSUPPORTED, ERR_OUT_OF_CONTRACT, ERR_OOM, ERR_INTERNAL = (
     0, -1, -2, -3, -4, -5, -6, -7)
@@ -134,6 +134,14 @@ class BamView(C.Structure):
                 ("read_rec_off", C.c_void_p), ("n_failed_reads", C.c_uint64), ("read_status", C.c_void_p)]
 
 
+class BgzfView(C.Structure):
+    """thm_bgzf_view (include/thermite_io.h)"""
+
+    _fields_ = [("n_reads", C.c_uint64), ("n_records", C.c_uint64), ("n_raw_bytes", C.c_uint64), ("n_blocks", C.c_uint64),
+                ("n_bytes", C.c_uint64), ("data", C.c_void_p), ("block_off", C.c_void_p), ("n_failed_reads", C.c_uint64),
+                ("read_status", C.c_void_p)]
+
+
 BAM_NO_ANNOTATION_TAGS = 1
 
 # every symbol include/thermite.h declares
@@ -156,6 +164,7 @@ IO_ABI_SYMBOLS = [
     "thm_writer_format_batch", "thm_writer_trailer", "thm_align_files", "thm_align_files_multi",
     "thm_writer_format_batch_cigars",
     "thm_batch_upload_reads", "thm_batch_fetch_bam", "thm_align_batch_bam", "thm_writer_wrap_bam",
+    "thm_batch_fetch_bgzf", "thm_align_batch_bgzf",
 ]
 ERR_IO, ERR_FORMAT = -8, -9
 FMT_PAF, FMT_SAM, FMT_BAM = 0, 1, 2
@@ -294,6 +303,12 @@ def lib():
     L.thm_batch_fetch_bam.argtypes = [vp, u32, vp]
     L.thm_align_batch_bam.restype = i32
     L.thm_align_batch_bam.argtypes = [vp, vp, u32, vp]
+    L.thm_batch_fetch_bgzf.restype = i32
+    L.thm_batch_fetch_bgzf.argtypes = [vp, u32, vp]
+    L.thm_align_batch_bgzf.restype = i32
+    L.thm_align_batch_bgzf.argtypes = [vp, vp, u32, vp]
+    L.thm_debug_bgzf_device.restype = i32
+    L.thm_debug_bgzf_device.argtypes = [vp, vp, u64, vp, u64, vp, vp]
     L.thm_writer_wrap_bam.restype = i32
     L.thm_writer_wrap_bam.argtypes = [vp, vp, vp]
     L.thm_align_files.restype = i32
@@ -588,6 +603,30 @@ class BamResult:
         return out
 
 
+class BgzfResult:
+    """thm_bgzf_view copied out, or (copy=False) numpy views of the aligner's pinned result set: the BAM records of the
+    batch as complete BGZF members back to back (no BAM header, no end-of-file block) and the byte offset of every member."""
+
+    def __init__(self, view, copy=True):
+        self.n_reads = view.n_reads
+        self.n_records = view.n_records
+        self.n_raw_bytes = view.n_raw_bytes
+        self.n_blocks = view.n_blocks
+        self.data = _copy(view.data, view.n_bytes, np.uint8, copy)
+        self.block_off = _copy(view.block_off, view.n_blocks + 1, "<u8", copy)
+        self.n_failed = view.n_failed_reads
+        self.status = _copy(view.read_status, view.n_reads, "<i4", copy) if view.read_status else None
+
+    @property
+    def nbytes(self):
+        """bytes the fetch moved to the host"""
+        return sum(a.nbytes for a in (self.data, self.block_off, self.status) if a is not None)
+
+    def block(self, b):
+        """member b as a byte string"""
+        return self.data[int(self.block_off[b]): int(self.block_off[b + 1])].tobytes()
+
+
 def cigar_text(words):
     """BAM CIGAR words -> SAM text ('*' when there are none)"""
     return "".join("%d%s" % (int(w) >> 4, "MIDNSHP=X"[int(w) & 15]) for w in words) or "*"
@@ -676,6 +715,26 @@ class Aligner:
         v = BamView()
         self._chk(lib().thm_align_batch_bam(self.h, C.byref(rb), flags, C.byref(v)))
         return BamResult(v, copy)
+
+    def fetch_bgzf(self, flags=0, copy=True):
+        """thm_batch_fetch_bgzf: the run's BAM records, encoded and BGZF-compressed on the device"""
+        v = BgzfView()
+        self._chk(lib().thm_batch_fetch_bgzf(self.h, flags, C.byref(v)))
+        return BgzfResult(v, copy)
+
+    def align_batch_bgzf(self, batch, flags=0, copy=True):
+        rb, keep = read_batch_struct(batch)
+        v = BgzfView()
+        self._chk(lib().thm_align_batch_bgzf(self.h, C.byref(rb), flags, C.byref(v)))
+        return BgzfResult(v, copy)
+
+    def debug_bgzf_device(self, data):
+        """test hook: bytes through the device BGZF encoder -> (the members back to back, their number)"""
+        src = np.frombuffer(bytes(data), np.uint8) if len(data) else np.zeros(1, np.uint8)
+        out = np.empty(len(data) + 31 * (len(data) // 0xff00 + 1) + 64, np.uint8)
+        n, nb = C.c_uint64(0), C.c_uint64(0)
+        self._chk(lib().thm_debug_bgzf_device(self.h, src.ctypes.data, len(data), out.ctypes.data, len(out), C.byref(n), C.byref(nb)))
+        return out[: n.value].tobytes(), nb.value
 
     def cigar_encode_batch(self, ops, off):
         """thm_cigar_encode_batch: serialised op streams ops[off[i]:off[i+1]] -> CigarResult, one digest per stream"""

@@ -241,7 +241,8 @@ void thm_aligner_free(thm_aligner* a) {
                  &a->c_scan_tmp, &a->c_flags, &a->c_dig, &a->c_words, &a->c_in_ops, &a->c_in_off,
                  &a->bn_names, &a->bn_name_off, &a->bn_quals, &a->bt_tx_pool, &a->bt_tx_off, &a->bt_gid_pool, &a->bt_gid_off,
                  &a->bt_gname_pool, &a->bt_gname_off, &a->bt_tx_gene, &a->bt_ref_sq, &a->bm_cnt, &a->bm_first, &a->bm_qn,
-                 &a->bm_rec_read, &a->bm_len, &a->bm_off, &a->bm_out, &a->bm_read_off, &a->bm_err, &a->bm_scan_tmp};
+                 &a->bm_rec_read, &a->bm_len, &a->bm_off, &a->bm_out, &a->bm_read_off, &a->bm_err, &a->bm_scan_tmp,
+                 &a->bz_match, &a->bz_slots, &a->bz_sizes, &a->bz_off, &a->bz_out, &a->bz_scan_tmp, &a->bz_dbg_in};
   for (DBuf* b : all) b->release();
   for (int k = 0; k < 2; k++) {
     a->r_off[k].release();
@@ -256,10 +257,15 @@ void thm_aligner_free(thm_aligner* a) {
     a->bh_data[k].release();
     a->bh_off[k].release();
     a->bh_stat[k].release();
+    a->zh_data[k].release();
+    a->zh_off[k].release();
+    a->zh_stat[k].release();
   }
   for (auto& e : a->ev_cig)
     if (e) (void)hipEventDestroy(e);
   for (auto& e : a->ev_bam)
+    if (e) (void)hipEventDestroy(e);
+  for (auto& e : a->ev_bgzf)
     if (e) (void)hipEventDestroy(e);
   for (auto& e : a->ev)
     if (e) (void)hipEventDestroy(e);

@@ -200,6 +200,13 @@ struct thm_aligner {
   int b_cur = 0;
   int bam_stage = -1;  // emit through LDS and dword stores (1) or byte stores (0); -1: not read from THM_BAM_EMIT yet
   hipEvent_t ev_bam[4] = {nullptr, nullptr, nullptr, nullptr};  // created by the first call
+  // BGZF members on the device (bgzf.hip): per-position scratch of the workgroups, the members in their slots, their
+  // sizes and the scan, the members behind one another; the bytes thm_debug_bgzf_device uploads; two pinned host sets
+  // of their own, used alternately
+  DBuf bz_match, bz_slots, bz_sizes, bz_off, bz_out, bz_scan_tmp, bz_dbg_in;
+  HBuf zh_data[2], zh_off[2], zh_stat[2];
+  int z_cur = 0;
+  hipEvent_t ev_bgzf[2] = {nullptr, nullptr};  // created by the first call
 };
 
 inline int fail(thm_aligner* a, int code, const char* fmt, ...) {
@@ -224,6 +231,17 @@ inline int fail(thm_aligner* a, int code, const char* fmt, ...) {
 // cigar.hip: count -> scan -> emit over the streams of `p`; results in c_dig / c_words (synchronises the stream once)
 int run_cigar_passes(thm_aligner* a, thm::CigarParams p, uint64_t n_digests, uint64_t* n_words, unsigned* any_flags);
 int cigar_ensure_events(thm_aligner* a);
+// bam.hip: everything of thm_batch_fetch_bam up to the copies -- after it the records of the run are in bm_out on the
+// device and the per-read byte offsets in bm_read_off (both fetches that hand records out start here; the messages name
+// thm_batch_fetch_bam whichever it is).  Of the timings only `timing`, the caller's own, is touched: zeroed once the
+// arguments have passed; ev_bam[0..3] are left recorded around the size and emit passes.
+struct BamOnDevice {
+  uint64_t n_reads = 0, n_alns = 0, n_records = 0, n_bytes = 0;
+  bool any_failed = false;  // a read of the batch may have failed: the statuses are worth copying
+};
+int bam_records_on_device(thm_aligner* a, uint32_t flags, int timing, BamOnDevice* r);
+// n statuses in `st` (copied from r_status after bam_records_on_device said any_failed) -> the view's two fields
+void bam_failed_reads(const int32_t* st, uint64_t n, uint64_t* n_failed, const int32_t** status);
 int reset_queue(thm_aligner* a);
 int grid_blocks(const thm_aligner* a, uint64_t n_items, int waves_per_block, int blocks_per_cu);
 // pipeline.hip: what THM_SEED_FILL and THM_TEAM_DIV_PER_CU resolved to (read once per process)

@@ -57,9 +57,7 @@ int ensure_tables(thm_aligner* a) {
 
 }  // namespace
 
-extern "C" {
-
-int32_t thm_batch_upload_reads(thm_aligner* a, const thm_read_batch* reads) {
+extern "C" int32_t thm_batch_upload_reads(thm_aligner* a, const thm_read_batch* reads) {
   if (!a || !reads) return THM_ERR_INVALID_ARG;
   const uint64_t n = reads->n_reads;
   if (!reads->offsets || !reads->name_off || (n && !reads->names && reads->name_off[n] > 0))
@@ -85,9 +83,7 @@ int32_t thm_batch_upload_reads(thm_aligner* a, const thm_read_batch* reads) {
   return THM_OK;
 }
 
-int32_t thm_batch_fetch_bam(thm_aligner* a, uint32_t flags, thm_bam_view* out) {
-  if (!a || !out) return THM_ERR_INVALID_ARG;
-  memset(out, 0, sizeof(*out));
+int bam_records_on_device(thm_aligner* a, uint32_t flags, int timing, BamOnDevice* r) {
   if (flags & ~(uint32_t)THM_BAM_NO_ANNOTATION_TAGS) return fail(a, THM_ERR_INVALID_ARG, "thm_batch_fetch_bam: unknown flag bits 0x%x", flags);
   if (!a->uploaded || !a->reads_named)
     return fail(a, THM_ERR_INVALID_ARG, "thm_batch_fetch_bam: the batch was not uploaded by thm_batch_upload_reads (no names)");
@@ -105,7 +101,7 @@ int32_t thm_batch_fetch_bam(thm_aligner* a, uint32_t flags, thm_bam_view* out) {
   }
   const uint64_t n = a->n_reads;
   hipStream_t s = a->stream;
-  a->timings[THM_T_BAM] = 0;
+  a->timings[timing] = 0;
   const thm_index* ix = a->ix;
   BamParams p;
   memset(&p, 0, sizeof p);
@@ -193,25 +189,51 @@ int32_t thm_batch_fetch_bam(thm_aligner* a, uint32_t flags, thm_bam_view* out) {
   if (err & BAM_ERR_DIGEST_FLAGS) return fail(a, THM_ERR_INTERNAL, "thm_writer_format_batch: a run of 2^28 or more has no CIGAR word");
   if (err & BAM_ERR_CIGAR_WORDS) return fail(a, THM_ERR_INTERNAL, "thm_writer_format_batch: malformed op stream");
   if (err & BAM_ERR_RANGE) return fail(a, THM_ERR_INTERNAL, "thm_writer_format_batch: alignment record out of range");
-  // ---- emit, offsets, and the copies
-  const int k = a->b_cur ^= 1;  // the other set still backs the previous view
-  HBuf& h_data = a->bh_data[k];
-  HBuf& h_off = a->bh_off[k];
-  HBuf& h_stat = a->bh_stat[k];
+  // ---- emit and offsets
   HIPCHK(a, a->bm_out.ensure(n_bytes + 16));
-  HIPCHK(a, h_data.ensure(n_bytes));
-  HIPCHK(a, h_off.ensure((n + 1) * 8));
   p.out = a->bm_out.as<uint8_t>();
   HIPCHK(a, hipEventRecord(a->ev_bam[2], s));
   HIPCHK(a, launch_bam_emit(p, a->bam_stage == 1, a->n_cu, s));
   HIPCHK(a, hipEventRecord(a->ev_bam[3], s));
   HIPCHK(a, launch_bam_offsets(p, s));
-  if (n_bytes) HIPCHK(a, hipMemcpyAsync(h_data.p, a->bm_out.p, n_bytes, hipMemcpyDeviceToHost, s));
-  HIPCHK(a, hipMemcpyAsync(h_off.p, a->bm_read_off.p, (n + 1) * 8, hipMemcpyDeviceToHost, s));
   uint64_t n_beyond = a->n_over;
   for (const auto& lc : a->len_hist)
     if (lc.first > a->slow_max_len) n_beyond += lc.second;
-  const bool any_failed = n_beyond || n_contract;
+  r->n_reads = n;
+  r->n_alns = n_alns;
+  r->n_records = n_rec;
+  r->n_bytes = n_bytes;
+  r->any_failed = n_beyond || n_contract;
+  return THM_OK;
+}
+
+void bam_failed_reads(const int32_t* st, uint64_t n, uint64_t* n_failed, const int32_t** status) {
+  uint64_t bad = 0;
+  for (uint64_t i = 0; i < n; i++) bad += st[i] != THM_OK;
+  *n_failed = bad;
+  *status = bad ? st : nullptr;
+}
+
+extern "C" {
+
+int32_t thm_batch_fetch_bam(thm_aligner* a, uint32_t flags, thm_bam_view* out) {
+  if (!a || !out) return THM_ERR_INVALID_ARG;
+  memset(out, 0, sizeof(*out));
+  BamOnDevice r;
+  int rc = bam_records_on_device(a, flags, THM_T_BAM, &r);
+  if (rc != THM_OK) return rc;
+  const uint64_t n = r.n_reads, n_rec = r.n_records, n_bytes = r.n_bytes;
+  const bool any_failed = r.any_failed;
+  hipStream_t s = a->stream;
+  // ---- the copies
+  const int k = a->b_cur ^= 1;  // the other set still backs the previous view
+  HBuf& h_data = a->bh_data[k];
+  HBuf& h_off = a->bh_off[k];
+  HBuf& h_stat = a->bh_stat[k];
+  HIPCHK(a, h_data.ensure(n_bytes));
+  HIPCHK(a, h_off.ensure((n + 1) * 8));
+  if (n_bytes) HIPCHK(a, hipMemcpyAsync(h_data.p, a->bm_out.p, n_bytes, hipMemcpyDeviceToHost, s));
+  HIPCHK(a, hipMemcpyAsync(h_off.p, a->bm_read_off.p, (n + 1) * 8, hipMemcpyDeviceToHost, s));
   if (any_failed) {
     HIPCHK(a, h_stat.ensure((n + 1) * 4));
     HIPCHK(a, hipMemcpyAsync(h_stat.p, a->r_status.p, n * 4, hipMemcpyDeviceToHost, s));
@@ -225,13 +247,7 @@ int32_t thm_batch_fetch_bam(thm_aligner* a, uint32_t flags, thm_bam_view* out) {
   out->n_bytes = n_bytes;
   out->data = h_data.as<uint8_t>();
   out->read_rec_off = h_off.as<uint64_t>();
-  if (any_failed) {
-    const int32_t* st = h_stat.as<int32_t>();
-    uint64_t bad = 0;
-    for (uint64_t i = 0; i < n; i++) bad += st[i] != THM_OK;
-    out->n_failed_reads = bad;
-    out->read_status = bad ? st : nullptr;
-  }
+  if (any_failed) bam_failed_reads(h_stat.as<int32_t>(), n, &out->n_failed_reads, &out->read_status);
   return THM_OK;
 }
 

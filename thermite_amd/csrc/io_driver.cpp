@@ -50,6 +50,8 @@ struct Slot {
   thm::HostBatch reads;
   thm_batch_view res;  // into the pinned result buffers of the aligner that ran it (two sets per aligner, used alternately)
   thm_bam_view bam;    // ... or, with THM_BAM_DEVICE=1, the BAM records encoded on the device (likewise two sets)
+  thm_bgzf_view bgzf;  // ... or, with THM_BAM_DEVICE=2, their BGZF members deflated there (likewise)
+  uint64_t bgzf_aligned = 0;  // reads of the batch with an alignment (the members do not show it)
   bool aligned = false;
 };
 
@@ -228,7 +230,9 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
   if (batch_reads == 0) batch_reads = 250000;
   // THM_BAM_DEVICE=1: BAM records are encoded on the device (thm_batch_fetch_bam) and only deflated here
   const char* bam_dev_env = getenv("THM_BAM_DEVICE");
-  const bool bam_device = format == THM_FMT_BAM && bam_dev_env && !strcmp(bam_dev_env, "1");
+  // THM_BAM_DEVICE=2: ... and BGZF-compressed there too (thm_batch_fetch_bgzf): the formatting stage passes bytes on
+  const bool bgzf_device = format == THM_FMT_BAM && bam_dev_env && !strcmp(bam_dev_env, "2");
+  const bool bam_device = bgzf_device || (format == THM_FMT_BAM && bam_dev_env && !strcmp(bam_dev_env, "1"));
   const thm_index* ix = thm_aligner_index(aligners[0]);
   for (uint32_t i = 1; i < n_aligners; i++)
     if (thm_aligner_index(aligners[i]) != ix) {
@@ -528,10 +532,13 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
             done_cv.wait(g, [&] { return n_written > must || sh.failed(); });
           }
           const auto t2 = Clock::now();
-          if (grc == THM_OK) grc = sh.step([&] { return bam_device ? thm_batch_fetch_bam(a, 0, &s->bam) : thm_batch_fetch(a, &s->res); });
-          const uint64_t n_res = bam_device ? s->bam.n_reads : s->res.n_reads;
-          const int32_t* res_status = bam_device ? s->bam.read_status : s->res.read_status;
-          if (grc == THM_OK && (bam_device ? s->bam.n_failed_reads : s->res.n_failed_reads)) {
+          if (grc == THM_OK) grc = sh.step([&] {
+            if (!bgzf_device) return bam_device ? thm_batch_fetch_bam(a, 0, &s->bam) : thm_batch_fetch(a, &s->res);
+            return thm::batch_fetch_bgzf(a, 0, &s->bgzf, &s->bgzf_aligned);
+          });
+          const uint64_t n_res = bgzf_device ? s->bgzf.n_reads : bam_device ? s->bam.n_reads : s->res.n_reads;
+          const int32_t* res_status = bgzf_device ? s->bgzf.read_status : bam_device ? s->bam.read_status : s->res.read_status;
+          if (grc == THM_OK && (bgzf_device ? s->bgzf.n_failed_reads : bam_device ? s->bam.n_failed_reads : s->res.n_failed_reads)) {
             // the reference aligns every read or panics; a read this build cannot take fails the run, by name
             uint64_t bad = 0;
             while (bad < n_res && res_status[bad] == THM_OK) bad++;
@@ -579,6 +586,7 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
       Slot* s = nullptr;
       uint64_t seq = 0;
       std::vector<const std::string*> chunks;
+      std::vector<std::pair<const char*, size_t>> spans;  // what is written: the chunks, or the members of a thm_bgzf_view
       std::vector<uint64_t> at;
       bool stop = false;
     };
@@ -612,15 +620,15 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
         }
         if (j->stop) break;
         const auto t1 = Clock::now();
-        std::vector<char> good(j->chunks.size(), 1);
-        auto put = [&](size_t c) { good[c] = write_all(j->chunks[c]->data(), j->chunks[c]->size(), j->at[c]) ? 1 : 0; };
-        if (positional && j->chunks.size() > 1) {
+        std::vector<char> good(j->spans.size(), 1);
+        auto put = [&](size_t c) { good[c] = write_all(j->spans[c].first, j->spans[c].second, j->at[c]) ? 1 : 0; };
+        if (positional && j->spans.size() > 1) {
           std::vector<std::thread> th;
-          for (size_t c = 1; c < j->chunks.size(); c++) th.emplace_back(put, c);
+          for (size_t c = 1; c < j->spans.size(); c++) th.emplace_back(put, c);
           put(0);
           for (auto& x : th) x.join();
         } else {
-          for (size_t c = 0; c < j->chunks.size(); c++) put(c);
+          for (size_t c = 0; c < j->spans.size(); c++) put(c);
         }
         for (char g : good)
           if (!g) sh.set(THM_ERR_IO, "short write");
@@ -656,19 +664,29 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
         WriteJob& j = jobs[k];
         const thm_bam_view& bv = s->bam;
         const int wrc = sh.step([&] {
+          // nothing to format: the members leave as one chunk, written from the aligner's pinned set (the GPU thread
+          // waits for this batch to be written before the fetch that reuses the set)
+          if (bgzf_device) return (int)THM_OK;
           return bam_device ? thm::writer_wrap_bam_chunks(ws[k], &bv, j.chunks) : thm::writer_format_chunks(ws[k], &rb, &v, j.chunks);
         });
         st.format_s += secs(t0, Clock::now());
         if (wrc != THM_OK) {
           sh.set(wrc, thm_last_error(nullptr));
         } else {
-          j.at.resize(j.chunks.size());
-          for (size_t c = 0; c < j.chunks.size(); c++) {
+          j.spans.clear();
+          if (bgzf_device) j.spans.emplace_back((const char*)s->bgzf.data, (size_t)s->bgzf.n_bytes);
+          else
+            for (const std::string* c : j.chunks) j.spans.emplace_back(c->data(), c->size());
+          j.at.resize(j.spans.size());
+          for (size_t c = 0; c < j.spans.size(); c++) {
             j.at[c] = file_off;
-            file_off += j.chunks[c]->size();
-            st.n_output_bytes += j.chunks[c]->size();
+            file_off += j.spans[c].second;
+            st.n_output_bytes += j.spans[c].second;
           }
-          if (bam_device) {
+          if (bgzf_device) {
+            st.n_aligned_reads += s->bgzf_aligned;
+            st.n_records += s->bgzf.n_records;
+          } else if (bam_device) {
             // a read is unmapped when its first record carries flag 4 (bytes 18 .. 19 of the record)
             for (uint64_t r = 0; r < bv.n_reads; r++) st.n_aligned_reads += !(bv.data[bv.read_rec_off[r] + 18] & 4);
             st.n_records += bv.n_records;

@@ -97,6 +97,10 @@ int writer_format_chunks(thm_writer* w, const thm_read_batch* reads, const thm_b
 // thm_writer_wrap_bam without the final concatenation (chunks as above)
 int writer_wrap_bam_chunks(thm_writer* w, const thm_bam_view* view, std::vector<const std::string*>& chunks);
 
+// bgzf.hip: thm_batch_fetch_bgzf, which also reports the reads of the batch with at least one alignment (the view
+// holds compressed bytes only; the file driver counts them in its statistics); n_aligned_reads may be null
+int batch_fetch_bgzf(thm_aligner* a, uint32_t flags, thm_bgzf_view* out, uint64_t* n_aligned_reads);
+
 // contig name_id -> index of its @SQ line (the BAM refID), build_sam_header's order (src/aln_writer.rs:256-276);
 // `sq`: the lines' (name, length), when asked for
 std::vector<int32_t> sq_of_name(const thm_index* ix, std::vector<std::pair<std::string, uint64_t>>* sq);

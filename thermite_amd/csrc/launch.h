@@ -630,5 +630,21 @@ hipError_t launch_bam_size(const BamParams& p, hipStream_t s);
 hipError_t launch_bam_emit(const BamParams& p, bool stage, int n_cu, hipStream_t s);
 hipError_t launch_bam_offsets(const BamParams& p, hipStream_t s);
 
+// ---- BGZF members on the device (kernels_bgzf.hip, bgzf_device.h; host side bgzf.hip) ----
+// deflate (one workgroup per block of 0xff00 input bytes: a complete member into the block's slot, its size) -> scan of
+// the sizes (launch_exclusive_scan_u64) -> compact (the members behind one another).
+struct BgzfParams {
+  const uint8_t* in;  // [n], 4-byte aligned
+  uint64_t n, n_blocks;
+  uint32_t* match;      // [bgzf_grid(n_blocks, n_cu) * 0xff00]  per-position scratch of the workgroups
+  uint8_t* slots;       // [n_blocks * 65536]
+  uint64_t* sizes;      // [n_blocks]      deflate
+  const uint64_t* off;  // [n_blocks + 1]  scan of sizes
+  uint8_t* out;         // [off[n_blocks]], 4-byte aligned
+};
+unsigned bgzf_grid(uint64_t n_blocks, int n_cu);
+hipError_t launch_bgzf_deflate(const BgzfParams& p, int n_cu, hipStream_t s);
+hipError_t launch_bgzf_compact(const BgzfParams& p, int n_cu, hipStream_t s);
+
 }  // namespace thm
 #endif

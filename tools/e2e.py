@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """End-to-end file throughput on the GPU box (tuning aid, not the benchmark):
 FASTQ on disk -> thm_align_files -> SAM / PAF.   python tools_e2e.py [ref_len] [n_reads] [threads] [rep]
---bam-device[=RUNS]: only FASTQ -> BAM and .fastq.gz -> BAM, each RUNS times (default 4) with THM_BAM_DEVICE off and on
+--bam-device[=RUNS]: only FASTQ -> BAM and .fastq.gz -> BAM, each RUNS times (default 4) with THM_BAM_DEVICE 0, 1 and 2
 in turn (the driver reads the switch at every call), in one session."""
 import os, sys, time
 BAM_RUNS = 0
@@ -104,15 +104,30 @@ if BAM_RUNS:
     run("warm-up: bam from plain fastq, host encoder", [big], capi.FMT_BAM, "/tmp/thm_e2e_out.bam", 1)
     sums = {}
     for k in range(BAM_RUNS):
-        for dev in ("0", "1"):
+        for dev in ("0", "1", "2"):
             os.environ["THM_BAM_DEVICE"] = dev
-            what = "device encoder" if dev == "1" else "host encoder"
+            what = {"0": "host encoder", "1": "device encoder", "2": "device encoder and deflate"}[dev]
             run("bam from plain fastq, %s, round %d" % (what, k), [big], capi.FMT_BAM, "/tmp/thm_e2e_out.%s.bam" % dev, 1)
             run("bam from two .gz, %s, round %d" % (what, k), [gz, gz2], capi.FMT_BAM, "/tmp/thm_e2e_out.gz%s.bam" % dev, 1)
     same = digest("/tmp/thm_e2e_out.0.bam") == digest("/tmp/thm_e2e_out.1.bam") and digest("/tmp/thm_e2e_out.gz0.bam") == digest("/tmp/thm_e2e_out.gz1.bam")
     print("BAM files of the two encoders are %s" % ("IDENTICAL" if same else "DIFFERENT"), flush=True)
+
+    def inflated_digest(p):
+        import hashlib
+        h = hashlib.sha256()
+        with gzip.open(p, "rb") as f:
+            for blk in iter(lambda: f.read(1 << 24), b""):
+                h.update(blk)
+        return h.hexdigest()
+
+    # the device's members are other bytes than the host's blocks: the files are compared inflated
+    same2 = inflated_digest("/tmp/thm_e2e_out.2.bam") == inflated_digest("/tmp/thm_e2e_out.0.bam")
+    print("BAM file of the device deflate inflates to %s; %d bytes against %d" % ("THE SAME BYTES" if same2 else "OTHER BYTES", os.path.getsize("/tmp/thm_e2e_out.2.bam"),
+                                                                                 os.path.getsize("/tmp/thm_e2e_out.0.bam")), flush=True)
+    same = same and same2
     a.close()
-    for f in (path, big, gz, gz2, "/tmp/thm_e2e_out.bam", "/tmp/thm_e2e_out.0.bam", "/tmp/thm_e2e_out.1.bam", "/tmp/thm_e2e_out.gz0.bam", "/tmp/thm_e2e_out.gz1.bam"):
+    for f in (path, big, gz, gz2, "/tmp/thm_e2e_out.bam", "/tmp/thm_e2e_out.0.bam", "/tmp/thm_e2e_out.1.bam", "/tmp/thm_e2e_out.2.bam", "/tmp/thm_e2e_out.gz0.bam",
+              "/tmp/thm_e2e_out.gz1.bam", "/tmp/thm_e2e_out.gz2.bam"):
         if os.path.exists(f):
             os.remove(f)
     assert same

@@ -1,11 +1,14 @@
 #!/usr/bin/env python3
 """Quick stage timing on the GPU box (tuning aid, not the benchmark):
-python tools/perf.py [ref_len] [n_reads] [opts] [--cigars] [--bam]
+python tools/perf.py [ref_len] [n_reads] [opts] [--cigars] [--bam] [--bgzf]
 --cigars: on the resident batch, thm_batch_fetch against thm_batch_fetch_cigars -- milliseconds and bytes moved to the
 host by each, and the device time of the two CIGAR passes (THM_T_CIGAR).
 --bam: on the resident batch, thm_batch_fetch_bam with both forms of the emit kernel (THM_BAM_EMIT) -- milliseconds,
 bytes, THM_T_BAM -- beside thm_batch_fetch plus the host's record encoding of the same batch (thm_writer_format_batch
-at THM_BAM_LEVEL=0 minus thm_writer_wrap_bam of the same records: stored blocks, so the difference is the encoding)."""
+at THM_BAM_LEVEL=0 minus thm_writer_wrap_bam of the same records: stored blocks, so the difference is the encoding).
+--bgzf (without --bam, which turns the host's deflate off): on the resident batch, thm_batch_fetch_bgzf -- milliseconds,
+bytes, THM_T_BGZF -- beside thm_batch_fetch_bam plus thm_writer_wrap_bam of the same records on 16 threads and on 1, and
+the compressed sizes of the device encoder, the host encoder and zlib level 1 over the device's cuts."""
 import sys, time
 import numpy as np
 sys.path.insert(0, __import__("os").path.dirname(__import__("os").path.dirname(__import__("os").path.abspath(__file__))))
@@ -13,7 +16,8 @@ from thermite_amd import capi, synth
 
 cigars = "--cigars" in sys.argv
 bam = "--bam" in sys.argv
-sys.argv = [x for x in sys.argv if x not in ("--cigars", "--bam")]
+bgzf = "--bgzf" in sys.argv
+sys.argv = [x for x in sys.argv if x not in ("--cigars", "--bam", "--bgzf")]
 if bam:
     __import__("os").environ["THM_BAM_LEVEL"] = "0"  # (read once, by the first BGZF block of the process)
 ref_len = int(sys.argv[1]) if len(sys.argv) > 1 else 4000000
@@ -105,6 +109,54 @@ for name, opts in (("ci", capi.CI_OPTS), ("default", capi.DEFAULT_OPTS)):
                   "median %.2f ms (min %.2f max %.2f); encoding = %.2f ms; outputs %s" % (threads, m1, lo1, hi1, m2, lo2, hi2, m1 - m2,
                                                                                          "equal" if o1 == o2 else "DIFFER"), flush=True)
             w.close()
+    if bgzf:
+        import zlib
+        K2 = 7
+        names = [b"SYN:%d 1:N:0:ACGT" % i for i in range(n)]
+        batch = dict(bases=bases, offsets=off, quals=np.full(len(bases), ord("F"), np.uint8), names=np.frombuffer(b"".join(names), np.uint8),
+                     name_off=np.cumsum([0] + [len(x) for x in names]).astype("<u8"))
+
+        def med(f):
+            ms = []
+            for _ in range(K2):
+                t0 = time.perf_counter()
+                r = f()
+                ms.append((time.perf_counter() - t0) * 1e3)
+            return r, float(np.median(ms)), min(ms), max(ms)
+
+        b = capi.Aligner(ix, opts)
+        b.upload_reads(batch)
+        b.run(); b.sync()
+        for _ in range(2):   # buffers grow
+            b.fetch_bgzf(copy=False)
+            b.fetch_bam(copy=False)
+        tz = []
+        for _ in range(K2):
+            b.fetch_bgzf(copy=False)
+            tz.append(b.timings()["bgzf"])
+        # alternately, in one session
+        mz, mg = [], []
+        for _ in range(K2):
+            t0 = time.perf_counter(); z = b.fetch_bgzf(copy=False); mz.append((time.perf_counter() - t0) * 1e3)
+            t0 = time.perf_counter(); g = b.fetch_bam(copy=False); mg.append((time.perf_counter() - t0) * 1e3)
+        print("         fetch_bgzf  median %.2f ms (min %.2f max %.2f)  %d bytes to the host  %d blocks of %d raw bytes  THM_T_BGZF median %.3f ms (min %.3f max %.3f)" % (
+            float(np.median(mz)), min(mz), max(mz), z.nbytes, z.n_blocks, z.n_raw_bytes, float(np.median(tz)), min(tz), max(tz)), flush=True)
+        print("         fetch_bam   median %.2f ms (min %.2f max %.2f)  %d bytes to the host" % (float(np.median(mg)), min(mg), max(mg), g.nbytes), flush=True)
+        raw = g.data.tobytes()
+        dev_bytes = len(z.data)
+        for threads in (16, 1):
+            w = capi.Writer(ix, capi.FMT_BAM, n_threads=threads)
+            w.wrap_bam(g)
+            o, m, lo, hi = med(lambda: w.wrap_bam(g))
+            print("         host, %2d threads: wrap_bam (deflate) median %.2f ms (min %.2f max %.2f); fetch_bam + wrap_bam = %.2f ms; %d bytes" % (
+                threads, m, lo, hi, float(np.median(mg)) + m, len(o)), flush=True)
+            w.close()
+        z1 = 0
+        for at in range(0, len(raw), 0xff00):
+            c = zlib.compressobj(1, zlib.DEFLATED, -15)
+            z1 += len(c.compress(raw[at: at + 0xff00]) + c.flush()) + 26
+        print("         compressed sizes of %d record bytes: device %d, host encoder %d, zlib level 1 %d" % (len(raw), dev_bytes, len(o), z1), flush=True)
+        b.close()
     c = dict(zip(capi.COUNTER_NAMES, a.counters().tolist()))
     runs = K + 2
     print("         per read: smems %.2f hits %.2f swg_calls %.2f cols %.1f cells %.0f alns %.2f win_bytes %.0f" % tuple(
