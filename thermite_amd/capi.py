@@ -196,6 +196,9 @@ def lib():
     if hasattr(L, "thm_debug_check_lut"):
         L.thm_debug_check_lut.restype = i32
         L.thm_debug_check_lut.argtypes = [vp]
+    if hasattr(L, "thm_debug_host_lut"):
+        L.thm_debug_host_lut.restype = i32
+        L.thm_debug_host_lut.argtypes = [vp, vp, vp, u64]
     L.thm_index_free.argtypes = [vp]
     L.thm_index_text_len.restype = u64
     L.thm_index_text_len.argtypes = [vp]
@@ -331,6 +334,12 @@ def lib():
     if hasattr(L, "thm_debug_seed_stats"):
         L.thm_debug_seed_stats.restype = i32
         L.thm_debug_seed_stats.argtypes = [vp, vp]
+    if hasattr(L, "thm_debug_seed_direct_stats"):
+        L.thm_debug_seed_direct_stats.restype = i32
+        L.thm_debug_seed_direct_stats.argtypes = [vp, vp]
+    if hasattr(L, "thm_debug_fetch_lut"):
+        L.thm_debug_fetch_lut.restype = i32
+        L.thm_debug_fetch_lut.argtypes = [vp, vp, u64]
     if hasattr(L, "thm_debug_knobs"):
         L.thm_debug_knobs.restype = i32
         L.thm_debug_knobs.argtypes = [vp, vp]
@@ -517,6 +526,16 @@ class Index:
     def check_lut(self):
         """test hook: the k-mer table (built by counting) equals the one read off the suffix array"""
         return lib().thm_debug_check_lut(self.h) == 0
+
+    def debug_host_lut(self):
+        """test hook: the host's k-mer prefix table, 4^kt rows of (lo, hi) in the index's coordinate width"""
+        kt = C.c_uint32()
+        if lib().thm_debug_host_lut(self.h, C.byref(kt), None, 0) != 0:
+            raise ThermiteError(ERR_INTERNAL, "thm_debug_host_lut")
+        out = np.zeros((4 ** kt.value, 2), "<u8" if self.coord_bytes == 8 else "<u4")
+        if lib().thm_debug_host_lut(self.h, C.byref(kt), _ptr(out), out.nbytes) != 0:
+            raise ThermiteError(ERR_INTERNAL, "thm_debug_host_lut")
+        return out
 
     def idx_to_ref(self, idx):
         off = C.c_uint64()
@@ -817,14 +836,17 @@ class Aligner:
         self._chk(lib().thm_debug_set_pool_caps(self.h, smem_cap, cand_cap, ops_cap, C.byref(n)))
         return n.value
 
-    def debug_set_flags(self, tpr=None, rounds=0, seed_infer=None, seed_stats=None):
+    def debug_set_flags(self, tpr=None, rounds=0, seed_infer=None, seed_stats=None, seed_direct=None):
         """test / tuning hook: tpr = False: every read takes the wave-per-read kernels, True: the problem-parallel path
         in front of them (None: keep); rounds = its request rounds (1..8, 0: keep); seed_infer = False: no seed probe
         is decided from its table entry and a neighbouring match (bit 2 of the word; True: bit 4, on again);
-        seed_stats = True: the seed kernels count their probes for debug_seed_stats (bit 3; False: bit 5).  None: keep."""
+        seed_stats = True: the seed kernels count their probes for debug_seed_stats (bit 3; False: bit 5);
+        seed_direct = False: a probe into a single-suffix bucket reads the suffix array although its table entry holds
+        the text position (bit 6; True: bit 7, the position is used again).  None: keep."""
         word = (0 if tpr is None else (2 if tpr else 1)) | (int(rounds) << 8)
         word |= 0 if seed_infer is None else (16 if seed_infer else 4)
         word |= 0 if seed_stats is None else (8 if seed_stats else 32)
+        word |= 0 if seed_direct is None else (128 if seed_direct else 64)
         self._chk(lib().thm_debug_set_flags(self.h, word))
 
     def debug_seed_stats(self):
@@ -832,6 +854,20 @@ class Aligner:
         out = np.zeros(2, "<u8")
         self._chk(lib().thm_debug_seed_stats(self.h, _ptr(out)))
         return int(out[0]), int(out[1])
+
+    def debug_seed_direct_stats(self):
+        """thm_debug_seed_direct_stats: (the device table holds text positions in its single-suffix entries, entries
+        rewritten, full probes of the last batch that took the position from the entry, full probes into a single-suffix
+        bucket that read the suffix array); the last two are counted while seed_stats is on"""
+        out = np.zeros(4, "<u8")
+        self._chk(lib().thm_debug_seed_direct_stats(self.h, _ptr(out)))
+        return tuple(int(x) for x in out)
+
+    def debug_fetch_lut(self, like):
+        """test hook: the device copy of the k-mer table as the kernels read it; `like` = Index.debug_host_lut()"""
+        out = np.zeros_like(like)
+        self._chk(lib().thm_debug_fetch_lut(self.h, _ptr(out), out.nbytes))
+        return out
 
     def debug_set_band_clip(self, max_bw=None):
         """test hook: the register-resident kernels pretend to hold bands up to max_bw only (None: off)"""

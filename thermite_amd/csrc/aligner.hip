@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "aligner_internal.h"
+#include "lut_direct.h"
 
 namespace thm {
 const char* global_error_cstr();
@@ -32,6 +33,12 @@ static int swg_blocks_per_cu() {
     return (v >= 1 && v <= 8) ? v : 4;
   }();
   return v;
+}
+
+// knob THM_LUT_DIRECT=0, read when a device copy of an index is made: the k-mer table stays plain (lut_direct.h; A/B runs)
+static bool lut_direct_wanted() {
+  const char* e = getenv("THM_LUT_DIRECT");
+  return !(e && e[0] == '0');
 }
 
 template <class T>
@@ -94,6 +101,21 @@ static int get_dev_copy(thm_aligner* a) {
       up(d->exon_grid, ix->exon_grid);
       up(d->gene_grid, ix->gene_grid);
     }
+    // text positions into the single-suffix entries of the device table (lut_direct.h): sa and lut are on their way
+    // on this stream; the host tables stay as they are
+    const bool tag = lut_direct_wanted() && (ix->wide ? lutd::can_tag<uint64_t>(ix->n) : lutd::can_tag<uint32_t>(ix->n)) &&
+                     (ix->wide ? !ix->lut64.empty() : !ix->lut.empty());
+    if (tag) {
+      if (e == hipSuccess) e = d->lut_cnt.ensure(16);
+      if (e == hipSuccess) e = hipMemsetAsync(d->lut_cnt.p, 0, 16, s);
+      if (e == hipSuccess)
+        e = ix->wide ? launch_lut_tag(d->lut.as<LutEntryT<uint64_t>>(), d->sa.as<uint64_t>(), ix->lut64.size(), ix->n,
+                                      d->lut_cnt.as<unsigned long long>(), s)
+                     : launch_lut_tag(d->lut.as<LutEntryT<uint32_t>>(), d->sa.as<uint32_t>(), ix->lut.size(), ix->n,
+                                      d->lut_cnt.as<unsigned long long>(), s);
+      if (e == hipSuccess) e = hipMemcpyAsync(&d->lut_tagged, d->lut_cnt.p, 8, hipMemcpyDeviceToHost, s);
+      d->lut_direct = true;
+    }
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) {
       free_dev_copy(d);
@@ -122,6 +144,7 @@ static int get_dev_copy(thm_aligner* a) {
       v.n_txs = (uint32_t)ix->txs.size();
       v.kt = ix->kt;
       v.max_tx_exons = ix->max_tx_exons;
+      v.lut_direct = d->lut_direct ? 1u : 0u;
     };
     memset(&d->view, 0, sizeof d->view);
     memset(&d->view64, 0, sizeof d->view64);
@@ -588,6 +611,10 @@ int32_t thm_debug_set_flags(thm_aligner* a, uint32_t flags) {
   if (flags & 16u) a->dbg_seed_noinfer = false;
   if (flags & 8u) a->dbg_seed_stats = true;
   if (flags & 32u) a->dbg_seed_stats = false;
+  // bit 6: a probe into a single-suffix bucket ignores the text position its table entry holds and reads sa[lo] (the
+  // table stays as it is; lut_direct.h), bit 7: it uses the position again
+  if (flags & 64u) a->dbg_seed_nodirect = true;
+  if (flags & 128u) a->dbg_seed_nodirect = false;
   return THM_OK;
 }
 // thm_debug_seed_stats: the last batch's seed stage, counted when bit 3 of thm_debug_set_flags is set (else zeros) --
@@ -599,6 +626,32 @@ int32_t thm_debug_seed_stats(thm_aligner* a, uint64_t stats[2]) {
   HIPCHK(a, hipSetDevice(a->device));
   HIPCHK(a, hipStreamSynchronize(a->stream));
   HIPCHK(a, hipMemcpy(stats, a->s_work_counts.as<unsigned long long>() + 8, 16, hipMemcpyDeviceToHost));
+  return THM_OK;
+}
+// thm_debug_seed_direct_stats: [0] the device copy of the k-mer table holds text positions (lut_direct.h; 0 under
+// THM_LUT_DIRECT=0 or for a 32-bit table over 2^31 symbols or more), [1] entries the pass rewrote; of the last batch,
+// counted like thm_debug_seed_stats: [2] full probes that took the text position from the table entry, [3] full probes
+// into a single-suffix bucket that read the suffix array
+int32_t thm_debug_seed_direct_stats(thm_aligner* a, uint64_t stats[4]) {
+  if (!a || !stats) return THM_ERR_INVALID_ARG;
+  stats[0] = stats[1] = stats[2] = stats[3] = 0;
+  if (!a->dix) return THM_OK;
+  stats[0] = a->dix->lut_direct ? 1 : 0;
+  stats[1] = a->dix->lut_tagged;
+  if (!a->s_work_counts.p || a->s_work_counts.cap < 128) return THM_OK;
+  HIPCHK(a, hipSetDevice(a->device));
+  HIPCHK(a, hipStreamSynchronize(a->stream));
+  HIPCHK(a, hipMemcpy(stats + 2, a->s_work_counts.as<unsigned long long>() + 10, 16, hipMemcpyDeviceToHost));
+  return THM_OK;
+}
+// test hook: the device copy of the k-mer table as the kernels read it, `bytes` = 4^kt entries of two coordinates
+int32_t thm_debug_fetch_lut(thm_aligner* a, void* out, uint64_t bytes) {
+  if (!a || !out || !a->dix) return THM_ERR_INVALID_ARG;
+  const uint64_t have = a->dix->wide ? a->ix->lut64.size() * sizeof(LutEntryT<uint64_t>) : a->ix->lut.size() * sizeof(LutEntryT<uint32_t>);
+  if (bytes != have) return fail(a, THM_ERR_INVALID_ARG, "thm_debug_fetch_lut: the table has %llu bytes", (unsigned long long)have);
+  HIPCHK(a, hipSetDevice(a->device));
+  HIPCHK(a, hipStreamSynchronize(a->stream));
+  if (bytes) HIPCHK(a, hipMemcpy(out, a->dix->lut.p, bytes, hipMemcpyDeviceToHost));
   return THM_OK;
 }
 // test hook: the register-resident kernels pretend their class holds bands up to `max_bw` only (max_bw + 1 is stored; 0 turns

@@ -75,6 +75,11 @@ struct thm_index::DevCopy {
   int device = -1;
   DBuf text, sa, lut, refs, name_rank, ref_recs, ref_bin, txs, exons, exon_txoff, tx_seq, exon_grid_off, exon_grid, gene_grid_off, gene_grid;
   bool wide = false;                     // which of the two views is valid (thermite_internal.h, "Coordinate width")
+  // lut_direct.h: the pass that runs once behind the upload put text positions into the single-suffix entries of `lut`
+  // (THM_LUT_DIRECT=0, or a 32-bit table over 2^31 symbols or more: plain); how many entries it rewrote
+  bool lut_direct = false;
+  uint64_t lut_tagged = 0;
+  DBuf lut_cnt;                          // the pass's counter (one u64)
   thm::DeviceIndexT<uint32_t> view;
   thm::DeviceIndexT<uint64_t> view64;
 };
@@ -85,7 +90,7 @@ inline void free_dev_copy(thm_index::DevCopy* d) {
   (void)hipGetDevice(&cur);
   (void)hipSetDevice(d->device);
   DBuf* all[] = {&d->text, &d->sa,         &d->lut,    &d->refs,      &d->name_rank, &d->ref_recs, &d->ref_bin, &d->txs,
-                 &d->exons, &d->exon_txoff, &d->tx_seq, &d->exon_grid_off, &d->exon_grid, &d->gene_grid_off, &d->gene_grid};
+                 &d->exons, &d->exon_txoff, &d->tx_seq, &d->exon_grid_off, &d->exon_grid, &d->gene_grid_off, &d->gene_grid, &d->lut_cnt};
   for (DBuf* b : all) b->release();
   (void)hipSetDevice(cur);
   delete d;
@@ -158,6 +163,8 @@ struct thm_aligner {
   // test / tuning hook (thm_debug_set_flags bits 2, 3): seed probes never decided from the table entry and a neighbouring
   // match; seed probes counted (thm_debug_seed_stats)
   bool dbg_seed_noinfer = false, dbg_seed_stats = false;
+  // ... bit 6: a probe into a single-suffix bucket reads sa[lo] although the table entry holds the text position
+  bool dbg_seed_nodirect = false;
   uint32_t n_replays = 0;  // pool-overflow replays since the aligner was created
   bool ran = false, synced = false;
   hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};

@@ -653,6 +653,18 @@ int32_t thm_debug_check_lut(const thm_index* ix) {
   return ok ? THM_OK : THM_ERR_INTERNAL;
 }
 
+// test hook: kt and, with `out`, the host's k-mer table (`bytes` = 4^kt entries of two coordinates)
+int32_t thm_debug_host_lut(const thm_index* ix, uint32_t* kt, void* out, uint64_t bytes) {
+  if (!ix || !kt) return THM_ERR_INVALID_ARG;
+  *kt = ix->kt;
+  if (!out) return THM_OK;
+  const void* src = ix->wide ? (const void*)ix->lut64.data() : (const void*)ix->lut.data();
+  const uint64_t have = ix->wide ? ix->lut64.size() * sizeof(ix->lut64[0]) : ix->lut.size() * sizeof(ix->lut[0]);
+  if (bytes != have) return THM_ERR_INVALID_ARG;
+  if (bytes) memcpy(out, src, bytes);
+  return THM_OK;
+}
+
 uint64_t thm_index_text_len(const thm_index* ix) { return ix ? ix->n : 0; }
 const uint32_t* thm_index_suffix_array(const thm_index* ix) { return (ix && !ix->wide) ? ix->sa.data() : nullptr; }
 

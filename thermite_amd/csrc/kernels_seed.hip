@@ -21,6 +21,7 @@
 #include <algorithm>
 
 #include "launch.h"
+#include "lut_direct.h"
 #include "swg_device.h"
 
 namespace thm {
@@ -109,12 +110,19 @@ __device__ __forceinline__ int lcp_cmp(const uint8_t* tp, const uint8_t* q, int 
 //      search, the better of the two neighbours of the insertion point gives the
 //      match length, two more binary searches give the interval.
 // `known_end` (0: none) is E[a] = a + MS[a] of some position a < pos of the same read with MS[a] >= k, as an earlier
-// probe stored it.  Returns true when the table entry and that end decided the probe (no suffix-array or text read).
+// probe stored it.  Returns MS_DECIDED when the table entry and that end decided the probe (no suffix-array or text read).
+// Where the table is tagged (lut_direct.h) the entry of a one-suffix bucket holds the text position sa[lo] in place of
+// hi = lo + 1: it is decoded right behind the load, everything below sees the plain interval, and step 2 goes from the
+// entry to the text without the dependent read of the suffix array (MS_DIRECT; `use_pos` false: the position is dropped
+// and sa[lo] read, MS_SA_ONE, as with a plain table).
+enum : int { MS_FULL = 0, MS_DECIDED = 1, MS_DIRECT = 2, MS_SA_ONE = 3 };
 template <class C>
-__device__ bool ms_search(const DeviceIndexT<C>& ix, const uint8_t* rd, int L, int pos, int k, int known_end, int& out_d, C& out_lo,
-                          C& out_hi) {
+__device__ int ms_search(const DeviceIndexT<C>& ix, const uint8_t* rd, int L, int pos, int k, int known_end, bool use_pos, int& out_d,
+                         C& out_lo, C& out_hi) {
   C lo = 0, hi = (C)ix.n;
+  C tpos = ~(C)0;  // text position of the bucket's one suffix, from the table entry (all ones: none; a position has the top bit clear)
   int d = 0;
+  int how = MS_FULL;
   const int kt = (int)ix.kt;
   if (kt <= k) {
     uint32_t code = 0;
@@ -129,6 +137,7 @@ __device__ bool ms_search(const DeviceIndexT<C>& ix, const uint8_t* rd, int L, i
       const LutEntryT<C> e = ix.lut[code];
       lo = e.lo;
       hi = e.hi;
+      if (lutd::decode(ix.lut_direct != 0, lo, hi, &tpos) && !use_pos) tpos = ~(C)0;
       d = kt;
       // Shortcut: a single suffix in the bucket and a left neighbour whose match reaches past the kt-mer.
       // Let a < pos be the neighbour, E = known_end = a + MS[a], and pos + kt <= E.  "Match" below is what
@@ -145,13 +154,14 @@ __device__ bool ms_search(const DeviceIndexT<C>& ix, const uint8_t* rd, int L, i
       //     read, and N == N is a match for the neighbour and for this position alike).  In each case the
       //     same two bytes face each other here, so the match from pos stops at E too.
       // Hence MS[pos] = E - pos exactly and the interval is the bucket, which is what the sz == 1 path below
-      // returns (it never changes lo / hi).  Every other case (two or more suffixes, an empty entry, no hint, a
+      // returns (it never changes lo / hi).  With a tagged table the value stored in place of hi is sa[lo] of a
+      // one-suffix bucket, hi was set back to lo + 1 above, and the test below sees that.  Every other case (two or more suffixes, an empty entry, no hint, a
       // hint that ends inside the kt-mer, kt > k, a byte outside ACGT in the kt-mer) takes the full path.
       if (known_end != 0 && hi - lo == 1 && pos + kt <= known_end) {
         out_d = known_end - pos;
         out_lo = lo;
         out_hi = hi;
-        return true;
+        return MS_DECIDED;
       }
     }
   }
@@ -161,7 +171,9 @@ __device__ bool ms_search(const DeviceIndexT<C>& ix, const uint8_t* rd, int L, i
     bool less;
     const C sz = hi - lo;
     if (sz == 1) {
-      d += lcp_cmp<false>(ix.text + ix.sa[lo] + d, q, cap, &less);
+      how = (tpos != ~(C)0) ? MS_DIRECT : MS_SA_ONE;
+      const C s = (tpos != ~(C)0) ? tpos : ix.sa[lo];
+      d += lcp_cmp<false>(ix.text + s + d, q, cap, &less);
     } else if (q[0] != 0) {  // a byte outside ACGTN matches nothing: the interval stays at depth d
       if (sz <= 8) {
         C sav[8];
@@ -247,7 +259,7 @@ __device__ bool ms_search(const DeviceIndexT<C>& ix, const uint8_t* rd, int L, i
   out_d = (lo < hi) ? d : 0;
   out_lo = lo;
   out_hi = hi;
-  return false;
+  return how;
 }
 
 // upper-case + sanitise the batch once (reference src/aligner.rs:125); both the
@@ -332,25 +344,29 @@ __device__ __forceinline__ void block_append(bool flag, unsigned long long value
   __syncthreads();
 }
 
-// SEED_STATS: a workgroup's probe counts (decided from the table entry alone / run in full) are gathered in LDS, a
-// ballot and popcount per wavefront, and added to work_counts[8], [9] with one atomic per counter and workgroup.  Every thread calls _begin and _end, under a
+// SEED_STATS: a workgroup's probe counts (decided from the table entry alone / run in full; of the latter, those that took
+// the text position from the table entry / read the suffix array for a one-suffix bucket) are gathered in LDS, a
+// ballot and popcount per wavefront, and added to work_counts[8 .. 11] with one atomic per counter and workgroup.  Every thread calls _begin and _end, under a
 // branch on p.flags (uniform for the launch); nothing is counted, and no register is held, when the bit is clear.
 __device__ __forceinline__ unsigned* seed_stats_lds() {
-  __shared__ unsigned s_cnt[2];
+  __shared__ unsigned s_cnt[4];
   return s_cnt;
 }
 __device__ __forceinline__ void seed_stats_begin() {
   unsigned* c = seed_stats_lds();
-  if (threadIdx.x == 0) c[0] = c[1] = 0;
+  if (threadIdx.x == 0) c[0] = c[1] = c[2] = c[3] = 0;
   __syncthreads();
 }
 // the probes of the lanes that are here together: one pair of LDS adds per wavefront
-__device__ __forceinline__ void seed_stats_note(bool decided) {
-  const unsigned long long here = __ballot(1), dec = __ballot(decided);
+__device__ __forceinline__ void seed_stats_note(int how) {  // what ms_search returned
+  const unsigned long long here = __ballot(1), dec = __ballot(how == MS_DECIDED);
+  const unsigned long long dir = __ballot(how == MS_DIRECT), one = __ballot(how == MS_SA_ONE);
   if (lane_id() == (int)__builtin_ctzll(here)) {
     unsigned* c = seed_stats_lds();
     if (dec) atomicAdd(&c[0], (unsigned)__popcll(dec));
     if (here & ~dec) atomicAdd(&c[1], (unsigned)__popcll(here & ~dec));
+    if (dir) atomicAdd(&c[2], (unsigned)__popcll(dir));
+    if (one) atomicAdd(&c[3], (unsigned)__popcll(one));
   }
 }
 template <class C>
@@ -360,6 +376,8 @@ __device__ __forceinline__ void seed_stats_end(const SeedParamsT<C>& p) {
   if (threadIdx.x == 0) {
     if (c[0]) atomicAdd(&p.work_counts[8], (unsigned long long)c[0]);
     if (c[1]) atomicAdd(&p.work_counts[9], (unsigned long long)c[1]);
+    if (c[2]) atomicAdd(&p.work_counts[10], (unsigned long long)c[2]);
+    if (c[3]) atomicAdd(&p.work_counts[11], (unsigned long long)c[3]);
   }
 }
 
@@ -377,8 +395,9 @@ __device__ __forceinline__ int probe_store(const SeedParamsT<C>& p, const uint8_
   const int k = (int)p.min_seed_len;
   int d = 0;
   C lo = 0, hi = 0;
-  decided = ms_search(p.ix, rd, L, pos, k, hint, d, lo, hi);
-  if (p.flags & SEED_STATS) seed_stats_note(decided);
+  const int how = ms_search(p.ix, rd, L, pos, k, hint, !(p.flags & SEED_NODIRECT), d, lo, hi);
+  decided = how == MS_DECIDED;
+  if (p.flags & SEED_STATS) seed_stats_note(how);
   const int e = (d >= k) ? pos + d : 0;
   const uint64_t item = item0 + (uint64_t)pos;
   p.ms_end[item] = (uint16_t)e;
@@ -396,7 +415,7 @@ __global__ __launch_bounds__(256) void seed_first_kernel(SeedParamsT<C> p) {
   const bool active = read < p.reads.n_reads;
   const int k = (int)p.min_seed_len;
   if (p.flags & SEED_STATS) seed_stats_begin();
-  int d = 0, L = 0;
+  int d = 0, L = 0, how = MS_FULL;
   C lo = 0, hi = 0;
   bool too_long = false;
   if (active) {
@@ -405,7 +424,7 @@ __global__ __launch_bounds__(256) void seed_first_kernel(SeedParamsT<C> p) {
     too_long = Lfull > MAX_READ_LEN;
     L = too_long ? 0 : (int)Lfull;
     if (too_long) p.read_status[read] = THM_ERR_UNSUPPORTED;
-    if (k <= L) (void)ms_search(p.ix, p.reads.bases + r0, L, 0, k, 0, d, lo, hi);
+    if (k <= L) how = ms_search(p.ix, p.reads.bases + r0, L, 0, k, 0, !(p.flags & SEED_NODIRECT), d, lo, hi);
     if (L > 0) {
       const uint64_t item = ms_row(r0, read);
       p.ms_end[item] = (uint16_t)((d >= k) ? d : 0);
@@ -414,7 +433,7 @@ __global__ __launch_bounds__(256) void seed_first_kernel(SeedParamsT<C> p) {
     }
   }
   if (p.flags & SEED_STATS) {
-    if (active && k <= L) seed_stats_note(false);
+    if (active && k <= L) seed_stats_note(how);
     seed_stats_end(p);
   }
   const bool covered = active && d >= k && d == L;

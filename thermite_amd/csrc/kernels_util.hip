@@ -3,9 +3,28 @@
 #include <hip/hip_runtime.h>
 
 #include "launch.h"
+#include "lut_direct.h"
 
 namespace thm {
 namespace dev {
+
+// lut_direct.h: the text position into every single-suffix entry of the device copy of the k-mer table, once per device
+// copy.  One thread per entry; an entry whose lo is not a rank (no valid table has one) is left alone.
+template <class C>
+__global__ __launch_bounds__(256) void lut_tag_kernel(LutEntryT<C>* lut, const C* sa, uint64_t n_entries, uint64_t n,
+                                                      unsigned long long* count) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  bool tagged = false;
+  if (i < n_entries) {
+    const LutEntryT<C> e = lut[i];
+    if (lutd::single_suffix(e.lo, e.hi) && (uint64_t)e.lo < n) {
+      lut[i].hi = lutd::encode(sa[e.lo]);
+      tagged = true;
+    }
+  }
+  const unsigned long long m = __ballot(tagged);
+  if (m && (threadIdx.x & 63u) == (unsigned)__builtin_ctzll(m)) atomicAdd(count, (unsigned long long)__popcll(m));
+}
 
 constexpr int SCAN_THREADS = 256;
 constexpr int SCAN_ITEMS = 8;
@@ -173,6 +192,22 @@ hipError_t launch_calib_gather(const uint8_t* table, uint64_t span, uint64_t n_t
   hipLaunchKernelGGL(dev::calib_gather_kernel, dim3((unsigned)((n_threads + 255) / 256)), dim3(256), 0, s, table, span, n_threads,
                      pattern, sink);
   return hipGetLastError();
+}
+
+template <class C>
+static hipError_t launch_lut_tag_t(LutEntryT<C>* lut, const C* sa, uint64_t n_entries, uint64_t n, unsigned long long* count,
+                                   hipStream_t s) {
+  if (n_entries == 0) return hipSuccess;
+  hipLaunchKernelGGL(dev::lut_tag_kernel<C>, dim3((unsigned)((n_entries + 255) / 256)), dim3(256), 0, s, lut, sa, n_entries, n, count);
+  return hipGetLastError();
+}
+hipError_t launch_lut_tag(LutEntryT<uint32_t>* lut, const uint32_t* sa, uint64_t n_entries, uint64_t n, unsigned long long* count,
+                          hipStream_t s) {
+  return launch_lut_tag_t(lut, sa, n_entries, n, count, s);
+}
+hipError_t launch_lut_tag(LutEntryT<uint64_t>* lut, const uint64_t* sa, uint64_t n_entries, uint64_t n, unsigned long long* count,
+                          hipStream_t s) {
+  return launch_lut_tag_t(lut, sa, n_entries, n, count, s);
 }
 
 size_t scan_tmp_entries(uint64_t n) { return (size_t)((n + SCAN_TILE - 1) / SCAN_TILE) + 1; }

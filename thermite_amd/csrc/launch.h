@@ -96,9 +96,10 @@ struct SeedParamsT {
   unsigned long long* work_long;    // [n_long] long reads, the same
   unsigned long long* work_cells;   // [cells] (read << 16 | cell) of grid cells to probe
   unsigned long long* work_counts;  // [16] list lengths: 0 short, 1 cells, 2 heavy, 3 select overflow, 4 long, 5 slow; with
-                                    // SEED_STATS 8 = probes decided from the table entry alone, 9 = probes run in full;
-                                    // zeroed before launch
-  uint32_t flags;                   // SEED_INFER | SEED_STATS
+                                    // SEED_STATS 8 = probes decided from the table entry alone, 9 = probes run in full,
+                                    // 10 = full probes that took the text position from the table entry, 11 = full
+                                    // probes into a one-suffix bucket that read the suffix array; zeroed before launch
+  uint32_t flags;                   // SEED_INFER | SEED_STATS | SEED_NODIRECT
   SmemT<C>* smems;             // pool
   uint64_t smem_cap;           // pool capacity (entries)
   unsigned long long* cursor;  // bump allocator head (entries), zeroed before launch
@@ -121,8 +122,10 @@ struct SeedParamsT {
 };
 // SeedParamsT::flags.  SEED_INFER: a probe may be decided by its table entry and a match further left in the read, and
 // stores its interval only where an SMEM can start (kernels_seed.hip; thm_debug_set_flags bit 2 clears it, bit 4 sets it again).
-// SEED_STATS: the probing kernels count their probes into work_counts[8], [9] (thm_debug_set_flags bit 3; bit 5 ends it).
-constexpr uint32_t SEED_INFER = 1u, SEED_STATS = 2u;
+// SEED_STATS: the probing kernels count their probes into work_counts[8 .. 11] (thm_debug_set_flags bit 3; bit 5 ends it).
+// SEED_NODIRECT: a text position kept in a table entry (lut_direct.h) is decoded and then ignored: the probe reads sa[lo]
+// as it does with a plain table (thm_debug_set_flags bit 6; bit 7 clears it).
+constexpr uint32_t SEED_INFER = 1u, SEED_STATS = 2u, SEED_NODIRECT = 4u;
 constexpr int FILL_KEY_BASES = 7;
 constexpr unsigned FILL_BUCKETS = 1u << (2 * FILL_KEY_BASES);  // + one bucket for k-mers with a byte outside ACGT
 size_t seed_select_lds_bytes(uint32_t max_read_len);         // per workgroup (4 waves)
@@ -131,6 +134,10 @@ constexpr size_t SEED_SELECT_LDS_LIMIT = 64 * 1024;          // above this the l
 hipError_t launch_seed(const SeedParamsT<uint32_t>& p, int n_blocks, hipStream_t s);
 hipError_t launch_seed(const SeedParamsT<uint64_t>& p, int n_blocks, hipStream_t s);
 hipError_t launch_sanitize(const uint8_t* in, uint8_t* out, uint64_t n, uint64_t n_padded, hipStream_t s);
+// lut_direct.h: one pass over the n_entries entries of the device table, in place; *count (zeroed by the caller) gets
+// the number of entries rewritten.  n = text length (suffix-array entries).
+hipError_t launch_lut_tag(LutEntryT<uint32_t>* lut, const uint32_t* sa, uint64_t n_entries, uint64_t n, unsigned long long* count, hipStream_t s);
+hipError_t launch_lut_tag(LutEntryT<uint64_t>* lut, const uint64_t* sa, uint64_t n_entries, uint64_t n, unsigned long long* count, hipStream_t s);
 
 // What a run of the read-level pipeline zeroes before its first kernel, done by the sanitising launch itself
 // (launch_sanitize_reset): the aligner's control block, the per-read statuses and the 16 bytes in front of the

@@ -151,7 +151,7 @@ int enqueue_seed_t(thm_aligner* a, uint32_t min_seed_len, bool finish_scan) {
   sp.work_long = a->s_work_long.as<unsigned long long>();
   sp.work_cells = a->s_work_cells.as<unsigned long long>();
   sp.work_counts = a->s_work_counts.as<unsigned long long>();
-  sp.flags = (a->dbg_seed_noinfer ? 0u : SEED_INFER) | (a->dbg_seed_stats ? SEED_STATS : 0u);
+  sp.flags = (a->dbg_seed_noinfer ? 0u : SEED_INFER) | (a->dbg_seed_stats ? SEED_STATS : 0u) | (a->dbg_seed_nodirect ? SEED_NODIRECT : 0u);
   sp.smems = a->s_smems.as<SmemT<C>>();
   sp.smem_cap = a->smem_cap;
   sp.cursor = a->d_cursors.as<unsigned long long>();

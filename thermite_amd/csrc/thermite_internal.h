@@ -83,7 +83,8 @@ struct RefRecT {
   uint32_t strand;
 };
 
-// k-mer prefix table entry: suffix-array interval of one ACGT-only kt-mer
+// k-mer prefix table entry: suffix-array interval of one ACGT-only kt-mer (the device copy may keep the text position
+// of a one-suffix interval in hi: lut_direct.h)
 template <class C>
 struct LutEntryT {
   C lo, hi;
@@ -112,6 +113,7 @@ struct DeviceIndexT {
   uint32_t n_refs, n_txs;
   uint32_t kt;
   uint32_t max_tx_exons;  // most exons any transcript has (bounds the introns one alignment can span)
+  uint32_t lut_direct;    // 1: single-suffix entries of lut hold TAG | text position in hi (lut_direct.h)
 };
 
 // one SMEM as the seed kernel emits it: occurrences are sa[lo..hi)
