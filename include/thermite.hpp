@@ -264,6 +264,13 @@ class Aligner {
     return out;
   }
 
+  // a block of whole FASTQ records as raw bytes, parsed on the device where it is in the strict form (thm_batch_upload_fastq)
+  thm_fastq_upload_info upload_fastq(const std::string& raw, const std::string& path = "", std::uint64_t first_line = 1, bool last_block = true) {
+    thm_fastq_upload_info info;
+    check(thm_batch_upload_fastq(h_.get(), (const std::uint8_t*)raw.data(), raw.size(), path.c_str(), first_line, last_block ? 1 : 0, &info));
+    return info;
+  }
+
   // to_noodles_cigar for one serialised op stream (thm_cigar_encode_batch): its digest, words through *words
   thm_aln_digest cigar_encode(const std::vector<std::uint8_t>& ops, std::vector<std::uint32_t>* words = nullptr) {
     const std::uint64_t off[2] = {0, ops.size()};

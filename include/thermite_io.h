@@ -155,6 +155,32 @@ int32_t thm_batch_fetch_bgzf(thm_aligner* a, uint32_t flags, thm_bgzf_view* out)
 /* upload_reads + run + the fetch above */
 int32_t thm_align_batch_bgzf(thm_aligner* a, const thm_read_batch* reads, uint32_t flags, thm_bgzf_view* out);
 
+/* ------------------------------------------------- FASTQ blocks parsed on the device */
+
+typedef struct thm_fastq_upload_info {
+  uint64_t n_reads, n_bases, n_name_bytes;
+  uint32_t on_device; /* 1: parsed by the device; 0: the block was not device-parsable and went through the host parser */
+  float device_ms;    /* HIP-event time of the parse kernels; 0 when on_device == 0 */
+} thm_fastq_upload_info;
+
+/* thm_batch_upload_reads for a block of whole FASTQ records as raw bytes (what the file driver cuts its input into):
+ * the bytes go up as they are and the device cuts them into names, bases and qualities (needletail's record loop,
+ * src/aligner.rs:51-56, for 4-line records).  The device takes the strict form only -- the line count a multiple of 4;
+ * with every trailing CR of a line stripped, line 4r non-empty and beginning with '@', line 4r+2 non-empty and beginning
+ * with '+', lines 4r+1 and 4r+3 of one length -- and declines everything else; a declined block is parsed on the host,
+ * as the driver parses its blocks, and uploaded by thm_batch_upload_reads, or the call returns that parser's
+ * THM_ERR_FORMAT and message.  Either way the batch in place, or the error, is what the host parser makes of the bytes.
+ * path / first_line (the number of the block's first line in its file) only word error messages; last_block: nothing of
+ * the input follows (blank lines are tolerated at its end only).  n == 0: a batch of 0 reads.
+ * THM_ERR_INVALID_ARG: null aligner, raw (with n > 0) or info. */
+int32_t thm_batch_upload_fastq(thm_aligner* a, const uint8_t* raw, uint64_t n, const char* path, uint64_t first_line,
+                               int32_t last_block, thm_fastq_upload_info* info);
+
+/* The uploaded batch back on the host (names, bases as uploaded, qualities -- NULL for a batch uploaded without --, both
+ * offset arrays), whichever upload placed it; the view is valid until the next call of this function on the aligner.
+ * THM_ERR_INVALID_ARG: no batch with names is uploaded (plain thm_batch_upload carries none). */
+int32_t thm_batch_fetch_reads(thm_aligner* a, thm_read_batch* out);
+
 /* -------------------------------------------------------- SAM / PAF writer */
 
 /* OutputFormat, src/aln_writer.rs:16-21 */
@@ -218,7 +244,10 @@ typedef struct thm_run_stats {
  * the file's inflated bytes are the same.
  * THM_BAM_DEVICE=2 and THM_FMT_BAM: the records are encoded and BGZF-compressed on the device (thm_batch_fetch_bgzf)
  * and the formatting stage only passes the members on; the file's inflated bytes are the same again, the compressed
- * ones are the device encoder's (THM_BAM_LEVEL does not apply), and n_output_bytes counts them. */
+ * ones are the device encoder's (THM_BAM_LEVEL does not apply), and n_output_bytes counts them.
+ * THM_FASTQ_DEVICE=1 together with THM_FMT_BAM and THM_BAM_DEVICE=1 or 2 (the modes in which the host needs no read
+ * bytes; ignored otherwise): the blocks of 4-line FASTQ input are not parsed by the parser threads but go to the device
+ * as they are (thm_batch_upload_fastq); the output file is the same byte for byte. */
 int32_t thm_align_files(thm_aligner* a, const char* const* fastq_paths, uint32_t n_paths, const char* output_path,
                         int32_t format, uint64_t batch_reads, uint32_t n_threads, thm_run_stats* stats);
 /* The same over several aligners -- one per GPU of the node, all over one index (the shape of ThermiteAligner: Clone +

@@ -142,6 +142,13 @@ class BgzfView(C.Structure):
                 ("read_status", C.c_void_p)]
 
 
+class FastqUploadInfo(C.Structure):
+    """thm_fastq_upload_info (include/thermite_io.h)"""
+
+    _fields_ = [("n_reads", C.c_uint64), ("n_bases", C.c_uint64), ("n_name_bytes", C.c_uint64), ("on_device", C.c_uint32),
+                ("device_ms", C.c_float)]
+
+
 BAM_NO_ANNOTATION_TAGS = 1
 
 # every symbol include/thermite.h declares
@@ -165,6 +172,7 @@ IO_ABI_SYMBOLS = [
     "thm_writer_format_batch_cigars",
     "thm_batch_upload_reads", "thm_batch_fetch_bam", "thm_align_batch_bam", "thm_writer_wrap_bam",
     "thm_batch_fetch_bgzf", "thm_align_batch_bgzf",
+    "thm_batch_upload_fastq", "thm_batch_fetch_reads",
 ]
 ERR_IO, ERR_FORMAT = -8, -9
 FMT_PAF, FMT_SAM, FMT_BAM = 0, 1, 2
@@ -312,6 +320,12 @@ def lib():
     L.thm_align_batch_bgzf.argtypes = [vp, vp, u32, vp]
     L.thm_debug_bgzf_device.restype = i32
     L.thm_debug_bgzf_device.argtypes = [vp, vp, u64, vp, u64, vp, vp]
+    L.thm_batch_upload_fastq.restype = i32
+    L.thm_batch_upload_fastq.argtypes = [vp, vp, u64, cp, u64, i32, vp]
+    L.thm_batch_fetch_reads.restype = i32
+    L.thm_batch_fetch_reads.argtypes = [vp, vp]
+    L.thm_debug_fastq_device_blocks.restype = i32
+    L.thm_debug_fastq_device_blocks.argtypes = [vp, vp, vp]
     L.thm_writer_wrap_bam.restype = i32
     L.thm_writer_wrap_bam.argtypes = [vp, vp, vp]
     L.thm_align_files.restype = i32
@@ -746,6 +760,31 @@ class Aligner:
         v = BgzfView()
         self._chk(lib().thm_align_batch_bgzf(self.h, C.byref(rb), flags, C.byref(v)))
         return BgzfResult(v, copy)
+
+    def upload_fastq(self, raw, path=b"", first_line=1, last_block=True):
+        """thm_batch_upload_fastq: a block of whole FASTQ records as raw bytes -> the info as a dict (on_device: 1 when the
+        device parsed it, 0 when it went through the host parser)"""
+        src = np.frombuffer(bytes(raw), np.uint8) if len(raw) else None
+        info = FastqUploadInfo()
+        self._chk(lib().thm_batch_upload_fastq(self.h, _ptr(src), len(raw), os.fsencode(path), first_line, int(bool(last_block)),
+                                               C.byref(info)))
+        return {k: getattr(info, k) for k, _ in FastqUploadInfo._fields_}
+
+    def fetch_reads(self):
+        """thm_batch_fetch_reads: the uploaded batch as the dict FastqReader.next_batch gives"""
+        v = ReadBatch()
+        self._chk(lib().thm_batch_fetch_reads(self.h, C.byref(v)))
+        off = _copy(v.offsets, v.n_reads + 1, "<u8")
+        noff = _copy(v.name_off, v.n_reads + 1, "<u8")
+        return dict(bases=_copy(v.bases, v.n_bases, np.uint8), offsets=off,
+                    quals=_copy(v.quals, v.n_bases, np.uint8) if v.quals else None,
+                    names=_copy(v.names, int(noff[-1]), np.uint8), name_off=noff)
+
+    def debug_fastq_device_blocks(self):
+        """test hook: blocks upload_fastq (and the file driver with THM_FASTQ_DEVICE=1) parsed (on the device, on the host)"""
+        d, h = C.c_uint64(0), C.c_uint64(0)
+        self._chk(lib().thm_debug_fastq_device_blocks(self.h, C.byref(d), C.byref(h)))
+        return d.value, h.value
 
     def debug_bgzf_device(self, data):
         """test hook: bytes through the device BGZF encoder -> (the members back to back, their number)"""

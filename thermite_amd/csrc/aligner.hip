@@ -265,7 +265,8 @@ void thm_aligner_free(thm_aligner* a) {
                  &a->bn_names, &a->bn_name_off, &a->bn_quals, &a->bt_tx_pool, &a->bt_tx_off, &a->bt_gid_pool, &a->bt_gid_off,
                  &a->bt_gname_pool, &a->bt_gname_off, &a->bt_tx_gene, &a->bt_ref_sq, &a->bm_cnt, &a->bm_first, &a->bm_qn,
                  &a->bm_rec_read, &a->bm_len, &a->bm_off, &a->bm_out, &a->bm_read_off, &a->bm_err, &a->bm_scan_tmp,
-                 &a->bz_match, &a->bz_slots, &a->bz_sizes, &a->bz_off, &a->bz_out, &a->bz_scan_tmp, &a->bz_dbg_in};
+                 &a->bz_match, &a->bz_slots, &a->bz_sizes, &a->bz_off, &a->bz_out, &a->bz_scan_tmp, &a->bz_dbg_in,
+                 &a->fq_raw, &a->fq_cnt, &a->fq_base, &a->fq_lines, &a->fq_name_len, &a->fq_seq_len, &a->fq_flag, &a->fq_scan_tmp};
   for (DBuf* b : all) b->release();
   for (int k = 0; k < 2; k++) {
     a->r_off[k].release();
@@ -284,6 +285,10 @@ void thm_aligner_free(thm_aligner* a) {
     a->zh_off[k].release();
     a->zh_stat[k].release();
   }
+  HBuf* pinned[] = {&a->fq_h_off, &a->fr_bases, &a->fr_off, &a->fr_quals, &a->fr_names, &a->fr_name_off};
+  for (HBuf* b : pinned) b->release();
+  for (auto& e : a->ev_fq)
+    if (e) (void)hipEventDestroy(e);
   for (auto& e : a->ev_cig)
     if (e) (void)hipEventDestroy(e);
   for (auto& e : a->ev_bam)

@@ -214,6 +214,15 @@ struct thm_aligner {
   HBuf zh_data[2], zh_off[2], zh_stat[2];
   int z_cur = 0;
   hipEvent_t ev_bgzf[2] = {nullptr, nullptr};  // created by the first call
+  // FASTQ blocks parsed on the device (fastq.hip): the block's bytes, newline counts per chunk and their scan, the line
+  // starts, the records' lengths and the flag word; the offsets come back into fq_h_off for the length classes.  The
+  // blocks that went either way since the aligner was created (thm_debug_fastq_device_blocks).  One pinned set behind
+  // thm_batch_fetch_reads.
+  DBuf fq_raw, fq_cnt, fq_base, fq_lines, fq_name_len, fq_seq_len, fq_flag, fq_scan_tmp;
+  HBuf fq_h_off;
+  uint64_t fq_on_device = 0, fq_on_host = 0;
+  hipEvent_t ev_fq[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // created by the first call
+  HBuf fr_bases, fr_off, fr_quals, fr_names, fr_name_off;
 };
 
 inline int fail(thm_aligner* a, int code, const char* fmt, ...) {
@@ -249,6 +258,9 @@ struct BamOnDevice {
 int bam_records_on_device(thm_aligner* a, uint32_t flags, int timing, BamOnDevice* r);
 // n statuses in `st` (copied from r_status after bam_records_on_device said any_failed) -> the view's two fields
 void bam_failed_reads(const int32_t* st, uint64_t n, uint64_t* n_failed, const int32_t** status);
+// pipeline.hip: what thm_batch_upload derives from the offsets of a batch -- n_reads, n_bases, max_read_len, the length
+// classes (len_hist) and n_over -- for every upload path; THM_ERR_INVALID_ARG for offsets that do not start at 0 or descend
+int batch_length_classes(thm_aligner* a, const uint64_t* offsets, uint64_t n_reads);
 int reset_queue(thm_aligner* a);
 int grid_blocks(const thm_aligner* a, uint64_t n_items, int waves_per_block, int blocks_per_cu);
 // pipeline.hip: what THM_SEED_FILL and THM_TEAM_DIV_PER_CU resolved to (read once per process)

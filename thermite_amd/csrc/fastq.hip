@@ -1,0 +1,188 @@
+// fastq.hip -- host side of thm_batch_upload_fastq / thm_batch_fetch_reads (include/thermite_io.h): a block of whole
+// FASTQ records goes up as the bytes it is, and kernels_fastq.hip cuts it into names, bases and qualities where
+// thm_batch_upload_reads would have placed them.  The device takes the strict form only (fastq_device.h); a block it
+// declines is parsed by fastq_parse_block (io_fastq.cpp) and uploaded the old way, or is that parser's error: what the
+// call does is the host parser's doing on every input.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+
+#include "aligner_internal.h"
+#include "fastq_device.h"
+#include "io_internal.h"
+
+using namespace thm;
+
+namespace {
+
+// 1: the batch is in place, parsed by the device; 0: declined (nothing of the aligner's batch state is valid); < 0: error
+int parse_on_device(thm_aligner* a, const uint8_t* raw, uint64_t n, thm_fastq_upload_info* info) {
+  hipStream_t s = a->stream;
+  for (auto& e : a->ev_fq)
+    if (!e) HIPCHK(a, hipEventCreate(&e));
+  FastqParams p;
+  memset(&p, 0, sizeof p);
+  p.n = n;
+  p.n_chunks = (n + fq::CHUNK - 1) / fq::CHUNK;
+  HIPCHK(a, a->fq_raw.ensure(n + 64));
+  HIPCHK(a, a->fq_cnt.ensure(p.n_chunks * 8));
+  HIPCHK(a, a->fq_base.ensure((p.n_chunks + 2) * 8));
+  HIPCHK(a, a->fq_flag.ensure(64));
+  HIPCHK(a, a->fq_scan_tmp.ensure(scan_tmp_entries(p.n_chunks + 1) * 8 + 64));
+  p.raw = a->fq_raw.as<uint8_t>();
+  p.chunk_cnt = a->fq_cnt.as<uint64_t>();
+  p.chunk_base = a->fq_base.as<uint64_t>();
+  p.flag = a->fq_flag.as<unsigned>();
+  HIPCHK(a, hipMemcpyAsync(a->fq_raw.p, raw, n, hipMemcpyHostToDevice, s));
+  HIPCHK(a, hipMemsetAsync(a->fq_flag.p, 0, 64, s));
+  // ---- newlines: per chunk, their scan; the total sizes the line table
+  HIPCHK(a, hipEventRecord(a->ev_fq[0], s));
+  HIPCHK(a, launch_fastq_count(p, a->n_cu, s));
+  HIPCHK(a, launch_exclusive_scan_u64(a->fq_cnt.as<uint64_t>(), a->fq_base.as<uint64_t>(), p.n_chunks, a->fq_scan_tmp.as<uint64_t>(), s));
+  HIPCHK(a, hipEventRecord(a->ev_fq[1], s));
+  unsigned long long n_nl = 0;
+  HIPCHK(a, hipMemcpyAsync(&n_nl, a->fq_base.as<uint64_t>() + p.n_chunks, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(a, hipStreamSynchronize(s));
+  if (n_nl > n) return fail(a, THM_ERR_INTERNAL, "thm_batch_upload_fastq: more newlines than bytes");
+  p.n_newlines = n_nl;
+  p.n_lines = fq::line_count(n_nl, raw[n - 1]);
+  if (p.n_lines % 4 != 0) return 0;
+  const uint64_t nr = p.n_records = p.n_lines / 4;
+  if (nr >= 0xFFFFFFF0ull) return 0;  // (the host path words the refusal)
+  // ---- line starts, the rule per record, name_off and offsets
+  HIPCHK(a, a->fq_lines.ensure((p.n_lines + 2) * 8));
+  HIPCHK(a, a->fq_name_len.ensure((nr + 1) * 8));
+  HIPCHK(a, a->fq_seq_len.ensure((nr + 1) * 8));
+  HIPCHK(a, a->fq_scan_tmp.ensure(scan_tmp_entries(nr + 1) * 8 + 64));
+  HIPCHK(a, a->bn_name_off.ensure((nr + 1) * 8));
+  HIPCHK(a, a->r_offsets.ensure((nr + 1) * 8));
+  HIPCHK(a, a->fq_h_off.ensure((nr + 2) * 8));
+  p.line_start = a->fq_lines.as<uint64_t>();
+  p.name_len = a->fq_name_len.as<uint64_t>();
+  p.seq_len = a->fq_seq_len.as<uint64_t>();
+  p.name_off = a->bn_name_off.as<uint64_t>();
+  p.offsets = a->r_offsets.as<uint64_t>();
+  HIPCHK(a, hipEventRecord(a->ev_fq[2], s));
+  HIPCHK(a, launch_fastq_starts(p, a->n_cu, s));
+  HIPCHK(a, launch_fastq_records(p, s));
+  HIPCHK(a, launch_exclusive_scan_u64(p.name_len, a->bn_name_off.as<uint64_t>(), nr, a->fq_scan_tmp.as<uint64_t>(), s));
+  HIPCHK(a, launch_exclusive_scan_u64(p.seq_len, a->r_offsets.as<uint64_t>(), nr, a->fq_scan_tmp.as<uint64_t>(), s));
+  HIPCHK(a, hipEventRecord(a->ev_fq[3], s));
+  // the offsets come down for the length classes (8 bytes a read); the name bytes' total behind them
+  unsigned flag = 0;
+  uint64_t* h_off = a->fq_h_off.as<uint64_t>();
+  HIPCHK(a, hipMemcpyAsync(&flag, a->fq_flag.p, 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(a, hipMemcpyAsync(h_off, a->r_offsets.p, (nr + 1) * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(a, hipMemcpyAsync(h_off + nr + 1, a->bn_name_off.as<uint64_t>() + nr, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(a, hipStreamSynchronize(s));
+  if (flag == 2) return fail(a, THM_ERR_INTERNAL, "thm_batch_upload_fastq: inconsistent line table");
+  if (flag != 0) return 0;
+  const uint64_t nb = h_off[nr], nn = h_off[nr + 1];
+  if (nn + 2 * nb > n) return fail(a, THM_ERR_INTERNAL, "thm_batch_upload_fastq: a parse larger than its block");
+  int rc = batch_length_classes(a, h_off, nr);
+  if (rc != THM_OK) return rc;
+  // ---- gather, into the buffers (and with the paddings) of thm_batch_upload / thm_batch_upload_reads
+  HIPCHK(a, a->r_bases.ensure(nb + 64));
+  HIPCHK(a, a->bn_names.ensure(nn + 16));
+  HIPCHK(a, a->bn_quals.ensure(nb + 16));
+  p.names = a->bn_names.as<uint8_t>();
+  p.bases = a->r_bases.as<uint8_t>();
+  p.quals = a->bn_quals.as<uint8_t>();
+  HIPCHK(a, hipEventRecord(a->ev_fq[4], s));
+  HIPCHK(a, launch_fastq_gather(p, a->n_cu, s));
+  HIPCHK(a, hipEventRecord(a->ev_fq[5], s));
+  HIPCHK(a, hipStreamSynchronize(s));
+  float ms = 0, sum = 0;
+  for (int k = 0; k < 6; k += 2)
+    if (hipEventElapsedTime(&ms, a->ev_fq[k], a->ev_fq[k + 1]) == hipSuccess) sum += ms;
+  info->n_reads = nr;
+  info->n_bases = nb;
+  info->n_name_bytes = nn;
+  info->on_device = 1;
+  info->device_ms = sum;
+  return 1;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t thm_batch_upload_fastq(thm_aligner* a, const uint8_t* raw, uint64_t n, const char* path, uint64_t first_line,
+                               int32_t last_block, thm_fastq_upload_info* info) {
+  if (!a || !info || (!raw && n)) return THM_ERR_INVALID_ARG;
+  memset(info, 0, sizeof(*info));
+  HIPCHK(a, hipSetDevice(a->device));
+  a->uploaded = a->ran = a->synced = false;
+  a->reads_named = false;
+  if (n) {
+    const int d = parse_on_device(a, raw, n, info);
+    if (d < 0) return d;
+    if (d == 1) {
+      a->reads_have_quals = true;
+      a->reads_named = true;
+      a->uploaded = true;
+      a->fq_on_device++;
+      return THM_OK;
+    }
+    a->fq_on_host++;
+  }
+  // not device-parsable (or empty): the host parser's batch, or its error with its message
+  HostBatch b;
+  std::string err;
+  const int rc = fastq_parse_block((const char*)raw, (size_t)n, path ? path : "", first_line, last_block != 0, b, err);
+  if (rc != THM_OK) {
+    a->err = err;
+    set_global_error(err);
+    return rc;
+  }
+  const thm_read_batch v = b.view();
+  const int urc = thm_batch_upload_reads(a, &v);
+  if (urc != THM_OK) return urc;
+  info->n_reads = v.n_reads;
+  info->n_bases = v.n_bases;
+  info->n_name_bytes = v.name_off[v.n_reads];
+  return THM_OK;
+}
+
+int32_t thm_batch_fetch_reads(thm_aligner* a, thm_read_batch* out) {
+  if (!a || !out) return THM_ERR_INVALID_ARG;
+  memset(out, 0, sizeof(*out));
+  if (!a->uploaded || !a->reads_named)
+    return fail(a, THM_ERR_INVALID_ARG, "thm_batch_fetch_reads: no batch with names is uploaded (thm_batch_upload_reads / thm_batch_upload_fastq)");
+  HIPCHK(a, hipSetDevice(a->device));
+  hipStream_t s = a->stream;
+  const uint64_t n = a->n_reads, nb = a->n_bases;
+  HIPCHK(a, a->fr_off.ensure((n + 1) * 8));
+  HIPCHK(a, a->fr_name_off.ensure((n + 1) * 8));
+  HIPCHK(a, hipMemcpyAsync(a->fr_off.p, a->r_offsets.p, (n + 1) * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(a, hipMemcpyAsync(a->fr_name_off.p, a->bn_name_off.p, (n + 1) * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(a, hipStreamSynchronize(s));
+  const uint64_t nn = a->fr_name_off.as<uint64_t>()[n];
+  HIPCHK(a, a->fr_bases.ensure(nb + 1));
+  HIPCHK(a, a->fr_names.ensure(nn + 1));
+  if (nb) HIPCHK(a, hipMemcpyAsync(a->fr_bases.p, a->r_bases.p, nb, hipMemcpyDeviceToHost, s));
+  if (nn) HIPCHK(a, hipMemcpyAsync(a->fr_names.p, a->bn_names.p, nn, hipMemcpyDeviceToHost, s));
+  if (a->reads_have_quals) {
+    HIPCHK(a, a->fr_quals.ensure(nb + 1));
+    if (nb) HIPCHK(a, hipMemcpyAsync(a->fr_quals.p, a->bn_quals.p, nb, hipMemcpyDeviceToHost, s));
+  }
+  HIPCHK(a, hipStreamSynchronize(s));
+  out->n_reads = n;
+  out->n_bases = nb;
+  out->bases = a->fr_bases.as<uint8_t>();
+  out->offsets = a->fr_off.as<uint64_t>();
+  out->quals = a->reads_have_quals ? a->fr_quals.as<uint8_t>() : nullptr;
+  out->names = a->fr_names.as<uint8_t>();
+  out->name_off = a->fr_name_off.as<uint64_t>();
+  return THM_OK;
+}
+
+// test hook: the blocks thm_batch_upload_fastq parsed on the device / handed to the host parser since the aligner was created
+int32_t thm_debug_fastq_device_blocks(thm_aligner* a, uint64_t* on_device, uint64_t* on_host) {
+  if (!a || !on_device || !on_host) return THM_ERR_INVALID_ARG;
+  *on_device = a->fq_on_device;
+  *on_host = a->fq_on_host;
+  return THM_OK;
+}
+
+}  // extern "C"

@@ -4,7 +4,8 @@
 //     inflate one thread per gzip input file, a few files at a time: gzip bytes -> blocks of whole FASTQ
 //             records, ahead of the file's turn within a memory budget (the records still leave in input order)
 //     cut     one thread: mapped file bytes / the inflaters' blocks -> slots, in input order
-//     parse   a few threads: block -> batch (names, bases, qualities)
+//     parse   a few threads: block -> batch (names, bases, qualities); with THM_FASTQ_DEVICE=1 the block passes through
+//             and the device parses it (thm_batch_upload_fastq)
 //     GPU     one thread per aligner (= per GPU): upload, run, sync, fetch
 //     write   one thread: batches in input order -> formatting threads -> pwrite
 // connected by queues over a fixed set of reusable slots, so that the host work either
@@ -233,6 +234,10 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
   // THM_BAM_DEVICE=2: ... and BGZF-compressed there too (thm_batch_fetch_bgzf): the formatting stage passes bytes on
   const bool bgzf_device = format == THM_FMT_BAM && bam_dev_env && !strcmp(bam_dev_env, "2");
   const bool bam_device = bgzf_device || (format == THM_FMT_BAM && bam_dev_env && !strcmp(bam_dev_env, "1"));
+  // THM_FASTQ_DEVICE=1, in those two modes only (the host needs no read bytes there): blocks of 4-line FASTQ go to the
+  // device unparsed (thm_batch_upload_fastq)
+  const char* fq_dev_env = getenv("THM_FASTQ_DEVICE");
+  const bool fastq_device = bam_device && fq_dev_env && !strcmp(fq_dev_env, "1");
   const thm_index* ix = thm_aligner_index(aligners[0]);
   for (uint32_t i = 1; i < n_aligners; i++)
     if (thm_aligner_index(aligners[i]) != ix) {
@@ -471,7 +476,7 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
       for (;;) {
         Slot* s = q_raw.pop();
         if (!s) break;
-        if (!s->parsed && !sh.failed()) {
+        if (!s->parsed && !fastq_device && !sh.failed()) {  // (with THM_FASTQ_DEVICE the block passes through as it is)
           const auto t0 = Clock::now();
           std::string err;
           const int prc = sh.step([&] { return thm::fastq_parse_block(s->raw_ptr, s->raw_len, s->path, s->first_line, s->last_block, s->reads, err); });
@@ -515,11 +520,24 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
           next_align++;
         }
         par_cv.notify_all();
-        if (!sh.failed() && s->reads.n_reads() != 0) {  // (a blank tail cut into a block of its own holds no read)
-          const auto t0 = Clock::now();
+        // a raw block goes up as it is and is parsed there; the slot keeps its bytes (its own buffer, or the mapping,
+        // which lives until every batch is written) until it is released behind the write
+        const bool raw_up = fastq_device && !s->parsed;
+        bool have = !sh.failed() && (raw_up || s->reads.n_reads() != 0);  // (a blank tail cut into a block of its own holds no read)
+        const auto t0 = Clock::now();
+        int up_rc = THM_OK;
+        if (have && raw_up) {
+          thm_fastq_upload_info fi;
+          memset(&fi, 0, sizeof fi);
+          up_rc = sh.step([&] {
+            return (int)thm_batch_upload_fastq(a, (const uint8_t*)s->raw_ptr, s->raw_len, s->path.c_str(), s->first_line, s->last_block ? 1 : 0, &fi);
+          });
+          if (up_rc == THM_OK && fi.n_reads == 0) have = false;  // (that blank tail)
+        }
+        if (have) {
           const thm_read_batch rb = s->reads.view();
           int grc = sh.step([&] {
-            int g2 = bam_device ? thm_batch_upload_reads(a, &rb) : thm_batch_upload(a, rb.bases, rb.offsets, rb.n_reads);
+            int g2 = raw_up ? up_rc : bam_device ? thm_batch_upload_reads(a, &rb) : thm_batch_upload(a, rb.bases, rb.offsets, rb.n_reads);
             if (g2 == THM_OK) g2 = thm_batch_run(a);
             if (g2 == THM_OK) g2 = thm_batch_sync(a);
             return g2;
@@ -542,8 +560,13 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
             // the reference aligns every read or panics; a read this build cannot take fails the run, by name
             uint64_t bad = 0;
             while (bad < n_res && res_status[bad] == THM_OK) bad++;
+            if (raw_up) {  // the host has not seen the names of this block: parse it now, for the one message
+              std::string perr;
+              (void)sh.step([&] { return thm::fastq_parse_block(s->raw_ptr, s->raw_len, s->path, s->first_line, s->last_block, s->reads, perr); });
+            }
             const thm_read_batch v = s->reads.view();
-            std::string name((const char*)v.names + v.name_off[bad], (size_t)(v.name_off[bad + 1] - v.name_off[bad]));
+            std::string name;
+            if (bad < v.n_reads) name.assign((const char*)v.names + v.name_off[bad], (size_t)(v.name_off[bad + 1] - v.name_off[bad]));
             sh.set(res_status[bad], "read " + name + (res_status[bad] == THM_ERR_UNSUPPORTED
                                                            ? ": longer than 65535 bases, or its DP trace exceeds the device-memory budget"
                                                            : ": hits a condition that panics in the reference (lift_mem_to_tx / lift_tx_to_gx)"));

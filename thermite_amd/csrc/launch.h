@@ -653,5 +653,26 @@ unsigned bgzf_grid(uint64_t n_blocks, int n_cu);
 hipError_t launch_bgzf_deflate(const BgzfParams& p, int n_cu, hipStream_t s);
 hipError_t launch_bgzf_compact(const BgzfParams& p, int n_cu, hipStream_t s);
 
+// ---- FASTQ blocks parsed on the device (kernels_fastq.hip, fastq_device.h; host side fastq.hip) ----
+// count (newlines per chunk) -> scan -> starts (line_start) -> records (the parse rule: lengths, or the flag) -> two
+// scans (name_off, offsets) -> gather (names, bases, qualities to their places).
+struct FastqParams {
+  const uint8_t* raw;  // [n], 4-byte aligned, readable up to n + 4
+  uint64_t n, n_chunks;        // n_chunks = ceil(n / fq::CHUNK)
+  uint64_t* chunk_cnt;         // [n_chunks]      count
+  const uint64_t* chunk_base;  // [n_chunks + 1]  scan of chunk_cnt
+  uint64_t n_newlines, n_lines;
+  uint64_t* line_start;        // [n_lines + 1]   starts
+  uint64_t n_records;          // n_lines / 4
+  uint64_t *name_len, *seq_len;  // [n_records]   records
+  unsigned* flag;                // 0: every record passed; 1: the block is declined; 2: the line table is inconsistent
+  const uint64_t *name_off, *offsets;  // [n_records + 1]  scans of name_len, seq_len
+  uint8_t *names, *bases, *quals;      // gather
+};
+hipError_t launch_fastq_count(const FastqParams& p, int n_cu, hipStream_t s);
+hipError_t launch_fastq_starts(const FastqParams& p, int n_cu, hipStream_t s);
+hipError_t launch_fastq_records(const FastqParams& p, hipStream_t s);
+hipError_t launch_fastq_gather(const FastqParams& p, int n_cu, hipStream_t s);
+
 }  // namespace thm
 #endif

@@ -642,13 +642,7 @@ int expand_mems_t(thm_aligner* a, uint64_t n) {
 
 }  // namespace
 
-extern "C" {
-
-int32_t thm_batch_upload(thm_aligner* a, const uint8_t* bases, const uint64_t* offsets, uint64_t n_reads) {
-  if (!a || !offsets || (!bases && n_reads && offsets[n_reads] > 0)) return THM_ERR_INVALID_ARG;
-  HIPCHK(a, hipSetDevice(a->device));
-  a->uploaded = a->ran = a->synced = false;
-  a->reads_named = false;  // (thm_batch_upload_reads sets it)
+int batch_length_classes(thm_aligner* a, const uint64_t* offsets, uint64_t n_reads) {
   if (n_reads >= 0xFFFFFFF0ull) return fail(a, THM_ERR_UNSUPPORTED, "more than 2^32-16 reads in one batch");
   if (offsets[0] != 0) return fail(a, THM_ERR_INVALID_ARG, "offsets[0] must be 0");
   // the lengths present in the batch (usually one or a handful): histogram by sorting the distinct ones
@@ -685,6 +679,18 @@ int32_t thm_batch_upload(thm_aligner* a, const uint8_t* bases, const uint64_t* o
   a->n_reads = n_reads;
   a->n_bases = offsets[n_reads];
   a->max_read_len = lmax;
+  return THM_OK;
+}
+
+extern "C" {
+
+int32_t thm_batch_upload(thm_aligner* a, const uint8_t* bases, const uint64_t* offsets, uint64_t n_reads) {
+  if (!a || !offsets || (!bases && n_reads && offsets[n_reads] > 0)) return THM_ERR_INVALID_ARG;
+  HIPCHK(a, hipSetDevice(a->device));
+  a->uploaded = a->ran = a->synced = false;
+  a->reads_named = false;  // (thm_batch_upload_reads sets it)
+  const int rc = batch_length_classes(a, offsets, n_reads);
+  if (rc != THM_OK) return rc;
   HIPCHK(a, a->r_bases.ensure(a->n_bases + 64));
   HIPCHK(a, a->r_offsets.ensure((n_reads + 1) * 8));
   if (a->n_bases) HIPCHK(a, hipMemcpyAsync(a->r_bases.p, bases, a->n_bases, hipMemcpyHostToDevice, a->stream));

@@ -2,10 +2,16 @@
 """End-to-end file throughput on the GPU box (tuning aid, not the benchmark):
 FASTQ on disk -> thm_align_files -> SAM / PAF.   python tools_e2e.py [ref_len] [n_reads] [threads] [rep]
 --bam-device[=RUNS]: only FASTQ -> BAM and .fastq.gz -> BAM, each RUNS times (default 4) with THM_BAM_DEVICE 0, 1 and 2
-in turn (the driver reads the switch at every call), in one session."""
+in turn (the driver reads the switch at every call), in one session.
+--fastq-device[=ROUNDS]: FASTQ -> BAM and two .fastq.gz -> BAM with THM_BAM_DEVICE 1 and 2, each with THM_FASTQ_DEVICE off
+and on alternately, ROUNDS rounds (default 3) in one session; the files of a pair must be identical."""
 import os, sys, time
-BAM_RUNS = 0
+BAM_RUNS = FQ_ROUNDS = 0
 for arg in list(sys.argv[1:]):
+    if arg.startswith("--fastq-device"):
+        FQ_ROUNDS = int(arg.split("=")[1]) if "=" in arg else 3
+        sys.argv.remove(arg)
+        continue
     if arg.startswith("--bam-device"):
         BAM_RUNS = int(arg.split("=")[1]) if "=" in arg else 4
         sys.argv.remove(arg)
@@ -46,7 +52,7 @@ with open(big, "wb") as f:
         f.write(one)
     del one
 print("plain input: %d reads, %.1f MB" % (n * REP, os.path.getsize(big) / 1e6), flush=True)
-for fmt, name in (() if BAM_RUNS else ((capi.FMT_SAM, "sam"), (capi.FMT_PAF, "paf"))):
+for fmt, name in (() if BAM_RUNS or FQ_ROUNDS else ((capi.FMT_SAM, "sam"), (capi.FMT_PAF, "paf"))):
     for rep in range(2):
         out = "/tmp/thm_e2e_out.%s" % name
         st = capi.align_files(a, [big], out, fmt, batch_reads=250000, n_threads=threads)
@@ -88,7 +94,7 @@ def digest(path):
     return h.hexdigest()
 
 
-paf_of_plain = None if BAM_RUNS else digest("/tmp/thm_e2e_out.paf")  # (the last plain run wrote PAF of the REP-copy file)
+paf_of_plain = None if BAM_RUNS or FQ_ROUNDS else digest("/tmp/thm_e2e_out.paf")  # (the last plain run wrote PAF of the REP-copy file)
 
 
 def run(tag, paths, fmt, out, reps=2):
@@ -99,6 +105,34 @@ def run(tag, paths, fmt, out, reps=2):
             st["n_output_bytes"] / 1e6), flush=True)
 
 
+if FQ_ROUNDS:
+    os.environ["THM_BAM_DEVICE"] = "1"
+    os.environ.pop("THM_FASTQ_DEVICE", None)
+    run("warm-up: bam from plain fastq, device encoder, host parser", [big], capi.FMT_BAM, "/tmp/thm_e2e_out.bam", 1)
+    outs, same = [], True
+    for k in range(FQ_ROUNDS):
+        for dev in ("1", "2"):
+            os.environ["THM_BAM_DEVICE"] = dev
+            for tag, paths in (("plain fastq", [big]), ("two .gz", [gz, gz2])):
+                pair = []
+                for fq in ("0", "1"):
+                    os.environ["THM_FASTQ_DEVICE"] = fq
+                    out = "/tmp/thm_e2e_out.fq%s%s%d.bam" % (dev, fq, len(paths))
+                    before = a.debug_fastq_device_blocks()
+                    run("bam from %s, THM_BAM_DEVICE=%s, %s parser, round %d" % (tag, dev, "device" if fq == "1" else "host  ", k), paths, capi.FMT_BAM, out, 1)
+                    after = a.debug_fastq_device_blocks()
+                    if fq == "1":
+                        print("    blocks parsed on the device %d, on the host %d" % (after[0] - before[0], after[1] - before[1]), flush=True)
+                    pair.append(digest(out))
+                    outs.append(out)
+                same = same and pair[0] == pair[1]
+    print("BAM files with and without THM_FASTQ_DEVICE are %s" % ("IDENTICAL" if same else "DIFFERENT"), flush=True)
+    a.close()
+    for f in [path, big, gz, gz2, "/tmp/thm_e2e_out.bam"] + outs:
+        if os.path.exists(f):
+            os.remove(f)
+    assert same
+    sys.exit(0)
 if BAM_RUNS:
     os.environ.pop("THM_BAM_DEVICE", None)
     run("warm-up: bam from plain fastq, host encoder", [big], capi.FMT_BAM, "/tmp/thm_e2e_out.bam", 1)

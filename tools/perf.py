@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Quick stage timing on the GPU box (tuning aid, not the benchmark):
-python tools/perf.py [ref_len] [n_reads] [opts] [--cigars] [--bam] [--bgzf]
+python tools/perf.py [ref_len] [n_reads] [opts] [--cigars] [--bam] [--bgzf] [--fastq]
 --cigars: on the resident batch, thm_batch_fetch against thm_batch_fetch_cigars -- milliseconds and bytes moved to the
 host by each, and the device time of the two CIGAR passes (THM_T_CIGAR).
 --bam: on the resident batch, thm_batch_fetch_bam with both forms of the emit kernel (THM_BAM_EMIT) -- milliseconds,
@@ -8,7 +8,9 @@ bytes, THM_T_BAM -- beside thm_batch_fetch plus the host's record encoding of th
 at THM_BAM_LEVEL=0 minus thm_writer_wrap_bam of the same records: stored blocks, so the difference is the encoding).
 --bgzf (without --bam, which turns the host's deflate off): on the resident batch, thm_batch_fetch_bgzf -- milliseconds,
 bytes, THM_T_BGZF -- beside thm_batch_fetch_bam plus thm_writer_wrap_bam of the same records on 16 threads and on 1, and
-the compressed sizes of the device encoder, the host encoder and zlib level 1 over the device's cuts."""
+the compressed sizes of the device encoder, the host encoder and zlib level 1 over the device's cuts.
+--fastq: the batch written out as one FASTQ block: thm_batch_upload_fastq -- milliseconds of the call and of its parse
+kernels (device_ms) -- beside thm_batch_upload_reads of the parsed batch, and the host's parse of the block on one thread."""
 import sys, time
 import numpy as np
 sys.path.insert(0, __import__("os").path.dirname(__import__("os").path.dirname(__import__("os").path.abspath(__file__))))
@@ -17,7 +19,8 @@ from thermite_amd import capi, synth
 cigars = "--cigars" in sys.argv
 bam = "--bam" in sys.argv
 bgzf = "--bgzf" in sys.argv
-sys.argv = [x for x in sys.argv if x not in ("--cigars", "--bam", "--bgzf")]
+fastq = "--fastq" in sys.argv
+sys.argv = [x for x in sys.argv if x not in ("--cigars", "--bam", "--bgzf", "--fastq")]
 if bam:
     __import__("os").environ["THM_BAM_LEVEL"] = "0"  # (read once, by the first BGZF block of the process)
 ref_len = int(sys.argv[1]) if len(sys.argv) > 1 else 4000000
@@ -156,6 +159,43 @@ for name, opts in (("ci", capi.CI_OPTS), ("default", capi.DEFAULT_OPTS)):
             c = zlib.compressobj(1, zlib.DEFLATED, -15)
             z1 += len(c.compress(raw[at: at + 0xff00]) + c.flush()) + 26
         print("         compressed sizes of %d record bytes: device %d, host encoder %d, zlib level 1 %d" % (len(raw), dev_bytes, len(o), z1), flush=True)
+        b.close()
+    if fastq:
+        import os, tempfile
+        K2 = 9
+        reads = bases.reshape(n, 91)
+        qual = b"F" * 91
+        block = b"".join(b"@SYN:%d 1:N:0:ACGT\n" % i + reads[i].tobytes() + b"\n+\n" + qual + b"\n" for i in range(n))
+        with tempfile.NamedTemporaryFile(suffix=".fastq", delete=False) as f:
+            f.write(block)
+        t0 = time.perf_counter()
+        r = capi.FastqReader(f.name)
+        batch = r.all_by_blocks(n)
+        host_ms = (time.perf_counter() - t0) * 1e3   # (cut + parse + the copies of the test hook: an upper bound)
+        r.close()
+        os.remove(f.name)
+        b = capi.Aligner(ix, opts)
+        src = np.frombuffer(block, np.uint8)
+        info = capi.FastqUploadInfo()
+        rb, keep = capi.read_batch_struct(batch)
+
+        def up_fastq():
+            b._chk(capi.lib().thm_batch_upload_fastq(b.h, src.ctypes.data, len(block), b"perf", 1, 1, capi.C.byref(info)))
+
+        def up_reads():
+            b._chk(capi.lib().thm_batch_upload_reads(b.h, capi.C.byref(rb)))
+
+        for _ in range(2):   # buffers grow
+            up_fastq(); up_reads()
+        mf, mr, md = [], [], []
+        for _ in range(K2):   # alternately, in one session
+            t0 = time.perf_counter(); up_fastq(); mf.append((time.perf_counter() - t0) * 1e3); md.append(info.device_ms)
+            t0 = time.perf_counter(); up_reads(); mr.append((time.perf_counter() - t0) * 1e3)
+        assert info.on_device == 1 and info.n_reads == n
+        print("         upload_fastq median %.2f ms (min %.2f max %.2f)  block of %d bytes, %d reads  device_ms median %.3f (min %.3f max %.3f)" % (
+            float(np.median(mf)), min(mf), max(mf), len(block), n, float(np.median(md)), min(md), max(md)), flush=True)
+        print("         upload_reads median %.2f ms (min %.2f max %.2f)  %d bytes in five arrays; host cut + parse of the block, one thread, at most %.1f ms" % (
+            float(np.median(mr)), min(mr), max(mr), sum(np.asarray(batch[k]).nbytes for k in batch), host_ms), flush=True)
         b.close()
     c = dict(zip(capi.COUNTER_NAMES, a.counters().tolist()))
     runs = K + 2
