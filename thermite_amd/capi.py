@@ -338,6 +338,12 @@ def lib():
     if hasattr(L, "thm_debug_set_pool_caps"):
         L.thm_debug_set_pool_caps.restype = i32
         L.thm_debug_set_pool_caps.argtypes = [vp, u64, u64, u64, vp]
+    if hasattr(L, "thm_debug_host_table"):
+        L.thm_debug_host_table.restype = i32
+        L.thm_debug_host_table.argtypes = [vp, i32, vp, u64, vp]
+    if hasattr(L, "thm_debug_smem_finish_stats"):
+        L.thm_debug_smem_finish_stats.restype = i32
+        L.thm_debug_smem_finish_stats.argtypes = [vp, vp]
     if hasattr(L, "thm_debug_set_flags"):
         L.thm_debug_set_flags.restype = i32
         L.thm_debug_set_flags.argtypes = [vp, C.c_uint32]
@@ -549,6 +555,19 @@ class Index:
         out = np.zeros((4 ** kt.value, 2), "<u8" if self.coord_bytes == 8 else "<u4")
         if lib().thm_debug_host_lut(self.h, C.byref(kt), _ptr(out), out.nbytes) != 0:
             raise ThermiteError(ERR_INTERNAL, "thm_debug_host_lut")
+        return out
+
+    HOST_TABLES = ("ref_bin", "ref_recs", "exon_grid_off", "exon_grid", "gene_grid_off", "gene_grid")
+
+    def debug_host_table(self, name):
+        """test hook: one of HOST_TABLES as the extend stage's kernels get it (raw bytes, the index's coordinate width)"""
+        which = self.HOST_TABLES.index(name)
+        n = C.c_uint64()
+        if lib().thm_debug_host_table(self.h, which, None, 0, C.byref(n)) != 0:
+            raise ThermiteError(ERR_INTERNAL, "thm_debug_host_table")
+        out = np.zeros(n.value, np.uint8)
+        if lib().thm_debug_host_table(self.h, which, _ptr(out), out.nbytes, C.byref(n)) != 0:
+            raise ThermiteError(ERR_INTERNAL, "thm_debug_host_table")
         return out
 
     def idx_to_ref(self, idx):
@@ -875,17 +894,22 @@ class Aligner:
         self._chk(lib().thm_debug_set_pool_caps(self.h, smem_cap, cand_cap, ops_cap, C.byref(n)))
         return n.value
 
-    def debug_set_flags(self, tpr=None, rounds=0, seed_infer=None, seed_stats=None, seed_direct=None):
+    def debug_set_flags(self, tpr=None, rounds=0, seed_infer=None, seed_stats=None, seed_direct=None, finish_exact=None,
+                        finish_subst=None):
         """test / tuning hook: tpr = False: every read takes the wave-per-read kernels, True: the problem-parallel path
         in front of them (None: keep); rounds = its request rounds (1..8, 0: keep); seed_infer = False: no seed probe
         is decided from its table entry and a neighbouring match (bit 2 of the word; True: bit 4, on again);
         seed_stats = True: the seed kernels count their probes for debug_seed_stats (bit 3; False: bit 5);
         seed_direct = False: a probe into a single-suffix bucket reads the suffix array although its table entry holds
-        the text position (bit 6; True: bit 7, the position is used again).  None: keep."""
+        the text position (bit 6; True: bit 7, the position is used again); finish_exact = False: the finisher in front
+        of the extend kernel leaves whole-read exact matches (class E) to it (bit 12; True: bit 13, it takes them);
+        finish_subst: the same for reads with one substitution between two SMEMs (class S, bits 14 / 15).  None: keep."""
         word = (0 if tpr is None else (2 if tpr else 1)) | (int(rounds) << 8)
         word |= 0 if seed_infer is None else (16 if seed_infer else 4)
         word |= 0 if seed_stats is None else (8 if seed_stats else 32)
         word |= 0 if seed_direct is None else (128 if seed_direct else 64)
+        word |= 0 if finish_exact is None else (0x2000 if finish_exact else 0x1000)
+        word |= 0 if finish_subst is None else (0x8000 if finish_subst else 0x4000)
         self._chk(lib().thm_debug_set_flags(self.h, word))
 
     def debug_seed_stats(self):
@@ -893,6 +917,13 @@ class Aligner:
         out = np.zeros(2, "<u8")
         self._chk(lib().thm_debug_seed_stats(self.h, _ptr(out)))
         return int(out[0]), int(out[1])
+
+    def debug_smem_finish_stats(self):
+        """thm_debug_smem_finish_stats, the finisher in the last batch: (class E reads finished, reads of class E's shape
+        left to the extend kernel, class S finished, class S left); zeros when it did not run"""
+        out = np.zeros(4, "<u8")
+        self._chk(lib().thm_debug_smem_finish_stats(self.h, _ptr(out)))
+        return tuple(int(x) for x in out)
 
     def debug_seed_direct_stats(self):
         """thm_debug_seed_direct_stats: (the device table holds text positions in its single-suffix entries, entries

@@ -256,7 +256,7 @@ void thm_aligner_free(thm_aligner* a) {
   if (a->stream3) (void)hipStreamSynchronize(a->stream3);
   if (a->stream4) (void)hipStreamSynchronize(a->stream4);
   DBuf* all[] = {&a->d_counters, &a->d_ctl, &a->b0, &a->b1, &a->b2, &a->b3, &a->b4,
-                 &a->b5, &a->b6, &a->b7, &a->b8, &a->r_bases, &a->r_offsets, &a->r_san, &a->s_ms_end, &a->s_ms_lo, &a->s_ms_hi, &a->s_work_reads, &a->s_work_long, &a->s_work_cells, &a->s_fill_keys, &a->s_fill_perm, &a->s_fill_hist, &a->s_sel_scratch, &a->s_heavy, &a->s_slow, &a->s_team, &a->r_status, &a->e_slow, &a->e_recs, &a->e_wcnt, &a->t_memos, &a->t_recs, &a->t_dpops, &a->t_qlist, &a->t_act[0], &a->t_act[1], &a->t_ctl, &a->t_bail, &a->t_queue2, &a->t_trace, &a->t_ttrace, &a->t_hdr, &a->t_sums, &a->s_smems, &a->s_off, &a->s_cnt,
+                 &a->b5, &a->b6, &a->b7, &a->b8, &a->r_bases, &a->r_offsets, &a->r_san, &a->s_ms_end, &a->s_ms_lo, &a->s_ms_hi, &a->s_work_reads, &a->s_work_long, &a->s_work_cells, &a->s_fill_keys, &a->s_fill_perm, &a->s_fill_hist, &a->s_sel_scratch, &a->s_heavy, &a->s_slow, &a->s_team, &a->r_status, &a->e_slow, &a->e_recs, &a->e_wcnt, &a->e_finstats, &a->t_memos, &a->t_recs, &a->t_dpops, &a->t_qlist, &a->t_act[0], &a->t_act[1], &a->t_ctl, &a->t_bail, &a->t_queue2, &a->t_trace, &a->t_ttrace, &a->t_hdr, &a->t_sums, &a->s_smems, &a->s_off, &a->s_cnt,
                  &a->s_hits, &a->s_cand_off, &a->scan_tmp, &a->e_cands, &a->e_heavy, &a->e_rel, &a->e_order, &a->e_ops, &a->e_nalns,
                  &a->e_opbytes, &a->e_aln_off, &a->e_ops_off, &a->e_trace, &a->o_alns, &a->o_ops, &a->o_mems,
                  &a->sh_bases, &a->sh_san, &a->sh_off, &a->sh_hits, &a->sh_read, &a->sh_bw, &a->sh_xd, &a->sh_list, &a->sh_out,
@@ -620,6 +620,27 @@ int32_t thm_debug_set_flags(thm_aligner* a, uint32_t flags) {
   // table stays as it is; lut_direct.h), bit 7: it uses the position again
   if (flags & 64u) a->dbg_seed_nodirect = true;
   if (flags & 128u) a->dbg_seed_nodirect = false;
+  // bit 12: the finisher (kernels_finish.hip) leaves class E (whole-read exact matches) to the extend kernel, bit 13: it
+  // takes them again; bits 14 / 15: the same for class S (one substitution between two SMEMs).  Default: both on.
+  if (flags & 0x1000u) a->fin_classes &= ~1u;
+  if (flags & 0x2000u) a->fin_classes |= 1u;
+  if (flags & 0x4000u) a->fin_classes &= ~2u;
+  if (flags & 0x8000u) a->fin_classes |= 2u;
+  return THM_OK;
+}
+// thm_debug_smem_finish_stats: the finisher in the last batch -- [0] reads of class E it finished, [1] reads with class E's
+// SMEM shape it left to the extend kernel, [2] / [3] the same for class S (zeros when it did not run: a class switched
+// off is not counted)
+int32_t thm_debug_smem_finish_stats(thm_aligner* a, uint64_t stats[4]) {
+  if (!a || !stats) return THM_ERR_INVALID_ARG;
+  stats[0] = stats[1] = stats[2] = stats[3] = 0;
+  if (!a->fin_blocks || !a->e_finstats.p) return THM_OK;
+  HIPCHK(a, hipSetDevice(a->device));
+  HIPCHK(a, hipStreamSynchronize(a->stream));
+  std::vector<unsigned long long> rows((size_t)a->fin_blocks * 4);
+  HIPCHK(a, hipMemcpy(rows.data(), a->e_finstats.p, rows.size() * 8, hipMemcpyDeviceToHost));
+  for (size_t b = 0; b < a->fin_blocks; b++)
+    for (int k = 0; k < 4; k++) stats[k] += rows[b * 4 + k];
   return THM_OK;
 }
 // thm_debug_seed_stats: the last batch's seed stage, counted when bit 3 of thm_debug_set_flags is set (else zeros) --

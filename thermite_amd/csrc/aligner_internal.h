@@ -165,6 +165,15 @@ struct thm_aligner {
   bool dbg_seed_noinfer = false, dbg_seed_stats = false;
   // ... bit 6: a probe into a single-suffix bucket reads sa[lo] although the table entry holds the text position
   bool dbg_seed_nodirect = false;
+  // The finisher (kernels_finish.hip): classes it takes (thm_debug_set_flags bits 12..15; fin::CLASS_E | fin::CLASS_S), the
+  // read-only op run at the front of e_ops (where it was written and for which read length, 0: none; while it exists every
+  // run starts the pool's cursor behind it), the classes and workgroups of the last enqueue, its per-workgroup statistics
+  uint32_t fin_classes = 3;
+  const void* ops_run_ptr = nullptr;
+  size_t ops_run_cap = 0;
+  uint32_t ops_run_half = 0;
+  uint32_t fin_run_classes = 0, fin_blocks = 0;
+  DBuf e_finstats;
   uint32_t n_replays = 0;  // pool-overflow replays since the aligner was created
   bool ran = false, synced = false;
   hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};

@@ -665,6 +665,33 @@ int32_t thm_debug_host_lut(const thm_index* ix, uint32_t* kt, void* out, uint64_
   return THM_OK;
 }
 
+// test hook: a table of the host index the extend stage reads, as its kernels get it (the index's coordinate width) --
+// which = 0 ref_bin, 1 ref_recs, 2 exon_grid_off, 3 exon_grid, 4 gene_grid_off, 5 gene_grid.  *bytes gets the table's
+// size; with `out`, cap >= that size, the table is copied.
+int32_t thm_debug_host_table(const thm_index* ix, int32_t which, void* out, uint64_t cap, uint64_t* bytes) {
+  if (!ix || !bytes) return THM_ERR_INVALID_ARG;
+  const void* src = nullptr;
+  uint64_t have = 0;
+  auto pick = [&](const auto& v) {
+    src = v.data();
+    have = (uint64_t)v.size() * sizeof(v[0]);
+  };
+  switch (which) {
+    case 0: pick(ix->ref_bin); break;
+    case 1: ix->wide ? pick(ix->ref_recs64) : pick(ix->ref_recs); break;
+    case 2: pick(ix->exon_grid_off); break;
+    case 3: ix->wide ? pick(ix->exon_grid64) : pick(ix->exon_grid); break;
+    case 4: pick(ix->gene_grid_off); break;
+    case 5: ix->wide ? pick(ix->gene_grid64) : pick(ix->gene_grid); break;
+    default: return THM_ERR_INVALID_ARG;
+  }
+  *bytes = have;
+  if (!out) return THM_OK;
+  if (cap < have) return THM_ERR_INVALID_ARG;
+  if (have) memcpy(out, src, have);
+  return THM_OK;
+}
+
 uint64_t thm_index_text_len(const thm_index* ix) { return ix ? ix->n : 0; }
 const uint32_t* thm_index_suffix_array(const thm_index* ix) { return (ix && !ix->wide) ? ix->sa.data() : nullptr; }
 

@@ -1029,6 +1029,7 @@ template <class C>
 __global__ __launch_bounds__(256) void plan_pack_kernel(PlanParams p, PackParamsT<C> q) {
   const uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   const bool active = r < p.n_reads;
+  if (r == 0 && p.ops_start) *p.ops_cursor = p.ops_start;  // the extend kernels allocate behind the finisher's op run
   uint64_t b0 = 0, L = 0, hits = 0;
   if (active) {
     b0 = p.offsets[r];

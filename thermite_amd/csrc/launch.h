@@ -172,6 +172,8 @@ struct PlanParams {
   int32_t* read_status;
   uint32_t* read_n_alns;       // zeroed for unsupported reads
   uint64_t* read_op_bytes;
+  unsigned long long* ops_cursor;  // head of the candidate op pool (zeroed when the run began) ...
+  uint64_t ops_start;              // ... starts here: behind the finisher's read-only op run (0: no run, nothing is written)
 };
 
 // Everything the extend kernel needs to start on a read, in one 64-byte record (one scalar load instead of a chain of
@@ -332,6 +334,31 @@ inline bool team_fits_lds(size_t lds4) { return lds4 / 4 * TEAM_WAVES + TEAM_STA
 // team = true: the workgroup-per-read variant for reads with very many hits (cpl 1 or 2 only; TEAM_WAVES waves per workgroup)
 hipError_t launch_extend(const ExtendParamsT<uint32_t>& p, int cpl, int n_blocks, hipStream_t s, bool team = false);
 hipError_t launch_extend(const ExtendParamsT<uint64_t>& p, int cpl, int n_blocks, hipStream_t s, bool team = false);
+// ---- the finisher (kernels_finish.hip, smem_finish.h): one thread per read, between plan_pack_kernel and the wave-per-read
+// extend kernel; reads whose SMEMs decide their whole result are finished here and marked in their records ----
+template <class C>
+struct FinishParamsT {
+  DeviceIndexT<C> ix;
+  ReadBatch reads;
+  thm_align_opts opts;
+  const SmemT<C>* smems;
+  ReadRecT<C>* recs;        // = ExtendParamsT::read_recs, writable: a finished read gets len = 0xFFFFFFFF
+  Cand* cands;
+  uint64_t cand_cap;
+  uint32_t* order;
+  uint32_t* read_n_alns;
+  uint64_t* read_op_bytes;
+  unsigned long long* rows;   // [workgroups of the launch][THM_N_COUNTERS]: rows of ExtendParamsT::wave_counters
+  unsigned long long* stats;  // [workgroups of the launch][4]: class E finished, left, class S finished, left
+  const int* fault_seed;
+  uint32_t max_read_len, max_bw, cpl;  // the fast class as the wave-per-read launch sees it
+  uint32_t classes;                    // fin::CLASS_E | fin::CLASS_S
+  uint32_t run_half;                   // the op run at the front of cand_ops: Match x run_half, Subst, Match x run_half
+};
+hipError_t launch_smem_finish(const FinishParamsT<uint32_t>& p, int n_blocks, hipStream_t s);
+hipError_t launch_smem_finish(const FinishParamsT<uint64_t>& p, int n_blocks, hipStream_t s);
+constexpr int FINISH_BLOCKS_PER_CU = 8;  // the finisher strides over the batch with at most this many workgroups per CU
+
 // ---- hit summaries (kernels_hit.hip): the part of align_seed_hit that does not depend on the state align_read carries
 // from hit to hit (band, X-drop, best score), computed once per hit by a group of eight lanes ----
 // What an extension looks like before any DP (swg_device.h::swg_one_mismatch_shortcut and the bound argument in

@@ -21,6 +21,7 @@
 #include <cstring>
 
 #include "aligner_internal.h"
+#include "smem_finish.h"
 
 using namespace thm;
 
@@ -339,7 +340,10 @@ int enqueue_extend_t(thm_aligner* a, const ExtClasses& cls, uint32_t mk_cap_slow
   // rows: [main | team | slow | control kernel's workgroups | the wave-per-read launch for what the control kernel leaves]
   const int bail_blocks = tpr ? std::min(ext_blocks, a->n_cu) : 0;
   const uint64_t tpr_rows = (uint64_t)ctl_blocks + (uint64_t)bail_blocks * 4;
-  const uint64_t n_rows = main_rows + team_rows + slow_waves + tpr_rows;
+  // the finisher (kernels_finish.hip) in front of the wave-per-read kernel: a row per workgroup behind the others
+  const int fin_blocks = (!tpr && a->fin_run_classes && n > 0) ? (int)std::min<uint64_t>((n + 255) / 256, (uint64_t)a->n_cu * FINISH_BLOCKS_PER_CU) : 0;
+  a->fin_blocks = (uint32_t)fin_blocks;
+  const uint64_t n_rows = main_rows + team_rows + slow_waves + tpr_rows + (uint64_t)fin_blocks;
   // The rows are zero from one run to the next (launch_counters_reduce zeroes what it read, and no launch writes past
   // its run's n_rows): only a new allocation is zeroed here -- or the rows of an enqueue that failed half way.
   HIPCHK(a, a->e_wcnt.ensure(n_rows * THM_N_COUNTERS * 8 + 64));
@@ -347,6 +351,28 @@ int enqueue_extend_t(thm_aligner* a, const ExtClasses& cls, uint32_t mk_cap_slow
   a->wcnt_clean_cap = 0;
   ep.wave_counters = a->e_wcnt.as<unsigned long long>();
   ep.skip_scan = 0;
+  FinishParamsT<C> fp;
+  if (fin_blocks) {
+    HIPCHK(a, a->e_finstats.ensure((size_t)fin_blocks * 4 * 8));
+    fp.ix = ep.ix;
+    fp.reads = ep.reads;
+    fp.opts = ep.opts;
+    fp.smems = ep.smems;
+    fp.recs = a->e_recs.as<ReadRecT<C>>();
+    fp.cands = ep.cands;
+    fp.cand_cap = ep.cand_cap;
+    fp.order = ep.order;
+    fp.read_n_alns = ep.read_n_alns;
+    fp.read_op_bytes = ep.read_op_bytes;
+    fp.rows = ep.wave_counters + (main_rows + team_rows + slow_waves + tpr_rows) * THM_N_COUNTERS;
+    fp.stats = a->e_finstats.as<unsigned long long>();
+    fp.fault_seed = ep.fault_seed;
+    fp.max_read_len = ep.max_read_len;
+    fp.max_bw = ep.max_bw;
+    fp.cpl = (uint32_t)cpl;
+    fp.classes = a->fin_run_classes;
+    fp.run_half = a->ops_run_half;
+  }
   if (tpr) {
     const uint64_t rec_cap = std::min<uint64_t>(4 * n + 65536, 64ull << 20);
     HIPCHK(a, a->t_memos.ensure(n * sizeof(ReadMemo) + 64));
@@ -480,6 +506,10 @@ int enqueue_extend_t(thm_aligner* a, const ExtClasses& cls, uint32_t mk_cap_slow
     tp.list_only = 1;
     tp.wave_counters = ep.wave_counters + main_rows * THM_N_COUNTERS;
     tp.trace_scratch = ep.trace_scratch + main_trace_waves * trace_per_wave / 8;
+    // The finisher runs before the fork, with the machine to itself.  (On the main kernel's stream, beside the team kernel --
+    // whose reads are never the finisher's -- it was measured at 120 - 430 us instead: a team workgroup takes a whole CU's
+    // registers, and the main kernel waited for the finisher all that time)
+    if (fin_blocks) HIPCHK(a, launch_smem_finish(fp, fin_blocks, s));
     HIPCHK(a, hipEventRecord(a->ev_fork, s));
     HIPCHK(a, launch_extend(tp, cpl, a->n_cu, s, true));
     HIPCHK(a, hipStreamWaitEvent(a->stream2, a->ev_fork, 0));
@@ -487,6 +517,7 @@ int enqueue_extend_t(thm_aligner* a, const ExtClasses& cls, uint32_t mk_cap_slow
     HIPCHK(a, hipEventRecord(a->ev_join, a->stream2));
     HIPCHK(a, hipStreamWaitEvent(s, a->ev_join, 0));
   } else {
+    if (fin_blocks) HIPCHK(a, launch_smem_finish(fp, fin_blocks, s));
     HIPCHK(a, launch_extend(ep, cpl, ext_blocks, s));
   }
   // ---- slow class (and the fast kernel's retries) ----
@@ -537,7 +568,8 @@ int enqueue_run(thm_aligner* a) {
   HIPCHK(a, a->e_aln_off.ensure((n + 2) * 8));
   HIPCHK(a, a->e_ops_off.ensure((n + 2) * 8));
   HIPCHK(a, a->o_alns.ensure(a->cand_cap * sizeof(thm_aln)));
-  HIPCHK(a, a->o_ops.ensure(a->cand_ops_cap + 64));
+  // (a finished read's op bytes are not taken from the pool: 2 L at most per read on top of what the pool holds)
+  HIPCHK(a, a->o_ops.ensure(a->cand_ops_cap + 2 * a->n_bases + 64));
   HIPCHK(a, a->s_heavy.ensure((n + 1) * 8));
   HIPCHK(a, a->s_slow.ensure((n + 1) * 8));
   HIPCHK(a, a->s_team.ensure((n + 1) * 8));
@@ -549,6 +581,24 @@ int enqueue_run(thm_aligner* a) {
   a->n_slow_host = cls.n_slow;
   a->fast_max_len = cls.fast_max;
   a->slow_max_len = cls.slow_max;
+  // The finisher's op run (smem_finish.h): Match x H, Subst, Match x H at the front of the op pool, H = the longest read of
+  // the fast class so far.  It is written when the finisher is wanted and the pool is new (growth, replay) or H grows.  Once
+  // it exists, EVERY run on this aligner starts the pool's cursor behind it -- also a run without the finisher (both classes
+  // switched off, the problem-parallel path, a batch without a read of the fast class) -- so nothing ever writes there.  The
+  // one run that cannot keep it, a pool (test hook) too small to hold it, forgets it: it is written again when next wanted.
+  const bool run_valid = a->ops_run_half > 0 && a->ops_run_ptr == a->e_ops.p && a->ops_run_cap == a->e_ops.cap;
+  if (!run_valid) a->ops_run_half = 0;
+  const bool fin_wanted = !a->use_tpr && a->fin_classes && cls.fast_len > 0;
+  if (fin_wanted && a->ops_run_half < cls.fast_len && fin::run_bytes(cls.fast_len) <= a->cand_ops_cap) {
+    HIPCHK(a, hipMemsetAsync(a->e_ops.p, THM_OP_MATCH, fin::run_bytes(cls.fast_len), s));
+    HIPCHK(a, hipMemsetAsync(a->e_ops.as<uint8_t>() + cls.fast_len, THM_OP_SUBST, 1, s));
+    a->ops_run_ptr = a->e_ops.p;
+    a->ops_run_cap = a->e_ops.cap;
+    a->ops_run_half = cls.fast_len;
+  }
+  if (a->ops_run_half && fin::run_bytes(a->ops_run_half) > a->cand_ops_cap) a->ops_run_half = 0;  // this run writes over it
+  const uint64_t ops_start = a->ops_run_half ? fin::run_bytes(a->ops_run_half) : 0;
+  a->fin_run_classes = (fin_wanted && a->ops_run_half >= cls.fast_len) ? a->fin_classes : 0;
   PlanParams pp;
   pp.offsets = a->r_offsets.as<uint64_t>();
   pp.read_hits = a->s_hits.as<uint64_t>();
@@ -569,6 +619,8 @@ int enqueue_run(thm_aligner* a) {
   pp.read_status = a->r_status.as<int32_t>();
   pp.read_n_alns = a->e_nalns.as<uint32_t>();
   pp.read_op_bytes = a->e_opbytes.as<uint64_t>();
+  pp.ops_cursor = a->d_cursors.as<unsigned long long>() + 1;
+  pp.ops_start = ops_start;
   rc = a->dix->wide ? enqueue_plan_pack_t<uint64_t>(a, pp) : enqueue_plan_pack_t<uint32_t>(a, pp);
   if (rc != THM_OK) return rc;
   HIPCHK(a, hipEventRecord(a->ev[2], s));
@@ -594,7 +646,7 @@ int enqueue_run(thm_aligner* a) {
   cp.ops = a->o_ops.as<uint8_t>();
   cp.fault = a->d_fault.as<int>();
   cp.alns_cap = a->cand_cap;
-  cp.ops_cap = a->cand_ops_cap;
+  cp.ops_cap = a->cand_ops_cap + 2 * a->n_bases;
   // (a heavy read has more than 8 alignments and a descriptor stands for 4 of them: cand_cap / 2 entries hold either list)
   cp.heavy_cap = a->cand_cap / 2 + 16;
   cp.heavy_cnt = a->d_cursors.as<unsigned long long>() + 2;  // zeroed with the cursors when the batch starts
