@@ -215,18 +215,12 @@ int32_t thm_aligner_create(const thm_index* ix, const thm_align_opts* opts, int3
   if (hipSetDevice(device_id) != hipSuccess) return bail(fail(nullptr, THM_ERR_HIP, "hipSetDevice failed"));
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device_id) == hipSuccess) a->n_cu = prop.multiProcessorCount;
-  if (hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking) != hipSuccess)
-    return bail(fail(nullptr, THM_ERR_HIP, "hipStreamCreate failed"));
-  for (auto& e : a->ev)
-    if (hipEventCreate(&e) != hipSuccess) return bail(fail(nullptr, THM_ERR_HIP, "hipEventCreate failed"));
-  if (hipStreamCreateWithFlags(&a->stream2, hipStreamNonBlocking) != hipSuccess ||
-      hipStreamCreateWithFlags(&a->stream3, hipStreamNonBlocking) != hipSuccess ||
-      hipStreamCreateWithFlags(&a->stream4, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(&a->ev_dpt_fork, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&a->ev_dpt_join, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&a->ev_join3, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&a->ev_fork, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&a->ev_join, hipEventDisableTiming) != hipSuccess)
+  if (a->stream.create() != hipSuccess) return bail(fail(nullptr, THM_ERR_HIP, "hipStreamCreate failed"));
+  if (ensure_events(a->ev) != hipSuccess) return bail(fail(nullptr, THM_ERR_HIP, "hipEventCreate failed"));
+  if (a->stream2.create() != hipSuccess || a->stream3.create() != hipSuccess || a->stream4.create() != hipSuccess ||
+      a->ev_dpt_fork.ensure(false) != hipSuccess || a->ev_dpt_join.ensure(false) != hipSuccess ||
+      a->ev_join3.ensure(false) != hipSuccess || a->ev_fork.ensure(false) != hipSuccess ||
+      a->ev_join.ensure(false) != hipSuccess)
     return bail(fail(nullptr, THM_ERR_HIP, "second stream / events: creation failed"));
   if (a->d_counters.ensure(THM_N_COUNTERS * 8 * 3) != hipSuccess || a->d_ctl.ensure(thm_aligner::CTL_BYTES) != hipSuccess)
     return bail(fail(nullptr, THM_ERR_OOM, "scratch allocation failed"));
@@ -251,61 +245,9 @@ int32_t thm_aligner_create(const thm_index* ix, const thm_align_opts* opts, int3
 void thm_aligner_free(thm_aligner* a) {
   if (!a) return;
   (void)hipSetDevice(a->device);
-  if (a->stream) (void)hipStreamSynchronize(a->stream);
-  if (a->stream2) (void)hipStreamSynchronize(a->stream2);
-  if (a->stream3) (void)hipStreamSynchronize(a->stream3);
-  if (a->stream4) (void)hipStreamSynchronize(a->stream4);
-  DBuf* all[] = {&a->d_counters, &a->d_ctl, &a->b0, &a->b1, &a->b2, &a->b3, &a->b4,
-                 &a->b5, &a->b6, &a->b7, &a->b8, &a->r_bases, &a->r_offsets, &a->r_san, &a->s_ms_end, &a->s_ms_lo, &a->s_ms_hi, &a->s_work_reads, &a->s_work_long, &a->s_work_cells, &a->s_fill_keys, &a->s_fill_perm, &a->s_fill_hist, &a->s_sel_scratch, &a->s_heavy, &a->s_slow, &a->s_team, &a->r_status, &a->e_slow, &a->e_recs, &a->e_wcnt, &a->e_finstats, &a->t_memos, &a->t_recs, &a->t_dpops, &a->t_qlist, &a->t_act[0], &a->t_act[1], &a->t_ctl, &a->t_bail, &a->t_queue2, &a->t_trace, &a->t_ttrace, &a->t_hdr, &a->t_sums, &a->s_smems, &a->s_off, &a->s_cnt,
-                 &a->s_hits, &a->s_cand_off, &a->scan_tmp, &a->e_cands, &a->e_heavy, &a->e_rel, &a->e_order, &a->e_ops, &a->e_nalns,
-                 &a->e_opbytes, &a->e_aln_off, &a->e_ops_off, &a->e_trace, &a->o_alns, &a->o_ops, &a->o_mems,
-                 &a->sh_bases, &a->sh_san, &a->sh_off, &a->sh_hits, &a->sh_read, &a->sh_bw, &a->sh_xd, &a->sh_list, &a->sh_out,
-                 &a->sh_status, &a->sh_ops, &a->sh_ctl, &a->sh_trace, &a->sh_slow, &a->c_sums, &a->c_nwords, &a->c_woff,
-                 &a->c_scan_tmp, &a->c_flags, &a->c_dig, &a->c_words, &a->c_in_ops, &a->c_in_off,
-                 &a->bn_names, &a->bn_name_off, &a->bn_quals, &a->bt_tx_pool, &a->bt_tx_off, &a->bt_gid_pool, &a->bt_gid_off,
-                 &a->bt_gname_pool, &a->bt_gname_off, &a->bt_tx_gene, &a->bt_ref_sq, &a->bm_cnt, &a->bm_first, &a->bm_qn,
-                 &a->bm_rec_read, &a->bm_len, &a->bm_off, &a->bm_out, &a->bm_read_off, &a->bm_err, &a->bm_scan_tmp,
-                 &a->bz_match, &a->bz_slots, &a->bz_sizes, &a->bz_off, &a->bz_out, &a->bz_scan_tmp, &a->bz_dbg_in,
-                 &a->fq_raw, &a->fq_cnt, &a->fq_base, &a->fq_lines, &a->fq_name_len, &a->fq_seq_len, &a->fq_flag, &a->fq_scan_tmp};
-  for (DBuf* b : all) b->release();
-  for (int k = 0; k < 2; k++) {
-    a->r_off[k].release();
-    a->r_alns[k].release();
-    a->r_ops[k].release();
-    a->r_stat[k].release();
-    a->ch_off[k].release();
-    a->ch_alns[k].release();
-    a->ch_dig[k].release();
-    a->ch_words[k].release();
-    a->ch_stat[k].release();
-    a->bh_data[k].release();
-    a->bh_off[k].release();
-    a->bh_stat[k].release();
-    a->zh_data[k].release();
-    a->zh_off[k].release();
-    a->zh_stat[k].release();
-  }
-  HBuf* pinned[] = {&a->fq_h_off, &a->fr_bases, &a->fr_off, &a->fr_quals, &a->fr_names, &a->fr_name_off};
-  for (HBuf* b : pinned) b->release();
-  for (auto& e : a->ev_fq)
-    if (e) (void)hipEventDestroy(e);
-  for (auto& e : a->ev_cig)
-    if (e) (void)hipEventDestroy(e);
-  for (auto& e : a->ev_bam)
-    if (e) (void)hipEventDestroy(e);
-  for (auto& e : a->ev_bgzf)
-    if (e) (void)hipEventDestroy(e);
-  for (auto& e : a->ev)
-    if (e) (void)hipEventDestroy(e);
-  if (a->ev_fork) (void)hipEventDestroy(a->ev_fork);
-  if (a->ev_join) (void)hipEventDestroy(a->ev_join);
-  if (a->ev_join3) (void)hipEventDestroy(a->ev_join3);
-  if (a->ev_dpt_fork) (void)hipEventDestroy(a->ev_dpt_fork);
-  if (a->ev_dpt_join) (void)hipEventDestroy(a->ev_dpt_join);
-  if (a->stream4) (void)hipStreamDestroy(a->stream4);
-  if (a->stream3) (void)hipStreamDestroy(a->stream3);
-  if (a->stream2) (void)hipStreamDestroy(a->stream2);
-  if (a->stream) (void)hipStreamDestroy(a->stream);
+  // work may still be in flight; after it every buffer, event and stream frees itself (aligner_internal.h)
+  for (const Stream* s : {&a->stream, &a->stream2, &a->stream3, &a->stream4})
+    if (s->s) (void)hipStreamSynchronize(s->s);
   delete a;
 }
 

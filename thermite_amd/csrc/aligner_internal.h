@@ -6,20 +6,27 @@
 #include <cstdarg>
 #include <cstdio>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "launch.h"
 #include "thermite_internal.h"
 
+// Ownership: a DBuf, an HBuf, an Event and a Stream each free what they hold when they are destroyed, and none of them
+// can be copied, so `delete` of the struct that holds them (thm_aligner, thm_index::DevCopy) is the whole clean-up and a
+// new member needs no entry anywhere.
+
 // grow-only device buffer
 struct DBuf {
   void* p = nullptr;
   size_t cap = 0;
+  DBuf() = default;
+  DBuf(const DBuf&) = delete;
+  DBuf& operator=(const DBuf&) = delete;
+  ~DBuf() { release(); }
   hipError_t ensure(size_t bytes) {
     if (bytes <= cap) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
+    release();
     size_t want = bytes + bytes / 4 + 256;
     hipError_t e = hipMalloc(&p, want);
     if (e == hipSuccess) cap = want;
@@ -50,11 +57,13 @@ struct DView {
 struct HBuf {
   void* p = nullptr;
   size_t cap = 0;
+  HBuf() = default;
+  HBuf(const HBuf&) = delete;
+  HBuf& operator=(const HBuf&) = delete;
+  ~HBuf() { release(); }
   hipError_t ensure(size_t bytes) {
     if (bytes <= cap) return hipSuccess;
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = 0;
+    release();
     size_t want = bytes + bytes / 4 + 4096;
     hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
     if (e == hipSuccess) cap = want;
@@ -69,6 +78,58 @@ struct HBuf {
   T* as() const {
     return (T*)p;
   }
+};
+static_assert(!std::is_copy_constructible_v<DBuf> && !std::is_copy_assignable_v<DBuf>, "one owner per device allocation");
+static_assert(!std::is_copy_constructible_v<HBuf> && !std::is_copy_assignable_v<HBuf>, "one owner per pinned allocation");
+
+// an event of the aligner's: made by the first ensure(), passed to the HIP calls as the hipEvent_t it holds
+struct Event {
+  hipEvent_t e = nullptr;
+  Event() = default;
+  Event(const Event&) = delete;
+  Event& operator=(const Event&) = delete;
+  ~Event() {
+    if (e) (void)hipEventDestroy(e);
+  }
+  hipError_t ensure(bool timed = true) {
+    if (e) return hipSuccess;
+    return timed ? hipEventCreate(&e) : hipEventCreateWithFlags(&e, hipEventDisableTiming);
+  }
+  operator hipEvent_t() const { return e; }
+};
+template <size_t N>
+inline hipError_t ensure_events(Event (&ev)[N]) {
+  for (Event& e : ev)
+    if (hipError_t r = e.ensure(); r != hipSuccess) return r;
+  return hipSuccess;
+}
+// milliseconds from `from` to `to` into *ms, once the stream that recorded them has been synchronised; false, and *ms as
+// it was, where HIP cannot tell
+inline bool elapsed_ms(const Event& from, const Event& to, float* ms) {
+  float t = 0;
+  if (hipEventElapsedTime(&t, from, to) != hipSuccess) return false;
+  *ms = t;
+  return true;
+}
+// ... of two passes with a synchronisation between them: ev[0] to ev[1] plus ev[2] to ev[3], or false as above
+inline bool elapsed_ms(const Event (&ev)[4], float* ms) {
+  float m1 = 0, m2 = 0;
+  if (!elapsed_ms(ev[0], ev[1], &m1) || !elapsed_ms(ev[2], ev[3], &m2)) return false;
+  *ms = m1 + m2;
+  return true;
+}
+
+// a non-blocking stream of the aligner's, made by create()
+struct Stream {
+  hipStream_t s = nullptr;
+  Stream() = default;
+  Stream(const Stream&) = delete;
+  Stream& operator=(const Stream&) = delete;
+  ~Stream() {
+    if (s) (void)hipStreamDestroy(s);
+  }
+  hipError_t create() { return hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
+  operator hipStream_t() const { return s; }
 };
 
 struct thm_index::DevCopy {
@@ -89,11 +150,8 @@ inline void free_dev_copy(thm_index::DevCopy* d) {
   int cur = 0;
   (void)hipGetDevice(&cur);
   (void)hipSetDevice(d->device);
-  DBuf* all[] = {&d->text, &d->sa,         &d->lut,    &d->refs,      &d->name_rank, &d->ref_recs, &d->ref_bin, &d->txs,
-                 &d->exons, &d->exon_txoff, &d->tx_seq, &d->exon_grid_off, &d->exon_grid, &d->gene_grid_off, &d->gene_grid, &d->lut_cnt};
-  for (DBuf* b : all) b->release();
-  (void)hipSetDevice(cur);
   delete d;
+  (void)hipSetDevice(cur);
 }
 
 struct thm_aligner {
@@ -101,13 +159,13 @@ struct thm_aligner {
   thm_index::DevCopy* dix = nullptr;
   int device = 0;
   int n_cu = 256;
-  hipStream_t stream = nullptr;
-  hipStream_t stream2 = nullptr;  // the team kernel runs beside the wave-per-read kernel
-  hipStream_t stream3 = nullptr;  // ... and both beside the rounds of the problem-parallel path
-  hipEvent_t ev_join3 = nullptr;
-  hipStream_t stream4 = nullptr;  // the thread-per-problem DP kernel of a round runs beside the wave-per-problem one
-  hipEvent_t ev_dpt_fork = nullptr, ev_dpt_join = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  // The streams stand in front of every buffer and event: members are destroyed in reverse order, so the streams go last,
+  // after what their work may still have touched has been freed (thm_aligner_free synchronises them first).
+  Stream stream;
+  Stream stream2;  // the team kernel runs beside the wave-per-read kernel
+  Stream stream3;  // ... and both beside the rounds of the problem-parallel path
+  Stream stream4;  // the thread-per-problem DP kernel of a round runs beside the wave-per-problem one
+  Event ev_fork, ev_join, ev_join3, ev_dpt_fork, ev_dpt_join;  // untimed, made by thm_aligner_create
   thm_align_opts opts;
   std::string err;
 
@@ -156,6 +214,8 @@ struct thm_aligner {
   uint64_t cand_cap = 0, cand_ops_cap = 0;
   // compacted outputs
   DBuf o_alns, o_ops, o_mems;
+  // out_alns_cap, out_ops_cap: cand_cap and cand_ops_cap as the last enqueued run had them, which is what a fetch checks the
+  // batch against (thm_debug_set_pool_caps zeroes those two for the next run while this one's views are still being fetched)
   uint64_t out_alns_cap = 0, out_ops_cap = 0;
   // test hook (thm_debug_set_pool_caps): initial pool sizes instead of the heuristics, to force the grow-and-replay path
   uint64_t dbg_smem_cap = 0, dbg_cand_cap = 0, dbg_ops_cap = 0;
@@ -176,7 +236,7 @@ struct thm_aligner {
   DBuf e_finstats;
   uint32_t n_replays = 0;  // pool-overflow replays since the aligner was created
   bool ran = false, synced = false;
-  hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  Event ev[6];  // made by thm_aligner_create
   float timings[THM_N_TIMINGS] = {0};
 
   // host results of the read-level path: two pinned sets used alternately, so that the view
@@ -201,7 +261,7 @@ struct thm_aligner {
   DBuf c_sums, c_nwords, c_woff, c_scan_tmp, c_flags, c_dig, c_words, c_in_ops, c_in_off;
   HBuf ch_off[2], ch_alns[2], ch_dig[2], ch_words[2], ch_stat[2];
   int c_cur = 0;
-  hipEvent_t ev_cig[4] = {nullptr, nullptr, nullptr, nullptr};  // created by the first call
+  Event ev_cig[4];  // made by the first call
   std::vector<thm_aln_digest> h_cig_dig;
   std::vector<uint32_t> h_cig_words;
   // BAM records on the device (bam.hip): names and qualities of the batch (thm_batch_upload_reads), the index's name
@@ -215,14 +275,14 @@ struct thm_aligner {
   HBuf bh_data[2], bh_off[2], bh_stat[2];
   int b_cur = 0;
   int bam_stage = -1;  // emit through LDS and dword stores (1) or byte stores (0); -1: not read from THM_BAM_EMIT yet
-  hipEvent_t ev_bam[4] = {nullptr, nullptr, nullptr, nullptr};  // created by the first call
+  Event ev_bam[4];  // made by the first call
   // BGZF members on the device (bgzf.hip): per-position scratch of the workgroups, the members in their slots, their
   // sizes and the scan, the members behind one another; the bytes thm_debug_bgzf_device uploads; two pinned host sets
   // of their own, used alternately
   DBuf bz_match, bz_slots, bz_sizes, bz_off, bz_out, bz_scan_tmp, bz_dbg_in;
   HBuf zh_data[2], zh_off[2], zh_stat[2];
   int z_cur = 0;
-  hipEvent_t ev_bgzf[2] = {nullptr, nullptr};  // created by the first call
+  Event ev_bgzf[2];  // made by the first call
   // FASTQ blocks parsed on the device (fastq.hip): the block's bytes, newline counts per chunk and their scan, the line
   // starts, the records' lengths and the flag word; the offsets come back into fq_h_off for the length classes.  The
   // blocks that went either way since the aligner was created (thm_debug_fastq_device_blocks).  One pinned set behind
@@ -230,7 +290,7 @@ struct thm_aligner {
   DBuf fq_raw, fq_cnt, fq_base, fq_lines, fq_name_len, fq_seq_len, fq_flag, fq_scan_tmp;
   HBuf fq_h_off;
   uint64_t fq_on_device = 0, fq_on_host = 0;
-  hipEvent_t ev_fq[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // created by the first call
+  Event ev_fq[6];  // made by the first call
   HBuf fr_bases, fr_off, fr_quals, fr_names, fr_name_off;
 };
 
@@ -255,18 +315,30 @@ inline int fail(thm_aligner* a, int code, const char* fmt, ...) {
 
 // cigar.hip: count -> scan -> emit over the streams of `p`; results in c_dig / c_words (synchronises the stream once)
 int run_cigar_passes(thm_aligner* a, thm::CigarParams p, uint64_t n_digests, uint64_t* n_words, unsigned* any_flags);
-int cigar_ensure_events(thm_aligner* a);
 // bam.hip: everything of thm_batch_fetch_bam up to the copies -- after it the records of the run are in bm_out on the
 // device and the per-read byte offsets in bm_read_off (both fetches that hand records out start here; the messages name
 // thm_batch_fetch_bam whichever it is).  Of the timings only `timing`, the caller's own, is touched: zeroed once the
 // arguments have passed; ev_bam[0..3] are left recorded around the size and emit passes.
 struct BamOnDevice {
   uint64_t n_reads = 0, n_alns = 0, n_records = 0, n_bytes = 0;
-  bool any_failed = false;  // a read of the batch may have failed: the statuses are worth copying
+  bool any_failed = false;  // as in BatchSizes
 };
 int bam_records_on_device(thm_aligner* a, uint32_t flags, int timing, BamOnDevice* r);
-// n statuses in `st` (copied from r_status after bam_records_on_device said any_failed) -> the view's two fields
-void bam_failed_reads(const int32_t* st, uint64_t n, uint64_t* n_failed, const int32_t** status);
+// ---- pipeline.hip: the head and the tail of every fetch entry point (after thm_batch_sync; a new one calls all of them)
+struct BatchSizes {
+  uint64_t n_alns = 0, n_ops = 0;  // alignments and op bytes of the compacted batch, checked against the pools
+  bool any_failed = false;         // a read of the batch may have failed: the statuses are worth copying
+};
+// One round trip (a single synchronisation of the stream): e_aln_off[n], e_ops_off[n] and the device's count of
+// out-of-contract reads.  With `h_off` the whole offsets array comes into it, (n + 2) words with the op bytes last; with
+// `d_extra` that device word comes into *extra.
+int fetch_batch_sizes(thm_aligner* a, HBuf* h_off, const uint64_t* d_extra, uint64_t* extra, BatchSizes* z);
+// r_status on its way into `h_stat` where any_failed says so; after the next synchronisation failed_reads fills the two
+// fields of a view from it: the count of reads that failed, and the statuses where there is one (else null)
+int enqueue_statuses(thm_aligner* a, bool any_failed, HBuf& h_stat);
+void failed_reads(const thm_aligner* a, bool any_failed, const HBuf& h_stat, uint64_t* n_failed, const int32_t** status);
+// the two op streams of every alignment in the compacted pool, for run_cigar_passes
+thm::CigarParams compacted_cigar_params(const thm_aligner* a, const BatchSizes& z);
 // pipeline.hip: what thm_batch_upload derives from the offsets of a batch -- n_reads, n_bases, max_read_len, the length
 // classes (len_hist) and n_over -- for every upload path; THM_ERR_INVALID_ARG for offsets that do not start at 0 or descend
 int batch_length_classes(thm_aligner* a, const uint64_t* offsets, uint64_t n_reads);

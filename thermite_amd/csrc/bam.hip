@@ -91,10 +91,8 @@ int bam_records_on_device(thm_aligner* a, uint32_t flags, int timing, BamOnDevic
   if (rc != THM_OK) return rc;
   HIPCHK(a, hipSetDevice(a->device));
   rc = ensure_tables(a);
-  if (rc == THM_OK) rc = cigar_ensure_events(a);
   if (rc != THM_OK) return rc;
-  for (auto& e : a->ev_bam)
-    if (!e) HIPCHK(a, hipEventCreate(&e));
+  HIPCHK(a, ensure_events(a->ev_bam));
   if (a->bam_stage < 0) {  // THM_BAM_EMIT=bytes: the other form of the emit kernel (DESIGN.md section 4.9 has both times)
     const char* e = getenv("THM_BAM_EMIT");
     a->bam_stage = e && !strcmp(e, "bytes") ? 0 : 1;
@@ -140,26 +138,17 @@ int bam_records_on_device(thm_aligner* a, uint32_t flags, int timing, BamOnDevic
   HIPCHK(a, hipMemsetAsync(a->bm_err.p, 0, 64, s));
   HIPCHK(a, launch_bam_prep(p, s));
   HIPCHK(a, launch_exclusive_scan_u64(a->bm_cnt.as<uint64_t>(), a->bm_first.as<uint64_t>(), n, a->bm_scan_tmp.as<uint64_t>(), s));
-  unsigned long long sizes[3] = {0, 0, 0}, n_contract = 0;  // alignments, op bytes, records
-  HIPCHK(a, hipMemcpyAsync(&sizes[0], a->e_aln_off.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(a, hipMemcpyAsync(&sizes[1], a->e_ops_off.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(a, hipMemcpyAsync(&sizes[2], a->bm_first.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(a, hipMemcpyAsync(&n_contract, a->s_work_counts.as<unsigned long long>() + 6, 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(a, hipStreamSynchronize(s));
-  const uint64_t n_alns = sizes[0], n_ops = sizes[1], n_rec = sizes[2];
-  if (n_alns > a->cand_cap || n_ops > a->cand_ops_cap) return fail(a, THM_ERR_INTERNAL, "compacted batch exceeds its pools");
+  BatchSizes z;
+  uint64_t n_rec = 0;
+  rc = fetch_batch_sizes(a, nullptr, a->bm_first.as<uint64_t>() + n, &n_rec, &z);
+  if (rc != THM_OK) return rc;
+  const uint64_t n_alns = z.n_alns;
   if (n_rec > n_alns + n) return fail(a, THM_ERR_INTERNAL, "more BAM records than alignments and reads");
   // ---- the two CIGAR passes, as thm_batch_fetch_cigars runs them (THM_T_CIGAR belongs to that call)
-  CigarParams cp;
-  memset(&cp, 0, sizeof cp);
-  cp.ops = a->o_ops.as<uint8_t>();
-  cp.ops_bytes = n_ops;
-  cp.n_streams = 2 * n_alns;
-  cp.alns = a->o_alns.as<thm_aln>();
   uint64_t n_words = 0;
   unsigned any_flags = 0;
   const float t_cigar = a->timings[THM_T_CIGAR];
-  rc = run_cigar_passes(a, cp, n_alns, &n_words, &any_flags);
+  rc = run_cigar_passes(a, compacted_cigar_params(a, z), n_alns, &n_words, &any_flags);
   a->timings[THM_T_CIGAR] = t_cigar;
   if (rc != THM_OK) return rc;
   p.n_rec = n_rec;
@@ -196,22 +185,12 @@ int bam_records_on_device(thm_aligner* a, uint32_t flags, int timing, BamOnDevic
   HIPCHK(a, launch_bam_emit(p, a->bam_stage == 1, a->n_cu, s));
   HIPCHK(a, hipEventRecord(a->ev_bam[3], s));
   HIPCHK(a, launch_bam_offsets(p, s));
-  uint64_t n_beyond = a->n_over;
-  for (const auto& lc : a->len_hist)
-    if (lc.first > a->slow_max_len) n_beyond += lc.second;
   r->n_reads = n;
   r->n_alns = n_alns;
   r->n_records = n_rec;
   r->n_bytes = n_bytes;
-  r->any_failed = n_beyond || n_contract;
+  r->any_failed = z.any_failed;
   return THM_OK;
-}
-
-void bam_failed_reads(const int32_t* st, uint64_t n, uint64_t* n_failed, const int32_t** status) {
-  uint64_t bad = 0;
-  for (uint64_t i = 0; i < n; i++) bad += st[i] != THM_OK;
-  *n_failed = bad;
-  *status = bad ? st : nullptr;
 }
 
 extern "C" {
@@ -223,7 +202,6 @@ int32_t thm_batch_fetch_bam(thm_aligner* a, uint32_t flags, thm_bam_view* out) {
   int rc = bam_records_on_device(a, flags, THM_T_BAM, &r);
   if (rc != THM_OK) return rc;
   const uint64_t n = r.n_reads, n_rec = r.n_records, n_bytes = r.n_bytes;
-  const bool any_failed = r.any_failed;
   hipStream_t s = a->stream;
   // ---- the copies
   const int k = a->b_cur ^= 1;  // the other set still backs the previous view
@@ -234,20 +212,16 @@ int32_t thm_batch_fetch_bam(thm_aligner* a, uint32_t flags, thm_bam_view* out) {
   HIPCHK(a, h_off.ensure((n + 1) * 8));
   if (n_bytes) HIPCHK(a, hipMemcpyAsync(h_data.p, a->bm_out.p, n_bytes, hipMemcpyDeviceToHost, s));
   HIPCHK(a, hipMemcpyAsync(h_off.p, a->bm_read_off.p, (n + 1) * 8, hipMemcpyDeviceToHost, s));
-  if (any_failed) {
-    HIPCHK(a, h_stat.ensure((n + 1) * 4));
-    HIPCHK(a, hipMemcpyAsync(h_stat.p, a->r_status.p, n * 4, hipMemcpyDeviceToHost, s));
-  }
+  rc = enqueue_statuses(a, r.any_failed, h_stat);
+  if (rc != THM_OK) return rc;
   HIPCHK(a, hipStreamSynchronize(s));
-  float m1 = 0, m2 = 0;
-  if (hipEventElapsedTime(&m1, a->ev_bam[0], a->ev_bam[1]) == hipSuccess && hipEventElapsedTime(&m2, a->ev_bam[2], a->ev_bam[3]) == hipSuccess)
-    a->timings[THM_T_BAM] = m1 + m2;
+  (void)elapsed_ms(a->ev_bam, &a->timings[THM_T_BAM]);
   out->n_reads = n;
   out->n_records = n_rec;
   out->n_bytes = n_bytes;
   out->data = h_data.as<uint8_t>();
   out->read_rec_off = h_off.as<uint64_t>();
-  if (any_failed) bam_failed_reads(h_stat.as<int32_t>(), n, &out->n_failed_reads, &out->read_status);
+  failed_reads(a, r.any_failed, h_stat, &out->n_failed_reads, &out->read_status);
   return THM_OK;
 }
 

@@ -17,8 +17,7 @@ namespace {
 // and sets THM_T_BGZF
 int bgzf_on_device(thm_aligner* a, const uint8_t* d_in, uint64_t n, uint64_t* n_blocks, uint64_t* n_bytes) {
   hipStream_t s = a->stream;
-  for (auto& e : a->ev_bgzf)
-    if (!e) HIPCHK(a, hipEventCreate(&e));
+  HIPCHK(a, ensure_events(a->ev_bgzf));
   a->timings[THM_T_BGZF] = 0;
   const uint64_t nb = (n + bgz::BLOCK_IN - 1) / bgz::BLOCK_IN;
   *n_blocks = nb;
@@ -53,8 +52,7 @@ int bgzf_on_device(thm_aligner* a, const uint8_t* d_in, uint64_t n, uint64_t* n_
   HIPCHK(a, hipMemcpyAsync(&total, a->bz_off.as<uint64_t>() + nb, 8, hipMemcpyDeviceToHost, s));
   HIPCHK(a, hipStreamSynchronize(s));
   if (total > n + nb * 31 || total < nb * 28) return fail(a, THM_ERR_INTERNAL, "BGZF members of impossible size");
-  float ms = 0;
-  if (hipEventElapsedTime(&ms, a->ev_bgzf[0], a->ev_bgzf[1]) == hipSuccess) a->timings[THM_T_BGZF] = ms;
+  (void)elapsed_ms(a->ev_bgzf[0], a->ev_bgzf[1], &a->timings[THM_T_BGZF]);
   *n_bytes = total;
   return THM_OK;
 }
@@ -80,10 +78,8 @@ int thm::batch_fetch_bgzf(thm_aligner* a, uint32_t flags, thm_bgzf_view* out, ui
   HIPCHK(a, h_off.ensure((nb + 1) * 8));
   if (n_bytes) HIPCHK(a, hipMemcpyAsync(h_data.p, a->bz_out.p, n_bytes, hipMemcpyDeviceToHost, s));
   HIPCHK(a, hipMemcpyAsync(h_off.p, a->bz_off.p, (nb + 1) * 8, hipMemcpyDeviceToHost, s));
-  if (r.any_failed) {
-    HIPCHK(a, h_stat.ensure((n + 1) * 4));
-    HIPCHK(a, hipMemcpyAsync(h_stat.p, a->r_status.p, n * 4, hipMemcpyDeviceToHost, s));
-  }
+  rc = enqueue_statuses(a, r.any_failed, h_stat);
+  if (rc != THM_OK) return rc;
   HIPCHK(a, hipStreamSynchronize(s));
   out->n_reads = n;
   out->n_records = r.n_records;
@@ -92,7 +88,7 @@ int thm::batch_fetch_bgzf(thm_aligner* a, uint32_t flags, thm_bgzf_view* out, ui
   out->n_bytes = n_bytes;
   out->data = h_data.as<uint8_t>();
   out->block_off = h_off.as<uint64_t>();
-  if (r.any_failed) bam_failed_reads(h_stat.as<int32_t>(), n, &out->n_failed_reads, &out->read_status);
+  failed_reads(a, r.any_failed, h_stat, &out->n_failed_reads, &out->read_status);
   // a read without alignments has exactly one record, the unmapped one
   if (n_aligned_reads) *n_aligned_reads = n - (r.n_records - r.n_alns);
   return THM_OK;

@@ -15,6 +15,7 @@ using namespace thm;
 // is sized by the count)
 int run_cigar_passes(thm_aligner* a, CigarParams p, uint64_t n_digests, uint64_t* n_words, unsigned* any_flags) {
   hipStream_t s = a->stream;
+  HIPCHK(a, ensure_events(a->ev_cig));
   const uint64_t ns = p.n_streams;
   *n_words = 0;
   *any_flags = 0;
@@ -50,22 +51,6 @@ int run_cigar_passes(thm_aligner* a, CigarParams p, uint64_t n_digests, uint64_t
   return THM_OK;
 }
 
-int cigar_ensure_events(thm_aligner* a) {
-  for (auto& e : a->ev_cig)
-    if (!e) HIPCHK(a, hipEventCreate(&e));
-  return THM_OK;
-}
-
-namespace {
-
-void cigar_timing(thm_aligner* a) {  // after the stream has been synchronised
-  float m1 = 0, m2 = 0;
-  if (hipEventElapsedTime(&m1, a->ev_cig[0], a->ev_cig[1]) == hipSuccess && hipEventElapsedTime(&m2, a->ev_cig[2], a->ev_cig[3]) == hipSuccess)
-    a->timings[THM_T_CIGAR] = m1 + m2;
-}
-
-}  // namespace
-
 extern "C" {
 
 int32_t thm_batch_fetch_cigars(thm_aligner* a, thm_cigar_view* out) {
@@ -74,8 +59,6 @@ int32_t thm_batch_fetch_cigars(thm_aligner* a, thm_cigar_view* out) {
   int rc = thm_batch_sync(a);
   if (rc != THM_OK) return rc;
   HIPCHK(a, hipSetDevice(a->device));
-  rc = cigar_ensure_events(a);
-  if (rc != THM_OK) return rc;
   const uint64_t n = a->n_reads;
   hipStream_t s = a->stream;
   const int k = a->c_cur ^= 1;  // the other set still backs the previous view
@@ -84,42 +67,24 @@ int32_t thm_batch_fetch_cigars(thm_aligner* a, thm_cigar_view* out) {
   HBuf& h_dig = a->ch_dig[k];
   HBuf& h_words = a->ch_words[k];
   HBuf& h_stat = a->ch_stat[k];
-  HIPCHK(a, h_off.ensure((n + 2) * 8));
-  // offsets, the op-pool size behind them and the count of out-of-contract reads, as thm_batch_fetch takes them
-  HIPCHK(a, hipMemcpyAsync(h_off.p, a->e_aln_off.p, (n + 1) * 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(a, hipMemcpyAsync(h_off.as<uint64_t>() + n + 1, a->e_ops_off.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, s));
-  unsigned long long n_contract = 0;
-  HIPCHK(a, hipMemcpyAsync(&n_contract, a->s_work_counts.as<unsigned long long>() + 6, 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(a, hipStreamSynchronize(s));
-  const uint64_t n_alns = h_off.as<uint64_t>()[n];
-  const uint64_t n_ops = h_off.as<uint64_t>()[n + 1];
-  if (n_alns > a->cand_cap || n_ops > a->cand_ops_cap) return fail(a, THM_ERR_INTERNAL, "compacted batch exceeds its pools");
+  BatchSizes z;  // offsets, the op-pool size behind them and the count of out-of-contract reads, as thm_batch_fetch takes them
+  rc = fetch_batch_sizes(a, &h_off, nullptr, nullptr, &z);
+  if (rc != THM_OK) return rc;
+  const uint64_t n_alns = z.n_alns;
   HIPCHK(a, h_alns.ensure(n_alns * sizeof(thm_aln)));
   HIPCHK(a, h_dig.ensure(n_alns * sizeof(thm_aln_digest)));
   if (n_alns) HIPCHK(a, hipMemcpyAsync(h_alns.p, a->o_alns.p, n_alns * sizeof(thm_aln), hipMemcpyDeviceToHost, s));
-  CigarParams p;
-  memset(&p, 0, sizeof p);
-  p.ops = a->o_ops.as<uint8_t>();
-  p.ops_bytes = n_ops;
-  p.n_streams = 2 * n_alns;
-  p.alns = a->o_alns.as<thm_aln>();
   uint64_t n_words = 0;
   unsigned any_flags = 0;
-  rc = run_cigar_passes(a, p, n_alns, &n_words, &any_flags);
+  rc = run_cigar_passes(a, compacted_cigar_params(a, z), n_alns, &n_words, &any_flags);
   if (rc != THM_OK) return rc;
   HIPCHK(a, h_words.ensure(n_words * 4));
   if (n_alns) HIPCHK(a, hipMemcpyAsync(h_dig.p, a->c_dig.p, n_alns * sizeof(thm_aln_digest), hipMemcpyDeviceToHost, s));
   if (n_words) HIPCHK(a, hipMemcpyAsync(h_words.p, a->c_words.p, n_words * 4, hipMemcpyDeviceToHost, s));
-  uint64_t n_beyond = a->n_over;
-  for (const auto& lc : a->len_hist)
-    if (lc.first > a->slow_max_len) n_beyond += lc.second;
-  const bool any_failed = n_beyond || n_contract;
-  if (any_failed) {
-    HIPCHK(a, h_stat.ensure((n + 1) * 4));
-    HIPCHK(a, hipMemcpyAsync(h_stat.p, a->r_status.p, n * 4, hipMemcpyDeviceToHost, s));
-  }
+  rc = enqueue_statuses(a, z.any_failed, h_stat);
+  if (rc != THM_OK) return rc;
   HIPCHK(a, hipStreamSynchronize(s));
-  if (n_alns) cigar_timing(a);
+  if (n_alns) (void)elapsed_ms(a->ev_cig, &a->timings[THM_T_CIGAR]);
   // the extend kernels write well-formed streams: anything else is a fault of this library, not of the input
   if (any_flags & THM_DIGEST_MALFORMED) return fail(a, THM_ERR_INTERNAL, "malformed op stream in the compacted pool");
   out->n_reads = n;
@@ -129,15 +94,7 @@ int32_t thm_batch_fetch_cigars(thm_aligner* a, thm_cigar_view* out) {
   out->alns = h_alns.as<thm_aln>();
   out->digests = h_dig.as<thm_aln_digest>();
   out->cigar = h_words.as<uint32_t>();
-  out->n_failed_reads = 0;
-  out->read_status = nullptr;
-  if (any_failed) {
-    const int32_t* st = h_stat.as<int32_t>();
-    uint64_t bad = 0;
-    for (uint64_t i = 0; i < n; i++) bad += st[i] != THM_OK;
-    out->n_failed_reads = bad;
-    out->read_status = bad ? st : nullptr;
-  }
+  failed_reads(a, z.any_failed, h_stat, &out->n_failed_reads, &out->read_status);
   return THM_OK;
 }
 
@@ -163,8 +120,6 @@ int32_t thm_cigar_encode_batch(thm_aligner* a, const uint8_t* ops, const uint64_
     if (off[i + 1] - off[i] >= (1ull << 32)) return fail(a, THM_ERR_UNSUPPORTED, "stream %llu has 2^32 bytes or more", (unsigned long long)i);
   }
   HIPCHK(a, hipSetDevice(a->device));
-  int rc = cigar_ensure_events(a);
-  if (rc != THM_OK) return rc;
   hipStream_t s = a->stream;
   // the pool is uploaded from off[0] on; the offsets travel relative to it
   const uint64_t o0 = off[0], pool = off[n] - o0;
@@ -182,14 +137,14 @@ int32_t thm_cigar_encode_batch(thm_aligner* a, const uint8_t* ops, const uint64_
   p.off = a->c_in_off.as<uint64_t>();
   uint64_t n_words = 0;
   unsigned any_flags = 0;
-  rc = run_cigar_passes(a, p, n, &n_words, &any_flags);  // (synchronises: `rel` has been read by then)
+  const int rc = run_cigar_passes(a, p, n, &n_words, &any_flags);  // (synchronises: `rel` has been read by then)
   if (rc != THM_OK) return rc;
   a->h_cig_dig.resize(n);
   a->h_cig_words.resize(n_words);
   HIPCHK(a, hipMemcpyAsync(a->h_cig_dig.data(), a->c_dig.p, n * sizeof(thm_aln_digest), hipMemcpyDeviceToHost, s));
   if (n_words) HIPCHK(a, hipMemcpyAsync(a->h_cig_words.data(), a->c_words.p, n_words * 4, hipMemcpyDeviceToHost, s));
   HIPCHK(a, hipStreamSynchronize(s));
-  cigar_timing(a);
+  (void)elapsed_ms(a->ev_cig, &a->timings[THM_T_CIGAR]);
   out->n_alns = n;
   out->n_cigar_words = n_words;
   out->digests = a->h_cig_dig.data();

@@ -18,8 +18,7 @@ namespace {
 // 1: the batch is in place, parsed by the device; 0: declined (nothing of the aligner's batch state is valid); < 0: error
 int parse_on_device(thm_aligner* a, const uint8_t* raw, uint64_t n, thm_fastq_upload_info* info) {
   hipStream_t s = a->stream;
-  for (auto& e : a->ev_fq)
-    if (!e) HIPCHK(a, hipEventCreate(&e));
+  HIPCHK(a, ensure_events(a->ev_fq));
   FastqParams p;
   memset(&p, 0, sizeof p);
   p.n = n;

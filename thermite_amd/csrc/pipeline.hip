@@ -558,6 +558,8 @@ int enqueue_run(thm_aligner* a) {
   const uint64_t ops_min = a->dbg_ops_cap ? a->dbg_ops_cap : std::max<uint64_t>(n * 384, a->n_bases * 3) + 65536;
   if (a->cand_cap < cand_min) a->cand_cap = cand_min;
   if (a->cand_ops_cap < ops_min) a->cand_ops_cap = ops_min;
+  a->out_alns_cap = a->cand_cap;
+  a->out_ops_cap = a->cand_ops_cap;
   HIPCHK(a, a->e_cands.ensure(a->cand_cap * sizeof(Cand)));
   HIPCHK(a, a->e_order.ensure(a->cand_cap * 2 * 4));
   HIPCHK(a, a->e_heavy.ensure((a->cand_cap / 2 + 16) * 2 * 8));
@@ -734,6 +736,62 @@ int batch_length_classes(thm_aligner* a, const uint64_t* offsets, uint64_t n_rea
   return THM_OK;
 }
 
+int fetch_batch_sizes(thm_aligner* a, HBuf* h_off, const uint64_t* d_extra, uint64_t* extra, BatchSizes* z) {
+  const uint64_t n = a->n_reads;
+  hipStream_t s = a->stream;
+  uint64_t w[2] = {0, 0}, n_contract = 0;
+  uint64_t* sizes = w;  // alignments, op bytes
+  if (h_off) {
+    HIPCHK(a, h_off->ensure((n + 2) * 8));
+    sizes = h_off->as<uint64_t>() + n;
+    HIPCHK(a, hipMemcpyAsync(h_off->p, a->e_aln_off.p, (n + 1) * 8, hipMemcpyDeviceToHost, s));
+  } else {
+    HIPCHK(a, hipMemcpyAsync(&sizes[0], a->e_aln_off.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, s));
+  }
+  HIPCHK(a, hipMemcpyAsync(&sizes[1], a->e_ops_off.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, s));
+  if (d_extra) HIPCHK(a, hipMemcpyAsync(extra, d_extra, 8, hipMemcpyDeviceToHost, s));
+  // per-read statuses travel only when a read can have failed: reads beyond the classes are known to the host,
+  // out-of-contract reads are counted by the device (the word behind the list counters)
+  HIPCHK(a, hipMemcpyAsync(&n_contract, a->s_work_counts.as<uint64_t>() + 6, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(a, hipStreamSynchronize(s));
+  z->n_alns = sizes[0];
+  z->n_ops = sizes[1];
+  if (z->n_alns > a->out_alns_cap || z->n_ops > a->out_ops_cap) return fail(a, THM_ERR_INTERNAL, "compacted batch exceeds its pools");
+  uint64_t n_beyond = a->n_over;
+  for (const auto& lc : a->len_hist)
+    if (lc.first > a->slow_max_len) n_beyond += lc.second;
+  z->any_failed = n_beyond || n_contract;
+  return THM_OK;
+}
+
+int enqueue_statuses(thm_aligner* a, bool any_failed, HBuf& h_stat) {
+  if (!any_failed) return THM_OK;
+  HIPCHK(a, h_stat.ensure((a->n_reads + 1) * 4));
+  HIPCHK(a, hipMemcpyAsync(h_stat.p, a->r_status.p, a->n_reads * 4, hipMemcpyDeviceToHost, a->stream));
+  return THM_OK;
+}
+
+void failed_reads(const thm_aligner* a, bool any_failed, const HBuf& h_stat, uint64_t* n_failed, const int32_t** status) {
+  *n_failed = 0;
+  *status = nullptr;
+  if (!any_failed) return;
+  const int32_t* st = h_stat.as<int32_t>();
+  uint64_t bad = 0;
+  for (uint64_t i = 0; i < a->n_reads; i++) bad += st[i] != THM_OK;
+  *n_failed = bad;
+  if (bad) *status = st;
+}
+
+CigarParams compacted_cigar_params(const thm_aligner* a, const BatchSizes& z) {
+  CigarParams p;
+  memset(&p, 0, sizeof p);
+  p.ops = a->o_ops.as<uint8_t>();
+  p.ops_bytes = z.n_ops;
+  p.n_streams = 2 * z.n_alns;
+  p.alns = a->o_alns.as<thm_aln>();
+  return p;
+}
+
 extern "C" {
 
 int32_t thm_batch_upload(thm_aligner* a, const uint8_t* bases, const uint64_t* offsets, uint64_t n_reads) {
@@ -776,11 +834,8 @@ int32_t thm_batch_sync(thm_aligner* a) {
     if (!st.fault_seed && (st.fault_ext & 2)) return fail(a, THM_ERR_INTERNAL, "extend kernel reported an internal inconsistency (fault word 0x%x)", st.fault_ext);
     const bool grow = st.fault_seed || (st.fault_ext & 1);
     if (!grow) {
-      float ms = 0;
-      for (int k = 0; k < 4; k++) {
-        if (hipEventElapsedTime(&ms, a->ev[k], a->ev[k + 1]) == hipSuccess) a->timings[k] = ms;
-      }
-      if (hipEventElapsedTime(&ms, a->ev[0], a->ev[4]) == hipSuccess) a->timings[THM_T_TOTAL] = ms;
+      for (int k = 0; k < 4; k++) (void)elapsed_ms(a->ev[k], a->ev[k + 1], &a->timings[k]);
+      (void)elapsed_ms(a->ev[0], a->ev[4], &a->timings[THM_T_TOTAL]);
       a->synced = true;
       return THM_OK;
     }
@@ -811,29 +866,16 @@ int32_t thm_batch_fetch(thm_aligner* a, thm_batch_view* out) {
   HBuf& h_alns = a->r_alns[k];
   HBuf& h_ops = a->r_ops[k];
   HBuf& h_stat = a->r_stat[k];
-  HIPCHK(a, h_off.ensure((n + 2) * 8));
-  // offsets, and behind them the op-pool size, in one round trip
-  HIPCHK(a, hipMemcpyAsync(h_off.p, a->e_aln_off.p, (n + 1) * 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(a, hipMemcpyAsync(h_off.as<uint64_t>() + n + 1, a->e_ops_off.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, s));
-  // per-read statuses travel only when a read can have failed: reads beyond the classes are known to the host,
-  // out-of-contract reads are counted by the device (the word behind the list counters)
-  unsigned long long n_contract = 0;
-  HIPCHK(a, hipMemcpyAsync(&n_contract, a->s_work_counts.as<unsigned long long>() + 6, 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(a, hipStreamSynchronize(s));
-  const uint64_t n_alns = h_off.as<uint64_t>()[n];
-  const uint64_t n_ops = h_off.as<uint64_t>()[n + 1];
+  BatchSizes z;  // offsets, and behind them the op-pool size, in one round trip
+  rc = fetch_batch_sizes(a, &h_off, nullptr, nullptr, &z);
+  if (rc != THM_OK) return rc;
+  const uint64_t n_alns = z.n_alns, n_ops = z.n_ops;
   HIPCHK(a, h_alns.ensure(n_alns * sizeof(thm_aln)));
   HIPCHK(a, h_ops.ensure(n_ops));
   if (n_alns) HIPCHK(a, hipMemcpyAsync(h_alns.p, a->o_alns.p, n_alns * sizeof(thm_aln), hipMemcpyDeviceToHost, s));
   if (n_ops) HIPCHK(a, hipMemcpyAsync(h_ops.p, a->o_ops.p, n_ops, hipMemcpyDeviceToHost, s));
-  uint64_t n_beyond = a->n_over;
-  for (const auto& lc : a->len_hist)
-    if (lc.first > a->slow_max_len) n_beyond += lc.second;
-  const bool any_failed = n_beyond || n_contract;
-  if (any_failed) {
-    HIPCHK(a, h_stat.ensure((n + 1) * 4));
-    HIPCHK(a, hipMemcpyAsync(h_stat.p, a->r_status.p, n * 4, hipMemcpyDeviceToHost, s));
-  }
+  rc = enqueue_statuses(a, z.any_failed, h_stat);
+  if (rc != THM_OK) return rc;
   HIPCHK(a, hipStreamSynchronize(s));
   out->n_reads = n;
   out->n_alns = n_alns;
@@ -841,15 +883,7 @@ int32_t thm_batch_fetch(thm_aligner* a, thm_batch_view* out) {
   out->read_aln_off = h_off.as<uint64_t>();
   out->alns = h_alns.as<thm_aln>();
   out->ops = h_ops.as<uint8_t>();
-  out->n_failed_reads = 0;
-  out->read_status = nullptr;
-  if (any_failed) {
-    const int32_t* st = h_stat.as<int32_t>();
-    uint64_t bad = 0;
-    for (uint64_t i = 0; i < n; i++) bad += st[i] != THM_OK;
-    out->n_failed_reads = bad;
-    out->read_status = bad ? st : nullptr;
-  }
+  failed_reads(a, z.any_failed, h_stat, &out->n_failed_reads, &out->read_status);
   return THM_OK;
 }
 
