@@ -248,7 +248,7 @@ def initial_band(opts, L):  # align_read's initial band and X-drop, src/aligner.
 
 # ------------------------------------------------------------------ micro-exon reference
 # Transcripts with hundreds of exons of 1-3 bases: an alignment along one of them crosses more introns than the
-# register-resident extend kernels keep markers for (FAST_MAX_YCLIPS = 64, launch.h), so its read is handed to the
+# register-resident extend kernels keep markers for (FAST_MAX_YCLIPS = 64, extend_plan.h), so its read is handed to the
 # any-width kernel (the retry list).  Nothing else in the suite has a transcript of more than 11 exons.
 MICRO_SLOT = 10000      # contig bases reserved per micro-exon transcript
 MICRO_TERMINAL = 60     # first and last exon: long enough for a genomic seed

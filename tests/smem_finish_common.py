@@ -157,7 +157,7 @@ def sanitise(bases):
 
 # ------------------------------------------------------------------ the host program
 def fast_class(opts, lengths, limit=400):
-    """(longest length of the fast class among `lengths`, its band, cells per lane) as pipeline.hip's classify() cuts it for
+    """(longest length of the fast class among `lengths`, its band, cells per lane) as extend_plan.h's classify() cuts it for
     reads of a few hundred bases (LDS is no limit there: lengths above `limit` are taken to be the slow class's)"""
     fast_len = fast_bw = 0
     for L in sorted(set(int(x) for x in lengths)):

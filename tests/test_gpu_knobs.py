@@ -29,7 +29,7 @@ from gpu_common import COMPACT_HEAVY_N, TEAM_HITS, TEAM_MAX_HITS, World, assert_
 pytestmark = pytest.mark.gpu
 
 CHILD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "knob_child.py")
-TEAM_MIN_HITS, TPR_MAX_HITS = 32, 32  # launch.h
+TEAM_MIN_HITS, TPR_MAX_HITS = 32, 32  # launch.h, extend_plan.h
 # seconds; the child's wall time (interpreter start, workload, index, device runs, saving) measured at first run beside it
 LIMITS = {
     "fill": 120,      # 2 s

@@ -1,6 +1,6 @@
 """-m gpu: alignments across more introns than the register-resident extend kernels keep markers for.
 
-Those kernels hold FAST_MAX_YCLIPS = 64 intron markers per alignment (launch.h).  An alignment that needs more sets
+Those kernels hold FAST_MAX_YCLIPS = 64 intron markers per alignment (extend_plan.h).  An alignment that needs more sets
 FAULT_RETRY: the read goes on the retry list, its wave's DP counters are zeroed, and the any-width kernel redoes it
 (kernels_extend.hip).  The host arms this when the index has a transcript of more than 65 exons (pipeline.hip,
 seed_hits.hip), which no other reference of the suite has.  The micro-exon reference of gpu_common has transcripts of up

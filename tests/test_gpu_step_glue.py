@@ -175,6 +175,54 @@ def test_counter_rows_stay_clean(wide):
     a.close()
 
 
+def slow_batch():
+    """2000 mixed reads of 91 bases with 24 reads of 300 - 1000 bases among them: under the CI options (band = L - 30) the
+    long ones are the slow class, which the any-width launch takes"""
+    def make():
+        t = tables()
+        rng = np.random.default_rng(31)
+        reads = mixed_reads(2000, 16)
+        for j, L in enumerate([300, 333, 450, 512, 640, 777, 1000, 1000]):
+            lb, lo, _ = synth.simulate_reads(t, 3, L, sub_rate=0.02, indel_rate=0.004, intronic_frac=0.5, stream=80 + j)
+            for i in range(3):
+                reads.insert(int(rng.integers(0, len(reads) + 1)), lb[int(lo[i]): int(lo[i + 1])])
+        bases, off = refdata.pack_reads(reads)
+        return bases, off, oracle(("counters", "slow"), bases, off)
+    return _once("slow_batch", make)
+
+
+@WIDTHS
+def test_counter_rows_across_launch_mixes(wide):
+    """One aligner, consecutive batches whose launches differ, so that the sections of the counter rows (main | team | slow |
+    problem-parallel path | finisher) come and go from run to run: the finisher without team reads, team reads, the slow
+    class, the problem-parallel path (no finisher), and three reads on the default path again.  Records and op bytes are
+    the oracle's after every run and the counters its running sums: a row written outside its section, or left unreduced,
+    is a wrong sum in the following run."""
+    by_key = {key: (bases, off, ref) for key, bases, off, ref in counter_batches()}
+    by_key["slow"] = slow_batch()
+    lens = np.diff(by_key["slow"][1].astype(np.int64))
+    assert (lens > 255).sum() == 24 and (np.diff(by_key["slow"][2].offsets.astype(np.int64))[lens > 255] > 0).sum() >= 12
+    a = world(wide).aligner(capi.CI_OPTS)
+    a.debug_set_flags(tpr=False)
+    a.reset_counters()
+    total = np.zeros(capi.N_COUNTERS, "<u8")
+    for step, (key, tpr) in enumerate([("plain", False), ("team", False), ("slow", False), ("team", True), ("three", False)]):
+        bases, off, ref = by_key[key]
+        a.debug_set_flags(tpr=tpr)
+        g = a.align_batch(bases, off)
+        assert g.n_failed == 0
+        assert_batch_equal(g, ref)
+        total += ref.counters
+        assert_counters_match(a.counters(), total, (step, key, tpr))
+        # the launches that make the step what it is did run
+        assert int(a.debug_knobs()[13]) == int(tpr)
+        fin = a.debug_smem_finish_stats()   # (of three reads none may have one of the finisher's shapes)
+        assert sum(fin) == 0 if tpr else (fin[0] + fin[2] > 0 or key == "three"), (step, fin)
+        if tpr:
+            assert a.debug_tpr_stats()[16] > 0   # DP records the rounds asked for
+    a.close()
+
+
 # ------------------------------------------------------------------ replay
 def replay_batch():
     def make():

@@ -1,5 +1,5 @@
 """CPU: the inputs of tests/test_gpu_many_exons.py, pinned with the oracle alone.  The register-resident extend kernels
-keep at most 64 intron markers per alignment (FAST_MAX_YCLIPS, launch.h) and hand a read that needs more to the
+keep at most 64 intron markers per alignment (FAST_MAX_YCLIPS, extend_plan.h) and hand a read that needs more to the
 any-width kernel; the GPU tests of that hand-over mean something only if their reads have alignments on both sides of the
 limit.  That is asserted here, where no device is involved."""
 import numpy as np

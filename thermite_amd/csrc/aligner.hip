@@ -164,12 +164,6 @@ int reset_queue(thm_aligner* a) {
   return THM_OK;
 }
 
-int grid_blocks(const thm_aligner* a, uint64_t n_items, int waves_per_block, int blocks_per_cu) {
-  uint64_t need = (n_items + waves_per_block - 1) / waves_per_block;
-  uint64_t cap = (uint64_t)a->n_cu * blocks_per_cu;
-  return (int)std::max<uint64_t>(1, std::min(need, cap));
-}
-
 extern "C" {
 
 const char* thm_version(void) { return "thermite_amd 0.1 (gfx950)"; }
@@ -203,10 +197,10 @@ int32_t thm_aligner_create(const thm_index* ix, const thm_align_opts* opts, int3
   a->opts = *opts;
   {
     const char* e = getenv("THM_TPR");  // 0 / 1: the problem-parallel path off / on (A/B measurements)
-    if (e && e[0] == '0') a->use_tpr = false;
-    if (e && e[0] == '1') a->use_tpr = true;
+    if (e && e[0] == '0') a->tpr.use_tpr = false;
+    if (e && e[0] == '1') a->tpr.use_tpr = true;
     e = getenv("THM_TPR_ROUNDS");
-    if (e && atoi(e) >= 1 && atoi(e) <= TPR_MAX_ROUNDS) a->tpr_rounds = atoi(e);
+    if (e && atoi(e) >= 1 && atoi(e) <= TPR_MAX_ROUNDS) a->tpr.tpr_rounds = atoi(e);
   }
   auto bail = [&](int code) {
     thm_aligner_free(a);
@@ -217,9 +211,9 @@ int32_t thm_aligner_create(const thm_index* ix, const thm_align_opts* opts, int3
   if (hipGetDeviceProperties(&prop, device_id) == hipSuccess) a->n_cu = prop.multiProcessorCount;
   if (a->stream.create() != hipSuccess) return bail(fail(nullptr, THM_ERR_HIP, "hipStreamCreate failed"));
   if (ensure_events(a->ev) != hipSuccess) return bail(fail(nullptr, THM_ERR_HIP, "hipEventCreate failed"));
-  if (a->stream2.create() != hipSuccess || a->stream3.create() != hipSuccess || a->stream4.create() != hipSuccess ||
-      a->ev_dpt_fork.ensure(false) != hipSuccess || a->ev_dpt_join.ensure(false) != hipSuccess ||
-      a->ev_join3.ensure(false) != hipSuccess || a->ev_fork.ensure(false) != hipSuccess ||
+  if (a->stream2.create() != hipSuccess || a->tpr.stream3.create() != hipSuccess || a->tpr.stream4.create() != hipSuccess ||
+      a->tpr.ev_dpt_fork.ensure(false) != hipSuccess || a->tpr.ev_dpt_join.ensure(false) != hipSuccess ||
+      a->tpr.ev_join3.ensure(false) != hipSuccess || a->ev_fork.ensure(false) != hipSuccess ||
       a->ev_join.ensure(false) != hipSuccess)
     return bail(fail(nullptr, THM_ERR_HIP, "second stream / events: creation failed"));
   if (a->d_counters.ensure(THM_N_COUNTERS * 8 * 3) != hipSuccess || a->d_ctl.ensure(thm_aligner::CTL_BYTES) != hipSuccess)
@@ -246,7 +240,7 @@ void thm_aligner_free(thm_aligner* a) {
   if (!a) return;
   (void)hipSetDevice(a->device);
   // work may still be in flight; after it every buffer, event and stream frees itself (aligner_internal.h)
-  for (const Stream* s : {&a->stream, &a->stream2, &a->stream3, &a->stream4})
+  for (const Stream* s : {&a->stream, &a->stream2, &a->tpr.stream3, &a->tpr.stream4})
     if (s->s) (void)hipStreamSynchronize(s->s);
   delete a;
 }
@@ -313,7 +307,7 @@ int32_t thm_swg_extend_batch(thm_aligner* a, const uint8_t* x_bases, const uint6
     y_max = std::max<uint32_t>(y_max, (uint32_t)cols);
     ops_off[i + 1] = ops_off[i] + xl + cols + 8;
   }
-  int cpl = (int)((2 * bw_max + 1 + 63) / 64);
+  int cpl = cells_per_lane(bw_max);
   SwgBatchParams p;
   p.x_cap = (x_max + 15u) & ~15u;
   p.y_cap = (y_max + 15u) & ~15u;
@@ -433,7 +427,7 @@ int32_t thm_extend_left_right_batch(thm_aligner* a, const uint8_t* x_bases, cons
     y_max = std::max<uint32_t>(y_max, (uint32_t)std::max(yr, ylft));
     ops_off[i + 1] = ops_off[i] + xr + yr + xlft + ylft + h.len + 16;
   }
-  int cpl = (int)((2 * bw_max + 1 + 63) / 64);
+  int cpl = cells_per_lane(bw_max);
   ElrBatchParams p;
   p.x_cap = (x_max + 15u) & ~15u;
   p.y_cap = (y_max + 15u) & ~15u;
@@ -547,10 +541,10 @@ int32_t thm_debug_set_pool_caps(thm_aligner* a, uint64_t smem_cap, uint64_t cand
 // [18..21] by band class, [22] reads still waiting when the rounds ran out.
 int32_t thm_debug_set_flags(thm_aligner* a, uint32_t flags) {
   if (!a) return THM_ERR_INVALID_ARG;
-  if (flags & 1u) a->use_tpr = false;
-  if (flags & 2u) a->use_tpr = true;
+  if (flags & 1u) a->tpr.use_tpr = false;
+  if (flags & 2u) a->tpr.use_tpr = true;
   const int r = (int)((flags >> 8) & 15u);
-  if (r >= 1 && r <= TPR_MAX_ROUNDS) a->tpr_rounds = r;
+  if (r >= 1 && r <= TPR_MAX_ROUNDS) a->tpr.tpr_rounds = r;
   // bit 2: the seed probes are never decided from the table entry and a neighbouring match, and store every interval
   // (kernels_seed.hip; for A/B runs), bit 4: they are again; bit 3: the seed kernels count their probes for
   // thm_debug_seed_stats, bit 5: they stop counting.  Neither bit of a pair: keep, as with bits 0 and 1.
@@ -633,16 +627,16 @@ int32_t thm_debug_set_band_clip(thm_aligner* a, uint32_t max_bw_plus_1) {
 int32_t thm_debug_tpr_stats(thm_aligner* a, uint64_t stats[32]) {
   if (!a || !stats) return THM_ERR_INVALID_ARG;
   memset(stats, 0, 256);
-  if (!a->t_ctl.p) return THM_OK;
+  if (!a->tpr.t_ctl.p) return THM_OK;
   HIPCHK(a, hipSetDevice(a->device));
   HIPCHK(a, hipStreamSynchronize(a->stream));
   unsigned long long c[40];
-  HIPCHK(a, hipMemcpy(c, a->t_ctl.p, sizeof c, hipMemcpyDeviceToHost));
+  HIPCHK(a, hipMemcpy(c, a->tpr.t_ctl.p, sizeof c, hipMemcpyDeviceToHost));
   for (int k = 0; k < 16; k++) stats[k] = c[TPRC_STATS + k];
   stats[16] = c[TPRC_REC_CUR];
   stats[17] = c[TPRC_Q_CUR];  // class 0: thread-per-problem kernel
   for (int k = 0; k < 4; k++) stats[18 + k] = c[TPRC_Q_CUR + 1 + k];
-  stats[22] = c[TPRC_N_ACT + a->tpr_rounds + 1];
+  stats[22] = c[TPRC_N_ACT + a->tpr.tpr_rounds + 1];
   return THM_OK;
 }
 // test hook: what the run-time knobs of INTEGRATION.md section 6 resolved to in this process, as the launches will use
@@ -659,8 +653,8 @@ int32_t thm_debug_knobs(thm_aligner* a, uint32_t out[16]) {
     for (int wide = 0; wide < 2; wide++) out[3 + 2 * (cpl - 1) + wide] = (uint32_t)extend_waves_per_simd(cpl, wide != 0);
   out[11] = team_div_per_cu();
   out[12] = (uint32_t)swg_blocks_per_cu();
-  out[13] = a->use_tpr ? 1u : 0u;
-  out[14] = (uint32_t)a->tpr_rounds;
+  out[13] = a->tpr.use_tpr ? 1u : 0u;
+  out[14] = (uint32_t)a->tpr.tpr_rounds;
   out[15] = (uint32_t)a->n_cu;
   return THM_OK;
 }

@@ -1,4 +1,4 @@
-// aligner_internal.h -- host-side state shared by aligner.hip and pipeline.hip.
+// aligner_internal.h -- host-side state shared by aligner.hip, pipeline.hip and the other host files.
 #ifndef THERMITE_ALIGNER_INTERNAL_H
 #define THERMITE_ALIGNER_INTERNAL_H
 #include <hip/hip_runtime.h>
@@ -154,6 +154,21 @@ inline void free_dev_copy(thm_index::DevCopy* d) {
   (void)hipSetDevice(cur);
 }
 
+// The opt-in problem-parallel path of the extend stage (pipeline_tpr.hip; kernels_tpr.hip: thread-per-read control kernel
+// + wave-per-request DP kernels, in rounds, ahead of the wave-per-read kernels, which take what is left): everything only
+// that path uses.  THM_TPR=1 or thm_debug_set_flags turn it on; THM_TPR_ROUNDS = 1..8.
+// It holds streams, so thm_aligner declares it among its streams, in front of every buffer and event of its own: the
+// aligner's buffers that stream3 and stream4 worked on are freed before this struct is destroyed, and within it the
+// streams stand first for the same reason (buffers, then events, then streams go).
+struct TprState {
+  Stream stream3;  // the wave-per-read and team kernels run beside the rounds
+  Stream stream4;  // the thread-per-problem DP kernel of a round runs beside the wave-per-problem one
+  Event ev_join3, ev_dpt_fork, ev_dpt_join;  // untimed, made by thm_aligner_create
+  DBuf t_memos, t_recs, t_dpops, t_qlist, t_act[2], t_ctl, t_bail, t_queue2, t_trace, t_ttrace, t_hdr, t_sums;
+  bool use_tpr = false;  // (until the path is the faster one on the headline workload)
+  int tpr_rounds = 8;
+};
+
 struct thm_aligner {
   const thm_index* ix = nullptr;
   thm_index::DevCopy* dix = nullptr;
@@ -163,9 +178,8 @@ struct thm_aligner {
   // after what their work may still have touched has been freed (thm_aligner_free synchronises them first).
   Stream stream;
   Stream stream2;  // the team kernel runs beside the wave-per-read kernel
-  Stream stream3;  // ... and both beside the rounds of the problem-parallel path
-  Stream stream4;  // the thread-per-problem DP kernel of a round runs beside the wave-per-problem one
-  Event ev_fork, ev_join, ev_join3, ev_dpt_fork, ev_dpt_join;  // untimed, made by thm_aligner_create
+  TprState tpr;    // (two more streams: see the struct)
+  Event ev_fork, ev_join;  // untimed, made by thm_aligner_create
   thm_align_opts opts;
   std::string err;
 
@@ -203,12 +217,6 @@ struct thm_aligner {
   // only a new allocation is zeroed by the host.  The capacity that is known clean (0 while a run's launches are being
   // enqueued: an enqueue that fails half way leaves rows nobody reduced)
   size_t wcnt_clean_cap = 0;
-  // Extension problems as the unit of wavefront work (kernels_tpr.hip: thread-per-read control kernel + wave-per-request
-  // DP kernel, in rounds), ahead of the wave-per-read kernels, which take what is left.  THM_TPR=0 or
-  // thm_debug_set_flags turn it off (every read then takes the wave-per-read path); THM_TPR_ROUNDS = 1..8.
-  DBuf t_memos, t_recs, t_dpops, t_qlist, t_act[2], t_ctl, t_bail, t_queue2, t_trace, t_ttrace, t_hdr, t_sums;
-  bool use_tpr = false;  // (until the path is the faster one on the headline workload)
-  int tpr_rounds = 8;
   uint64_t n_slow_host = 0;     // reads of the slow class in the last enqueue (host count)
   uint32_t fast_max_len = 0, slow_max_len = 0;
   uint64_t cand_cap = 0, cand_ops_cap = 0;
@@ -343,7 +351,24 @@ thm::CigarParams compacted_cigar_params(const thm_aligner* a, const BatchSizes& 
 // classes (len_hist) and n_over -- for every upload path; THM_ERR_INVALID_ARG for offsets that do not start at 0 or descend
 int batch_length_classes(thm_aligner* a, const uint64_t* offsets, uint64_t n_reads);
 int reset_queue(thm_aligner* a);
-int grid_blocks(const thm_aligner* a, uint64_t n_items, int waves_per_block, int blocks_per_cu);
+inline int grid_blocks(const thm_aligner* a, uint64_t n_items, int waves_per_block, int blocks_per_cu) {
+  return thm::grid_blocks(a->n_cu, n_items, waves_per_block, blocks_per_cu);
+}
+// ---- the extend stage's launches (pipeline.hip, pipeline_tpr.hip) over one run's thm::ExtendPlan ----
+// where a launch's waves leave their counters: row `row` of e_wcnt (the plan's row_* offsets)
+inline unsigned long long* counter_rows(const thm_aligner* a, uint64_t row) { return a->e_wcnt.as<unsigned long long>() + row * THM_N_COUNTERS; }
+// the team kernel's parameter block: `p` over the team list only, with the team's own counter rows and trace slices
+template <class C>
+thm::ExtendParamsT<C> team_params(const thm_aligner* a, const thm::ExtendPlan& plan, thm::ExtendParamsT<C> p) {
+  p.list_only = 1;
+  p.wave_counters = counter_rows(a, plan.row_team);
+  p.trace_scratch = a->e_trace.as<unsigned long long>() + plan.trace_team_off / 8;
+  return p;
+}
+// pipeline_tpr.hip: the problem-parallel path's launches (plan.tpr), in place of the main and team launches of the default
+// path.  `base` is the fast class's parameter block as the main kernel would take it.
+int enqueue_tpr_rounds(thm_aligner* a, const thm::ExtendPlan& plan, const thm::ExtendParamsT<uint32_t>& base);
+int enqueue_tpr_rounds(thm_aligner* a, const thm::ExtendPlan& plan, const thm::ExtendParamsT<uint64_t>& base);
 // pipeline.hip: what THM_SEED_FILL and THM_TEAM_DIV_PER_CU resolved to (read once per process)
 uint32_t seed_fill_mode();
 unsigned team_div_per_cu();

@@ -82,18 +82,7 @@ __device__ RefInfoT<C> idx_to_ref(const IX& ix, C idx) {
   return o;
 }
 
-// What retain / filter_overlapping / the final sort (src/aligner.rs:177-187) look at, per accepted candidate: kept in
-// LDS for the first KEYCAP candidates of a read, so that the usual multi-candidate read (a handful) is finished
-// from registers without going back to the candidate array in global memory.
-struct CandKey {
-  uint64_t ystart, yend;
-  int32_t score;
-  uint32_t name_rank;
-  uint32_t bytes;        // serialised op bytes (genome + transcript streams)
-  uint32_t strand_type;  // strand | aln_type << 8
-};
-static_assert(sizeof(CandKey) == 32, "CandKey layout");
-constexpr int KEYCAP = 16;
+// (CandKey, KEYCAP: extend_plan.h)
 
 // wave-private buffers: LDS in the register-resident kernels, a slice of global memory in the any-width
 // kernel (GS).  Lanes exchange data through them, so every exchange is followed by wsync(): a wavefront-scope
@@ -581,53 +570,7 @@ constexpr int READ_RUN = THM_READ_RUN;  // consecutive reads per queue atomic of
 constexpr int TEAM_MAX_CHUNKS = 16384;  // chunks a team keeps book of (reads beyond that stay with the sequential path)
 constexpr int TEAM_CHUNK = 4;           // hits per chunk of a team
 
-// per-wave buffer sizes, shared by the kernel's carve-up and the host's sizing functions
-struct ExtCaps {
-  uint32_t lcap, wcap, ycols, trb, opcap;
-};
-// cpl: cells per lane of the kernel's widest band (0: the any-width kernel)
-__host__ __device__ inline ExtCaps ext_caps(uint32_t max_read_len, uint32_t max_bw, int cpl = 1) {
-  ExtCaps k;
-  k.lcap = (max_read_len + 31u) & ~15u;
-  k.wcap = (2u * (max_read_len + max_bw) + max_read_len + 48u) & ~15u;
-  k.ycols = max_read_len + max_bw + 2u;
-  // LDS trace: one cell per lane (16 bytes per column).  The kernels for bands beyond 128 slots (three and four cells per
-  // lane: 150 bp reads with a band of +-64) keep room for two cells per lane: most of their extensions have 65..128 slots
-  // (min(2 bw + 1, |x| + 1)), and a trace in global memory -- a store per column, an agent-scope fence, a traceback of
-  // dependent global loads -- is what such a launch was spending its time on.  Wider extensions still use trace_g.
-  k.trb = (k.ycols + 1u) * (cpl >= 3 ? 32u : 16u);
-  k.opcap = (2u * max_read_len + 2u * max_bw + 31u) & ~15u;
-  return k;
-}
-// any-width kernel: layout of one wave's slice of global memory
-struct SlowLayout {
-  uint64_t rd, win, wing, pa, pb, pc, mk_k, ycl, dp, trace, total;
-  uint32_t dp_stride;
-};
-__host__ __device__ inline SlowLayout slow_layout(uint32_t max_read_len, uint32_t max_bw, uint32_t mk_cap) {
-  const ExtCaps k = ext_caps(max_read_len, max_bw);
-  SlowLayout s;
-  uint64_t o = 0;
-  auto take = [&](uint64_t bytes) {
-    const uint64_t at = o;
-    o += (bytes + 63u) & ~63ull;
-    return at;
-  };
-  s.rd = take(k.lcap);
-  s.win = take(k.wcap);
-  s.wing = take(k.wcap);
-  s.pa = take(k.opcap);
-  s.pb = take(k.opcap);
-  s.pc = take(k.opcap);
-  s.mk_k = take((uint64_t)mk_cap * 4);
-  s.ycl = take((uint64_t)mk_cap * 4);
-  const uint32_t tiles = (2u * max_bw + 1u + 63u) / 64u;
-  s.dp_stride = tiles * 64u + 64u;
-  s.dp = take((uint64_t)s.dp_stride * 4u * 4u);
-  s.trace = take((uint64_t)(k.ycols + 1u) * tiles * 16u);
-  s.total = o;
-  return s;
-}
+// (ExtCaps / ext_caps, SlowLayout / slow_layout: extend_plan.h)
 
 #ifndef THM_KARG_QUAL
 #define THM_KARG_QUAL volatile
@@ -657,7 +600,7 @@ __global__ __launch_bounds__(TEAM > 0 ? 64 * TEAM : 256, TEAM > 0 ? 1 : MINW) vo
   __shared__ int t_state[4];          // the state in force at chunk t_ctl[1]: band, X-drop, best score
   __shared__ unsigned t_ctl[4];       // [0] list slot of the read, [1] first chunk of the round, [2] accepted so far, [3] per-read fault bits
   __shared__ unsigned char t_nacc[TM ? TEAM_MAX_CHUNKS : 1];  // accepted candidates per finished chunk (<= TEAM_CHUNK)
-  static_assert(!TM || sizeof(t_res) + sizeof(t_state) + sizeof(t_ctl) + sizeof(t_nacc) <= TEAM_STATIC_LDS, "launch.h: TEAM_STATIC_LDS");
+  static_assert(!TM || sizeof(t_res) + sizeof(t_state) + sizeof(t_ctl) + sizeof(t_nacc) <= TEAM_STATIC_LDS, "extend_plan.h: TEAM_STATIC_LDS");
   typedef WctxT<GS> Wctx;
   // The parameter block (about 80 dwords) is read from the kernel-argument segment where it is
   // needed (scalar loads, THM_KARG_QUAL = volatile keeps them at their use sites) instead of being
@@ -2372,22 +2315,6 @@ static hipError_t launch_seed_hits_t(const SeedHitParamsT<C>& p, int cpl, int n_
 }
 hipError_t launch_seed_hits(const SeedHitParamsT<uint32_t>& p, int cpl, int n_blocks, hipStream_t s) { return launch_seed_hits_t(p, cpl, n_blocks, s); }
 hipError_t launch_seed_hits(const SeedHitParamsT<uint64_t>& p, int cpl, int n_blocks, hipStream_t s) { return launch_seed_hits_t(p, cpl, n_blocks, s); }
-
-size_t extend_lds_bytes(uint32_t max_read_len, uint32_t max_bw, int cpl) {
-  const dev::ExtCaps k = dev::ext_caps(max_read_len, max_bw, cpl);
-  const uint32_t per_wave = k.lcap + 2u * k.wcap + k.trb + 3u * k.opcap + 8u * FAST_MAX_YCLIPS + (uint32_t)(dev::KEYCAP * sizeof(dev::CandKey));
-  return 4 * (size_t)per_wave;
-}
-
-// global trace scratch of one wave (extensions over more than 64 band slots), in bytes
-size_t extend_trace_scratch_bytes(uint32_t max_read_len, uint32_t max_bw, int cpl) {
-  return cpl > 1 ? (size_t)(max_read_len + max_bw + 3u) * (size_t)cpl * 16u : 0;
-}
-
-// everything one wave of the any-width kernel keeps in global memory, in bytes
-size_t extend_slow_scratch_bytes(uint32_t max_read_len, uint32_t max_bw, uint32_t mk_cap) {
-  return (size_t)dev::slow_layout(max_read_len, max_bw, mk_cap).total;
-}
 
 constexpr int EXT_MINW_CPL34 = 4;  // default register budget of the three- and four-cell kernels (waves per SIMD)
 // waves per SIMD the wave-per-read kernel chosen for (cpl, coordinate width) is compiled for = workgroups of 4 waves

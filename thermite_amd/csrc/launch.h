@@ -8,6 +8,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "extend_plan.h"
 #include "thermite_internal.h"
 
 namespace thm {
@@ -268,11 +269,8 @@ constexpr unsigned HEAVY_HITS = 8;  // reads with at least this many seed hits a
 constexpr unsigned TEAM_HITS = 256;
 constexpr unsigned TEAM_MIN_HITS = 32;
 constexpr unsigned TEAM_DIV_PER_CU = 22;
-constexpr int TEAM_WAVES = 16;
 constexpr unsigned TEAM_MAX_HITS = 60000;   // beyond that the team's per-chunk book (16384 chunks of 4 hits, less one per SMEM) does not fit: sequential path
-// intron markers one alignment can carry in the register-resident kernel (LDS); an alignment across more
-// introns sends its read to the any-width kernel, whose marker list is sized by the longest transcript
-constexpr int FAST_MAX_YCLIPS = 64;
+// (TEAM_WAVES, FAST_MAX_YCLIPS and the sizing functions extend_lds_bytes, extend_trace_scratch_bytes, extend_slow_scratch_bytes: extend_plan.h)
 
 template <class C>
 struct ExtendParamsT {
@@ -320,17 +318,9 @@ struct ExtendParamsT {
   uint64_t slow_scratch_per_wave;
   unsigned long long* prof;  // 16 slots of shader clocks per section (THM_PROF builds), else unused
 };
-size_t extend_lds_bytes(uint32_t max_read_len, uint32_t max_bw, int cpl);
 int extend_waves_per_simd(int cpl, bool wide);
 int compact_k();  // compact_kernel<K> that launch_compact runs (THM_COMPACT_K)
 int hit_gl();     // lanes per hit of the hit-summary kernel that launch_hit_summaries runs (THM_HIT_GL)
-size_t extend_trace_scratch_bytes(uint32_t max_read_len, uint32_t max_bw, int cpl);
-size_t extend_slow_scratch_bytes(uint32_t max_read_len, uint32_t max_bw, uint32_t mk_cap);  // per wave
-constexpr size_t EXTEND_LDS_LIMIT = 160 * 1024;  // gfx950: one workgroup may take the whole LDS of its CU
-// does a team workgroup (TEAM_WAVES waves' buffers + the team's own static LDS: per-chunk book, round results) fit?
-// lds4 = extend_lds_bytes(...) of an ordinary 4-wave workgroup
-constexpr size_t TEAM_STATIC_LDS = 16384 + TEAM_WAVES * 32 + 64;  // t_nacc[TEAM_MAX_CHUNKS], t_res, t_state, t_ctl (kernels_extend.hip)
-inline bool team_fits_lds(size_t lds4) { return lds4 / 4 * TEAM_WAVES + TEAM_STATIC_LDS + 256 <= EXTEND_LDS_LIMIT; }
 // team = true: the workgroup-per-read variant for reads with very many hits (cpl 1 or 2 only; TEAM_WAVES waves per workgroup)
 hipError_t launch_extend(const ExtendParamsT<uint32_t>& p, int cpl, int n_blocks, hipStream_t s, bool team = false);
 hipError_t launch_extend(const ExtendParamsT<uint64_t>& p, int cpl, int n_blocks, hipStream_t s, bool team = false);
@@ -357,7 +347,6 @@ struct FinishParamsT {
 };
 hipError_t launch_smem_finish(const FinishParamsT<uint32_t>& p, int n_blocks, hipStream_t s);
 hipError_t launch_smem_finish(const FinishParamsT<uint64_t>& p, int n_blocks, hipStream_t s);
-constexpr int FINISH_BLOCKS_PER_CU = 8;  // the finisher strides over the batch with at most this many workgroups per CU
 
 // ---- hit summaries (kernels_hit.hip): the part of align_seed_hit that does not depend on the state align_read carries
 // from hit to hit (band, X-drop, best score), computed once per hit by a group of eight lanes ----
@@ -459,12 +448,8 @@ struct DpRec {
   uint32_t pad2_;
 };
 static_assert(sizeof(DpRec) == 64, "DpRec layout");
-constexpr int DPT_SLOTS = 16;      // band slots of the thread-per-problem DP kernel (registers of one thread)
 constexpr int DP_NQ = 5;           // request queues: class 0 (narrow) and band classes 1..4
 constexpr int TPR_MAX_ROUNDS = 8;  // rounds of requests one read may take (then: the wave-per-read kernel)
-// Reads with this many seed hits and more stay with the workgroup-per-read / wave-per-read kernels: the control kernel
-// replays a read's hits in one thread, and a thread with thousands of hits would be the tail of its launch.
-constexpr unsigned TPR_MAX_HITS = 32;
 // The records of a read, by round: round k asked for the extension problems of the hits from first_hit[k] on (one
 // hit, or all the remaining ones), in the order the replay meets them, under the band and X-drop in force there:
 // records base[k] .. base[k] + cnt[k].
@@ -527,7 +512,6 @@ hipError_t launch_tpr_order(const ReadRecT<uint32_t>* recs, uint64_t n, uint32_t
                             unsigned long long* n_out, const int* fault_seed, hipStream_t s);
 hipError_t launch_tpr_order(const ReadRecT<uint64_t>* recs, uint64_t n, uint32_t max_len, uint32_t max_hits, unsigned long long* bins, uint32_t* out,
                             unsigned long long* n_out, const int* fault_seed, hipStream_t s);
-constexpr int TPR_CTL_BLOCKS_PER_CU = 4, TPR_DP_BLOCKS_PER_CU = 8;
 // layout of the small control block of a run (u64 words; zeroed before the run)
 enum { TPRC_REC_CUR = 0, TPRC_Q_CUR = 2 /* [DP_NQ] */, TPRC_Q_DONE = 7 /* [DP_NQ] */, TPRC_N_ACT = 12 /* [TPR_MAX_ROUNDS + 2] */, TPRC_STATS = 24 /* [16] */, TPRC_BAIL_CNT = 23,
        TPRC_BINS = 40 /* [128]: reads per hit count, cursors (tpr_order_kernel) */,

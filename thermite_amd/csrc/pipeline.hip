@@ -46,26 +46,6 @@ unsigned team_div_per_cu() {
 
 namespace {
 
-// bw0(L) of reference src/aligner.rs:130-138; non-decreasing in L
-int band_for_len(const thm_align_opts& o, uint32_t L) {
-  volatile float prod = o.min_aln_score_percent * (float)L;
-  float pv = prod;
-  int pct = (pv != pv) ? 0 : (pv >= 2147483648.0f ? 2147483647 : (pv <= -2147483648.0f ? (-2147483647 - 1) : (int)pv));
-  int ms = std::max(pct, o.min_aln_score);
-  if (ms < 0) return 0;
-  return std::max((int)L - ms, 0);
-}
-
-int blocks_for(const thm_aligner* a, uint64_t n, size_t lds_per_block) {
-  int per_cu = 8;
-  if (lds_per_block > 0) per_cu = (int)std::min<size_t>(8, (160 * 1024) / lds_per_block);
-  if (per_cu < 1) per_cu = 1;
-  return grid_blocks(a, n, 4, per_cu);
-}
-
-// device memory the any-width kernel may take for its wave-private buffers (traces grow with length x band)
-constexpr uint64_t SLOW_SCRATCH_BUDGET = 24ull << 30;
-
 template <class C>
 const DeviceIndexT<C>& dev_view(const thm_aligner* a);
 template <>
@@ -135,7 +115,7 @@ int enqueue_seed_t(thm_aligner* a, uint32_t min_seed_len, bool finish_scan) {
   HIPCHK(a, a->s_work_reads.ensure((n + 1) * 8));
   HIPCHK(a, a->s_work_long.ensure((n_long + 1) * 8));
   HIPCHK(a, a->s_work_cells.ensure((std::max(cells, n) + 1) * 8));
-  const int n_blocks = blocks_for(a, n, std::min(seed_select_lds_bytes(std::max(max_short, 1u)), SEED_SELECT_LDS_LIMIT));
+  const int n_blocks = grid_blocks(a, n, 4, lds_blocks_per_cu(std::min(seed_select_lds_bytes(std::max(max_short, 1u)), SEED_SELECT_LDS_LIMIT), 8));
   SeedParamsT<C> sp;
   sp.ix = dev_view<C>(a);
   sp.reads.bases = a->r_san.as<uint8_t>() + 16;
@@ -219,43 +199,21 @@ int enqueue_plan_pack_t(thm_aligner* a, const PlanParams& pp) {
   return THM_OK;
 }
 
-// Length classes of the extend stage for the current options.  Band and buffer sizes grow with the read
-// length, so each class is a range of lengths:
-//   fast   L <= fast_max: band within +-127 and the wave-private buffers within LDS -> register-resident kernel;
-//   slow   fast_max < L <= slow_max: any-width kernel (band in tiles, buffers in global memory);
-//   beyond slow_max: the DP trace alone would exceed the memory budget -> per-read THM_ERR_UNSUPPORTED.
-struct ExtClasses {
-  uint32_t fast_max = 0, fast_len = 0, fast_bw = 0;  // threshold; longest fast read present and its band
-  uint32_t slow_max = 0, slow_len = 0, slow_bw = 0;
-  uint64_t n_slow = 0;
-};
-ExtClasses classify(const thm_aligner* a, uint32_t mk_cap_slow) {
-  ExtClasses c;
-  bool fast_open = true;
-  for (const auto& lc : a->len_hist) {
-    const uint32_t L = lc.first;
-    const uint32_t bw = (uint32_t)band_for_len(a->opts, L);
-    const int cpl = (int)((2 * bw + 1 + 63) / 64);
-    if (fast_open && cpl <= 4 && extend_lds_bytes(L, bw, cpl) <= EXTEND_LDS_LIMIT) {
-      c.fast_len = L;
-      c.fast_bw = bw;
-      continue;
-    }
-    fast_open = false;
-    if (extend_slow_scratch_bytes(L, bw, mk_cap_slow) > SLOW_SCRATCH_BUDGET) break;
-    c.slow_len = L;
-    c.slow_bw = bw;
-    c.n_slow += lc.second;
-  }
-  c.fast_max = c.fast_len;
-  c.slow_max = std::max(c.slow_len, c.fast_len);
-  return c;
-}
-
+// The extend stage of one run over its plan (extend_plan.h): the finisher, then the team kernel beside the wave-per-read
+// kernel (or the problem-parallel path in their place), the any-width launch, and the reduction of the waves' counters.
 template <class C>
-int enqueue_extend_t(thm_aligner* a, const ExtClasses& cls, uint32_t mk_cap_slow, bool retry_possible) {
+int enqueue_extend_t(thm_aligner* a, const ExtendPlan& plan) {
   const uint64_t n = a->n_reads;
   hipStream_t s = a->stream;
+  const int cpl = plan.cpl;
+  a->fin_blocks = (uint32_t)plan.fin_blocks;
+  HIPCHK(a, a->e_trace.ensure(plan.trace_bytes + 64));
+  // The counter rows are zero from one run to the next (launch_counters_reduce zeroes what it read, and no launch writes
+  // past its run's n_rows): only a new allocation is zeroed here -- or the rows of an enqueue that failed half way.
+  HIPCHK(a, a->e_wcnt.ensure(plan.n_rows * THM_N_COUNTERS * 8 + 64));
+  if (a->wcnt_clean_cap != a->e_wcnt.cap) HIPCHK(a, hipMemsetAsync(a->e_wcnt.p, 0, a->e_wcnt.cap, s));
+  a->wcnt_clean_cap = 0;
+  // ---- fast class: the main kernel's parameter block; the other launches take copies of it ----
   ExtendParamsT<C> ep;
   ep.ix = dev_view<C>(a);
   ep.reads.bases = a->r_san.as<uint8_t>() + 16;
@@ -283,77 +241,27 @@ int enqueue_extend_t(thm_aligner* a, const ExtClasses& cls, uint32_t mk_cap_slow
   ep.retry_count = a->s_work_counts.as<unsigned long long>() + 5;
   ep.n_contract = a->s_work_counts.as<unsigned long long>() + 6;
   ep.counters = a->d_counters.as<unsigned long long>();
+  ep.wave_counters = counter_rows(a, plan.row_main);
   ep.queue = a->d_queue_ext.as<unsigned int>();  // (not the seed stage's words: both sets were zeroed when the run began)
   ep.fault = a->d_fault.as<int>() + 1;
   ep.fault_seed = a->d_fault.as<int>();
   ep.prof = a->d_counters.as<unsigned long long>() + 2 * THM_N_COUNTERS;
-  ep.slow_scratch = nullptr;
-  ep.slow_scratch_per_wave = 0;
-  ep.trace_scratch = nullptr;
-  // ---- fast class ----
-  ep.max_read_len = cls.fast_len;
-  ep.max_bw = cls.fast_bw;
+  ep.max_read_len = plan.fast_len;
+  ep.max_bw = plan.fast_bw;
   if (a->dbg_band_clip) ep.max_bw = std::min<uint32_t>(ep.max_bw, a->dbg_band_clip - 1);  // test hook: reads beyond get THM_ERR_INTERNAL
   ep.mk_cap = FAST_MAX_YCLIPS;
   ep.list_only = 0;
-  const int cpl = std::max(1, (int)((2 * cls.fast_bw + 1 + 63) / 64));
-  const size_t lds = extend_lds_bytes(cls.fast_len, cls.fast_bw, cpl);
-  // workgroups that fit the machine at once: LDS and the kernel's register budget
-  const int ext_blocks = std::min(blocks_for(a, n, lds), a->n_cu * extend_waves_per_simd(cpl, sizeof(C) == 8));
-  const bool team_ok = cpl <= 2 && team_fits_lds(lds);
-  // global trace scratch (extensions over more than 64 band slots): the team kernel runs BESIDE the main kernel, so
-  // its waves have their own slices behind the main kernel's
-  const size_t trace_per_wave = extend_trace_scratch_bytes(cls.fast_len, cls.fast_bw, cpl);
-  const size_t main_trace_waves = (size_t)ext_blocks * 4, team_trace_waves = team_ok ? (size_t)a->n_cu * TEAM_WAVES : 0;
-  HIPCHK(a, a->e_trace.ensure((main_trace_waves + team_trace_waves) * trace_per_wave + 64));
-  ep.trace_scratch = a->e_trace.as<unsigned long long>();
-  // reads with very many hits: a workgroup per read (speculative chunks of hits, kernels_extend.hip TEAM) BESIDE the
-  // wave-per-read kernel: such reads are the long jobs of a batch, a launch behind the main kernel would put them on
-  // the critical path.  A team workgroup needs a whole CU's registers, so it must be placed before the persistent
-  // waves of the main kernel fill the machine: the team kernel goes first on this stream, the main kernel on the second
-  // stream behind an event (the event's latency is the team's head start; the other way round the team kernel started
-  // 10 us late and waited for the main kernel to drain -- rocprofv3 kernel trace, tools/overlap_trace.py).
-  // rows for the waves' counters: [main | team | slow] (launch.h, ExtendParamsT::wave_counters)
-  uint64_t slow_waves = 0, slow_per_wave = 0;
-  if (cls.n_slow || retry_possible) {
-    const uint32_t sl_len = std::max(cls.slow_len, cls.fast_len), sl_bw = std::max(cls.slow_bw, cls.fast_bw);
-    slow_per_wave = (extend_slow_scratch_bytes(sl_len, sl_bw, mk_cap_slow) + 255) & ~255ull;
-    slow_waves = std::max<uint64_t>(1, std::min<uint64_t>(SLOW_SCRATCH_BUDGET / std::max<uint64_t>(slow_per_wave, 1), (uint64_t)a->n_cu * 8));
-    if (!retry_possible) slow_waves = std::min(slow_waves, std::max<uint64_t>(cls.n_slow, 1));
-    slow_waves = (slow_waves + 3) / 4 * 4;
-  }
-  const uint64_t main_rows = (uint64_t)ext_blocks * 4, team_rows = team_ok ? (uint64_t)a->n_cu * TEAM_WAVES : 0;
-  // ---- extension problems as the unit of wavefront work (kernels_tpr.hip): rounds of [control kernel, thread per
-  // read | DP kernel, wave per request]; what it cannot take goes on the wave-per-read kernel's list ----
-  const bool tpr = a->use_tpr && n > 0 && cpl <= 4;
-  const int ctl_blocks = tpr ? (int)std::min<uint64_t>((n + 255) / 256, (uint64_t)a->n_cu * TPR_CTL_BLOCKS_PER_CU) : 0;
-  // DP workgroups that fit the machine at once (LDS: x, y, trace and op buffer of four waves)
-  const uint32_t dp_x_cap = (cls.fast_len + 64u + 15u) & ~15u, dp_y_cap = (cls.fast_len + cls.fast_bw + 2u + 64u + 15u) & ~15u;
-  const int dp_per_cu = (int)std::max<size_t>(1, std::min<size_t>(TPR_DP_BLOCKS_PER_CU, EXTEND_LDS_LIMIT / std::max<size_t>(1, extend_dp_lds_bytes(dp_x_cap, dp_y_cap))));
-  const int dp_blocks = tpr ? a->n_cu * dp_per_cu : 0;
-  // thread-per-problem kernel (class 0: at most DPT_SLOTS band slots hold cells): columns of its LDS trace -- such a problem
-  // has a band of at most +-7 (|y| <= |x| + 8) or an x of at most 15 symbols (|y| <= 16 + bw); workgroups that fit a CU
-  // (at most 128 columns, 64 KiB of LDS per workgroup: longer ones are the wave-per-problem kernel's)
-  const uint32_t dpt_tcols = std::min<uint32_t>(std::min<uint32_t>(dp_y_cap, 128u), std::max<uint32_t>(cls.fast_len + DPT_SLOTS / 2 + 2, DPT_SLOTS + cls.fast_bw + 2));
-  const int dpt_per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, EXTEND_LDS_LIMIT / std::max<size_t>(1, extend_dpt_lds_bytes(dpt_tcols))));
-  const int dpt_blocks = tpr ? a->n_cu * dpt_per_cu : 0;
-  // rows: [main | team | slow | control kernel's workgroups | the wave-per-read launch for what the control kernel leaves]
-  const int bail_blocks = tpr ? std::min(ext_blocks, a->n_cu) : 0;
-  const uint64_t tpr_rows = (uint64_t)ctl_blocks + (uint64_t)bail_blocks * 4;
-  // the finisher (kernels_finish.hip) in front of the wave-per-read kernel: a row per workgroup behind the others
-  const int fin_blocks = (!tpr && a->fin_run_classes && n > 0) ? (int)std::min<uint64_t>((n + 255) / 256, (uint64_t)a->n_cu * FINISH_BLOCKS_PER_CU) : 0;
-  a->fin_blocks = (uint32_t)fin_blocks;
-  const uint64_t n_rows = main_rows + team_rows + slow_waves + tpr_rows + (uint64_t)fin_blocks;
-  // The rows are zero from one run to the next (launch_counters_reduce zeroes what it read, and no launch writes past
-  // its run's n_rows): only a new allocation is zeroed here -- or the rows of an enqueue that failed half way.
-  HIPCHK(a, a->e_wcnt.ensure(n_rows * THM_N_COUNTERS * 8 + 64));
-  if (a->wcnt_clean_cap != a->e_wcnt.cap) HIPCHK(a, hipMemsetAsync(a->e_wcnt.p, 0, a->e_wcnt.cap, s));
-  a->wcnt_clean_cap = 0;
-  ep.wave_counters = a->e_wcnt.as<unsigned long long>();
   ep.skip_scan = 0;
-  FinishParamsT<C> fp;
-  if (fin_blocks) {
-    HIPCHK(a, a->e_finstats.ensure((size_t)fin_blocks * 4 * 8));
+  ep.trace_scratch = a->e_trace.as<unsigned long long>() + plan.trace_main_off / 8;
+  ep.slow_scratch = nullptr;
+  ep.slow_scratch_per_wave = 0;
+  // ---- the finisher (kernels_finish.hip), in front of the wave-per-read kernel ----
+  // It runs before the fork, with the machine to itself.  (On the main kernel's stream, beside the team kernel -- whose reads
+  // are never the finisher's -- it was measured at 120 - 430 us instead: a team workgroup takes a whole CU's registers, and
+  // the main kernel waited for the finisher all that time)
+  if (plan.fin_blocks) {
+    HIPCHK(a, a->e_finstats.ensure((size_t)plan.fin_blocks * 4 * 8));
+    FinishParamsT<C> fp;
     fp.ix = ep.ix;
     fp.reads = ep.reads;
     fp.opts = ep.opts;
@@ -364,7 +272,7 @@ int enqueue_extend_t(thm_aligner* a, const ExtClasses& cls, uint32_t mk_cap_slow
     fp.order = ep.order;
     fp.read_n_alns = ep.read_n_alns;
     fp.read_op_bytes = ep.read_op_bytes;
-    fp.rows = ep.wave_counters + (main_rows + team_rows + slow_waves + tpr_rows) * THM_N_COUNTERS;
+    fp.rows = counter_rows(a, plan.row_fin);
     fp.stats = a->e_finstats.as<unsigned long long>();
     fp.fault_seed = ep.fault_seed;
     fp.max_read_len = ep.max_read_len;
@@ -372,174 +280,44 @@ int enqueue_extend_t(thm_aligner* a, const ExtClasses& cls, uint32_t mk_cap_slow
     fp.cpl = (uint32_t)cpl;
     fp.classes = a->fin_run_classes;
     fp.run_half = a->ops_run_half;
+    HIPCHK(a, launch_smem_finish(fp, plan.fin_blocks, s));
   }
-  if (tpr) {
-    const uint64_t rec_cap = std::min<uint64_t>(4 * n + 65536, 64ull << 20);
-    HIPCHK(a, a->t_memos.ensure(n * sizeof(ReadMemo) + 64));
-    HIPCHK(a, a->t_recs.ensure(rec_cap * sizeof(DpRec) + 64));
-    HIPCHK(a, a->t_qlist.ensure((size_t)DP_NQ * rec_cap * 4 + 64));
-    HIPCHK(a, a->t_act[0].ensure(n * 4 + 64));
-    HIPCHK(a, a->t_act[1].ensure(n * 4 + 64));
-    HIPCHK(a, a->t_bail.ensure((n + 1) * 8));
-    HIPCHK(a, a->t_queue2.ensure(thm::QUEUE_BYTES));
-    HIPCHK(a, hipMemsetAsync(a->t_queue2.p, 0, thm::QUEUE_BYTES, s));
-    HIPCHK(a, a->t_ctl.ensure(TPRC_BYTES));
-    HIPCHK(a, hipMemsetAsync(a->t_ctl.p, 0, TPRC_BYTES, s));
-    unsigned long long* ctl = a->t_ctl.as<unsigned long long>();
-    TprParamsT<C> tq;
-    tq.recs_rw = a->e_recs.as<ReadRecT<C>>();
-    tq.memos = a->t_memos.as<ReadMemo>();
-    tq.recs = a->t_recs.as<DpRec>();
-    tq.rec_cap = rec_cap;
-    tq.rec_cursor = ctl + TPRC_REC_CUR;
-    tq.q_list = a->t_qlist.as<uint32_t>();
-    tq.q_stride = rec_cap;
-    tq.q_cur = ctl + TPRC_Q_CUR;
-    tq.bail = a->t_bail.as<unsigned long long>();
-    tq.bail_count = ctl + TPRC_BAIL_CNT;
-    tq.team = nullptr;  // (the team kernel is running already; a read of this path has fewer hits than it takes anyway)
-    tq.team_count = nullptr;
-    tq.max_hits = TPR_MAX_HITS;
-    tq.dpt_cols = dpt_tcols;
-    tq.stats = ctl + TPRC_STATS;
-    ExtendParamsT<C> zp = ep;
-    zp.wave_counters = ep.wave_counters + (main_rows + team_rows + slow_waves) * THM_N_COUNTERS;
-    DpParams dq;
-    dq.recs = tq.recs;
-    dq.q_list = tq.q_list;
-    dq.q_stride = tq.q_stride;
-    dq.q_cur = ctl + TPRC_Q_CUR;
-    dq.q_done = ctl + TPRC_Q_DONE;
-    dq.fault = ep.fault;
-    dq.x_cap = dp_x_cap;
-    dq.y_cap = dp_y_cap;
-    {
-      const size_t tb = extend_dp_trace_bytes(dp_y_cap, cpl);
-      HIPCHK(a, a->t_trace.ensure((size_t)dp_blocks * 4 * tb + 64));
-      dq.trace_scratch = a->t_trace.as<unsigned long long>();
-      dq.trace_per_wave = tb / 8;
-      dq.tcols = dpt_tcols;
-    }
-    // hit summaries: everything about a hit that does not depend on the state align_read carries, all hits side by side
-    {
-      const uint64_t slot_cap = a->cand_cap;
-      HIPCHK(a, a->t_hdr.ensure(slot_cap * sizeof(HitHdr) + 64));
-      HIPCHK(a, a->t_sums.ensure(slot_cap * sizeof(HitSum) + 64));
-      HIPCHK(a, hipMemsetAsync(a->t_hdr.p, 0xFF, slot_cap * sizeof(HitHdr), s));
-      HitParamsT<C> hq;
-      hq.ix = ep.ix;
-      hq.reads = ep.reads;
-      hq.opts = ep.opts;
-      hq.smems = ep.smems;
-      hq.read_recs = ep.read_recs;
-      hq.max_read_len = cls.fast_len;
-      hq.max_hits = TPR_MAX_HITS;
-      hq.hdr = a->t_hdr.as<HitHdr>();
-      hq.sums = a->t_sums.as<HitSum>();
-      hq.total_hits = a->s_cand_off.as<uint64_t>() + n;
-      hq.slot_cap = slot_cap;
-      hq.fault_seed = a->d_fault.as<int>();
-      HIPCHK(a, launch_hit_expand(hq, s));
-      HIPCHK(a, launch_hit_summaries(hq, a->n_cu * 12, s));
-      tq.sums = a->t_sums.as<HitSum>();
-    }
-    // The reads with HEAVY_HITS hits and more (the lists of plan_kernel) are the wave-per-read / workgroup-per-read
-    // kernels': they run BESIDE the rounds below, on their own streams.
-    {
-      ExtendParamsT<C> hp = ep;
-      hp.skip_scan = 1;
-      hp.team_limit = 16u * (uint32_t)a->n_cu;  // no scan of the batch to share the machine with: the team kernel keeps every read it can take
-      HIPCHK(a, hipEventRecord(a->ev_fork, s));
-      HIPCHK(a, hipStreamWaitEvent(a->stream2, a->ev_fork, 0));
-      HIPCHK(a, hipStreamWaitEvent(a->stream3, a->ev_fork, 0));
-      if (team_ok) {
-        ExtendParamsT<C> tp = hp;
-        tp.list_only = 1;
-        tp.wave_counters = ep.wave_counters + main_rows * THM_N_COUNTERS;
-        tp.trace_scratch = ep.trace_scratch + main_trace_waves * trace_per_wave / 8;
-        HIPCHK(a, launch_extend(tp, cpl, a->n_cu, a->stream2, true));
-      }
-      HIPCHK(a, launch_extend(hp, cpl, std::min(ext_blocks, a->n_cu), a->stream3));  // (a few thousand reads: one workgroup per CU leaves the machine to the rounds)
-      HIPCHK(a, hipEventRecord(a->ev_join, a->stream2));
-      HIPCHK(a, hipEventRecord(a->ev_join3, a->stream3));
-    }
-    // round 0's list: the reads of this path by descending hit count
-    HIPCHK(a, launch_tpr_order(a->e_recs.as<ReadRecT<C>>(), n, cls.fast_len, TPR_MAX_HITS, ctl + TPRC_BINS, a->t_act[0].as<uint32_t>(), ctl + TPRC_N_ACT,
-                               a->d_fault.as<int>(), s));
-    const int n_rounds = a->tpr_rounds;  // rounds of requests a read may take (then: the wave-per-read kernel)
-    for (int r = 0; r <= n_rounds; r++) {
-      tq.round = (uint32_t)r;
-      tq.act_in = a->t_act[r & 1].as<uint32_t>();
-      tq.n_act_in = ctl + TPRC_N_ACT + r;
-      tq.act_out = a->t_act[(r + 1) & 1].as<uint32_t>();
-      tq.n_act_out = ctl + TPRC_N_ACT + r + 1;
-      tq.last_round = r == n_rounds ? 1u : 0u;
-      HIPCHK(a, launch_extend_ctl(zp, tq, ctl_blocks, s));
-      if (r == n_rounds) break;
-      dq.work = (unsigned int*)((uint8_t*)a->t_ctl.p + TPRC_WORK_BYTES + (size_t)r * 4 * 64);
-      // the two DP kernels of a round side by side: the thread-per-problem one has a few hundred wavefronts of long
-      // serial work (one column after the other, per thread), the wave-per-problem one fills the machine
-      HIPCHK(a, hipEventRecord(a->ev_dpt_fork, s));
-      HIPCHK(a, hipStreamWaitEvent(a->stream4, a->ev_dpt_fork, 0));
-      HIPCHK(a, launch_extend_dpt(dq, dpt_blocks, a->stream4));
-      HIPCHK(a, hipEventRecord(a->ev_dpt_join, a->stream4));
-      HIPCHK(a, launch_extend_dp(dq, cpl, dp_blocks, s));
-      HIPCHK(a, hipStreamWaitEvent(s, a->ev_dpt_join, 0));
-      HIPCHK(a, hipMemcpyAsync(ctl + TPRC_Q_DONE, ctl + TPRC_Q_CUR, DP_NQ * 8, hipMemcpyDeviceToDevice, s));
-    }
-    // what the control kernel left (capacities, rounds): one more wave-per-read launch over that list, behind the others
-    HIPCHK(a, hipStreamWaitEvent(s, a->ev_join, 0));
-    HIPCHK(a, hipStreamWaitEvent(s, a->ev_join3, 0));
-    {
-      ExtendParamsT<C> bp = ep;
-      bp.skip_scan = 1;
-      bp.heavy = a->t_bail.as<unsigned long long>();
-      bp.heavy_count = ctl + TPRC_BAIL_CNT;
-      bp.team = nullptr;
-      bp.team_count = nullptr;
-      bp.queue = a->t_queue2.as<unsigned int>();
-      bp.wave_counters = zp.wave_counters + (uint64_t)ctl_blocks * THM_N_COUNTERS;
-      HIPCHK(a, launch_extend(bp, cpl, bail_blocks, s));
-    }
-  } else if (team_ok) {
-    ExtendParamsT<C> tp = ep;
-    tp.list_only = 1;
-    tp.wave_counters = ep.wave_counters + main_rows * THM_N_COUNTERS;
-    tp.trace_scratch = ep.trace_scratch + main_trace_waves * trace_per_wave / 8;
-    // The finisher runs before the fork, with the machine to itself.  (On the main kernel's stream, beside the team kernel --
-    // whose reads are never the finisher's -- it was measured at 120 - 430 us instead: a team workgroup takes a whole CU's
-    // registers, and the main kernel waited for the finisher all that time)
-    if (fin_blocks) HIPCHK(a, launch_smem_finish(fp, fin_blocks, s));
+  if (plan.tpr) {
+    const int rc = enqueue_tpr_rounds(a, plan, ep);
+    if (rc != THM_OK) return rc;
+  } else if (plan.team_ok) {
+    // Reads with very many hits: a workgroup per read (speculative chunks of hits, kernels_extend.hip TEAM) BESIDE the
+    // wave-per-read kernel: such reads are the long jobs of a batch, a launch behind the main kernel would put them on the
+    // critical path.  A team workgroup needs a whole CU's registers, so it must be placed before the persistent waves of
+    // the main kernel fill the machine: the team kernel goes first on this stream, the main kernel on the second stream
+    // behind an event (the event's latency is the team's head start; the other way round the team kernel started 10 us
+    // late and waited for the main kernel to drain -- rocprofv3 kernel trace, tools/overlap_trace.py).
     HIPCHK(a, hipEventRecord(a->ev_fork, s));
-    HIPCHK(a, launch_extend(tp, cpl, a->n_cu, s, true));
+    HIPCHK(a, launch_extend(team_params(a, plan, ep), cpl, a->n_cu, s, true));
     HIPCHK(a, hipStreamWaitEvent(a->stream2, a->ev_fork, 0));
-    HIPCHK(a, launch_extend(ep, cpl, ext_blocks, a->stream2));
+    HIPCHK(a, launch_extend(ep, cpl, plan.ext_blocks, a->stream2));
     HIPCHK(a, hipEventRecord(a->ev_join, a->stream2));
     HIPCHK(a, hipStreamWaitEvent(s, a->ev_join, 0));
   } else {
-    if (fin_blocks) HIPCHK(a, launch_smem_finish(fp, fin_blocks, s));
-    HIPCHK(a, launch_extend(ep, cpl, ext_blocks, s));
+    HIPCHK(a, launch_extend(ep, cpl, plan.ext_blocks, s));
   }
   // ---- slow class (and the fast kernel's retries) ----
-  if (cls.n_slow || retry_possible) {
-    const uint32_t sl_len = std::max(cls.slow_len, cls.fast_len), sl_bw = std::max(cls.slow_bw, cls.fast_bw);
-    const uint64_t per_wave = slow_per_wave;
-    const int blocks = (int)(slow_waves / 4);
-    ep.wave_counters = a->e_wcnt.as<unsigned long long>() + (main_rows + team_rows) * THM_N_COUNTERS;
-    HIPCHK(a, a->e_slow.ensure((size_t)blocks * 4 * per_wave + 256));
-    ep.max_read_len = sl_len;
-    ep.max_bw = sl_bw;
-    ep.mk_cap = mk_cap_slow;
+  if (plan.slow) {
+    HIPCHK(a, a->e_slow.ensure((size_t)plan.slow_waves * plan.slow_per_wave + 256));
+    ep.wave_counters = counter_rows(a, plan.row_slow);
+    ep.max_read_len = plan.slow_len;
+    ep.max_bw = plan.slow_bw;
+    ep.mk_cap = plan.mk_cap_slow;
     ep.list_only = 1;
     ep.heavy = a->s_slow.as<unsigned long long>();
     ep.heavy_count = a->s_work_counts.as<unsigned long long>() + 5;
     ep.team = nullptr;
     ep.team_count = nullptr;
     ep.slow_scratch = a->e_slow.as<uint8_t>();
-    ep.slow_scratch_per_wave = per_wave;
-    HIPCHK(a, launch_extend(ep, 0, blocks, s));
+    ep.slow_scratch_per_wave = plan.slow_per_wave;
+    HIPCHK(a, launch_extend(ep, 0, (int)(plan.slow_waves / 4), s));
   }
-  HIPCHK(a, launch_counters_reduce(a->e_wcnt.as<unsigned long long>(), (uint32_t)n_rows, a->d_counters.as<unsigned long long>(), s));
+  HIPCHK(a, launch_counters_reduce(a->e_wcnt.as<unsigned long long>(), (uint32_t)plan.n_rows, a->d_counters.as<unsigned long long>(), s));
   a->wcnt_clean_cap = a->e_wcnt.cap;
   return THM_OK;
 }
@@ -579,7 +357,7 @@ int enqueue_run(thm_aligner* a) {
   // length classes for the current options; lists for the extend stage
   const uint32_t mk_cap_slow = std::max<uint32_t>(a->ix->max_tx_exons, 1);
   const bool retry_possible = a->ix->max_tx_exons > (uint32_t)FAST_MAX_YCLIPS + 1;
-  const ExtClasses cls = classify(a, mk_cap_slow);
+  const ExtClasses cls = classify(a->len_hist, a->opts, mk_cap_slow);
   a->n_slow_host = cls.n_slow;
   a->fast_max_len = cls.fast_max;
   a->slow_max_len = cls.slow_max;
@@ -590,7 +368,7 @@ int enqueue_run(thm_aligner* a) {
   // one run that cannot keep it, a pool (test hook) too small to hold it, forgets it: it is written again when next wanted.
   const bool run_valid = a->ops_run_half > 0 && a->ops_run_ptr == a->e_ops.p && a->ops_run_cap == a->e_ops.cap;
   if (!run_valid) a->ops_run_half = 0;
-  const bool fin_wanted = !a->use_tpr && a->fin_classes && cls.fast_len > 0;
+  const bool fin_wanted = !a->tpr.use_tpr && a->fin_classes && cls.fast_len > 0;
   if (fin_wanted && a->ops_run_half < cls.fast_len && fin::run_bytes(cls.fast_len) <= a->cand_ops_cap) {
     HIPCHK(a, hipMemsetAsync(a->e_ops.p, THM_OP_MATCH, fin::run_bytes(cls.fast_len), s));
     HIPCHK(a, hipMemsetAsync(a->e_ops.as<uint8_t>() + cls.fast_len, THM_OP_SUBST, 1, s));
@@ -601,6 +379,19 @@ int enqueue_run(thm_aligner* a) {
   if (a->ops_run_half && fin::run_bytes(a->ops_run_half) > a->cand_ops_cap) a->ops_run_half = 0;  // this run writes over it
   const uint64_t ops_start = a->ops_run_half ? fin::run_bytes(a->ops_run_half) : 0;
   a->fin_run_classes = (fin_wanted && a->ops_run_half >= cls.fast_len) ? a->fin_classes : 0;
+  // every launch of the extend stage: grids, scratch slices, counter rows (extend_plan.h)
+  ExtendPlanIn pin;
+  pin.n_reads = n;
+  pin.n_cu = a->n_cu;
+  pin.cls = cls;
+  pin.mk_cap_slow = mk_cap_slow;
+  pin.retry_possible = retry_possible;
+  pin.waves_per_simd = extend_waves_per_simd(cells_per_lane(cls.fast_bw), a->dix->wide);
+  pin.use_tpr = a->tpr.use_tpr;
+  pin.dp_lds = extend_dp_lds_bytes(tpr_dp_x_cap(cls), tpr_dp_y_cap(cls));
+  pin.dpt_lds = extend_dpt_lds_bytes(tpr_dpt_tcols(cls));
+  pin.fin_classes = a->fin_run_classes;
+  const ExtendPlan plan = plan_extend(pin);
   PlanParams pp;
   pp.offsets = a->r_offsets.as<uint64_t>();
   pp.read_hits = a->s_hits.as<uint64_t>();
@@ -610,13 +401,10 @@ int enqueue_run(thm_aligner* a) {
   pp.heavy = a->s_heavy.as<unsigned long long>();
   pp.slow = a->s_slow.as<unsigned long long>();
   pp.team = a->s_team.as<unsigned long long>();
-  {
-    const int cpl_f = std::max(1, (int)((2 * cls.fast_bw + 1 + 63) / 64));
-    pp.team_ok = (cpl_f <= 2 && team_fits_lds(extend_lds_bytes(cls.fast_len, cls.fast_bw, cpl_f))) ? 1u : 0u;
-  }
+  pp.team_ok = plan.team_ok ? 1u : 0u;
   pp.total_hits = a->s_cand_off.as<uint64_t>() + n;
   pp.team_div = team_div_per_cu() * (uint32_t)std::max(a->n_cu, 1);
-  pp.tpr_max_hits = (a->use_tpr && std::max(1, (int)((2 * cls.fast_bw + 1 + 63) / 64)) <= 4) ? TPR_MAX_HITS : 0u;
+  pp.tpr_max_hits = plan.tpr_max_hits;
   pp.counts = a->s_work_counts.as<unsigned long long>();
   pp.read_status = a->r_status.as<int32_t>();
   pp.read_n_alns = a->e_nalns.as<uint32_t>();
@@ -627,8 +415,7 @@ int enqueue_run(thm_aligner* a) {
   if (rc != THM_OK) return rc;
   HIPCHK(a, hipEventRecord(a->ev[2], s));
 
-  rc = a->dix->wide ? enqueue_extend_t<uint64_t>(a, cls, mk_cap_slow, retry_possible)
-                    : enqueue_extend_t<uint32_t>(a, cls, mk_cap_slow, retry_possible);
+  rc = a->dix->wide ? enqueue_extend_t<uint64_t>(a, plan) : enqueue_extend_t<uint32_t>(a, plan);
   if (rc != THM_OK) return rc;
   HIPCHK(a, hipEventRecord(a->ev[3], s));
 

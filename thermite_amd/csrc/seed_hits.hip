@@ -1,6 +1,6 @@
 // seed_hits.hip -- host side of thm_align_seed_hits_batch (include/thermite.h): align_seed_hit
 // (reference src/aligner.rs:198-314) for hits the caller chooses.  The checks that decide a hit's status on the host,
-// the band classes (as classify() in pipeline.hip cuts them for reads), the launches of seed_hit_kernel
+// the band classes (as classify() in extend_plan.h cuts them for reads), the launches of seed_hit_kernel
 // (kernels_extend.hip) and the canonical layout of the result.
 #include <hip/hip_runtime.h>
 
@@ -14,8 +14,6 @@ using namespace thm;
 
 namespace {
 
-// device memory the any-width launches may take for their wave-private buffers (as pipeline.hip)
-constexpr uint64_t SLOW_SCRATCH_BUDGET = 24ull << 30;
 constexpr int FAULT_OPS_POOL = 1, FAULT_INTERNAL = 2;  // kernels_extend.hip
 
 struct Launch {
@@ -68,18 +66,15 @@ int run_seed_hits(thm_aligner* a, const std::vector<Launch>& launches, uint64_t 
     p.slow_scratch_per_wave = 0;
     int n_blocks;
     if (l.cpl == 0) {
-      const uint64_t per_wave = (extend_slow_scratch_bytes(l.max_len, l.max_bw, p.mk_cap) + 255) & ~255ull;
-      const uint64_t want = l.retries ? (uint64_t)a->n_cu * 8 : std::max<uint64_t>(l.n, 1);
-      uint64_t waves = std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(SLOW_SCRATCH_BUDGET / per_wave, (uint64_t)a->n_cu * 8), want));
-      waves = (waves + 3) / 4 * 4;
+      const uint64_t per_wave = slow_wave_bytes(l.max_len, l.max_bw, p.mk_cap);
+      const uint64_t waves = slow_launch_waves(per_wave, a->n_cu, l.retries ? (uint64_t)a->n_cu * 8 : std::max<uint64_t>(l.n, 1));
       n_blocks = (int)(waves / 4);
       HIPCHK(a, a->sh_slow.ensure((size_t)waves * per_wave + 256));
       p.slow_scratch = a->sh_slow.as<uint8_t>();
       p.slow_scratch_per_wave = per_wave;
     } else {
       const size_t lds = extend_lds_bytes(l.max_len, l.max_bw, l.cpl);
-      const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(4, EXTEND_LDS_LIMIT / std::max<size_t>(lds, 1)));
-      n_blocks = grid_blocks(a, l.n, 4, per_cu);
+      n_blocks = grid_blocks(a, l.n, 4, lds_blocks_per_cu(lds, 4));
       const size_t trace_per_wave = extend_trace_scratch_bytes(l.max_len, l.max_bw, l.cpl);
       HIPCHK(a, a->sh_trace.ensure((size_t)n_blocks * 4 * trace_per_wave + 64));
       p.trace_scratch = a->sh_trace.as<unsigned long long>();
@@ -152,7 +147,7 @@ int32_t thm_align_seed_hits_batch(thm_aligner* a, const uint8_t* bases, const ui
   std::vector<uint32_t> by_cls[5];
   for (uint64_t h = 0; h < n_hits; h++) {
     if (status[h] != THM_OK) continue;
-    const int cpl = std::max(1, (int)((2 * band_width[h] + 1 + 63) / 64));
+    const int cpl = cells_per_lane(band_width[h]);
     by_cls[cpl <= 4 ? cpl : 0].push_back((uint32_t)h);
   }
   auto len_of = [&](uint32_t h) { return (uint32_t)(offsets[hit_read[h] + 1] - offsets[hit_read[h]]); };
