@@ -271,6 +271,16 @@ class Aligner {
     return info;
   }
 
+  // head ++ the inflated gzip members as a block of FASTQ, inflated and parsed on the device where they are BGZF
+  // (thm_batch_upload_fastq_bgzf); info.tail, the bytes behind the batch, is the head of the next call
+  thm_fastq_bgzf_info upload_fastq_bgzf(const std::string& members, const std::string& head = "", const std::string& path = "",
+                                        std::uint64_t first_line = 1, bool last_block = true) {
+    thm_fastq_bgzf_info info;
+    check(thm_batch_upload_fastq_bgzf(h_.get(), (const std::uint8_t*)head.data(), head.size(), (const std::uint8_t*)members.data(),
+                                      members.size(), path.c_str(), first_line, last_block ? 1 : 0, &info));
+    return info;
+  }
+
   // to_noodles_cigar for one serialised op stream (thm_cigar_encode_batch): its digest, words through *words
   thm_aln_digest cigar_encode(const std::vector<std::uint8_t>& ops, std::vector<std::uint32_t>* words = nullptr) {
     const std::uint64_t off[2] = {0, ops.size()};

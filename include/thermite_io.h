@@ -176,6 +176,37 @@ typedef struct thm_fastq_upload_info {
 int32_t thm_batch_upload_fastq(thm_aligner* a, const uint8_t* raw, uint64_t n, const char* path, uint64_t first_line,
                                int32_t last_block, thm_fastq_upload_info* info);
 
+/* ------------------------------------------------- BGZF FASTQ inflated and parsed on the device */
+
+typedef struct thm_fastq_bgzf_info {
+  uint64_t n_reads, n_bases, n_name_bytes;
+  uint64_t n_lines;           /* lines of the block that the batch consumed (a driver's next first_line advances by it) */
+  uint64_t n_members;         /* members of the chain as the header walk counts them; 0 where the walk fails (the chain is not
+                                 BGZF throughout), whichever side then inflates */
+  uint64_t n_inflated_bytes;
+  const uint8_t* tail;        /* the block's bytes behind the batch; valid until the next call of this function on `a` */
+  uint64_t tail_len;
+  uint32_t inflated_on_device, parsed_on_device;
+  float inflate_ms, parse_ms; /* HIP-event times; 0 where the host did the step */
+} thm_fastq_bgzf_info;
+
+/* thm_batch_upload_fastq for input that is still compressed.  `members` is zero or more whole gzip members back to back
+ * and the block is head ++ inflate(members).  With last_block != 0 the batch is the whole block and the tail is empty.
+ * Otherwise, with L the block's newline count, the batch is the block's first 4 * (L / 4) lines and the tail is what
+ * follows them (the whole block, and a batch of 0 reads, when L < 4).  The batch that ends up uploaded, or the error and
+ * its message, is exactly what thm_batch_upload_fastq makes of the batch bytes with the same path, first_line and
+ * last_block.  The tail comes back on the host, in one of two buffers used alternately, so that it can be handed in as
+ * `head` of the next call on this or any other aligner.
+ * The device inflates BGZF only: every member with the header 1f 8b 08, FLG exactly 4 and an extra field with a BC
+ * subfield of SLEN 2, BSIZE keeping it inside `members`, the chain ending exactly at n, ISIZE at most 65536, and the raw
+ * DEFLATE stream decoding to exactly ISIZE bytes with the trailer's CRC-32.  Anything else -- a plain gzip member, FNAME,
+ * a larger ISIZE, a corrupt stream -- is inflated on the host instead, as a whole, and is then that inflater's bytes or
+ * its THM_ERR_IO and message: valid gzip the device does not take only costs host time.  The parse step declines to the
+ * host parser on its own terms, as in thm_batch_upload_fastq; bytes the device inflated are brought down for it, not
+ * inflated again.  THM_ERR_INVALID_ARG: null aligner or info, null members with n > 0, null head with head_len > 0. */
+int32_t thm_batch_upload_fastq_bgzf(thm_aligner* a, const uint8_t* head, uint64_t head_len, const uint8_t* members, uint64_t n,
+                                    const char* path, uint64_t first_line, int32_t last_block, thm_fastq_bgzf_info* info);
+
 /* The uploaded batch back on the host (names, bases as uploaded, qualities -- NULL for a batch uploaded without --, both
  * offset arrays), whichever upload placed it; the view is valid until the next call of this function on the aligner.
  * THM_ERR_INVALID_ARG: no batch with names is uploaded (plain thm_batch_upload carries none). */
@@ -247,7 +278,14 @@ typedef struct thm_run_stats {
  * ones are the device encoder's (THM_BAM_LEVEL does not apply), and n_output_bytes counts them.
  * THM_FASTQ_DEVICE=1 together with THM_FMT_BAM and THM_BAM_DEVICE=1 or 2 (the modes in which the host needs no read
  * bytes; ignored otherwise): the blocks of 4-line FASTQ input are not parsed by the parser threads but go to the device
- * as they are (thm_batch_upload_fastq); the output file is the same byte for byte. */
+ * as they are (thm_batch_upload_fastq); the output file is the same byte for byte.
+ * THM_FASTQ_DEVICE=2, in the same two modes: as =1, and an input file that is BGZF throughout -- gzip magic, every member
+ * of its chain with the BGZF header, the chain ending exactly at the end of the file, the first member inflating to
+ * text that begins with '@' -- is not inflated on the host either: it is mapped, cut into groups of whole members of
+ * about batch_reads reads (by the bytes per record of the batches so far, one member at least; a batch may hold more
+ * reads than batch_reads) and every group goes to the device compressed (thm_batch_upload_fastq_bgzf), the tail of one
+ * batch being the head of the next, across aligners in input order.  The file's inflated bytes are the same; batch
+ * boundaries, and with THM_BAM_DEVICE=2 the compressed bytes, may differ.  Every other file takes the path of =1. */
 int32_t thm_align_files(thm_aligner* a, const char* const* fastq_paths, uint32_t n_paths, const char* output_path,
                         int32_t format, uint64_t batch_reads, uint32_t n_threads, thm_run_stats* stats);
 /* The same over several aligners -- one per GPU of the node, all over one index (the shape of ThermiteAligner: Clone +

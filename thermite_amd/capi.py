@@ -149,6 +149,15 @@ class FastqUploadInfo(C.Structure):
                 ("device_ms", C.c_float)]
 
 
+class FastqBgzfInfo(C.Structure):
+    """thm_fastq_bgzf_info (include/thermite_io.h)"""
+
+    _fields_ = [("n_reads", C.c_uint64), ("n_bases", C.c_uint64), ("n_name_bytes", C.c_uint64), ("n_lines", C.c_uint64),
+                ("n_members", C.c_uint64), ("n_inflated_bytes", C.c_uint64), ("tail", C.c_void_p), ("tail_len", C.c_uint64),
+                ("inflated_on_device", C.c_uint32), ("parsed_on_device", C.c_uint32), ("inflate_ms", C.c_float),
+                ("parse_ms", C.c_float)]
+
+
 BAM_NO_ANNOTATION_TAGS = 1
 
 # every symbol include/thermite.h declares
@@ -173,6 +182,7 @@ IO_ABI_SYMBOLS = [
     "thm_batch_upload_reads", "thm_batch_fetch_bam", "thm_align_batch_bam", "thm_writer_wrap_bam",
     "thm_batch_fetch_bgzf", "thm_align_batch_bgzf",
     "thm_batch_upload_fastq", "thm_batch_fetch_reads",
+    "thm_batch_upload_fastq_bgzf",
 ]
 ERR_IO, ERR_FORMAT = -8, -9
 FMT_PAF, FMT_SAM, FMT_BAM = 0, 1, 2
@@ -326,6 +336,12 @@ def lib():
     L.thm_batch_fetch_reads.argtypes = [vp, vp]
     L.thm_debug_fastq_device_blocks.restype = i32
     L.thm_debug_fastq_device_blocks.argtypes = [vp, vp, vp]
+    L.thm_batch_upload_fastq_bgzf.restype = i32
+    L.thm_batch_upload_fastq_bgzf.argtypes = [vp, vp, u64, vp, u64, cp, u64, i32, vp]
+    L.thm_debug_bgzf_inflate.restype = i32
+    L.thm_debug_bgzf_inflate.argtypes = [vp, vp, u64, vp, u64, vp]
+    L.thm_debug_fastq_bgzf_blocks.restype = i32
+    L.thm_debug_fastq_bgzf_blocks.argtypes = [vp, vp]
     L.thm_writer_wrap_bam.restype = i32
     L.thm_writer_wrap_bam.argtypes = [vp, vp, vp]
     L.thm_align_files.restype = i32
@@ -804,6 +820,33 @@ class Aligner:
         d, h = C.c_uint64(0), C.c_uint64(0)
         self._chk(lib().thm_debug_fastq_device_blocks(self.h, C.byref(d), C.byref(h)))
         return d.value, h.value
+
+    def upload_fastq_bgzf(self, members, head=b"", path=b"", first_line=1, last_block=True):
+        """thm_batch_upload_fastq_bgzf: head ++ the inflated gzip members as a block of FASTQ -> the info as a dict, `tail`
+        (the block's bytes behind the batch: the head of the next call) as bytes"""
+        m = np.frombuffer(bytes(members), np.uint8) if len(members) else None
+        h = np.frombuffer(bytes(head), np.uint8) if len(head) else None
+        info = FastqBgzfInfo()
+        self._chk(lib().thm_batch_upload_fastq_bgzf(self.h, _ptr(h), len(head), _ptr(m), len(members), os.fsencode(path), first_line,
+                                                    int(bool(last_block)), C.byref(info)))
+        out = {k: getattr(info, k) for k, _ in FastqBgzfInfo._fields_}
+        out["tail"] = C.string_at(info.tail, info.tail_len) if info.tail_len else b""
+        return out
+
+    def debug_bgzf_inflate(self, members, cap=None):
+        """test hook: gzip members through the device inflater alone (no host inflater behind it) -> the inflated bytes;
+        a chain the device does not take, or a member it declines, raises"""
+        src = np.frombuffer(bytes(members), np.uint8) if len(members) else np.zeros(1, np.uint8)
+        out = np.empty((65536 * (len(members) // 27 + 1) if cap is None else cap) + 64, np.uint8)
+        n = C.c_uint64(0)
+        self._chk(lib().thm_debug_bgzf_inflate(self.h, src.ctypes.data, len(members), out.ctypes.data, len(out), C.byref(n)))
+        return out[: n.value].tobytes()
+
+    def debug_fastq_bgzf_blocks(self):
+        """test hook: what upload_fastq_bgzf did so far: (inflates on the device, on the host, parses on the device, on the host)"""
+        c = (C.c_uint64 * 4)()
+        self._chk(lib().thm_debug_fastq_bgzf_blocks(self.h, c))
+        return tuple(int(x) for x in c)
 
     def debug_bgzf_device(self, data):
         """test hook: bytes through the device BGZF encoder -> (the members back to back, their number)"""

@@ -300,6 +300,16 @@ struct thm_aligner {
   uint64_t fq_on_device = 0, fq_on_host = 0;
   Event ev_fq[6];  // made by the first call
   HBuf fr_bases, fr_off, fr_quals, fr_names, fr_name_off;
+  // BGZF members inflated on the device (inflate.hip): the members' bytes, the host's table of them and their status
+  // words (the table and the statuses in pinned memory too); the inflated block is built in fq_raw.  Two tail buffers,
+  // used alternately; the block on the host where the host inflated or parsed it.  Counts for
+  // thm_debug_fastq_bgzf_blocks: inflates on device / on host, parses on device / on host.
+  DBuf fz_in, fz_tab, fz_status;
+  HBuf fz_h_tab, fz_h_status, fz_tail[2], fz_h_last;
+  int fz_cur = 0;
+  std::vector<uint8_t> fz_block;
+  uint64_t fz_counts[4] = {0, 0, 0, 0};
+  Event ev_fz[2];  // made by the first call
 };
 
 inline int fail(thm_aligner* a, int code, const char* fmt, ...) {
@@ -350,6 +360,27 @@ thm::CigarParams compacted_cigar_params(const thm_aligner* a, const BatchSizes& 
 // pipeline.hip: what thm_batch_upload derives from the offsets of a batch -- n_reads, n_bases, max_read_len, the length
 // classes (len_hist) and n_over -- for every upload path; THM_ERR_INVALID_ARG for offsets that do not start at 0 or descend
 int batch_length_classes(thm_aligner* a, const uint64_t* offsets, uint64_t n_reads);
+// fastq.hip: the device FASTQ parse (count, starts, records, gather) of a block of n > 0 bytes that stands in fq_raw,
+// which the caller has sized to n + 64 -- put there by a copy (thm_batch_upload_fastq) or by the device inflater
+// (inflate.hip).  Three synchronisations of the stream, whichever it is.
+struct FastqBlock {
+  uint64_t n = 0;
+  const uint8_t* host = nullptr;  // the block's bytes on the host; null: its last byte comes down with the newline total
+  bool whole = true;              // the batch is the whole block; false: its first 4 * (newlines / 4) lines
+  const uint32_t* d_status = nullptr;  // status words of an inflate (device), checked at the first synchronisation
+  uint64_t n_status = 0;
+  HBuf* tail = nullptr;  // where the bytes behind the batch go, in the copy-back the gather ends with (null: not wanted)
+  // results
+  uint64_t bad_member = 0;  // FQ_NOT_INFLATED: the first member with a status other than 0 (the word is in fz_h_status)
+  uint64_t n_newlines = 0;
+  uint64_t cut = 0;         // bytes of the batch (valid once the call returns 0 or 1)
+  uint64_t n_reads = 0, n_bases = 0, n_name_bytes = 0;
+  float ms = 0;
+};
+enum { FQ_NOT_INFLATED = 2, FQ_NO_RECORD = 3 };  // beside 1 (parsed), 0 (declined: the host parser's) and errors (< 0)
+namespace thm {
+int parse_resident(thm_aligner* a, FastqBlock& b);
+}
 int reset_queue(thm_aligner* a);
 inline int grid_blocks(const thm_aligner* a, uint64_t n_items, int waves_per_block, int blocks_per_cu) {
   return thm::grid_blocks(a->n_cu, n_items, waves_per_block, blocks_per_cu);

@@ -2,7 +2,9 @@
 // FASTQ records goes up as the bytes it is, and kernels_fastq.hip cuts it into names, bases and qualities where
 // thm_batch_upload_reads would have placed them.  The device takes the strict form only (fastq_device.h); a block it
 // declines is parsed by fastq_parse_block (io_fastq.cpp) and uploaded the old way, or is that parser's error: what the
-// call does is the host parser's doing on every input.
+// call does is the host parser's doing on every input.  The kernels run on the block where it stands in fq_raw
+// (parse_resident), so that a block the device inflated there (inflate.hip, thm_batch_upload_fastq_bgzf) takes the same
+// path as one that was copied up.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -13,17 +15,16 @@
 
 using namespace thm;
 
-namespace {
-
-// 1: the batch is in place, parsed by the device; 0: declined (nothing of the aligner's batch state is valid); < 0: error
-int parse_on_device(thm_aligner* a, const uint8_t* raw, uint64_t n, thm_fastq_upload_info* info) {
+// The parse of a block that stands in fq_raw (FastqBlock, aligner_internal.h): 1: the batch is in place, parsed by the
+// device; 0: declined (nothing of the aligner's batch state is valid); < 0: error; FQ_NOT_INFLATED / FQ_NO_RECORD as there
+int thm::parse_resident(thm_aligner* a, FastqBlock& b) {
   hipStream_t s = a->stream;
+  const uint64_t n = b.n;
   HIPCHK(a, ensure_events(a->ev_fq));
   FastqParams p;
   memset(&p, 0, sizeof p);
   p.n = n;
   p.n_chunks = (n + fq::CHUNK - 1) / fq::CHUNK;
-  HIPCHK(a, a->fq_raw.ensure(n + 64));
   HIPCHK(a, a->fq_cnt.ensure(p.n_chunks * 8));
   HIPCHK(a, a->fq_base.ensure((p.n_chunks + 2) * 8));
   HIPCHK(a, a->fq_flag.ensure(64));
@@ -32,7 +33,6 @@ int parse_on_device(thm_aligner* a, const uint8_t* raw, uint64_t n, thm_fastq_up
   p.chunk_cnt = a->fq_cnt.as<uint64_t>();
   p.chunk_base = a->fq_base.as<uint64_t>();
   p.flag = a->fq_flag.as<unsigned>();
-  HIPCHK(a, hipMemcpyAsync(a->fq_raw.p, raw, n, hipMemcpyHostToDevice, s));
   HIPCHK(a, hipMemsetAsync(a->fq_flag.p, 0, 64, s));
   // ---- newlines: per chunk, their scan; the total sizes the line table
   HIPCHK(a, hipEventRecord(a->ev_fq[0], s));
@@ -41,21 +41,42 @@ int parse_on_device(thm_aligner* a, const uint8_t* raw, uint64_t n, thm_fastq_up
   HIPCHK(a, hipEventRecord(a->ev_fq[1], s));
   unsigned long long n_nl = 0;
   HIPCHK(a, hipMemcpyAsync(&n_nl, a->fq_base.as<uint64_t>() + p.n_chunks, 8, hipMemcpyDeviceToHost, s));
+  // a block the host has not seen: its last byte, and the words its inflate left, come down with the total
+  if (!b.host) {
+    HIPCHK(a, a->fz_h_last.ensure(64));
+    HIPCHK(a, hipMemcpyAsync(a->fz_h_last.p, a->fq_raw.as<uint8_t>() + n - 1, 1, hipMemcpyDeviceToHost, s));
+  }
+  if (b.n_status) {
+    HIPCHK(a, a->fz_h_status.ensure(b.n_status * 4));
+    HIPCHK(a, hipMemcpyAsync(a->fz_h_status.p, b.d_status, b.n_status * 4, hipMemcpyDeviceToHost, s));
+  }
   HIPCHK(a, hipStreamSynchronize(s));
-  if (n_nl > n) return fail(a, THM_ERR_INTERNAL, "thm_batch_upload_fastq: more newlines than bytes");
+  for (uint64_t k = 0; k < b.n_status; k++)
+    if (a->fz_h_status.as<uint32_t>()[k] != 0) {
+      b.bad_member = k;
+      return FQ_NOT_INFLATED;
+    }
+  if (n_nl > n) return fail(a, THM_ERR_INTERNAL, "device FASTQ parse: more newlines than bytes");
   p.n_newlines = n_nl;
-  p.n_lines = fq::line_count(n_nl, raw[n - 1]);
-  if (p.n_lines % 4 != 0) return 0;
+  b.n_newlines = n_nl;
+  b.cut = n;
+  if (b.whole) {
+    p.n_lines = fq::line_count(n_nl, b.host ? b.host[n - 1] : a->fz_h_last.as<uint8_t>()[0]);
+    if (p.n_lines % 4 != 0) return 0;
+  } else {
+    p.n_lines = 4 * (n_nl / 4);
+    if (p.n_lines == 0) return FQ_NO_RECORD;
+  }
   const uint64_t nr = p.n_records = p.n_lines / 4;
   if (nr >= 0xFFFFFFF0ull) return 0;  // (the host path words the refusal)
   // ---- line starts, the rule per record, name_off and offsets
-  HIPCHK(a, a->fq_lines.ensure((p.n_lines + 2) * 8));
+  HIPCHK(a, a->fq_lines.ensure(((p.n_lines > n_nl ? p.n_lines : n_nl) + 2) * 8));
   HIPCHK(a, a->fq_name_len.ensure((nr + 1) * 8));
   HIPCHK(a, a->fq_seq_len.ensure((nr + 1) * 8));
   HIPCHK(a, a->fq_scan_tmp.ensure(scan_tmp_entries(nr + 1) * 8 + 64));
   HIPCHK(a, a->bn_name_off.ensure((nr + 1) * 8));
   HIPCHK(a, a->r_offsets.ensure((nr + 1) * 8));
-  HIPCHK(a, a->fq_h_off.ensure((nr + 2) * 8));
+  HIPCHK(a, a->fq_h_off.ensure((nr + 3) * 8));
   p.line_start = a->fq_lines.as<uint64_t>();
   p.name_len = a->fq_name_len.as<uint64_t>();
   p.seq_len = a->fq_seq_len.as<uint64_t>();
@@ -67,17 +88,23 @@ int parse_on_device(thm_aligner* a, const uint8_t* raw, uint64_t n, thm_fastq_up
   HIPCHK(a, launch_exclusive_scan_u64(p.name_len, a->bn_name_off.as<uint64_t>(), nr, a->fq_scan_tmp.as<uint64_t>(), s));
   HIPCHK(a, launch_exclusive_scan_u64(p.seq_len, a->r_offsets.as<uint64_t>(), nr, a->fq_scan_tmp.as<uint64_t>(), s));
   HIPCHK(a, hipEventRecord(a->ev_fq[3], s));
-  // the offsets come down for the length classes (8 bytes a read); the name bytes' total behind them
+  // the offsets come down for the length classes (8 bytes a read); the name bytes' total behind them, and behind that
+  // the cut of a block that is not the whole batch: where the line behind the batch's last begins
   unsigned flag = 0;
   uint64_t* h_off = a->fq_h_off.as<uint64_t>();
   HIPCHK(a, hipMemcpyAsync(&flag, a->fq_flag.p, 4, hipMemcpyDeviceToHost, s));
   HIPCHK(a, hipMemcpyAsync(h_off, a->r_offsets.p, (nr + 1) * 8, hipMemcpyDeviceToHost, s));
   HIPCHK(a, hipMemcpyAsync(h_off + nr + 1, a->bn_name_off.as<uint64_t>() + nr, 8, hipMemcpyDeviceToHost, s));
+  if (!b.whole) HIPCHK(a, hipMemcpyAsync(h_off + nr + 2, p.line_start + p.n_lines, 8, hipMemcpyDeviceToHost, s));
   HIPCHK(a, hipStreamSynchronize(s));
-  if (flag == 2) return fail(a, THM_ERR_INTERNAL, "thm_batch_upload_fastq: inconsistent line table");
+  if (flag == 2) return fail(a, THM_ERR_INTERNAL, "device FASTQ parse: inconsistent line table");
+  if (!b.whole) {
+    if (h_off[nr + 2] > n) return fail(a, THM_ERR_INTERNAL, "device FASTQ parse: a cut behind the block");
+    b.cut = h_off[nr + 2];
+  }
   if (flag != 0) return 0;
   const uint64_t nb = h_off[nr], nn = h_off[nr + 1];
-  if (nn + 2 * nb > n) return fail(a, THM_ERR_INTERNAL, "thm_batch_upload_fastq: a parse larger than its block");
+  if (nn + 2 * nb > b.cut) return fail(a, THM_ERR_INTERNAL, "device FASTQ parse: a parse larger than its block");
   int rc = batch_length_classes(a, h_off, nr);
   if (rc != THM_OK) return rc;
   // ---- gather, into the buffers (and with the paddings) of thm_batch_upload / thm_batch_upload_reads
@@ -90,15 +117,37 @@ int parse_on_device(thm_aligner* a, const uint8_t* raw, uint64_t n, thm_fastq_up
   HIPCHK(a, hipEventRecord(a->ev_fq[4], s));
   HIPCHK(a, launch_fastq_gather(p, a->n_cu, s));
   HIPCHK(a, hipEventRecord(a->ev_fq[5], s));
+  if (b.tail && n > b.cut) {
+    HIPCHK(a, b.tail->ensure(n - b.cut));
+    HIPCHK(a, hipMemcpyAsync(b.tail->p, a->fq_raw.as<uint8_t>() + b.cut, n - b.cut, hipMemcpyDeviceToHost, s));
+  }
   HIPCHK(a, hipStreamSynchronize(s));
   float ms = 0, sum = 0;
   for (int k = 0; k < 6; k += 2)
     if (hipEventElapsedTime(&ms, a->ev_fq[k], a->ev_fq[k + 1]) == hipSuccess) sum += ms;
-  info->n_reads = nr;
-  info->n_bases = nb;
-  info->n_name_bytes = nn;
+  b.n_reads = nr;
+  b.n_bases = nb;
+  b.n_name_bytes = nn;
+  b.ms = sum;
+  return 1;
+}
+
+namespace {
+
+// the block goes up as it is, then the parse above
+int parse_on_device(thm_aligner* a, const uint8_t* raw, uint64_t n, thm_fastq_upload_info* info) {
+  HIPCHK(a, a->fq_raw.ensure(n + 64));
+  HIPCHK(a, hipMemcpyAsync(a->fq_raw.p, raw, n, hipMemcpyHostToDevice, a->stream));
+  FastqBlock b;
+  b.n = n;
+  b.host = raw;
+  const int d = parse_resident(a, b);
+  if (d != 1) return d;
+  info->n_reads = b.n_reads;
+  info->n_bases = b.n_bases;
+  info->n_name_bytes = b.n_name_bytes;
   info->on_device = 1;
-  info->device_ms = sum;
+  info->device_ms = b.ms;
   return 1;
 }
 

@@ -6,6 +6,10 @@
 //     cut     one thread: mapped file bytes / the inflaters' blocks -> slots, in input order
 //     parse   a few threads: block -> batch (names, bases, qualities); with THM_FASTQ_DEVICE=1 the block passes through
 //             and the device parses it (thm_batch_upload_fastq)
+//             THM_FASTQ_DEVICE=2: a .fastq.gz that is BGZF throughout is not inflated here at all -- the cutter walks its
+//             member chain over the mapping and cuts it into groups of whole members, which go to the device
+//             compressed (thm_batch_upload_fastq_bgzf); the tail of one batch is the head of the next, so the uploads
+//             of such a run are chained in input order across the GPU threads (runs and fetches still overlap)
 //     GPU     one thread per aligner (= per GPU): upload, run, sync, fetch
 //     write   one thread: batches in input order -> formatting threads -> pwrite
 // connected by queues over a fixed set of reusable slots, so that the host work either
@@ -18,6 +22,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <condition_variable>
 #include <cstdio>
@@ -31,6 +36,7 @@
 #include <thread>
 #include <vector>
 
+#include "inflate_device.h"
 #include "io_internal.h"
 #include "thermite_internal.h"
 
@@ -47,6 +53,9 @@ struct Slot {
   uint64_t first_line = 0;
   bool last_block = false;  // nothing of this input file follows the block (blank lines are tolerated at its end)
   std::string path;
+  bool zmembers = false;    // raw_ptr / raw_len are whole BGZF members of the mapped input (THM_FASTQ_DEVICE=2) ...
+  bool file_first = false;  // ... the first group of its file: the chain of tails starts empty, at line 1
+  std::vector<uint8_t> head;  // ... and the head it went up with (kept for the failed-read message)
   bool parsed = false;  // `reads` already holds the batch (sequential parser: FASTA, odd inputs)
   thm::HostBatch reads;
   thm_batch_view res;  // into the pinned result buffers of the aligner that ran it (two sets per aligner, used alternately)
@@ -182,6 +191,72 @@ struct Queue {
   }
 };
 
+// A gzip input that is BGZF throughout (THM_FASTQ_DEVICE=2): the mapping and its members.  Eligible: gzip magic, every
+// member of the chain with the BGZF header (inflate_device.h, the rule the device takes), the chain ending exactly at the
+// end of the file, and the first member, inflated on the host, beginning with '@'.
+struct BgzfFile {
+  const uint8_t* map = nullptr;
+  size_t len = 0;
+  std::vector<thm::inf::Member> tab;  // in_off - 12 - xlen is not kept: `at` below is
+  std::vector<uint64_t> at;           // first byte of every member, and the file's length behind the last
+  double bytes_per_read = 256;        // of the first member's text
+  bool ok = false;
+  BgzfFile() = default;
+  BgzfFile(const BgzfFile&) = delete;
+  BgzfFile& operator=(const BgzfFile&) = delete;
+  ~BgzfFile() {
+    if (map) munmap((void*)map, len);  // (a file the run did not get to; otherwise the mapping was handed on)
+  }
+  void open(const char* path) {
+    const int fd = ::open(path, O_RDONLY);
+    if (fd < 0) return;
+    struct stat st;
+    if (fstat(fd, &st) == 0 && S_ISREG(st.st_mode) && st.st_size >= 28) {
+      void* m = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
+      if (m != MAP_FAILED) {
+        map = (const uint8_t*)m;
+        len = (size_t)st.st_size;
+      }
+    }
+    close(fd);
+    if (!map) return;
+    uint64_t p = 0, out = 0;
+    bool good = true;
+    while (p < len && good) {
+      thm::inf::Member mb;
+      uint64_t size = 0;
+      good = thm::inf::walk_member(map, len, p, out, &mb, &size);
+      if (!good) break;
+      tab.push_back(mb);
+      at.push_back(p);
+      p += size;
+      out += mb.isize;
+    }
+    at.push_back(p);
+    if (good && !tab.empty()) {
+      std::vector<uint8_t> first;
+      std::string err;
+      uint64_t cut = 0;
+      // the first member with text decides: FASTA and anything else keep today's path
+      size_t k = 0;
+      while (k + 1 < tab.size() && tab[k].isize == 0) k++;
+      if (thm::bgzf_block_on_host(nullptr, 0, map + at[k], at[k + 1] - at[k], path, true, first, &cut, err) == THM_OK && !first.empty() &&
+          first[0] == '@' && k == 0) {
+        size_t nl = 0;
+        for (uint8_t c : first) nl += c == '\n';
+        if (nl >= 4) bytes_per_read = (double)first.size() / (double)(nl / 4);
+        ok = true;
+      }
+    }
+    if (!ok) {
+      munmap((void*)map, len);
+      map = nullptr;
+      tab.clear();
+      at.clear();
+    }
+  }
+};
+
 struct Shared {
   std::mutex mu;
   int rc = THM_OK;
@@ -237,7 +312,10 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
   // THM_FASTQ_DEVICE=1, in those two modes only (the host needs no read bytes there): blocks of 4-line FASTQ go to the
   // device unparsed (thm_batch_upload_fastq)
   const char* fq_dev_env = getenv("THM_FASTQ_DEVICE");
-  const bool fastq_device = bam_device && fq_dev_env && !strcmp(fq_dev_env, "1");
+  // THM_FASTQ_DEVICE=2: as =1, and input files that are BGZF throughout go to the device compressed
+  // (thm_batch_upload_fastq_bgzf); every other file takes the path of =1
+  const bool fastq_bgzf = bam_device && fq_dev_env && !strcmp(fq_dev_env, "2");
+  const bool fastq_device = fastq_bgzf || (bam_device && fq_dev_env && !strcmp(fq_dev_env, "1"));
   const thm_index* ix = thm_aligner_index(aligners[0]);
   for (uint32_t i = 1; i < n_aligners; i++)
     if (thm_aligner_index(aligners[i]) != ix) {
@@ -300,6 +378,15 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
   bool cut_done = false;
   uint64_t n_written = 0;  // batches the writer has finished (guarded by done_mu)
 
+  // THM_FASTQ_DEVICE=2: the chain of tails.  Every slot of such a run takes its turn in input order for its upload (a
+  // slot that is not BGZF only passes the turn on); the holder of the turn alone touches ch_tail and ch_line.  The
+  // bytes and reads of the batches so far size the next groups.
+  std::mutex ch_mu;
+  std::condition_variable ch_cv;
+  uint64_t ch_turn = 0;
+  std::vector<uint8_t> ch_tail;
+  uint64_t ch_line = 1;
+  std::atomic<uint64_t> est_bytes{0}, est_reads{0};
   std::vector<std::pair<const char*, size_t>> maps;
   // ---- stage 1: cut the input into blocks of whole records ----
   std::thread cutter([&] {
@@ -307,6 +394,7 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
     // gzip inputs get an inflater thread each (Ahead), those of the next few files running ahead of their turn
     std::vector<std::unique_ptr<Ahead>> ahead(n_paths);
     std::vector<char> is_gz(n_paths, 0);
+    std::vector<std::unique_ptr<BgzfFile>> bgzf_files(n_paths);
     unsigned n_gz = 0;
     for (uint32_t pi = 0; pi < n_paths; pi++) {
       unsigned char magic[2] = {0, 0};
@@ -314,6 +402,20 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
       if (fd >= 0) {
         is_gz[pi] = pread(fd, magic, 2, 0) == 2 && magic[0] == 0x1f && magic[1] == 0x8b;
         close(fd);
+      }
+      if (is_gz[pi] && fastq_bgzf) {  // eligible: no inflater thread, the file is cut by its members
+        const auto t0 = Clock::now();
+        (void)sh.step([&] {
+          std::unique_ptr<BgzfFile> bf(new BgzfFile());
+          bf->open(fastq_paths[pi]);
+          if (bf->ok) {
+            bgzf_files[pi] = std::move(bf);
+            is_gz[pi] = 0;
+          }
+          return THM_OK;
+        });
+        std::lock_guard<std::mutex> g(st_mu);
+        st.parse_s += secs(t0, Clock::now());
       }
       n_gz += is_gz[pi];
     }
@@ -339,6 +441,36 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
       int prc = THM_OK;
       bool fast = false;
       if (sh.step([&] { top_up(pi); return THM_OK; }) != THM_OK) break;
+      if (bgzf_files[pi]) {
+        // groups of whole members of about batch_reads reads, by the bytes per record of the batches so far
+        BgzfFile& bf = *bgzf_files[pi];
+        const size_t nm = bf.tab.size();
+        for (size_t k = 0; k < nm && !sh.failed();) {
+          Slot* s = q_free.pop();
+          const uint64_t eb = est_bytes.load(), er = est_reads.load();
+          const double per = er >= 64 ? (double)eb / (double)er : bf.bytes_per_read;
+          const double want = per * (double)batch_reads;
+          size_t k1 = k;
+          double have_bytes = 0;
+          do have_bytes += bf.tab[k1++].isize;
+          while (k1 < nm && have_bytes < want);
+          s->seq = seq++;
+          s->parsed = false;
+          s->aligned = false;
+          s->zmembers = true;
+          s->file_first = k == 0;
+          s->path = fastq_paths[pi];
+          s->raw_ptr = (const char*)bf.map + bf.at[k];
+          s->raw_len = (size_t)(bf.at[k1] - bf.at[k]);
+          s->last_block = k1 == nm;
+          s->first_line = 0;
+          k = k1;
+          q_raw.push(s);
+        }
+        maps.emplace_back((const char*)bf.map, bf.len);  // unmapped when every batch has been written
+        bf.map = nullptr;
+        continue;
+      }
       if (is_gz[pi]) {
         ah = ahead[pi].get();
         const int kind = ah->wait_kind();
@@ -384,6 +516,7 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
         Slot* s = q_free.pop();
         s->seq = seq;
         s->parsed = false;
+        s->zmembers = false;
         s->aligned = false;
         s->path = fastq_paths[pi];
         const auto t0 = Clock::now();
@@ -526,7 +659,42 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
         bool have = !sh.failed() && (raw_up || s->reads.n_reads() != 0);  // (a blank tail cut into a block of its own holds no read)
         const auto t0 = Clock::now();
         int up_rc = THM_OK;
-        if (have && raw_up) {
+        if (fastq_bgzf) {  // this slot's turn in the chain of uploads
+          std::unique_lock<std::mutex> g(ch_mu);
+          ch_cv.wait(g, [&] { return ch_turn == s->seq; });
+        }
+        if (s->zmembers) {
+          if (s->file_first) {
+            ch_tail.clear();
+            ch_line = 1;
+          }
+          s->first_line = ch_line;
+          if (have) {
+            thm_fastq_bgzf_info zi;
+            memset(&zi, 0, sizeof zi);
+            up_rc = sh.step([&] {
+              s->head = ch_tail;
+              const int r2 = (int)thm_batch_upload_fastq_bgzf(a, s->head.data(), s->head.size(), (const uint8_t*)s->raw_ptr, s->raw_len,
+                                                              s->path.c_str(), s->first_line, s->last_block ? 1 : 0, &zi);
+              if (r2 == THM_OK) {
+                ch_tail.assign(zi.tail, zi.tail + zi.tail_len);
+                ch_line += zi.n_lines;
+                est_bytes += s->head.size() + zi.n_inflated_bytes - zi.tail_len;
+                est_reads += zi.n_reads;
+              }
+              return r2;
+            });
+            if (up_rc == THM_OK && zi.n_reads == 0) have = false;  // (a group without a whole record: all of it is tail)
+          }
+        }
+        if (fastq_bgzf) {
+          {
+            std::lock_guard<std::mutex> g(ch_mu);
+            ch_turn = s->seq + 1;
+          }
+          ch_cv.notify_all();
+        }
+        if (have && raw_up && !s->zmembers) {
           thm_fastq_upload_info fi;
           memset(&fi, 0, sizeof fi);
           up_rc = sh.step([&] {
@@ -560,7 +728,16 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
             // the reference aligns every read or panics; a read this build cannot take fails the run, by name
             uint64_t bad = 0;
             while (bad < n_res && res_status[bad] == THM_OK) bad++;
-            if (raw_up) {  // the host has not seen the names of this block: parse it now, for the one message
+            if (raw_up && s->zmembers) {  // ... inflate and parse that one block here, for the one message
+              std::string perr;
+              (void)sh.step([&] {
+                std::vector<uint8_t> blk;
+                uint64_t cut = 0;
+                int r2 = thm::bgzf_block_on_host(s->head.data(), s->head.size(), (const uint8_t*)s->raw_ptr, s->raw_len, s->path, s->last_block, blk, &cut, perr);
+                if (r2 == THM_OK) r2 = thm::fastq_parse_block((const char*)blk.data(), (size_t)cut, s->path, s->first_line, s->last_block, s->reads, perr);
+                return r2;
+              });
+            } else if (raw_up) {  // the host has not seen the names of this block: parse it now, for the one message
               std::string perr;
               (void)sh.step([&] { return thm::fastq_parse_block(s->raw_ptr, s->raw_len, s->path, s->first_line, s->last_block, s->reads, perr); });
             }

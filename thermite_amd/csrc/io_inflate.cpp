@@ -1257,6 +1257,12 @@ void GzInflater::open(int fd, const std::string& path, unsigned n_threads) {
   p_->ib = p_->inbuf.data();
 }
 
+void GzInflater::open_memory(const uint8_t* data, size_t n, const std::string& path) {
+  p_->inbuf.assign(n + Impl::IN_PAD, 0);  // (the decoder reads a few zero bytes past the end of its input)
+  if (n) memcpy(p_->inbuf.data(), data, n);
+  p_->open_memory(p_->inbuf.data(), n, path);
+}
+
 long GzInflater::par_read(uint8_t* dst, size_t cap) {
   Par& P = *par_;
   Impl& s = *p_;  // (only its error string is used here)

@@ -64,6 +64,8 @@ class GzInflater {
   // Takes the descriptor over.  n_threads > 1 and a regular file of some size: the file is mapped and inflated by
   // that many worker threads (io_inflate.cpp, "several threads on one gzip file"); the calling thread only collects.
   void open(int fd, const std::string& path, unsigned n_threads = 1);
+  // A memory source in place of a descriptor: the gzip members data[0, n), copied; `path` only words the messages.
+  void open_memory(const uint8_t* data, size_t n, const std::string& path);
   // Up to `cap` further bytes of the inflated stream into dst (cap >= 1024; the call stops a few hundred bytes short
   // of cap rather than in the middle of a match).  dst[-history, 0) must hold the `history` bytes that came before
   // (min(bytes so far, 32768) of them: matches reach back there).  0: end of the input; -1: error().
@@ -100,6 +102,11 @@ int writer_wrap_bam_chunks(thm_writer* w, const thm_bam_view* view, std::vector<
 // bgzf.hip: thm_batch_fetch_bgzf, which also reports the reads of the batch with at least one alignment (the view
 // holds compressed bytes only; the file driver counts them in its statistics); n_aligned_reads may be null
 int batch_fetch_bgzf(thm_aligner* a, uint32_t flags, thm_bgzf_view* out, uint64_t* n_aligned_reads);
+
+// inflate.hip: head ++ inflate(members) by the host inflater into `block` (THM_ERR_IO and `err` as GzInflater words it);
+// *cut: bytes of the batch thm_batch_upload_fastq_bgzf takes of it (all of it for a last block)
+int bgzf_block_on_host(const uint8_t* head, uint64_t head_len, const uint8_t* members, uint64_t n, const std::string& path,
+                       bool last_block, std::vector<uint8_t>& block, uint64_t* cut, std::string& err);
 
 // contig name_id -> index of its @SQ line (the BAM refID), build_sam_header's order (src/aln_writer.rs:256-276);
 // `sq`: the lines' (name, length), when asked for

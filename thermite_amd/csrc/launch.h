@@ -685,5 +685,22 @@ hipError_t launch_fastq_starts(const FastqParams& p, int n_cu, hipStream_t s);
 hipError_t launch_fastq_records(const FastqParams& p, hipStream_t s);
 hipError_t launch_fastq_gather(const FastqParams& p, int n_cu, hipStream_t s);
 
+// ---- BGZF members inflated on the device (kernels_inflate.hip, inflate_device.h; host side inflate.hip) ----
+// one wavefront per member of the host's table: its raw DEFLATE stream in `in` -> its isize bytes at out + out_off, and
+// a status word (0, or the reason the member is declined for: nothing of `out` is then to be used)
+namespace inf {
+struct Member;
+}
+struct InflateParams {
+  const uint8_t* in;  // [n_in], 4-byte aligned, readable up to the next multiple of 4
+  uint64_t n_in;
+  const inf::Member* members;  // [n_members]
+  uint64_t n_members;
+  uint8_t* out;  // [n_out]
+  uint64_t n_out;
+  uint32_t* status;  // [n_members]
+};
+hipError_t launch_bgzf_inflate(const InflateParams& p, hipStream_t s);
+
 }  // namespace thm
 #endif

@@ -4,10 +4,17 @@ FASTQ on disk -> thm_align_files -> SAM / PAF.   python tools_e2e.py [ref_len] [
 --bam-device[=RUNS]: only FASTQ -> BAM and .fastq.gz -> BAM, each RUNS times (default 4) with THM_BAM_DEVICE 0, 1 and 2
 in turn (the driver reads the switch at every call), in one session.
 --fastq-device[=ROUNDS]: FASTQ -> BAM and two .fastq.gz -> BAM with THM_BAM_DEVICE 1 and 2, each with THM_FASTQ_DEVICE off
-and on alternately, ROUNDS rounds (default 3) in one session; the files of a pair must be identical."""
+and on alternately, ROUNDS rounds (default 3) in one session; the files of a pair must be identical.
+--fastq-bgzf[=ROUNDS]: the .fastq.gz files are written BGZF-framed with Python's zlib (level 6, members of 0xff00 bytes);
+two of them -> BAM with THM_BAM_DEVICE 1 and 2, each with THM_FASTQ_DEVICE 1 and 2 alternately, ROUNDS rounds (default 3)
+in one session; the inflated BAM streams of a pair must be identical (batch boundaries differ)."""
 import os, sys, time
-BAM_RUNS = FQ_ROUNDS = 0
+BAM_RUNS = FQ_ROUNDS = BGZF_ROUNDS = 0
 for arg in list(sys.argv[1:]):
+    if arg.startswith("--fastq-bgzf"):
+        BGZF_ROUNDS = int(arg.split("=")[1]) if "=" in arg else 3
+        sys.argv.remove(arg)
+        continue
     if arg.startswith("--fastq-device"):
         FQ_ROUNDS = int(arg.split("=")[1]) if "=" in arg else 3
         sys.argv.remove(arg)
@@ -52,7 +59,7 @@ with open(big, "wb") as f:
         f.write(one)
     del one
 print("plain input: %d reads, %.1f MB" % (n * REP, os.path.getsize(big) / 1e6), flush=True)
-for fmt, name in (() if BAM_RUNS or FQ_ROUNDS else ((capi.FMT_SAM, "sam"), (capi.FMT_PAF, "paf"))):
+for fmt, name in (() if BAM_RUNS or FQ_ROUNDS or BGZF_ROUNDS else ((capi.FMT_SAM, "sam"), (capi.FMT_PAF, "paf"))):
     for rep in range(2):
         out = "/tmp/thm_e2e_out.%s" % name
         st = capi.align_files(a, [big], out, fmt, batch_reads=250000, n_threads=threads)
@@ -63,7 +70,15 @@ for fmt, name in (() if BAM_RUNS or FQ_ROUNDS else ((capi.FMT_SAM, "sam"), (capi
 import gzip, shutil, subprocess
 gz = path + ".gz"
 t0 = time.time()
-if shutil.which("gzip"):
+if BGZF_ROUNDS:
+    import struct, zlib
+    with open(path, "rb") as fi, open(gz, "wb") as fo:
+        for piece in iter(lambda: fi.read(0xff00), b""):
+            c = zlib.compressobj(6, zlib.DEFLATED, -15)
+            z = c.compress(piece) + c.flush()
+            fo.write(b"\x1f\x8b\x08\x04\0\0\0\0\0\xff\x06\0BC\x02\0" + struct.pack("<H", len(z) + 25) + z +
+                     struct.pack("<II", zlib.crc32(piece), len(piece)))
+elif shutil.which("gzip"):
     subprocess.check_call("gzip -6 -c %s > %s" % (path, gz), shell=True)
 else:
     with open(path, "rb") as fi, gzip.open(gz, "wb", compresslevel=6) as fo:
@@ -94,7 +109,7 @@ def digest(path):
     return h.hexdigest()
 
 
-paf_of_plain = None if BAM_RUNS or FQ_ROUNDS else digest("/tmp/thm_e2e_out.paf")  # (the last plain run wrote PAF of the REP-copy file)
+paf_of_plain = None if BAM_RUNS or FQ_ROUNDS or BGZF_ROUNDS else digest("/tmp/thm_e2e_out.paf")  # (the last plain run wrote PAF of the REP-copy file)
 
 
 def run(tag, paths, fmt, out, reps=2):
@@ -105,6 +120,44 @@ def run(tag, paths, fmt, out, reps=2):
             st["n_output_bytes"] / 1e6), flush=True)
 
 
+def inflated_sha(p):
+    import hashlib
+    h = hashlib.sha256()
+    with gzip.open(p, "rb") as f:
+        for blk in iter(lambda: f.read(1 << 24), b""):
+            h.update(blk)
+    return h.hexdigest()
+
+
+if BGZF_ROUNDS:
+    os.environ["THM_BAM_DEVICE"] = "1"
+    os.environ["THM_FASTQ_DEVICE"] = "1"
+    run("warm-up: bam from two BGZF .gz, THM_BAM_DEVICE=1, THM_FASTQ_DEVICE=1", [gz, gz2], capi.FMT_BAM, "/tmp/thm_e2e_out.bam", 1)
+    outs, same = [], True
+    for k in range(BGZF_ROUNDS):
+        for dev in ("1", "2"):
+            os.environ["THM_BAM_DEVICE"] = dev
+            pair = []
+            for fq in ("1", "2"):
+                os.environ["THM_FASTQ_DEVICE"] = fq
+                out = "/tmp/thm_e2e_out.z%s%s.bam" % (dev, fq)
+                before = a.debug_fastq_bgzf_blocks()
+                run("bam from two BGZF .gz, THM_BAM_DEVICE=%s, THM_FASTQ_DEVICE=%s, round %d" % (dev, fq, k), [gz, gz2], capi.FMT_BAM, out, 1)
+                after = a.debug_fastq_bgzf_blocks()
+                if fq == "2":
+                    print("    groups inflated on the device %d, on the host %d; parsed on the device %d, on the host %d" % tuple(
+                        y - x for x, y in zip(before, after)), flush=True)
+                if k == 0:
+                    pair.append(inflated_sha(out))
+                outs.append(out)
+            same = same and (k > 0 or pair[0] == pair[1])
+    print("inflated BAM streams with THM_FASTQ_DEVICE 1 and 2 are %s" % ("IDENTICAL" if same else "DIFFERENT"), flush=True)
+    a.close()
+    for f in [path, big, gz, gz2, "/tmp/thm_e2e_out.bam"] + outs:
+        if os.path.exists(f):
+            os.remove(f)
+    assert same
+    sys.exit(0)
 if FQ_ROUNDS:
     os.environ["THM_BAM_DEVICE"] = "1"
     os.environ.pop("THM_FASTQ_DEVICE", None)

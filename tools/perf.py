@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Quick stage timing on the GPU box (tuning aid, not the benchmark):
-python tools/perf.py [ref_len] [n_reads] [opts] [--cigars] [--bam] [--bgzf] [--fastq]
+python tools/perf.py [ref_len] [n_reads] [opts] [--cigars] [--bam] [--bgzf] [--fastq] [--fastq-bgzf]
 --cigars: on the resident batch, thm_batch_fetch against thm_batch_fetch_cigars -- milliseconds and bytes moved to the
 host by each, and the device time of the two CIGAR passes (THM_T_CIGAR).
 --bam: on the resident batch, thm_batch_fetch_bam with both forms of the emit kernel (THM_BAM_EMIT) -- milliseconds,
@@ -10,7 +10,10 @@ at THM_BAM_LEVEL=0 minus thm_writer_wrap_bam of the same records: stored blocks,
 bytes, THM_T_BGZF -- beside thm_batch_fetch_bam plus thm_writer_wrap_bam of the same records on 16 threads and on 1, and
 the compressed sizes of the device encoder, the host encoder and zlib level 1 over the device's cuts.
 --fastq: the batch written out as one FASTQ block: thm_batch_upload_fastq -- milliseconds of the call and of its parse
-kernels (device_ms) -- beside thm_batch_upload_reads of the parsed batch, and the host's parse of the block on one thread."""
+kernels (device_ms) -- beside thm_batch_upload_reads of the parsed batch, and the host's parse of the block on one thread.
+--fastq-bgzf: the same block BGZF-framed with Python's zlib (level 6, members of 0xff00 bytes): thm_batch_upload_fastq_bgzf
+-- milliseconds of the call, of its inflate kernel (inflate_ms) and of its parse kernels (parse_ms) -- beside
+thm_batch_upload_fastq of the inflated bytes and zlib's inflate of the members on one host thread."""
 import sys, time
 import numpy as np
 sys.path.insert(0, __import__("os").path.dirname(__import__("os").path.dirname(__import__("os").path.abspath(__file__))))
@@ -20,7 +23,8 @@ cigars = "--cigars" in sys.argv
 bam = "--bam" in sys.argv
 bgzf = "--bgzf" in sys.argv
 fastq = "--fastq" in sys.argv
-sys.argv = [x for x in sys.argv if x not in ("--cigars", "--bam", "--bgzf", "--fastq")]
+fastq_bgzf = "--fastq-bgzf" in sys.argv
+sys.argv = [x for x in sys.argv if x not in ("--cigars", "--bam", "--bgzf", "--fastq", "--fastq-bgzf")]
 if bam:
     __import__("os").environ["THM_BAM_LEVEL"] = "0"  # (read once, by the first BGZF block of the process)
 ref_len = int(sys.argv[1]) if len(sys.argv) > 1 else 4000000
@@ -196,6 +200,47 @@ for name, opts in (("ci", capi.CI_OPTS), ("default", capi.DEFAULT_OPTS)):
             float(np.median(mf)), min(mf), max(mf), len(block), n, float(np.median(md)), min(md), max(md)), flush=True)
         print("         upload_reads median %.2f ms (min %.2f max %.2f)  %d bytes in five arrays; host cut + parse of the block, one thread, at most %.1f ms" % (
             float(np.median(mr)), min(mr), max(mr), sum(np.asarray(batch[k]).nbytes for k in batch), host_ms), flush=True)
+        b.close()
+    if fastq_bgzf:
+        import struct, zlib
+        K2 = 9
+        reads = bases.reshape(n, 91)
+        qual = b"F" * 91
+        block = b"".join(b"@SYN:%d 1:N:0:ACGT\n" % i + reads[i].tobytes() + b"\n+\n" + qual + b"\n" for i in range(n))
+        parts = []
+        for at in range(0, len(block), 0xff00):
+            piece = block[at: at + 0xff00]
+            c = zlib.compressobj(6, zlib.DEFLATED, -15)
+            z = c.compress(piece) + c.flush()
+            parts.append(b"\x1f\x8b\x08\x04\0\0\0\0\0\xff\x06\0BC\x02\0" + struct.pack("<H", len(z) + 25) + z +
+                         struct.pack("<II", zlib.crc32(piece), len(piece)))
+        members = b"".join(parts)
+        t0 = time.perf_counter()
+        for m in parts:
+            zlib.decompress(m, 31)
+        zlib_ms = (time.perf_counter() - t0) * 1e3
+        b = capi.Aligner(ix, opts)
+        src, msrc = np.frombuffer(block, np.uint8), np.frombuffer(members, np.uint8)
+        info, zinfo = capi.FastqUploadInfo(), capi.FastqBgzfInfo()
+
+        def up_fastq():
+            b._chk(capi.lib().thm_batch_upload_fastq(b.h, src.ctypes.data, len(block), b"perf", 1, 1, capi.C.byref(info)))
+
+        def up_bgzf():
+            b._chk(capi.lib().thm_batch_upload_fastq_bgzf(b.h, None, 0, msrc.ctypes.data, len(members), b"perf", 1, 1, capi.C.byref(zinfo)))
+
+        for _ in range(2):   # buffers grow
+            up_bgzf(); up_fastq()
+        mz, mf, mi, mp = [], [], [], []
+        for _ in range(K2):   # alternately, in one session
+            t0 = time.perf_counter(); up_bgzf(); mz.append((time.perf_counter() - t0) * 1e3); mi.append(zinfo.inflate_ms); mp.append(zinfo.parse_ms)
+            t0 = time.perf_counter(); up_fastq(); mf.append((time.perf_counter() - t0) * 1e3)
+        assert zinfo.inflated_on_device == 1 and zinfo.parsed_on_device == 1 and zinfo.n_reads == n and info.n_reads == n
+        print("         upload_fastq_bgzf median %.2f ms (min %.2f max %.2f)  %d members, %d -> %d bytes, %d reads  inflate_ms median %.3f (min %.3f max %.3f)  parse_ms median %.3f (min %.3f max %.3f)" % (
+            float(np.median(mz)), min(mz), max(mz), len(parts), len(members), len(block), n, float(np.median(mi)), min(mi), max(mi),
+            float(np.median(mp)), min(mp), max(mp)), flush=True)
+        print("         upload_fastq of the inflated bytes median %.2f ms (min %.2f max %.2f); zlib inflate of the members, one host thread, %.1f ms" % (
+            float(np.median(mf)), min(mf), max(mf), zlib_ms), flush=True)
         b.close()
     c = dict(zip(capi.COUNTER_NAMES, a.counters().tolist()))
     runs = K + 2
