@@ -207,6 +207,66 @@ typedef struct thm_fastq_bgzf_info {
 int32_t thm_batch_upload_fastq_bgzf(thm_aligner* a, const uint8_t* head, uint64_t head_len, const uint8_t* members, uint64_t n,
                                     const char* path, uint64_t first_line, int32_t last_block, thm_fastq_bgzf_info* info);
 
+/* ------------------------------------------------- plain gzip FASTQ inflated and parsed on the device */
+
+/* Where a gzip stream stands between two calls: caller-owned, plain data, all zero = the start of a file.  It moves
+ * between aligners as the tail does. */
+typedef struct thm_gzip_state {
+  uint8_t window[32768];  /* the last window_len inflated bytes of the member in progress */
+  uint32_t window_len;    /* min(member_len, 32768) while in_member, else 0 */
+  uint32_t bit_offset;    /* 0..7: bits of bytes[0] already consumed; 0 when in_member == 0 */
+  uint32_t in_member;     /* 1: `bytes` begins (bit_offset bits in) with a DEFLATE block header inside a member;
+                             0: `bytes` begins with a gzip member header (or is the end of the input) */
+  uint32_t crc;           /* CRC-32 of the member's bytes so far */
+  uint64_t member_len;    /* their count */
+  uint64_t n_members_done, stream_offset; /* members ended / compressed bytes consumed so far: they only word messages
+                             and tell the first member header of a file from what may follow its last member */
+} thm_gzip_state;
+
+typedef struct thm_fastq_gzip_info {
+  uint64_t n_reads, n_bases, n_name_bytes;
+  uint64_t n_lines;           /* as in thm_fastq_bgzf_info */
+  uint64_t n_inflated_bytes;
+  const uint8_t* tail;        /* the block's bytes behind the batch; valid until the next call of this function on `a` */
+  uint64_t tail_len;
+  uint32_t inflated_on_device, parsed_on_device;
+  float inflate_ms, parse_ms; /* HIP-event times; 0 where the host did the step */
+  uint64_t n_consumed_bytes;  /* the next call's `bytes` begins at bytes + n_consumed_bytes */
+  uint64_t n_chunks;          /* chunks of compressed bytes the device cut `bytes` into (0 where it was not asked) */
+  uint64_t n_starts;          /* ... and the block starts it decoded from, the one the state gives included */
+  uint32_t decline_reason;    /* 0, or the status word that sent the inflate to the host */
+  uint32_t reserved;
+} thm_fastq_gzip_info;
+
+/* thm_batch_upload_fastq_bgzf for ordinary gzip: `bytes` is any n bytes of a gzip stream (RFC 1952 members back to back,
+ * each one long DEFLATE stream) that begin where *st says, and need end nowhere in particular.
+ * Unit of consumption: the DEFLATE block.  The call consumes every block whose last bit lies inside bytes[0, n) -- a
+ * member's final block only together with the 8-byte trailer behind it, a member header only together with its member's
+ * first block -- so that between calls the stream stands at a block start inside a member or at a member boundary, which
+ * is what *st records.  info->n_consumed_bytes is the byte that holds the next block's first bit (st->bit_offset bits of
+ * it are consumed already); the caller presents the stream from there on next time.
+ * The block is head ++ the bytes the consumed blocks inflate to; batch, tail, n_lines and the parse step are exactly
+ * those of thm_batch_upload_fastq_bgzf for that block, the tail in the same two alternating buffers.
+ * A call in which no block ends: n_consumed_bytes == 0, a batch of 0 reads, the head comes back as the tail, *st is
+ * unchanged; the caller presents more bytes.
+ * last_block != 0: nothing of the input follows bytes[0, n).  Everything must then be consumed and the stream must stand
+ * at a member boundary (a stream cut short is the inflater's "truncated stream"); behind the last member may follow
+ * what GzInflater accepts there: nothing, or ten bytes or more that do not begin with the gzip magic.
+ * Every member's CRC-32 and ISIZE (mod 2^32) are checked, across calls through st->crc / st->member_len.
+ * On any error *st is unchanged.
+ * The device takes the clean case only (thermite_amd/csrc/gzip_device.h): at most 64 MiB of bytes; a stream in which
+ * every decode started at a block start it found ends exactly on the next (so every start was a true one); every such
+ * run inflating to at most 16 bytes per byte of its 32 KiB chunks (8 is always taken); at most 4 member ends per
+ * chunk; sound members.  Anything else -- a corrupt or odd stream, starts that do not meet, output over the room, more
+ * member ends -- declines the inflate as a whole (info->decline_reason) and GzInflater inflates the same bytes by the
+ * same rule of consumption: its bytes, or its THM_ERR_IO and message, are then the result.  A stream the device does
+ * not take only costs host time.
+ * THM_ERR_INVALID_ARG: null aligner, st or info, null bytes with n > 0, null head with head_len > 0, a state whose
+ * fields contradict each other. */
+int32_t thm_batch_upload_fastq_gzip(thm_aligner* a, thm_gzip_state* st, const uint8_t* head, uint64_t head_len,
+                                    const uint8_t* bytes, uint64_t n, const char* path, uint64_t first_line,
+                                    int32_t last_block, thm_fastq_gzip_info* info);
+
 /* The uploaded batch back on the host (names, bases as uploaded, qualities -- NULL for a batch uploaded without --, both
  * offset arrays), whichever upload placed it; the view is valid until the next call of this function on the aligner.
  * THM_ERR_INVALID_ARG: no batch with names is uploaded (plain thm_batch_upload carries none). */
@@ -285,7 +345,14 @@ typedef struct thm_run_stats {
  * about batch_reads reads (by the bytes per record of the batches so far, one member at least; a batch may hold more
  * reads than batch_reads) and every group goes to the device compressed (thm_batch_upload_fastq_bgzf), the tail of one
  * batch being the head of the next, across aligners in input order.  The file's inflated bytes are the same; batch
- * boundaries, and with THM_BAM_DEVICE=2 the compressed bytes, may differ.  Every other file takes the path of =1. */
+ * boundaries, and with THM_BAM_DEVICE=2 the compressed bytes, may differ.  Every other file takes the path of =1.
+ * THM_FASTQ_DEVICE=3, in the same two modes: as =2 (files that are BGZF throughout keep that path), and a gzip file that
+ * is not BGZF throughout gets no inflater thread either, provided its first bytes, inflated on the host, begin with '@':
+ * it is mapped and goes to the device in slices (thm_batch_upload_fastq_gzip), sized from the bytes per record and the
+ * compression ratio of the batches so far, each beginning at the last one's n_consumed_bytes, doubled while nothing of
+ * one is consumed, last_block set on the slice that reaches the end of the file; state and tail pass along the same
+ * in-order chain of uploads and are reset per file.  The file's inflated bytes are those of the unset run; batch
+ * boundaries may differ.  FASTA and input that is not gzip keep the path of =1. */
 int32_t thm_align_files(thm_aligner* a, const char* const* fastq_paths, uint32_t n_paths, const char* output_path,
                         int32_t format, uint64_t batch_reads, uint32_t n_threads, thm_run_stats* stats);
 /* The same over several aligners -- one per GPU of the node, all over one index (the shape of ThermiteAligner: Clone +

@@ -158,6 +158,33 @@ class FastqBgzfInfo(C.Structure):
                 ("parse_ms", C.c_float)]
 
 
+class GzipState(C.Structure):
+    """thm_gzip_state (include/thermite_io.h): all zero = the start of a file"""
+
+    _fields_ = [("window", C.c_uint8 * 32768), ("window_len", C.c_uint32), ("bit_offset", C.c_uint32), ("in_member", C.c_uint32),
+                ("crc", C.c_uint32), ("member_len", C.c_uint64), ("n_members_done", C.c_uint64), ("stream_offset", C.c_uint64)]
+
+    def key(self):
+        """the fields that say where the stream stands, the window cut to its length"""
+        return (bytes(self.window[: self.window_len]), self.window_len, self.bit_offset, self.in_member, self.crc, self.member_len,
+                self.n_members_done, self.stream_offset)
+
+    def copy(self):
+        out = GzipState()
+        C.memmove(C.byref(out), C.byref(self), C.sizeof(GzipState))
+        return out
+
+
+class FastqGzipInfo(C.Structure):
+    """thm_fastq_gzip_info (include/thermite_io.h)"""
+
+    _fields_ = [("n_reads", C.c_uint64), ("n_bases", C.c_uint64), ("n_name_bytes", C.c_uint64), ("n_lines", C.c_uint64),
+                ("n_inflated_bytes", C.c_uint64), ("tail", C.c_void_p), ("tail_len", C.c_uint64),
+                ("inflated_on_device", C.c_uint32), ("parsed_on_device", C.c_uint32), ("inflate_ms", C.c_float),
+                ("parse_ms", C.c_float), ("n_consumed_bytes", C.c_uint64), ("n_chunks", C.c_uint64), ("n_starts", C.c_uint64),
+                ("decline_reason", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 BAM_NO_ANNOTATION_TAGS = 1
 
 # every symbol include/thermite.h declares
@@ -183,6 +210,7 @@ IO_ABI_SYMBOLS = [
     "thm_batch_fetch_bgzf", "thm_align_batch_bgzf",
     "thm_batch_upload_fastq", "thm_batch_fetch_reads",
     "thm_batch_upload_fastq_bgzf",
+    "thm_batch_upload_fastq_gzip",
 ]
 ERR_IO, ERR_FORMAT = -8, -9
 FMT_PAF, FMT_SAM, FMT_BAM = 0, 1, 2
@@ -342,6 +370,14 @@ def lib():
     L.thm_debug_bgzf_inflate.argtypes = [vp, vp, u64, vp, u64, vp]
     L.thm_debug_fastq_bgzf_blocks.restype = i32
     L.thm_debug_fastq_bgzf_blocks.argtypes = [vp, vp]
+    L.thm_batch_upload_fastq_gzip.restype = i32
+    L.thm_batch_upload_fastq_gzip.argtypes = [vp, vp, vp, u64, vp, u64, cp, u64, i32, vp]
+    L.thm_debug_gzip_inflate.restype = i32
+    L.thm_debug_gzip_inflate.argtypes = [vp, vp, vp, u64, u32, i32, vp, u64, vp, vp, vp]
+    L.thm_debug_fastq_gzip_blocks.restype = i32
+    L.thm_debug_fastq_gzip_blocks.argtypes = [vp, vp]
+    L.thm_debug_gzip_host_slice.restype = i32
+    L.thm_debug_gzip_host_slice.argtypes = [vp, vp, u64, i32, vp, u64, vp, vp]
     L.thm_writer_wrap_bam.restype = i32
     L.thm_writer_wrap_bam.argtypes = [vp, vp, vp]
     L.thm_align_files.restype = i32
@@ -833,6 +869,36 @@ class Aligner:
         out["tail"] = C.string_at(info.tail, info.tail_len) if info.tail_len else b""
         return out
 
+    def upload_fastq_gzip(self, state, data, head=b"", path=b"", first_line=1, last_block=True):
+        """thm_batch_upload_fastq_gzip: `data`, bytes of a gzip stream that begin where `state` (a GzipState, moved on in
+        place) says -> the info as a dict, `tail` as bytes"""
+        m = np.frombuffer(bytes(data), np.uint8) if len(data) else None
+        h = np.frombuffer(bytes(head), np.uint8) if len(head) else None
+        info = FastqGzipInfo()
+        self._chk(lib().thm_batch_upload_fastq_gzip(self.h, C.byref(state), _ptr(h), len(head), _ptr(m), len(data), os.fsencode(path),
+                                                    first_line, int(bool(last_block)), C.byref(info)))
+        out = {k: getattr(info, k) for k, _ in FastqGzipInfo._fields_}
+        out["tail"] = C.string_at(info.tail, info.tail_len) if info.tail_len else b""
+        return out
+
+    def debug_gzip_inflate(self, state, data, chunk_bytes=0, last_block=True, cap=None):
+        """test hook: bytes of a gzip stream through the device inflater alone (no host inflater behind it), in chunks
+        of chunk_bytes (0: the default) -> (the inflated bytes, n_consumed, (n_chunks, n_starts, refused starts, path
+        flags)); `state` moves on in place; a stream the device declines raises"""
+        src = np.frombuffer(bytes(data), np.uint8) if len(data) else np.zeros(1, np.uint8)
+        out = np.empty((16 * len(data) + 65536 if cap is None else cap) + 64, np.uint8)
+        n, used = C.c_uint64(0), C.c_uint64(0)
+        counts = (C.c_uint64 * 4)()
+        self._chk(lib().thm_debug_gzip_inflate(self.h, C.byref(state), src.ctypes.data, len(data), chunk_bytes, int(bool(last_block)),
+                                               out.ctypes.data, len(out), C.byref(n), C.byref(used), counts))
+        return out[: n.value].tobytes(), used.value, tuple(int(x) for x in counts)
+
+    def debug_fastq_gzip_blocks(self):
+        """test hook: what upload_fastq_gzip did so far: (inflates on the device, on the host, parses on the device, on the host)"""
+        c = (C.c_uint64 * 4)()
+        self._chk(lib().thm_debug_fastq_gzip_blocks(self.h, c))
+        return tuple(int(x) for x in c)
+
     def debug_bgzf_inflate(self, members, cap=None):
         """test hook: gzip members through the device inflater alone (no host inflater behind it) -> the inflated bytes;
         a chain the device does not take, or a member it declines, raises"""
@@ -1216,3 +1282,16 @@ def align_files(aligner, fastq_paths, output_path, fmt=FMT_SAM, batch_reads=0, n
     if rc != 0:
         raise ThermiteError(rc, _last_error())
     return {k: getattr(st, k) for k, _ in RunStats._fields_}
+
+
+def debug_gzip_host_slice(state, data, last_block=True, cap=None):
+    """test hook: the host side of upload_fastq_gzip's inflate (GzInflater's resume entry), no aligner needed -> (the
+    inflated bytes of the blocks that end inside `data`, n_consumed); `state` moves on in place"""
+    src = np.frombuffer(bytes(data), np.uint8) if len(data) else np.zeros(1, np.uint8)
+    out = np.empty((1100 * len(data) + 65536 if cap is None else cap) + 64, np.uint8)
+    n, used = C.c_uint64(0), C.c_uint64(0)
+    rc = lib().thm_debug_gzip_host_slice(C.byref(state), src.ctypes.data, len(data), int(bool(last_block)), out.ctypes.data, len(out),
+                                         C.byref(n), C.byref(used))
+    if rc != 0:
+        raise ThermiteError(rc, (lib().thm_last_error(None) or b"").decode(errors="replace"))
+    return out[: n.value].tobytes(), used.value

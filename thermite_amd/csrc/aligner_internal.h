@@ -310,6 +310,15 @@ struct thm_aligner {
   std::vector<uint8_t> fz_block;
   uint64_t fz_counts[4] = {0, 0, 0, 0};
   Event ev_fz[2];  // made by the first call
+  // plain gzip inflated on the device (gzip.hip; the arrays of gz::Job, gzip_device.h): the compressed bytes, both
+  // states, candidates, runs, member ends, symbol regions, windows and what the chain derives; summary and outgoing
+  // state in pinned memory too.  The inflated block is built in fq_raw and the tail buffers are fz_tail.  Counts for
+  // thm_debug_fastq_gzip_blocks, as fz_counts.
+  DBuf gz_in, gz_state, gz_cand, gz_runs, gz_ends, gz_syms, gz_windows, gz_run_list, gz_run_off, gz_end_abs, gz_end_crc, gz_end_isize,
+      gz_member_crc, gz_sum;
+  HBuf gz_h_sum, gz_h_state;
+  uint64_t gz_counts[4] = {0, 0, 0, 0};
+  Event ev_gz[2];  // made by the first call
 };
 
 inline int fail(thm_aligner* a, int code, const char* fmt, ...) {

@@ -91,8 +91,10 @@ int inflate_on_host(thm_aligner* a, const uint8_t* head, uint64_t head_len, cons
   return rc;
 }
 
+}  // namespace
+
 // where the batch of a block that is not the last ends: behind its first 4 * (newlines / 4) lines; *n_lines: those
-uint64_t host_cut(const uint8_t* blk, uint64_t n, uint64_t* n_lines) {
+uint64_t thm::fastq_host_cut(const uint8_t* blk, uint64_t n, uint64_t* n_lines) {
   uint64_t nl = 0;
   for (const uint8_t* q = blk; (q = (const uint8_t*)memchr(q, '\n', (size_t)(blk + n - q))) != nullptr; q++) nl++;
   const uint64_t want = 4 * (nl / 4);
@@ -107,14 +109,12 @@ uint64_t host_cut(const uint8_t* blk, uint64_t n, uint64_t* n_lines) {
   return (uint64_t)(q - blk);
 }
 
-}  // namespace
-
 int thm::bgzf_block_on_host(const uint8_t* head, uint64_t head_len, const uint8_t* members, uint64_t n, const std::string& path,
                             bool last_block, std::vector<uint8_t>& block, uint64_t* cut, std::string& err) {
   const int rc = inflate_to(block, head, head_len, members, n, path, err);
   if (rc != THM_OK) return rc;
   uint64_t n_lines = 0;
-  *cut = last_block || block.empty() ? block.size() : host_cut(block.data(), block.size(), &n_lines);
+  *cut = last_block || block.empty() ? block.size() : fastq_host_cut(block.data(), block.size(), &n_lines);
   return THM_OK;
 }
 
@@ -219,7 +219,7 @@ int32_t thm_batch_upload_fastq_bgzf(thm_aligner* a, const uint8_t* head, uint64_
   // ---- the host parser's batch of the batch bytes, or its error with its message (a batch without a record included:
   // nothing is counted as parsed then)
   uint64_t cut = blk_n, n_lines = 0;
-  if (!last_block) cut = blk_n ? host_cut(host_blk, blk_n, &n_lines) : 0;
+  if (!last_block) cut = blk_n ? fastq_host_cut(host_blk, blk_n, &n_lines) : 0;
   if (cut) a->fz_counts[3]++;
   HostBatch hb;
   std::string err;

@@ -10,6 +10,9 @@
 //             member chain over the mapping and cuts it into groups of whole members, which go to the device
 //             compressed (thm_batch_upload_fastq_bgzf); the tail of one batch is the head of the next, so the uploads
 //             of such a run are chained in input order across the GPU threads (runs and fetches still overlap)
+//             THM_FASTQ_DEVICE=3: ... and an ordinary .fastq.gz is not inflated here either -- it is mapped and goes to the
+//             device in slices (thm_batch_upload_fastq_gzip), each beginning where the last one's blocks ended; that
+//             is known at the slice's turn in the same chain only, so the cutter cuts such a file one slot at a time
 //     GPU     one thread per aligner (= per GPU): upload, run, sync, fetch
 //     write   one thread: batches in input order -> formatting threads -> pwrite
 // connected by queues over a fixed set of reusable slots, so that the host work either
@@ -56,6 +59,9 @@ struct Slot {
   bool zmembers = false;    // raw_ptr / raw_len are whole BGZF members of the mapped input (THM_FASTQ_DEVICE=2) ...
   bool file_first = false;  // ... the first group of its file: the chain of tails starts empty, at line 1
   std::vector<uint8_t> head;  // ... and the head it went up with (kept for the failed-read message)
+  bool gzslice = false;     // a slice of the mapped plain-gzip input gz_map[0, gz_len) (THM_FASTQ_DEVICE=3): where it begins and
+  const uint8_t* gz_map = nullptr;  // how long it is, is known at its turn in the chain of uploads only (file_first as above)
+  size_t gz_len = 0;
   bool parsed = false;  // `reads` already holds the batch (sequential parser: FASTA, odd inputs)
   thm::HostBatch reads;
   thm_batch_view res;  // into the pinned result buffers of the aligner that ran it (two sets per aligner, used alternately)
@@ -257,6 +263,57 @@ struct BgzfFile {
   }
 };
 
+// A gzip input that is not BGZF throughout (THM_FASTQ_DEVICE=3): the mapping.  Eligible: gzip magic, and the first
+// bytes, inflated on the host, beginning with '@' (FASTA and anything else keep the inflater thread and its parser).
+struct GzipFile {
+  const uint8_t* map = nullptr;
+  size_t len = 0;
+  double bytes_per_read = 256, ratio = 4;  // of the first blocks' text
+  bool ok = false;
+  GzipFile() = default;
+  GzipFile(const GzipFile&) = delete;
+  GzipFile& operator=(const GzipFile&) = delete;
+  ~GzipFile() {
+    if (map) munmap((void*)map, len);  // (a file the run did not get to; otherwise the mapping was handed on)
+  }
+  void open(const char* path) {
+    const int fd = ::open(path, O_RDONLY);
+    if (fd < 0) return;
+    struct stat st;
+    if (fstat(fd, &st) == 0 && S_ISREG(st.st_mode) && st.st_size >= 18) {
+      void* m = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
+      if (m != MAP_FAILED) {
+        map = (const uint8_t*)m;
+        len = (size_t)st.st_size;
+      }
+    }
+    close(fd);
+    if (!map) return;
+    // the first blocks that end inside 64 KiB, or inside 1 MiB
+    for (size_t take = 65536; !ok; take *= 16) {
+      const size_t n = std::min(take, len);
+      std::unique_ptr<thm_gzip_state> zs(new thm_gzip_state());
+      std::vector<uint8_t> first;
+      std::string err;
+      uint64_t used = 0;
+      if (thm::GzInflater::inflate_slice(zs.get(), map, n, path, n == len, first, &used, err) != THM_OK) break;
+      if (!first.empty()) {
+        if (first[0] != '@') break;
+        size_t nl = 0;
+        for (uint8_t c : first) nl += c == '\n';
+        if (nl >= 4) bytes_per_read = (double)first.size() / (double)(nl / 4);
+        if (used) ratio = std::max(1.0, (double)first.size() / (double)used);
+        ok = true;
+      }
+      if (n == len || take >= (1u << 20)) break;
+    }
+    if (!ok) {
+      munmap((void*)map, len);
+      map = nullptr;
+    }
+  }
+};
+
 struct Shared {
   std::mutex mu;
   int rc = THM_OK;
@@ -314,7 +371,10 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
   const char* fq_dev_env = getenv("THM_FASTQ_DEVICE");
   // THM_FASTQ_DEVICE=2: as =1, and input files that are BGZF throughout go to the device compressed
   // (thm_batch_upload_fastq_bgzf); every other file takes the path of =1
-  const bool fastq_bgzf = bam_device && fq_dev_env && !strcmp(fq_dev_env, "2");
+  // THM_FASTQ_DEVICE=3: as =2, and gzip files that are not BGZF throughout go to the device compressed too, in slices
+  // (thm_batch_upload_fastq_gzip)
+  const bool fastq_gzip = bam_device && fq_dev_env && !strcmp(fq_dev_env, "3");
+  const bool fastq_bgzf = fastq_gzip || (bam_device && fq_dev_env && !strcmp(fq_dev_env, "2"));
   const bool fastq_device = fastq_bgzf || (bam_device && fq_dev_env && !strcmp(fq_dev_env, "1"));
   const thm_index* ix = thm_aligner_index(aligners[0]);
   for (uint32_t i = 1; i < n_aligners; i++)
@@ -387,6 +447,11 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
   std::vector<uint8_t> ch_tail;
   uint64_t ch_line = 1;
   std::atomic<uint64_t> est_bytes{0}, est_reads{0};
+  // THM_FASTQ_DEVICE=3: where the plain-gzip file of the turn stands (the holder of the turn alone touches them), and
+  // what the cutter waits for before it cuts the next slot of that file: the upload that tells whether there is one
+  std::unique_ptr<thm_gzip_state> gz_state(new thm_gzip_state());
+  uint64_t gz_pos = 0, gz_in = 0, gz_out = 0;  // the position in the file; compressed and inflated bytes so far, for the ratio
+  bool gz_file_done = false;                   // (guarded by ch_mu)
   std::vector<std::pair<const char*, size_t>> maps;
   // ---- stage 1: cut the input into blocks of whole records ----
   std::thread cutter([&] {
@@ -395,6 +460,7 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
     std::vector<std::unique_ptr<Ahead>> ahead(n_paths);
     std::vector<char> is_gz(n_paths, 0);
     std::vector<std::unique_ptr<BgzfFile>> bgzf_files(n_paths);
+    std::vector<std::unique_ptr<GzipFile>> gzip_files(n_paths);
     unsigned n_gz = 0;
     for (uint32_t pi = 0; pi < n_paths; pi++) {
       unsigned char magic[2] = {0, 0};
@@ -411,6 +477,13 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
           if (bf->ok) {
             bgzf_files[pi] = std::move(bf);
             is_gz[pi] = 0;
+          } else if (fastq_gzip) {  // ... or in slices, wherever its blocks end
+            std::unique_ptr<GzipFile> gf(new GzipFile());
+            gf->open(fastq_paths[pi]);
+            if (gf->ok) {
+              gzip_files[pi] = std::move(gf);
+              is_gz[pi] = 0;
+            }
           }
           return THM_OK;
         });
@@ -458,6 +531,7 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
           s->parsed = false;
           s->aligned = false;
           s->zmembers = true;
+          s->gzslice = false;
           s->file_first = k == 0;
           s->path = fastq_paths[pi];
           s->raw_ptr = (const char*)bf.map + bf.at[k];
@@ -469,6 +543,38 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
         }
         maps.emplace_back((const char*)bf.map, bf.len);  // unmapped when every batch has been written
         bf.map = nullptr;
+        continue;
+      }
+      if (gzip_files[pi]) {
+        // one slot after the other: where a slice begins is known once the one before has gone up
+        GzipFile& gf = *gzip_files[pi];
+        for (bool first = true, more = true; more && !sh.failed(); first = false) {
+          Slot* s = q_free.pop();
+          s->seq = seq++;
+          s->parsed = false;
+          s->aligned = false;
+          s->zmembers = false;
+          s->gzslice = true;
+          s->file_first = first;
+          s->path = fastq_paths[pi];
+          s->gz_map = gf.map;
+          s->gz_len = gf.len;
+          s->raw_ptr = nullptr;
+          s->raw_len = 0;
+          s->last_block = false;
+          s->first_line = 0;
+          if (first) {
+            std::lock_guard<std::mutex> g(ch_mu);
+            gz_file_done = false;
+          }
+          const uint64_t mine = s->seq;
+          q_raw.push(s);
+          std::unique_lock<std::mutex> g(ch_mu);
+          ch_cv.wait(g, [&] { return ch_turn > mine; });
+          more = !gz_file_done;
+        }
+        maps.emplace_back((const char*)gf.map, gf.len);  // unmapped when every batch has been written
+        gf.map = nullptr;
         continue;
       }
       if (is_gz[pi]) {
@@ -517,6 +623,7 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
         s->seq = seq;
         s->parsed = false;
         s->zmembers = false;
+        s->gzslice = false;
         s->aligned = false;
         s->path = fastq_paths[pi];
         const auto t0 = Clock::now();
@@ -687,6 +794,52 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
             if (up_rc == THM_OK && zi.n_reads == 0) have = false;  // (a group without a whole record: all of it is tail)
           }
         }
+        if (s->gzslice) {
+          if (s->file_first) {
+            ch_tail.clear();
+            ch_line = 1;
+            memset(gz_state.get(), 0, sizeof(thm_gzip_state));
+            gz_pos = gz_in = gz_out = 0;
+          }
+          s->first_line = ch_line;
+          bool file_done = !have;  // (a run that has failed cuts no further slot)
+          if (have) {
+            thm_fastq_gzip_info zi;
+            memset(&zi, 0, sizeof zi);
+            // a slice of about batch_reads reads, by the bytes per record and the ratio of the batches so far; doubled
+            // while no block ends inside it
+            const uint64_t eb = est_bytes.load(), er = est_reads.load();
+            const double per = er >= 64 ? (double)eb / (double)er : 256.0;
+            const double ratio = gz_in >= 65536 ? std::max(1.0, (double)gz_out / (double)gz_in) : 4.0;
+            uint64_t want = (uint64_t)(per * (double)batch_reads / ratio) + 4096;
+            up_rc = sh.step([&] {
+              s->head = ch_tail;
+              for (;;) {
+                const uint64_t left = s->gz_len - gz_pos, n = std::min<uint64_t>(want, left);
+                s->last_block = n == left;
+                const int r2 = (int)thm_batch_upload_fastq_gzip(a, gz_state.get(), s->head.data(), s->head.size(), s->gz_map + gz_pos, n,
+                                                                s->path.c_str(), s->first_line, s->last_block ? 1 : 0, &zi);
+                if (r2 != THM_OK) return r2;
+                if (zi.n_consumed_bytes == 0 && !s->last_block) {
+                  want = 2 * n;
+                  continue;
+                }
+                gz_pos += zi.n_consumed_bytes;
+                gz_in += zi.n_consumed_bytes;
+                gz_out += zi.n_inflated_bytes;
+                ch_tail.assign(zi.tail, zi.tail + zi.tail_len);
+                ch_line += zi.n_lines;
+                est_bytes += s->head.size() + zi.n_inflated_bytes - zi.tail_len;
+                est_reads += zi.n_reads;
+                return (int)THM_OK;
+              }
+            });
+            file_done = up_rc != THM_OK || s->last_block;
+            if (up_rc == THM_OK && zi.n_reads == 0) have = false;  // (a slice without a whole record: all of it is tail)
+          }
+          std::lock_guard<std::mutex> g(ch_mu);
+          gz_file_done = file_done;
+        }
         if (fastq_bgzf) {
           {
             std::lock_guard<std::mutex> g(ch_mu);
@@ -694,7 +847,7 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
           }
           ch_cv.notify_all();
         }
-        if (have && raw_up && !s->zmembers) {
+        if (have && raw_up && !s->zmembers && !s->gzslice) {
           thm_fastq_upload_info fi;
           memset(&fi, 0, sizeof fi);
           up_rc = sh.step([&] {
@@ -728,7 +881,11 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
             // the reference aligns every read or panics; a read this build cannot take fails the run, by name
             uint64_t bad = 0;
             while (bad < n_res && res_status[bad] == THM_OK) bad++;
-            if (raw_up && s->zmembers) {  // ... inflate and parse that one block here, for the one message
+            thm_read_batch up;  // (the batch as it stands on the device: the host has not seen a byte of a gzip slice)
+            memset(&up, 0, sizeof up);
+            if (raw_up && s->gzslice) {
+              (void)sh.step([&] { return (int)thm_batch_fetch_reads(a, &up); });
+            } else if (raw_up && s->zmembers) {  // ... inflate and parse that one block here, for the one message
               std::string perr;
               (void)sh.step([&] {
                 std::vector<uint8_t> blk;
@@ -741,7 +898,7 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
               std::string perr;
               (void)sh.step([&] { return thm::fastq_parse_block(s->raw_ptr, s->raw_len, s->path, s->first_line, s->last_block, s->reads, perr); });
             }
-            const thm_read_batch v = s->reads.view();
+            const thm_read_batch v = raw_up && s->gzslice ? up : s->reads.view();
             std::string name;
             if (bad < v.n_reads) name.assign((const char*)v.names + v.name_off[bad], (size_t)(v.name_off[bad + 1] - v.name_off[bad]));
             sh.set(res_status[bad], "read " + name + (res_status[bad] == THM_ERR_UNSUPPORTED

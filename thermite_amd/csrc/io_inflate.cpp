@@ -259,6 +259,9 @@ struct GzInflater::Impl {
   bool strict = false;          // block search: only complete Huffman codes pass
   size_t ipos = 0, iend = 0;
   bool in_eof = false;
+  bool stop_at_unit = false;    // inflate_slice: serial_read returns where a unit of consumption ends (unit_end set)
+  bool unit_end = false;
+  bool truncated = false;       // the error is "truncated stream"
   uint64_t bitbuf = 0;
   int bitcnt = 0;
   enum State { MEMBER_HEADER, BLOCK_HEADER, STORED, HUFFMAN, TRAILER, END } state = MEMBER_HEADER;
@@ -313,6 +316,7 @@ struct GzInflater::Impl {
     return iend - ipos >= n;
   }
   bool fail(const char* what) {
+    if (!strcmp(what, "truncated stream")) truncated = true;
     if (quiet) {
       if (err.empty()) err = "x";
       return false;
@@ -677,6 +681,7 @@ long GzInflater::serial_read(Impl& s, uint8_t* dst, size_t cap, size_t history) 
   };
   bool ok = true;
   while (ok && s.state != Impl::END && out < out_end - Impl::OUT_SLACK) {
+    const Impl::State was = s.state;
     switch (s.state) {
       case Impl::MEMBER_HEADER:
         ok = s.member_header();
@@ -733,6 +738,12 @@ long GzInflater::serial_read(Impl& s, uint8_t* dst, size_t cap, size_t history) 
       }
       case Impl::END:
         break;
+    }
+    // a block that is not its member's last has ended, or a member with its trailer
+    if (s.stop_at_unit && ok && s.err.empty() &&
+        (((was == Impl::STORED || was == Impl::HUFFMAN) && s.state == Impl::BLOCK_HEADER) || (was == Impl::TRAILER && s.state == Impl::MEMBER_HEADER))) {
+      s.unit_end = true;
+      break;
     }
   }
   if (!ok || !s.err.empty()) {
@@ -1263,6 +1274,108 @@ void GzInflater::open_memory(const uint8_t* data, size_t n, const std::string& p
   p_->open_memory(p_->inbuf.data(), n, path);
 }
 
+void GzInflater::open_memory_at(const uint8_t* data, size_t n, const std::string& path, uint32_t bit_offset, bool in_member,
+                                const uint8_t* /*window: the caller places it before read()'s dst*/, uint32_t crc, uint64_t member_len,
+                                uint64_t n_members_done) {
+  open_memory(data, n, path);
+  Impl& s = *p_;
+  s.n_members = n_members_done + (in_member ? 1 : 0);
+  if (in_member && n) {
+    s.set_bit_position(bit_offset & 7u);
+    s.state = Impl::BLOCK_HEADER;
+    s.crc = crc;
+    s.member_out = member_len;
+  }
+}
+
+int GzInflater::inflate_slice(thm_gzip_state* st, const uint8_t* data, size_t n, const std::string& path, bool last_block,
+                              std::vector<uint8_t>& out, uint64_t* n_consumed, std::string& err) {
+  *n_consumed = 0;
+  const bool in_member = st->in_member != 0;
+  if (st->bit_offset > 7 || st->window_len > WINDOW || (!in_member && st->bit_offset) ||
+      (in_member && st->window_len != std::min<uint64_t>(st->member_len, WINDOW))) {
+    err = "gzip read error in " + path + ": not a state of this stream";
+    return THM_ERR_INVALID_ARG;
+  }
+  if (n == 0) {
+    if (last_block && in_member) {
+      err = "gzip read error in " + path + ": truncated stream";
+      return THM_ERR_IO;
+    }
+    return THM_OK;
+  }
+  GzInflater z;
+  z.open_memory_at(data, n, path, st->bit_offset, in_member, st->window, st->crc, st->member_len, st->n_members_done);
+  Impl& s = *z.p_;
+  s.stop_at_unit = true;
+  constexpr size_t STEP = 1u << 20;
+  std::vector<uint8_t> buf(WINDOW + STEP), got;
+  size_t hist = in_member ? st->window_len : 0;
+  memcpy(buf.data() + WINDOW - hist, st->window, hist);
+  // where the last unit ended
+  struct {
+    size_t n_out;
+    uint64_t bit, member_len, n_members;
+    bool in_member;
+    uint32_t crc;
+  } ck = {0, st->bit_offset, st->member_len, s.n_members, in_member, st->crc};
+  bool at_end = false;
+  for (;;) {
+    const long k = serial_read(s, buf.data() + WINDOW, STEP, hist);
+    if (k > 0) {
+      got.insert(got.end(), buf.data() + WINDOW, buf.data() + WINDOW + k);
+      const size_t keep = std::min(hist + (size_t)k, WINDOW);
+      memmove(buf.data() + WINDOW - keep, buf.data() + WINDOW + (size_t)k - keep, keep);
+      hist = keep;
+    }
+    if (!s.err.empty()) {
+      // bytes that are not the input's last end somewhere: what they cut off is no error, and neither is a verdict
+      // reached within the decoder's read-ahead of their end
+      if (!last_block && (s.truncated || s.bit_position() + 64 > 8 * (uint64_t)n)) break;
+      err = s.err;
+      return THM_ERR_IO;
+    }
+    if (s.unit_end) {
+      s.unit_end = false;
+      // (zeros stand behind the bytes, and seven of them are the end-of-block code of a fixed block)
+      if (s.bit_position() > 8 * (uint64_t)n) {
+        if (!last_block) break;
+        err = "gzip read error in " + path + ": truncated stream";
+        return THM_ERR_IO;
+      }
+      ck = {got.size(), s.bit_position(), s.member_out, s.n_members, s.state == Impl::BLOCK_HEADER, s.crc};
+    }
+    if (s.state == Impl::END) {
+      at_end = true;
+      ck = {got.size(), 8 * (uint64_t)n, 0, s.n_members, false, 0};
+      break;
+    }
+  }
+  (void)at_end;
+  // the window of the member in progress: the last bytes of the old window ++ the new bytes
+  if (ck.in_member) {
+    const size_t wl = (size_t)std::min<uint64_t>(ck.member_len, WINDOW);
+    std::vector<uint8_t> w(wl);
+    for (size_t t = 0; t < wl; t++) {
+      const size_t back = wl - 1 - t;
+      w[t] = back < ck.n_out ? got[ck.n_out - 1 - back] : st->window[st->window_len - 1 - (back - ck.n_out)];
+    }
+    memcpy(st->window, w.data(), wl);
+    st->window_len = (uint32_t)wl;
+    st->crc = ck.crc;
+    st->member_len = ck.member_len;
+    st->bit_offset = (uint32_t)(ck.bit & 7u);
+  } else {
+    st->window_len = 0, st->crc = 0, st->member_len = 0, st->bit_offset = 0;
+  }
+  st->in_member = ck.in_member ? 1 : 0;
+  st->n_members_done = ck.n_members - (ck.in_member ? 1 : 0);
+  *n_consumed = ck.bit >> 3;
+  st->stream_offset += *n_consumed;
+  out.insert(out.end(), got.begin(), got.begin() + ck.n_out);
+  return THM_OK;
+}
+
 long GzInflater::par_read(uint8_t* dst, size_t cap) {
   Par& P = *par_;
   Impl& s = *p_;  // (only its error string is used here)
@@ -1385,6 +1498,29 @@ long GzInflater::par_read(uint8_t* dst, size_t cap) {
 }
 
 }  // namespace thm
+
+// test hook: GzInflater::inflate_slice, the host side of thm_batch_upload_fastq_gzip's inflate, without an aligner
+extern "C" int32_t thm_debug_gzip_host_slice(thm_gzip_state* st, const uint8_t* bytes, uint64_t n, int32_t last_block, uint8_t* out,
+                                             uint64_t cap, uint64_t* n_out, uint64_t* n_consumed) {
+  if (!st || (!bytes && n) || !out || !n_out || !n_consumed) return THM_ERR_INVALID_ARG;
+  *n_out = 0;
+  std::vector<uint8_t> got;
+  std::string err;
+  std::unique_ptr<thm_gzip_state> next(new thm_gzip_state(*st));
+  const int rc = thm::GzInflater::inflate_slice(next.get(), bytes, (size_t)n, "<memory>", last_block != 0, got, n_consumed, err);
+  if (rc != THM_OK) {
+    thm::set_global_error(err);
+    return rc;
+  }
+  if (got.size() > cap) {
+    thm::set_global_error("thm_debug_gzip_host_slice: output buffer too small");
+    return THM_ERR_INVALID_ARG;
+  }
+  if (!got.empty()) memcpy(out, got.data(), got.size());
+  *n_out = got.size();
+  *st = *next;
+  return THM_OK;
+}
 
 // test hook: the whole gzip file through GzInflater in calls of `chunk` bytes (so that matches, stored blocks and
 // members straddle calls); *n_out bytes land in out[0, cap).  THM_ERR_IO with the inflater's message on a bad stream.

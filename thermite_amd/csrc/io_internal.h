@@ -71,6 +71,16 @@ class GzInflater {
   // (min(bytes so far, 32768) of them: matches reach back there).  0: end of the input; -1: error().
   long read(uint8_t* dst, size_t cap, size_t history);
   const std::string& error() const;
+  // A memory source that begins inside a stream: at a block header `bit_offset` bits into data[0], inside a member of
+  // which member_len bytes with the CRC-32 `crc` are out already (in_member), or at a member header at data[0];
+  // n_members_done members came before.  The first read()'s dst[-history, 0) holds the window.
+  void open_memory_at(const uint8_t* data, size_t n, const std::string& path, uint32_t bit_offset, bool in_member, const uint8_t* window,
+                      uint32_t crc, uint64_t member_len, uint64_t n_members_done);
+  // The host side of thm_batch_upload_fastq_gzip's inflate (include/thermite_io.h has the rule of consumption): the
+  // bytes of every unit that ends inside data[0, n) appended to `out`, *st moved on, *n_consumed set.  THM_ERR_IO with
+  // the inflater's message in `err` (THM_ERR_INVALID_ARG for a state that is none); *st and `out` are then unchanged.
+  static int inflate_slice(thm_gzip_state* st, const uint8_t* data, size_t n, const std::string& path, bool last_block,
+                           std::vector<uint8_t>& out, uint64_t* n_consumed, std::string& err);
 
  private:
   struct Impl;
@@ -107,6 +117,9 @@ int batch_fetch_bgzf(thm_aligner* a, uint32_t flags, thm_bgzf_view* out, uint64_
 // *cut: bytes of the batch thm_batch_upload_fastq_bgzf takes of it (all of it for a last block)
 int bgzf_block_on_host(const uint8_t* head, uint64_t head_len, const uint8_t* members, uint64_t n, const std::string& path,
                        bool last_block, std::vector<uint8_t>& block, uint64_t* cut, std::string& err);
+
+// inflate.hip: where the batch of a block that is not the last ends (behind its first 4 * (newlines / 4) lines; *n_lines: those)
+uint64_t fastq_host_cut(const uint8_t* blk, uint64_t n, uint64_t* n_lines);
 
 // contig name_id -> index of its @SQ line (the BAM refID), build_sam_header's order (src/aln_writer.rs:256-276);
 // `sq`: the lines' (name, length), when asked for

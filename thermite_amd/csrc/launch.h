@@ -702,5 +702,13 @@ struct InflateParams {
 };
 hipError_t launch_bgzf_inflate(const InflateParams& p, hipStream_t s);
 
+// ---- plain gzip inflated on the device (kernels_gzip.hip, gzip_device.h; host side gzip.hip) ----
+// search, decode, chain, resolve, verify over one job: its summary, bytes and outgoing state are there when the stream
+// has run them.  j.member_crc must be zero.
+namespace gz {
+struct Job;
+}
+hipError_t launch_gzip_inflate(const gz::Job& j, hipStream_t s);
+
 }  // namespace thm
 #endif

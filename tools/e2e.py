@@ -7,10 +7,17 @@ in turn (the driver reads the switch at every call), in one session.
 and on alternately, ROUNDS rounds (default 3) in one session; the files of a pair must be identical.
 --fastq-bgzf[=ROUNDS]: the .fastq.gz files are written BGZF-framed with Python's zlib (level 6, members of 0xff00 bytes);
 two of them -> BAM with THM_BAM_DEVICE 1 and 2, each with THM_FASTQ_DEVICE 1 and 2 alternately, ROUNDS rounds (default 3)
-in one session; the inflated BAM streams of a pair must be identical (batch boundaries differ)."""
+in one session; the inflated BAM streams of a pair must be identical (batch boundaries differ).
+--fastq-gzip[=ROUNDS]: the `gzip -6` files as they are, one and two of them -> BAM with THM_BAM_DEVICE 1 and 2, each with
+THM_FASTQ_DEVICE 1 and 3 alternately, ROUNDS rounds (default 3) in one session; the inflated BAM streams of a pair must be
+identical (batch boundaries differ)."""
 import os, sys, time
-BAM_RUNS = FQ_ROUNDS = BGZF_ROUNDS = 0
+BAM_RUNS = FQ_ROUNDS = BGZF_ROUNDS = GZIP_ROUNDS = 0
 for arg in list(sys.argv[1:]):
+    if arg.startswith("--fastq-gzip"):
+        GZIP_ROUNDS = int(arg.split("=")[1]) if "=" in arg else 3
+        sys.argv.remove(arg)
+        continue
     if arg.startswith("--fastq-bgzf"):
         BGZF_ROUNDS = int(arg.split("=")[1]) if "=" in arg else 3
         sys.argv.remove(arg)
@@ -59,7 +66,7 @@ with open(big, "wb") as f:
         f.write(one)
     del one
 print("plain input: %d reads, %.1f MB" % (n * REP, os.path.getsize(big) / 1e6), flush=True)
-for fmt, name in (() if BAM_RUNS or FQ_ROUNDS or BGZF_ROUNDS else ((capi.FMT_SAM, "sam"), (capi.FMT_PAF, "paf"))):
+for fmt, name in (() if BAM_RUNS or FQ_ROUNDS or BGZF_ROUNDS or GZIP_ROUNDS else ((capi.FMT_SAM, "sam"), (capi.FMT_PAF, "paf"))):
     for rep in range(2):
         out = "/tmp/thm_e2e_out.%s" % name
         st = capi.align_files(a, [big], out, fmt, batch_reads=250000, n_threads=threads)
@@ -109,7 +116,7 @@ def digest(path):
     return h.hexdigest()
 
 
-paf_of_plain = None if BAM_RUNS or FQ_ROUNDS or BGZF_ROUNDS else digest("/tmp/thm_e2e_out.paf")  # (the last plain run wrote PAF of the REP-copy file)
+paf_of_plain = None if BAM_RUNS or FQ_ROUNDS or BGZF_ROUNDS or GZIP_ROUNDS else digest("/tmp/thm_e2e_out.paf")  # (the last plain run wrote PAF of the REP-copy file)
 
 
 def run(tag, paths, fmt, out, reps=2):
@@ -152,6 +159,36 @@ if BGZF_ROUNDS:
                 outs.append(out)
             same = same and (k > 0 or pair[0] == pair[1])
     print("inflated BAM streams with THM_FASTQ_DEVICE 1 and 2 are %s" % ("IDENTICAL" if same else "DIFFERENT"), flush=True)
+    a.close()
+    for f in [path, big, gz, gz2, "/tmp/thm_e2e_out.bam"] + outs:
+        if os.path.exists(f):
+            os.remove(f)
+    assert same
+    sys.exit(0)
+if GZIP_ROUNDS:
+    os.environ["THM_BAM_DEVICE"] = "1"
+    os.environ["THM_FASTQ_DEVICE"] = "1"
+    run("warm-up: bam from two .gz, THM_BAM_DEVICE=1, THM_FASTQ_DEVICE=1", [gz, gz2], capi.FMT_BAM, "/tmp/thm_e2e_out.bam", 1)
+    outs, same = [], True
+    for k in range(GZIP_ROUNDS):
+        for files in ([gz], [gz, gz2]):
+            for dev in ("1", "2"):
+                os.environ["THM_BAM_DEVICE"] = dev
+                pair = []
+                for fq in ("1", "3"):
+                    os.environ["THM_FASTQ_DEVICE"] = fq
+                    out = "/tmp/thm_e2e_out.g%d%s%s.bam" % (len(files), dev, fq)
+                    before = a.debug_fastq_gzip_blocks()
+                    run("bam from %d gzip -6 .gz, THM_BAM_DEVICE=%s, THM_FASTQ_DEVICE=%s, round %d" % (len(files), dev, fq, k), files, capi.FMT_BAM, out, 1)
+                    after = a.debug_fastq_gzip_blocks()
+                    if fq == "3":
+                        print("    slices inflated on the device %d, on the host %d; parsed on the device %d, on the host %d" % tuple(
+                            y - x for x, y in zip(before, after)), flush=True)
+                    if k == 0:
+                        pair.append(inflated_sha(out))
+                    outs.append(out)
+                same = same and (k > 0 or pair[0] == pair[1])
+    print("inflated BAM streams with THM_FASTQ_DEVICE 1 and 3 are %s" % ("IDENTICAL" if same else "DIFFERENT"), flush=True)
     a.close()
     for f in [path, big, gz, gz2, "/tmp/thm_e2e_out.bam"] + outs:
         if os.path.exists(f):

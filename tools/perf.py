@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Quick stage timing on the GPU box (tuning aid, not the benchmark):
-python tools/perf.py [ref_len] [n_reads] [opts] [--cigars] [--bam] [--bgzf] [--fastq] [--fastq-bgzf]
+python tools/perf.py [ref_len] [n_reads] [opts] [--cigars] [--bam] [--bgzf] [--fastq] [--fastq-bgzf] [--fastq-gzip]
 --cigars: on the resident batch, thm_batch_fetch against thm_batch_fetch_cigars -- milliseconds and bytes moved to the
 host by each, and the device time of the two CIGAR passes (THM_T_CIGAR).
 --bam: on the resident batch, thm_batch_fetch_bam with both forms of the emit kernel (THM_BAM_EMIT) -- milliseconds,
@@ -13,7 +13,11 @@ the compressed sizes of the device encoder, the host encoder and zlib level 1 ov
 kernels (device_ms) -- beside thm_batch_upload_reads of the parsed batch, and the host's parse of the block on one thread.
 --fastq-bgzf: the same block BGZF-framed with Python's zlib (level 6, members of 0xff00 bytes): thm_batch_upload_fastq_bgzf
 -- milliseconds of the call, of its inflate kernel (inflate_ms) and of its parse kernels (parse_ms) -- beside
-thm_batch_upload_fastq of the inflated bytes and zlib's inflate of the members on one host thread."""
+thm_batch_upload_fastq of the inflated bytes and zlib's inflate of the members on one host thread.
+--fastq-gzip: the same block as ONE gzip member (zlib level 6): thm_batch_upload_fastq_gzip -- milliseconds of the call, of
+its inflate kernels (inflate_ms) and of its parse kernels (parse_ms), chunks, starts and the starts the chain refused --
+beside thm_batch_upload_fastq of the inflated bytes and zlib's inflate of the member on one host thread; then the same
+with varied qualities (the tool's all-F lines are kind to a decoder).  THM_GZIP_CHUNK_KB sets the chunk size."""
 import sys, time
 import numpy as np
 sys.path.insert(0, __import__("os").path.dirname(__import__("os").path.dirname(__import__("os").path.abspath(__file__))))
@@ -24,7 +28,8 @@ bam = "--bam" in sys.argv
 bgzf = "--bgzf" in sys.argv
 fastq = "--fastq" in sys.argv
 fastq_bgzf = "--fastq-bgzf" in sys.argv
-sys.argv = [x for x in sys.argv if x not in ("--cigars", "--bam", "--bgzf", "--fastq", "--fastq-bgzf")]
+fastq_gzip = "--fastq-gzip" in sys.argv
+sys.argv = [x for x in sys.argv if x not in ("--cigars", "--bam", "--bgzf", "--fastq", "--fastq-bgzf", "--fastq-gzip")]
 if bam:
     __import__("os").environ["THM_BAM_LEVEL"] = "0"  # (read once, by the first BGZF block of the process)
 ref_len = int(sys.argv[1]) if len(sys.argv) > 1 else 4000000
@@ -242,6 +247,50 @@ for name, opts in (("ci", capi.CI_OPTS), ("default", capi.DEFAULT_OPTS)):
         print("         upload_fastq of the inflated bytes median %.2f ms (min %.2f max %.2f); zlib inflate of the members, one host thread, %.1f ms" % (
             float(np.median(mf)), min(mf), max(mf), zlib_ms), flush=True)
         b.close()
+    if fastq_gzip:
+        import os, zlib
+        K2 = 9
+        reads = bases.reshape(n, 91)
+        rng = np.random.default_rng(7)
+        walk = np.clip(36 + np.cumsum(rng.integers(-2, 3, size=(n, 91)), axis=1), 2, 40).astype(np.uint8) + 33
+        for label, qual_of in (("all-F qualities", lambda i: b"F" * 91), ("varied qualities", lambda i: walk[i].tobytes())):
+            block = b"".join(b"@SYN:%d 1:N:0:ACGT\n" % i + reads[i].tobytes() + b"\n+\n" + qual_of(i) + b"\n" for i in range(n))
+            c = zlib.compressobj(6, zlib.DEFLATED, 31)
+            member = c.compress(block) + c.flush()
+            t0 = time.perf_counter()
+            assert len(zlib.decompress(member, 31)) == len(block)
+            zlib_ms = (time.perf_counter() - t0) * 1e3
+            b = capi.Aligner(ix, opts)
+            src, msrc = np.frombuffer(block, np.uint8), np.frombuffer(member, np.uint8)
+            info, zinfo = capi.FastqUploadInfo(), capi.FastqGzipInfo()
+
+            def up_fastq():
+                b._chk(capi.lib().thm_batch_upload_fastq(b.h, src.ctypes.data, len(block), b"perf", 1, 1, capi.C.byref(info)))
+
+            def up_gzip():
+                st = capi.GzipState()
+                b._chk(capi.lib().thm_batch_upload_fastq_gzip(b.h, capi.C.byref(st), None, 0, msrc.ctypes.data, len(member), b"perf", 1, 1,
+                                                              capi.C.byref(zinfo)))
+
+            for _ in range(2):   # buffers grow
+                up_gzip(); up_fastq()
+            mz, mf, mi, mp = [], [], [], []
+            for _ in range(K2):   # alternately, in one session
+                t0 = time.perf_counter(); up_gzip(); mz.append((time.perf_counter() - t0) * 1e3); mi.append(zinfo.inflate_ms); mp.append(zinfo.parse_ms)
+                t0 = time.perf_counter(); up_fastq(); mf.append((time.perf_counter() - t0) * 1e3)
+            print("         %s, chunks of %s KiB: upload_fastq_gzip median %.2f ms (min %.2f max %.2f)  one member, %d -> %d bytes, %d reads  "
+                  "inflated_on_device %d (decline_reason %d) n_chunks %d n_starts %d  inflate_ms median %.3f (min %.3f max %.3f)  "
+                  "parse_ms median %.3f (min %.3f max %.3f)" % (
+                      label, os.environ.get("THM_GZIP_CHUNK_KB", "32"), float(np.median(mz)), min(mz), max(mz), len(member), len(block), zinfo.n_reads,
+                      zinfo.inflated_on_device, zinfo.decline_reason, zinfo.n_chunks, zinfo.n_starts, float(np.median(mi)), min(mi), max(mi),
+                      float(np.median(mp)), min(mp), max(mp)), flush=True)
+            print("         upload_fastq of the inflated bytes median %.2f ms (min %.2f max %.2f); zlib inflate of the member, one host thread, %.1f ms" % (
+                float(np.median(mf)), min(mf), max(mf), zlib_ms), flush=True)
+            assert zinfo.n_reads == n and info.n_reads == n
+            if zinfo.inflated_on_device:
+                _, _, counts = b.debug_gzip_inflate(capi.GzipState(), member, chunk_bytes=int(os.environ.get("THM_GZIP_CHUNK_KB", "32")) << 10, cap=len(block))
+                print("         the device inflate alone: n_chunks %d n_starts %d starts the chain refused %d path flags %d" % counts, flush=True)
+            b.close()
     c = dict(zip(capi.COUNTER_NAMES, a.counters().tolist()))
     runs = K + 2
     print("         per read: smems %.2f hits %.2f swg_calls %.2f cols %.1f cells %.0f alns %.2f win_bytes %.0f" % tuple(
