@@ -155,6 +155,58 @@ int32_t thm_batch_fetch_bgzf(thm_aligner* a, uint32_t flags, thm_bgzf_view* out)
 /* upload_reads + run + the fetch above */
 int32_t thm_align_batch_bgzf(thm_aligner* a, const thm_read_batch* reads, uint32_t flags, thm_bgzf_view* out);
 
+/* ------------------------------------------------- coordinate-sorted BAM: a whole run's records sorted on the device */
+
+/* The records of every batch of a run stay in device memory (thm_bam_sorter_add in place of a fetch); at the end they
+ * are sorted once and handed out in coordinate order, window by window, through the device deflater.  The order, with
+ * n_sq the number of @SQ lines (BAM refIDs) of the index and refID, pos, flag the record's fields:
+ *     rank = refID >= 0 ? refID : n_sq                              (unmapped last)
+ *     key  = rank << 33 | (uint32)(pos + 1) << 1 | (flag >> 4 & 1)  (position, then forward before reverse)
+ * Records are ordered by key; records with equal keys keep the order in which they were added (add order, then record
+ * order within the batch).  Not done: spilling to the host when the records exceed device memory, merging across
+ * devices, an index file (raw_offset and block_off give the virtual offsets one needs), name order. */
+typedef struct thm_bam_sorter thm_bam_sorter;
+
+typedef struct thm_bam_sort_info {      /* what one add did, and the totals so far */
+  uint64_t n_reads, n_records, n_bytes;            /* this batch */
+  uint64_t total_records, total_bytes;             /* held by the sorter */
+  uint64_t n_failed_reads; const int32_t* read_status;   /* as in thm_bam_view; valid until the next add */
+  float add_ms;                                    /* key kernel + copy, device events */
+} thm_bam_sort_info;
+
+typedef struct thm_bam_sorted_view {
+  uint64_t total_records, total_raw_bytes;   /* of the whole sorted stream */
+  uint64_t raw_offset, n_raw_bytes;          /* this window of it; n_raw_bytes == 0: the stream is exhausted */
+  uint64_t n_blocks, n_bytes;
+  const uint8_t* data;                       /* BGZF members back to back, or with THM_SORT_RAW the window's record bytes */
+  const uint64_t* block_off;                 /* [n_blocks+1]; NULL with THM_SORT_RAW */
+  float gather_ms, deflate_ms;
+} thm_bam_sorted_view;
+
+#define THM_SORT_RAW 1u
+
+/* A sorter belongs to one aligner: it works on that aligner's device and stream and must be freed before it.
+ * max_bytes caps the record bytes held (0: no cap but the device's memory). */
+int32_t thm_bam_sorter_create(thm_aligner* a, uint64_t max_bytes, thm_bam_sorter** out);
+/* Stands where thm_batch_fetch_bam stands after thm_batch_run and takes its flags, preconditions and errors (same codes
+ * and messages): the run's records are encoded on the device and stay there, appended behind those already held (what is
+ * held is never copied again); only counts and statuses come back.  It may precede or follow any of the four fetches of
+ * the same run and disturbs none of their views, no counter and no timing.  THM_ERR_OOM: the cap would be exceeded, or a
+ * device allocation failed (the message names the bytes needed and the cap); the batch is then not added and the sorter
+ * stays usable with what it held.  THM_ERR_INVALID_ARG: more than 2^32-1 records in all, or a call after finish. */
+int32_t thm_bam_sorter_add(thm_bam_sorter* s, uint32_t bam_flags, thm_bam_sort_info* info);
+/* sorts (key, ordinal) pairs and scans the sorted lengths; sort_ms (may be NULL): device events.  Once. */
+int32_t thm_bam_sorter_finish(thm_bam_sorter* s, float* sort_ms);
+/* The next window of the sorted stream: max_raw_bytes rounded down to a multiple of 0xff00 and at least 0xff00 (0: 256
+ * blocks), the last one shorter.  Every window begins on a multiple of 0xff00, so the members of all windows back to
+ * back are the sorted stream cut every 0xff00 bytes, whatever the window size and however the records came in batches:
+ * thm_writer_header_sorted + all members + thm_writer_trailer is a valid coordinate-sorted .bam.  Two pinned result sets,
+ * used alternately: a view stays valid until the second-next call on this sorter.  THM_ERR_INVALID_ARG: before finish,
+ * unknown bits in flags.  THM_SORT_GATHER=pieces in the environment when the sorter is created selects the other of the
+ * two gather kernels (same bytes). */
+int32_t thm_bam_sorter_next(thm_bam_sorter* s, uint64_t max_raw_bytes, uint32_t flags, thm_bam_sorted_view* out);
+void thm_bam_sorter_free(thm_bam_sorter* s);
+
 /* ------------------------------------------------- FASTQ blocks parsed on the device */
 
 typedef struct thm_fastq_upload_info {
@@ -290,6 +342,9 @@ void thm_writer_free(thm_writer* w);
  * BGZF-compressed magic + header text + reference list of bam::Writer::write_header
  * / write_reference_sequences, src/aligner.rs:41-46) */
 int32_t thm_writer_header(thm_writer* w, thm_text* out);
+/* the same with "@HD\tVN:1.6\tSO:coordinate\n" as the first line of the header text (for BAM l_text counts it): the
+ * header of a file whose records come from a thm_bam_sorter.  Empty for PAF. */
+int32_t thm_writer_header_sorted(thm_writer* w, thm_text* out);
 /* what closes the file: the BGZF end-of-file block for BAM, nothing otherwise */
 int32_t thm_writer_trailer(thm_writer* w, thm_text* out);
 /* aln_to_sam_record / unmapped_sam_record / PafEntry, src/aln_writer.rs:47-253,
@@ -352,7 +407,16 @@ typedef struct thm_run_stats {
  * compression ratio of the batches so far, each beginning at the last one's n_consumed_bytes, doubled while nothing of
  * one is consumed, last_block set on the slice that reaches the end of the file; state and tail pass along the same
  * in-order chain of uploads and are reset per file.  The file's inflated bytes are those of the unset run; batch
- * boundaries may differ.  FASTA and input that is not gzip keep the path of =1. */
+ * boundaries may differ.  FASTA and input that is not gzip keep the path of =1.
+ * THM_BAM_SORT=1 and THM_FMT_BAM (ignored for the other formats): the file is coordinate-sorted.  Batches go up as with
+ * THM_BAM_DEVICE=1 (THM_FASTQ_DEVICE=1..3 apply as there) and their records stay on the device (thm_bam_sorter_add);
+ * nothing is formatted or written until the input is exhausted.  Then the records are sorted (thm_bam_sorter_finish),
+ * thm_writer_header_sorted is written, the windows of thm_bam_sorter_next follow -- window k being written while the
+ * device produces window k + 1 -- and the end-of-file block closes the file.  Inflated, the file is the sorted header and
+ * the records of the unset run in the order of thm_bam_sorter; the members are the device encoder's.  n_output_bytes
+ * counts the file's bytes; the drain's time goes into format_s (sort, gather, deflate, copy) and write_s.  One aligner
+ * only: with more, THM_ERR_INVALID_ARG (merging across devices is not done).  Records beyond the device's memory:
+ * THM_ERR_OOM from the add that meets it. */
 int32_t thm_align_files(thm_aligner* a, const char* const* fastq_paths, uint32_t n_paths, const char* output_path,
                         int32_t format, uint64_t batch_reads, uint32_t n_threads, thm_run_stats* stats);
 /* The same over several aligners -- one per GPU of the node, all over one index (the shape of ThermiteAligner: Clone +

@@ -142,6 +142,24 @@ class BgzfView(C.Structure):
                 ("read_status", C.c_void_p)]
 
 
+class BamSortInfo(C.Structure):
+    """thm_bam_sort_info (include/thermite_io.h)"""
+
+    _fields_ = [("n_reads", C.c_uint64), ("n_records", C.c_uint64), ("n_bytes", C.c_uint64), ("total_records", C.c_uint64),
+                ("total_bytes", C.c_uint64), ("n_failed_reads", C.c_uint64), ("read_status", C.c_void_p), ("add_ms", C.c_float)]
+
+
+class BamSortedView(C.Structure):
+    """thm_bam_sorted_view (include/thermite_io.h)"""
+
+    _fields_ = [("total_records", C.c_uint64), ("total_raw_bytes", C.c_uint64), ("raw_offset", C.c_uint64), ("n_raw_bytes", C.c_uint64),
+                ("n_blocks", C.c_uint64), ("n_bytes", C.c_uint64), ("data", C.c_void_p), ("block_off", C.c_void_p),
+                ("gather_ms", C.c_float), ("deflate_ms", C.c_float)]
+
+
+SORT_RAW = 1
+
+
 class FastqUploadInfo(C.Structure):
     """thm_fastq_upload_info (include/thermite_io.h)"""
 
@@ -211,6 +229,8 @@ IO_ABI_SYMBOLS = [
     "thm_batch_upload_fastq", "thm_batch_fetch_reads",
     "thm_batch_upload_fastq_bgzf",
     "thm_batch_upload_fastq_gzip",
+    "thm_bam_sorter_create", "thm_bam_sorter_add", "thm_bam_sorter_finish", "thm_bam_sorter_next", "thm_bam_sorter_free",
+    "thm_writer_header_sorted",
 ]
 ERR_IO, ERR_FORMAT = -8, -9
 FMT_PAF, FMT_SAM, FMT_BAM = 0, 1, 2
@@ -380,6 +400,22 @@ def lib():
     L.thm_debug_gzip_host_slice.argtypes = [vp, vp, u64, i32, vp, u64, vp, vp]
     L.thm_writer_wrap_bam.restype = i32
     L.thm_writer_wrap_bam.argtypes = [vp, vp, vp]
+    L.thm_writer_header_sorted.restype = i32
+    L.thm_writer_header_sorted.argtypes = [vp, vp]
+    L.thm_bam_sorter_create.restype = i32
+    L.thm_bam_sorter_create.argtypes = [vp, u64, vp]
+    L.thm_bam_sorter_add.restype = i32
+    L.thm_bam_sorter_add.argtypes = [vp, u32, vp]
+    L.thm_bam_sorter_finish.restype = i32
+    L.thm_bam_sorter_finish.argtypes = [vp, vp]
+    L.thm_bam_sorter_next.restype = i32
+    L.thm_bam_sorter_next.argtypes = [vp, u64, u32, vp]
+    L.thm_bam_sorter_free.restype = None
+    L.thm_bam_sorter_free.argtypes = [vp]
+    L.thm_debug_bam_sorter_add_records.restype = i32
+    L.thm_debug_bam_sorter_add_records.argtypes = [vp, vp, u64]
+    L.thm_debug_bam_sorter_gather.restype = i32
+    L.thm_debug_bam_sorter_gather.argtypes = [vp, i32]
     L.thm_align_files.restype = i32
     L.thm_align_files.argtypes = [vp, vp, u32, cp, i32, u64, u32, vp]
     L.thm_align_files_multi.restype = i32
@@ -729,6 +765,77 @@ class BgzfResult:
     def block(self, b):
         """member b as a byte string"""
         return self.data[int(self.block_off[b]): int(self.block_off[b + 1])].tobytes()
+
+
+class SortedWindow:
+    """thm_bam_sorted_view copied out: one window of the sorted stream, as BGZF members (block_off) or raw record bytes"""
+
+    def __init__(self, view, copy=True):
+        self.total_records, self.total_raw_bytes = view.total_records, view.total_raw_bytes
+        self.raw_offset, self.n_raw_bytes = view.raw_offset, view.n_raw_bytes
+        self.n_blocks, self.n_bytes = view.n_blocks, view.n_bytes
+        self.data = _copy(view.data, view.n_bytes, np.uint8, copy)
+        self.block_off = _copy(view.block_off, view.n_blocks + 1, "<u8", copy) if view.block_off else None
+        self.gather_ms, self.deflate_ms = view.gather_ms, view.deflate_ms
+
+
+class BamSorter:
+    """thm_bam_sorter: the BAM records of every batch of a run kept on the aligner's device, sorted by coordinate at the
+    end and handed out window by window.  Close it before its aligner."""
+
+    def __init__(self, aligner, max_bytes=0):
+        self.aligner = aligner
+        h = C.c_void_p()
+        rc = lib().thm_bam_sorter_create(aligner.h, max_bytes, C.byref(h))
+        if rc != 0:
+            raise ThermiteError(rc, (lib().thm_last_error(None) or b"").decode())
+        self.h = h
+
+    def add(self, flags=0):
+        """thm_bam_sorter_add, after Aligner.run -> the info as a dict (`status`: the per-read statuses, or None)"""
+        info = BamSortInfo()
+        self.aligner._chk(lib().thm_bam_sorter_add(self.h, flags, C.byref(info)))
+        out = {k: getattr(info, k) for k, _ in BamSortInfo._fields_ if k != "read_status"}
+        out["status"] = _copy(info.read_status, info.n_reads, np.int32) if info.read_status else None
+        return out
+
+    def add_records(self, data):
+        """test hook: caller-made records through the same key kernel and arena"""
+        src = _u8(data)
+        self.aligner._chk(lib().thm_debug_bam_sorter_add_records(self.h, _ptr(src) if len(src) else None, len(src)))
+
+    def gather_shape(self, shape=None):
+        """test / tuning hook: "pieces" (16 bytes a lane) or "records" (a wavefront per record) for the next windows (None
+        only asks) -> the shape in use before the call; a new sorter starts with "records" unless THM_SORT_GATHER=pieces"""
+        was = lib().thm_debug_bam_sorter_gather(self.h, {None: -1, "pieces": 0, "records": 1}[shape])
+        return ("pieces", "records")[was]
+
+    def finish(self):
+        """thm_bam_sorter_finish -> the sort's milliseconds"""
+        ms = C.c_float(0)
+        self.aligner._chk(lib().thm_bam_sorter_finish(self.h, C.byref(ms)))
+        return ms.value
+
+    def next(self, max_raw_bytes=0, raw=False, copy=True):
+        v = BamSortedView()
+        self.aligner._chk(lib().thm_bam_sorter_next(self.h, max_raw_bytes, SORT_RAW if raw else 0, C.byref(v)))
+        return SortedWindow(v, copy)
+
+    def windows(self, max_raw_bytes=0, raw=False):
+        """every window of the sorted stream that is left, in order"""
+        while True:
+            w = self.next(max_raw_bytes, raw)
+            if w.n_raw_bytes == 0:
+                return
+            yield w
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().thm_bam_sorter_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
 
 
 def cigar_text(words):
@@ -1214,6 +1321,14 @@ class Writer:
     def header(self):
         t = Text()
         rc = lib().thm_writer_header(self.h, C.byref(t))
+        if rc != 0:
+            raise ThermiteError(rc, _last_error())
+        return bytes(_copy(t.data, t.len, np.uint8))
+
+    def header_sorted(self):
+        """thm_writer_header_sorted: the header with the @HD line of a coordinate-sorted file"""
+        t = Text()
+        rc = lib().thm_writer_header_sorted(self.h, C.byref(t))
         if rc != 0:
             raise ThermiteError(rc, _last_error())
         return bytes(_copy(t.data, t.len, np.uint8))

@@ -351,6 +351,10 @@ struct BamOnDevice {
   bool any_failed = false;  // as in BatchSizes
 };
 int bam_records_on_device(thm_aligner* a, uint32_t flags, int timing, BamOnDevice* r);
+// bgzf.hip: d_in[0, n) (device, 4-byte aligned) cut every 0xff00 bytes and deflated -> the members back to back in bz_out,
+// their offsets in bz_off[0 .. *n_blocks]; synchronises the stream once and sets THM_T_BGZF (bam_sort.hip deflates the
+// windows of the sorted stream through it)
+int bgzf_range_on_device(thm_aligner* a, const uint8_t* d_in, uint64_t n, uint64_t* n_blocks, uint64_t* n_bytes);
 // ---- pipeline.hip: the head and the tail of every fetch entry point (after thm_batch_sync; a new one calls all of them)
 struct BatchSizes {
   uint64_t n_alns = 0, n_ops = 0;  // alignments and op bytes of the compacted batch, checked against the pools

@@ -59,6 +59,10 @@ int bgzf_on_device(thm_aligner* a, const uint8_t* d_in, uint64_t n, uint64_t* n_
 
 }  // namespace
 
+int bgzf_range_on_device(thm_aligner* a, const uint8_t* d_in, uint64_t n, uint64_t* n_blocks, uint64_t* n_bytes) {
+  return bgzf_on_device(a, d_in, n, n_blocks, n_bytes);
+}
+
 int thm::batch_fetch_bgzf(thm_aligner* a, uint32_t flags, thm_bgzf_view* out, uint64_t* n_aligned_reads) {
   if (!a || !out) return THM_ERR_INVALID_ARG;
   memset(out, 0, sizeof(*out));

@@ -68,6 +68,8 @@ struct Slot {
   thm_bam_view bam;    // ... or, with THM_BAM_DEVICE=1, the BAM records encoded on the device (likewise two sets)
   thm_bgzf_view bgzf;  // ... or, with THM_BAM_DEVICE=2, their BGZF members deflated there (likewise)
   uint64_t bgzf_aligned = 0;  // reads of the batch with an alignment (the members do not show it)
+  thm_bam_sort_info sorted;   // ... or, with THM_BAM_SORT=1, what adding them to the sorter reported (no bytes come back)
+  uint64_t sorted_aligned = 0;
   bool aligned = false;
 };
 
@@ -364,8 +366,16 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
   // THM_BAM_DEVICE=1: BAM records are encoded on the device (thm_batch_fetch_bam) and only deflated here
   const char* bam_dev_env = getenv("THM_BAM_DEVICE");
   // THM_BAM_DEVICE=2: ... and BGZF-compressed there too (thm_batch_fetch_bgzf): the formatting stage passes bytes on
-  const bool bgzf_device = format == THM_FMT_BAM && bam_dev_env && !strcmp(bam_dev_env, "2");
-  const bool bam_device = bgzf_device || (format == THM_FMT_BAM && bam_dev_env && !strcmp(bam_dev_env, "1"));
+  // THM_BAM_SORT=1: the records of every batch stay on the device (thm_bam_sorter_add, uploads as with THM_BAM_DEVICE=1);
+  // once the input is exhausted they are sorted there and leave window by window as finished members
+  const char* bam_sort_env = getenv("THM_BAM_SORT");
+  const bool bam_sort = format == THM_FMT_BAM && bam_sort_env && !strcmp(bam_sort_env, "1");
+  if (bam_sort && n_aligners > 1) {
+    thm::set_global_error("thm_align_files_multi: THM_BAM_SORT=1 takes one aligner (merging across devices is not done)");
+    return THM_ERR_INVALID_ARG;
+  }
+  const bool bgzf_device = !bam_sort && format == THM_FMT_BAM && bam_dev_env && !strcmp(bam_dev_env, "2");
+  const bool bam_device = bam_sort || bgzf_device || (format == THM_FMT_BAM && bam_dev_env && !strcmp(bam_dev_env, "1"));
   // THM_FASTQ_DEVICE=1, in those two modes only (the host needs no read bytes there): blocks of 4-line FASTQ go to the
   // device unparsed (thm_batch_upload_fastq)
   const char* fq_dev_env = getenv("THM_FASTQ_DEVICE");
@@ -412,6 +422,12 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
     return true;
   };
 
+  thm_bam_sorter* sorter = nullptr;
+  if (bam_sort && (rc = thm_bam_sorter_create(aligners[0], 0, &sorter)) != THM_OK) {
+    if (!to_stdout) close(fo);
+    thm_writer_free(w);
+    return rc;
+  }
   thm_run_stats st;
   memset(&st, 0, sizeof st);
   std::mutex st_mu;  // parse_s / gpu_s are summed by several threads
@@ -872,12 +888,15 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
           }
           const auto t2 = Clock::now();
           if (grc == THM_OK) grc = sh.step([&] {
+            if (bam_sort) return thm::bam_sorter_add(sorter, 0, &s->sorted, &s->sorted_aligned);
             if (!bgzf_device) return bam_device ? thm_batch_fetch_bam(a, 0, &s->bam) : thm_batch_fetch(a, &s->res);
             return thm::batch_fetch_bgzf(a, 0, &s->bgzf, &s->bgzf_aligned);
           });
-          const uint64_t n_res = bgzf_device ? s->bgzf.n_reads : bam_device ? s->bam.n_reads : s->res.n_reads;
-          const int32_t* res_status = bgzf_device ? s->bgzf.read_status : bam_device ? s->bam.read_status : s->res.read_status;
-          if (grc == THM_OK && (bgzf_device ? s->bgzf.n_failed_reads : bam_device ? s->bam.n_failed_reads : s->res.n_failed_reads)) {
+          const uint64_t n_res = bam_sort ? s->sorted.n_reads : bgzf_device ? s->bgzf.n_reads : bam_device ? s->bam.n_reads : s->res.n_reads;
+          const int32_t* res_status = bam_sort ? s->sorted.read_status
+                                      : bgzf_device ? s->bgzf.read_status : bam_device ? s->bam.read_status : s->res.read_status;
+          if (grc == THM_OK && (bam_sort ? s->sorted.n_failed_reads
+                                : bgzf_device ? s->bgzf.n_failed_reads : bam_device ? s->bam.n_failed_reads : s->res.n_failed_reads)) {
             // the reference aligns every read or panics; a read this build cannot take fails the run, by name
             uint64_t bad = 0;
             while (bad < n_res && res_status[bad] == THM_OK) bad++;
@@ -953,7 +972,8 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
     WriteJob jobs[2];
     bool job_busy[2] = {false, false};
     thm_text t;
-    if (thm_writer_header(w, &t) == THM_OK && t.len) {
+    // (a sorted file's header is written when the drain begins)
+    if (!bam_sort && thm_writer_header(w, &t) == THM_OK && t.len) {
       if (!write_all((const char*)t.data, t.len, file_off)) sh.set(THM_ERR_IO, "short write");
       file_off += t.len;
       st.n_output_bytes += t.len;
@@ -1014,7 +1034,11 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
         wj_cv.wait(g, [&] { return !job_busy[k]; });
       }
       bool queued = false;
-      if (!sh.failed() && s->aligned) {
+      if (!sh.failed() && s->aligned && bam_sort) {
+        // nothing leaves before the input is exhausted: the batch is in the sorter
+        st.n_aligned_reads += s->sorted_aligned;
+        st.n_records += s->sorted.n_records;
+      } else if (!sh.failed() && s->aligned) {
         const auto t0 = Clock::now();
         const thm_read_batch rb = s->reads.view();
         const thm_batch_view& v = s->res;
@@ -1085,6 +1109,44 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
     }
     wj_cv.notify_all();
     wthread.join();
+    if (bam_sort && !sh.failed()) {
+      // the drain: sort, the sorted header, then window after window -- window k is written (from one of the sorter's two
+      // pinned sets) while the device gathers and deflates window k + 1
+      const auto t0 = Clock::now();
+      int drc = sh.step([&] { return (int)thm_bam_sorter_finish(sorter, nullptr); });
+      st.format_s += secs(t0, Clock::now());
+      if (drc != THM_OK) sh.set(drc, thm_last_error(aligners[0]));
+      if (drc == THM_OK && thm_writer_header_sorted(w, &t) == THM_OK && t.len) {
+        if (!write_all((const char*)t.data, t.len, file_off)) sh.set(THM_ERR_IO, "short write");
+        file_off += t.len;
+        st.n_output_bytes += t.len;
+      }
+      std::thread wr;
+      bool wrote = true;
+      while (drc == THM_OK && !sh.failed()) {
+        thm_bam_sorted_view v;
+        const auto t1 = Clock::now();
+        drc = sh.step([&] { return (int)thm_bam_sorter_next(sorter, 0, 0, &v); });
+        st.format_s += secs(t1, Clock::now());
+        if (wr.joinable()) wr.join();  // the next call reuses the set the write before last came from
+        if (!wrote) sh.set(THM_ERR_IO, "short write");
+        if (drc != THM_OK) {
+          sh.set(drc, thm_last_error(aligners[0]));
+          break;
+        }
+        if (v.n_raw_bytes == 0) break;
+        const uint64_t at = file_off;
+        file_off += v.n_bytes;
+        st.n_output_bytes += v.n_bytes;
+        wr = std::thread([&, v, at] {
+          const auto t2 = Clock::now();
+          wrote = write_all((const char*)v.data, (size_t)v.n_bytes, at);
+          st.write_s += secs(t2, Clock::now());
+        });
+      }
+      if (wr.joinable()) wr.join();
+      if (!wrote) sh.set(THM_ERR_IO, "short write");
+    }
     if (!sh.failed() && thm_writer_trailer(w, &t) == THM_OK && t.len) {
       if (!write_all((const char*)t.data, t.len, file_off)) sh.set(THM_ERR_IO, "short write");
       file_off += t.len;
@@ -1096,6 +1158,7 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
   for (auto& m : maps) munmap((void*)m.first, m.second);
   for (auto& x : parsers) x.join();
   for (auto& x : gpus) x.join();
+  thm_bam_sorter_free(sorter);
   bool ok = true;
   if (!to_stdout) ok = close(fo) == 0;
   if (!ok) sh.set(THM_ERR_IO, std::string("error closing ") + output_path);

@@ -113,6 +113,10 @@ int writer_wrap_bam_chunks(thm_writer* w, const thm_bam_view* view, std::vector<
 // holds compressed bytes only; the file driver counts them in its statistics); n_aligned_reads may be null
 int batch_fetch_bgzf(thm_aligner* a, uint32_t flags, thm_bgzf_view* out, uint64_t* n_aligned_reads);
 
+// bam_sort.hip: thm_bam_sorter_add, which also reports the reads of the batch with at least one alignment (the file
+// driver counts them in its statistics); n_aligned_reads may be null
+int bam_sorter_add(thm_bam_sorter* s, uint32_t flags, thm_bam_sort_info* info, uint64_t* n_aligned_reads);
+
 // inflate.hip: head ++ inflate(members) by the host inflater into `block` (THM_ERR_IO and `err` as GzInflater words it);
 // *cut: bytes of the batch thm_batch_upload_fastq_bgzf takes of it (all of it for a last block)
 int bgzf_block_on_host(const uint8_t* head, uint64_t head_len, const uint8_t* members, uint64_t n, const std::string& path,

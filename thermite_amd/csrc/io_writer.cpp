@@ -29,6 +29,7 @@ struct thm_writer {
   unsigned n_threads = 1;
   std::string header;                // SAM text header; for BAM: the BGZF-compressed BAM header
   std::string trailer;               // BAM: the BGZF end-of-file block
+  std::string header_sorted;         // `header` with the @HD line of a coordinate-sorted file in front of the text
   std::vector<int32_t> sq_of_name;   // contig name_id -> index of its @SQ line (BAM refID)
   std::vector<std::string> chunk;    // per formatting thread
   std::vector<std::string> raw;      // BAM: uncompressed records per formatting thread
@@ -896,21 +897,26 @@ int32_t thm_writer_create(const thm_index* ix, int32_t format, uint32_t n_thread
     std::string text;
     for (const auto& q : sq) text += "@SQ\tSN:" + q.first + "\tLN:" + std::to_string(q.second) + "\n";
     text += "@PG\tID:thermite\n";
+    const std::string text_sorted = "@HD\tVN:1.6\tSO:coordinate\n" + text;
     if (format == THM_FMT_SAM) {
       w->header = text;
+      w->header_sorted = text_sorted;
     } else {
       // bam::Writer::write_header + write_reference_sequences, src/aligner.rs:41-46
-      std::string raw("BAM\1", 4);
-      le32(raw, (uint32_t)text.size());
-      raw += text;
-      le32(raw, (uint32_t)sq.size());
-      for (const auto& q : sq) {
-        le32(raw, (uint32_t)q.first.size() + 1);
-        raw += q.first;
-        raw.push_back('\0');
-        le32(raw, (uint32_t)q.second);
-      }
-      if (!bgzf_compress(raw.data(), raw.size(), w->header) || !bgzf_compress(nullptr, 0, w->trailer)) {
+      auto bam_header = [&](const std::string& txt, std::string& out_z) {
+        std::string raw("BAM\1", 4);
+        le32(raw, (uint32_t)txt.size());
+        raw += txt;
+        le32(raw, (uint32_t)sq.size());
+        for (const auto& q : sq) {
+          le32(raw, (uint32_t)q.first.size() + 1);
+          raw += q.first;
+          raw.push_back('\0');
+          le32(raw, (uint32_t)q.second);
+        }
+        return bgzf_compress(raw.data(), raw.size(), out_z);
+      };
+      if (!bam_header(text, w->header) || !bam_header(text_sorted, w->header_sorted) || !bgzf_compress(nullptr, 0, w->trailer)) {
         delete w;
         return fail(THM_ERR_INTERNAL, "BGZF compression failed");
       }
@@ -926,6 +932,13 @@ int32_t thm_writer_header(thm_writer* w, thm_text* out) {
   if (!w || !out) return THM_ERR_INVALID_ARG;
   out->data = (const uint8_t*)w->header.data();
   out->len = w->header.size();
+  return THM_OK;
+}
+
+int32_t thm_writer_header_sorted(thm_writer* w, thm_text* out) {
+  if (!w || !out) return THM_ERR_INVALID_ARG;
+  out->data = (const uint8_t*)w->header_sorted.data();
+  out->len = w->header_sorted.size();
   return THM_OK;
 }
 

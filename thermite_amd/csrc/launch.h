@@ -664,6 +664,37 @@ unsigned bgzf_grid(uint64_t n_blocks, int n_cu);
 hipError_t launch_bgzf_deflate(const BgzfParams& p, int n_cu, hipStream_t s);
 hipError_t launch_bgzf_compact(const BgzfParams& p, int n_cu, hipStream_t s);
 
+// ---- coordinate sort of a run's BAM records (kernels_bam_sort.hip, bam_sort_device.h; host side bam_sort.hip) ----
+// keys (one thread per record of the batch just added: its key, length and place in the arena) ... sort of (key, ordinal)
+// ... order (lengths and places by sorted ordinal; the caller scans the lengths) ... gather (a window of the sorted
+// stream, 16 bytes a lane).
+struct BamSortKeysParams {
+  const uint8_t* data;  // the batch's records back to back
+  const uint64_t* off;  // [n + 1] their offsets in `data`
+  uint64_t n;
+  uint32_t n_sq;
+  uint64_t base;        // global arena offset of data[0]
+  uint64_t* key;        // [n]  (the three arrays begin at the batch's first ordinal)
+  uint32_t* len;        // [n]
+  uint64_t* loc;        // [n]
+};
+struct BamSortGatherParams {
+  const uint64_t* off;        // [n + 1] scan of the sorted lengths
+  const uint64_t* loc;        // [n] global arena offset of every sorted record
+  uint64_t n;
+  const uint64_t* seg_start;  // [n_seg] global offset at which every arena segment begins, ascending from 0
+  const uint8_t* const* seg;  // [n_seg] the segments, 4-byte aligned, 16 readable bytes behind their records
+  uint32_t n_seg;
+  uint64_t w0, w1;            // the window: w0 a multiple of 16, w0 < w1 <= off[n]
+  uint8_t* out;               // [w1 - w0], 16-byte aligned
+};
+hipError_t launch_bam_sort_keys(const BamSortKeysParams& p, hipStream_t s);
+hipError_t launch_bam_sort_iota(uint32_t* ord, uint64_t n, hipStream_t s);
+hipError_t launch_bam_sort_order(const uint32_t* ord, const uint32_t* len, const uint64_t* loc, uint64_t n, uint64_t* s_len,
+                                 uint64_t* s_loc, hipStream_t s);
+// by_records: the record-centric shape (a wavefront per record), else the output-centric one (16 bytes a lane)
+hipError_t launch_bam_sort_gather(const BamSortGatherParams& p, bool by_records, int n_cu, hipStream_t s);
+
 // ---- FASTQ blocks parsed on the device (kernels_fastq.hip, fastq_device.h; host side fastq.hip) ----
 // count (newlines per chunk) -> scan -> starts (line_start) -> records (the parse rule: lengths, or the flag) -> two
 // scans (name_off, offsets) -> gather (names, bases, qualities to their places).

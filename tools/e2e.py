@@ -10,10 +10,18 @@ two of them -> BAM with THM_BAM_DEVICE 1 and 2, each with THM_FASTQ_DEVICE 1 and
 in one session; the inflated BAM streams of a pair must be identical (batch boundaries differ).
 --fastq-gzip[=ROUNDS]: the `gzip -6` files as they are, one and two of them -> BAM with THM_BAM_DEVICE 1 and 2, each with
 THM_FASTQ_DEVICE 1 and 3 alternately, ROUNDS rounds (default 3) in one session; the inflated BAM streams of a pair must be
-identical (batch boundaries differ)."""
+identical (batch boundaries differ).
+--bam-sort[=ROUNDS]: only plain FASTQ -> BAM with THM_FASTQ_DEVICE=1: THM_BAM_DEVICE=2 (input order) and THM_BAM_SORT=1
+(coordinate order) alternately, ROUNDS rounds (default 3) in one session; then the same reads through thm_bam_sorter by
+hand: sort_ms of thm_bam_sorter_finish and the drain with the two gather shapes alternating window by window (gather_ms,
+deflate_ms per window).  The gzip files are not made."""
 import os, sys, time
-BAM_RUNS = FQ_ROUNDS = BGZF_ROUNDS = GZIP_ROUNDS = 0
+BAM_RUNS = FQ_ROUNDS = BGZF_ROUNDS = GZIP_ROUNDS = SORT_ROUNDS = 0
 for arg in list(sys.argv[1:]):
+    if arg.startswith("--bam-sort"):
+        SORT_ROUNDS = int(arg.split("=")[1]) if "=" in arg else 3
+        sys.argv.remove(arg)
+        continue
     if arg.startswith("--fastq-gzip"):
         GZIP_ROUNDS = int(arg.split("=")[1]) if "=" in arg else 3
         sys.argv.remove(arg)
@@ -66,6 +74,60 @@ with open(big, "wb") as f:
         f.write(one)
     del one
 print("plain input: %d reads, %.1f MB" % (n * REP, os.path.getsize(big) / 1e6), flush=True)
+if SORT_ROUNDS:
+    os.environ["THM_FASTQ_DEVICE"] = "1"
+    os.environ["THM_BAM_DEVICE"] = "2"
+    st = capi.align_files(a, [big], "/tmp/thm_e2e_out.bam", capi.FMT_BAM, batch_reads=250000, n_threads=threads)   # warm-up: buffers grow
+    for k in range(SORT_ROUNDS):
+        for tag, env in (("input order, THM_BAM_DEVICE=2", {"THM_BAM_DEVICE": "2"}), ("sorted,      THM_BAM_SORT=1  ", {"THM_BAM_SORT": "1"})):
+            os.environ.pop("THM_BAM_DEVICE", None)
+            os.environ.pop("THM_BAM_SORT", None)
+            os.environ.update(env)
+            st = capi.align_files(a, [big], "/tmp/thm_e2e_out.bam", capi.FMT_BAM, batch_reads=250000, n_threads=threads)
+            print("bam %s round %d: %.2f Mreads/s wall %.2fs | parse %.2fs gpu %.2fs format %.2fs write %.2fs | %d records, %.0f MB out" % (
+                tag, k, st["n_reads"] / st["wall_s"] / 1e6, st["wall_s"], st["parse_s"], st["gpu_s"], st["format_s"], st["write_s"],
+                st["n_records"], st["n_output_bytes"] / 1e6), flush=True)
+    os.environ.pop("THM_BAM_SORT", None)
+    # the sorter by hand: add every batch, sort, drain with the gather shapes alternating
+    W = 256 * 0xff00
+    for rnd in range(2):
+        rd = capi.FastqReader(big)
+        srt = capi.BamSorter(a)
+        t0 = time.perf_counter()
+        add_ms = []
+        while True:
+            batch = rd.next_batch(250000)
+            if batch is None or len(batch["offsets"]) <= 1:
+                break
+            a.upload_reads(batch)
+            a.run()
+            add_ms.append(srt.add()["add_ms"])
+        rd.close()
+        t_add = time.perf_counter() - t0
+        t0 = time.perf_counter(); sort_ms = srt.finish(); t_fin = time.perf_counter() - t0
+        per, defl, k, total = {"pieces": [], "records": []}, [], 0, 0
+        t0 = time.perf_counter()
+        while True:
+            shape = ("pieces", "records")[(k + rnd) & 1]
+            srt.gather_shape(shape)
+            v = srt.next(0, copy=False)
+            if v.n_raw_bytes == 0:
+                break
+            total = v.total_raw_bytes
+            if v.n_raw_bytes == W:
+                per[shape].append(v.gather_ms)
+                defl.append(v.deflate_ms)
+            k += 1
+        t_drain = time.perf_counter() - t0
+        print("sorter round %d: %d batches added in %.2fs (add_ms median %.3f); finish: %d records, sort_ms %.2f, call %.3fs; drain: %d windows, %.0f MB of records in %.2fs" % (
+            rnd, len(add_ms), t_add, float(np.median(add_ms)), v.total_records, sort_ms, t_fin, k, total / 1e6, t_drain), flush=True)
+        for shape, ms in per.items():
+            print("  gather[%-7s] %d windows of %d bytes: median %.3f ms (min %.3f max %.3f) = %.2f TB/s read+written" % (
+                shape, len(ms), W, float(np.median(ms)), min(ms), max(ms), 2 * W / (float(np.median(ms)) * 1e-3) / 1e12), flush=True)
+        print("  deflate per window: median %.3f ms (min %.3f max %.3f)" % (float(np.median(defl)), min(defl), max(defl)), flush=True)
+        srt.close()
+    a.close()
+    sys.exit(0)
 for fmt, name in (() if BAM_RUNS or FQ_ROUNDS or BGZF_ROUNDS or GZIP_ROUNDS else ((capi.FMT_SAM, "sam"), (capi.FMT_PAF, "paf"))):
     for rep in range(2):
         out = "/tmp/thm_e2e_out.%s" % name

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Quick stage timing on the GPU box (tuning aid, not the benchmark):
-python tools/perf.py [ref_len] [n_reads] [opts] [--cigars] [--bam] [--bgzf] [--fastq] [--fastq-bgzf] [--fastq-gzip]
+python tools/perf.py [ref_len] [n_reads] [opts] [--cigars] [--bam] [--bgzf] [--bam-sort] [--fastq] [--fastq-bgzf] [--fastq-gzip]
 --cigars: on the resident batch, thm_batch_fetch against thm_batch_fetch_cigars -- milliseconds and bytes moved to the
 host by each, and the device time of the two CIGAR passes (THM_T_CIGAR).
 --bam: on the resident batch, thm_batch_fetch_bam with both forms of the emit kernel (THM_BAM_EMIT) -- milliseconds,
@@ -9,6 +9,9 @@ at THM_BAM_LEVEL=0 minus thm_writer_wrap_bam of the same records: stored blocks,
 --bgzf (without --bam, which turns the host's deflate off): on the resident batch, thm_batch_fetch_bgzf -- milliseconds,
 bytes, THM_T_BGZF -- beside thm_batch_fetch_bam plus thm_writer_wrap_bam of the same records on 16 threads and on 1, and
 the compressed sizes of the device encoder, the host encoder and zlib level 1 over the device's cuts.
+--bam-sort: on the resident batch, thm_bam_sorter_add (the records stay on the device) against thm_batch_fetch_bam (they
+cross to the host), alternately in one session -- milliseconds of the calls and add_ms (key kernel + copy) -- then
+thm_bam_sorter_finish over everything added (sort_ms) and the drain with the two gather shapes alternating window by window.
 --fastq: the batch written out as one FASTQ block: thm_batch_upload_fastq -- milliseconds of the call and of its parse
 kernels (device_ms) -- beside thm_batch_upload_reads of the parsed batch, and the host's parse of the block on one thread.
 --fastq-bgzf: the same block BGZF-framed with Python's zlib (level 6, members of 0xff00 bytes): thm_batch_upload_fastq_bgzf
@@ -26,10 +29,11 @@ from thermite_amd import capi, synth
 cigars = "--cigars" in sys.argv
 bam = "--bam" in sys.argv
 bgzf = "--bgzf" in sys.argv
+bam_sort = "--bam-sort" in sys.argv
 fastq = "--fastq" in sys.argv
 fastq_bgzf = "--fastq-bgzf" in sys.argv
 fastq_gzip = "--fastq-gzip" in sys.argv
-sys.argv = [x for x in sys.argv if x not in ("--cigars", "--bam", "--bgzf", "--fastq", "--fastq-bgzf", "--fastq-gzip")]
+sys.argv = [x for x in sys.argv if x not in ("--cigars", "--bam", "--bgzf", "--bam-sort", "--fastq", "--fastq-bgzf", "--fastq-gzip")]
 if bam:
     __import__("os").environ["THM_BAM_LEVEL"] = "0"  # (read once, by the first BGZF block of the process)
 ref_len = int(sys.argv[1]) if len(sys.argv) > 1 else 4000000
@@ -121,6 +125,47 @@ for name, opts in (("ci", capi.CI_OPTS), ("default", capi.DEFAULT_OPTS)):
                   "median %.2f ms (min %.2f max %.2f); encoding = %.2f ms; outputs %s" % (threads, m1, lo1, hi1, m2, lo2, hi2, m1 - m2,
                                                                                          "equal" if o1 == o2 else "DIFFER"), flush=True)
             w.close()
+    if bam_sort:
+        K2 = 7
+        names = [b"SYN:%d 1:N:0:ACGT" % i for i in range(n)]
+        batch = dict(bases=bases, offsets=off, quals=np.full(len(bases), ord("F"), np.uint8), names=np.frombuffer(b"".join(names), np.uint8),
+                     name_off=np.cumsum([0] + [len(x) for x in names]).astype("<u8"))
+        b = capi.Aligner(ix, opts)
+        b.upload_reads(batch)
+        b.run(); b.sync()
+        srt = capi.BamSorter(b)
+        for _ in range(2):   # buffers grow
+            srt.add()
+            b.fetch_bam(copy=False)
+        ma, mk, mg = [], [], []
+        for _ in range(K2):   # alternately, in one session
+            t0 = time.perf_counter(); info = srt.add(); ma.append((time.perf_counter() - t0) * 1e3); mk.append(info["add_ms"])
+            t0 = time.perf_counter(); g = b.fetch_bam(copy=False); mg.append((time.perf_counter() - t0) * 1e3)
+        print("         sorter_add  median %.2f ms (min %.2f max %.2f, %d calls)  %d bytes stay on the device  add_ms median %.3f (min %.3f max %.3f)" % (
+            float(np.median(ma)), min(ma), max(ma), K2, info["n_bytes"], float(np.median(mk)), min(mk), max(mk)), flush=True)
+        print("         fetch_bam   median %.2f ms (min %.2f max %.2f, %d calls)  %d bytes to the host" % (float(np.median(mg)), min(mg), max(mg), K2, g.nbytes), flush=True)
+        t0 = time.perf_counter(); sort_ms = srt.finish(); wall = (time.perf_counter() - t0) * 1e3
+        print("         finish: %d records, %d bytes: sort_ms %.2f, call %.2f ms" % (info["total_records"], info["total_bytes"], sort_ms, wall), flush=True)
+        per = {"pieces": [], "records": []}
+        defl, k, t0 = [], 0, time.perf_counter()
+        while True:
+            shape = ("pieces", "records")[k & 1]
+            srt.gather_shape(shape)
+            v = srt.next(0, copy=False)
+            if v.n_raw_bytes == 0:
+                break
+            if v.n_raw_bytes == 256 * 0xff00:
+                per[shape].append(v.gather_ms)
+                defl.append(v.deflate_ms)
+            k += 1
+        wall = time.perf_counter() - t0
+        for shape, ms in per.items():
+            print("         gather[%-7s] %d windows of %d bytes: median %.3f ms (min %.3f max %.3f) = %.2f TB/s read+written" % (
+                shape, len(ms), 256 * 0xff00, float(np.median(ms)), min(ms), max(ms), 2 * 256 * 0xff00 / (float(np.median(ms)) * 1e-3) / 1e12), flush=True)
+        print("         deflate per window median %.3f ms (min %.3f max %.3f); drain of %d windows %.2f s = %.2f GB/s of records" % (
+            float(np.median(defl)), min(defl), max(defl), k, wall, info["total_bytes"] / wall / 1e9), flush=True)
+        srt.close()
+        b.close()
     if bgzf:
         import zlib
         K2 = 7
