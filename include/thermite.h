@@ -360,6 +360,20 @@ int32_t thm_build_suffix_array_gpu(const uint8_t* text, uint64_t n, void* sa_out
 int32_t thm_aligner_create(const thm_index*, const thm_align_opts*, int32_t device_id, thm_aligner** out);
 void thm_aligner_free(thm_aligner*);
 const char* thm_last_error(const thm_aligner*); /* NULL: the calling thread's last error from a call without an aligner */
+/* New options for the runs that start after the call (thm_aligner_create checks its options the same way).
+ * thm_batch_run keeps a copy of the options it starts with: a call between thm_batch_run and the run's
+ * thm_batch_sync or fetch does not touch that run -- if it overflows a pool, its replay runs under the copy.
+ * intron_mode is a bool (any nonzero value is true), reserved is ignored.
+ * THM_ERR_INVALID_ARG, and the options in force stay: min_seed_len outside 1..65535, min_aln_score_percent outside
+ * [0, 1] or NaN (src/main.rs:46-49).
+ * THM_ERR_OUT_OF_CONTRACT, likewise: a multimap_score_range on which align_read's own arithmetic overflows for some
+ * read of up to 65535 bases (src/aligner.rs:156-178) --
+ *   range > 2^64 - 1 - 65535                       (read.len() + range, usize);
+ *   (int32_t)range < 0 and max(65535, min_aln_score) - (int32_t)range > INT32_MAX
+ *                                                  (max_aln_score - (range as i32), i32).
+ * Every other range is taken as the reference takes it: the comparisons use (int32_t)range -- 2^32 - 1 is -1, and no
+ * read keeps an alignment -- and the narrowing of band and X-drop uses all 64 bits, so that 2^31 - 1 keeps every
+ * multimapper at the band the thresholds give. */
 int32_t thm_aligner_set_opts(thm_aligner*, const thm_align_opts*);
 /* the aligner's hipStream_t, as void* (for events / ExternalStream) */
 void* thm_aligner_stream(thm_aligner*);

@@ -250,6 +250,14 @@ int32_t thm_aligner_set_opts(thm_aligner* a, const thm_align_opts* o) {
   if (o->min_seed_len < 1 || o->min_seed_len > 65535) return fail(a, THM_ERR_INVALID_ARG, "min_seed_len out of range");
   if (!(o->min_aln_score_percent >= 0.0f && o->min_aln_score_percent <= 1.0f))
     return fail(a, THM_ERR_INVALID_ARG, "min_aln_score_percent must be within [0,1] (src/main.rs:46-49)");
+  // Ranges on which align_read's own arithmetic overflows (src/aligner.rs:156-178; a read has at most 65535 bases here, and
+  // max_aln_score lies between min_aln_score and the read's length): read.len() + range in usize, and
+  // max_aln_score - (range as i32) in i32 where the cast is negative.
+  const int64_t range_i32 = (int64_t)(int32_t)(uint32_t)o->multimap_score_range;
+  const int64_t max_score = std::max<int64_t>(65535, o->min_aln_score);
+  if (o->multimap_score_range > UINT64_MAX - 65535 || (range_i32 < 0 && max_score - range_i32 > INT32_MAX))
+    return fail(a, THM_ERR_OUT_OF_CONTRACT, "multimap_score_range %llu overflows in the reference's align_read",
+                (unsigned long long)o->multimap_score_range);
   a->opts = *o;
   return THM_OK;
 }

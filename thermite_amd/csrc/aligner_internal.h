@@ -181,6 +181,9 @@ struct thm_aligner {
   TprState tpr;    // (two more streams: see the struct)
   Event ev_fork, ev_join;  // untimed, made by thm_aligner_create
   thm_align_opts opts;
+  // the options thm_batch_run started the current run with: every replay of that run (thm_batch_sync, after a pool
+  // overflow) runs under them again, whatever thm_aligner_set_opts has been given since
+  thm_align_opts run_opts;
   std::string err;
 
   DBuf d_counters;

@@ -785,7 +785,10 @@ __global__ __launch_bounds__(TEAM > 0 ? 64 * TEAM : 256, TEAM > 0 ? 1 : MINW) vo
     int max_aln_score = min_aln_score;
     int band_width = (min_aln_score < 0) ? 0 : max(L - min_aln_score, 0);
     int x_drop = band_width;
-    const int range = (int)p.opts.multimap_score_range;
+    const int range = (int)p.opts.multimap_score_range;  // `as i32`: the comparisons (:156, :178)
+    // The narrowing (:162-171) takes the untruncated u64 in usize arithmetic.  Band, X-drop and score are at most L <= 65535,
+    // so L + r - score >= r: a range of 65535 or more never narrows, and min(range, 2^20) as an int narrows exactly.
+    const int narrow = (int)min(p.opts.multimap_score_range, (uint64_t)NARROW_RANGE_MAX);
     const bool intron_mode = p.opts.intron_mode != 0;
     bool band_bad = false;
     if (band_width > (int)p.max_bw || (CPL > 0 && 2 * band_width + 1 > 64 * CPL)) {
@@ -1286,7 +1289,7 @@ __global__ __launch_bounds__(TEAM > 0 ? 64 * TEAM : 256, TEAM > 0 ? 1 : MINW) vo
             acc_type = aln_type;
             PROF_MARK(c, PS_EMIT);
             // narrow the band (:162-172)
-            const int lim = max(L + range - sc, 0);
+            const int lim = max(L + narrow - sc, 0);
             band_width = min(band_width, lim);
             x_drop = min(x_drop, lim);
             max_aln_score = max(max_aln_score, sc);
@@ -1398,8 +1401,9 @@ __global__ __launch_bounds__(TEAM > 0 ? 64 * TEAM : 256, TEAM > 0 ? 1 : MINW) vo
 #endif
     uint32_t nres = 0;
     unsigned long long opb = 0;
-    if (!TM && n_acc == 1) {
-      // the common case: one candidate, which by construction passes retain() (its score is the maximum)
+    if (!TM && n_acc == 1 && range >= 0) {
+      // the common case: one candidate, which passes retain() (its score is the maximum) unless the range is negative as
+      // i32 -- then retain() asks for more than the maximum and keeps nothing (nres stays 0)
       nres = 1;
       if (lane == 0) order[0] = 0;
       opb = acc_bytes;

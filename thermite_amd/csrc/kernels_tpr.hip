@@ -453,7 +453,8 @@ __global__ __launch_bounds__(256, TPR_CTL_MINW) void extend_ctl_kernel(ExtendPar
         int max_aln_score = min_aln_score;
         int band_width = (min_aln_score < 0) ? 0 : max(L - min_aln_score, 0);
         int x_drop = band_width;
-        const int range = (int)p.opts.multimap_score_range;
+        const int range = (int)p.opts.multimap_score_range;  // `as i32`: the comparisons
+        const int narrow = (int)min(p.opts.multimap_score_range, (uint64_t)NARROW_RANGE_MAX);  // the narrowing (see extend_kernel)
         const bool intron_mode = p.opts.intron_mode != 0;
         if (band_width > (int)p.max_bw) {  // the wave-per-read kernel reports the inconsistency
           bail = true;
@@ -696,7 +697,7 @@ __global__ __launch_bounds__(256, TPR_CTL_MINW) void extend_ctl_kernel(ExtendPar
             cd[n_acc] = k;
             n_acc++;
             // narrow the band (:162-172)
-            const int lim = max(L + range - sc, 0);
+            const int lim = max(L + narrow - sc, 0);
             band_width = min(band_width, lim);
             x_drop = min(x_drop, lim);
             max_aln_score = max(max_aln_score, sc);

@@ -259,6 +259,10 @@ struct Cand {
 constexpr unsigned EXT_NQ = 8, EXT_QSTRIDE = 64;
 constexpr size_t QUEUE_BYTES = (EXT_NQ + 3) * EXT_QSTRIDE * 4;  // + the counters of the heavy-read list, the slow list and the team list
 constexpr unsigned HEAVY_HITS = 8;  // reads with at least this many seed hits are scheduled first
+// align_read narrows band and X-drop to L + multimap_score_range - score (src/aligner.rs:162-171, usize arithmetic with the
+// whole u64).  Nothing above 65535 ever narrows (band, X-drop and score are at most L <= 65535), so the kernels narrow
+// with min(range, this) as an int: exact, and no sum leaves the int's range.  (fin::MAX_RANGE, smem_finish.h, is the same.)
+constexpr uint64_t NARROW_RANGE_MAX = 1u << 20;
 // Reads with very many hits are worked on by a whole workgroup (extend_kernel, TEAM): speculative chunks of hits.
 // Which reads: a wave takes ~20 us per hit (a chain of dependent memory round trips) whatever else runs, the whole
 // machine ~4.5 ns per hit of a batch (256 CUs) -- a read whose hits take one wave longer than the rest of the batch

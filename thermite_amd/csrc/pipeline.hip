@@ -219,7 +219,7 @@ int enqueue_extend_t(thm_aligner* a, const ExtendPlan& plan) {
   ep.reads.bases = a->r_san.as<uint8_t>() + 16;
   ep.reads.offsets = a->r_offsets.as<uint64_t>();
   ep.reads.n_reads = n;
-  ep.opts = a->opts;
+  ep.opts = a->run_opts;
   ep.smems = a->s_smems.as<SmemT<C>>();
   // one record per read (offsets, SMEM run, candidate slice, first SMEM and its first occurrence): enqueue_plan_pack_t
   ep.read_recs = a->e_recs.as<ReadRecT<C>>();
@@ -327,7 +327,7 @@ int enqueue_run(thm_aligner* a) {
   hipStream_t s = a->stream;
   HIPCHK(a, hipEventRecord(a->ev[0], s));
   // (the seed stage's first kernel zeroes the run's control words and takes the counter snapshot)
-  int rc = enqueue_seed(a, (uint32_t)a->opts.min_seed_len, false);
+  int rc = enqueue_seed(a, (uint32_t)a->run_opts.min_seed_len, false);
   if (rc != THM_OK) return rc;
   HIPCHK(a, hipEventRecord(a->ev[1], s));
 
@@ -354,10 +354,10 @@ int enqueue_run(thm_aligner* a) {
   HIPCHK(a, a->s_slow.ensure((n + 1) * 8));
   HIPCHK(a, a->s_team.ensure((n + 1) * 8));
 
-  // length classes for the current options; lists for the extend stage
+  // length classes for the run's options; lists for the extend stage
   const uint32_t mk_cap_slow = std::max<uint32_t>(a->ix->max_tx_exons, 1);
   const bool retry_possible = a->ix->max_tx_exons > (uint32_t)FAST_MAX_YCLIPS + 1;
-  const ExtClasses cls = classify(a->len_hist, a->opts, mk_cap_slow);
+  const ExtClasses cls = classify(a->len_hist, a->run_opts, mk_cap_slow);
   a->n_slow_host = cls.n_slow;
   a->fast_max_len = cls.fast_max;
   a->slow_max_len = cls.slow_max;
@@ -603,6 +603,7 @@ int32_t thm_batch_run(thm_aligner* a) {
   HIPCHK(a, hipSetDevice(a->device));
   a->ran = false;
   a->synced = false;
+  a->run_opts = a->opts;  // a replay is this run again: under these, not under what set_opts brings later
   int rc = enqueue_run(a);
   if (rc == THM_OK) a->ran = true;
   return rc;
