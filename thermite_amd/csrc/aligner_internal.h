@@ -394,8 +394,36 @@ struct FastqBlock {
   float ms = 0;
 };
 enum { FQ_NOT_INFLATED = 2, FQ_NO_RECORD = 3 };  // beside 1 (parsed), 0 (declined: the host parser's) and errors (< 0)
+// What an upload entry point (thm_batch_upload_fastq, ..._bgzf, ..._gzip) made of its block; each copies it into its own
+// public info struct.
+struct FastqOutcome {
+  uint64_t n_reads = 0, n_bases = 0, n_name_bytes = 0;
+  uint64_t n_lines = 0;  // lines of the block that the batch consumed
+  const uint8_t* tail = nullptr;  // the block's bytes behind the batch (in the HBuf handed in)
+  uint64_t tail_len = 0;
+  uint32_t parsed_on_device = 0;
+  float parse_ms = 0;
+  // a parse_resident that returned 1
+  void take(const FastqBlock& b) {
+    n_reads = b.n_reads, n_bases = b.n_bases, n_name_bytes = b.n_name_bytes;
+    n_lines = 4 * b.n_reads;
+    parse_ms = b.ms;
+    tail_len = b.n - b.cut;
+  }
+};
 namespace thm {
 int parse_resident(thm_aligner* a, FastqBlock& b);
+// fastq.hip, the finish the three entry points share.
+// A block that stands on the host: copied into fq_raw and parsed there (parse_resident's codes).  On 1 `o` holds the
+// counts and the cut, and the bytes behind it are in `tail` (null: the batch is the whole block).
+int parse_host_block(thm_aligner* a, const uint8_t* blk, uint64_t n, bool whole, HBuf* tail, FastqOutcome& o);
+// The device parsed the batch: the aligner's batch state, and o.tail.
+void batch_parsed_on_device(thm_aligner* a, HBuf* tail, FastqOutcome& o);
+// The host parser's batch of a block the device did not parse: the batch bytes -- all of the block for a last block or
+// with no `tail`, else up to fastq_host_cut -- through fastq_parse_block and thm_batch_upload_reads, the lines and the
+// tail into `o`; *on_host counts a batch that has bytes.  The parser's error goes into a->err and the global error.
+int host_parser_batch(thm_aligner* a, const uint8_t* blk, uint64_t n, const std::string& path, uint64_t first_line, bool last_block,
+                      HBuf* tail, uint64_t* on_host, FastqOutcome& o);
 }
 int reset_queue(thm_aligner* a);
 inline int grid_blocks(const thm_aligner* a, uint64_t n_items, int waves_per_block, int blocks_per_cu) {

@@ -10,6 +10,7 @@
 #include <cstring>
 
 #include "aligner_internal.h"
+#include "fastq_cut.h"
 #include "fastq_device.h"
 #include "io_internal.h"
 
@@ -132,26 +133,65 @@ int thm::parse_resident(thm_aligner* a, FastqBlock& b) {
   return 1;
 }
 
-namespace {
-
-// the block goes up as it is, then the parse above
-int parse_on_device(thm_aligner* a, const uint8_t* raw, uint64_t n, thm_fastq_upload_info* info) {
+// ---- the finish of the three upload entry points (aligner_internal.h)
+int thm::parse_host_block(thm_aligner* a, const uint8_t* blk, uint64_t n, bool whole, HBuf* tail, FastqOutcome& o) {
   HIPCHK(a, a->fq_raw.ensure(n + 64));
-  HIPCHK(a, hipMemcpyAsync(a->fq_raw.p, raw, n, hipMemcpyHostToDevice, a->stream));
+  HIPCHK(a, hipMemcpyAsync(a->fq_raw.p, blk, n, hipMemcpyHostToDevice, a->stream));
   FastqBlock b;
   b.n = n;
-  b.host = raw;
+  b.host = blk;
+  b.whole = whole;
   const int d = parse_resident(a, b);
   if (d != 1) return d;
-  info->n_reads = b.n_reads;
-  info->n_bases = b.n_bases;
-  info->n_name_bytes = b.n_name_bytes;
-  info->on_device = 1;
-  info->device_ms = b.ms;
+  o.take(b);
+  if (tail && o.tail_len) {
+    HIPCHK(a, tail->ensure(o.tail_len));
+    memcpy(tail->p, blk + b.cut, o.tail_len);
+  }
   return 1;
 }
 
-}  // namespace
+void thm::batch_parsed_on_device(thm_aligner* a, HBuf* tail, FastqOutcome& o) {
+  a->reads_have_quals = true;
+  a->reads_named = true;
+  a->uploaded = true;
+  o.parsed_on_device = 1;
+  o.tail = tail && o.tail_len ? tail->as<uint8_t>() : nullptr;
+}
+
+int thm::host_parser_batch(thm_aligner* a, const uint8_t* blk, uint64_t n, const std::string& path, uint64_t first_line, bool last_block,
+                           HBuf* tail, uint64_t* on_host, FastqOutcome& o) {
+  // (a batch without a record included: nothing is counted as parsed then)
+  uint64_t cut = n, n_lines = 0;
+  if (tail && !last_block) cut = n ? fastq_host_cut(blk, n, &n_lines) : 0;
+  if (cut) ++*on_host;
+  HostBatch hb;
+  std::string err;
+  const int rc = fastq_parse_block((const char*)blk, (size_t)cut, path, first_line, last_block, hb, err);
+  if (rc != THM_OK) {
+    a->err = err;
+    set_global_error(err);
+    return rc;
+  }
+  const thm_read_batch v = hb.view();
+  const int urc = thm_batch_upload_reads(a, &v);
+  if (urc != THM_OK) return urc;
+  o.n_reads = v.n_reads;
+  o.n_bases = v.n_bases;
+  o.n_name_bytes = v.name_off[v.n_reads];
+  if (tail && last_block) {  // every line of the block, counted as fq::line_count counts them
+    for (uint64_t i = 0; i < n; i++) n_lines += blk[i] == (uint8_t)'\n';
+    if (n && blk[n - 1] != (uint8_t)'\n') n_lines++;
+  }
+  o.n_lines = n_lines;
+  o.tail_len = n - cut;
+  if (o.tail_len) {
+    HIPCHK(a, tail->ensure(o.tail_len));
+    memcpy(tail->p, blk + cut, o.tail_len);
+    o.tail = tail->as<uint8_t>();
+  }
+  return THM_OK;
+}
 
 extern "C" {
 
@@ -162,33 +202,24 @@ int32_t thm_batch_upload_fastq(thm_aligner* a, const uint8_t* raw, uint64_t n, c
   HIPCHK(a, hipSetDevice(a->device));
   a->uploaded = a->ran = a->synced = false;
   a->reads_named = false;
-  if (n) {
-    const int d = parse_on_device(a, raw, n, info);
+  FastqOutcome o;
+  int d = 0;
+  if (n) {  // the block goes up as it is and is parsed where it stands
+    d = parse_host_block(a, raw, n, true, nullptr, o);
     if (d < 0) return d;
-    if (d == 1) {
-      a->reads_have_quals = true;
-      a->reads_named = true;
-      a->uploaded = true;
-      a->fq_on_device++;
-      return THM_OK;
-    }
-    a->fq_on_host++;
   }
-  // not device-parsable (or empty): the host parser's batch, or its error with its message
-  HostBatch b;
-  std::string err;
-  const int rc = fastq_parse_block((const char*)raw, (size_t)n, path ? path : "", first_line, last_block != 0, b, err);
-  if (rc != THM_OK) {
-    a->err = err;
-    set_global_error(err);
-    return rc;
+  if (d == 1) {
+    batch_parsed_on_device(a, nullptr, o);
+    a->fq_on_device++;
+  } else {  // not device-parsable (or empty): the host parser's batch, or its error with its message
+    const int rc = host_parser_batch(a, raw, n, path ? path : "", first_line, last_block != 0, nullptr, &a->fq_on_host, o);
+    if (rc != THM_OK) return rc;
   }
-  const thm_read_batch v = b.view();
-  const int urc = thm_batch_upload_reads(a, &v);
-  if (urc != THM_OK) return urc;
-  info->n_reads = v.n_reads;
-  info->n_bases = v.n_bases;
-  info->n_name_bytes = v.name_off[v.n_reads];
+  info->n_reads = o.n_reads;
+  info->n_bases = o.n_bases;
+  info->n_name_bytes = o.n_name_bytes;
+  info->on_device = o.parsed_on_device;
+  info->device_ms = o.parse_ms;
   return THM_OK;
 }
 

@@ -119,6 +119,7 @@ int32_t thm_batch_upload_fastq_gzip(thm_aligner* a, thm_gzip_state* st, const ui
   uint64_t blk_n = head_len, consumed = 0;
   const uint8_t* host_blk = nullptr;  // the block on the host, once it is there
   int d = FQ_NO_RECORD;
+  FastqOutcome o;
   if (on_device) {
     gz::Summary sum;
     const int rc = inflate_on_device(a, st, bytes, n, chunk_bytes(), last_block != 0, head_len, &sum);
@@ -147,10 +148,7 @@ int32_t thm_batch_upload_fastq_gzip(thm_aligner* a, thm_gzip_state* st, const ui
         d = parse_resident(a, b);
         if (d < 0) return d;
         if (d == 1) {
-          info->n_reads = b.n_reads, info->n_bases = b.n_bases, info->n_name_bytes = b.n_name_bytes;
-          info->n_lines = 4 * b.n_reads;
-          info->parse_ms = b.ms;
-          info->tail_len = blk_n - b.cut;
+          o.take(b);
         } else {  // the parse is the host's: the inflated bytes come down, they are not inflated again
           a->fz_block.resize(blk_n);
           HIPCHK(a, hipMemcpyAsync(a->fz_block.data(), a->fq_raw.p, blk_n, hipMemcpyDeviceToHost, s));
@@ -170,69 +168,22 @@ int32_t thm_batch_upload_fastq_gzip(thm_aligner* a, thm_gzip_state* st, const ui
     if (n) a->gz_counts[1]++;
     blk_n = a->fz_block.size();
     host_blk = a->fz_block.data();
-    if (blk_n > head_len) {
-      HIPCHK(a, a->fq_raw.ensure(blk_n + 64));
-      HIPCHK(a, hipMemcpyAsync(a->fq_raw.p, host_blk, blk_n, hipMemcpyHostToDevice, s));
-      FastqBlock b;
-      b.n = blk_n;
-      b.host = host_blk;
-      b.whole = last_block != 0;
-      d = parse_resident(a, b);
-      if (d < 0) return d;
-      if (d == 1) {
-        info->n_reads = b.n_reads, info->n_bases = b.n_bases, info->n_name_bytes = b.n_name_bytes;
-        info->n_lines = 4 * b.n_reads;
-        info->parse_ms = b.ms;
-        info->tail_len = blk_n - b.cut;
-        if (info->tail_len) {
-          HIPCHK(a, tail.ensure(info->tail_len));
-          memcpy(tail.p, host_blk + b.cut, info->tail_len);
-        }
-      }
-    }
+    if (blk_n > head_len && (d = parse_host_block(a, host_blk, blk_n, last_block != 0, &tail, o)) < 0) return d;
   }
   info->n_inflated_bytes = blk_n - head_len;
   info->n_consumed_bytes = consumed;
   if (d == 1) {
-    a->reads_have_quals = true;
-    a->reads_named = true;
-    a->uploaded = true;
+    batch_parsed_on_device(a, &tail, o);
     a->gz_counts[2]++;
-    info->parsed_on_device = 1;
-    info->tail = info->tail_len ? tail.as<uint8_t>() : nullptr;
-    *st = *next;
-    return THM_OK;
+  } else {
+    const int rc = host_parser_batch(a, host_blk, blk_n, name, first_line, last_block != 0, &tail, &a->gz_counts[3], o);
+    if (rc != THM_OK) return rc;
   }
-  // ---- the host parser's batch of the batch bytes, or its error with its message (a batch without a record included:
-  // nothing is counted as parsed then)
-  uint64_t cut = blk_n, n_lines = 0;
-  if (!last_block) cut = blk_n ? fastq_host_cut(host_blk, blk_n, &n_lines) : 0;
-  if (cut) a->gz_counts[3]++;
-  HostBatch hb;
-  std::string err;
-  const int rc = fastq_parse_block((const char*)host_blk, (size_t)cut, name, first_line, last_block != 0, hb, err);
-  if (rc != THM_OK) {
-    a->err = err;
-    set_global_error(err);
-    return rc;
-  }
-  const thm_read_batch v = hb.view();
-  const int urc = thm_batch_upload_reads(a, &v);
-  if (urc != THM_OK) return urc;
-  info->n_reads = v.n_reads;
-  info->n_bases = v.n_bases;
-  info->n_name_bytes = v.name_off[v.n_reads];
-  if (last_block) {  // every line of the block, counted as fq::line_count counts them
-    for (uint64_t i = 0; i < blk_n; i++) n_lines += host_blk[i] == (uint8_t)'\n';
-    if (blk_n && host_blk[blk_n - 1] != (uint8_t)'\n') n_lines++;
-  }
-  info->n_lines = n_lines;
-  info->tail_len = blk_n - cut;
-  if (info->tail_len) {
-    HIPCHK(a, tail.ensure(info->tail_len));
-    memcpy(tail.p, host_blk + cut, info->tail_len);
-    info->tail = tail.as<uint8_t>();
-  }
+  info->n_reads = o.n_reads, info->n_bases = o.n_bases, info->n_name_bytes = o.n_name_bytes;
+  info->n_lines = o.n_lines;
+  info->tail = o.tail, info->tail_len = o.tail_len;
+  info->parsed_on_device = o.parsed_on_device;
+  info->parse_ms = o.parse_ms;
   *st = *next;
   return THM_OK;
 }

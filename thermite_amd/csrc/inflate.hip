@@ -12,6 +12,7 @@
 #include <cstring>
 
 #include "aligner_internal.h"
+#include "fastq_cut.h"
 #include "inflate_device.h"
 #include "io_internal.h"
 
@@ -93,22 +94,6 @@ int inflate_on_host(thm_aligner* a, const uint8_t* head, uint64_t head_len, cons
 
 }  // namespace
 
-// where the batch of a block that is not the last ends: behind its first 4 * (newlines / 4) lines; *n_lines: those
-uint64_t thm::fastq_host_cut(const uint8_t* blk, uint64_t n, uint64_t* n_lines) {
-  uint64_t nl = 0;
-  for (const uint8_t* q = blk; (q = (const uint8_t*)memchr(q, '\n', (size_t)(blk + n - q))) != nullptr; q++) nl++;
-  const uint64_t want = 4 * (nl / 4);
-  *n_lines = want;
-  if (want == 0) return 0;
-  uint64_t seen = 0;
-  const uint8_t* q = blk;
-  while ((q = (const uint8_t*)memchr(q, '\n', (size_t)(blk + n - q))) != nullptr) {
-    q++;
-    if (++seen == want) break;
-  }
-  return (uint64_t)(q - blk);
-}
-
 int thm::bgzf_block_on_host(const uint8_t* head, uint64_t head_len, const uint8_t* members, uint64_t n, const std::string& path,
                             bool last_block, std::vector<uint8_t>& block, uint64_t* cut, std::string& err) {
   const int rc = inflate_to(block, head, head_len, members, n, path, err);
@@ -138,6 +123,7 @@ int32_t thm_batch_upload_fastq_bgzf(thm_aligner* a, const uint8_t* head, uint64_
   uint64_t blk_n = head_len + total;
   const uint8_t* host_blk = nullptr;  // the block on the host, once it is there
   int d = FQ_NOT_INFLATED;
+  FastqOutcome o;
   if (on_device) {
     HIPCHK(a, a->fq_raw.ensure(blk_n + 64));
     if (head_len) HIPCHK(a, hipMemcpyAsync(a->fq_raw.p, head, head_len, hipMemcpyHostToDevice, s));
@@ -159,12 +145,7 @@ int32_t thm_batch_upload_fastq_bgzf(thm_aligner* a, const uint8_t* head, uint64_
       b.tail = &tail;
       d = parse_resident(a, b);
       if (d < 0) return d;
-      if (d == 1) {
-        info->n_reads = b.n_reads, info->n_bases = b.n_bases, info->n_name_bytes = b.n_name_bytes;
-        info->n_lines = 4 * b.n_reads;
-        info->parse_ms = b.ms;
-        info->tail_len = blk_n - b.cut;
-      }
+      if (d == 1) o.take(b);
     }
     on_device = d != FQ_NOT_INFLATED;
   }
@@ -185,67 +166,21 @@ int32_t thm_batch_upload_fastq_bgzf(thm_aligner* a, const uint8_t* head, uint64_
     blk_n = a->fz_block.size();
     host_blk = a->fz_block.data();
     d = FQ_NO_RECORD;
-    if (blk_n) {
-      HIPCHK(a, a->fq_raw.ensure(blk_n + 64));
-      HIPCHK(a, hipMemcpyAsync(a->fq_raw.p, host_blk, blk_n, hipMemcpyHostToDevice, s));
-      FastqBlock b;
-      b.n = blk_n;
-      b.host = host_blk;
-      b.whole = last_block != 0;
-      d = parse_resident(a, b);
-      if (d < 0) return d;
-      if (d == 1) {
-        info->n_reads = b.n_reads, info->n_bases = b.n_bases, info->n_name_bytes = b.n_name_bytes;
-        info->n_lines = 4 * b.n_reads;
-        info->parse_ms = b.ms;
-        info->tail_len = blk_n - b.cut;
-        if (info->tail_len) {
-          HIPCHK(a, tail.ensure(info->tail_len));
-          memcpy(tail.p, host_blk + b.cut, info->tail_len);
-        }
-      }
-    }
+    if (blk_n && (d = parse_host_block(a, host_blk, blk_n, last_block != 0, &tail, o)) < 0) return d;
   }
   info->n_inflated_bytes = blk_n - head_len;
   if (d == 1) {
-    a->reads_have_quals = true;
-    a->reads_named = true;
-    a->uploaded = true;
+    batch_parsed_on_device(a, &tail, o);
     a->fz_counts[2]++;
-    info->parsed_on_device = 1;
-    info->tail = info->tail_len ? tail.as<uint8_t>() : nullptr;
-    return THM_OK;
+  } else {
+    const int rc = host_parser_batch(a, host_blk, blk_n, name, first_line, last_block != 0, &tail, &a->fz_counts[3], o);
+    if (rc != THM_OK) return rc;
   }
-  // ---- the host parser's batch of the batch bytes, or its error with its message (a batch without a record included:
-  // nothing is counted as parsed then)
-  uint64_t cut = blk_n, n_lines = 0;
-  if (!last_block) cut = blk_n ? fastq_host_cut(host_blk, blk_n, &n_lines) : 0;
-  if (cut) a->fz_counts[3]++;
-  HostBatch hb;
-  std::string err;
-  const int rc = fastq_parse_block((const char*)host_blk, (size_t)cut, name, first_line, last_block != 0, hb, err);
-  if (rc != THM_OK) {
-    a->err = err;
-    set_global_error(err);
-    return rc;
-  }
-  const thm_read_batch v = hb.view();
-  const int urc = thm_batch_upload_reads(a, &v);
-  if (urc != THM_OK) return urc;
-  info->n_reads = v.n_reads;
-  info->n_bases = v.n_bases;
-  info->n_name_bytes = v.name_off[v.n_reads];
-  if (last_block) {  // every line of the block, counted as fq::line_count counts them
-    for (uint64_t i = 0; i < blk_n; i++) n_lines += host_blk[i] == (uint8_t)'\n';
-    if (blk_n && host_blk[blk_n - 1] != (uint8_t)'\n') n_lines++;
-  }
-  info->n_lines = n_lines;
-  info->tail_len = blk_n - cut;
-  if (info->tail_len) {
-    HIPCHK(a, tail.ensure(info->tail_len));
-    memcpy(tail.p, host_blk + cut, info->tail_len);
-    info->tail = tail.as<uint8_t>();
-  }
+  info->n_reads = o.n_reads, info->n_bases = o.n_bases, info->n_name_bytes = o.n_name_bytes;
+  info->n_lines = o.n_lines;
+  info->tail = o.tail, info->tail_len = o.tail_len;
+  info->parsed_on_device = o.parsed_on_device;
+  info->parse_ms = o.parse_ms;
   return THM_OK;
 }
 

@@ -18,7 +18,7 @@
 // connected by queues over a fixed set of reusable slots, so that the host work either
 // side of the hot path hides behind the GPUs (or the other way round: at tens of millions
 // of reads per second per GPU the host side is the bottleneck).
-// Records leave in input order whatever the number of GPUs.
+// Records leave in input order whatever the number of GPUs.  The stages are the member functions of Run, below.
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -39,6 +39,7 @@
 #include <thread>
 #include <vector>
 
+#include "fastq_cut.h"
 #include "inflate_device.h"
 #include "io_internal.h"
 #include "thermite_internal.h"
@@ -47,6 +48,174 @@ namespace {
 
 using Clock = std::chrono::steady_clock;
 double secs(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double>(b - a).count(); }
+
+// Runs f.  An exception (bad_alloc from a growing buffer, mostly) must not leave a thread body: std::terminate would
+// take the host process down, and a thread that simply stopped would leave the others waiting on its queue.  The
+// failure goes to fail(code, message) and comes back as the code; the thread goes on with its hand-over protocol.
+template <class F, class E>
+int guarded(F&& f, E&& fail) {
+  try {
+    return f();
+  } catch (const std::bad_alloc&) {
+    fail(THM_ERR_OOM, "out of host memory in the file driver");
+    return THM_ERR_OOM;
+  } catch (const std::exception& e) {
+    fail(THM_ERR_INTERNAL, std::string("file driver: ") + e.what());
+    return THM_ERR_INTERNAL;
+  } catch (...) {
+    fail(THM_ERR_INTERNAL, "file driver: unknown exception");
+    return THM_ERR_INTERNAL;
+  }
+}
+
+// the status of the run: the first failure stays
+struct Shared {
+  std::mutex mu;
+  int rc = THM_OK;
+  std::string msg;
+  void set(int code, const std::string& m) {
+    std::lock_guard<std::mutex> g(mu);
+    if (rc == THM_OK) {
+      rc = code;
+      msg = m;
+    }
+  }
+  bool failed() {
+    std::lock_guard<std::mutex> g(mu);
+    return rc != THM_OK;
+  }
+  // one step of a pipeline thread: its failure becomes the run's status
+  template <class F>
+  int step(F&& f) {
+    return guarded(f, [this](int code, const std::string& m) { set(code, m); });
+  }
+};
+
+// A file mapped read-only, unmapped when the value dies.  Movable, not copyable.
+struct Mapping {
+  const uint8_t* p = nullptr;
+  size_t len = 0;
+  Mapping() = default;
+  Mapping(Mapping&& o) noexcept : p(o.p), len(o.len) { o.p = nullptr, o.len = 0; }
+  Mapping& operator=(Mapping&& o) noexcept {
+    if (this != &o) {
+      reset();
+      p = o.p, len = o.len;
+      o.p = nullptr, o.len = 0;
+    }
+    return *this;
+  }
+  Mapping(const Mapping&) = delete;
+  Mapping& operator=(const Mapping&) = delete;
+  ~Mapping() { reset(); }
+  explicit operator bool() const { return p != nullptr; }
+  void reset() {
+    if (p) munmap((void*)p, len);
+    p = nullptr, len = 0;
+  }
+  bool is_gzip() const { return len >= 2 && p[0] == 0x1f && p[1] == 0x8b; }
+  // a regular file of min_len bytes or more; `sequential`: it is read front to back
+  static Mapping open(const char* path, size_t min_len, bool sequential) {
+    Mapping m;
+    const int fd = ::open(path, O_RDONLY);
+    if (fd < 0) return m;
+    struct stat st;
+    if (fstat(fd, &st) == 0 && S_ISREG(st.st_mode) && (size_t)st.st_size >= min_len && st.st_size > 0) {
+      void* q = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
+      if (q != MAP_FAILED) {
+        m.p = (const uint8_t*)q;
+        m.len = (size_t)st.st_size;
+        if (sequential) (void)madvise(q, m.len, MADV_SEQUENTIAL);
+      }
+    }
+    close(fd);
+    return m;
+  }
+};
+
+// The first text of a compressed file decides whether it goes to the device compressed: 4-line FASTQ begins with '@'
+// (FASTA and anything else keep the inflater thread and its parser).  *bytes_per_read: of that text, where it holds a read.
+bool first_text_is_fastq(const std::vector<uint8_t>& first, double* bytes_per_read) {
+  if (first.empty() || first[0] != '@') return false;
+  size_t nl = 0;
+  for (uint8_t c : first) nl += c == '\n';
+  if (nl >= 4) *bytes_per_read = (double)first.size() / (double)(nl / 4);
+  return true;
+}
+
+// A gzip input that is BGZF throughout (THM_FASTQ_DEVICE=2): the mapping and its members.  Eligible: gzip magic, every
+// member of the chain with the BGZF header (inflate_device.h, the rule the device takes), the chain ending exactly at the
+// end of the file, and the first member, inflated on the host, beginning with '@'.
+struct BgzfFile {
+  Mapping map;
+  std::vector<thm::inf::Member> tab;  // in_off - 12 - xlen is not kept: `at` below is
+  std::vector<uint64_t> at;           // first byte of every member, and the file's length behind the last
+  double bytes_per_read = 256;        // of the first member's text
+  bool open(const char* path) {
+    map = Mapping::open(path, 28, false);
+    if (!map) return false;
+    uint64_t p = 0, out = 0;
+    bool good = true;
+    while (p < map.len && good) {
+      thm::inf::Member mb;
+      uint64_t size = 0;
+      good = thm::inf::walk_member(map.p, map.len, p, out, &mb, &size);
+      if (!good) break;
+      tab.push_back(mb);
+      at.push_back(p);
+      p += size;
+      out += mb.isize;
+    }
+    at.push_back(p);
+    std::vector<uint8_t> first;
+    std::string err;
+    uint64_t cut = 0;
+    // the first member with text decides, and it must be the file's first
+    const bool ok = good && !tab.empty() && tab[0].isize != 0 &&
+                    thm::bgzf_block_on_host(nullptr, 0, map.p, at[1], path, true, first, &cut, err) == THM_OK &&
+                    first_text_is_fastq(first, &bytes_per_read);
+    if (!ok) map.reset();
+    return ok;
+  }
+};
+
+// A gzip input that is not BGZF throughout (THM_FASTQ_DEVICE=3): the mapping.  Eligible: gzip magic, and the first
+// bytes, inflated on the host, beginning with '@'.
+struct GzipFile {
+  Mapping map;
+  double bytes_per_read = 256;  // of the first blocks' text
+  bool open(const char* path) {
+    map = Mapping::open(path, 18, false);
+    if (!map) return false;
+    bool ok = false;
+    // the first blocks that end inside 64 KiB, or inside 1 MiB
+    for (size_t take = 65536; !ok; take *= 16) {
+      const size_t n = std::min(take, map.len);
+      std::unique_ptr<thm_gzip_state> zs(new thm_gzip_state());
+      std::vector<uint8_t> first;
+      std::string err;
+      uint64_t used = 0;
+      if (thm::GzInflater::inflate_slice(zs.get(), map.p, n, path, n == map.len, first, &used, err) != THM_OK) break;
+      if (!first.empty()) {
+        if (!first_text_is_fastq(first, &bytes_per_read)) break;
+        ok = true;
+      }
+      if (n == map.len || take >= (1u << 20)) break;
+    }
+    if (!ok) map.reset();
+    return ok;
+  }
+};
+
+// what the fetch step made of a batch, whichever fetch it was
+struct Fetched {
+  uint64_t n_reads = 0;
+  const int32_t* read_status = nullptr;
+  uint64_t n_failed_reads = 0;
+  uint64_t n_records = 0, n_aligned = 0;  // for the statistics (the host-format paths count them when they format)
+  const char* span = nullptr;  // bytes that are written as they are (THM_BAM_DEVICE=2: the members), where there are any
+  size_t span_len = 0;
+};
 
 struct Slot {
   uint64_t seq = 0;  // position of the batch in the input
@@ -58,7 +227,6 @@ struct Slot {
   std::string path;
   bool zmembers = false;    // raw_ptr / raw_len are whole BGZF members of the mapped input (THM_FASTQ_DEVICE=2) ...
   bool file_first = false;  // ... the first group of its file: the chain of tails starts empty, at line 1
-  std::vector<uint8_t> head;  // ... and the head it went up with (kept for the failed-read message)
   bool gzslice = false;     // a slice of the mapped plain-gzip input gz_map[0, gz_len) (THM_FASTQ_DEVICE=3): where it begins and
   const uint8_t* gz_map = nullptr;  // how long it is, is known at its turn in the chain of uploads only (file_first as above)
   size_t gz_len = 0;
@@ -66,11 +234,25 @@ struct Slot {
   thm::HostBatch reads;
   thm_batch_view res;  // into the pinned result buffers of the aligner that ran it (two sets per aligner, used alternately)
   thm_bam_view bam;    // ... or, with THM_BAM_DEVICE=1, the BAM records encoded on the device (likewise two sets)
-  thm_bgzf_view bgzf;  // ... or, with THM_BAM_DEVICE=2, their BGZF members deflated there (likewise)
-  uint64_t bgzf_aligned = 0;  // reads of the batch with an alignment (the members do not show it)
-  thm_bam_sort_info sorted;   // ... or, with THM_BAM_SORT=1, what adding them to the sorter reported (no bytes come back)
-  uint64_t sorted_aligned = 0;
+  Fetched got;
   bool aligned = false;
+  // A slot is reused across files and modes: every per-batch field starts from here (the buffers keep their memory),
+  // and a cut sets only what it means.
+  void reset(uint64_t seq_, const char* path_) {
+    seq = seq_;
+    path = path_;
+    raw_ptr = nullptr;
+    raw_len = 0;
+    first_line = 0;
+    last_block = false;
+    zmembers = file_first = gzslice = parsed = aligned = false;
+    gz_map = nullptr;
+    gz_len = 0;
+    reads.clear();
+    memset(&res, 0, sizeof res);
+    memset(&bam, 0, sizeof bam);
+    got = Fetched();
+  }
 };
 
 // A gzip FASTQ file on a thread of its own: inflate, cut into blocks of whole records, queue.  The reference reads its
@@ -100,10 +282,11 @@ struct Ahead {
   int kind = -1;  // -1 not known yet; 0 not 4-line FASTQ (the cutter runs the sequential parser on `r`); 1 blocks; 2 cannot open
   int open_rc = THM_OK;
   std::string open_err;
+  int dead_rc = THM_OK;  // the thread left with an exception: what wait_kind() / next() report once nothing is queued
   bool cancel = false;
   double busy_s = 0;
 
-  void run() {
+  void inflate() {
     const auto t0 = Clock::now();
     int rc = thm_fastq_open(path.c_str(), &r);
     bool fast = false;
@@ -147,9 +330,24 @@ struct Ahead {
       if (last) return;
     }
   }
-  void start() {
-    th = std::thread([this] { run(); });
+  // The thread body.  An exception anywhere in it (the open, a push into the queue) ends the file with an error in place
+  // of the thread: a file whose kind is not known yet cannot be opened, any other ends with a last block that fails, so
+  // that wait_kind() and next() always wake.
+  void run() {
+    (void)guarded([this] { inflate(); return (int)THM_OK; }, [this](int code, const std::string& m) {
+      {
+        std::lock_guard<std::mutex> g(mu);
+        dead_rc = code;
+        if (kind < 0) kind = 2, open_rc = code;
+        try {
+          open_err = m;
+        } catch (...) {
+        }
+      }
+      cv.notify_all();
+    });
   }
+  void start() { th = std::thread(&Ahead::run, this); }
   int wait_kind() {
     std::unique_lock<std::mutex> g(mu);
     cv.wait(g, [&] { return kind >= 0; });
@@ -158,7 +356,13 @@ struct Ahead {
   // the next block of the file (the last one holds no line, or an error); `old` goes back for reuse
   void next(Block& out, std::vector<char>& old) {
     std::unique_lock<std::mutex> g(mu);
-    cv.wait(g, [&] { return !ready.empty(); });
+    cv.wait(g, [&] { return !ready.empty() || dead_rc != THM_OK; });
+    if (ready.empty()) {
+      out = Block();
+      out.rc = dead_rc;
+      out.err = open_err;
+      return;
+    }
     out = std::move(ready.front());
     ready.pop_front();
     queued -= out.raw_len;
@@ -199,158 +403,879 @@ struct Queue {
   }
 };
 
-// A gzip input that is BGZF throughout (THM_FASTQ_DEVICE=2): the mapping and its members.  Eligible: gzip magic, every
-// member of the chain with the BGZF header (inflate_device.h, the rule the device takes), the chain ending exactly at the
-// end of the file, and the first member, inflated on the host, beginning with '@'.
-struct BgzfFile {
-  const uint8_t* map = nullptr;
-  size_t len = 0;
-  std::vector<thm::inf::Member> tab;  // in_off - 12 - xlen is not kept: `at` below is
-  std::vector<uint64_t> at;           // first byte of every member, and the file's length behind the last
-  double bytes_per_read = 256;        // of the first member's text
-  bool ok = false;
-  BgzfFile() = default;
-  BgzfFile(const BgzfFile&) = delete;
-  BgzfFile& operator=(const BgzfFile&) = delete;
-  ~BgzfFile() {
-    if (map) munmap((void*)map, len);  // (a file the run did not get to; otherwise the mapping was handed on)
-  }
-  void open(const char* path) {
-    const int fd = ::open(path, O_RDONLY);
-    if (fd < 0) return;
-    struct stat st;
-    if (fstat(fd, &st) == 0 && S_ISREG(st.st_mode) && st.st_size >= 28) {
-      void* m = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
-      if (m != MAP_FAILED) {
-        map = (const uint8_t*)m;
-        len = (size_t)st.st_size;
-      }
-    }
-    close(fd);
-    if (!map) return;
-    uint64_t p = 0, out = 0;
-    bool good = true;
-    while (p < len && good) {
-      thm::inf::Member mb;
-      uint64_t size = 0;
-      good = thm::inf::walk_member(map, len, p, out, &mb, &size);
-      if (!good) break;
-      tab.push_back(mb);
-      at.push_back(p);
-      p += size;
-      out += mb.isize;
-    }
-    at.push_back(p);
-    if (good && !tab.empty()) {
-      std::vector<uint8_t> first;
-      std::string err;
-      uint64_t cut = 0;
-      // the first member with text decides: FASTA and anything else keep today's path
-      size_t k = 0;
-      while (k + 1 < tab.size() && tab[k].isize == 0) k++;
-      if (thm::bgzf_block_on_host(nullptr, 0, map + at[k], at[k + 1] - at[k], path, true, first, &cut, err) == THM_OK && !first.empty() &&
-          first[0] == '@' && k == 0) {
-        size_t nl = 0;
-        for (uint8_t c : first) nl += c == '\n';
-        if (nl >= 4) bytes_per_read = (double)first.size() / (double)(nl / 4);
-        ok = true;
-      }
-    }
-    if (!ok) {
-      munmap((void*)map, len);
-      map = nullptr;
-      tab.clear();
-      at.clear();
-    }
-  }
-};
-
-// A gzip input that is not BGZF throughout (THM_FASTQ_DEVICE=3): the mapping.  Eligible: gzip magic, and the first
-// bytes, inflated on the host, beginning with '@' (FASTA and anything else keep the inflater thread and its parser).
-struct GzipFile {
-  const uint8_t* map = nullptr;
-  size_t len = 0;
-  double bytes_per_read = 256, ratio = 4;  // of the first blocks' text
-  bool ok = false;
-  GzipFile() = default;
-  GzipFile(const GzipFile&) = delete;
-  GzipFile& operator=(const GzipFile&) = delete;
-  ~GzipFile() {
-    if (map) munmap((void*)map, len);  // (a file the run did not get to; otherwise the mapping was handed on)
-  }
-  void open(const char* path) {
-    const int fd = ::open(path, O_RDONLY);
-    if (fd < 0) return;
-    struct stat st;
-    if (fstat(fd, &st) == 0 && S_ISREG(st.st_mode) && st.st_size >= 18) {
-      void* m = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
-      if (m != MAP_FAILED) {
-        map = (const uint8_t*)m;
-        len = (size_t)st.st_size;
-      }
-    }
-    close(fd);
-    if (!map) return;
-    // the first blocks that end inside 64 KiB, or inside 1 MiB
-    for (size_t take = 65536; !ok; take *= 16) {
-      const size_t n = std::min(take, len);
-      std::unique_ptr<thm_gzip_state> zs(new thm_gzip_state());
-      std::vector<uint8_t> first;
-      std::string err;
-      uint64_t used = 0;
-      if (thm::GzInflater::inflate_slice(zs.get(), map, n, path, n == len, first, &used, err) != THM_OK) break;
-      if (!first.empty()) {
-        if (first[0] != '@') break;
-        size_t nl = 0;
-        for (uint8_t c : first) nl += c == '\n';
-        if (nl >= 4) bytes_per_read = (double)first.size() / (double)(nl / 4);
-        if (used) ratio = std::max(1.0, (double)first.size() / (double)used);
-        ok = true;
-      }
-      if (n == len || take >= (1u << 20)) break;
-    }
-    if (!ok) {
-      munmap((void*)map, len);
-      map = nullptr;
-    }
-  }
-};
-
-struct Shared {
+// The hand-over from the parsers to the GPU threads: slots are put in any order and taken strictly by sequence number
+// (parsers may finish out of order; an aligner that ran ahead of a batch it would later have to wait for could block the
+// writer for good).
+class ToGpu {
   std::mutex mu;
-  int rc = THM_OK;
-  std::string msg;
-  void set(int code, const std::string& m) {
-    std::lock_guard<std::mutex> g(mu);
-    if (rc == THM_OK) {
-      rc = code;
-      msg = m;
+  std::condition_variable cv;
+  std::map<uint64_t, Slot*> ready;
+  uint64_t next = 0;
+  bool closed = false;
+
+ public:
+  void put(Slot* s) {
+    {
+      std::lock_guard<std::mutex> g(mu);
+      ready[s->seq] = s;
     }
+    cv.notify_all();
   }
-  bool failed() {
-    std::lock_guard<std::mutex> g(mu);
-    return rc != THM_OK;
-  }
-  // Runs one step of a pipeline thread.  An exception (bad_alloc from a growing buffer, mostly) must not leave the
-  // thread body: std::terminate would take the host process down, and a thread that simply stopped would leave the
-  // others waiting on its queue.  The step's failure becomes the run's status and the thread goes on with its
-  // hand-over protocol.
-  template <class F>
-  int step(F&& f) {
-    try {
-      return f();
-    } catch (const std::bad_alloc&) {
-      set(THM_ERR_OOM, "out of host memory in the file driver");
-      return THM_ERR_OOM;
-    } catch (const std::exception& e) {
-      set(THM_ERR_INTERNAL, std::string("file driver: ") + e.what());
-      return THM_ERR_INTERNAL;
-    } catch (...) {
-      set(THM_ERR_INTERNAL, "file driver: unknown exception");
-      return THM_ERR_INTERNAL;
+  void close() {  // the last parser has left
+    {
+      std::lock_guard<std::mutex> g(mu);
+      closed = true;
     }
+    cv.notify_all();
+  }
+  Slot* take_next() {  // null: the input is exhausted
+    Slot* s = nullptr;
+    {
+      std::unique_lock<std::mutex> g(mu);
+      cv.wait(g, [&] { return ready.count(next) || (closed && ready.empty()); });
+      auto it = ready.find(next);
+      if (it == ready.end()) return nullptr;
+      s = it->second;
+      ready.erase(it);
+      next++;
+    }
+    cv.notify_all();
+    return s;
   }
 };
+
+// The hand-over from the GPU threads to the writer: finished batches by sequence number, and how far the writer is.
+class ToWriter {
+  std::mutex mu;
+  std::condition_variable cv;
+  std::map<uint64_t, Slot*> done;
+  uint64_t next = 0;           // the batch the writer takes next
+  uint64_t n_batches_cut = 0;  // set when the cutter has seen the end of the input
+  bool cut_done = false;
+  uint64_t n_written = 0;  // batches the writer has finished
+
+ public:
+  void put(Slot* s) {
+    {
+      std::lock_guard<std::mutex> g(mu);
+      done[s->seq] = s;
+    }
+    cv.notify_all();
+  }
+  void close(uint64_t n_batches) {  // the cutter has cut its last batch
+    {
+      std::lock_guard<std::mutex> g(mu);
+      n_batches_cut = n_batches;
+      cut_done = true;
+    }
+    cv.notify_all();
+  }
+  Slot* take_next() {  // null: the input is exhausted
+    std::unique_lock<std::mutex> g(mu);
+    cv.wait(g, [&] { return done.count(next) || (cut_done && next >= n_batches_cut); });
+    auto it = done.find(next);
+    if (it == done.end()) return nullptr;
+    Slot* s = it->second;
+    done.erase(it);
+    next++;
+    return s;
+  }
+  void written(uint64_t seq) {
+    {
+      std::lock_guard<std::mutex> g(mu);
+      n_written = seq + 1;
+    }
+    cv.notify_all();
+  }
+  void wait_written(uint64_t seq, Shared& sh) {  // ... or until the run has failed
+    std::unique_lock<std::mutex> g(mu);
+    cv.wait(g, [&] { return n_written > seq || sh.failed(); });
+  }
+};
+
+// THM_FASTQ_DEVICE>=2: the chain of uploads.  Every slot of such a run takes its turn in input order for its upload (a
+// slot that is not compressed only passes the turn on).  The holder of the turn alone touches the Carry -- the tail that
+// is the next head, the line count, where the plain-gzip file of the turn stands -- which wait_turn() hands out; the
+// bytes and reads of the batches so far size the next groups and slices, from any thread.
+class UploadChain {
+ public:
+  struct Carry {
+    std::vector<uint8_t> tail;
+    uint64_t line = 1;
+    std::unique_ptr<thm_gzip_state> gz{new thm_gzip_state()};
+    uint64_t gz_pos = 0, gz_in = 0, gz_out = 0;  // the position in the file; compressed and inflated bytes so far, for the ratio
+    void begin_file() {
+      tail.clear();
+      line = 1;
+      memset(gz.get(), 0, sizeof(thm_gzip_state));
+      gz_pos = gz_in = gz_out = 0;
+    }
+    double ratio() const { return gz_in >= 65536 ? std::max(1.0, (double)gz_out / (double)gz_in) : 4.0; }
+  };
+  Carry& wait_turn(uint64_t seq) {
+    std::unique_lock<std::mutex> g(mu);
+    cv.wait(g, [&] { return turn == seq; });
+    return carry;
+  }
+  // file_done: the upload that tells whether its plain-gzip file has another slice found none (or failed)
+  void pass_turn(uint64_t seq, bool file_done_) {
+    {
+      std::lock_guard<std::mutex> g(mu);
+      file_done = file_done_;
+      turn = seq + 1;
+    }
+    cv.notify_all();
+  }
+  // the cutter, behind a slice: until that slice's upload has passed; true: the file has another slice
+  bool wait_passed(uint64_t seq) {
+    std::unique_lock<std::mutex> g(mu);
+    cv.wait(g, [&] { return turn > seq; });
+    return !file_done;
+  }
+  void count(uint64_t bytes, uint64_t reads) {
+    est_bytes += bytes;
+    est_reads += reads;
+  }
+  double bytes_per_read(double first_guess) const {
+    const uint64_t eb = est_bytes.load(), er = est_reads.load();
+    return er >= 64 ? (double)eb / (double)er : first_guess;
+  }
+
+ private:
+  std::mutex mu;
+  std::condition_variable cv;
+  uint64_t turn = 0;
+  bool file_done = false;
+  Carry carry;
+  std::atomic<uint64_t> est_bytes{0}, est_reads{0};
+};
+
+// what the knobs of the environment ask of a run to `format`
+struct Modes {
+  bool bam_sort = false;      // THM_BAM_SORT=1: the records of every batch stay on the device (thm_bam_sorter_add, uploads as with
+                              // THM_BAM_DEVICE=1); once the input is exhausted they are sorted there and leave window by window
+  bool bgzf_device = false;   // THM_BAM_DEVICE=2: ... and BGZF-compressed there too (thm_batch_fetch_bgzf): the formatting stage passes bytes on
+  bool bam_device = false;    // THM_BAM_DEVICE=1: BAM records are encoded on the device (thm_batch_fetch_bam) and only deflated here
+  // THM_FASTQ_DEVICE, in those modes only (the host needs no read bytes there):
+  bool fastq_device = false;  // =1: blocks of 4-line FASTQ go to the device unparsed (thm_batch_upload_fastq)
+  bool fastq_bgzf = false;    // =2: as =1, and input files that are BGZF throughout go to the device compressed
+                              // (thm_batch_upload_fastq_bgzf); every other file takes the path of =1
+  bool fastq_gzip = false;    // =3: as =2, and gzip files that are not BGZF throughout go to the device compressed too, in slices
+                              // (thm_batch_upload_fastq_gzip)
+  static Modes read(int32_t format) {
+    auto is = [](const char* name, const char* v) {
+      const char* e = getenv(name);
+      return e && !strcmp(e, v);
+    };
+    Modes m;
+    const bool bam = format == THM_FMT_BAM;
+    m.bam_sort = bam && is("THM_BAM_SORT", "1");
+    m.bgzf_device = !m.bam_sort && bam && is("THM_BAM_DEVICE", "2");
+    m.bam_device = m.bam_sort || m.bgzf_device || (bam && is("THM_BAM_DEVICE", "1"));
+    m.fastq_gzip = m.bam_device && is("THM_FASTQ_DEVICE", "3");
+    m.fastq_bgzf = m.fastq_gzip || (m.bam_device && is("THM_FASTQ_DEVICE", "2"));
+    m.fastq_device = m.fastq_bgzf || (m.bam_device && is("THM_FASTQ_DEVICE", "1"));
+    return m;
+  }
+};
+
+// the output file (or stdout): a regular file takes the chunks of a batch at their final offsets from several threads
+struct Output {
+  int fd = -1;
+  bool to_stdout = false, positional = false;
+  uint64_t off = 0;  // where the next bytes go (the writer stage's)
+  bool open(const char* path) {
+    to_stdout = strcmp(path, "-") == 0;
+    if (to_stdout) fflush(stdout);
+    fd = to_stdout ? 1 : ::open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
+    struct stat sb;
+    positional = fd >= 0 && !to_stdout && fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode);
+    return fd >= 0;
+  }
+  bool close() {
+    const bool ok = to_stdout || fd < 0 || ::close(fd) == 0;
+    fd = -1;
+    return ok;
+  }
+  bool write_all(const char* p, size_t n, uint64_t at) const {
+    while (n) {
+      const ssize_t k = positional ? pwrite(fd, p, n, (off_t)at) : write(fd, p, n);
+      if (k <= 0) return false;
+      p += k;
+      n -= (size_t)k;
+      at += (uint64_t)k;
+    }
+    return true;
+  }
+};
+
+// what the writer thread writes of one batch; two of them alternate (job k & 1 for batch k)
+struct WriteJob {
+  Slot* s = nullptr;
+  std::vector<const std::string*> chunks;
+  std::vector<std::pair<const char*, size_t>> spans;  // what is written: the chunks, or the span the fetch left
+  std::vector<uint64_t> at;
+};
+class WriteJobs {
+  std::mutex mu;
+  std::condition_variable cv;
+  std::deque<WriteJob*> q;  // nullptr = end of stream
+  WriteJob jobs[2];
+  bool busy[2] = {false, false};
+
+ public:
+  WriteJob& job(int k) { return jobs[k]; }  // the formatter's while it is not busy
+  void wait_free(int k) {  // job k's previous batch has left
+    std::unique_lock<std::mutex> g(mu);
+    cv.wait(g, [&] { return !busy[k]; });
+  }
+  void wait_idle() {
+    std::unique_lock<std::mutex> g(mu);
+    cv.wait(g, [&] { return !busy[0] && !busy[1]; });
+  }
+  void submit(int k) {
+    {
+      std::lock_guard<std::mutex> g(mu);
+      busy[k] = true;
+      q.push_back(&jobs[k]);
+    }
+    cv.notify_all();
+  }
+  void stop() {
+    {
+      std::lock_guard<std::mutex> g(mu);
+      q.push_back(nullptr);
+    }
+    cv.notify_all();
+  }
+  WriteJob* take() {
+    std::unique_lock<std::mutex> g(mu);
+    cv.wait(g, [&] { return !q.empty(); });
+    WriteJob* j = q.front();
+    q.pop_front();
+    return j;
+  }
+  void finished(WriteJob* j) {
+    {
+      std::lock_guard<std::mutex> g(mu);
+      busy[j - jobs] = false;
+    }
+    cv.notify_all();
+  }
+};
+
+// One run of thm_align_files_multi: the state the stages share, and the stages -- cut(), parse(), gpu(gi) and
+// format_and_write() with its write_jobs() thread and drain_sorted() -- each on a thread of its own (format_and_write on
+// the caller's).  What holds between them, whatever the modes:
+//   1. Slots reach the GPU threads strictly in seq order, whichever parser finished first (ToGpu).
+//   2. With THM_FASTQ_DEVICE>=2 every slot takes and passes the upload turn in seq order (UploadChain) -- slots that are not
+//      compressed, slots of a run that has failed and slots with no read included.
+//   3. For a gzip slice, file_done is published before the turn passes (pass_turn does both), and the cutter cuts the next
+//      slice of that file only after it (wait_passed).
+//   4. A fetch on an aligner waits until that aligner's second-last fetched batch has been written (ToWriter::wait_written):
+//      every aligner keeps the results of its last two fetches.
+//   5. Batches are formatted and written in seq order (ToWriter::take_next).  Two writer objects alternate, and job k & 1 is
+//      reused only after its write has left (WriteJobs).
+//   6. After any failure every thread still completes its hand-over protocol: every slot that was cut passes through every
+//      stage and back to q_free, so that no thread is left blocked, q_free does not starve and all threads join.
+//   7. Every mapping lives until every batch has been written: `maps` dies with the run, after the stages have joined.
+struct Run {
+  thm_aligner* const* aligners;
+  const uint32_t n_aligners;
+  const char* const* paths;
+  const uint32_t n_paths;
+  const int32_t format;
+  const uint64_t batch_reads;
+  const uint32_t n_threads;
+  const unsigned n_parsers;
+  const Modes m;
+  thm_writer* ws[2];  // used alternately: the chunks of batch k are views into writer k & 1 and are still being written while
+                      // batch k + 1 is formatted, so one object cannot stand in for both
+  Output& out;
+  thm_bam_sorter* sorter;
+
+  Shared sh;
+  thm_run_stats st;
+  std::mutex st_mu;  // parse_s / gpu_s / n_reads / n_batches are summed by several threads
+  // every aligner keeps the results of its last two fetches: two batches per GPU may be between fetch and write,
+  // one more is running; the parsers and the cutter work ahead of that
+  std::vector<Slot> slots;
+  Queue q_free, q_raw;
+  ToGpu to_gpu;
+  ToWriter to_writer;
+  UploadChain chain;
+  WriteJobs wj;
+  std::vector<Mapping> maps;  // of the input files that were cut in place (the cutter's, until it has joined)
+  std::mutex parsers_mu;
+  unsigned parsers_left;
+
+  Run(thm_aligner* const* aligners_, uint32_t n_aligners_, const char* const* paths_, uint32_t n_paths_, int32_t format_, uint64_t batch_reads_,
+      uint32_t n_threads_, unsigned n_parsers_, const Modes& m_, thm_writer* w0, thm_writer* w1, Output& out_, thm_bam_sorter* sorter_)
+      : aligners(aligners_), n_aligners(n_aligners_), paths(paths_), n_paths(n_paths_), format(format_), batch_reads(batch_reads_),
+        n_threads(n_threads_), n_parsers(n_parsers_), m(m_), ws{w0, w1}, out(out_), sorter(sorter_), slots(3 * n_aligners_ + n_parsers_ + 2),
+        parsers_left(n_parsers_) {
+    memset(&st, 0, sizeof st);
+    for (auto& s : slots) q_free.push(&s);
+  }
+
+  void add_parse_time(double s) {
+    std::lock_guard<std::mutex> g(st_mu);
+    st.parse_s += s;
+  }
+  // a free slot, reset for batch `seq` of `path`; null, and the run has failed, where that throws (the slot is free again)
+  Slot* fresh_slot(uint64_t seq, const char* path) {
+    Slot* s = q_free.pop();
+    if (sh.step([&] { s->reset(seq, path); return (int)THM_OK; }) == THM_OK) return s;
+    q_free.push(s);
+    return nullptr;
+  }
+  // header, trailer: bytes of the writer stage's own, at the end of what is written so far
+  void append(const thm_text& t) {
+    if (!t.len) return;
+    if (!out.write_all((const char*)t.data, t.len, out.off)) sh.set(THM_ERR_IO, "short write");
+    out.off += t.len;
+    st.n_output_bytes += t.len;
+  }
+
+  // ---- stage 1: cut the input into blocks of whole records
+  void cut();
+  void cut_members(BgzfFile& bf, const char* path, uint64_t& seq);
+  void cut_slices(GzipFile& gf, const char* path, uint64_t& seq);
+  void cut_blocks(const char* path, Ahead* ah, uint64_t& seq);
+  // ---- stage 2: parse blocks (several threads)
+  void parse();
+  // ---- stage 3: one thread per aligner
+  void gpu(uint32_t gi);
+  int upload_members(thm_aligner* a, Slot* s, UploadChain::Carry& c, bool& have);
+  int upload_slice(thm_aligner* a, Slot* s, UploadChain::Carry& c, bool& have, bool& file_done);
+  int fetch(thm_aligner* a, Slot* s);
+  int fail_by_name(thm_aligner* a, Slot* s, bool raw_up);
+  // ---- stage 4: format (the caller's thread, on the formatting threads of the writer) and write (one more thread), in
+  // input order, so that batch k + 1 is formatted while batch k is written
+  void format_and_write();
+  int format_batch(Slot* s, int k);
+  void write_jobs();
+  void release(Slot* s);
+  void drain_sorted();
+};
+
+// groups of whole members of about batch_reads reads, by the bytes per record of the batches so far
+void Run::cut_members(BgzfFile& bf, const char* path, uint64_t& seq) {
+  const size_t nm = bf.tab.size();
+  maps.push_back(std::move(bf.map));  // the run's before the first slot points into it: whatever happens here, it outlives the writes
+  const Mapping& map = maps.back();
+  for (size_t k = 0; k < nm && !sh.failed();) {
+    Slot* s = fresh_slot(seq, path);
+    if (!s) break;
+    const size_t k1 = thm::member_group_end(bf.tab, nm, k, chain.bytes_per_read(bf.bytes_per_read) * (double)batch_reads);
+    s->zmembers = true;
+    s->file_first = k == 0;
+    s->raw_ptr = (const char*)map.p + bf.at[k];
+    s->raw_len = (size_t)(bf.at[k1] - bf.at[k]);
+    s->last_block = k1 == nm;
+    k = k1;
+    seq++;
+    q_raw.push(s);
+  }
+}
+
+// one slot after the other: where a slice begins is known once the one before has gone up
+void Run::cut_slices(GzipFile& gf, const char* path, uint64_t& seq) {
+  maps.push_back(std::move(gf.map));  // (as in cut_members)
+  const Mapping& map = maps.back();
+  for (bool first = true, more = true; more && !sh.failed(); first = false) {
+    Slot* s = fresh_slot(seq, path);
+    if (!s) break;
+    s->gzslice = true;
+    s->file_first = first;
+    s->gz_map = map.p;
+    s->gz_len = map.len;
+    const uint64_t mine = seq++;
+    q_raw.push(s);
+    more = chain.wait_passed(mine);
+  }
+}
+
+// Blocks of text: ranges of the mapping of a plain (not gzip) FASTQ file, which is cut in place; the blocks of the file's
+// inflater thread; the blocks of a reader; or, for FASTA and anything that is not plain 4-line FASTQ, batches of the
+// sequential parser.
+void Run::cut_blocks(const char* path, Ahead* ah, uint64_t& seq) {
+  thm_fastq* r = nullptr;
+  bool fast = false;
+  if (ah) {
+    const int kind = ah->wait_kind();
+    if (kind == 2) {
+      sh.set(ah->open_rc, ah->open_err);
+      return;
+    }
+    fast = kind == 1;
+    r = ah->r;  // (the sequential parser's, when the file is not 4-line FASTQ: the inflater thread has left)
+  } else {
+    const int orc = thm_fastq_open(path, &r);
+    if (orc != THM_OK) {
+      sh.set(orc, thm_last_error(nullptr));
+      return;
+    }
+    fast = thm::fastq_is_plain_fastq(r);
+  }
+  const char* map = nullptr;
+  size_t map_len = 0;
+  if (fast && !ah) {
+    Mapping m = Mapping::open(path, 2, true);
+    if (m && !m.is_gzip()) {
+      map = (const char*)m.p;
+      map_len = m.len;
+      maps.push_back(std::move(m));  // (as in cut_members)
+    }
+  }
+  size_t map_pos = 0;
+  uint64_t map_line = 1;
+  for (;;) {
+    Slot* s = fresh_slot(seq, path);
+    if (!s) break;
+    const auto t0 = Clock::now();
+    uint64_t n_lines = 0;
+    int prc = THM_OK;
+    if (map) {
+      const size_t p = thm::mapped_cut(map, map_len, map_pos, batch_reads * 4, &n_lines);
+      s->raw_ptr = map + map_pos;
+      s->raw_len = p - map_pos;
+      s->last_block = p == map_len;
+      s->first_line = map_line;
+      map_line += n_lines;
+      map_pos = p;
+    } else if (fast && ah) {
+      Ahead::Block b;
+      prc = sh.step([&] { ah->next(b, s->raw); return (int)THM_OK; });
+      if (prc == THM_OK) {
+        s->raw.swap(b.raw);
+        s->raw_len = b.raw_len;
+        s->first_line = b.first_line;
+        s->last_block = b.last_block;
+        n_lines = b.n_lines;
+        prc = b.rc;
+        if (prc != THM_OK) thm::set_global_error(b.err);
+        s->raw_ptr = s->raw.data();
+      }
+    } else if (fast) {
+      prc = sh.step([&] { return thm::fastq_next_raw_block(r, batch_reads, s->raw, s->raw_len, n_lines, s->first_line, s->last_block); });
+      s->raw_ptr = s->raw.data();
+    } else {
+      prc = sh.step([&] { return thm::fastq_fill(r, batch_reads, s->reads); });
+      s->parsed = true;
+      n_lines = s->reads.n_reads();
+    }
+    if (!(fast && ah)) add_parse_time(secs(t0, Clock::now()));  // (an inflater thread counts its own time)
+    if (prc != THM_OK || sh.failed() || n_lines == 0) {
+      if (prc != THM_OK) sh.set(prc, thm_last_error(nullptr));
+      q_free.push(s);
+      break;
+    }
+    seq++;
+    q_raw.push(s);
+  }
+  if (ah) {
+    ah->stop();  // (closes the reader)
+    add_parse_time(ah->busy_s);
+  } else {
+    thm_fastq_close(r);
+  }
+}
+
+void Run::cut() {
+  uint64_t seq = 0;
+  // gzip inputs get an inflater thread each (Ahead), those of the next few files running ahead of their turn -- unless
+  // the file goes to the device compressed: no inflater thread then, it is cut by its members or in slices
+  std::vector<std::unique_ptr<Ahead>> ahead(n_paths);
+  std::vector<char> is_gz(n_paths, 0);
+  std::vector<std::unique_ptr<BgzfFile>> bgzf_files(n_paths);
+  std::vector<std::unique_ptr<GzipFile>> gzip_files(n_paths);
+  unsigned n_gz = 0;
+  (void)sh.step([&] { maps.reserve(n_paths); return (int)THM_OK; });
+  for (uint32_t pi = 0; pi < n_paths; pi++) {
+    unsigned char magic[2] = {0, 0};
+    const int fd = open(paths[pi], O_RDONLY);
+    if (fd >= 0) {
+      is_gz[pi] = pread(fd, magic, 2, 0) == 2 && magic[0] == 0x1f && magic[1] == 0x8b;
+      close(fd);
+    }
+    if (is_gz[pi] && m.fastq_bgzf) {
+      const auto t0 = Clock::now();
+      (void)sh.step([&] {
+        std::unique_ptr<BgzfFile> bf(new BgzfFile());
+        if (bf->open(paths[pi])) {
+          bgzf_files[pi] = std::move(bf);
+        } else if (m.fastq_gzip) {  // ... or in slices, wherever its blocks end
+          std::unique_ptr<GzipFile> gf(new GzipFile());
+          if (gf->open(paths[pi])) gzip_files[pi] = std::move(gf);
+        }
+        if (bgzf_files[pi] || gzip_files[pi]) is_gz[pi] = 0;
+        return (int)THM_OK;
+      });
+      add_parse_time(secs(t0, Clock::now()));
+    }
+    n_gz += is_gz[pi];
+  }
+  const unsigned ahead_files = std::max(1u, std::min(n_gz, std::max(2u, n_threads / 4)));
+  size_t ahead_bytes = (size_t)768 << 20;  // all inflaters together; THM_INFLATE_AHEAD_MB overrides
+  if (const char* e = getenv("THM_INFLATE_AHEAD_MB")) ahead_bytes = (size_t)std::max(1L, atol(e)) << 20;
+  auto top_up = [&](uint32_t from) {  // the inflaters of the next `ahead_files` gzip files at or behind `from`
+    unsigned running = 0;
+    for (uint32_t k = from; k < n_paths && running < ahead_files; k++) {
+      if (!is_gz[k]) continue;
+      running++;
+      if (ahead[k]) continue;
+      ahead[k].reset(new Ahead());
+      ahead[k]->path = paths[k];
+      ahead[k]->batch_reads = batch_reads;
+      ahead[k]->budget = ahead_bytes / ahead_files;
+      ahead[k]->start();
+    }
+    return (int)THM_OK;
+  };
+  for (uint32_t pi = 0; pi < n_paths && !sh.failed(); pi++) {
+    if (sh.step([&] { return top_up(pi); }) != THM_OK) break;
+    if (sh.step([&] {
+          if (bgzf_files[pi]) cut_members(*bgzf_files[pi], paths[pi], seq);
+          else if (gzip_files[pi]) cut_slices(*gzip_files[pi], paths[pi], seq);
+          else cut_blocks(paths[pi], is_gz[pi] ? ahead[pi].get() : nullptr, seq);
+          return (int)THM_OK;
+        }) != THM_OK)
+      break;
+  }
+  for (auto& a : ahead)
+    if (a) a->stop();  // (inflaters started ahead of a run that failed)
+  to_writer.close(seq);
+  for (unsigned k = 0; k < n_parsers; k++) q_raw.push(nullptr);
+}
+
+void Run::parse() {
+  while (Slot* s = q_raw.pop()) {
+    if (!s->parsed && !m.fastq_device && !sh.failed()) {  // (with THM_FASTQ_DEVICE the block passes through as it is)
+      const auto t0 = Clock::now();
+      std::string err;
+      const int prc = sh.step([&] { return thm::fastq_parse_block(s->raw_ptr, s->raw_len, s->path, s->first_line, s->last_block, s->reads, err); });
+      add_parse_time(secs(t0, Clock::now()));
+      if (prc != THM_OK) sh.set(prc, err);
+    }
+    to_gpu.put(s);
+  }
+  std::lock_guard<std::mutex> g(parsers_mu);
+  if (--parsers_left == 0) to_gpu.close();
+}
+
+// a group of members at its turn in the chain: the tail so far is its head
+int Run::upload_members(thm_aligner* a, Slot* s, UploadChain::Carry& c, bool& have) {
+  if (s->file_first) c.begin_file();
+  s->first_line = c.line;
+  if (!have) return THM_OK;
+  thm_fastq_bgzf_info zi;
+  memset(&zi, 0, sizeof zi);
+  const int rc = sh.step([&] {
+    const size_t head_len = c.tail.size();
+    const int r2 = (int)thm_batch_upload_fastq_bgzf(a, c.tail.data(), head_len, (const uint8_t*)s->raw_ptr, s->raw_len, s->path.c_str(), s->first_line,
+                                                    s->last_block ? 1 : 0, &zi);
+    if (r2 == THM_OK) {
+      c.tail.assign(zi.tail, zi.tail + zi.tail_len);
+      c.line += zi.n_lines;
+      chain.count(head_len + zi.n_inflated_bytes - zi.tail_len, zi.n_reads);
+    }
+    return r2;
+  });
+  if (rc == THM_OK && zi.n_reads == 0) have = false;  // (a group without a whole record: all of it is tail)
+  return rc;
+}
+
+// A slice of a plain-gzip file at its turn in the chain, where the slice before it ended: of about batch_reads reads, by
+// the bytes per record and the ratio of the batches so far; doubled while no block ends inside it.  file_done: the file
+// has no further slice (a run that has failed cuts none).
+int Run::upload_slice(thm_aligner* a, Slot* s, UploadChain::Carry& c, bool& have, bool& file_done) {
+  if (s->file_first) c.begin_file();
+  s->first_line = c.line;
+  file_done = true;
+  if (!have) return THM_OK;
+  thm_fastq_gzip_info zi;
+  memset(&zi, 0, sizeof zi);
+  uint64_t want = (uint64_t)(chain.bytes_per_read(256.0) * (double)batch_reads / c.ratio()) + 4096;
+  const int rc = sh.step([&] {
+    const size_t head_len = c.tail.size();
+    for (;;) {
+      const uint64_t left = s->gz_len - c.gz_pos, n = std::min<uint64_t>(want, left);
+      s->last_block = n == left;
+      const int r2 = (int)thm_batch_upload_fastq_gzip(a, c.gz.get(), c.tail.data(), head_len, s->gz_map + c.gz_pos, n, s->path.c_str(), s->first_line,
+                                                      s->last_block ? 1 : 0, &zi);
+      if (r2 != THM_OK) return r2;
+      if (zi.n_consumed_bytes == 0 && !s->last_block) {
+        want = 2 * n;
+        continue;
+      }
+      c.gz_pos += zi.n_consumed_bytes;
+      c.gz_in += zi.n_consumed_bytes;
+      c.gz_out += zi.n_inflated_bytes;
+      c.tail.assign(zi.tail, zi.tail + zi.tail_len);
+      c.line += zi.n_lines;
+      chain.count(head_len + zi.n_inflated_bytes - zi.tail_len, zi.n_reads);
+      return (int)THM_OK;
+    }
+  });
+  file_done = rc != THM_OK || s->last_block;
+  if (rc == THM_OK && zi.n_reads == 0) have = false;  // (a slice without a whole record: all of it is tail)
+  return rc;
+}
+
+// the fetch the modes ask for, into s->got (and the view the formatting needs, where the host formats)
+int Run::fetch(thm_aligner* a, Slot* s) {
+  Fetched& f = s->got;
+  int rc;
+  if (m.bam_sort) {
+    thm_bam_sort_info v;
+    memset(&v, 0, sizeof v);
+    rc = thm::bam_sorter_add(sorter, 0, &v, &f.n_aligned);
+    f.n_reads = v.n_reads, f.read_status = v.read_status, f.n_failed_reads = v.n_failed_reads, f.n_records = v.n_records;
+  } else if (m.bgzf_device) {
+    thm_bgzf_view v;
+    memset(&v, 0, sizeof v);
+    rc = thm::batch_fetch_bgzf(a, 0, &v, &f.n_aligned);
+    f.n_reads = v.n_reads, f.read_status = v.read_status, f.n_failed_reads = v.n_failed_reads, f.n_records = v.n_records;
+    f.span = (const char*)v.data, f.span_len = (size_t)v.n_bytes;
+  } else if (m.bam_device) {
+    rc = thm_batch_fetch_bam(a, 0, &s->bam);
+    f.n_reads = s->bam.n_reads, f.read_status = s->bam.read_status, f.n_failed_reads = s->bam.n_failed_reads;
+  } else {
+    rc = thm_batch_fetch(a, &s->res);
+    f.n_reads = s->res.n_reads, f.read_status = s->res.read_status, f.n_failed_reads = s->res.n_failed_reads;
+  }
+  return rc;
+}
+
+// The reference aligns every read or panics; a read this build cannot take fails the run, by name.  The name is the
+// host's where the host parsed the batch; a block that went up raw stands on the device with its names.
+int Run::fail_by_name(thm_aligner* a, Slot* s, bool raw_up) {
+  const Fetched& f = s->got;
+  uint64_t bad = 0;
+  while (bad < f.n_reads && f.read_status[bad] == THM_OK) bad++;
+  thm_read_batch v = s->reads.view();
+  if (raw_up) {
+    memset(&v, 0, sizeof v);
+    (void)sh.step([&] { return (int)thm_batch_fetch_reads(a, &v); });
+  }
+  std::string name;
+  if (bad < v.n_reads) name.assign((const char*)v.names + v.name_off[bad], (size_t)(v.name_off[bad + 1] - v.name_off[bad]));
+  sh.set(f.read_status[bad], "read " + name + (f.read_status[bad] == THM_ERR_UNSUPPORTED
+                                                   ? ": longer than 65535 bases, or its DP trace exceeds the device-memory budget"
+                                                   : ": hits a condition that panics in the reference (lift_mem_to_tx / lift_tx_to_gx)"));
+  return f.read_status[bad];
+}
+
+void Run::gpu(uint32_t gi) {
+  thm_aligner* a = aligners[gi];
+  std::deque<uint64_t> fetched;  // sequence numbers of this aligner's fetched batches, oldest first
+  while (Slot* s = to_gpu.take_next()) {
+    // a raw block goes up as it is and is parsed there; the slot keeps its bytes (its own buffer, or the mapping) until
+    // it is released behind the write
+    const bool raw_up = m.fastq_device && !s->parsed;
+    bool have = !sh.failed() && (raw_up || s->reads.n_reads() != 0);  // (a blank tail cut into a block of its own holds no read)
+    const auto t0 = Clock::now();
+    int up_rc = THM_OK;
+    if (m.fastq_bgzf) {  // this slot's turn in the chain of uploads
+      UploadChain::Carry& c = chain.wait_turn(s->seq);
+      bool file_done = false;
+      if (s->zmembers) up_rc = upload_members(a, s, c, have);
+      if (s->gzslice) up_rc = upload_slice(a, s, c, have, file_done);
+      chain.pass_turn(s->seq, file_done);
+    }
+    if (have && raw_up && !s->zmembers && !s->gzslice) {
+      thm_fastq_upload_info fi;
+      memset(&fi, 0, sizeof fi);
+      up_rc = sh.step([&] {
+        return (int)thm_batch_upload_fastq(a, (const uint8_t*)s->raw_ptr, s->raw_len, s->path.c_str(), s->first_line, s->last_block ? 1 : 0, &fi);
+      });
+      if (up_rc == THM_OK && fi.n_reads == 0) have = false;  // (that blank tail)
+    }
+    if (have) {
+      const thm_read_batch rb = s->reads.view();
+      int grc = sh.step([&] {
+        int g2 = raw_up ? up_rc : m.bam_device ? thm_batch_upload_reads(a, &rb) : thm_batch_upload(a, rb.bases, rb.offsets, rb.n_reads);
+        if (g2 == THM_OK) g2 = thm_batch_run(a);
+        if (g2 == THM_OK) g2 = thm_batch_sync(a);
+        return g2;
+      });
+      const auto t1 = Clock::now();
+      // the fetch below reuses the buffers of this aligner's second-last fetch: that batch must have been written
+      if (grc == THM_OK && fetched.size() >= 2) to_writer.wait_written(fetched[fetched.size() - 2], sh);
+      const auto t2 = Clock::now();
+      if (grc == THM_OK) grc = sh.step([&] { return fetch(a, s); });
+      if (grc == THM_OK && s->got.n_failed_reads) grc = fail_by_name(a, s, raw_up);
+      if (grc != THM_OK) {
+        sh.set(grc, thm_last_error(a));
+      } else {
+        s->aligned = true;
+        fetched.push_back(s->seq);
+        if (fetched.size() > 4) fetched.pop_front();
+      }
+      std::lock_guard<std::mutex> g(st_mu);
+      st.gpu_s += secs(t0, t1) + secs(t2, Clock::now());
+      if (grc == THM_OK) {
+        st.n_reads += s->got.n_reads;
+        st.n_batches += 1;
+      }
+    }
+    to_writer.put(s);
+  }
+}
+
+void Run::release(Slot* s) {
+  to_writer.written(s->seq);
+  q_free.push(s);
+}
+
+// the writer thread: the spans of a job at their offsets (those of a regular file from several threads)
+void Run::write_jobs() {
+  while (WriteJob* j = wj.take()) {
+    const auto t1 = Clock::now();
+    std::vector<char> good(j->spans.size(), 1);
+    auto put = [&](size_t c) { good[c] = out.write_all(j->spans[c].first, j->spans[c].second, j->at[c]) ? 1 : 0; };
+    if (out.positional && j->spans.size() > 1) {
+      std::vector<std::thread> th;
+      for (size_t c = 1; c < j->spans.size(); c++) th.emplace_back(put, c);
+      put(0);
+      for (auto& x : th) x.join();
+    } else {
+      for (size_t c = 0; c < j->spans.size(); c++) put(c);
+    }
+    for (char g : good)
+      if (!g) sh.set(THM_ERR_IO, "short write");
+    st.write_s += secs(t1, Clock::now());
+    release(j->s);
+    wj.finished(j);
+  }
+}
+
+// Batch s into job k: the spans to write and their offsets, and the batch's part in the statistics.  Where the fetch
+// left a span there is nothing to format: the members leave as one chunk, written from the aligner's pinned set (the GPU
+// thread waits for this batch to be written before the fetch that reuses the set).
+int Run::format_batch(Slot* s, int k) {
+  WriteJob& j = wj.job(k);
+  Fetched& f = s->got;
+  const auto t0 = Clock::now();
+  const thm_read_batch rb = s->reads.view();
+  const int wrc = sh.step([&] {
+    if (m.bgzf_device) return (int)THM_OK;
+    return m.bam_device ? thm::writer_wrap_bam_chunks(ws[k], &s->bam, j.chunks) : thm::writer_format_chunks(ws[k], &rb, &s->res, j.chunks);
+  });
+  st.format_s += secs(t0, Clock::now());
+  if (wrc != THM_OK) {
+    sh.set(wrc, thm_last_error(nullptr));
+    return wrc;
+  }
+  j.spans.clear();
+  if (m.bgzf_device) j.spans.emplace_back(f.span, f.span_len);
+  else
+    for (const std::string* c : j.chunks) j.spans.emplace_back(c->data(), c->size());
+  j.at.resize(j.spans.size());
+  for (size_t c = 0; c < j.spans.size(); c++) {
+    j.at[c] = out.off;
+    out.off += j.spans[c].second;
+    st.n_output_bytes += j.spans[c].second;
+  }
+  if (m.bgzf_device) return THM_OK;
+  if (m.bam_device) {
+    // a read is unmapped when its first record carries flag 4 (bytes 18 .. 19 of the record)
+    const thm_bam_view& bv = s->bam;
+    for (uint64_t r = 0; r < bv.n_reads; r++) f.n_aligned += !(bv.data[bv.read_rec_off[r] + 18] & 4);
+    f.n_records = bv.n_records;
+  } else {
+    const thm_batch_view& v = s->res;
+    for (uint64_t r = 0; r < v.n_reads; r++) {
+      const uint64_t kk = v.read_aln_off[r + 1] - v.read_aln_off[r];
+      f.n_aligned += kk != 0;
+      f.n_records += kk ? kk : (format == THM_FMT_PAF ? 0 : 1);
+    }
+  }
+  return THM_OK;
+}
+
+void Run::format_and_write() {
+  thm_text t;
+  // (a sorted file's header is written when the drain begins)
+  if (!m.bam_sort && thm_writer_header(ws[0], &t) == THM_OK) append(t);
+  std::thread wthread(&Run::write_jobs, this);
+  for (;;) {
+    Slot* s = to_writer.take_next();
+    if (!s) break;  // the input is exhausted
+    const int k = (int)(s->seq & 1);
+    wj.wait_free(k);  // the writer object (and job) of this parity: its previous batch must have left
+    bool queued = false;
+    // (after a failure nothing is formatted any more; a sorted run's batch is in the sorter: nothing leaves before the
+    // input is exhausted)
+    if (!sh.failed() && s->aligned && (m.bam_sort || format_batch(s, k) == THM_OK)) {
+      st.n_aligned_reads += s->got.n_aligned;
+      st.n_records += s->got.n_records;
+      if (!m.bam_sort) {
+        wj.job(k).s = s;
+        wj.submit(k);
+        queued = true;
+      }
+    }
+    if (!queued) {
+      // nothing to write for this batch: it still leaves in order behind the writes that are queued
+      wj.wait_idle();
+      release(s);
+    }
+  }
+  wj.wait_idle();
+  wj.stop();
+  wthread.join();
+  if (m.bam_sort && !sh.failed()) drain_sorted();
+  if (!sh.failed() && thm_writer_trailer(ws[0], &t) == THM_OK) append(t);
+}
+
+// the drain: sort, the sorted header, then window after window -- window k is written (from one of the sorter's two
+// pinned sets) while the device gathers and deflates window k + 1
+void Run::drain_sorted() {
+  struct Write {  // one window on its way out, on a thread of its own
+    Run* run;
+    thm_bam_sorted_view v;
+    uint64_t at = 0;
+    bool ok = true;
+    std::thread th;
+    void go() {
+      const auto t2 = Clock::now();
+      ok = run->out.write_all((const char*)v.data, (size_t)v.n_bytes, at);
+      run->st.write_s += secs(t2, Clock::now());
+    }
+    void join() {
+      if (th.joinable()) th.join();
+      if (!ok) run->sh.set(THM_ERR_IO, "short write");
+      ok = true;
+    }
+  } wr;
+  wr.run = this;
+  thm_text t;
+  const auto t0 = Clock::now();
+  int drc = sh.step([&] { return (int)thm_bam_sorter_finish(sorter, nullptr); });
+  st.format_s += secs(t0, Clock::now());
+  if (drc != THM_OK) sh.set(drc, thm_last_error(aligners[0]));
+  if (drc == THM_OK && thm_writer_header_sorted(ws[0], &t) == THM_OK) append(t);
+  while (drc == THM_OK && !sh.failed()) {
+    thm_bam_sorted_view v;
+    const auto t1 = Clock::now();
+    drc = sh.step([&] { return (int)thm_bam_sorter_next(sorter, 0, 0, &v); });
+    st.format_s += secs(t1, Clock::now());
+    wr.join();  // the next call reuses the set the write before last came from
+    if (drc != THM_OK) {
+      sh.set(drc, thm_last_error(aligners[0]));
+      break;
+    }
+    if (v.n_raw_bytes == 0) break;
+    wr.v = v;
+    wr.at = out.off;
+    out.off += v.n_bytes;
+    st.n_output_bytes += v.n_bytes;
+    wr.th = std::thread(&Write::go, &wr);
+  }
+  wr.join();
+}
 
 }  // namespace
 
@@ -363,29 +1288,11 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
   for (uint32_t i = 0; i < n_aligners; i++)
     if (!aligners[i]) return THM_ERR_INVALID_ARG;
   if (batch_reads == 0) batch_reads = 250000;
-  // THM_BAM_DEVICE=1: BAM records are encoded on the device (thm_batch_fetch_bam) and only deflated here
-  const char* bam_dev_env = getenv("THM_BAM_DEVICE");
-  // THM_BAM_DEVICE=2: ... and BGZF-compressed there too (thm_batch_fetch_bgzf): the formatting stage passes bytes on
-  // THM_BAM_SORT=1: the records of every batch stay on the device (thm_bam_sorter_add, uploads as with THM_BAM_DEVICE=1);
-  // once the input is exhausted they are sorted there and leave window by window as finished members
-  const char* bam_sort_env = getenv("THM_BAM_SORT");
-  const bool bam_sort = format == THM_FMT_BAM && bam_sort_env && !strcmp(bam_sort_env, "1");
-  if (bam_sort && n_aligners > 1) {
+  const Modes m = Modes::read(format);
+  if (m.bam_sort && n_aligners > 1) {
     thm::set_global_error("thm_align_files_multi: THM_BAM_SORT=1 takes one aligner (merging across devices is not done)");
     return THM_ERR_INVALID_ARG;
   }
-  const bool bgzf_device = !bam_sort && format == THM_FMT_BAM && bam_dev_env && !strcmp(bam_dev_env, "2");
-  const bool bam_device = bam_sort || bgzf_device || (format == THM_FMT_BAM && bam_dev_env && !strcmp(bam_dev_env, "1"));
-  // THM_FASTQ_DEVICE=1, in those two modes only (the host needs no read bytes there): blocks of 4-line FASTQ go to the
-  // device unparsed (thm_batch_upload_fastq)
-  const char* fq_dev_env = getenv("THM_FASTQ_DEVICE");
-  // THM_FASTQ_DEVICE=2: as =1, and input files that are BGZF throughout go to the device compressed
-  // (thm_batch_upload_fastq_bgzf); every other file takes the path of =1
-  // THM_FASTQ_DEVICE=3: as =2, and gzip files that are not BGZF throughout go to the device compressed too, in slices
-  // (thm_batch_upload_fastq_gzip)
-  const bool fastq_gzip = bam_device && fq_dev_env && !strcmp(fq_dev_env, "3");
-  const bool fastq_bgzf = fastq_gzip || (bam_device && fq_dev_env && !strcmp(fq_dev_env, "2"));
-  const bool fastq_device = fastq_bgzf || (bam_device && fq_dev_env && !strcmp(fq_dev_env, "1"));
   const thm_index* ix = thm_aligner_index(aligners[0]);
   for (uint32_t i = 1; i < n_aligners; i++)
     if (thm_aligner_index(aligners[i]) != ix) {
@@ -396,777 +1303,48 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
   if (n_threads == 0) n_threads = std::min(hw, 16u);
   // parser threads: a block parses at roughly 10 M records/s per thread; the rest of the budget formats
   const unsigned n_parsers = std::max(1u, std::min(4u, n_threads / 4));
+  // ---- the writer, the output and the sorter
   thm_writer* w = nullptr;
   int rc = thm_writer_create(ix, format, n_threads, &w);
   if (rc != THM_OK) return rc;
-  const bool to_stdout = strcmp(output_path, "-") == 0;
-  if (to_stdout) fflush(stdout);
-  const int fo = to_stdout ? 1 : open(output_path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
-  if (fo < 0) {
+  Output out;
+  if (!out.open(output_path)) {
     thm_writer_free(w);
     thm::set_global_error(std::string("cannot create ") + output_path);
     return THM_ERR_IO;
   }
-  // a regular file takes the chunks of a batch at their final offsets from several threads
-  struct stat sb;
-  const bool positional = !to_stdout && fstat(fo, &sb) == 0 && S_ISREG(sb.st_mode);
-  uint64_t file_off = 0;
-  auto write_all = [&](const char* p, size_t n, uint64_t off) -> bool {
-    while (n) {
-      const ssize_t k = positional ? pwrite(fo, p, n, (off_t)off) : write(fo, p, n);
-      if (k <= 0) return false;
-      p += k;
-      n -= (size_t)k;
-      off += (uint64_t)k;
-    }
-    return true;
-  };
-
   thm_bam_sorter* sorter = nullptr;
-  if (bam_sort && (rc = thm_bam_sorter_create(aligners[0], 0, &sorter)) != THM_OK) {
-    if (!to_stdout) close(fo);
+  if (m.bam_sort && (rc = thm_bam_sorter_create(aligners[0], 0, &sorter)) != THM_OK) {
+    (void)out.close();
     thm_writer_free(w);
     return rc;
   }
-  thm_run_stats st;
-  memset(&st, 0, sizeof st);
-  std::mutex st_mu;  // parse_s / gpu_s are summed by several threads
   const auto t_start = Clock::now();
-  Shared sh;
-  // every aligner keeps the results of its last two fetches: two batches per GPU may be between fetch and write,
-  // one more is running; the parsers and the cutter work ahead of that
-  const unsigned n_slots = 3 * n_aligners + n_parsers + 2;
-  std::vector<Slot> slots(n_slots);
-  Queue q_free, q_raw;
-  for (auto& s : slots) q_free.push(&s);
-  // parsed batches are handed to the GPU threads strictly in input order (parsers may finish out of order; an aligner
-  // that ran ahead of a batch it would later have to wait for could block the writer for good)
-  std::mutex par_mu;
-  std::condition_variable par_cv;
-  std::map<uint64_t, Slot*> parsed;
-  uint64_t next_align = 0;
-  bool parse_done = false;
-  // finished batches, by sequence number, for the writer
-  std::mutex done_mu;
-  std::condition_variable done_cv;
-  std::map<uint64_t, Slot*> done;
-  uint64_t n_batches_cut = 0;  // set when the cutter has seen the end of the input
-  bool cut_done = false;
-  uint64_t n_written = 0;  // batches the writer has finished (guarded by done_mu)
-
-  // THM_FASTQ_DEVICE=2: the chain of tails.  Every slot of such a run takes its turn in input order for its upload (a
-  // slot that is not BGZF only passes the turn on); the holder of the turn alone touches ch_tail and ch_line.  The
-  // bytes and reads of the batches so far size the next groups.
-  std::mutex ch_mu;
-  std::condition_variable ch_cv;
-  uint64_t ch_turn = 0;
-  std::vector<uint8_t> ch_tail;
-  uint64_t ch_line = 1;
-  std::atomic<uint64_t> est_bytes{0}, est_reads{0};
-  // THM_FASTQ_DEVICE=3: where the plain-gzip file of the turn stands (the holder of the turn alone touches them), and
-  // what the cutter waits for before it cuts the next slot of that file: the upload that tells whether there is one
-  std::unique_ptr<thm_gzip_state> gz_state(new thm_gzip_state());
-  uint64_t gz_pos = 0, gz_in = 0, gz_out = 0;  // the position in the file; compressed and inflated bytes so far, for the ratio
-  bool gz_file_done = false;                   // (guarded by ch_mu)
-  std::vector<std::pair<const char*, size_t>> maps;
-  // ---- stage 1: cut the input into blocks of whole records ----
-  std::thread cutter([&] {
-    uint64_t seq = 0;
-    // gzip inputs get an inflater thread each (Ahead), those of the next few files running ahead of their turn
-    std::vector<std::unique_ptr<Ahead>> ahead(n_paths);
-    std::vector<char> is_gz(n_paths, 0);
-    std::vector<std::unique_ptr<BgzfFile>> bgzf_files(n_paths);
-    std::vector<std::unique_ptr<GzipFile>> gzip_files(n_paths);
-    unsigned n_gz = 0;
-    for (uint32_t pi = 0; pi < n_paths; pi++) {
-      unsigned char magic[2] = {0, 0};
-      const int fd = open(fastq_paths[pi], O_RDONLY);
-      if (fd >= 0) {
-        is_gz[pi] = pread(fd, magic, 2, 0) == 2 && magic[0] == 0x1f && magic[1] == 0x8b;
-        close(fd);
-      }
-      if (is_gz[pi] && fastq_bgzf) {  // eligible: no inflater thread, the file is cut by its members
-        const auto t0 = Clock::now();
-        (void)sh.step([&] {
-          std::unique_ptr<BgzfFile> bf(new BgzfFile());
-          bf->open(fastq_paths[pi]);
-          if (bf->ok) {
-            bgzf_files[pi] = std::move(bf);
-            is_gz[pi] = 0;
-          } else if (fastq_gzip) {  // ... or in slices, wherever its blocks end
-            std::unique_ptr<GzipFile> gf(new GzipFile());
-            gf->open(fastq_paths[pi]);
-            if (gf->ok) {
-              gzip_files[pi] = std::move(gf);
-              is_gz[pi] = 0;
-            }
-          }
-          return THM_OK;
-        });
-        std::lock_guard<std::mutex> g(st_mu);
-        st.parse_s += secs(t0, Clock::now());
-      }
-      n_gz += is_gz[pi];
-    }
-    const unsigned ahead_files = std::max(1u, std::min(n_gz, std::max(2u, n_threads / 4)));
-    size_t ahead_bytes = (size_t)768 << 20;  // all inflaters together; THM_INFLATE_AHEAD_MB overrides
-    if (const char* e = getenv("THM_INFLATE_AHEAD_MB")) ahead_bytes = (size_t)std::max(1L, atol(e)) << 20;
-    auto top_up = [&](uint32_t from) {  // the inflaters of the next `ahead_files` gzip files at or behind `from`
-      unsigned running = 0;
-      for (uint32_t k = from; k < n_paths && running < ahead_files; k++) {
-        if (!is_gz[k]) continue;
-        running++;
-        if (ahead[k]) continue;
-        ahead[k].reset(new Ahead());
-        ahead[k]->path = fastq_paths[k];
-        ahead[k]->batch_reads = batch_reads;
-        ahead[k]->budget = ahead_bytes / ahead_files;
-        ahead[k]->start();
-      }
-    };
-    for (uint32_t pi = 0; pi < n_paths && !sh.failed(); pi++) {
-      thm_fastq* r = nullptr;
-      Ahead* ah = nullptr;
-      int prc = THM_OK;
-      bool fast = false;
-      if (sh.step([&] { top_up(pi); return THM_OK; }) != THM_OK) break;
-      if (bgzf_files[pi]) {
-        // groups of whole members of about batch_reads reads, by the bytes per record of the batches so far
-        BgzfFile& bf = *bgzf_files[pi];
-        const size_t nm = bf.tab.size();
-        for (size_t k = 0; k < nm && !sh.failed();) {
-          Slot* s = q_free.pop();
-          const uint64_t eb = est_bytes.load(), er = est_reads.load();
-          const double per = er >= 64 ? (double)eb / (double)er : bf.bytes_per_read;
-          const double want = per * (double)batch_reads;
-          size_t k1 = k;
-          double have_bytes = 0;
-          do have_bytes += bf.tab[k1++].isize;
-          while (k1 < nm && have_bytes < want);
-          s->seq = seq++;
-          s->parsed = false;
-          s->aligned = false;
-          s->zmembers = true;
-          s->gzslice = false;
-          s->file_first = k == 0;
-          s->path = fastq_paths[pi];
-          s->raw_ptr = (const char*)bf.map + bf.at[k];
-          s->raw_len = (size_t)(bf.at[k1] - bf.at[k]);
-          s->last_block = k1 == nm;
-          s->first_line = 0;
-          k = k1;
-          q_raw.push(s);
-        }
-        maps.emplace_back((const char*)bf.map, bf.len);  // unmapped when every batch has been written
-        bf.map = nullptr;
-        continue;
-      }
-      if (gzip_files[pi]) {
-        // one slot after the other: where a slice begins is known once the one before has gone up
-        GzipFile& gf = *gzip_files[pi];
-        for (bool first = true, more = true; more && !sh.failed(); first = false) {
-          Slot* s = q_free.pop();
-          s->seq = seq++;
-          s->parsed = false;
-          s->aligned = false;
-          s->zmembers = false;
-          s->gzslice = true;
-          s->file_first = first;
-          s->path = fastq_paths[pi];
-          s->gz_map = gf.map;
-          s->gz_len = gf.len;
-          s->raw_ptr = nullptr;
-          s->raw_len = 0;
-          s->last_block = false;
-          s->first_line = 0;
-          if (first) {
-            std::lock_guard<std::mutex> g(ch_mu);
-            gz_file_done = false;
-          }
-          const uint64_t mine = s->seq;
-          q_raw.push(s);
-          std::unique_lock<std::mutex> g(ch_mu);
-          ch_cv.wait(g, [&] { return ch_turn > mine; });
-          more = !gz_file_done;
-        }
-        maps.emplace_back((const char*)gf.map, gf.len);  // unmapped when every batch has been written
-        gf.map = nullptr;
-        continue;
-      }
-      if (is_gz[pi]) {
-        ah = ahead[pi].get();
-        const int kind = ah->wait_kind();
-        if (kind == 2) {
-          sh.set(ah->open_rc, ah->open_err);
-          break;
-        }
-        fast = kind == 1;
-        r = ah->r;  // (the sequential parser's, when the file is not 4-line FASTQ: the inflater thread has left)
-      } else {
-        prc = thm_fastq_open(fastq_paths[pi], &r);
-        if (prc != THM_OK) {
-          sh.set(prc, thm_last_error(nullptr));
-          break;
-        }
-        fast = thm::fastq_is_plain_fastq(r);
-      }
-      // a plain (not gzip) FASTQ file is mapped and cut in place: a block is a range of the mapping
-      const char* map = nullptr;
-      size_t map_len = 0, map_pos = 0;
-      uint64_t map_line = 1;
-      if (fast) {
-        unsigned char magic[2] = {0, 0};
-        const int fd = open(fastq_paths[pi], O_RDONLY);
-        struct stat ms;
-        if (fd >= 0 && fstat(fd, &ms) == 0 && S_ISREG(ms.st_mode) && ms.st_size > 0 && pread(fd, magic, 2, 0) == 2 &&
-            !(magic[0] == 0x1f && magic[1] == 0x8b)) {
-          void* m = mmap(nullptr, (size_t)ms.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
-          if (m != MAP_FAILED) {
-            map = (const char*)m;
-            map_len = (size_t)ms.st_size;
-            (void)madvise(m, map_len, MADV_SEQUENTIAL);
-          }
-        }
-        if (fd >= 0) close(fd);
-      }
-      auto count_nl = [](const char* p, size_t n) {
-        size_t c = 0;
-        for (size_t i = 0; i < n; i++) c += p[i] == '\n';
-        return c;
-      };
-      for (;;) {
-        Slot* s = q_free.pop();
-        s->seq = seq;
-        s->parsed = false;
-        s->zmembers = false;
-        s->gzslice = false;
-        s->aligned = false;
-        s->path = fastq_paths[pi];
-        const auto t0 = Clock::now();
-        uint64_t n_lines = 0;
-        s->raw_ptr = nullptr;
-        if (map) {
-          // the position behind the (4 x batch_reads)-th newline from map_pos, found a span at a time
-          const uint64_t want = batch_reads * 4;
-          size_t p0 = map_pos, p = map_pos;
-          while (p < map_len && n_lines < want) {
-            const size_t span = std::min<size_t>(map_len - p, 1u << 20);
-            const size_t nl = count_nl(map + p, span);
-            if (n_lines + nl < want) {
-              n_lines += nl;
-              p += span;
-              continue;
-            }
-            const char* q = map + p;
-            while (n_lines < want) {
-              q = (const char*)memchr(q, '\n', (size_t)(map + p + span - q)) + 1;
-              n_lines++;
-            }
-            p = (size_t)(q - map);
-          }
-          if (p == map_len && p > p0 && map[p - 1] != '\n') n_lines++;
-          s->raw_ptr = map + p0;
-          s->raw_len = p - p0;
-          s->last_block = p == map_len;
-          s->first_line = map_line;
-          map_line += n_lines;
-          map_pos = p;
-          prc = THM_OK;
-        } else if (fast && ah) {
-          Ahead::Block b;
-          ah->next(b, s->raw);
-          s->raw.swap(b.raw);
-          s->raw_len = b.raw_len;
-          s->first_line = b.first_line;
-          s->last_block = b.last_block;
-          n_lines = b.n_lines;
-          prc = b.rc;
-          if (prc != THM_OK) thm::set_global_error(b.err);
-          s->raw_ptr = s->raw.data();
-        } else if (fast) {
-          prc = sh.step([&] { return thm::fastq_next_raw_block(r, batch_reads, s->raw, s->raw_len, n_lines, s->first_line, s->last_block); });
-          s->raw_ptr = s->raw.data();
-        } else {  // FASTA and anything that is not plain 4-line FASTQ: the sequential parser
-          prc = sh.step([&] { return thm::fastq_fill(r, batch_reads, s->reads); });
-          s->parsed = true;
-          n_lines = s->reads.n_reads();
-        }
-        if (!(fast && ah)) {  // (an inflater thread counts its own time)
-          std::lock_guard<std::mutex> g(st_mu);
-          st.parse_s += secs(t0, Clock::now());
-        }
-        if (prc != THM_OK || sh.failed() || n_lines == 0) {
-          if (prc != THM_OK) sh.set(prc, thm_last_error(nullptr));
-          q_free.push(s);
-          break;
-        }
-        seq++;
-        q_raw.push(s);
-      }
-      if (ah) {
-        ah->stop();  // (closes the reader)
-        std::lock_guard<std::mutex> g(st_mu);
-        st.parse_s += ah->busy_s;
-      } else {
-        thm_fastq_close(r);
-      }
-      if (map) maps.emplace_back(map, map_len);  // unmapped when every batch has been written
-    }
-    for (auto& a : ahead)
-      if (a) a->stop();  // (inflaters started ahead of a run that failed)
-    {
-      std::lock_guard<std::mutex> g(done_mu);
-      n_batches_cut = seq;
-      cut_done = true;
-    }
-    done_cv.notify_all();
-    for (unsigned k = 0; k < n_parsers; k++) q_raw.push(nullptr);
-  });
-
-  // ---- stage 2: parse blocks (several threads) ----
-  std::vector<std::thread> parsers;
-  std::mutex parsers_mu;
-  unsigned parsers_left = n_parsers;
-  for (unsigned k = 0; k < n_parsers; k++)
-    parsers.emplace_back([&] {
-      for (;;) {
-        Slot* s = q_raw.pop();
-        if (!s) break;
-        if (!s->parsed && !fastq_device && !sh.failed()) {  // (with THM_FASTQ_DEVICE the block passes through as it is)
-          const auto t0 = Clock::now();
-          std::string err;
-          const int prc = sh.step([&] { return thm::fastq_parse_block(s->raw_ptr, s->raw_len, s->path, s->first_line, s->last_block, s->reads, err); });
-          {
-            std::lock_guard<std::mutex> g(st_mu);
-            st.parse_s += secs(t0, Clock::now());
-          }
-          if (prc != THM_OK) sh.set(prc, err);
-        }
-        {
-          std::lock_guard<std::mutex> g(par_mu);
-          parsed[s->seq] = s;
-        }
-        par_cv.notify_all();
-      }
-      std::lock_guard<std::mutex> g(parsers_mu);
-      if (--parsers_left == 0) {
-        {
-          std::lock_guard<std::mutex> g2(par_mu);
-          parse_done = true;
-        }
-        par_cv.notify_all();
-      }
-    });
-
-  // ---- stage 3: one thread per aligner ----
-  std::vector<std::thread> gpus;
-  for (uint32_t gi = 0; gi < n_aligners; gi++)
-    gpus.emplace_back([&, gi] {
-      thm_aligner* a = aligners[gi];
-      std::deque<uint64_t> fetched;  // sequence numbers of this aligner's fetched batches, oldest first
-      for (;;) {
-        Slot* s = nullptr;
-        {
-          std::unique_lock<std::mutex> g(par_mu);
-          par_cv.wait(g, [&] { return parsed.count(next_align) || (parse_done && parsed.empty()); });
-          auto it = parsed.find(next_align);
-          if (it == parsed.end()) break;
-          s = it->second;
-          parsed.erase(it);
-          next_align++;
-        }
-        par_cv.notify_all();
-        // a raw block goes up as it is and is parsed there; the slot keeps its bytes (its own buffer, or the mapping,
-        // which lives until every batch is written) until it is released behind the write
-        const bool raw_up = fastq_device && !s->parsed;
-        bool have = !sh.failed() && (raw_up || s->reads.n_reads() != 0);  // (a blank tail cut into a block of its own holds no read)
-        const auto t0 = Clock::now();
-        int up_rc = THM_OK;
-        if (fastq_bgzf) {  // this slot's turn in the chain of uploads
-          std::unique_lock<std::mutex> g(ch_mu);
-          ch_cv.wait(g, [&] { return ch_turn == s->seq; });
-        }
-        if (s->zmembers) {
-          if (s->file_first) {
-            ch_tail.clear();
-            ch_line = 1;
-          }
-          s->first_line = ch_line;
-          if (have) {
-            thm_fastq_bgzf_info zi;
-            memset(&zi, 0, sizeof zi);
-            up_rc = sh.step([&] {
-              s->head = ch_tail;
-              const int r2 = (int)thm_batch_upload_fastq_bgzf(a, s->head.data(), s->head.size(), (const uint8_t*)s->raw_ptr, s->raw_len,
-                                                              s->path.c_str(), s->first_line, s->last_block ? 1 : 0, &zi);
-              if (r2 == THM_OK) {
-                ch_tail.assign(zi.tail, zi.tail + zi.tail_len);
-                ch_line += zi.n_lines;
-                est_bytes += s->head.size() + zi.n_inflated_bytes - zi.tail_len;
-                est_reads += zi.n_reads;
-              }
-              return r2;
-            });
-            if (up_rc == THM_OK && zi.n_reads == 0) have = false;  // (a group without a whole record: all of it is tail)
-          }
-        }
-        if (s->gzslice) {
-          if (s->file_first) {
-            ch_tail.clear();
-            ch_line = 1;
-            memset(gz_state.get(), 0, sizeof(thm_gzip_state));
-            gz_pos = gz_in = gz_out = 0;
-          }
-          s->first_line = ch_line;
-          bool file_done = !have;  // (a run that has failed cuts no further slot)
-          if (have) {
-            thm_fastq_gzip_info zi;
-            memset(&zi, 0, sizeof zi);
-            // a slice of about batch_reads reads, by the bytes per record and the ratio of the batches so far; doubled
-            // while no block ends inside it
-            const uint64_t eb = est_bytes.load(), er = est_reads.load();
-            const double per = er >= 64 ? (double)eb / (double)er : 256.0;
-            const double ratio = gz_in >= 65536 ? std::max(1.0, (double)gz_out / (double)gz_in) : 4.0;
-            uint64_t want = (uint64_t)(per * (double)batch_reads / ratio) + 4096;
-            up_rc = sh.step([&] {
-              s->head = ch_tail;
-              for (;;) {
-                const uint64_t left = s->gz_len - gz_pos, n = std::min<uint64_t>(want, left);
-                s->last_block = n == left;
-                const int r2 = (int)thm_batch_upload_fastq_gzip(a, gz_state.get(), s->head.data(), s->head.size(), s->gz_map + gz_pos, n,
-                                                                s->path.c_str(), s->first_line, s->last_block ? 1 : 0, &zi);
-                if (r2 != THM_OK) return r2;
-                if (zi.n_consumed_bytes == 0 && !s->last_block) {
-                  want = 2 * n;
-                  continue;
-                }
-                gz_pos += zi.n_consumed_bytes;
-                gz_in += zi.n_consumed_bytes;
-                gz_out += zi.n_inflated_bytes;
-                ch_tail.assign(zi.tail, zi.tail + zi.tail_len);
-                ch_line += zi.n_lines;
-                est_bytes += s->head.size() + zi.n_inflated_bytes - zi.tail_len;
-                est_reads += zi.n_reads;
-                return (int)THM_OK;
-              }
-            });
-            file_done = up_rc != THM_OK || s->last_block;
-            if (up_rc == THM_OK && zi.n_reads == 0) have = false;  // (a slice without a whole record: all of it is tail)
-          }
-          std::lock_guard<std::mutex> g(ch_mu);
-          gz_file_done = file_done;
-        }
-        if (fastq_bgzf) {
-          {
-            std::lock_guard<std::mutex> g(ch_mu);
-            ch_turn = s->seq + 1;
-          }
-          ch_cv.notify_all();
-        }
-        if (have && raw_up && !s->zmembers && !s->gzslice) {
-          thm_fastq_upload_info fi;
-          memset(&fi, 0, sizeof fi);
-          up_rc = sh.step([&] {
-            return (int)thm_batch_upload_fastq(a, (const uint8_t*)s->raw_ptr, s->raw_len, s->path.c_str(), s->first_line, s->last_block ? 1 : 0, &fi);
-          });
-          if (up_rc == THM_OK && fi.n_reads == 0) have = false;  // (that blank tail)
-        }
-        if (have) {
-          const thm_read_batch rb = s->reads.view();
-          int grc = sh.step([&] {
-            int g2 = raw_up ? up_rc : bam_device ? thm_batch_upload_reads(a, &rb) : thm_batch_upload(a, rb.bases, rb.offsets, rb.n_reads);
-            if (g2 == THM_OK) g2 = thm_batch_run(a);
-            if (g2 == THM_OK) g2 = thm_batch_sync(a);
-            return g2;
-          });
-          const auto t1 = Clock::now();
-          // the fetch below reuses the buffers of this aligner's second-last fetch: that batch must have been written
-          if (grc == THM_OK && fetched.size() >= 2) {
-            const uint64_t must = fetched[fetched.size() - 2];
-            std::unique_lock<std::mutex> g(done_mu);
-            done_cv.wait(g, [&] { return n_written > must || sh.failed(); });
-          }
-          const auto t2 = Clock::now();
-          if (grc == THM_OK) grc = sh.step([&] {
-            if (bam_sort) return thm::bam_sorter_add(sorter, 0, &s->sorted, &s->sorted_aligned);
-            if (!bgzf_device) return bam_device ? thm_batch_fetch_bam(a, 0, &s->bam) : thm_batch_fetch(a, &s->res);
-            return thm::batch_fetch_bgzf(a, 0, &s->bgzf, &s->bgzf_aligned);
-          });
-          const uint64_t n_res = bam_sort ? s->sorted.n_reads : bgzf_device ? s->bgzf.n_reads : bam_device ? s->bam.n_reads : s->res.n_reads;
-          const int32_t* res_status = bam_sort ? s->sorted.read_status
-                                      : bgzf_device ? s->bgzf.read_status : bam_device ? s->bam.read_status : s->res.read_status;
-          if (grc == THM_OK && (bam_sort ? s->sorted.n_failed_reads
-                                : bgzf_device ? s->bgzf.n_failed_reads : bam_device ? s->bam.n_failed_reads : s->res.n_failed_reads)) {
-            // the reference aligns every read or panics; a read this build cannot take fails the run, by name
-            uint64_t bad = 0;
-            while (bad < n_res && res_status[bad] == THM_OK) bad++;
-            thm_read_batch up;  // (the batch as it stands on the device: the host has not seen a byte of a gzip slice)
-            memset(&up, 0, sizeof up);
-            if (raw_up && s->gzslice) {
-              (void)sh.step([&] { return (int)thm_batch_fetch_reads(a, &up); });
-            } else if (raw_up && s->zmembers) {  // ... inflate and parse that one block here, for the one message
-              std::string perr;
-              (void)sh.step([&] {
-                std::vector<uint8_t> blk;
-                uint64_t cut = 0;
-                int r2 = thm::bgzf_block_on_host(s->head.data(), s->head.size(), (const uint8_t*)s->raw_ptr, s->raw_len, s->path, s->last_block, blk, &cut, perr);
-                if (r2 == THM_OK) r2 = thm::fastq_parse_block((const char*)blk.data(), (size_t)cut, s->path, s->first_line, s->last_block, s->reads, perr);
-                return r2;
-              });
-            } else if (raw_up) {  // the host has not seen the names of this block: parse it now, for the one message
-              std::string perr;
-              (void)sh.step([&] { return thm::fastq_parse_block(s->raw_ptr, s->raw_len, s->path, s->first_line, s->last_block, s->reads, perr); });
-            }
-            const thm_read_batch v = raw_up && s->gzslice ? up : s->reads.view();
-            std::string name;
-            if (bad < v.n_reads) name.assign((const char*)v.names + v.name_off[bad], (size_t)(v.name_off[bad + 1] - v.name_off[bad]));
-            sh.set(res_status[bad], "read " + name + (res_status[bad] == THM_ERR_UNSUPPORTED
-                                                           ? ": longer than 65535 bases, or its DP trace exceeds the device-memory budget"
-                                                           : ": hits a condition that panics in the reference (lift_mem_to_tx / lift_tx_to_gx)"));
-            grc = res_status[bad];
-          }
-          if (grc != THM_OK) {
-            sh.set(grc, thm_last_error(a));
-          } else {
-            s->aligned = true;
-            fetched.push_back(s->seq);
-            if (fetched.size() > 4) fetched.pop_front();
-          }
-          std::lock_guard<std::mutex> g(st_mu);
-          st.gpu_s += secs(t0, t1) + secs(t2, Clock::now());
-          if (grc == THM_OK) {
-            st.n_reads += n_res;
-            st.n_batches += 1;
-          }
-        }
-        {
-          std::lock_guard<std::mutex> g(done_mu);
-          done[s->seq] = s;
-        }
-        done_cv.notify_all();
-      }
-    });
-
-  // ---- stage 4: format (this thread, on the formatting threads of the writer) and write (one more thread), in input
-  // order; two writer objects are used alternately, so that batch k + 1 is formatted while batch k is written ----
-  {
-    // two writer objects, used alternately: the chunks of batch k are views into writer k & 1 and are still being
-    // written while batch k + 1 is formatted, so one object cannot stand in for both
-    thm_writer* w2 = nullptr;
-    if (thm_writer_create(ix, format, n_threads, &w2) != THM_OK) {
-      w2 = nullptr;
-      sh.set(THM_ERR_OOM, "cannot create the second writer object");
-    }
-    thm_writer* ws[2] = {w, w2 ? w2 : w};  // (after a failure nothing is formatted any more: sh.failed())
-    struct WriteJob {
-      Slot* s = nullptr;
-      uint64_t seq = 0;
-      std::vector<const std::string*> chunks;
-      std::vector<std::pair<const char*, size_t>> spans;  // what is written: the chunks, or the members of a thm_bgzf_view
-      std::vector<uint64_t> at;
-      bool stop = false;
-    };
-    std::mutex wj_mu;
-    std::condition_variable wj_cv;
-    std::deque<WriteJob*> wj_q;
-    WriteJob jobs[2];
-    bool job_busy[2] = {false, false};
-    thm_text t;
-    // (a sorted file's header is written when the drain begins)
-    if (!bam_sort && thm_writer_header(w, &t) == THM_OK && t.len) {
-      if (!write_all((const char*)t.data, t.len, file_off)) sh.set(THM_ERR_IO, "short write");
-      file_off += t.len;
-      st.n_output_bytes += t.len;
-    }
-    auto release = [&](Slot* s, uint64_t seq) {
-      {
-        std::lock_guard<std::mutex> g(done_mu);
-        n_written = seq + 1;
-      }
-      done_cv.notify_all();
-      q_free.push(s);
-    };
-    std::thread wthread([&] {
-      for (;;) {
-        WriteJob* j;
-        {
-          std::unique_lock<std::mutex> g(wj_mu);
-          wj_cv.wait(g, [&] { return !wj_q.empty(); });
-          j = wj_q.front();
-          wj_q.pop_front();
-        }
-        if (j->stop) break;
-        const auto t1 = Clock::now();
-        std::vector<char> good(j->spans.size(), 1);
-        auto put = [&](size_t c) { good[c] = write_all(j->spans[c].first, j->spans[c].second, j->at[c]) ? 1 : 0; };
-        if (positional && j->spans.size() > 1) {
-          std::vector<std::thread> th;
-          for (size_t c = 1; c < j->spans.size(); c++) th.emplace_back(put, c);
-          put(0);
-          for (auto& x : th) x.join();
-        } else {
-          for (size_t c = 0; c < j->spans.size(); c++) put(c);
-        }
-        for (char g : good)
-          if (!g) sh.set(THM_ERR_IO, "short write");
-        st.write_s += secs(t1, Clock::now());
-        release(j->s, j->seq);
-        {
-          std::lock_guard<std::mutex> g(wj_mu);
-          job_busy[j - jobs] = false;
-        }
-        wj_cv.notify_all();
-      }
-    });
-    for (uint64_t next = 0;; next++) {
-      Slot* s = nullptr;
-      {
-        std::unique_lock<std::mutex> g(done_mu);
-        done_cv.wait(g, [&] { return done.count(next) || (cut_done && next >= n_batches_cut); });
-        auto it = done.find(next);
-        if (it == done.end()) break;  // the input is exhausted
-        s = it->second;
-        done.erase(it);
-      }
-      const int k = (int)(next & 1);
-      {  // the writer object (and job) of this parity: its previous batch must have left
-        std::unique_lock<std::mutex> g(wj_mu);
-        wj_cv.wait(g, [&] { return !job_busy[k]; });
-      }
-      bool queued = false;
-      if (!sh.failed() && s->aligned && bam_sort) {
-        // nothing leaves before the input is exhausted: the batch is in the sorter
-        st.n_aligned_reads += s->sorted_aligned;
-        st.n_records += s->sorted.n_records;
-      } else if (!sh.failed() && s->aligned) {
-        const auto t0 = Clock::now();
-        const thm_read_batch rb = s->reads.view();
-        const thm_batch_view& v = s->res;
-        WriteJob& j = jobs[k];
-        const thm_bam_view& bv = s->bam;
-        const int wrc = sh.step([&] {
-          // nothing to format: the members leave as one chunk, written from the aligner's pinned set (the GPU thread
-          // waits for this batch to be written before the fetch that reuses the set)
-          if (bgzf_device) return (int)THM_OK;
-          return bam_device ? thm::writer_wrap_bam_chunks(ws[k], &bv, j.chunks) : thm::writer_format_chunks(ws[k], &rb, &v, j.chunks);
-        });
-        st.format_s += secs(t0, Clock::now());
-        if (wrc != THM_OK) {
-          sh.set(wrc, thm_last_error(nullptr));
-        } else {
-          j.spans.clear();
-          if (bgzf_device) j.spans.emplace_back((const char*)s->bgzf.data, (size_t)s->bgzf.n_bytes);
-          else
-            for (const std::string* c : j.chunks) j.spans.emplace_back(c->data(), c->size());
-          j.at.resize(j.spans.size());
-          for (size_t c = 0; c < j.spans.size(); c++) {
-            j.at[c] = file_off;
-            file_off += j.spans[c].second;
-            st.n_output_bytes += j.spans[c].second;
-          }
-          if (bgzf_device) {
-            st.n_aligned_reads += s->bgzf_aligned;
-            st.n_records += s->bgzf.n_records;
-          } else if (bam_device) {
-            // a read is unmapped when its first record carries flag 4 (bytes 18 .. 19 of the record)
-            for (uint64_t r = 0; r < bv.n_reads; r++) st.n_aligned_reads += !(bv.data[bv.read_rec_off[r] + 18] & 4);
-            st.n_records += bv.n_records;
-          } else {
-            for (uint64_t r = 0; r < v.n_reads; r++) {
-              const uint64_t kk = v.read_aln_off[r + 1] - v.read_aln_off[r];
-              st.n_aligned_reads += kk != 0;
-              st.n_records += kk ? kk : (format == THM_FMT_PAF ? 0 : 1);
-            }
-          }
-          j.s = s;
-          j.seq = next;
-          {
-            std::lock_guard<std::mutex> g(wj_mu);
-            job_busy[k] = true;
-            wj_q.push_back(&j);
-          }
-          wj_cv.notify_all();
-          queued = true;
-        }
-      }
-      if (!queued) {
-        // nothing to write for this batch: it still leaves in order behind the writes that are queued
-        std::unique_lock<std::mutex> g(wj_mu);
-        wj_cv.wait(g, [&] { return !job_busy[0] && !job_busy[1]; });
-        g.unlock();
-        release(s, next);
-      }
-    }
-    {
-      std::unique_lock<std::mutex> g(wj_mu);
-      wj_cv.wait(g, [&] { return !job_busy[0] && !job_busy[1]; });
-    }
-    WriteJob stop;
-    stop.stop = true;
-    {
-      std::lock_guard<std::mutex> g(wj_mu);
-      wj_q.push_back(&stop);
-    }
-    wj_cv.notify_all();
-    wthread.join();
-    if (bam_sort && !sh.failed()) {
-      // the drain: sort, the sorted header, then window after window -- window k is written (from one of the sorter's two
-      // pinned sets) while the device gathers and deflates window k + 1
-      const auto t0 = Clock::now();
-      int drc = sh.step([&] { return (int)thm_bam_sorter_finish(sorter, nullptr); });
-      st.format_s += secs(t0, Clock::now());
-      if (drc != THM_OK) sh.set(drc, thm_last_error(aligners[0]));
-      if (drc == THM_OK && thm_writer_header_sorted(w, &t) == THM_OK && t.len) {
-        if (!write_all((const char*)t.data, t.len, file_off)) sh.set(THM_ERR_IO, "short write");
-        file_off += t.len;
-        st.n_output_bytes += t.len;
-      }
-      std::thread wr;
-      bool wrote = true;
-      while (drc == THM_OK && !sh.failed()) {
-        thm_bam_sorted_view v;
-        const auto t1 = Clock::now();
-        drc = sh.step([&] { return (int)thm_bam_sorter_next(sorter, 0, 0, &v); });
-        st.format_s += secs(t1, Clock::now());
-        if (wr.joinable()) wr.join();  // the next call reuses the set the write before last came from
-        if (!wrote) sh.set(THM_ERR_IO, "short write");
-        if (drc != THM_OK) {
-          sh.set(drc, thm_last_error(aligners[0]));
-          break;
-        }
-        if (v.n_raw_bytes == 0) break;
-        const uint64_t at = file_off;
-        file_off += v.n_bytes;
-        st.n_output_bytes += v.n_bytes;
-        wr = std::thread([&, v, at] {
-          const auto t2 = Clock::now();
-          wrote = write_all((const char*)v.data, (size_t)v.n_bytes, at);
-          st.write_s += secs(t2, Clock::now());
-        });
-      }
-      if (wr.joinable()) wr.join();
-      if (!wrote) sh.set(THM_ERR_IO, "short write");
-    }
-    if (!sh.failed() && thm_writer_trailer(w, &t) == THM_OK && t.len) {
-      if (!write_all((const char*)t.data, t.len, file_off)) sh.set(THM_ERR_IO, "short write");
-      file_off += t.len;
-      st.n_output_bytes += t.len;
-    }
-    if (w2) thm_writer_free(w2);
-  }
+  thm_writer* w2 = nullptr;
+  const bool have_w2 = thm_writer_create(ix, format, n_threads, &w2) == THM_OK;
+  if (!have_w2) w2 = nullptr;
+  Run run(aligners, n_aligners, fastq_paths, n_paths, format, batch_reads, n_threads, n_parsers, m, w, w2 ? w2 : w, out, sorter);
+  if (!have_w2) run.sh.set(THM_ERR_OOM, "cannot create the second writer object");
+  // ---- the stages: the cutter, the parsers, a thread per aligner; this thread formats
+  std::thread cutter(&Run::cut, &run);
+  std::vector<std::thread> parsers, gpus;
+  for (unsigned k = 0; k < n_parsers; k++) parsers.emplace_back(&Run::parse, &run);
+  for (uint32_t gi = 0; gi < n_aligners; gi++) gpus.emplace_back(&Run::gpu, &run, gi);
+  run.format_and_write();
   cutter.join();
-  for (auto& m : maps) munmap((void*)m.first, m.second);
   for (auto& x : parsers) x.join();
   for (auto& x : gpus) x.join();
+  // ---- tear down: every batch has been written, so the mappings go (inside wall_s, as they always were; the slots go
+  // with the run, behind the clock)
+  run.maps.clear();
+  if (w2) thm_writer_free(w2);
   thm_bam_sorter_free(sorter);
-  bool ok = true;
-  if (!to_stdout) ok = close(fo) == 0;
-  if (!ok) sh.set(THM_ERR_IO, std::string("error closing ") + output_path);
+  if (!out.close()) run.sh.set(THM_ERR_IO, std::string("error closing ") + output_path);
   thm_writer_free(w);
-  st.wall_s = secs(t_start, Clock::now());
-  if (stats) *stats = st;
-  if (sh.rc != THM_OK) thm::set_global_error(sh.msg);
-  return sh.rc;
+  run.st.wall_s = secs(t_start, Clock::now());
+  if (stats) *stats = run.st;
+  if (run.sh.rc != THM_OK) thm::set_global_error(run.sh.msg);
+  return run.sh.rc;
 }
 
 extern "C" int32_t thm_align_files(thm_aligner* a, const char* const* fastq_paths, uint32_t n_paths, const char* output_path,

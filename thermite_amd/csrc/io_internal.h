@@ -122,9 +122,6 @@ int bam_sorter_add(thm_bam_sorter* s, uint32_t flags, thm_bam_sort_info* info, u
 int bgzf_block_on_host(const uint8_t* head, uint64_t head_len, const uint8_t* members, uint64_t n, const std::string& path,
                        bool last_block, std::vector<uint8_t>& block, uint64_t* cut, std::string& err);
 
-// inflate.hip: where the batch of a block that is not the last ends (behind its first 4 * (newlines / 4) lines; *n_lines: those)
-uint64_t fastq_host_cut(const uint8_t* blk, uint64_t n, uint64_t* n_lines);
-
 // contig name_id -> index of its @SQ line (the BAM refID), build_sam_header's order (src/aln_writer.rs:256-276);
 // `sq`: the lines' (name, length), when asked for
 std::vector<int32_t> sq_of_name(const thm_index* ix, std::vector<std::pair<std::string, uint64_t>>* sq);

@@ -14,10 +14,19 @@ identical (batch boundaries differ).
 --bam-sort[=ROUNDS]: only plain FASTQ -> BAM with THM_FASTQ_DEVICE=1: THM_BAM_DEVICE=2 (input order) and THM_BAM_SORT=1
 (coordinate order) alternately, ROUNDS rounds (default 3) in one session; then the same reads through thm_bam_sorter by
 hand: sort_ms of thm_bam_sorter_finish and the drain with the two gather shapes alternating window by window (gather_ms,
-deflate_ms per window).  The gzip files are not made."""
-import os, sys, time
+deflate_ms per window).  The gzip files are not made.
+--sha[=PART]: with any of the modes above, "sha256 <hash> <file> <bytes>" for every output file before it is removed (two
+builds of the library -- THM_LIB selects one -- are compared by these lines); with PART also, after every run that wrote a
+file whose name holds PART, "each <file> raw <hash> inflated <hash> size <bytes> batches <n>": does an output repeat from
+run to run, compressed and inflated?"""
+import hashlib, os, sys, time
 BAM_RUNS = FQ_ROUNDS = BGZF_ROUNDS = GZIP_ROUNDS = SORT_ROUNDS = 0
+SHA, SHA_EACH = False, None
 for arg in list(sys.argv[1:]):
+    if arg.startswith("--sha"):
+        SHA, SHA_EACH = True, (arg.split("=")[1] if "=" in arg else None)
+        sys.argv.remove(arg)
+        continue
     if arg.startswith("--bam-sort"):
         SORT_ROUNDS = int(arg.split("=")[1]) if "=" in arg else 3
         sys.argv.remove(arg)
@@ -38,6 +47,23 @@ for arg in list(sys.argv[1:]):
         BAM_RUNS = int(arg.split("=")[1]) if "=" in arg else 4
         sys.argv.remove(arg)
 import numpy as np
+
+
+def file_sha(p, opener=open):
+    h = hashlib.sha256()
+    with opener(p, "rb") as f:
+        for blk in iter(lambda: f.read(1 << 24), b""):
+            h.update(blk)
+    return h.hexdigest()
+
+
+def drop(p):
+    """removes a file of the tool's; an output file's hash first, with --sha"""
+    if SHA and os.path.basename(p).startswith("thm_e2e_out"):
+        print("sha256 %s %s %d" % (file_sha(p), p, os.path.getsize(p)), flush=True)
+    os.remove(p)
+
+
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from thermite_amd import capi, synth
 
@@ -127,6 +153,7 @@ if SORT_ROUNDS:
         print("  deflate per window: median %.3f ms (min %.3f max %.3f)" % (float(np.median(defl)), min(defl), max(defl)), flush=True)
         srt.close()
     a.close()
+    drop("/tmp/thm_e2e_out.bam")
     sys.exit(0)
 for fmt, name in (() if BAM_RUNS or FQ_ROUNDS or BGZF_ROUNDS or GZIP_ROUNDS else ((capi.FMT_SAM, "sam"), (capi.FMT_PAF, "paf"))):
     for rep in range(2):
@@ -187,6 +214,8 @@ def run(tag, paths, fmt, out, reps=2):
         print("%s run %d: %.2f Mreads/s wall %.2fs | parse+inflate %.2fs gpu %.2fs format %.2fs write %.2fs | %.0f MB out" % (
             tag, rep, st["n_reads"] / st["wall_s"] / 1e6, st["wall_s"], st["parse_s"], st["gpu_s"], st["format_s"], st["write_s"],
             st["n_output_bytes"] / 1e6), flush=True)
+        if SHA_EACH and SHA_EACH in os.path.basename(out):
+            print("each %s raw %s inflated %s size %d batches %d" % (out, file_sha(out), file_sha(out, gzip.open), os.path.getsize(out), st["n_batches"]), flush=True)
 
 
 def inflated_sha(p):
@@ -224,7 +253,7 @@ if BGZF_ROUNDS:
     a.close()
     for f in [path, big, gz, gz2, "/tmp/thm_e2e_out.bam"] + outs:
         if os.path.exists(f):
-            os.remove(f)
+            drop(f)
     assert same
     sys.exit(0)
 if GZIP_ROUNDS:
@@ -254,7 +283,7 @@ if GZIP_ROUNDS:
     a.close()
     for f in [path, big, gz, gz2, "/tmp/thm_e2e_out.bam"] + outs:
         if os.path.exists(f):
-            os.remove(f)
+            drop(f)
     assert same
     sys.exit(0)
 if FQ_ROUNDS:
@@ -282,7 +311,7 @@ if FQ_ROUNDS:
     a.close()
     for f in [path, big, gz, gz2, "/tmp/thm_e2e_out.bam"] + outs:
         if os.path.exists(f):
-            os.remove(f)
+            drop(f)
     assert same
     sys.exit(0)
 if BAM_RUNS:
@@ -315,7 +344,7 @@ if BAM_RUNS:
     for f in (path, big, gz, gz2, "/tmp/thm_e2e_out.bam", "/tmp/thm_e2e_out.0.bam", "/tmp/thm_e2e_out.1.bam", "/tmp/thm_e2e_out.2.bam", "/tmp/thm_e2e_out.gz0.bam",
               "/tmp/thm_e2e_out.gz1.bam", "/tmp/thm_e2e_out.gz2.bam"):
         if os.path.exists(f):
-            os.remove(f)
+            drop(f)
     assert same
     sys.exit(0)
 run("paf from one .gz", [gz], capi.FMT_PAF, "/tmp/thm_e2e_out.paf")
@@ -329,4 +358,4 @@ run("bam from two .gz", [gz, gz2], capi.FMT_BAM, "/tmp/thm_e2e_out.bam")
 a.close()
 for f in (path, big, gz, gz2, "/tmp/thm_e2e_out.sam", "/tmp/thm_e2e_out.paf", "/tmp/thm_e2e_out.bam"):
     if os.path.exists(f):
-        os.remove(f)
+        drop(f)
