@@ -91,10 +91,7 @@ uint32_t chunk_bytes() {
   return v;
 }
 
-bool state_ok(const thm_gzip_state* st) {
-  return st->bit_offset <= 7 && st->window_len <= gz::WINDOW && (st->in_member || st->bit_offset == 0) &&
-         (!st->in_member || st->window_len == std::min<uint64_t>(st->member_len, gz::WINDOW));
-}
+bool state_ok(const thm_gzip_state* st) { return gz::state_consistent(*reinterpret_cast<const gz::State*>(st)); }  // (the assert above)
 
 }  // namespace
 

@@ -1,8 +1,9 @@
 // gzip_device.h -- the rules of the device inflater for plain gzip (kernels_gzip.hip; host side gzip.hip; DESIGN.md
 // section 4.14), as functions that compile for the host too: tests/cpp/gzip_model_main.cpp runs the same text serially
 // (that file gives the build lines), corrupt streams first of all and under the sanitizers, before a byte of it reaches a
-// device.  Bit reader, table build, look-up, the length and distance rules and the CRC arithmetic are those of
-// inflate_device.h / bgzf_device.h.
+// device.  Bit reader, table build, look-up, the length and distance rules, the decoder of one block (inf::decode_block,
+// with the header reader the search uses too) and the CRC arithmetic are those of inflate_device.h / bgzf_device.h;
+// what a run does differently with a block's bytes is RingSink below.
 //
 // An ordinary gzip member is one long DEFLATE stream whose matches reach 32 KiB back across any cut.  The scheme is the
 // host inflater's (io_inflate.cpp, "several threads on one gzip file"), one wavefront where that has a thread:
@@ -86,6 +87,12 @@ struct State {
   uint32_t window_len, bit_offset, in_member, crc;
   uint64_t member_len, n_members_done, stream_offset;
 };
+
+// a state is one: a bit offset only inside a member, and there a window of all the member's bytes that fit one
+INF_HD bool state_consistent(const State& st) {
+  return st.bit_offset <= 7 && st.window_len <= WINDOW && (st.in_member || st.bit_offset == 0) &&
+         (!st.in_member || st.window_len == (st.member_len < WINDOW ? st.member_len : WINDOW));
+}
 
 struct Run {
   uint64_t start_bit, end_bit;
@@ -180,64 +187,9 @@ INF_HD bool prefilter(const uint8_t* in, uint64_t n, uint64_t bit) {
 }
 
 INF_HD void open_bits(BitIn& r, const uint8_t* in, uint64_t n, uint64_t bit) {
-  r.base = in, r.lo = 0, r.hi = (uint32_t)n, r.k = 0, r.bb = 0, r.bc = 0, r.win = 0, r.win_k = 0xFFFF0000u;
+  inf::open_bits(r, in, 0, (uint32_t)n);
   seek(r, (uint32_t)(bit >> 3));
   take(r, (uint32_t)bit & 7u);
-}
-
-// The header of a dynamic block behind its three first bits (the text of inflate_member's, on its own): the lengths of
-// both codes into w.lens, *hlit and *hdist their counts.  OK, TRUNCATED or CODE_LENGTHS.
-INF_HD uint32_t read_dynamic_header(BitIn& r, Work& w, uint64_t total_bits, uint32_t* hlit_out, uint32_t* hdist_out) {
-  refill(r);
-  const uint32_t hlit = take(r, 5) + 257, hdist = take(r, 5) + 1, hclen = take(r, 4) + 4;
-  if (hlit > 286 || hdist > 30) return CODE_LENGTHS;
-  INF_SYNC();
-  INF_LANES(lane) {
-    if (lane < 20) w.cl_lens[lane] = 0;
-  }
-  INF_SYNC();
-  for (uint32_t i = 0; i < hclen; i++) {
-    refill(r);
-    w.cl_lens[bgz::cl_order(i)] = (uint8_t)take(r, 3);  // (every lane stores the same value)
-  }
-  if (consumed(r) > total_bits) return TRUNCATED;
-  INF_SYNC();
-  if (build_table(w, w.cl_lens, 19, CL_BITS, w.cl, CL_ENTRIES, T_CL) != OK) return CODE_LENGTHS;
-  uint32_t n = 0, prev = 0;
-  while (n < hlit + hdist) {  // each turn takes a bit at least
-    refill(r);
-    if (consumed(r) > total_bits) return TRUNCATED;
-    const uint32_t e = INF_UNIFORM(w.cl[(uint32_t)r.bb & (CL_ENTRIES - 1)]);
-    if (kind_of(e) != K_LIT) return CODE_LENGTHS;
-    take(r, e & 15u);
-    const uint32_t sym = e >> 16;
-    if (sym < 16) {
-      w.lens[n++] = (uint8_t)sym;
-      prev = sym;
-      continue;
-    }
-    uint32_t rep, val = 0;
-    if (sym == 16) {
-      if (n == 0) return CODE_LENGTHS;
-      val = prev;
-      rep = 3 + take(r, 2);
-    } else if (sym == 17) {
-      rep = 3 + take(r, 3);
-    } else {
-      rep = 11 + take(r, 7);
-    }
-    if (rep > hlit + hdist - n) return CODE_LENGTHS;
-    INF_LANES(lane) {
-      for (uint32_t i = lane; i < rep; i += LANES) w.lens[n + i] = (uint8_t)val;
-    }
-    n += rep;
-    prev = val;
-  }
-  if (consumed(r) > total_bits) return TRUNCATED;
-  INF_SYNC();
-  if (INF_UNIFORM(w.lens[256]) == 0) return CODE_LENGTHS;
-  *hlit_out = hlit, *hdist_out = hdist;
-  return OK;
 }
 
 // Kraft sum of n code lengths in units of 2^-15, and how many are in use
@@ -295,146 +247,65 @@ struct RunWork {
   uint32_t flags;
 };
 
-// ring[flushed, pos) to the run's region
-INF_HD void flush_ring(RunWork& L, uint16_t* sym, uint32_t flushed, uint32_t pos) {
-  INF_SYNC();
-  INF_LANES(lane) {
-    for (uint32_t i = flushed + lane; i < pos; i += LANES) sym[i] = L.ring[i & RING_MASK];
+// A run's symbols, the sink of inf::decode_block: ring[pos & RING_MASK] first, the run's region FLUSH at a time.
+struct RingSink {
+  static constexpr uint32_t FULL = REGION, DIST_CODE_AT_END = TRUNCATED;
+  RunWork& L;
+  uint16_t* sym;  // the run's region
+  uint32_t region;
+  uint32_t member_start;  // as Run's
+  uint32_t pos, flushed;
+  uint32_t reach;  // as Run's
+  INF_M uint32_t room() const { return region - pos; }
+  INF_M void flush() {  // ring[flushed, pos) to the region
+    INF_SYNC();
+    INF_LANES(lane) {
+      for (uint32_t i = flushed + lane; i < pos; i += LANES) sym[i] = L.ring[i & RING_MASK];
+    }
+    INF_SYNC();
+    flushed = pos;
   }
-  INF_SYNC();
-}
-
-// One block at the reader's position, symbols into the ring from *pos_io on.  `region`: symbols the run may produce;
-// `member_start`: as Run's.  OK (*last: the block was final), or why not.
-INF_HD uint32_t decode_block(BitIn& r, RunWork& L, uint64_t total_bits, uint16_t* sym, uint32_t region, uint32_t member_start,
-                             uint32_t* pos_io, uint32_t* flushed_io, uint32_t* reach_io, uint32_t* last, uint32_t* paths_io) {
-  Work& w = L.w;
-  uint32_t pos = *pos_io, flushed = *flushed_io, reach = *reach_io, paths = *paths_io, status = OK;
-  refill(r);
-  *last = take(r, 1);
-  const uint32_t type = take(r, 2);
-  if (consumed(r) > total_bits) return TRUNCATED;
-  if (type == 3) return BLOCK_TYPE;
-  if (type == 0) {
-    take(r, r.bc & 7u);
-    refill(r);
-    const uint32_t len = take(r, 16);
-    refill(r);
-    const uint32_t nlen = take(r, 16);
-    if (consumed(r) > total_bits) return TRUNCATED;
-    if ((len ^ 0xFFFFu) != nlen) return STORED_LEN;
-    const uint32_t p = (uint32_t)(consumed(r) >> 3);
-    if (len > r.hi - p) return TRUNCATED;
-    if (len > region - pos) return REGION;
+  INF_M void before_symbol() {
+    if (pos - flushed >= FLUSH) flush();
+  }
+  INF_M void literal(uint32_t b) { L.ring[pos++ & RING_MASK] = (uint16_t)b; }  // (every lane stores the same value)
+  INF_M void stored(const uint8_t* src, uint32_t len) {
     for (uint32_t done = 0; done < len;) {  // (pieces that the ring holds unflushed)
       const uint32_t piece = len - done < FLUSH ? len - done : FLUSH;
       INF_SYNC();
       INF_LANES(lane) {
-        for (uint32_t i = lane; i < piece; i += LANES) L.ring[(pos + i) & RING_MASK] = (uint16_t)r.base[p + done + i];
+        for (uint32_t i = lane; i < piece; i += LANES) L.ring[(pos + i) & RING_MASK] = (uint16_t)src[done + i];
       }
       pos += piece, done += piece;
-      flush_ring(L, sym, flushed, pos);
-      flushed = pos;
-    }
-    seek(r, p + len);
-    paths |= P_STORED;
-  } else {
-    uint32_t hlit, hdist;
-    if (type == 1) {
-      hlit = 288, hdist = 32;
-      INF_SYNC();
-      INF_LANES(lane) {
-        for (uint32_t s = lane; s < 320; s += LANES) w.lens[s] = (uint8_t)(s < 144 ? 8 : s < 256 ? 9 : s < 280 ? 7 : s < 288 ? 8 : 5);
-      }
-      paths |= P_FIXED;
-    } else {
-      status = read_dynamic_header(r, w, total_bits, &hlit, &hdist);
-      if (status != OK) return status;
-      paths |= P_DYNAMIC;
-    }
-    INF_SYNC();
-    status = build_table(w, w.lens, hlit, LIT_BITS, w.lit, LIT_ENTRIES, T_LIT);
-    if (status == OK) status = build_table(w, w.lens + hlit, hdist, DIST_BITS, w.dist, DIST_ENTRIES, T_DIST);
-    if (status != OK) return status;
-    // symbols: each turn takes a bit at least, and a symbol counts only when all its bits were the input's
-    for (;;) {
-      if (pos - flushed >= FLUSH) {
-        flush_ring(L, sym, flushed, pos);
-        flushed = pos;
-      }
-      refill(r);
-      const uint32_t e = lookup(w.lit, LIT_BITS, r.bb, &paths), kind = kind_of(e);
-      if (kind == K_LIT) {
-        take(r, e & 15u);
-        if (consumed(r) > total_bits) {
-          status = TRUNCATED;
-          break;
-        }
-        if (pos >= region) {
-          status = REGION;
-          break;
-        }
-        L.ring[pos++ & RING_MASK] = (uint16_t)(e >> 16);  // (every lane stores the same value)
-        continue;
-      }
-      if (kind == K_EOB) {
-        take(r, e & 15u);
-        if (consumed(r) > total_bits) status = TRUNCATED;
-        break;
-      }
-      if (kind != K_BASE) {
-        status = consumed(r) + 1 > total_bits ? TRUNCATED : BAD_CODE;
-        break;
-      }
-      take(r, e & 15u);
-      const uint32_t len = (e >> 16) + take(r, (e >> 4) & 15u);
-      refill(r);
-      const uint32_t d = lookup(w.dist, DIST_BITS, r.bb, &paths);
-      if (kind_of(d) != K_BASE) {
-        status = consumed(r) + 1 > total_bits ? TRUNCATED : BAD_CODE;
-        break;
-      }
-      take(r, d & 15u);
-      const uint32_t dist = (d >> 16) + take(r, (d >> 4) & 15u);
-      if (consumed(r) > total_bits) {
-        status = TRUNCATED;
-        break;
-      }
-      if (member_start != BEFORE) {
-        if (dist > pos - member_start) {
-          status = DISTANCE;
-          break;
-        }
-      } else if (dist > pos) {  // into the window before the run: the chain judges how far is too far
-        if (dist - pos > reach) reach = dist - pos;
-        bgz::or_word(&L.flags, G_MARKER);
-      }
-      if (len > region - pos) {
-        status = REGION;
-        break;
-      }
-      if (dist < len) paths |= P_OVERLAP;
-      if (dist > 16384) paths |= P_FAR;
-      // sources lie before `pos` whatever the distance, 64 symbols a step: within a step every source is read before
-      // a destination of that step is written, which matters where the ring's slots of both coincide
-      INF_SYNC();
-      for (uint32_t base = 0; base < len; base += LANES) {
-        INF_LANES(lane) {
-          const uint32_t i = base + lane;
-          if (i < len) {
-            const uint32_t o = dist >= len ? i : dist == 1 ? 0 : i % dist;
-            const uint16_t s = L.ring[(pos - dist + o) & RING_MASK];
-            if ((s & 0x8000u) && dist <= pos + o) bgz::or_word(&L.flags, G_MARKER_COPY);
-            L.ring[(pos + i) & RING_MASK] = s;
-          }
-        }
-      }
-      pos += len;
+      flush();
     }
   }
-  *pos_io = pos, *flushed_io = flushed, *reach_io = reach, *paths_io = paths;
-  return status;
-}
+  INF_M uint32_t distance(uint32_t dist) {
+    if (member_start != BEFORE) return dist > pos - member_start ? (uint32_t)DISTANCE : (uint32_t)OK;
+    if (dist > pos) {  // into the window before the run: the chain judges how far is too far
+      if (dist - pos > reach) reach = dist - pos;
+      bgz::or_word(&L.flags, G_MARKER);
+    }
+    return OK;
+  }
+  INF_M void match(uint32_t len, uint32_t dist) {
+    // sources lie before `pos` whatever the distance, 64 symbols a step: within a step every source is read before
+    // a destination of that step is written, which matters where the ring's slots of both coincide
+    INF_SYNC();
+    for (uint32_t base = 0; base < len; base += LANES) {
+      INF_LANES(lane) {
+        const uint32_t i = base + lane;
+        if (i < len) {
+          const uint32_t o = dist >= len ? i : dist == 1 ? 0 : i % dist;
+          const uint16_t s = L.ring[(pos - dist + o) & RING_MASK];
+          if ((s & 0x8000u) && dist <= pos + o) bgz::or_word(&L.flags, G_MARKER_COPY);
+          L.ring[(pos + i) & RING_MASK] = s;
+        }
+      }
+    }
+    pos += len;
+  }
+};
 
 // the run that begins in chunk k, if one does
 INF_HD void decode_run(const Job& j, uint32_t k, RunWork& L) {
@@ -459,19 +330,19 @@ INF_HD void decode_run(const Job& j, uint32_t k, RunWork& L) {
     uint32_t pos, reach, n_ends, member_start, in_member;
   };
   uint32_t in_member = k == 0 ? (j.st_in->in_member != 0) : 1u;
-  uint32_t pos = 0, flushed = 0, reach = 0, n_ends = 0, paths = 0, status = OK, at_end = 0, rolled = 0;
-  uint32_t member_start = BEFORE;
+  uint32_t n_ends = 0, paths = 0, status = OK, at_end = 0, rolled = 0;
+  RingSink out = {L, sym, region, BEFORE, 0, 0, 0};
   uint64_t p = start >> 3;  // the byte position while between members
   BitIn r;
   open_bits(r, j.in, j.n, in_member ? start : 0);
-  Mark ck = {start, 0, 0, 0, member_start, in_member};
+  Mark ck = {start, 0, 0, 0, BEFORE, in_member};
   uint64_t end_bit = start, header_from = NONE;
   const bool first_ever = k == 0 && !in_member && j.st_in->n_members_done == 0;
   for (;;) {  // each turn takes a block, a member header with its block, or ends the run
     bool fresh = false;
     if (!in_member) {
       end_bit = 8 * p;
-      ck = Mark{end_bit, pos, reach, n_ends, member_start, 0};
+      ck = Mark{end_bit, out.pos, out.reach, n_ends, out.member_start, 0};
       if (!last_run && end_bit >= target) break;
       if (p >= j.n) {
         at_end = 1;
@@ -513,17 +384,19 @@ INF_HD void decode_run(const Job& j, uint32_t k, RunWork& L) {
         if (q > j.n) status = TRUNCATED;
       }
       if (status != OK) break;
-      member_start = pos;
+      out.member_start = out.pos;
       in_member = 1;
       header_from = 8 * p;
       fresh = true;  // (the header counts only together with the member's first block)
       seek(r, (uint32_t)q);
     }
     end_bit = consumed(r);
-    if (!fresh) ck = Mark{end_bit, pos, reach, n_ends, member_start, 1};
+    if (!fresh) ck = Mark{end_bit, out.pos, out.reach, n_ends, out.member_start, 1};
     if (!last_run && end_bit >= target) break;
     uint32_t last = 0;
-    status = decode_block(r, L, total_bits, sym, region, member_start, &pos, &flushed, &reach, &last, &paths);
+    // (`paths` also keeps the bit of a dynamic block whose tables then fail to build.  That ends the run with a status
+    // other than OK -- not TRUNCATED: the header was inside the input -- and the chain takes no paths from such a run.)
+    status = decode_block(r, L.w, total_bits, out, &last, &paths);
     // (a verdict reached on bits behind the input's end is a verdict on zeros: the stream is cut off, whatever it says)
     if (status != OK && consumed(r) > total_bits) status = TRUNCATED;
     if (status != OK) break;
@@ -541,28 +414,28 @@ INF_HD void decode_run(const Job& j, uint32_t k, RunWork& L) {
       }
       const uint32_t crc = le32_at(j.in, j.n, p), isize = le32_at(j.in, j.n, p + 4);
       INF_LANES(lane) {
-        if (lane == 0) ends[n_ends] = End{pos, crc, isize, 0};
+        if (lane == 0) ends[n_ends] = End{out.pos, crc, isize, 0};
       }
       n_ends++;
       p += 8;
       in_member = 0;
-      member_start = BEFORE;  // (set again by the next header)
+      out.member_start = BEFORE;  // (set again by the next header)
     }
   }
   // the last run of bytes that are not the input's last: what the bytes cut off is not an error, the run ends with the
   // last block that ended inside them
   if (status == TRUNCATED && last_run && !j.last_block) {
     status = OK, rolled = 1, header_from = NONE;
-    end_bit = ck.bit, pos = ck.pos, reach = ck.reach, n_ends = ck.n_ends, member_start = ck.member_start, in_member = ck.in_member;
+    end_bit = ck.bit, out.pos = ck.pos, out.reach = ck.reach, n_ends = ck.n_ends, out.member_start = ck.member_start, in_member = ck.in_member;
   }
-  if (flushed > pos) flushed = pos;
-  flush_ring(L, sym, flushed, pos);
+  if (out.flushed > out.pos) out.flushed = out.pos;
+  out.flush();
   INF_LANES(lane) {
     if (lane == 0) {
       Run& R = j.runs[k];
       R.start_bit = start, R.end_bit = end_bit, R.sym_off = 0;
-      R.status = status, R.n_sym = pos, R.reach = reach, R.n_ends = n_ends;
-      R.member_start = member_start, R.in_member = in_member, R.at_end = at_end;
+      R.status = status, R.n_sym = out.pos, R.reach = out.reach, R.n_ends = n_ends;
+      R.member_start = out.member_start, R.in_member = in_member, R.at_end = at_end;
       R.flags = L.flags | (n_ends ? (uint32_t)G_MEMBER_END : 0u) | (rolled ? (uint32_t)G_ROLLBACK : 0u);
       R.paths = paths, R.n_chunks = nxt - k, R.pad = 0;
       R.header_from = status == OK && in_member ? header_from : NONE;
@@ -581,9 +454,7 @@ INF_HD void chain_serial(const Job& j) {
   auto decline = [&](uint32_t why, uint32_t k) {
     if (s.status == OK) s.status = why, s.bad_chunk = k;
   };
-  if (j.n > MAX_IN || st.bit_offset > 7 || st.window_len > WINDOW || (!st.in_member && st.bit_offset) ||
-      (st.in_member && st.window_len != (st.member_len < WINDOW ? st.member_len : WINDOW)))
-    decline(INPUT, 0);
+  if (j.n > MAX_IN || !state_consistent(st)) decline(INPUT, 0);
   for (uint32_t k = 0; k < j.n_chunks && s.status != INPUT; k++) {
     if (j.cand[k] == NONE) continue;
     const Run R = j.runs[k];
@@ -672,7 +543,7 @@ INF_HD void resolve_tile(const Job& j, uint64_t T, TileWork& L) {
   }
   const uint32_t r0 = lo;
   INF_LANES(lane) {
-    for (uint32_t t = lane; t < 256; t += LANES) L.crc_tab[t] = bgz::crc_table_entry(t);
+    fill_crc_table(L.crc_tab, lane);
     uint32_t r = r0;
     for (uint32_t i = lane; i < len; i += LANES) {
       const uint64_t at = a + i;
@@ -703,8 +574,7 @@ INF_HD void resolve_tile(const Job& j, uint64_t T, TileWork& L) {
       L.seg_crc[lane] = c;
     }
     INF_SYNC();
-    uint32_t c = 0;
-    for (uint32_t i = 0; i < LANES; i++) c ^= L.seg_crc[i];
+    uint32_t c = fold_seg_crc(L.seg_crc);
     INF_SYNC();
     c = bgz::crc_mul(bgz::crc_xpow8((uint32_t)(member_end - (a + pb))), INF_UNIFORM(c));
     INF_LANES(lane) {

@@ -14,6 +14,12 @@
 // Lane-parallel phases are written INF_LANES(lane) { ... } with INF_SYNC() between phases that hand data from lane to
 // lane: on the device the body runs once in every lane, on the host as a loop over the 64 lanes.
 //
+// What RFC 1951 says about a block stands here once, for this inflater and for the one of plain gzip (gzip_device.h):
+// decode_block<Sink> reads BFINAL / BTYPE, the stored prologue, the fixed or dynamic header (fixed_lengths,
+// read_dynamic_header), builds both tables and runs the symbol loop; the bytes go to a sink, a template parameter that
+// holds only what the two formats do differently (the list stands at decode_block).  MemberSink is this inflater's;
+// inflate_member is the loop over a member's blocks and the checks behind the last one.
+//
 // Nothing here trusts the stream: compressed bytes are read inside the payload only (behind its end the reader yields
 // zeros and the member ends with TRUNCATED), every write is bounded by ISIZE, every match by the bytes produced so far,
 // every table index by the table's size, and every turn of every loop takes at least one bit off a stream whose bits
@@ -314,6 +320,11 @@ INF_HD uint32_t next_word(BitIn& r) {
   r.k++;
   return v;
 }
+// a reader over base[lo, hi) that stands nowhere yet: a seek comes next.  (win_k: no word is within 64 of it, so the
+// first next_word loads the window.)
+INF_HD void open_bits(BitIn& r, const uint8_t* base, uint32_t lo, uint32_t hi) {
+  r.base = base, r.lo = lo, r.hi = hi, r.k = 0, r.bb = 0, r.bc = 0, r.win = 0, r.win_k = 0xFFFF0000u;
+}
 // at byte p of the payload
 INF_HD void seek(BitIn& r, uint32_t p) {
   const uint32_t at = r.lo + p;
@@ -347,11 +358,17 @@ INF_HD uint32_t lookup(const uint32_t* table, uint32_t root, uint64_t bb, uint32
 
 // ---- CRC-32 of out[0, n): a segment of whole words per lane, an odd number of them so that the lanes' reads fall on
 // different banks; every segment's CRC is moved to the end of the data (x^(8 * bytes behind it)) and the lot is summed ----
+INF_HD void fill_crc_table(uint32_t* tab, uint32_t lane) {  // this lane's share of the 256 entries
+  for (uint32_t t = lane; t < 256; t += LANES) tab[t] = bgz::crc_table_entry(t);
+}
+INF_HD uint32_t fold_seg_crc(const uint32_t* seg_crc) {  // the lanes' pieces, each already moved to the end of the data
+  uint32_t c = 0;
+  for (uint32_t i = 0; i < LANES; i++) c ^= seg_crc[i];
+  return c;
+}
 INF_HD uint32_t crc_of_output(Work& w, const uint32_t* outw, uint32_t n) {
   INF_SYNC();
-  INF_LANES(lane) {
-    for (uint32_t t = lane; t < 256; t += LANES) w.crc_tab[t] = bgz::crc_table_entry(t);
-  }
+  INF_LANES(lane) { fill_crc_table(w.crc_tab, lane); }
   INF_SYNC();
   const uint32_t seg = 4 * ((((n + 3) / 4 + LANES - 1) / LANES) | 1u);
   INF_LANES(lane) {
@@ -368,10 +385,182 @@ INF_HD uint32_t crc_of_output(Work& w, const uint32_t* outw, uint32_t n) {
     w.seg_crc[lane] = c;
   }
   INF_SYNC();
-  uint32_t c = 0;
-  for (uint32_t i = 0; i < LANES; i++) c ^= w.seg_crc[i];
-  return INF_UNIFORM(c);
+  return INF_UNIFORM(fold_seg_crc(w.seg_crc));
 }
+
+// ---- one DEFLATE block, for both inflaters: this one's members and the runs of plain gzip (gzip_device.h) ----
+// The header of a dynamic block behind its three first bits: the lengths of both codes into w.lens, *hlit and *hdist
+// their counts.  OK, TRUNCATED or CODE_LENGTHS.
+INF_HD uint32_t read_dynamic_header(BitIn& r, Work& w, uint64_t total_bits, uint32_t* hlit_out, uint32_t* hdist_out) {
+  refill(r);
+  const uint32_t hlit = take(r, 5) + 257, hdist = take(r, 5) + 1, hclen = take(r, 4) + 4;
+  if (hlit > 286 || hdist > 30) return CODE_LENGTHS;
+  INF_SYNC();
+  INF_LANES(lane) {
+    if (lane < 20) w.cl_lens[lane] = 0;
+  }
+  INF_SYNC();
+  for (uint32_t i = 0; i < hclen; i++) {
+    refill(r);
+    w.cl_lens[bgz::cl_order(i)] = (uint8_t)take(r, 3);  // (every lane stores the same value)
+  }
+  if (consumed(r) > total_bits) return TRUNCATED;
+  INF_SYNC();
+  if (build_table(w, w.cl_lens, 19, CL_BITS, w.cl, CL_ENTRIES, T_CL) != OK) return CODE_LENGTHS;
+  uint32_t n = 0, prev = 0;
+  while (n < hlit + hdist) {  // each turn takes a bit at least
+    refill(r);
+    if (consumed(r) > total_bits) return TRUNCATED;
+    const uint32_t e = INF_UNIFORM(w.cl[(uint32_t)r.bb & (CL_ENTRIES - 1)]);
+    if (kind_of(e) != K_LIT) return CODE_LENGTHS;
+    take(r, e & 15u);
+    const uint32_t sym = e >> 16;
+    if (sym < 16) {
+      w.lens[n++] = (uint8_t)sym;
+      prev = sym;
+      continue;
+    }
+    uint32_t rep, val = 0;
+    if (sym == 16) {
+      if (n == 0) return CODE_LENGTHS;
+      val = prev;
+      rep = 3 + take(r, 2);
+    } else if (sym == 17) {
+      rep = 3 + take(r, 3);
+    } else {
+      rep = 11 + take(r, 7);
+    }
+    if (rep > hlit + hdist - n) return CODE_LENGTHS;
+    INF_LANES(lane) {
+      for (uint32_t i = lane; i < rep; i += LANES) w.lens[n + i] = (uint8_t)val;
+    }
+    n += rep;
+    prev = val;
+  }
+  if (consumed(r) > total_bits) return TRUNCATED;
+  INF_SYNC();
+  if (INF_UNIFORM(w.lens[256]) == 0) return CODE_LENGTHS;
+  *hlit_out = hlit, *hdist_out = hdist;
+  return OK;
+}
+// the lengths of the fixed codes into w.lens: 288 literal/length symbols, then 32 distance symbols
+INF_HD void fixed_lengths(Work& w) {
+  INF_SYNC();
+  INF_LANES(lane) {
+    for (uint32_t s = lane; s < 320; s += LANES) w.lens[s] = (uint8_t)(s < 144 ? 8 : s < 256 ? 9 : s < 280 ? 7 : s < 288 ? 8 : 5);
+  }
+}
+
+// The block at the reader's position, its bytes handed to `s`.  OK (*last: the block was final) or why not; *paths
+// gains the P_ bits of what the block went through.  A sink is where the two formats differ and nothing else:
+//   pos                  bytes it holds so far (wave-uniform, as the reader's state is)
+//   room()               bytes it still takes; FULL the status of a block that brings more
+//   before_symbol()      a turn of the symbol loop begins
+//   literal(b)           one byte                          } room() has been checked,
+//   stored(src, len)     len bytes from the input          } pos moves on
+//   match(len, dist)     len bytes from dist bytes back    }
+//   distance(dist)       OK, or the status of a match that begins before what it may reach
+//   DIST_CODE_AT_END     the status of an unassigned distance code whose first bit is past the input's end
+template <class Sink>
+INF_HD uint32_t decode_block(BitIn& r, Work& w, uint64_t total_bits, Sink& s, uint32_t* last, uint32_t* paths) {
+  refill(r);
+  *last = take(r, 1);
+  const uint32_t type = take(r, 2);
+  if (consumed(r) > total_bits) return TRUNCATED;
+  if (type == 3) return BLOCK_TYPE;
+  if (type == 0) {
+    take(r, r.bc & 7u);
+    refill(r);
+    const uint32_t len = take(r, 16);
+    refill(r);
+    const uint32_t nlen = take(r, 16);
+    if (consumed(r) > total_bits) return TRUNCATED;
+    if ((len ^ 0xFFFFu) != nlen) return STORED_LEN;
+    const uint32_t p = (uint32_t)(consumed(r) >> 3);
+    if (len > r.hi - r.lo - p) return TRUNCATED;
+    if (len > s.room()) return Sink::FULL;
+    s.stored(r.base + r.lo + p, len);
+    seek(r, p + len);
+    *paths |= P_STORED;
+    return OK;
+  }
+  uint32_t hlit, hdist;
+  if (type == 1) {
+    hlit = 288, hdist = 32;
+    fixed_lengths(w);
+    *paths |= P_FIXED;
+  } else {
+    const uint32_t status = read_dynamic_header(r, w, total_bits, &hlit, &hdist);
+    if (status != OK) return status;
+    *paths |= P_DYNAMIC;
+  }
+  INF_SYNC();
+  uint32_t status = build_table(w, w.lens, hlit, LIT_BITS, w.lit, LIT_ENTRIES, T_LIT);
+  if (status == OK) status = build_table(w, w.lens + hlit, hdist, DIST_BITS, w.dist, DIST_ENTRIES, T_DIST);
+  if (status != OK) return status;
+  // symbols: each turn takes a bit at least, and a symbol counts only when all its bits were the input's
+  for (;;) {
+    s.before_symbol();
+    refill(r);
+    const uint32_t e = lookup(w.lit, LIT_BITS, r.bb, paths), kind = kind_of(e);
+    if (kind != K_BASE) {  // (lengths are told apart first: their turn does not pay for the check below)
+      if (kind != K_LIT && kind != K_EOB) return consumed(r) + 1 > total_bits ? TRUNCATED : BAD_CODE;
+      // A literal or the end-of-block code: all its bits must be the input's, in both formats.  A member would come to
+      // the same word without the check on the end-of-block code: one past the payload's end leaves consumed(r) past
+      // it for good, so the next block's three bits, or inflate_member's epilogue behind a final block, end the
+      // member TRUNCATED before anything else is written or judged.  A run needs it: decode_run takes a block that
+      // ended with OK as a boundary it may stop at or roll back to.
+      take(r, e & 15u);
+      if (consumed(r) > total_bits) return TRUNCATED;
+      if (kind == K_EOB) return OK;
+      if (!s.room()) return Sink::FULL;
+      s.literal(e >> 16);
+      continue;
+    }
+    take(r, e & 15u);
+    const uint32_t len = (e >> 16) + take(r, (e >> 4) & 15u);
+    refill(r);
+    const uint32_t d = lookup(w.dist, DIST_BITS, r.bb, paths);
+    if (kind_of(d) != K_BASE) return consumed(r) + 1 > total_bits ? Sink::DIST_CODE_AT_END : BAD_CODE;
+    take(r, d & 15u);
+    const uint32_t dist = (d >> 16) + take(r, (d >> 4) & 15u);
+    if (consumed(r) > total_bits) return TRUNCATED;
+    status = s.distance(dist);
+    if (status != OK) return status;
+    if (len > s.room()) return Sink::FULL;
+    if (dist < len) *paths |= P_OVERLAP;
+    if (dist > 16384) *paths |= P_FAR;
+    s.match(len, dist);
+  }
+  // (not reached: every way out of the loop is a return above; no block ends without the check on its last bits)
+  return consumed(r) > total_bits ? TRUNCATED : OK;
+}
+
+// a member's bytes: out[0, isize) in one flat buffer
+struct MemberSink {
+  static constexpr uint32_t FULL = OUTPUT, DIST_CODE_AT_END = BAD_CODE;
+  uint8_t* out;
+  uint32_t isize, pos;
+  INF_M uint32_t room() const { return isize - pos; }
+  INF_M void before_symbol() {}
+  INF_M void literal(uint32_t b) { out[pos++] = (uint8_t)b; }  // (every lane stores the same value)
+  INF_M void stored(const uint8_t* src, uint32_t len) {
+    INF_LANES(lane) {
+      for (uint32_t i = lane; i < len; i += LANES) out[pos + i] = src[i];
+    }
+    pos += len;
+  }
+  INF_M uint32_t distance(uint32_t dist) const { return dist > pos ? (uint32_t)DISTANCE : (uint32_t)OK; }
+  INF_M void match(uint32_t len, uint32_t dist) {
+    // sources lie before `pos` whatever the distance: the lanes need no order among themselves
+    INF_SYNC();
+    INF_LANES(lane) {
+      const uint8_t* src = out + pos - dist;
+      for (uint32_t i = lane; i < len; i += LANES) out[pos + i] = src[dist >= len ? i : dist == 1 ? 0 : i % dist];
+    }
+    pos += len;
+  }
+};
 
 struct Result {
   uint32_t status, paths;
@@ -380,215 +569,25 @@ struct Result {
 // The raw DEFLATE stream base[lo, hi) -> outw (MAX_OUT bytes and a word of slack), which must come to exactly `isize`
 // bytes with CRC-32 `crc`.
 INF_HD Result inflate_member(const uint8_t* base, uint32_t lo, uint32_t hi, uint32_t isize, uint32_t crc, uint32_t* outw, Work& w) {
-  uint8_t* const out = (uint8_t*)outw;
   Result res = {OK, 0};
   if (isize > MAX_OUT || hi < lo) {
     res.status = MEMBER;
     return res;
   }
   BitIn r;
-  r.base = base, r.lo = lo, r.hi = hi, r.k = 0, r.bb = 0, r.bc = 0, r.win = 0, r.win_k = 0xFFFF0000u;
+  open_bits(r, base, lo, hi);
   seek(r, 0);
   const uint64_t total_bits = 8ull * (hi - lo);
-  uint32_t pos = 0, paths = 0, n_blocks = 0, status = OK;
-  for (;;) {  // blocks: each takes 3 bits at least
-    refill(r);
-    const uint32_t last = take(r, 1), type = take(r, 2);
-    if (consumed(r) > total_bits) {
-      status = TRUNCATED;
-      break;
-    }
-    if (++n_blocks > 1) paths |= P_MULTIBLOCK;
-    if (type == 3) {
-      status = BLOCK_TYPE;
-      break;
-    }
-    if (type == 0) {
-      take(r, r.bc & 7u);
-      refill(r);
-      const uint32_t len = take(r, 16);
-      refill(r);
-      const uint32_t nlen = take(r, 16);
-      if (consumed(r) > total_bits) {
-        status = TRUNCATED;
-        break;
-      }
-      if ((len ^ 0xFFFFu) != nlen) {
-        status = STORED_LEN;
-        break;
-      }
-      const uint32_t p = (uint32_t)(consumed(r) >> 3);
-      if (len > hi - lo - p) {
-        status = TRUNCATED;
-        break;
-      }
-      if (len > isize - pos) {
-        status = OUTPUT;
-        break;
-      }
-      INF_LANES(lane) {
-        for (uint32_t i = lane; i < len; i += LANES) out[pos + i] = base[lo + p + i];
-      }
-      pos += len;
-      seek(r, p + len);
-      paths |= P_STORED;
-    } else {
-      uint32_t hlit, hdist;
-      if (type == 1) {
-        hlit = 288, hdist = 32;
-        INF_SYNC();
-        INF_LANES(lane) {
-          for (uint32_t s = lane; s < 320; s += LANES) w.lens[s] = (uint8_t)(s < 144 ? 8 : s < 256 ? 9 : s < 280 ? 7 : s < 288 ? 8 : 5);
-        }
-        paths |= P_FIXED;
-      } else {
-        refill(r);
-        hlit = take(r, 5) + 257, hdist = take(r, 5) + 1;
-        const uint32_t hclen = take(r, 4) + 4;
-        if (hlit > 286 || hdist > 30) {
-          status = CODE_LENGTHS;
-          break;
-        }
-        INF_SYNC();
-        INF_LANES(lane) {
-          if (lane < 20) w.cl_lens[lane] = 0;
-        }
-        INF_SYNC();
-        for (uint32_t i = 0; i < hclen; i++) {
-          refill(r);
-          w.cl_lens[bgz::cl_order(i)] = (uint8_t)take(r, 3);  // (every lane stores the same value)
-        }
-        if (consumed(r) > total_bits) {
-          status = TRUNCATED;
-          break;
-        }
-        INF_SYNC();
-        if (build_table(w, w.cl_lens, 19, CL_BITS, w.cl, CL_ENTRIES, T_CL) != OK) {
-          status = CODE_LENGTHS;
-          break;
-        }
-        uint32_t n = 0, prev = 0;
-        while (n < hlit + hdist) {  // each turn takes a bit at least
-          refill(r);
-          if (consumed(r) > total_bits) {
-            status = TRUNCATED;
-            break;
-          }
-          const uint32_t e = INF_UNIFORM(w.cl[(uint32_t)r.bb & (CL_ENTRIES - 1)]);
-          if (kind_of(e) != K_LIT) {
-            status = CODE_LENGTHS;
-            break;
-          }
-          take(r, e & 15u);
-          const uint32_t sym = e >> 16;
-          if (sym < 16) {
-            w.lens[n++] = (uint8_t)sym;
-            prev = sym;
-            continue;
-          }
-          uint32_t rep, val = 0;
-          if (sym == 16) {
-            if (n == 0) {
-              status = CODE_LENGTHS;
-              break;
-            }
-            val = prev;
-            rep = 3 + take(r, 2);
-          } else if (sym == 17) {
-            rep = 3 + take(r, 3);
-          } else {
-            rep = 11 + take(r, 7);
-          }
-          if (rep > hlit + hdist - n) {
-            status = CODE_LENGTHS;
-            break;
-          }
-          INF_LANES(lane) {
-            for (uint32_t i = lane; i < rep; i += LANES) w.lens[n + i] = (uint8_t)val;
-          }
-          n += rep;
-          prev = val;
-        }
-        if (status != OK) break;
-        if (consumed(r) > total_bits) {
-          status = TRUNCATED;
-          break;
-        }
-        INF_SYNC();
-        if (INF_UNIFORM(w.lens[256]) == 0) {
-          status = CODE_LENGTHS;
-          break;
-        }
-        paths |= P_DYNAMIC;
-      }
-      INF_SYNC();
-      status = build_table(w, w.lens, hlit, LIT_BITS, w.lit, LIT_ENTRIES, T_LIT);
-      if (status == OK) status = build_table(w, w.lens + hlit, hdist, DIST_BITS, w.dist, DIST_ENTRIES, T_DIST);
-      if (status != OK) break;
-      // symbols: each turn takes a bit at least, and a symbol counts only when all its bits were the payload's
-      for (;;) {
-        refill(r);
-        const uint32_t e = lookup(w.lit, LIT_BITS, r.bb, &paths), kind = kind_of(e);
-        if (kind == K_LIT) {
-          take(r, e & 15u);
-          if (consumed(r) > total_bits) {
-            status = TRUNCATED;
-            break;
-          }
-          if (pos >= isize) {
-            status = OUTPUT;
-            break;
-          }
-          out[pos++] = (uint8_t)(e >> 16);  // (every lane stores the same value)
-          continue;
-        }
-        if (kind == K_EOB) {
-          take(r, e & 15u);
-          break;
-        }
-        if (kind != K_BASE) {
-          status = consumed(r) + 1 > total_bits ? TRUNCATED : BAD_CODE;
-          break;
-        }
-        take(r, e & 15u);
-        const uint32_t len = (e >> 16) + take(r, (e >> 4) & 15u);
-        refill(r);
-        const uint32_t d = lookup(w.dist, DIST_BITS, r.bb, &paths);
-        if (kind_of(d) != K_BASE) {
-          status = BAD_CODE;
-          break;
-        }
-        take(r, d & 15u);
-        const uint32_t dist = (d >> 16) + take(r, (d >> 4) & 15u);
-        if (consumed(r) > total_bits) {
-          status = TRUNCATED;
-          break;
-        }
-        if (dist > pos) {
-          status = DISTANCE;
-          break;
-        }
-        if (len > isize - pos) {
-          status = OUTPUT;
-          break;
-        }
-        if (dist < len) paths |= P_OVERLAP;
-        if (dist > 16384) paths |= P_FAR;
-        // sources lie before `pos` whatever the distance: the lanes need no order among themselves
-        INF_SYNC();
-        INF_LANES(lane) {
-          const uint8_t* src = out + pos - dist;
-          for (uint32_t i = lane; i < len; i += LANES) out[pos + i] = src[dist >= len ? i : dist == 1 ? 0 : i % dist];
-        }
-        pos += len;
-      }
-      if (status != OK) break;
-    }
-    if (last) break;
+  MemberSink out = {(uint8_t*)outw, isize, 0};
+  uint32_t paths = 0, last = 0, status = OK;
+  for (uint32_t n_blocks = 0; status == OK && !last; n_blocks++) {  // each takes 3 bits at least
+    // (a further block counts once its three first bits were the payload's)
+    if (n_blocks && consumed(r) + 3 <= total_bits) paths |= P_MULTIBLOCK;
+    status = decode_block(r, w, total_bits, out, &last, &paths);
   }
   if (status == OK && consumed(r) > total_bits) status = TRUNCATED;
   if (status == OK && (consumed(r) + 7) / 8 != hi - lo) status = TRAILING;
-  if (status == OK && pos != isize) status = OUTPUT;
+  if (status == OK && out.pos != isize) status = OUTPUT;
   if (status == OK && crc_of_output(w, outw, isize) != crc) status = CRC;
   res.status = status;
   res.paths = paths;
