@@ -417,7 +417,7 @@ def ordinary_reads(t, n, L=91, stream=0, sub_rate=0.01, indel_rate=0.001):
 
 
 # ------------------------------------------------------------------ more hits than the team kernel takes
-TEAM_HITS, TEAM_MAX_HITS, COMPACT_HEAVY_N = 256, 60000, 8  # launch.h, kernels_extend.hip
+TEAM_HITS, TEAM_MAX_HITS, COMPACT_HEAVY_N = 256, 60000, 8  # launch.h, kernels_compact.hip
 
 
 def _other_base(*avoid):

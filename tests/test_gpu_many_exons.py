@@ -2,7 +2,7 @@
 
 Those kernels hold FAST_MAX_YCLIPS = 64 intron markers per alignment (extend_plan.h).  An alignment that needs more sets
 FAULT_RETRY: the read goes on the retry list, its wave's DP counters are zeroed, and the any-width kernel redoes it
-(kernels_extend.hip).  The host arms this when the index has a transcript of more than 65 exons (pipeline.hip,
+(lift_markers in extend_device.h, kernels_extend.hip).  The host arms this when the index has a transcript of more than 65 exons (pipeline.hip,
 seed_hits.hip), which no other reference of the suite has.  The micro-exon reference of gpu_common has transcripts of up
 to 202 exons; tests/test_many_exons_host.py pins, with the oracle alone, that its read sets have alignments on both sides
 of the limit.  Every test states the path it enters as an assertion on oracle or smems_batch output, and compares

@@ -11,7 +11,7 @@ import pytest
 from oracle import pyoracle as orc
 from thermite_amd import capi, refdata, synth
 
-from gpu_common import World, assert_hits_equal, expected_batch, expected_hit, initial_band, mutate
+from gpu_common import World, _tx_exons, assert_hits_equal, check_align, expected_batch, expected_hit, initial_band, mutate
 
 pytestmark = pytest.mark.gpu
 
@@ -182,6 +182,73 @@ def test_align_seed_hits_synthetic(syn):
     """multi-exon transcripts on both strands, 150-base reads (bands of three cells per lane)"""
     _check_world(syn, 200, 91, 3)
     _check_world(syn, 60, 150, 4)
+
+
+def _short_intron_reference(seed=0x696E7472):
+    """One random contig whose transcripts have two or three exons of 36..44 bases separated by introns of 6..10 bases
+    (shorter than min_seed_len = 20), on both strands; every three-exon gene has a second isoform without the middle
+    exon.  tables["_spans"]: each gene's (first exon start, last exon end) on the contig."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    n_genes, slot = 60, 400
+    name = "shortintron"
+    seq = _ACGT[rng.integers(0, 4, n_genes * slot + 200)]
+    genes, txs, spans = [], [], []
+    for g in range(n_genes):
+        n_ex = 2 + g % 2
+        p = 100 + g * slot + int(rng.integers(0, 100))
+        exons = []
+        for _ in range(n_ex):
+            e = p + int(rng.integers(36, 45))
+            exons.append((p, e))
+            p = e + int(rng.integers(6, 11))
+        strand = bool(g % 4 < 2)
+        genes.append(dict(id="SIG%03d" % g, name="si%d" % g))
+        txs.append(dict(id="SIT%03d.0" % g, gene_idx=g, chrom=name, strand=strand, exons=exons))
+        if n_ex == 3:
+            txs.append(dict(id="SIT%03d.1" % g, gene_idx=g, chrom=name, strand=strand, exons=[exons[0], exons[2]]))
+        spans.append((exons[0][0], exons[-1][1]))
+    t = refdata.build_tables([(name, seq)], genes, txs)
+    t["_spans"] = spans
+    return t
+
+
+@pytest.fixture(params=[False, True], ids=["c32", "c64"])
+def short_introns(request):
+    return _world("short_introns", _short_intron_reference, request.param)
+
+
+def _seeds_meeting_two_exons(t, hits):
+    """hits whose seed [ref_idx, ref_idx + len) intersects at least two exons of one transcript"""
+    s = hits["ref_idx"].astype(np.int64)
+    e = s + hits["len"].astype(np.int64)
+    found = np.zeros(len(hits), bool)
+    for tx_idx in range(len(t["txs"])):
+        met = np.zeros(len(hits), np.int64)
+        for x0, x1, _ in _tx_exons(t, tx_idx):
+            met += (s < x1) & (x0 < e)
+        found |= met >= 2
+    return int(found.sum())
+
+
+def test_seed_across_short_intron(short_introns):
+    """Reads copied from the genome across introns shorter than min_seed_len: their seeds run through an intron into the
+    transcript's next exon, so the exon grid yields an entry whose previous exon reaches into the seed, and
+    lift_mem_to_tx (src/txome.rs:82-103) takes its general case, the first exon in transcript order that intersects
+    the seed (extend_device.h, lift_seed_to_tx).  Read level (thm_align_batch) and hit level (thm_align_seed_hits_batch)."""
+    w = short_introns
+    rng = np.random.default_rng(9)
+    fwd = w.t["text"][: int(w.t["refs"][0]["len"])]
+    reads = []
+    for i in range(240):
+        lo, hi = w.t["_spans"][i % len(w.t["_spans"])]
+        s = int(rng.integers(lo - 20, hi - 91 + 20))  # every 91-base window here holds an intron and part of both exons beside it
+        r = mutate(rng, fwd[s: s + 91], sub=0.015, indel=0.0)
+        reads.append(refdata.revcomp(r) if i % 3 == 2 else r)
+    bases, off = refdata.pack_reads(reads)
+    _, hits = w.a.smems_batch(bases, off, capi.CI_OPTS["min_seed_len"])
+    assert _seeds_meeting_two_exons(w.t, hits) > 0
+    check_align(w, bases, off, capi.CI_OPTS)
+    _check_world(w, 0, 0, 9, reads=(bases, off))
 
 
 def test_consistent_with_align_batch(syn):

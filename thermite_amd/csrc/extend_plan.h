@@ -2,7 +2,7 @@
 // length classes of a batch, and the plan of one run's launches (grids, scratch slices, the waves' counter rows).
 //
 // Plain C++17: no HIP runtime header, so that a host program can evaluate the plan (tests/cpp/extend_plan_main.cpp).
-// Under hipcc the buffer-size functions are __host__ __device__, and the kernels of kernels_extend.hip call the same
+// Under hipcc the buffer-size functions are __host__ __device__, and the kernels of kernels_extend.hip and kernels_seed_hit.hip call the same
 // inline functions as the host's sizing.
 #ifndef THERMITE_EXTEND_PLAN_H
 #define THERMITE_EXTEND_PLAN_H

@@ -357,14 +357,7 @@ size_t swg_batch_lds_bytes(const SwgBatchParams& p, int cpl) {
 
 hipError_t launch_swg_batch(const SwgBatchParams& p, int cpl, int n_blocks, hipStream_t s) {
   const size_t lds = swg_batch_lds_bytes(p, cpl);
-  auto go = [&](auto kern) -> hipError_t {
-    if (lds > 48 * 1024) {
-      hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(256), lds, s, p);
-    return hipGetLastError();
-  };
+  auto go = [&](auto kern) { return launch_with_lds(kern, n_blocks, 256, lds, s, p); };
   switch (cpl) {
     case 0: return go(dev::swg_batch_kernel<0>);
     case 1: return go(dev::swg_batch_kernel<1>);
@@ -385,14 +378,7 @@ size_t elr_batch_lds_bytes(const ElrBatchParams& p, int cpl) {
 
 hipError_t launch_elr_batch(const ElrBatchParams& p, int cpl, int n_blocks, hipStream_t s) {
   const size_t lds = elr_batch_lds_bytes(p, cpl);
-  auto go = [&](auto kern) -> hipError_t {
-    if (lds > 48 * 1024) {
-      hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(256), lds, s, p);
-    return hipGetLastError();
-  };
+  auto go = [&](auto kern) { return launch_with_lds(kern, n_blocks, 256, lds, s, p); };
   switch (cpl) {
     case 0: return go(dev::elr_batch_kernel<0>);
     case 1: return go(dev::elr_batch_kernel<1>);

@@ -62,8 +62,6 @@ constexpr int TPR_MAX_PEND = 24;  // extension problems one read may ask for in 
 #endif
 constexpr int TPR_CTL_MINW = THM_TPR_CTL_MINW;  // waves per SIMD the control kernel's register budget is set for
 
-enum : int { FAULT_OPS_POOL = 1 };  // kernels_extend.hip
-
 template <class C>
 struct TCoord {
   typedef int S;
@@ -131,7 +129,7 @@ struct TCand {
 };
 
 // One op stream: [Xclip(lead)] path with introns [Xclip(trail)], mirrored as a list when `rev`
-// (kernels_extend.hip::emit_alignment).  Paths are Match almost everywhere: zero fill, then patches.
+// (extend_device.h::emit_alignment).  Paths are Match almost everywhere: zero fill, then patches.
 // `o` is 4-byte aligned and the allocation is rounded up to 4 bytes.
 __device__ __forceinline__ void emit_stream(uint8_t* o, int total, const uint16_t* ed, int n_ed, int lead, int trail, bool rev, int n_y,
                                             const uint32_t* mk_k, const uint32_t* ycl) {
@@ -1373,7 +1371,7 @@ __global__ __launch_bounds__(256) void extend_dp_kernel(DpParams p) {
   if constexpr (CPLMAX >= 2) dp_class<2>(p, xs, ys, trace, opsb, ops_cap, wave_global, n_waves, fault);
   if constexpr (CPLMAX >= 3) dp_class<3>(p, xs, ys, trace, opsb, ops_cap, wave_global, n_waves, fault);
   if constexpr (CPLMAX >= 4) dp_class<4>(p, xs, ys, trace, opsb, ops_cap, wave_global, n_waves, fault);
-  if (lane_id() == 0 && fault) atomicOr(p.fault, 2 | (fault << 4));  // FAULT_INTERNAL (kernels_extend.hip) + which check (diagnosis)
+  if (lane_id() == 0 && fault) atomicOr(p.fault, FAULT_INTERNAL | (fault << 4));  // + which check (diagnosis)
 }
 
 }  // namespace dev
@@ -1419,25 +1417,12 @@ hipError_t launch_tpr_order(const ReadRecT<uint64_t>* recs, uint64_t n, uint32_t
 size_t extend_dpt_lds_bytes(uint32_t tcols) { return (size_t)dev::DPT_THREADS * tcols * 4; }
 hipError_t launch_extend_dpt(const DpParams& p, int n_blocks, hipStream_t s) {
   if (n_blocks <= 0) return hipSuccess;
-  const size_t lds = extend_dpt_lds_bytes(p.tcols);
-  if (lds > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)dev::extend_dpt_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(dev::extend_dpt_kernel, dim3(n_blocks), dim3(dev::DPT_THREADS), lds, s, p);
-  return hipGetLastError();
+  return launch_with_lds(dev::extend_dpt_kernel, n_blocks, dev::DPT_THREADS, extend_dpt_lds_bytes(p.tcols), s, p);
 }
 
 hipError_t launch_extend_dp(const DpParams& p, int cpl_max, int n_blocks, hipStream_t s) {
   const size_t lds = extend_dp_lds_bytes(p.x_cap, p.y_cap);
-  auto go = [&](auto kern) -> hipError_t {
-    if (lds > 48 * 1024) {
-      hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(256), lds, s, p);
-    return hipGetLastError();
-  };
+  auto go = [&](auto kern) { return launch_with_lds(kern, n_blocks, 256, lds, s, p); };
   switch (cpl_max) {
     case 1: return go(dev::extend_dp_kernel<1>);
     case 2: return go(dev::extend_dp_kernel<2>);

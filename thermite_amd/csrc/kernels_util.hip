@@ -1,6 +1,9 @@
 // kernels_util.hip -- small plumbing kernels: exclusive prefix sums that turn
-// per-read counts into offsets (count -> scan -> fill).
+// per-read counts into offsets (count -> scan -> fill), and the sum of the
+// counter rows the extend kernels' waves leave.
 #include <hip/hip_runtime.h>
+
+#include <algorithm>
 
 #include "launch.h"
 #include "lut_direct.h"
@@ -184,6 +187,43 @@ __global__ __launch_bounds__(256) void calib_gather_kernel(const uint8_t* table,
   if (acc == 0x7f4a7c15ull) *sink = acc;  // keeps the loads alive (a value all three patterns can produce)
 }
 
+// counters[k] += sum of wave_counters[row][k] (the rows the extend kernels' waves left), and every row that held
+// something is zeroed again: the rows are clean when the next run starts, whatever its number of rows.  A workgroup
+// takes REDUCE_GROUPS rows at a time (a row is one 128-byte line), sums them in LDS and adds its sums with one atomic
+// per counter (the sums are integers: the order of the workgroups does not show).
+constexpr int REDUCE_GROUPS = 64, REDUCE_MAX_BLOCKS = 32;
+__global__ __launch_bounds__(REDUCE_GROUPS * THM_N_COUNTERS) void counters_reduce_kernel(unsigned long long* rows, uint32_t n_rows,
+                                                                                       unsigned long long* counters) {
+  __shared__ unsigned long long part[REDUCE_GROUPS][THM_N_COUNTERS];
+  static_assert(THM_N_COUNTERS == 16, "one thread per counter and row group");
+  const int k = (int)(threadIdx.x & 15u), g = (int)(threadIdx.x >> 4);
+  const uint32_t step = gridDim.x * REDUCE_GROUPS;
+  unsigned long long sum = 0;
+  // four rows in flight per thread (the stores would otherwise order the loads behind them)
+  for (uint32_t r0 = blockIdx.x * REDUCE_GROUPS + (uint32_t)g; r0 < n_rows; r0 += 4 * step) {
+    unsigned long long v[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const uint64_t r = (uint64_t)r0 + (uint64_t)j * step;
+      v[j] = r < n_rows ? rows[r * THM_N_COUNTERS + k] : 0ull;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      if (v[j]) {
+        sum += v[j];
+        rows[((uint64_t)r0 + (uint64_t)j * step) * THM_N_COUNTERS + k] = 0;
+      }
+    }
+  }
+  part[g][k] = sum;
+  __syncthreads();
+  if (g == 0) {
+    unsigned long long t = 0;
+    for (int i = 0; i < REDUCE_GROUPS; i++) t += part[i][k];
+    if (t) atomicAdd(&counters[k], t);
+  }
+}
+
 }  // namespace dev
 
 hipError_t launch_calib_gather(const uint8_t* table, uint64_t span, uint64_t n_threads, int pattern, unsigned long long* sink,
@@ -240,6 +280,14 @@ hipError_t launch_exclusive_scan2(const uint32_t* in_a, const uint64_t* in_b, ui
   hipLaunchKernelGGL(dev::scan2_tiles_kernel, dim3((unsigned)tiles), dim3(dev::SCAN_THREADS), 0, s, in_a, in_b, out_a, out_b, n, tmp);
   hipLaunchKernelGGL(dev::scan2_sums_kernel, dim3(2), dim3(dev::SCAN_THREADS), 0, s, tmp, tiles, out_a + n, out_b + n);
   hipLaunchKernelGGL(dev::scan2_add_kernel, dim3((unsigned)tiles), dim3(dev::SCAN_THREADS), 0, s, out_a, out_b, n, tmp);
+  return hipGetLastError();
+}
+
+hipError_t launch_counters_reduce(unsigned long long* wave_counters, uint32_t n_rows, unsigned long long* counters, hipStream_t s) {
+  if (n_rows == 0) return hipSuccess;
+  const unsigned blocks = std::min<unsigned>((n_rows + dev::REDUCE_GROUPS - 1) / dev::REDUCE_GROUPS, dev::REDUCE_MAX_BLOCKS);
+  hipLaunchKernelGGL(dev::counters_reduce_kernel, dim3(blocks), dim3(dev::REDUCE_GROUPS * THM_N_COUNTERS), 0, s, wave_counters, n_rows,
+                     counters);
   return hipGetLastError();
 }
 

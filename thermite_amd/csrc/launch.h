@@ -13,6 +13,25 @@
 
 namespace thm {
 
+// Launch `kern` with `lds` bytes of dynamic LDS; a kernel has to be allowed more than 48 KB before it is launched with it.
+template <class K, class P>
+hipError_t launch_with_lds(K kern, unsigned n_blocks, unsigned threads, size_t lds, hipStream_t s, const P& p) {
+  if (lds > 48 * 1024) {
+    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(threads), lds, s, p);
+  return hipGetLastError();
+}
+
+// Fault bits of the extend stage and of thm_align_seed_hits_batch, set on the device and read on the host.
+// FAULT_OPS_POOL / FAULT_INTERNAL go to the batch's fault word; FAULT_CONTRACT (a condition that panics in the
+// reference), FAULT_RETRY (more introns in one alignment than the fast kernel's marker list holds) and FAULT_BAND are per read
+// FAULT_BAND (per read): the read's band does not fit this launch's class (cannot happen while the band is monotone in the
+// read length, which is how the classes are cut; the reference's own check, assert!(band_width <= max_band_width) at
+// src/swg.rs:32, is per call): the read gets the status THM_ERR_INTERNAL and no alignments, the batch goes on
+enum : int { FAULT_OPS_POOL = 1, FAULT_INTERNAL = 2, FAULT_CONTRACT = 4, FAULT_RETRY = 8, FAULT_BAND = 16 };
+
 struct SwgBatchParams {
   const uint8_t* xb;
   const uint64_t* xo;
@@ -536,7 +555,7 @@ struct CompactParams {
   uint8_t* ops;
   const int* fault;  // [0] seed stage, [1] extend stage: a faulted attempt is replayed by the host, nothing is compacted
   uint64_t alns_cap, ops_cap;  // entries in alns[], bytes in ops[]
-  // reads with many alignments (kernels_extend.hip, "final layout"): [0] reads listed, [1] descriptors written (zero
+  // reads with many alignments (kernels_compact.hip, "final layout"): [0] reads listed, [1] descriptors written (zero
   // when the launch starts); heavy_list / heavy_desc hold heavy_cap entries each; rel one word per alignment
   unsigned long long* heavy_cnt;
   uint64_t* heavy_list;

@@ -1,7 +1,7 @@
 // seed_hits.hip -- host side of thm_align_seed_hits_batch (include/thermite.h): align_seed_hit
 // (reference src/aligner.rs:198-314) for hits the caller chooses.  The checks that decide a hit's status on the host,
 // the band classes (as classify() in extend_plan.h cuts them for reads), the launches of seed_hit_kernel
-// (kernels_extend.hip) and the canonical layout of the result.
+// (kernels_seed_hit.hip) and the canonical layout of the result.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -13,8 +13,6 @@
 using namespace thm;
 
 namespace {
-
-constexpr int FAULT_OPS_POOL = 1, FAULT_INTERNAL = 2;  // kernels_extend.hip
 
 struct Launch {
   int cpl;                 // 1..4, or 0: any width

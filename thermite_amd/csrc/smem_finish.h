@@ -174,7 +174,7 @@ FIN_HD uint32_t tx_window_bytes(const ExonEntryT<C>& e, C hr, int len, int L, in
 }
 
 // rank of a grid entry in IntervalTree::find's yield order if it overlaps [qs, qe) and is the copy of its interval that
-// counts for a query whose first bin is b0, else -1 (kernels_extend.hip, grid_entry_rank)
+// counts for a query whose first bin is b0, else -1 (extend_device.h, grid_entry_rank)
 template <class C>
 FIN_HD int grid_rank(C start, C end, uint32_t rank, C qs, C qe, uint32_t b0) {
   const bool overlap = qs < end && start < qe;
