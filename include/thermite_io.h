@@ -163,8 +163,8 @@ int32_t thm_align_batch_bgzf(thm_aligner* a, const thm_read_batch* reads, uint32
  *     rank = refID >= 0 ? refID : n_sq                              (unmapped last)
  *     key  = rank << 33 | (uint32)(pos + 1) << 1 | (flag >> 4 & 1)  (position, then forward before reverse)
  * Records are ordered by key; records with equal keys keep the order in which they were added (add order, then record
- * order within the batch).  Not done: spilling to the host when the records exceed device memory, merging across
- * devices, an index file (raw_offset and block_off give the virtual offsets one needs), name order. */
+ * order within the batch).  The .bai of the sorted file is built on the device too (thm_bam_sorter_index below).  Not done:
+ * spilling to the host when the records exceed device memory, merging across devices, name order. */
 typedef struct thm_bam_sorter thm_bam_sorter;
 
 typedef struct thm_bam_sort_info {      /* what one add did, and the totals so far */
@@ -206,6 +206,44 @@ int32_t thm_bam_sorter_finish(thm_bam_sorter* s, float* sort_ms);
  * two gather kernels (same bytes). */
 int32_t thm_bam_sorter_next(thm_bam_sorter* s, uint64_t max_raw_bytes, uint32_t flags, thm_bam_sorted_view* out);
 void thm_bam_sorter_free(thm_bam_sorter* s);
+
+/* The .bai index (SAM specification section 5.2; UCSC binning of section 5.3: min_shift 14, 5 levels, pseudo-bin 37450)
+ * of the file thm_writer_header_sorted + all members + thm_writer_trailer, built on the device from the sorted records.
+ * These rules are the contract:
+ *   Virtual offsets.  F = first_member_offset, the file offset of the first record member (the length of what was written
+ *     before it).  coff[m] = F + the compressed sizes of members 0 .. m-1; coff[n_members] is where the trailer goes.  For
+ *     a stream offset s:  v(s) = coff[s / 0xff00] << 16 | s % 0xff00.  A record's vbeg is v of its first byte, its vend v
+ *     of the offset just past it (for the last record v(total), which points at the trailer member, offset 0, when total
+ *     is a multiple of 0xff00).
+ *   Per record, from refID, pos, flag, n_cigar_op and the CIGAR words of the record (its bin field is not trusted):
+ *     refID < 0: the record counts in n_no_coor and nothing else.  Otherwise beg = max(pos, 0); end = beg + the summed
+ *     lengths of its M, D, N, = and X ops, or beg + 1 where that sum is 0 (also with no CIGAR); bin = reg2bin(beg, end);
+ *     mapped = !(flag & 4).  A record with refID >= 0 and end > 2^29 makes the call fail with THM_ERR_INVALID_ARG (the
+ *     message names its reference and position): BAI cannot address it, and CSI is not written.
+ *   Chunks of a bin.  In stream order, a maximal run of consecutive records with one (refID, bin) is a chunk [vbeg of its
+ *     first, vend of its last).  Within a bin, in stream order, a chunk is merged into its predecessor when
+ *     pred.end >> 16 >= chunk.beg >> 16 (the predecessor's end becomes the chunk's end).  Nothing else is merged or
+ *     folded into parent bins.
+ *   Per reference, in @SQ order: the bins in ascending bin number, each with its chunks in stream order; then, exactly when
+ *     the reference has records, the pseudo-bin 37450 with two chunks, (vbeg of the reference's first record, vend of its
+ *     last) and (n_mapped, n_unmapped); it counts in n_bin.  A reference without records has n_bin = 0, n_intv = 0.
+ *   Linear index, from mapped records only: n_intv = 1 + max((end - 1) >> 14); ioffset[w] = the smallest vbeg of a mapped
+ *     record with beg >> 14 <= w <= (end - 1) >> 14; a window no record overlaps takes the value of the next window above
+ *     it that has one (the last window always has one).
+ *   Tail: n_no_coor (uint64), always.  An empty sorter gives "BAI\1", n_ref, n_ref x (0, 0), 0. */
+typedef struct thm_bai_view {
+  uint64_t n_bytes; const uint8_t* data;        /* the finished .bai file */
+  uint64_t n_refs, n_bins, n_chunks, n_intervals, n_no_coor;   /* n_bins includes the pseudo-bins; n_chunks: of the other bins */
+  float index_ms;                               /* device events, all index kernels */
+} thm_bai_view;
+/* Valid once thm_bam_sorter_next has returned the exhausted view (n_raw_bytes == 0; an empty sorter is exhausted as soon
+ * as it is finished) and every window was taken as BGZF: the sorter keeps every member's compressed size (8 bytes a
+ * member, host memory) as it hands the windows out.  THM_ERR_INVALID_ARG with a message: before finish, before the stream
+ * is exhausted, after any THM_SORT_RAW window (there are no member sizes then), a record beyond 2^29.  The call may be
+ * repeated, also with another first_member_offset: the result depends on the records and that offset only.  The view
+ * has a pinned buffer of its own and stays valid until the next index call or the free; no other view, timing or counter
+ * changes.  With THM_BAM_SORT=1 and THM_BAM_INDEX=1 thm_align_files writes it to <output_path>.bai. */
+int32_t thm_bam_sorter_index(thm_bam_sorter* s, uint64_t first_member_offset, thm_bai_view* out);
 
 /* ------------------------------------------------- FASTQ blocks parsed on the device */
 
@@ -416,7 +454,11 @@ typedef struct thm_run_stats {
  * the records of the unset run in the order of thm_bam_sorter; the members are the device encoder's.  n_output_bytes
  * counts the file's bytes; the drain's time goes into format_s (sort, gather, deflate, copy) and write_s.  One aligner
  * only: with more, THM_ERR_INVALID_ARG (merging across devices is not done).  Records beyond the device's memory:
- * THM_ERR_OOM from the add that meets it. */
+ * THM_ERR_OOM from the add that meets it.
+ * THM_BAM_INDEX=1 beside THM_BAM_SORT=1: after the end-of-file block, <output_path>.bai is written whole
+ * (thm_bam_sorter_index with the length of the sorted header); a failure to write it is THM_ERR_IO with the path.
+ * n_output_bytes still counts the BAM only.  THM_FMT_BAM with THM_BAM_INDEX=1 but without THM_BAM_SORT=1, or to standard
+ * output, is refused with THM_ERR_INVALID_ARG: only a sorted file has this index.  Ignored for the other formats. */
 int32_t thm_align_files(thm_aligner* a, const char* const* fastq_paths, uint32_t n_paths, const char* output_path,
                         int32_t format, uint64_t batch_reads, uint32_t n_threads, thm_run_stats* stats);
 /* The same over several aligners -- one per GPU of the node, all over one index (the shape of ThermiteAligner: Clone +

@@ -160,6 +160,13 @@ class BamSortedView(C.Structure):
 SORT_RAW = 1
 
 
+class BaiView(C.Structure):
+    """thm_bai_view (include/thermite_io.h)"""
+
+    _fields_ = [("n_bytes", C.c_uint64), ("data", C.c_void_p), ("n_refs", C.c_uint64), ("n_bins", C.c_uint64), ("n_chunks", C.c_uint64),
+                ("n_intervals", C.c_uint64), ("n_no_coor", C.c_uint64), ("index_ms", C.c_float)]
+
+
 class FastqUploadInfo(C.Structure):
     """thm_fastq_upload_info (include/thermite_io.h)"""
 
@@ -231,6 +238,7 @@ IO_ABI_SYMBOLS = [
     "thm_batch_upload_fastq_gzip",
     "thm_bam_sorter_create", "thm_bam_sorter_add", "thm_bam_sorter_finish", "thm_bam_sorter_next", "thm_bam_sorter_free",
     "thm_writer_header_sorted",
+    "thm_bam_sorter_index",
 ]
 ERR_IO, ERR_FORMAT = -8, -9
 FMT_PAF, FMT_SAM, FMT_BAM = 0, 1, 2
@@ -412,6 +420,8 @@ def lib():
     L.thm_bam_sorter_next.argtypes = [vp, u64, u32, vp]
     L.thm_bam_sorter_free.restype = None
     L.thm_bam_sorter_free.argtypes = [vp]
+    L.thm_bam_sorter_index.restype = i32
+    L.thm_bam_sorter_index.argtypes = [vp, u64, vp]
     L.thm_debug_bam_sorter_add_records.restype = i32
     L.thm_debug_bam_sorter_add_records.argtypes = [vp, vp, u64]
     L.thm_debug_bam_sorter_gather.restype = i32
@@ -828,6 +838,13 @@ class BamSorter:
             if w.n_raw_bytes == 0:
                 return
             yield w
+
+    def index(self, first_member_offset):
+        """thm_bam_sorter_index, once the windows are exhausted -> (the .bai file's bytes, the view's counts and index_ms)"""
+        v = BaiView()
+        self.aligner._chk(lib().thm_bam_sorter_index(self.h, first_member_offset, C.byref(v)))
+        info = {k: getattr(v, k) for k, _ in BaiView._fields_ if k != "data"}
+        return _copy(v.data, v.n_bytes, np.uint8).tobytes(), info
 
     def close(self):
         if getattr(self, "h", None):

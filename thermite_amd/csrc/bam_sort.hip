@@ -8,10 +8,10 @@
 
 #include <cstdlib>
 #include <cstring>
-#include <deque>
 
 #include "aligner_internal.h"
 #include "bam_sort_device.h"
+#include "bam_sort_internal.h"
 #include "bgzf_device.h"
 #include "io_internal.h"
 
@@ -19,43 +19,12 @@ using namespace thm;
 
 namespace {
 
-// one allocation of the arena, exactly as large as asked for (a DBuf rounds up by a quarter)
-struct Segment {
-  void* p = nullptr;
-  Segment() = default;
-  Segment(const Segment&) = delete;
-  Segment& operator=(const Segment&) = delete;
-  ~Segment() {
-    if (p) (void)hipFree(p);
-  }
-};
+using Segment = SortSegment;
 
 constexpr uint64_t DEFAULT_WINDOW_BLOCKS = 256;  // 16.7 MB of records a window
 constexpr uint64_t MAX_RECORDS = 0xFFFFFFFFull;
 
 }  // namespace
-
-struct thm_bam_sorter {
-  thm_aligner* a = nullptr;
-  uint64_t max_bytes = 0;
-  uint32_t n_sq = 0;
-  // the arena: one segment per add, a record's place a global offset (seg_start[s] + its offset in segment s)
-  std::deque<Segment> segs;
-  std::vector<uint64_t> seg_start;
-  // per record, in add order: key (u64), length (u32), place (u64); grown by doubling
-  DBuf key, len, loc;
-  uint64_t rec_cap = 0, n_rec = 0, n_bytes = 0;
-  bool finished = false;
-  bool by_records = true;  // THM_SORT_GATHER=pieces: the output-centric gather instead (DESIGN.md section 4.15 has both times)
-  // after finish: offsets of the sorted records in the sorted stream, their places, the segment table
-  DBuf s_off, s_loc, d_seg_start, d_seg_ptr;
-  uint64_t cursor = 0;
-  DBuf stage;  // the window the gather writes and the deflater reads
-  HBuf h_data[2], h_off[2], h_stat;
-  int cur = 0;
-  DBuf dbg_in, dbg_off;  // thm_debug_bam_sorter_add_records
-  Event ev[4];           // add or sort: [0], [1]; gather: [2], [3]
-};
 
 namespace {
 
@@ -199,7 +168,7 @@ int32_t thm_bam_sorter_finish(thm_bam_sorter* s, float* sort_ms) {
   if (s->finished) return fail(a, THM_ERR_INVALID_ARG, "thm_bam_sorter_finish: the sorter is finished already");
   const uint64_t n = s->n_rec;
   if (n == 0) {
-    s->finished = true;
+    s->finished = s->exhausted = true;  // (nothing to hand out: the index may follow at once)
     return THM_OK;
   }
   HIPCHK(a, hipSetDevice(a->device));
@@ -260,7 +229,10 @@ int32_t thm_bam_sorter_next(thm_bam_sorter* s, uint64_t max_raw_bytes, uint32_t 
   out->total_records = s->n_rec;
   out->total_raw_bytes = s->n_bytes;
   out->raw_offset = w0;
-  if (n == 0) return THM_OK;
+  if (n == 0) {
+    s->exhausted = true;
+    return THM_OK;
+  }
   HIPCHK(a, hipSetDevice(a->device));
   hipStream_t st = a->stream;
   HIPCHK(a, ensure_events(s->ev));
@@ -285,6 +257,7 @@ int32_t thm_bam_sorter_next(thm_bam_sorter* s, uint64_t max_raw_bytes, uint32_t 
     HIPCHK(a, hipMemcpyAsync(h_data.p, s->stage.p, n, hipMemcpyDeviceToHost, st));
     HIPCHK(a, hipStreamSynchronize(st));
     out->n_bytes = n;
+    s->raw_taken = true;
   } else {
     const float t_bgzf = a->timings[THM_T_BGZF];
     uint64_t nb = 0, n_bytes = 0;
@@ -301,6 +274,8 @@ int32_t thm_bam_sorter_next(thm_bam_sorter* s, uint64_t max_raw_bytes, uint32_t 
     out->n_blocks = nb;
     out->n_bytes = n_bytes;
     out->block_off = h_off.as<uint64_t>();
+    // the index needs every member's compressed size (8 bytes a member, 64 KiB of records each)
+    for (uint64_t b = 0; b < nb; b++) s->member_bytes.push_back(out->block_off[b + 1] - out->block_off[b]);
   }
   (void)elapsed_ms(s->ev[2], s->ev[3], &out->gather_ms);
   out->n_raw_bytes = n;

@@ -554,6 +554,7 @@ class UploadChain {
 struct Modes {
   bool bam_sort = false;      // THM_BAM_SORT=1: the records of every batch stay on the device (thm_bam_sorter_add, uploads as with
                               // THM_BAM_DEVICE=1); once the input is exhausted they are sorted there and leave window by window
+  bool bam_index = false;     // THM_BAM_INDEX=1 (asked for a BAM: valid beside THM_BAM_SORT=1 only): <output_path>.bai behind the sorted file
   bool bgzf_device = false;   // THM_BAM_DEVICE=2: ... and BGZF-compressed there too (thm_batch_fetch_bgzf): the formatting stage passes bytes on
   bool bam_device = false;    // THM_BAM_DEVICE=1: BAM records are encoded on the device (thm_batch_fetch_bam) and only deflated here
   // THM_FASTQ_DEVICE, in those modes only (the host needs no read bytes there):
@@ -570,6 +571,7 @@ struct Modes {
     Modes m;
     const bool bam = format == THM_FMT_BAM;
     m.bam_sort = bam && is("THM_BAM_SORT", "1");
+    m.bam_index = bam && is("THM_BAM_INDEX", "1");
     m.bgzf_device = !m.bam_sort && bam && is("THM_BAM_DEVICE", "2");
     m.bam_device = m.bam_sort || m.bgzf_device || (bam && is("THM_BAM_DEVICE", "1"));
     m.fastq_gzip = m.bam_device && is("THM_FASTQ_DEVICE", "3");
@@ -757,6 +759,9 @@ struct Run {
   void write_jobs();
   void release(Slot* s);
   void drain_sorted();
+  void write_index();
+  uint64_t first_member_offset = 0;  // where the sorted file's first record member stands: the sorted header's length
+  std::string index_path;            // THM_BAM_INDEX=1: <output_path>.bai
 };
 
 // groups of whole members of about batch_reads reads, by the bytes per record of the batches so far
@@ -1228,6 +1233,24 @@ void Run::format_and_write() {
   wthread.join();
   if (m.bam_sort && !sh.failed()) drain_sorted();
   if (!sh.failed() && thm_writer_trailer(ws[0], &t) == THM_OK) append(t);
+  if (m.bam_sort && m.bam_index && !sh.failed()) write_index();
+}
+
+// the .bai of the sorted file, whole, behind the file's end-of-file block
+void Run::write_index() {
+  thm_bai_view v;
+  const auto t0 = Clock::now();
+  const int rc = sh.step([&] { return (int)thm_bam_sorter_index(sorter, first_member_offset, &v); });
+  st.format_s += secs(t0, Clock::now());
+  if (rc != THM_OK) {
+    sh.set(rc, thm_last_error(aligners[0]));
+    return;
+  }
+  const auto t1 = Clock::now();
+  Output ix;
+  const bool ok = ix.open(index_path.c_str()) && ix.write_all((const char*)v.data, (size_t)v.n_bytes, 0);
+  if (!ix.close() || !ok) sh.set(THM_ERR_IO, "cannot write " + index_path);
+  st.write_s += secs(t1, Clock::now());
 }
 
 // the drain: sort, the sorted header, then window after window -- window k is written (from one of the sorter's two
@@ -1257,6 +1280,7 @@ void Run::drain_sorted() {
   st.format_s += secs(t0, Clock::now());
   if (drc != THM_OK) sh.set(drc, thm_last_error(aligners[0]));
   if (drc == THM_OK && thm_writer_header_sorted(ws[0], &t) == THM_OK) append(t);
+  first_member_offset = out.off;
   while (drc == THM_OK && !sh.failed()) {
     thm_bam_sorted_view v;
     const auto t1 = Clock::now();
@@ -1293,6 +1317,10 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
     thm::set_global_error("thm_align_files_multi: THM_BAM_SORT=1 takes one aligner (merging across devices is not done)");
     return THM_ERR_INVALID_ARG;
   }
+  if (m.bam_index && (!m.bam_sort || !strcmp(output_path, "-"))) {
+    thm::set_global_error("thm_align_files_multi: THM_BAM_INDEX=1 needs THM_BAM_SORT=1 and an output file (only a sorted file has a .bai)");
+    return THM_ERR_INVALID_ARG;
+  }
   const thm_index* ix = thm_aligner_index(aligners[0]);
   for (uint32_t i = 1; i < n_aligners; i++)
     if (thm_aligner_index(aligners[i]) != ix) {
@@ -1325,6 +1353,7 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
   if (!have_w2) w2 = nullptr;
   Run run(aligners, n_aligners, fastq_paths, n_paths, format, batch_reads, n_threads, n_parsers, m, w, w2 ? w2 : w, out, sorter);
   if (!have_w2) run.sh.set(THM_ERR_OOM, "cannot create the second writer object");
+  run.index_path = std::string(output_path) + ".bai";
   // ---- the stages: the cutter, the parsers, a thread per aligner; this thread formats
   std::thread cutter(&Run::cut, &run);
   std::vector<std::thread> parsers, gpus;

@@ -20,6 +20,7 @@
 #include <thread>
 #include <vector>
 
+#include "bai_device.h"
 #include "io_internal.h"
 #include "thermite_internal.h"
 
@@ -404,16 +405,7 @@ inline void le16(std::string& s, uint32_t v) {
   s.append(b, 2);
 }
 
-// UCSC binning scheme, SAM specification section 5.3
-inline uint32_t reg2bin(int64_t beg, int64_t end) {
-  --end;
-  if (beg >> 14 == end >> 14) return (uint32_t)(((1 << 15) - 1) / 7 + (beg >> 14));
-  if (beg >> 17 == end >> 17) return (uint32_t)(((1 << 12) - 1) / 7 + (beg >> 17));
-  if (beg >> 20 == end >> 20) return (uint32_t)(((1 << 9) - 1) / 7 + (beg >> 20));
-  if (beg >> 23 == end >> 23) return (uint32_t)(((1 << 6) - 1) / 7 + (beg >> 23));
-  if (beg >> 26 == end >> 26) return (uint32_t)(((1 << 3) - 1) / 7 + (beg >> 26));
-  return 0;
-}
+using thm::bai::reg2bin;  // UCSC binning scheme, SAM specification section 5.3 (bai_device.h)
 
 struct SeqCode {
   uint8_t t[256];

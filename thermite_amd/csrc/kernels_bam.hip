@@ -19,6 +19,7 @@
 // and tail (records beyond the slice take the byte path).  DESIGN.md section 4.9 has the two kernel times.
 #include <hip/hip_runtime.h>
 
+#include "bai_device.h"
 #include "launch.h"
 
 namespace thm {
@@ -78,16 +79,7 @@ __device__ __forceinline__ uint32_t int_tag_type(int64_t v) {
   return v >= -128 ? 'c' : (v >= -32768 ? 's' : 'i');
 }
 
-// reg2bin of io_writer.cpp (UCSC binning, SAM specification section 5.3)
-__device__ __forceinline__ uint32_t reg2bin(int64_t beg, int64_t end) {
-  --end;
-  if (beg >> 14 == end >> 14) return (uint32_t)(((1 << 15) - 1) / 7 + (beg >> 14));
-  if (beg >> 17 == end >> 17) return (uint32_t)(((1 << 12) - 1) / 7 + (beg >> 17));
-  if (beg >> 20 == end >> 20) return (uint32_t)(((1 << 9) - 1) / 7 + (beg >> 20));
-  if (beg >> 23 == end >> 23) return (uint32_t)(((1 << 6) - 1) / 7 + (beg >> 23));
-  if (beg >> 26 == end >> 26) return (uint32_t)(((1 << 3) - 1) / 7 + (beg >> 26));
-  return 0;
-}
+using bai::reg2bin;  // UCSC binning, SAM specification section 5.3 (bai_device.h: io_writer.cpp calls the same)
 
 __device__ __forceinline__ uint32_t multimapq(uint64_t n) {  // io_writer.cpp
   if (n <= 1) return 255;

@@ -718,6 +718,90 @@ hipError_t launch_bam_sort_order(const uint32_t* ord, const uint32_t* len, const
 // by_records: the record-centric shape (a wavefront per record), else the output-centric one (16 bytes a lane)
 hipError_t launch_bam_sort_gather(const BamSortGatherParams& p, bool by_records, int n_cu, hipStream_t s);
 
+// ---- BAI index of the sorted stream (kernels_bai.hip, bai_device.h; host side bai.hip) ----
+// fields (per sorted record: key = refID << 16 | bin, beg, end; per reference the mapped count and n_intv) -> run heads,
+// scan, runs (the chunks before merging, raw offsets) -> sort of (key, ordinal) -> chunk and bin heads, two scans, chunks
+// -> linear (atomic minima of raw offsets), the backward fill -> reference sizes, scan -> emit (the bytes of the file).
+// Offsets are raw offsets of the sorted stream up to the emitter, which translates them with coff[].
+struct BaiRecords {          // the sorted records: what thm_bam_sorter_finish left
+  const uint64_t* off;       // [n + 1]
+  const uint64_t* loc;       // [n]
+  uint64_t n;
+  const uint64_t* seg_start;
+  const uint8_t* const* seg;
+  uint32_t n_seg;
+  uint32_t n_sq;
+};
+struct BaiFieldsParams {
+  BaiRecords r;
+  uint64_t* key;                     // [n]
+  uint32_t* beg;                     // [n]  bai::MAPPED_BIT | beg
+  uint32_t* end;                     // [n]  (saturated; a record beyond bai::MAX_END is in err[0])
+  unsigned long long* ref_mapped;    // [n_sq] zeroed: mapped records
+  unsigned long long* ref_intv;      // [n_sq] zeroed: n_intv
+  unsigned long long* err;           // [2] all-ones: the first record with end > 2^29; the first whose CIGAR leaves it
+};
+struct BaiRunParams {
+  const uint64_t* key;   // [n]
+  const uint64_t* off;   // [n + 1]
+  uint64_t n;
+  uint32_t n_sq;
+  uint64_t* flag;        // [n]      heads: 1 where a run begins
+  const uint64_t* idx;   // [n + 1]  runs: scan of flag
+  uint64_t *ref_first, *ref_end;  // [n_sq] zeroed: the records of every reference
+  uint64_t* n_coor;      // [1] records with a reference
+  uint64_t *run_key, *run_beg, *run_end;  // [n_runs]
+};
+struct BaiChunkParams {
+  const uint64_t* skey;  // [n_runs] sorted
+  const uint32_t* ord;   // [n_runs] the run each came from
+  const uint64_t *run_beg, *run_end;
+  uint64_t n_runs;
+  uint32_t n_sq;
+  uint64_t *chunk_flag, *bin_flag;       // [n_runs]      heads
+  const uint64_t *chunk_idx, *bin_idx;   // [n_runs + 1]  chunks: their scans
+  uint64_t *chunk_beg, *chunk_end;       // [n_chunks]
+  uint32_t* chunk_bin;                   // [n_chunks] which bin (of all, in file order)
+  uint64_t* bin_key;                     // [n_bins]
+  uint64_t* bin_chunk0;                  // [n_bins + 1] first chunk of every bin
+  uint64_t *ref_bin0, *ref_bin1;         // [n_sq] zeroed: the bins of every reference
+};
+struct BaiLinearParams {
+  const uint64_t* key;
+  const uint32_t *beg, *end;
+  const uint64_t* off;
+  uint64_t n;            // the records with a reference
+  const uint64_t* intv_off;  // [n_sq + 1] scan of n_intv
+  unsigned long long* table; // [intv_off[n_sq]] all-ones
+  uint32_t n_sq;
+};
+struct BaiEmitParams {
+  uint32_t n_sq;
+  const uint64_t *ref_first, *ref_end, *ref_bin0, *ref_bin1;
+  const unsigned long long *ref_mapped, *ref_intv;
+  const uint64_t* intv_off;
+  const unsigned long long* table;
+  uint64_t* ref_size;        // [n_sq]       sizes
+  const uint64_t* ref_at;    // [n_sq + 1]   emit: scan of ref_size (bai::HEAD_BYTES to be added)
+  const uint64_t *bin_key, *bin_chunk0;
+  const uint64_t *chunk_beg, *chunk_end;
+  const uint32_t* chunk_bin;
+  uint64_t n_chunks;
+  const uint64_t* off;       // [n + 1] of the sorted records
+  const uint64_t* coff;      // [n_members + 1]
+  uint64_t n_no_coor, n_bytes;
+  uint8_t* out;              // [n_bytes], 4-byte aligned
+};
+hipError_t launch_bai_fields(const BaiFieldsParams& p, hipStream_t s);
+hipError_t launch_bai_run_heads(const BaiRunParams& p, hipStream_t s);
+hipError_t launch_bai_runs(const BaiRunParams& p, hipStream_t s);
+hipError_t launch_bai_chunk_heads(const BaiChunkParams& p, hipStream_t s);
+hipError_t launch_bai_chunks(const BaiChunkParams& p, hipStream_t s);
+hipError_t launch_bai_linear(const BaiLinearParams& p, hipStream_t s);
+hipError_t launch_bai_fill(const BaiLinearParams& p, hipStream_t s);
+hipError_t launch_bai_ref_sizes(const BaiEmitParams& p, hipStream_t s);
+hipError_t launch_bai_emit(const BaiEmitParams& p, hipStream_t s);
+
 // ---- FASTQ blocks parsed on the device (kernels_fastq.hip, fastq_device.h; host side fastq.hip) ----
 // count (newlines per chunk) -> scan -> starts (line_start) -> records (the parse rule: lengths, or the flag) -> two
 // scans (name_off, offsets) -> gather (names, bases, qualities to their places).

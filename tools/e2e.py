@@ -11,10 +11,11 @@ in one session; the inflated BAM streams of a pair must be identical (batch boun
 --fastq-gzip[=ROUNDS]: the `gzip -6` files as they are, one and two of them -> BAM with THM_BAM_DEVICE 1 and 2, each with
 THM_FASTQ_DEVICE 1 and 3 alternately, ROUNDS rounds (default 3) in one session; the inflated BAM streams of a pair must be
 identical (batch boundaries differ).
---bam-sort[=ROUNDS]: only plain FASTQ -> BAM with THM_FASTQ_DEVICE=1: THM_BAM_DEVICE=2 (input order) and THM_BAM_SORT=1
-(coordinate order) alternately, ROUNDS rounds (default 3) in one session; then the same reads through thm_bam_sorter by
-hand: sort_ms of thm_bam_sorter_finish and the drain with the two gather shapes alternating window by window (gather_ms,
-deflate_ms per window).  The gzip files are not made.
+--bam-sort[=ROUNDS]: only plain FASTQ -> BAM with THM_FASTQ_DEVICE=1: THM_BAM_DEVICE=2 (input order), THM_BAM_SORT=1
+(coordinate order) and THM_BAM_SORT=1 with THM_BAM_INDEX=1 (the .bai too; its size is reported) alternately, ROUNDS rounds
+(default 3) in one session; then the same reads through thm_bam_sorter by hand: sort_ms of thm_bam_sorter_finish, the drain
+with the two gather shapes alternating window by window (gather_ms, deflate_ms per window) and index_ms of
+thm_bam_sorter_index, three calls.  The gzip files are not made.
 --sha[=PART]: with any of the modes above, "sha256 <hash> <file> <bytes>" for every output file before it is removed (two
 builds of the library -- THM_LIB selects one -- are compared by these lines); with PART also, after every run that wrote a
 file whose name holds PART, "each <file> raw <hash> inflated <hash> size <bytes> batches <n>": does an output repeat from
@@ -105,15 +106,21 @@ if SORT_ROUNDS:
     os.environ["THM_BAM_DEVICE"] = "2"
     st = capi.align_files(a, [big], "/tmp/thm_e2e_out.bam", capi.FMT_BAM, batch_reads=250000, n_threads=threads)   # warm-up: buffers grow
     for k in range(SORT_ROUNDS):
-        for tag, env in (("input order, THM_BAM_DEVICE=2", {"THM_BAM_DEVICE": "2"}), ("sorted,      THM_BAM_SORT=1  ", {"THM_BAM_SORT": "1"})):
-            os.environ.pop("THM_BAM_DEVICE", None)
-            os.environ.pop("THM_BAM_SORT", None)
+        for tag, env in (("input order, THM_BAM_DEVICE=2", {"THM_BAM_DEVICE": "2"}), ("sorted,      THM_BAM_SORT=1  ", {"THM_BAM_SORT": "1"}),
+                         ("sorted + .bai, THM_BAM_INDEX=1", {"THM_BAM_SORT": "1", "THM_BAM_INDEX": "1"})):
+            for name in ("THM_BAM_DEVICE", "THM_BAM_SORT", "THM_BAM_INDEX"):
+                os.environ.pop(name, None)
             os.environ.update(env)
             st = capi.align_files(a, [big], "/tmp/thm_e2e_out.bam", capi.FMT_BAM, batch_reads=250000, n_threads=threads)
-            print("bam %s round %d: %.2f Mreads/s wall %.2fs | parse %.2fs gpu %.2fs format %.2fs write %.2fs | %d records, %.0f MB out" % (
+            bai = ""
+            if "THM_BAM_INDEX" in env:
+                bai = ", .bai %.2f MB" % (os.path.getsize("/tmp/thm_e2e_out.bam.bai") / 1e6)
+                os.remove("/tmp/thm_e2e_out.bam.bai")
+            print("bam %s round %d: %.2f Mreads/s wall %.2fs | parse %.2fs gpu %.2fs format %.2fs write %.2fs | %d records, %.0f MB out%s" % (
                 tag, k, st["n_reads"] / st["wall_s"] / 1e6, st["wall_s"], st["parse_s"], st["gpu_s"], st["format_s"], st["write_s"],
-                st["n_records"], st["n_output_bytes"] / 1e6), flush=True)
+                st["n_records"], st["n_output_bytes"] / 1e6, bai), flush=True)
     os.environ.pop("THM_BAM_SORT", None)
+    os.environ.pop("THM_BAM_INDEX", None)
     # the sorter by hand: add every batch, sort, drain with the gather shapes alternating
     W = 256 * 0xff00
     for rnd in range(2):
@@ -151,6 +158,9 @@ if SORT_ROUNDS:
             print("  gather[%-7s] %d windows of %d bytes: median %.3f ms (min %.3f max %.3f) = %.2f TB/s read+written" % (
                 shape, len(ms), W, float(np.median(ms)), min(ms), max(ms), 2 * W / (float(np.median(ms)) * 1e-3) / 1e12), flush=True)
         print("  deflate per window: median %.3f ms (min %.3f max %.3f)" % (float(np.median(defl)), min(defl), max(defl)), flush=True)
+        ims = [srt.index(1000) for _ in range(3)]
+        print("  index: %d bytes, %d bins, %d chunks, %d windows: index_ms %s (sort_ms %.2f)" % (
+            len(ims[0][0]), ims[0][1]["n_bins"], ims[0][1]["n_chunks"], ims[0][1]["n_intervals"], " ".join("%.2f" % x[1]["index_ms"] for x in ims), sort_ms), flush=True)
         srt.close()
     a.close()
     drop("/tmp/thm_e2e_out.bam")

@@ -11,7 +11,8 @@ bytes, THM_T_BGZF -- beside thm_batch_fetch_bam plus thm_writer_wrap_bam of the 
 the compressed sizes of the device encoder, the host encoder and zlib level 1 over the device's cuts.
 --bam-sort: on the resident batch, thm_bam_sorter_add (the records stay on the device) against thm_batch_fetch_bam (they
 cross to the host), alternately in one session -- milliseconds of the calls and add_ms (key kernel + copy) -- then
-thm_bam_sorter_finish over everything added (sort_ms) and the drain with the two gather shapes alternating window by window.
+thm_bam_sorter_finish over everything added (sort_ms), the drain with the two gather shapes alternating window by window and
+thm_bam_sorter_index over the drained stream (index_ms).
 --fastq: the batch written out as one FASTQ block: thm_batch_upload_fastq -- milliseconds of the call and of its parse
 kernels (device_ms) -- beside thm_batch_upload_reads of the parsed batch, and the host's parse of the block on one thread.
 --fastq-bgzf: the same block BGZF-framed with Python's zlib (level 6, members of 0xff00 bytes): thm_batch_upload_fastq_bgzf
@@ -164,6 +165,12 @@ for name, opts in (("ci", capi.CI_OPTS), ("default", capi.DEFAULT_OPTS)):
                 shape, len(ms), 256 * 0xff00, float(np.median(ms)), min(ms), max(ms), 2 * 256 * 0xff00 / (float(np.median(ms)) * 1e-3) / 1e12), flush=True)
         print("         deflate per window median %.3f ms (min %.3f max %.3f); drain of %d windows %.2f s = %.2f GB/s of records" % (
             float(np.median(defl)), min(defl), max(defl), k, wall, info["total_bytes"] / wall / 1e9), flush=True)
+        ims, iw = [], []
+        for _ in range(5):   # thm_bam_sorter_index over the drained stream, repeated (the first call grows the pinned result)
+            t0 = time.perf_counter(); bai, binfo = srt.index(1000); iw.append((time.perf_counter() - t0) * 1e3); ims.append(binfo["index_ms"])
+        print("         index: %d bytes, %d bins, %d chunks, %d windows, %d records without a reference: index_ms median %.2f (min %.2f max %.2f), "
+              "call median %.2f ms; sort_ms of this session %.2f" % (len(bai), binfo["n_bins"], binfo["n_chunks"], binfo["n_intervals"], binfo["n_no_coor"],
+                                                                      float(np.median(ims)), min(ims), max(ims), float(np.median(iw)), sort_ms), flush=True)
         srt.close()
         b.close()
     if bgzf:
