@@ -245,6 +245,90 @@ typedef struct thm_bai_view {
  * changes.  With THM_BAM_SORT=1 and THM_BAM_INDEX=1 thm_align_files writes it to <output_path>.bai. */
 int32_t thm_bam_sorter_index(thm_bam_sorter* s, uint64_t first_member_offset, thm_bai_view* out);
 
+/* ------------------------------------------------- gene and splice-junction count tables of a run, built on the device */
+
+/* What a counter reads back out of the run's SAM/BAM records -- per gene the reads (GX + RE + NH), per splice junction the
+ * reads that cross it (CIGAR N runs) -- accumulated on the device over any number of batches from what is resident there
+ * after thm_batch_run; only the finished tables cross to the host.  These rules are the contract, each phrased as what a
+ * pass over the run's SAM records would count.  For an alignment of read r, NH is the number of alignments of r
+ * (read_aln_off[r+1] - read_aln_off[r]); the alignment is unique when NH == 1 and multi when NH > 1.
+ *   Genes.  One row per gene of the index, in index order: exonic_unique, exonic_multi, intronic_unique, intronic_multi.  An
+ *     exonic alignment (RE:A:E) counts in the row of txs[tx_or_gene_idx].gene_idx, an intronic one (RE:A:N) in the row of
+ *     tx_or_gene_idx; intergenic alignments count only in the totals.  Counts are per alignment record, not per read.
+ *   Junctions.  Every N word of an alignment's genome CIGAR is one junction hit.  With p = ystart plus the lengths of all
+ *     M, D and N words before the N word: start = p (0-based first intron base), end = p + len.  ref is the BAM refID of
+ *     the alignment's contig (its @SQ index, as in thm_bam_view), strand that of the alignment's transcript (N occurs in
+ *     exonic alignments only: lift_tx_to_gx, src/txome.rs:110-160).  A hit has two anchors: left is the summed length of
+ *     the M words between the previous N word (or the CIGAR's start) and this one, right the same up to the next N word
+ *     (or the end); I, D and S words add nothing and interrupt nothing; overhang = min(left, right).  Two adjacent N
+ *     words are two hits, with anchor 0 between them.  The table has one row per distinct (ref, start, end, strand):
+ *     n_unique and n_multi (hits from unique / multi alignments) and max_overhang over all its hits.  Rows ascend by ref,
+ *     start, end, with forward before reverse.  An alignment whose digest has THM_DIGEST_LONG_RUN has no words: it
+ *     contributes no hit and counts in n_long_run_alns.
+ *   Totals.  Reads: n_reads = n_failed_reads + n_unmapped_reads + n_unique_reads + n_multi_reads; a failed read is one whose
+ *     status is not THM_OK, and is not counted as unmapped.  Alignments: n_alns = the sum of the gene table +
+ *     n_intergenic_unique + n_intergenic_multi.  n_spliced_alns: alignments with at least one hit; n_junction_hits = the
+ *     sum of n_unique + n_multi over the junction rows. */
+typedef struct thm_quant thm_quant;
+
+typedef struct thm_quant_gene {
+  uint64_t exonic_unique, exonic_multi, intronic_unique, intronic_multi;
+} thm_quant_gene; /* 32 bytes */
+
+typedef struct thm_quant_junction {
+  uint32_t ref_id;       /* BAM refID */
+  uint32_t strand;       /* 1 = forward, as thm_tx::strand */
+  uint64_t start, end;   /* 0-based, half open: the intron's first base, and the base behind its last */
+  uint64_t n_unique, n_multi;
+  uint32_t max_overhang;
+  uint32_t pad_;
+} thm_quant_junction; /* 48 bytes */
+
+typedef struct thm_quant_totals {
+  uint64_t n_reads, n_failed_reads, n_unmapped_reads, n_unique_reads, n_multi_reads;
+  uint64_t n_alns, n_intergenic_unique, n_intergenic_multi;
+  uint64_t n_spliced_alns, n_junction_hits, n_long_run_alns;
+} thm_quant_totals; /* 88 bytes */
+
+typedef struct thm_quant_info {  /* what one add did, and the table sizes so far */
+  thm_quant_totals batch;        /* this batch */
+  uint64_t n_junctions;          /* rows of the junction table */
+  uint64_t held_bytes;           /* device memory the object holds: both tables and one batch's scratch */
+  float add_ms;                  /* device events, all kernels and sorts of the add */
+} thm_quant_info;
+
+typedef struct thm_quant_view {
+  uint64_t n_genes;
+  const thm_quant_gene* genes;          /* [n_genes] */
+  uint64_t n_junctions;
+  const thm_quant_junction* junctions;  /* [n_junctions] */
+  thm_quant_totals totals;
+  float fetch_ms;                       /* device events: the row kernel and the copies */
+} thm_quant_view;
+
+/* A thm_quant belongs to one aligner, like a thm_bam_sorter: it works on that aligner's device and stream and must be
+ * freed before it.  THM_ERR_UNSUPPORTED: a contig of 2^32 bases or more (start and end are 32-bit in the sort key).
+ * THM_ERR_INVALID_ARG, with thm_batch_fetch_bam's message: an index without contig / transcript / gene names.  Device
+ * memory held is bounded by the distinct junctions, the gene table and one batch's scratch; it does not grow with the run. */
+int32_t thm_quant_create(thm_aligner* a, thm_quant** out);
+void thm_quant_free(thm_quant* q);
+/* Stands where thm_batch_fetch stands after thm_batch_run, and fails as it does before a run or after the next upload.
+ * It may precede or follow any fetch or a thm_bam_sorter_add of the same run and disturbs none of their views, no counter
+ * and no timing; it runs the CIGAR passes itself.  The batch's hits are extracted, sorted, reduced by key and merged into
+ * the running sorted table; the genes are counted last, so that a call that fails has added nothing.  Adding the same run
+ * twice counts it twice. */
+int32_t thm_quant_add(thm_quant* q, thm_quant_info* info);
+/* The same kernels over a caller-supplied view (read_aln_off, alns, digests, cigar, read_status), uploaded by the call:
+ * what thm_cigar_encode_batch is to the CIGAR layer.  The host checks the view first -- offsets that start at 0, ascend
+ * and end at n_alns; aln_type, tx_or_gene_idx and ref_id in range (a ref_id must have a BAM refID); cigar_off + n_cigar
+ * inside the pool; every position below 2^32 -- THM_ERR_INVALID_ARG with a message naming the alignment, and nothing is
+ * added. */
+int32_t thm_quant_add_view(thm_quant* q, const thm_cigar_view* v, thm_quant_info* info);
+/* A snapshot at any time.  The view has a pinned buffer of its own and stays valid until the next fetch, reset or free. */
+int32_t thm_quant_fetch(thm_quant* q, thm_quant_view* out);
+/* empties both tables and the totals */
+int32_t thm_quant_reset(thm_quant* q);
+
 /* ------------------------------------------------- FASTQ blocks parsed on the device */
 
 typedef struct thm_fastq_upload_info {
@@ -458,7 +542,15 @@ typedef struct thm_run_stats {
  * THM_BAM_INDEX=1 beside THM_BAM_SORT=1: after the end-of-file block, <output_path>.bai is written whole
  * (thm_bam_sorter_index with the length of the sorted header); a failure to write it is THM_ERR_IO with the path.
  * n_output_bytes still counts the BAM only.  THM_FMT_BAM with THM_BAM_INDEX=1 but without THM_BAM_SORT=1, or to standard
- * output, is refused with THM_ERR_INVALID_ARG: only a sorted file has this index.  Ignored for the other formats. */
+ * output, is refused with THM_ERR_INVALID_ARG: only a sorted file has this index.  Ignored for the other formats.
+ * THM_QUANT=1, in every format and mode: every aligner keeps a thm_quant and every batch is added to it after its run
+ * (thm_quant_add); the output file is the unset run's byte for byte.  At the end two files are written whole:
+ * <output_path>.genes.tsv -- the header line gene_id, gene_name, exonic_unique, exonic_multi, intronic_unique,
+ * intronic_multi, then one line per gene in index order -- and <output_path>.junctions.tsv -- the header line ref, start,
+ * end, strand, unique, multi, max_overhang, then one line per row, start and end the 1-based first and last base of the
+ * intron, strand + or -; both tab-separated.  With several aligners their tables are merged on the host by key (counts
+ * summed, overhang maximum), so the files do not depend on how the reads were dealt.  A failure to write one is THM_ERR_IO
+ * with the path; to standard output the knob is refused with THM_ERR_INVALID_ARG.  thm_run_stats is unchanged. */
 int32_t thm_align_files(thm_aligner* a, const char* const* fastq_paths, uint32_t n_paths, const char* output_path,
                         int32_t format, uint64_t batch_reads, uint32_t n_threads, thm_run_stats* stats);
 /* The same over several aligners -- one per GPU of the node, all over one index (the shape of ThermiteAligner: Clone +

@@ -167,6 +167,36 @@ class BaiView(C.Structure):
                 ("n_intervals", C.c_uint64), ("n_no_coor", C.c_uint64), ("index_ms", C.c_float)]
 
 
+QUANT_GENE_DT = np.dtype([("exonic_unique", "<u8"), ("exonic_multi", "<u8"), ("intronic_unique", "<u8"), ("intronic_multi", "<u8")])
+QUANT_JUNCTION_DT = np.dtype([("ref_id", "<u4"), ("strand", "<u4"), ("start", "<u8"), ("end", "<u8"), ("n_unique", "<u8"),
+                              ("n_multi", "<u8"), ("max_overhang", "<u4"), ("pad", "<u4")])
+assert QUANT_GENE_DT.itemsize == 32 and QUANT_JUNCTION_DT.itemsize == 48
+QUANT_TOTAL_NAMES = ["n_reads", "n_failed_reads", "n_unmapped_reads", "n_unique_reads", "n_multi_reads", "n_alns",
+                     "n_intergenic_unique", "n_intergenic_multi", "n_spliced_alns", "n_junction_hits", "n_long_run_alns"]
+
+
+class QuantTotals(C.Structure):
+    """thm_quant_totals (include/thermite_io.h)"""
+
+    _fields_ = [(k, C.c_uint64) for k in QUANT_TOTAL_NAMES]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k in QUANT_TOTAL_NAMES}
+
+
+class QuantInfo(C.Structure):
+    """thm_quant_info (include/thermite_io.h)"""
+
+    _fields_ = [("batch", QuantTotals), ("n_junctions", C.c_uint64), ("held_bytes", C.c_uint64), ("add_ms", C.c_float)]
+
+
+class QuantView(C.Structure):
+    """thm_quant_view (include/thermite_io.h)"""
+
+    _fields_ = [("n_genes", C.c_uint64), ("genes", C.c_void_p), ("n_junctions", C.c_uint64), ("junctions", C.c_void_p),
+                ("totals", QuantTotals), ("fetch_ms", C.c_float)]
+
+
 class FastqUploadInfo(C.Structure):
     """thm_fastq_upload_info (include/thermite_io.h)"""
 
@@ -239,6 +269,7 @@ IO_ABI_SYMBOLS = [
     "thm_bam_sorter_create", "thm_bam_sorter_add", "thm_bam_sorter_finish", "thm_bam_sorter_next", "thm_bam_sorter_free",
     "thm_writer_header_sorted",
     "thm_bam_sorter_index",
+    "thm_quant_create", "thm_quant_free", "thm_quant_add", "thm_quant_add_view", "thm_quant_fetch", "thm_quant_reset",
 ]
 ERR_IO, ERR_FORMAT = -8, -9
 FMT_PAF, FMT_SAM, FMT_BAM = 0, 1, 2
@@ -422,6 +453,18 @@ def lib():
     L.thm_bam_sorter_free.argtypes = [vp]
     L.thm_bam_sorter_index.restype = i32
     L.thm_bam_sorter_index.argtypes = [vp, u64, vp]
+    L.thm_quant_create.restype = i32
+    L.thm_quant_create.argtypes = [vp, vp]
+    L.thm_quant_free.restype = None
+    L.thm_quant_free.argtypes = [vp]
+    L.thm_quant_add.restype = i32
+    L.thm_quant_add.argtypes = [vp, vp]
+    L.thm_quant_add_view.restype = i32
+    L.thm_quant_add_view.argtypes = [vp, vp, vp]
+    L.thm_quant_fetch.restype = i32
+    L.thm_quant_fetch.argtypes = [vp, vp]
+    L.thm_quant_reset.restype = i32
+    L.thm_quant_reset.argtypes = [vp]
     L.thm_debug_bam_sorter_add_records.restype = i32
     L.thm_debug_bam_sorter_add_records.argtypes = [vp, vp, u64]
     L.thm_debug_bam_sorter_gather.restype = i32
@@ -849,6 +892,73 @@ class BamSorter:
     def close(self):
         if getattr(self, "h", None):
             lib().thm_bam_sorter_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+
+class QuantResult:
+    """thm_quant_view copied out: the gene table (QUANT_GENE_DT, one row per gene of the index), the junction table
+    (QUANT_JUNCTION_DT, sorted) and the totals as a dict"""
+
+    def __init__(self, view):
+        self.genes = _copy(view.genes, view.n_genes, QUANT_GENE_DT)
+        self.junctions = _copy(view.junctions, view.n_junctions, QUANT_JUNCTION_DT)
+        self.totals = view.totals.as_dict()
+        self.fetch_ms = view.fetch_ms
+
+
+class Quant:
+    """thm_quant: gene and splice-junction count tables of a run, accumulated on the aligner's device batch by batch.
+    Close it before its aligner."""
+
+    def __init__(self, aligner):
+        self.aligner = aligner
+        h = C.c_void_p()
+        rc = lib().thm_quant_create(aligner.h, C.byref(h))
+        if rc != 0:
+            raise ThermiteError(rc, (lib().thm_last_error(aligner.h) or b"").decode())
+        self.h = h
+
+    @staticmethod
+    def _info(info):
+        out = info.batch.as_dict()
+        out.update(n_junctions=int(info.n_junctions), held_bytes=int(info.held_bytes), add_ms=info.add_ms)
+        return out
+
+    def add(self):
+        """thm_quant_add, after Aligner.run -> the batch's totals, n_junctions, held_bytes and add_ms as a dict"""
+        info = QuantInfo()
+        self.aligner._chk(lib().thm_quant_add(self.h, C.byref(info)))
+        return self._info(info)
+
+    def add_view(self, offsets, alns, digests, cigar, status=None):
+        """thm_quant_add_view: the same kernels over caller-made arrays (ALN_DT, DIGEST_DT, CIGAR words)"""
+        off = np.ascontiguousarray(offsets, dtype="<u8")
+        al = np.ascontiguousarray(alns, dtype=ALN_DT)
+        dg = np.ascontiguousarray(digests, dtype=DIGEST_DT)
+        cg = np.ascontiguousarray(cigar, dtype="<u4")
+        st = np.ascontiguousarray(status, dtype="<i4") if status is not None else None
+        n_reads = max(len(off) - 1, 0)
+        v = CigarView(n_reads, len(al), len(cg), _ptr(off) if len(off) else None, _ptr(al) if len(al) else None,
+                      _ptr(dg) if len(dg) else None, _ptr(cg) if len(cg) else None,
+                      int((st != 0).sum()) if st is not None else 0, _ptr(st) if st is not None and len(st) else None)
+        info = QuantInfo()
+        self.aligner._chk(lib().thm_quant_add_view(self.h, C.byref(v), C.byref(info)))
+        return self._info(info)
+
+    def fetch(self):
+        v = QuantView()
+        self.aligner._chk(lib().thm_quant_fetch(self.h, C.byref(v)))
+        return QuantResult(v)
+
+    def reset(self):
+        self.aligner._chk(lib().thm_quant_reset(self.h))
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().thm_quant_free(self.h)
             self.h = None
 
     def __del__(self):

@@ -354,6 +354,9 @@ struct BamOnDevice {
   bool any_failed = false;  // as in BatchSizes
 };
 int bam_records_on_device(thm_aligner* a, uint32_t flags, int timing, BamOnDevice* r);
+// bam.hip: the index's name tables, tx -> gene (bt_tx_gene) and ref -> BAM refID (bt_ref_sq) on the device, once per aligner
+// (the aligner's device is current).  THM_ERR_INVALID_ARG: an index without names.  quant.hip counts from the last two.
+int bam_tables_on_device(thm_aligner* a);
 // bgzf.hip: d_in[0, n) (device, 4-byte aligned) cut every 0xff00 bytes and deflated -> the members back to back in bz_out,
 // their offsets in bz_off[0 .. *n_blocks]; synchronises the stream once and sets THM_T_BGZF (bam_sort.hip deflates the
 // windows of the sorted stream through it)

@@ -30,8 +30,10 @@ int upload_pool(thm_aligner* a, const std::vector<std::string>& v, DBuf& pool, D
   return THM_OK;
 }
 
+}  // namespace
+
 // the index's name tables, once per aligner
-int ensure_tables(thm_aligner* a) {
+int bam_tables_on_device(thm_aligner* a) {
   if (a->bam_tables) return THM_OK;
   const thm_index* ix = a->ix;
   if (ix->contig_names.empty() || ix->tx_ids.size() != ix->txs.size() || ix->gene_ids.size() != ix->genes.size() ||
@@ -54,8 +56,6 @@ int ensure_tables(thm_aligner* a) {
   a->bam_tables = true;
   return THM_OK;
 }
-
-}  // namespace
 
 extern "C" int32_t thm_batch_upload_reads(thm_aligner* a, const thm_read_batch* reads) {
   if (!a || !reads) return THM_ERR_INVALID_ARG;
@@ -90,7 +90,7 @@ int bam_records_on_device(thm_aligner* a, uint32_t flags, int timing, BamOnDevic
   int rc = thm_batch_sync(a);
   if (rc != THM_OK) return rc;
   HIPCHK(a, hipSetDevice(a->device));
-  rc = ensure_tables(a);
+  rc = bam_tables_on_device(a);
   if (rc != THM_OK) return rc;
   HIPCHK(a, ensure_events(a->ev_bam));
   if (a->bam_stage < 0) {  // THM_BAM_EMIT=bytes: the other form of the emit kernel (DESIGN.md section 4.9 has both times)

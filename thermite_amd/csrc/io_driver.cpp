@@ -37,6 +37,8 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <tuple>
+#include <utility>
 #include <vector>
 
 #include "fastq_cut.h"
@@ -563,6 +565,8 @@ struct Modes {
                               // (thm_batch_upload_fastq_bgzf); every other file takes the path of =1
   bool fastq_gzip = false;    // =3: as =2, and gzip files that are not BGZF throughout go to the device compressed too, in slices
                               // (thm_batch_upload_fastq_gzip)
+  bool quant = false;         // THM_QUANT=1, any format: every batch is added to its aligner's thm_quant behind its fetch, and
+                              // <output_path>.genes.tsv / .junctions.tsv are written at the end
   static Modes read(int32_t format) {
     auto is = [](const char* name, const char* v) {
       const char* e = getenv(name);
@@ -577,6 +581,7 @@ struct Modes {
     m.fastq_gzip = m.bam_device && is("THM_FASTQ_DEVICE", "3");
     m.fastq_bgzf = m.fastq_gzip || (m.bam_device && is("THM_FASTQ_DEVICE", "2"));
     m.fastq_device = m.fastq_bgzf || (m.bam_device && is("THM_FASTQ_DEVICE", "1"));
+    m.quant = is("THM_QUANT", "1");
     return m;
   }
 };
@@ -695,6 +700,7 @@ struct Run {
                       // batch k + 1 is formatted, so one object cannot stand in for both
   Output& out;
   thm_bam_sorter* sorter;
+  thm_quant* const* quants = nullptr;  // THM_QUANT=1: one per aligner
 
   Shared sh;
   thm_run_stats st;
@@ -1111,6 +1117,10 @@ void Run::gpu(uint32_t gi) {
       const auto t2 = Clock::now();
       if (grc == THM_OK) grc = sh.step([&] { return fetch(a, s); });
       if (grc == THM_OK && s->got.n_failed_reads) grc = fail_by_name(a, s, raw_up);
+      if (grc == THM_OK && quants) {
+        thm_quant_info qi;
+        grc = sh.step([&] { return (int)thm_quant_add(quants[gi], &qi); });
+      }
       if (grc != THM_OK) {
         sh.set(grc, thm_last_error(a));
       } else {
@@ -1301,6 +1311,62 @@ void Run::drain_sorted() {
   wr.join();
 }
 
+// THM_QUANT=1: the tables of every aligner, merged by key on the host (counts summed, overhang maximum), as
+// <output_path>.genes.tsv and <output_path>.junctions.tsv
+int write_quant_tables(const thm_index* ix, thm_aligner* const* aligners, thm_quant* const* quants, uint32_t n, const std::string& output_path,
+                       std::string& err) {
+  std::vector<thm_quant_gene> genes;
+  std::map<std::tuple<uint32_t, uint64_t, uint64_t, uint32_t>, thm_quant_junction> rows;  // (ref, start, end, reverse)
+  for (uint32_t i = 0; i < n; i++) {
+    thm_quant_view v;
+    const int rc = thm_quant_fetch(quants[i], &v);
+    if (rc != THM_OK) {
+      err = thm_last_error(aligners[i]);
+      return rc;
+    }
+    if (genes.empty()) genes.assign(v.n_genes, thm_quant_gene{0, 0, 0, 0});
+    for (uint64_t g = 0; g < v.n_genes; g++) {
+      genes[g].exonic_unique += v.genes[g].exonic_unique;
+      genes[g].exonic_multi += v.genes[g].exonic_multi;
+      genes[g].intronic_unique += v.genes[g].intronic_unique;
+      genes[g].intronic_multi += v.genes[g].intronic_multi;
+    }
+    for (uint64_t k = 0; k < v.n_junctions; k++) {
+      const thm_quant_junction& j = v.junctions[k];
+      auto at = rows.emplace(std::make_tuple(j.ref_id, j.start, j.end, j.strand ? 0u : 1u), j);
+      if (at.second) continue;
+      thm_quant_junction& have = at.first->second;
+      have.n_unique += j.n_unique;
+      have.n_multi += j.n_multi;
+      have.max_overhang = std::max(have.max_overhang, j.max_overhang);
+    }
+  }
+  std::vector<std::pair<std::string, uint64_t>> sq;
+  (void)thm::sq_of_name(ix, &sq);
+  std::string g_text = "gene_id\tgene_name\texonic_unique\texonic_multi\tintronic_unique\tintronic_multi\n";
+  for (size_t g = 0; g < genes.size(); g++) {
+    const char *id = thm_index_gene_id(ix, (uint32_t)g), *name = thm_index_gene_name(ix, (uint32_t)g);
+    g_text += std::string(id ? id : "") + "\t" + (name ? name : "") + "\t" + std::to_string(genes[g].exonic_unique) + "\t" + std::to_string(genes[g].exonic_multi) +
+              "\t" + std::to_string(genes[g].intronic_unique) + "\t" + std::to_string(genes[g].intronic_multi) + "\n";
+  }
+  std::string j_text = "ref\tstart\tend\tstrand\tunique\tmulti\tmax_overhang\n";
+  for (const auto& kv : rows) {
+    const thm_quant_junction& j = kv.second;
+    j_text += (j.ref_id < sq.size() ? sq[j.ref_id].first : std::string("*")) + "\t" + std::to_string(j.start + 1) + "\t" + std::to_string(j.end) + "\t" +
+              (j.strand ? "+" : "-") + "\t" + std::to_string(j.n_unique) + "\t" + std::to_string(j.n_multi) + "\t" + std::to_string(j.max_overhang) + "\n";
+  }
+  const std::pair<std::string, const std::string*> files[2] = {{output_path + ".genes.tsv", &g_text}, {output_path + ".junctions.tsv", &j_text}};
+  for (const auto& f : files) {
+    Output o;
+    const bool ok = o.open(f.first.c_str()) && o.write_all(f.second->data(), f.second->size(), 0);
+    if (!o.close() || !ok) {
+      err = "cannot write " + f.first;
+      return THM_ERR_IO;
+    }
+  }
+  return THM_OK;
+}
+
 }  // namespace
 
 extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t n_aligners, const char* const* fastq_paths,
@@ -1319,6 +1385,10 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
   }
   if (m.bam_index && (!m.bam_sort || !strcmp(output_path, "-"))) {
     thm::set_global_error("thm_align_files_multi: THM_BAM_INDEX=1 needs THM_BAM_SORT=1 and an output file (only a sorted file has a .bai)");
+    return THM_ERR_INVALID_ARG;
+  }
+  if (m.quant && !strcmp(output_path, "-")) {
+    thm::set_global_error("thm_align_files_multi: THM_QUANT=1 needs an output file (the tables are written beside it)");
     return THM_ERR_INVALID_ARG;
   }
   const thm_index* ix = thm_aligner_index(aligners[0]);
@@ -1347,6 +1417,16 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
     thm_writer_free(w);
     return rc;
   }
+  std::vector<thm_quant*> quants(m.quant ? n_aligners : 0, nullptr);
+  for (size_t i = 0; i < quants.size(); i++)
+    if ((rc = thm_quant_create(aligners[i], &quants[i])) != THM_OK) {
+      thm::set_global_error(thm_last_error(aligners[i]));
+      for (thm_quant* q : quants) thm_quant_free(q);
+      thm_bam_sorter_free(sorter);
+      (void)out.close();
+      thm_writer_free(w);
+      return rc;
+    }
   const auto t_start = Clock::now();
   thm_writer* w2 = nullptr;
   const bool have_w2 = thm_writer_create(ix, format, n_threads, &w2) == THM_OK;
@@ -1354,6 +1434,7 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
   Run run(aligners, n_aligners, fastq_paths, n_paths, format, batch_reads, n_threads, n_parsers, m, w, w2 ? w2 : w, out, sorter);
   if (!have_w2) run.sh.set(THM_ERR_OOM, "cannot create the second writer object");
   run.index_path = std::string(output_path) + ".bai";
+  if (m.quant) run.quants = quants.data();
   // ---- the stages: the cutter, the parsers, a thread per aligner; this thread formats
   std::thread cutter(&Run::cut, &run);
   std::vector<std::thread> parsers, gpus;
@@ -1367,6 +1448,12 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
   // with the run, behind the clock)
   run.maps.clear();
   if (w2) thm_writer_free(w2);
+  if (m.quant && run.sh.rc == THM_OK) {
+    std::string err;
+    const int qrc = run.sh.step([&] { return write_quant_tables(ix, aligners, quants.data(), n_aligners, output_path, err); });
+    if (qrc != THM_OK) run.sh.set(qrc, err);
+  }
+  for (thm_quant* q : quants) thm_quant_free(q);
   thm_bam_sorter_free(sorter);
   if (!out.close()) run.sh.set(THM_ERR_IO, std::string("error closing ") + output_path);
   thm_writer_free(w);

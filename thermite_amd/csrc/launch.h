@@ -8,6 +8,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "../../include/thermite_io.h"
 #include "extend_plan.h"
 #include "thermite_internal.h"
 
@@ -717,6 +718,76 @@ hipError_t launch_bam_sort_order(const uint32_t* ord, const uint32_t* len, const
                                  uint64_t* s_loc, hipStream_t s);
 // by_records: the record-centric shape (a wavefront per record), else the output-centric one (16 bytes a lane)
 hipError_t launch_bam_sort_gather(const BamSortGatherParams& p, bool by_records, int n_cu, hipStream_t s);
+
+// ---- gene and junction count tables of a run (kernels_quant.hip, quant_device.h; host side quant.hip) ----
+// count (per alignment: checks, its hits; per read: the read totals) -> scan -> extract (a row per hit) -> sort by the
+// 128-bit key as two stable 64-bit passes over a permutation -> heads, scan, reduce (by key: sums and the maximum) ->
+// lookup of the reduced rows in the running table, scan of the new ones -> update (found rows in place, new rows behind
+// the table's) -> the same sort over table + new rows -> genes (last, so that a refused batch has added nothing).
+struct QuantBatch {
+  uint64_t n_reads, n_alns, n_words;
+  const uint64_t* aln_off;        // [n_reads + 1]
+  const thm_aln* alns;            // [n_alns]
+  const thm_aln_digest* digests;  // [n_alns]
+  const uint32_t* words;          // [n_words]
+  const int32_t* status;          // [n_reads]; null: no read failed
+  uint32_t n_refs, n_txs, n_genes;
+  const uint32_t* tx_gene;        // [n_txs]
+  const uint8_t* tx_forward;      // [n_txs] thm_tx::strand
+  const int32_t* ref_sq;          // [n_refs] BAM refID, -1: none
+};
+// junction rows, one array per field: before the reduce a row is one hit (n_unique + n_multi == 1)
+struct QuantRows {
+  uint64_t *hi, *lo;  // the key (quant_device.h)
+  uint64_t *n_unique, *n_multi;
+  uint32_t* overhang;
+};
+struct QuantCountParams {
+  QuantBatch b;
+  uint64_t* hit_cnt;           // [n_alns + 1] hits of every alignment, for the scan
+  uint8_t* multi;              // [n_alns] NH > 1
+  unsigned long long* totals;  // [quant::N_TOTALS] zeroed by the caller
+  unsigned long long* bad;     // the first alignment with an index out of range (atomic minimum; ~0: none)
+};
+struct QuantExtractParams {
+  QuantBatch b;
+  const uint64_t* hit_off;  // [n_alns + 1]
+  const uint8_t* multi;
+  QuantRows out;            // [hit_off[n_alns]]
+};
+struct QuantGenesParams {
+  QuantBatch b;
+  const uint8_t* multi;
+  unsigned long long* genes;  // [n_genes * 4] the running table
+};
+struct QuantReduceParams {
+  QuantRows in;          // [n] unsorted
+  const uint32_t* perm;  // [n] sorted position -> row of `in`
+  const uint64_t* s_hi;  // [n] the sorted high key words
+  uint64_t n;
+  uint64_t* flag;        // [n + 1] 1 where a key begins (heads kernel), and its exclusive scan
+  const uint64_t* first;  // [n + 1]
+  QuantRows out;         // [first[n]] sums and maxima zeroed by the caller
+};
+struct QuantMergeParams {
+  QuantRows tab;   // [n_tab] the running table, sorted
+  uint64_t n_tab;
+  QuantRows red;   // [n_red] the batch's reduced rows
+  uint64_t n_red;
+  uint32_t* where;       // [n_red] row of `tab` with the same key, or 0xFFFFFFFF
+  uint64_t* is_new;      // [n_red + 1] for the scan
+  const uint64_t* new_at;  // [n_red + 1] its scan
+  QuantRows cat;   // new rows go to cat[n_tab + new_at[j]]
+};
+hipError_t launch_quant_count(const QuantCountParams& p, int n_cu, hipStream_t s);
+hipError_t launch_quant_extract(const QuantExtractParams& p, hipStream_t s);
+hipError_t launch_quant_genes(const QuantGenesParams& p, int n_cu, hipStream_t s);
+hipError_t launch_quant_gather(const uint64_t* in, const uint32_t* perm, uint64_t n, uint64_t* out, hipStream_t s);
+hipError_t launch_quant_heads(const QuantReduceParams& p, hipStream_t s);
+hipError_t launch_quant_reduce(const QuantReduceParams& p, hipStream_t s);
+hipError_t launch_quant_lookup(const QuantMergeParams& p, hipStream_t s);
+hipError_t launch_quant_update(const QuantMergeParams& p, hipStream_t s);
+hipError_t launch_quant_rows(const QuantRows& in, uint64_t n, thm_quant_junction* out, hipStream_t s);
 
 // ---- BAI index of the sorted stream (kernels_bai.hip, bai_device.h; host side bai.hip) ----
 // fields (per sorted record: key = refID << 16 | bin, beg, end; per reference the mapped count and n_intv) -> run heads,

@@ -1,0 +1,432 @@
+// quant.hip -- host side of thm_quant (include/thermite_io.h): the gene and junction count tables of a run, accumulated on
+// the device over its batches from what is resident after thm_batch_run -- the compacted thm_aln records, the per-read
+// offsets, the CIGAR words and digests of the CIGAR passes, and the tx -> gene and ref -> @SQ tables of the BAM encoder.
+// Only totals and the finished tables come back to the host.  The kernels are kernels_quant.hip, the per-alignment
+// functions quant_device.h; DESIGN.md section 4.17.
+#include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
+
+#include <cstring>
+
+#include "aligner_internal.h"
+#include "quant_device.h"
+
+using namespace thm;
+
+namespace {
+
+constexpr uint64_t MAX_ROWS = 0xFFFFFFFEull;  // a permutation entry is 32 bits, 0xFFFFFFFF the "not found" of the lookup
+
+// junction rows on the device, an array per field
+struct RowBuf {
+  DBuf hi, lo, nu, nm, ov;
+  hipError_t ensure(uint64_t n) {
+    hipError_t e = hi.ensure(n * 8);
+    if (e == hipSuccess) e = lo.ensure(n * 8);
+    if (e == hipSuccess) e = nu.ensure(n * 8);
+    if (e == hipSuccess) e = nm.ensure(n * 8);
+    if (e == hipSuccess) e = ov.ensure(n * 4);
+    return e;
+  }
+  QuantRows rows() const { return QuantRows{hi.as<uint64_t>(), lo.as<uint64_t>(), nu.as<uint64_t>(), nm.as<uint64_t>(), ov.as<uint32_t>()}; }
+  size_t bytes() const { return hi.cap + lo.cap + nu.cap + nm.cap + ov.cap; }
+};
+
+}  // namespace
+
+struct thm_quant {
+  thm_aligner* a = nullptr;
+  uint32_t n_sq = 0;
+  std::vector<int32_t> h_ref_sq;  // what bt_ref_sq holds, for the checks of thm_quant_add_view
+  DBuf tx_forward;                // [n_txs] thm_tx::strand
+  DBuf genes;                     // [n_genes * 4] u64, the running gene table
+  RowBuf tab[2];                  // the running junction table, sorted, in tab[cur]; the other takes the next merge
+  int cur = 0;
+  uint64_t n_tab = 0;
+  thm_quant_totals totals;
+  // one batch's scratch
+  RowBuf hits, red, cat;
+  DBuf hit_cnt, hit_off, multi, scan_tmp, d_tot, perm_a, perm_b, key_a, key_b, cub_tmp, flag, first, where, is_new, new_at;
+  DBuf v_off, v_alns, v_dig, v_words, v_stat;  // the view thm_quant_add_view uploads
+  DBuf d_rows;                                 // the table as records, for the fetch
+  HBuf h_out;
+  Event ev[2], ev_fetch[2];
+
+  uint64_t held_bytes() const {
+    size_t n = tx_forward.cap + genes.cap + tab[0].bytes() + tab[1].bytes() + hits.bytes() + red.bytes() + cat.bytes() + d_rows.cap;
+    for (const DBuf* b : {&hit_cnt, &hit_off, &multi, &scan_tmp, &d_tot, &perm_a, &perm_b, &key_a, &key_b, &cub_tmp, &flag, &first, &where,
+                          &is_new, &new_at, &v_off, &v_alns, &v_dig, &v_words, &v_stat})
+      n += b->cap;
+    return n;
+  }
+};
+
+namespace {
+
+// `in` (n rows, any order) sorted by key and reduced by key into `out` -> *m rows.  The 128-bit key is sorted as two
+// stable 64-bit passes over a permutation, low word first.  Synchronises the stream once: `out` is sized by the count.
+int sort_reduce(thm_quant* q, const QuantRows& in, uint64_t n, RowBuf& out, uint64_t* m) {
+  thm_aligner* a = q->a;
+  hipStream_t st = a->stream;
+  *m = 0;
+  if (n == 0) return THM_OK;
+  HIPCHK(a, q->perm_a.ensure(n * 4));
+  HIPCHK(a, q->perm_b.ensure(n * 4));
+  HIPCHK(a, q->key_a.ensure(n * 8));
+  HIPCHK(a, q->key_b.ensure(n * 8));
+  HIPCHK(a, q->flag.ensure((n + 1) * 8));
+  HIPCHK(a, q->first.ensure((n + 2) * 8));
+  HIPCHK(a, q->scan_tmp.ensure(scan_tmp_entries(n + 1) * 8 + 64));
+  uint32_t *pa = q->perm_a.as<uint32_t>(), *pb = q->perm_b.as<uint32_t>();
+  uint64_t *ka = q->key_a.as<uint64_t>(), *kb = q->key_b.as<uint64_t>();
+  const int hi_bits = quant::key_hi_bits(q->n_sq);
+  size_t b1 = 0, b2 = 0;
+  HIPCHK(a, hipcub::DeviceRadixSort::SortPairs(nullptr, b1, in.lo, kb, pa, pb, n, 0, quant::KEY_LO_BITS, st));
+  HIPCHK(a, hipcub::DeviceRadixSort::SortPairs(nullptr, b2, ka, kb, pb, pa, n, 0, hi_bits, st));
+  size_t tmp_bytes = b1 > b2 ? b1 : b2;
+  HIPCHK(a, q->cub_tmp.ensure(tmp_bytes + 16));
+  HIPCHK(a, launch_bam_sort_iota(pa, n, st));
+  // least significant word first, every pass stable: rows with equal high words keep the order of their low words
+  HIPCHK(a, hipcub::DeviceRadixSort::SortPairs(q->cub_tmp.p, tmp_bytes, in.lo, kb, pa, pb, n, 0, quant::KEY_LO_BITS, st));
+  HIPCHK(a, launch_quant_gather(in.hi, pb, n, ka, st));
+  HIPCHK(a, hipcub::DeviceRadixSort::SortPairs(q->cub_tmp.p, tmp_bytes, ka, kb, pb, pa, n, 0, hi_bits, st));
+  QuantReduceParams p;
+  memset(&p, 0, sizeof p);
+  p.in = in;
+  p.perm = pa;
+  p.s_hi = kb;
+  p.n = n;
+  p.flag = q->flag.as<uint64_t>();
+  p.first = q->first.as<uint64_t>();
+  HIPCHK(a, launch_quant_heads(p, st));
+  HIPCHK(a, launch_exclusive_scan_u64(p.flag, q->first.as<uint64_t>(), n, q->scan_tmp.as<uint64_t>(), st));
+  unsigned long long n_keys = 0;
+  HIPCHK(a, hipMemcpyAsync(&n_keys, q->first.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(a, hipStreamSynchronize(st));
+  if (n_keys == 0 || n_keys > n) return fail(a, THM_ERR_INTERNAL, "thm_quant: %llu keys among %llu rows", n_keys, (unsigned long long)n);
+  HIPCHK(a, out.ensure(n_keys));
+  HIPCHK(a, hipMemsetAsync(out.nu.p, 0, n_keys * 8, st));
+  HIPCHK(a, hipMemsetAsync(out.nm.p, 0, n_keys * 8, st));
+  HIPCHK(a, hipMemsetAsync(out.ov.p, 0, n_keys * 4, st));
+  p.out = out.rows();
+  HIPCHK(a, launch_quant_reduce(p, st));
+  *m = n_keys;
+  return THM_OK;
+}
+
+// The reduced rows of a batch (q->red, n_red of them) into the running table: rows whose key the table holds add to it
+// in place; new keys are sorted in together with the table's rows, into the other of the two table buffers.
+int merge_rows(thm_quant* q, uint64_t n_red) {
+  thm_aligner* a = q->a;
+  hipStream_t st = a->stream;
+  const uint64_t n_tab = q->n_tab;
+  HIPCHK(a, q->where.ensure(n_red * 4));
+  HIPCHK(a, q->is_new.ensure((n_red + 1) * 8));
+  HIPCHK(a, q->new_at.ensure((n_red + 2) * 8));
+  HIPCHK(a, q->scan_tmp.ensure(scan_tmp_entries(n_red + 1) * 8 + 64));
+  QuantMergeParams p;
+  memset(&p, 0, sizeof p);
+  p.tab = q->tab[q->cur].rows();
+  p.n_tab = n_tab;
+  p.red = q->red.rows();
+  p.n_red = n_red;
+  p.where = q->where.as<uint32_t>();
+  p.is_new = q->is_new.as<uint64_t>();
+  p.new_at = q->new_at.as<uint64_t>();
+  HIPCHK(a, launch_quant_lookup(p, st));
+  HIPCHK(a, launch_exclusive_scan_u64(p.is_new, q->new_at.as<uint64_t>(), n_red, q->scan_tmp.as<uint64_t>(), st));
+  unsigned long long n_new = 0;
+  HIPCHK(a, hipMemcpyAsync(&n_new, q->new_at.as<uint64_t>() + n_red, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(a, hipStreamSynchronize(st));
+  if (n_new > n_red) return fail(a, THM_ERR_INTERNAL, "thm_quant: %llu new keys among %llu rows", n_new, (unsigned long long)n_red);
+  const uint64_t n_cat = n_tab + n_new;
+  if (n_cat > MAX_ROWS) return fail(a, THM_ERR_UNSUPPORTED, "thm_quant: more than 2^32-2 distinct junctions");
+  if (n_new) HIPCHK(a, q->cat.ensure(n_cat));
+  p.cat = q->cat.rows();
+  HIPCHK(a, launch_quant_update(p, st));
+  if (n_new == 0) return THM_OK;
+  if (n_tab) {
+    const RowBuf& t = q->tab[q->cur];
+    HIPCHK(a, hipMemcpyAsync(q->cat.hi.p, t.hi.p, n_tab * 8, hipMemcpyDeviceToDevice, st));
+    HIPCHK(a, hipMemcpyAsync(q->cat.lo.p, t.lo.p, n_tab * 8, hipMemcpyDeviceToDevice, st));
+    HIPCHK(a, hipMemcpyAsync(q->cat.nu.p, t.nu.p, n_tab * 8, hipMemcpyDeviceToDevice, st));
+    HIPCHK(a, hipMemcpyAsync(q->cat.nm.p, t.nm.p, n_tab * 8, hipMemcpyDeviceToDevice, st));
+    HIPCHK(a, hipMemcpyAsync(q->cat.ov.p, t.ov.p, n_tab * 4, hipMemcpyDeviceToDevice, st));
+  }
+  uint64_t m = 0;
+  const int rc = sort_reduce(q, q->cat.rows(), n_cat, q->tab[q->cur ^ 1], &m);
+  if (rc != THM_OK) return rc;
+  if (m != n_cat) return fail(a, THM_ERR_INTERNAL, "thm_quant: %llu rows after a merge of %llu distinct keys", (unsigned long long)m, (unsigned long long)n_cat);
+  q->cur ^= 1;
+  q->n_tab = m;
+  return THM_OK;
+}
+
+// One batch that stands on the device.  Nothing of the tables changes before the batch has passed the device's checks.
+int add_batch(thm_quant* q, const char* who, QuantBatch b, thm_quant_info* info) {
+  thm_aligner* a = q->a;
+  hipStream_t st = a->stream;
+  const thm_index* ix = a->ix;
+  const uint64_t n_alns = b.n_alns;
+  if (n_alns >= MAX_ROWS) return fail(a, THM_ERR_UNSUPPORTED, "%s: 2^32-2 alignments or more in one batch", who);
+  b.n_refs = (uint32_t)ix->refs.size();
+  b.n_txs = (uint32_t)ix->txs.size();
+  b.n_genes = (uint32_t)ix->genes.size();
+  b.tx_gene = a->bt_tx_gene.as<uint32_t>();
+  b.tx_forward = q->tx_forward.as<uint8_t>();
+  b.ref_sq = a->bt_ref_sq.as<int32_t>();
+  HIPCHK(a, ensure_events(q->ev));
+  HIPCHK(a, q->hit_cnt.ensure((n_alns + 1) * 8));
+  HIPCHK(a, q->hit_off.ensure((n_alns + 2) * 8));
+  HIPCHK(a, q->multi.ensure(n_alns + 16));
+  HIPCHK(a, q->scan_tmp.ensure(scan_tmp_entries(n_alns + 1) * 8 + 64));
+  HIPCHK(a, q->d_tot.ensure((quant::N_TOTALS + 1) * 8));
+  QuantCountParams cp;
+  cp.b = b;
+  cp.hit_cnt = q->hit_cnt.as<uint64_t>();
+  cp.multi = q->multi.as<uint8_t>();
+  cp.totals = q->d_tot.as<unsigned long long>();
+  cp.bad = cp.totals + quant::N_TOTALS;
+  HIPCHK(a, hipEventRecord(q->ev[0], st));
+  HIPCHK(a, hipMemsetAsync(cp.totals, 0, quant::N_TOTALS * 8, st));
+  HIPCHK(a, hipMemsetAsync(cp.bad, 0xff, 8, st));
+  HIPCHK(a, launch_quant_count(cp, a->n_cu, st));
+  unsigned long long h_tot[quant::N_TOTALS + 1], n_hits = 0;
+  if (n_alns) {
+    HIPCHK(a, launch_exclusive_scan_u64(cp.hit_cnt, q->hit_off.as<uint64_t>(), n_alns, q->scan_tmp.as<uint64_t>(), st));
+    HIPCHK(a, hipMemcpyAsync(&n_hits, q->hit_off.as<uint64_t>() + n_alns, 8, hipMemcpyDeviceToHost, st));
+  }
+  HIPCHK(a, hipMemcpyAsync(h_tot, cp.totals, sizeof h_tot, hipMemcpyDeviceToHost, st));
+  HIPCHK(a, hipStreamSynchronize(st));
+  if (h_tot[quant::N_TOTALS] != ~0ull)
+    return fail(a, THM_ERR_INTERNAL, "%s: alignment %llu has an index, a CIGAR range or an intron outside the index's tables", who, h_tot[quant::N_TOTALS]);
+  if (n_hits != h_tot[quant::T_HITS]) return fail(a, THM_ERR_INTERNAL, "%s: %llu hits scanned, %llu counted", who, n_hits, h_tot[quant::T_HITS]);
+  if (n_hits > MAX_ROWS) return fail(a, THM_ERR_UNSUPPORTED, "%s: more than 2^32-2 junction hits in one batch", who);
+  if (n_hits) {
+    HIPCHK(a, q->hits.ensure(n_hits));
+    QuantExtractParams ep;
+    ep.b = b;
+    ep.hit_off = q->hit_off.as<uint64_t>();
+    ep.multi = cp.multi;
+    ep.out = q->hits.rows();
+    HIPCHK(a, launch_quant_extract(ep, st));
+    uint64_t n_red = 0;
+    int rc = sort_reduce(q, ep.out, n_hits, q->red, &n_red);
+    if (rc == THM_OK) rc = merge_rows(q, n_red);
+    if (rc != THM_OK) return rc;
+  }
+  QuantGenesParams gp;
+  gp.b = b;
+  gp.multi = cp.multi;
+  gp.genes = q->genes.as<unsigned long long>();
+  // (the fetch's row buffer is sized here, before anything is counted: held_bytes is what the object holds with a fetch)
+  HIPCHK(a, q->d_rows.ensure(q->n_tab * sizeof(thm_quant_junction) + 16));
+  HIPCHK(a, launch_quant_genes(gp, a->n_cu, st));
+  HIPCHK(a, hipEventRecord(q->ev[1], st));
+  HIPCHK(a, hipStreamSynchronize(st));
+  (void)elapsed_ms(q->ev[0], q->ev[1], &info->add_ms);
+  uint64_t* batch = (uint64_t*)&info->batch;
+  uint64_t* total = (uint64_t*)&q->totals;
+  for (int k = 0; k < quant::N_TOTALS; k++) {
+    batch[k] = h_tot[k];
+    total[k] += h_tot[k];
+  }
+  info->n_junctions = q->n_tab;
+  info->held_bytes = q->held_bytes();
+  return THM_OK;
+}
+
+// the checks of thm_quant_add_view, on the host before anything goes up
+int check_view(thm_quant* q, const thm_cigar_view* v) {
+  thm_aligner* a = q->a;
+  const char* who = "thm_quant_add_view";
+  const thm_index* ix = a->ix;
+  const uint64_t n = v->n_reads, n_alns = v->n_alns, n_words = v->n_cigar_words;
+  if ((n && !v->read_aln_off) || (n_alns && (!v->alns || !v->digests || !n)) || (n_words && !v->cigar))
+    return fail(a, THM_ERR_INVALID_ARG, "%s: null offsets, alignments, digests or words", who);
+  if (n) {
+    if (v->read_aln_off[0] != 0) return fail(a, THM_ERR_INVALID_ARG, "%s: read_aln_off[0] must be 0", who);
+    for (uint64_t r = 0; r < n; r++)
+      if (v->read_aln_off[r + 1] < v->read_aln_off[r]) return fail(a, THM_ERR_INVALID_ARG, "%s: the offsets descend at read %llu", who, (unsigned long long)r);
+    if (v->read_aln_off[n] != n_alns)
+      return fail(a, THM_ERR_INVALID_ARG, "%s: the offsets end at %llu, the view has %llu alignments", who, (unsigned long long)v->read_aln_off[n], (unsigned long long)n_alns);
+  }
+  for (uint64_t i = 0; i < n_alns; i++) {
+    const thm_aln& al = v->alns[i];
+    const thm_aln_digest& d = v->digests[i];
+    const unsigned long long at = i;
+    if (al.aln_type > THM_ALN_INTERGENIC) return fail(a, THM_ERR_INVALID_ARG, "%s: alignment %llu: aln_type %u is none", who, at, (unsigned)al.aln_type);
+    if (al.aln_type == THM_ALN_EXONIC && al.tx_or_gene_idx >= ix->txs.size())
+      return fail(a, THM_ERR_INVALID_ARG, "%s: alignment %llu: tx_or_gene_idx %u is outside the index's %zu transcripts", who, at, al.tx_or_gene_idx, ix->txs.size());
+    if (al.aln_type == THM_ALN_INTRONIC && al.tx_or_gene_idx >= ix->genes.size())
+      return fail(a, THM_ERR_INVALID_ARG, "%s: alignment %llu: tx_or_gene_idx %u is outside the index's %zu genes", who, at, al.tx_or_gene_idx, ix->genes.size());
+    if (al.ref_id >= q->h_ref_sq.size() || q->h_ref_sq[al.ref_id] < 0)
+      return fail(a, THM_ERR_INVALID_ARG, "%s: alignment %llu: ref_id %u has no @SQ line", who, at, al.ref_id);
+    if (d.cigar_off > n_words || d.n_cigar > n_words - d.cigar_off)
+      return fail(a, THM_ERR_INVALID_ARG, "%s: alignment %llu: CIGAR words [%llu, +%u) are outside the pool of %llu", who, at, (unsigned long long)d.cigar_off, d.n_cigar,
+                  (unsigned long long)n_words);
+    if (d.flags & THM_DIGEST_LONG_RUN) continue;
+    uint64_t span = 0;
+    const uint32_t n_hits = quant::count_hits(v->cigar + d.cigar_off, d.n_cigar, &span);
+    if (al.ystart > 0xFFFFFFFFull || al.ystart + span > 0xFFFFFFFFull)
+      return fail(a, THM_ERR_INVALID_ARG, "%s: alignment %llu: position %llu + %llu is 2^32 or more", who, at, (unsigned long long)al.ystart, (unsigned long long)span);
+    if (n_hits && al.aln_type != THM_ALN_EXONIC)
+      return fail(a, THM_ERR_INVALID_ARG, "%s: alignment %llu: an N word in an alignment that is not exonic has no strand", who, at);
+  }
+  return THM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t thm_quant_create(thm_aligner* a, thm_quant** out) {
+  if (!out) return THM_ERR_INVALID_ARG;
+  *out = nullptr;
+  if (!a) return THM_ERR_INVALID_ARG;
+  const thm_index* ix = a->ix;
+  for (size_t r = 0; r < ix->refs.size(); r++)
+    if (ix->refs[r].len >= (1ull << 32))
+      return fail(a, THM_ERR_UNSUPPORTED, "thm_quant_create: contig %zu has %llu bases, 2^32 or more", r, (unsigned long long)ix->refs[r].len);
+  if (ix->genes.size() > 0x3FFFFFFFull) return fail(a, THM_ERR_UNSUPPORTED, "thm_quant_create: 2^30 genes or more");
+  HIPCHK(a, hipSetDevice(a->device));
+  int rc = bam_tables_on_device(a);
+  if (rc != THM_OK) return rc;
+  thm_quant* q = new thm_quant();
+  q->a = a;
+  memset(&q->totals, 0, sizeof q->totals);
+  const size_t n_refs = ix->refs.size(), n_txs = ix->txs.size(), n_genes = ix->genes.size();
+  q->h_ref_sq.assign(n_refs, -1);
+  std::vector<uint8_t> fwd(n_txs + 1, 0);
+  for (size_t t = 0; t < n_txs; t++) fwd[t] = ix->txs[t].strand ? 1 : 0;
+  hipError_t e = q->tx_forward.ensure(fwd.size());
+  if (e == hipSuccess) e = q->genes.ensure((n_genes * 4 + 1) * 8);
+  if (e == hipSuccess) e = hipMemcpy(q->tx_forward.p, fwd.data(), fwd.size(), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(q->genes.p, 0, (n_genes * 4 + 1) * 8);
+  if (e == hipSuccess && n_refs) e = hipMemcpy(q->h_ref_sq.data(), a->bt_ref_sq.p, n_refs * 4, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) {
+    delete q;
+    return fail(a, e == hipErrorOutOfMemory ? THM_ERR_OOM : THM_ERR_HIP, "thm_quant_create: %s", hipGetErrorString(e));
+  }
+  int32_t top = -1;
+  for (int32_t s : q->h_ref_sq) top = s > top ? s : top;
+  q->n_sq = (uint32_t)(top + 1);
+  *out = q;
+  return THM_OK;
+}
+
+void thm_quant_free(thm_quant* q) {
+  if (!q) return;
+  int cur = 0;
+  (void)hipGetDevice(&cur);
+  (void)hipSetDevice(q->a->device);
+  (void)hipStreamSynchronize(q->a->stream);
+  delete q;
+  (void)hipSetDevice(cur);
+}
+
+int32_t thm_quant_add(thm_quant* q, thm_quant_info* info) {
+  if (!q || !info) return THM_ERR_INVALID_ARG;
+  memset(info, 0, sizeof(*info));
+  thm_aligner* a = q->a;
+  int rc = thm_batch_sync(a);
+  if (rc != THM_OK) return rc;
+  HIPCHK(a, hipSetDevice(a->device));
+  BatchSizes z;
+  rc = fetch_batch_sizes(a, nullptr, nullptr, nullptr, &z);
+  if (rc != THM_OK) return rc;
+  // the two CIGAR passes, as thm_batch_fetch_cigars runs them (THM_T_CIGAR belongs to that call)
+  uint64_t n_words = 0;
+  unsigned any_flags = 0;
+  const float t_cigar = a->timings[THM_T_CIGAR];
+  rc = run_cigar_passes(a, compacted_cigar_params(a, z), z.n_alns, &n_words, &any_flags);
+  a->timings[THM_T_CIGAR] = t_cigar;
+  if (rc != THM_OK) return rc;
+  if (any_flags & THM_DIGEST_MALFORMED) return fail(a, THM_ERR_INTERNAL, "malformed op stream in the compacted pool");
+  QuantBatch b;
+  memset(&b, 0, sizeof b);
+  b.n_reads = a->n_reads;
+  b.n_alns = z.n_alns;
+  b.n_words = n_words;
+  b.aln_off = a->e_aln_off.as<uint64_t>();
+  b.alns = a->o_alns.as<thm_aln>();
+  b.digests = a->c_dig.as<thm_aln_digest>();
+  b.words = a->c_words.as<uint32_t>();
+  b.status = z.any_failed ? a->r_status.as<int32_t>() : nullptr;
+  return add_batch(q, "thm_quant_add", b, info);
+}
+
+int32_t thm_quant_add_view(thm_quant* q, const thm_cigar_view* v, thm_quant_info* info) {
+  if (!q || !v || !info) return THM_ERR_INVALID_ARG;
+  memset(info, 0, sizeof(*info));
+  thm_aligner* a = q->a;
+  int rc = check_view(q, v);
+  if (rc != THM_OK) return rc;
+  HIPCHK(a, hipSetDevice(a->device));
+  hipStream_t st = a->stream;
+  const uint64_t n = v->n_reads, n_alns = v->n_alns, n_words = v->n_cigar_words;
+  const uint64_t zero = 0;
+  HIPCHK(a, q->v_off.ensure((n + 1) * 8));
+  HIPCHK(a, q->v_alns.ensure((n_alns + 1) * sizeof(thm_aln)));
+  HIPCHK(a, q->v_dig.ensure((n_alns + 1) * sizeof(thm_aln_digest)));
+  HIPCHK(a, q->v_words.ensure((n_words + 4) * 4));
+  HIPCHK(a, hipMemcpyAsync(q->v_off.p, n ? v->read_aln_off : &zero, (n + 1) * 8, hipMemcpyHostToDevice, st));
+  if (n_alns) HIPCHK(a, hipMemcpyAsync(q->v_alns.p, v->alns, n_alns * sizeof(thm_aln), hipMemcpyHostToDevice, st));
+  if (n_alns) HIPCHK(a, hipMemcpyAsync(q->v_dig.p, v->digests, n_alns * sizeof(thm_aln_digest), hipMemcpyHostToDevice, st));
+  if (n_words) HIPCHK(a, hipMemcpyAsync(q->v_words.p, v->cigar, n_words * 4, hipMemcpyHostToDevice, st));
+  if (v->read_status && n) {
+    HIPCHK(a, q->v_stat.ensure(n * 4));
+    HIPCHK(a, hipMemcpyAsync(q->v_stat.p, v->read_status, n * 4, hipMemcpyHostToDevice, st));
+  }
+  HIPCHK(a, hipStreamSynchronize(st));  // (`zero` and the caller's arrays have been read)
+  QuantBatch b;
+  memset(&b, 0, sizeof b);
+  b.n_reads = n;
+  b.n_alns = n_alns;
+  b.n_words = n_words;
+  b.aln_off = q->v_off.as<uint64_t>();
+  b.alns = q->v_alns.as<thm_aln>();
+  b.digests = q->v_dig.as<thm_aln_digest>();
+  b.words = q->v_words.as<uint32_t>();
+  b.status = v->read_status && n ? q->v_stat.as<int32_t>() : nullptr;
+  return add_batch(q, "thm_quant_add_view", b, info);
+}
+
+int32_t thm_quant_fetch(thm_quant* q, thm_quant_view* out) {
+  if (!q || !out) return THM_ERR_INVALID_ARG;
+  memset(out, 0, sizeof(*out));
+  thm_aligner* a = q->a;
+  HIPCHK(a, hipSetDevice(a->device));
+  hipStream_t st = a->stream;
+  const uint64_t n_genes = a->ix->genes.size(), n = q->n_tab;
+  const size_t gene_bytes = n_genes * sizeof(thm_quant_gene), row_bytes = n * sizeof(thm_quant_junction);
+  HIPCHK(a, ensure_events(q->ev_fetch));
+  HIPCHK(a, q->d_rows.ensure(row_bytes + 16));
+  HIPCHK(a, q->h_out.ensure(gene_bytes + row_bytes + 16));
+  HIPCHK(a, hipEventRecord(q->ev_fetch[0], st));
+  HIPCHK(a, launch_quant_rows(q->tab[q->cur].rows(), n, q->d_rows.as<thm_quant_junction>(), st));
+  if (gene_bytes) HIPCHK(a, hipMemcpyAsync(q->h_out.p, q->genes.p, gene_bytes, hipMemcpyDeviceToHost, st));
+  if (row_bytes) HIPCHK(a, hipMemcpyAsync(q->h_out.as<uint8_t>() + gene_bytes, q->d_rows.p, row_bytes, hipMemcpyDeviceToHost, st));
+  HIPCHK(a, hipEventRecord(q->ev_fetch[1], st));
+  HIPCHK(a, hipStreamSynchronize(st));
+  (void)elapsed_ms(q->ev_fetch[0], q->ev_fetch[1], &out->fetch_ms);
+  out->n_genes = n_genes;
+  out->genes = q->h_out.as<thm_quant_gene>();
+  out->n_junctions = n;
+  out->junctions = (const thm_quant_junction*)(q->h_out.as<uint8_t>() + gene_bytes);
+  out->totals = q->totals;
+  return THM_OK;
+}
+
+int32_t thm_quant_reset(thm_quant* q) {
+  if (!q) return THM_ERR_INVALID_ARG;
+  thm_aligner* a = q->a;
+  HIPCHK(a, hipSetDevice(a->device));
+  HIPCHK(a, hipMemsetAsync(q->genes.p, 0, (a->ix->genes.size() * 4 + 1) * 8, a->stream));
+  HIPCHK(a, hipStreamSynchronize(a->stream));
+  q->n_tab = 0;
+  memset(&q->totals, 0, sizeof q->totals);
+  return THM_OK;
+}
+
+}  // extern "C"

@@ -16,16 +16,23 @@ identical (batch boundaries differ).
 (default 3) in one session; then the same reads through thm_bam_sorter by hand: sort_ms of thm_bam_sorter_finish, the drain
 with the two gather shapes alternating window by window (gather_ms, deflate_ms per window) and index_ms of
 thm_bam_sorter_index, three calls.  The gzip files are not made.
+--quant[=ROUNDS]: only plain FASTQ -> BAM with THM_BAM_DEVICE=1, without and with THM_QUANT=1 alternately, ROUNDS rounds
+(default 3) in one session (the two .tsv files' sizes are reported); then one batch of 500 000 reads, of 91 and of 150
+bases, through thm_quant by hand: add_ms and fetch_ms beside THM_T_CIGAR and THM_T_COMPACT of the same run, five adds each.
 --sha[=PART]: with any of the modes above, "sha256 <hash> <file> <bytes>" for every output file before it is removed (two
 builds of the library -- THM_LIB selects one -- are compared by these lines); with PART also, after every run that wrote a
 file whose name holds PART, "each <file> raw <hash> inflated <hash> size <bytes> batches <n>": does an output repeat from
 run to run, compressed and inflated?"""
 import hashlib, os, sys, time
-BAM_RUNS = FQ_ROUNDS = BGZF_ROUNDS = GZIP_ROUNDS = SORT_ROUNDS = 0
+BAM_RUNS = FQ_ROUNDS = BGZF_ROUNDS = GZIP_ROUNDS = SORT_ROUNDS = QUANT_ROUNDS = 0
 SHA, SHA_EACH = False, None
 for arg in list(sys.argv[1:]):
     if arg.startswith("--sha"):
         SHA, SHA_EACH = True, (arg.split("=")[1] if "=" in arg else None)
+        sys.argv.remove(arg)
+        continue
+    if arg.startswith("--quant"):
+        QUANT_ROUNDS = int(arg.split("=")[1]) if "=" in arg else 3
         sys.argv.remove(arg)
         continue
     if arg.startswith("--bam-sort"):
@@ -101,6 +108,42 @@ with open(big, "wb") as f:
         f.write(one)
     del one
 print("plain input: %d reads, %.1f MB" % (n * REP, os.path.getsize(big) / 1e6), flush=True)
+if QUANT_ROUNDS:
+    os.environ["THM_BAM_DEVICE"] = "1"
+    out = "/tmp/thm_e2e_out.bam"
+    st = capi.align_files(a, [big], out, capi.FMT_BAM, batch_reads=250000, n_threads=threads)   # warm-up: buffers grow
+    for k in range(QUANT_ROUNDS):
+        for tag, on in (("THM_BAM_DEVICE=1            ", False), ("THM_BAM_DEVICE=1 THM_QUANT=1", True)):
+            os.environ.pop("THM_QUANT", None)
+            if on:
+                os.environ["THM_QUANT"] = "1"
+            st = capi.align_files(a, [big], out, capi.FMT_BAM, batch_reads=250000, n_threads=threads)
+            tsv = ""
+            if on:
+                tsv = ", genes.tsv %d bytes, junctions.tsv %d bytes" % (os.path.getsize(out + ".genes.tsv"), os.path.getsize(out + ".junctions.tsv"))
+                os.remove(out + ".genes.tsv")
+                os.remove(out + ".junctions.tsv")
+            print("bam %s round %d: %.2f Mreads/s wall %.3fs | parse %.2fs gpu %.2fs format %.2fs write %.2fs | %d batches, %.0f MB out%s" % (
+                tag, k, st["n_reads"] / st["wall_s"] / 1e6, st["wall_s"], st["parse_s"], st["gpu_s"], st["format_s"], st["write_s"],
+                st["n_batches"], st["n_output_bytes"] / 1e6, tsv), flush=True)
+    os.environ.pop("THM_QUANT", None)
+    # one batch of 500 000 reads by hand
+    for L in (91, 150):
+        b, o, _ = synth.simulate_reads(t, 500000, L, sub_rate=0.01, indel_rate=0.001, stream=7)
+        q = capi.Quant(a)
+        a.upload(b, o)
+        a.run()
+        a.fetch_cigars(copy=False)
+        tm = a.timings()
+        adds = [q.add() for _ in range(5)]
+        fetches = [q.fetch() for _ in range(3)]
+        print("quant %d bp: 500000 reads, %d alns, %d spliced, %d hits -> %d junctions, held %.1f MB | add_ms %s | fetch_ms %s | THM_T_CIGAR %.3f THM_T_COMPACT %.3f THM_T_TOTAL %.3f" % (
+            L, adds[0]["n_alns"], adds[0]["n_spliced_alns"], adds[0]["n_junction_hits"], adds[0]["n_junctions"], adds[0]["held_bytes"] / 1e6,
+            " ".join("%.3f" % x["add_ms"] for x in adds), " ".join("%.3f" % x.fetch_ms for x in fetches), tm["cigar"], tm["compact"], tm["total"]), flush=True)
+        q.close()
+    a.close()
+    drop(out)
+    sys.exit(0)
 if SORT_ROUNDS:
     os.environ["THM_FASTQ_DEVICE"] = "1"
     os.environ["THM_BAM_DEVICE"] = "2"
