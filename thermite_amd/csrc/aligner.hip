@@ -41,12 +41,21 @@ static bool lut_direct_wanted() {
   return !(e && e[0] == '0');
 }
 
+// `v` into `b`, which gets 16 bytes at least
 template <class T>
 static hipError_t upload(DBuf& b, const std::vector<T>& v, hipStream_t s) {
   size_t bytes = std::max<size_t>(v.size() * sizeof(T), 16);
   hipError_t e = b.ensure(bytes);
   if (e != hipSuccess) return e;
   if (!v.empty()) return hipMemcpyAsync(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s);
+  return hipSuccess;
+}
+template <class T>
+static hipError_t upload(DArr<T>& b, const std::vector<T>& v, hipStream_t s) {
+  const size_t bytes = v.size() * sizeof(T);
+  hipError_t e = b.ensure(v.size(), bytes < 16 ? 16 - bytes : 0);
+  if (e != hipSuccess) return e;
+  if (!v.empty()) return hipMemcpyAsync(b, v.data(), bytes, hipMemcpyHostToDevice, s);
   return hipSuccess;
 }
 
@@ -65,10 +74,10 @@ static int get_dev_copy(thm_aligner* a) {
     d->wide = ix->wide;
     // the text gets 16 bytes in front (left extensions are read in whole 8-byte words that may begin a few bytes before the
     // first symbol; the window staging of the wave-per-read kernels rounds its addresses down to 16 bytes)
-    if (e == hipSuccess) e = d->text.ensure(ix->text.size() + 16 + 16);
-    if (e == hipSuccess) e = hipMemsetAsync(d->text.p, '$', 16, s);
+    if (e == hipSuccess) e = d->text.ensure(ix->text.size(), 16 + 16);
+    if (e == hipSuccess) e = hipMemsetAsync(d->text, '$', 16, s);
     if (e == hipSuccess && !ix->text.empty())
-      e = hipMemcpyAsync(d->text.as<uint8_t>() + 16, ix->text.data(), ix->text.size(), hipMemcpyHostToDevice, s);
+      e = hipMemcpyAsync(d->text + 16, ix->text.data(), ix->text.size(), hipMemcpyHostToDevice, s);
     if (ix->wide) {
       up(d->sa, ix->sa64);
       up(d->lut, ix->lut64);
@@ -83,10 +92,10 @@ static int get_dev_copy(thm_aligner* a) {
     up(d->exon_txoff, ix->exon_txoff);
     // transcript sequences get 16 bytes of front padding: window staging reads whole 16-byte
     // granules and may start up to 15 bytes before a transcript
-    if (e == hipSuccess) e = d->tx_seq.ensure(ix->tx_seq.size() + 32);
-    if (e == hipSuccess) e = hipMemsetAsync(d->tx_seq.p, '$', 16, s);
+    if (e == hipSuccess) e = d->tx_seq.ensure(ix->tx_seq.size(), 32);
+    if (e == hipSuccess) e = hipMemsetAsync(d->tx_seq, '$', 16, s);
     if (e == hipSuccess && !ix->tx_seq.empty())
-      e = hipMemcpyAsync(d->tx_seq.as<uint8_t>() + 16, ix->tx_seq.data(), ix->tx_seq.size(), hipMemcpyHostToDevice, s);
+      e = hipMemcpyAsync(d->tx_seq + 16, ix->tx_seq.data(), ix->tx_seq.size(), hipMemcpyHostToDevice, s);
     up(d->exon_grid_off, ix->exon_grid_off);
     up(d->gene_grid_off, ix->gene_grid_off);
     up(d->ref_bin, ix->ref_bin);
@@ -106,14 +115,14 @@ static int get_dev_copy(thm_aligner* a) {
     const bool tag = lut_direct_wanted() && (ix->wide ? lutd::can_tag<uint64_t>(ix->n) : lutd::can_tag<uint32_t>(ix->n)) &&
                      (ix->wide ? !ix->lut64.empty() : !ix->lut.empty());
     if (tag) {
-      if (e == hipSuccess) e = d->lut_cnt.ensure(16);
-      if (e == hipSuccess) e = hipMemsetAsync(d->lut_cnt.p, 0, 16, s);
+      if (e == hipSuccess) e = d->lut_cnt.ensure(2);
+      if (e == hipSuccess) e = hipMemsetAsync(d->lut_cnt, 0, 16, s);
       if (e == hipSuccess)
         e = ix->wide ? launch_lut_tag(d->lut.as<LutEntryT<uint64_t>>(), d->sa.as<uint64_t>(), ix->lut64.size(), ix->n,
-                                      d->lut_cnt.as<unsigned long long>(), s)
+                                      d->lut_cnt, s)
                      : launch_lut_tag(d->lut.as<LutEntryT<uint32_t>>(), d->sa.as<uint32_t>(), ix->lut.size(), ix->n,
-                                      d->lut_cnt.as<unsigned long long>(), s);
-      if (e == hipSuccess) e = hipMemcpyAsync(&d->lut_tagged, d->lut_cnt.p, 8, hipMemcpyDeviceToHost, s);
+                                      d->lut_cnt, s);
+      if (e == hipSuccess) e = hipMemcpyAsync(&d->lut_tagged, d->lut_cnt, 8, hipMemcpyDeviceToHost, s);
       d->lut_direct = true;
     }
     if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -124,20 +133,20 @@ static int get_dev_copy(thm_aligner* a) {
     }
     auto fill_view = [&](auto& v) {
       typedef typename std::remove_reference<decltype(v)>::type::coord_t C;
-      v.text = d->text.as<uint8_t>() + 16;
+      v.text = d->text + 16;
       v.sa = d->sa.as<C>();
       v.lut = d->lut.as<LutEntryT<C>>();
-      v.refs = d->refs.as<thm_ref>();
-      v.name_rank = d->name_rank.as<uint32_t>();
+      v.refs = d->refs;
+      v.name_rank = d->name_rank;
       v.ref_recs = d->ref_recs.as<RefRecT<C>>();
-      v.ref_bin = d->ref_bin.as<uint32_t>();
-      v.txs = d->txs.as<thm_tx>();
-      v.exons = d->exons.as<thm_exon>();
-      v.exon_txoff = d->exon_txoff.as<uint64_t>();
-      v.tx_seq = d->tx_seq.as<uint8_t>() + 16;
-      v.exon_grid_off = d->exon_grid_off.as<uint32_t>();
+      v.ref_bin = d->ref_bin;
+      v.txs = d->txs;
+      v.exons = d->exons;
+      v.exon_txoff = d->exon_txoff;
+      v.tx_seq = d->tx_seq + 16;
+      v.exon_grid_off = d->exon_grid_off;
       v.exon_grid = d->exon_grid.as<ExonEntryT<C>>();
-      v.gene_grid_off = d->gene_grid_off.as<uint32_t>();
+      v.gene_grid_off = d->gene_grid_off;
       v.gene_grid = d->gene_grid.as<GridEntryT<C>>();
       v.n = ix->n;
       v.n_refs = (uint32_t)ix->refs.size();
@@ -159,8 +168,8 @@ static int get_dev_copy(thm_aligner* a) {
 }
 
 int reset_queue(thm_aligner* a) {
-  HIPCHK(a, hipMemsetAsync(a->d_queue.p, 0, thm::QUEUE_BYTES, a->stream));
-  HIPCHK(a, hipMemsetAsync(a->d_fault.p, 0, 64, a->stream));
+  HIPCHK(a, hipMemsetAsync(a->d_queue, 0, thm::QUEUE_BYTES, a->stream));
+  HIPCHK(a, hipMemsetAsync(a->d_fault, 0, 64, a->stream));
   return THM_OK;
 }
 
@@ -216,17 +225,17 @@ int32_t thm_aligner_create(const thm_index* ix, const thm_align_opts* opts, int3
       a->tpr.ev_join3.ensure(false) != hipSuccess || a->ev_fork.ensure(false) != hipSuccess ||
       a->ev_join.ensure(false) != hipSuccess)
     return bail(fail(nullptr, THM_ERR_HIP, "second stream / events: creation failed"));
-  if (a->d_counters.ensure(THM_N_COUNTERS * 8 * 3) != hipSuccess || a->d_ctl.ensure(thm_aligner::CTL_BYTES) != hipSuccess)
+  if (a->d_counters.ensure(THM_N_COUNTERS * 3) != hipSuccess || a->d_ctl.ensure(thm_aligner::CTL_BYTES) != hipSuccess)
     return bail(fail(nullptr, THM_ERR_OOM, "scratch allocation failed"));
   {
     uint8_t* ctl = a->d_ctl.as<uint8_t>();
-    a->s_work_counts = {ctl + thm_aligner::CTL_WORK_COUNTS, 128};
-    a->d_cursors = {ctl + thm_aligner::CTL_CURSORS, 64};
-    a->d_fault = {ctl + thm_aligner::CTL_FAULT, 64};
-    a->d_queue = {ctl + thm_aligner::CTL_QUEUE, thm::QUEUE_BYTES};
-    a->d_queue_ext = {ctl + thm_aligner::CTL_QUEUE_EXT, thm::QUEUE_BYTES};
+    a->s_work_counts = {(unsigned long long*)(ctl + thm_aligner::CTL_WORK_COUNTS), 128};
+    a->d_cursors = {(unsigned long long*)(ctl + thm_aligner::CTL_CURSORS), 64};
+    a->d_fault = {(int*)(ctl + thm_aligner::CTL_FAULT), 64};
+    a->d_queue = {(unsigned int*)(ctl + thm_aligner::CTL_QUEUE), thm::QUEUE_BYTES};
+    a->d_queue_ext = {(unsigned int*)(ctl + thm_aligner::CTL_QUEUE_EXT), thm::QUEUE_BYTES};
   }
-  (void)hipMemsetAsync(a->d_counters.p, 0, THM_N_COUNTERS * 8 * 3, a->stream);
+  (void)hipMemsetAsync(a->d_counters, 0, THM_N_COUNTERS * 8 * 3, a->stream);
   (void)hipMemsetAsync(a->d_ctl.p, 0, thm_aligner::CTL_BYTES, a->stream);
   int rc = get_dev_copy(a);
   if (rc != THM_OK) return bail(rc);
@@ -269,17 +278,17 @@ const thm_index* thm_aligner_index(const thm_aligner* a) { return a ? a->ix : nu
 int32_t thm_counters_get(thm_aligner* a, uint64_t out[THM_N_COUNTERS]) {
   if (!a || !out) return THM_ERR_INVALID_ARG;
   HIPCHK(a, hipSetDevice(a->device));
-  HIPCHK(a, hipMemcpyAsync(out, a->d_counters.p, THM_N_COUNTERS * 8, hipMemcpyDeviceToHost, a->stream));
+  HIPCHK(a, hipMemcpyAsync(out, a->d_counters, THM_N_COUNTERS * 8, hipMemcpyDeviceToHost, a->stream));
   HIPCHK(a, hipStreamSynchronize(a->stream));
   return THM_OK;
 }
 int32_t thm_counters_reset(thm_aligner* a) {
   if (!a) return THM_ERR_INVALID_ARG;
   HIPCHK(a, hipSetDevice(a->device));
-  HIPCHK(a, hipMemsetAsync(a->d_counters.p, 0, THM_N_COUNTERS * 8, a->stream));
+  HIPCHK(a, hipMemsetAsync(a->d_counters, 0, THM_N_COUNTERS * 8, a->stream));
   return THM_OK;
 }
-void* thm_counters_device_ptr(thm_aligner* a) { return a ? a->d_counters.p : nullptr; }
+void* thm_counters_device_ptr(thm_aligner* a) { return a ? a->d_counters.get() : nullptr; }
 
 int32_t thm_timings_get(thm_aligner* a, float out[THM_N_TIMINGS]) {
   if (!a || !out) return THM_ERR_INVALID_ARG;
@@ -355,9 +364,9 @@ int32_t thm_swg_extend_batch(thm_aligner* a, const uint8_t* x_bases, const uint6
   p.ops_off = a->b6.as<uint64_t>();
   p.ops = a->b7.as<uint8_t>();
   p.out = a->b8.as<thm_swg_aln>();
-  p.counters = a->d_counters.as<unsigned long long>();
-  p.queue = a->d_queue.as<unsigned int>();
-  p.fault = a->d_fault.as<int>();
+  p.counters = a->d_counters;
+  p.queue = a->d_queue;
+  p.fault = a->d_fault;
   p.n = n;
   const int bpc = swg_blocks_per_cu();
   int n_blocks = grid_blocks(a, n, 4, bpc);
@@ -367,8 +376,8 @@ int32_t thm_swg_extend_batch(thm_aligner* a, const uint8_t* x_bases, const uint6
     if (p.scratch_per_wave > budget) return fail(a, THM_ERR_UNSUPPORTED, "DP trace of %llu bytes per problem exceeds the device-memory budget",
                                                  (unsigned long long)p.scratch_per_wave);
     n_blocks = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)n_blocks, budget / p.scratch_per_wave / 4));
-    HIPCHK(a, a->e_slow.ensure((size_t)n_blocks * 4 * p.scratch_per_wave + 256));
-    p.scratch = a->e_slow.as<uint8_t>();
+    HIPCHK(a, a->ext.slow.ensure((size_t)n_blocks * 4 * p.scratch_per_wave, 256));
+    p.scratch = a->ext.slow;
   }
   HIPCHK(a, launch_swg_batch(p, cpl, n_blocks, s));
   std::vector<thm_swg_aln> raw(n);
@@ -376,7 +385,7 @@ int32_t thm_swg_extend_batch(thm_aligner* a, const uint8_t* x_bases, const uint6
   int fault = 0;
   HIPCHK(a, hipMemcpyAsync(raw.data(), a->b8.p, n * sizeof(thm_swg_aln), hipMemcpyDeviceToHost, s));
   HIPCHK(a, hipMemcpyAsync(pool_h.data(), a->b7.p, pool, hipMemcpyDeviceToHost, s));
-  HIPCHK(a, hipMemcpyAsync(&fault, a->d_fault.p, 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(a, hipMemcpyAsync(&fault, a->d_fault, 4, hipMemcpyDeviceToHost, s));
   HIPCHK(a, hipStreamSynchronize(s));
   if (fault) return fail(a, THM_ERR_INTERNAL, "inconsistent trace in swg_batch_kernel");
   // canonical layout: op streams back to back in problem order
@@ -456,7 +465,7 @@ int32_t thm_extend_left_right_batch(thm_aligner* a, const uint8_t* x_bases, cons
   HIPCHK(a, a->b6.ensure((n + 1) * 8));
   HIPCHK(a, a->b7.ensure(pool + 16));
   HIPCHK(a, a->b8.ensure(n * sizeof(thm_lr_aln)));
-  HIPCHK(a, a->sh_hits.ensure(n * sizeof(thm_mem)));
+  HIPCHK(a, a->sh.hits.ensure(n));
   hipStream_t s = a->stream;
   if (xb_n) HIPCHK(a, hipMemcpyAsync(a->b0.p, x_bases, xb_n, hipMemcpyHostToDevice, s));
   HIPCHK(a, hipMemcpyAsync(a->b1.p, x_off, (n + 1) * 8, hipMemcpyHostToDevice, s));
@@ -465,22 +474,22 @@ int32_t thm_extend_left_right_batch(thm_aligner* a, const uint8_t* x_bases, cons
   HIPCHK(a, hipMemcpyAsync(a->b4.p, band_width, n * 4, hipMemcpyHostToDevice, s));
   HIPCHK(a, hipMemcpyAsync(a->b5.p, x_drop, n * 4, hipMemcpyHostToDevice, s));
   HIPCHK(a, hipMemcpyAsync(a->b6.p, ops_off.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
-  HIPCHK(a, hipMemcpyAsync(a->sh_hits.p, hits, n * sizeof(thm_mem), hipMemcpyHostToDevice, s));
+  HIPCHK(a, hipMemcpyAsync(a->sh.hits, hits, n * sizeof(thm_mem), hipMemcpyHostToDevice, s));
   int rc = reset_queue(a);
   if (rc != THM_OK) return rc;
   p.xb = a->b0.as<uint8_t>();
   p.xo = a->b1.as<uint64_t>();
   p.yb = a->b2.as<uint8_t>();
   p.yo = a->b3.as<uint64_t>();
-  p.hits = a->sh_hits.as<thm_mem>();
+  p.hits = a->sh.hits;
   p.bw = a->b4.as<uint32_t>();
   p.xd = a->b5.as<int32_t>();
   p.ops_off = a->b6.as<uint64_t>();
   p.ops = a->b7.as<uint8_t>();
   p.out = a->b8.as<thm_lr_aln>();
-  p.counters = a->d_counters.as<unsigned long long>();
-  p.queue = a->d_queue.as<unsigned int>();
-  p.fault = a->d_fault.as<int>();
+  p.counters = a->d_counters;
+  p.queue = a->d_queue;
+  p.fault = a->d_fault;
   p.n = n;
   int n_blocks = grid_blocks(a, n, 4, 4);
   if (cpl == 0) {
@@ -489,8 +498,8 @@ int32_t thm_extend_left_right_batch(thm_aligner* a, const uint8_t* x_bases, cons
     if (p.scratch_per_wave > budget) return fail(a, THM_ERR_UNSUPPORTED, "DP trace of %llu bytes per problem exceeds the device-memory budget",
                                                  (unsigned long long)p.scratch_per_wave);
     n_blocks = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)n_blocks, budget / p.scratch_per_wave / 4));
-    HIPCHK(a, a->e_slow.ensure((size_t)n_blocks * 4 * p.scratch_per_wave + 256));
-    p.scratch = a->e_slow.as<uint8_t>();
+    HIPCHK(a, a->ext.slow.ensure((size_t)n_blocks * 4 * p.scratch_per_wave, 256));
+    p.scratch = a->ext.slow;
   }
   HIPCHK(a, launch_elr_batch(p, cpl, n_blocks, s));
   std::vector<thm_lr_aln> raw(n);
@@ -498,7 +507,7 @@ int32_t thm_extend_left_right_batch(thm_aligner* a, const uint8_t* x_bases, cons
   int fault = 0;
   HIPCHK(a, hipMemcpyAsync(raw.data(), a->b8.p, n * sizeof(thm_lr_aln), hipMemcpyDeviceToHost, s));
   if (pool) HIPCHK(a, hipMemcpyAsync(pool_h.data(), a->b7.p, pool, hipMemcpyDeviceToHost, s));
-  HIPCHK(a, hipMemcpyAsync(&fault, a->d_fault.p, 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(a, hipMemcpyAsync(&fault, a->d_fault, 4, hipMemcpyDeviceToHost, s));
   HIPCHK(a, hipStreamSynchronize(s));
   if (fault) return fail(a, THM_ERR_INTERNAL, "inconsistent trace in elr_batch_kernel");
   // canonical layout: op streams back to back in problem order
@@ -522,7 +531,7 @@ int32_t thm_extend_left_right_batch(thm_aligner* a, const uint8_t* x_bases, cons
 int32_t thm_debug_prof_get(thm_aligner* a, uint64_t out[16], int32_t reset) {
   if (!a || !out) return THM_ERR_INVALID_ARG;
   HIPCHK(a, hipSetDevice(a->device));
-  uint8_t* p = a->d_counters.as<uint8_t>() + 2 * THM_N_COUNTERS * 8;
+  unsigned long long* p = a->d_counters + 2 * THM_N_COUNTERS;
   HIPCHK(a, hipMemcpyAsync(out, p, 16 * 8, hipMemcpyDeviceToHost, a->stream));
   if (reset) HIPCHK(a, hipMemsetAsync(p, 0, 16 * 8, a->stream));
   HIPCHK(a, hipStreamSynchronize(a->stream));
@@ -536,7 +545,7 @@ int32_t thm_debug_set_pool_caps(thm_aligner* a, uint64_t smem_cap, uint64_t cand
   a->dbg_smem_cap = smem_cap;
   a->dbg_cand_cap = cand_cap;
   a->dbg_ops_cap = ops_cap;
-  a->smem_cap = a->cand_cap = a->cand_ops_cap = 0;
+  a->seed.smem_cap = a->ext.cand_cap = a->ext.cand_ops_cap = 0;
   if (n_replays) *n_replays = a->n_replays;
   return THM_OK;
 }
@@ -578,11 +587,11 @@ int32_t thm_debug_set_flags(thm_aligner* a, uint32_t flags) {
 int32_t thm_debug_smem_finish_stats(thm_aligner* a, uint64_t stats[4]) {
   if (!a || !stats) return THM_ERR_INVALID_ARG;
   stats[0] = stats[1] = stats[2] = stats[3] = 0;
-  if (!a->fin_blocks || !a->e_finstats.p) return THM_OK;
+  if (!a->fin_blocks || !a->ext.finstats.get()) return THM_OK;
   HIPCHK(a, hipSetDevice(a->device));
   HIPCHK(a, hipStreamSynchronize(a->stream));
   std::vector<unsigned long long> rows((size_t)a->fin_blocks * 4);
-  HIPCHK(a, hipMemcpy(rows.data(), a->e_finstats.p, rows.size() * 8, hipMemcpyDeviceToHost));
+  HIPCHK(a, hipMemcpy(rows.data(), a->ext.finstats, rows.size() * 8, hipMemcpyDeviceToHost));
   for (size_t b = 0; b < a->fin_blocks; b++)
     for (int k = 0; k < 4; k++) stats[k] += rows[b * 4 + k];
   return THM_OK;
@@ -595,7 +604,7 @@ int32_t thm_debug_seed_stats(thm_aligner* a, uint64_t stats[2]) {
   if (!a->s_work_counts.p || a->s_work_counts.cap < 128) return THM_OK;
   HIPCHK(a, hipSetDevice(a->device));
   HIPCHK(a, hipStreamSynchronize(a->stream));
-  HIPCHK(a, hipMemcpy(stats, a->s_work_counts.as<unsigned long long>() + 8, 16, hipMemcpyDeviceToHost));
+  HIPCHK(a, hipMemcpy(stats, a->s_work_counts + 8, 16, hipMemcpyDeviceToHost));
   return THM_OK;
 }
 // thm_debug_seed_direct_stats: [0] the device copy of the k-mer table holds text positions (lut_direct.h; 0 under
@@ -611,7 +620,7 @@ int32_t thm_debug_seed_direct_stats(thm_aligner* a, uint64_t stats[4]) {
   if (!a->s_work_counts.p || a->s_work_counts.cap < 128) return THM_OK;
   HIPCHK(a, hipSetDevice(a->device));
   HIPCHK(a, hipStreamSynchronize(a->stream));
-  HIPCHK(a, hipMemcpy(stats + 2, a->s_work_counts.as<unsigned long long>() + 10, 16, hipMemcpyDeviceToHost));
+  HIPCHK(a, hipMemcpy(stats + 2, a->s_work_counts + 10, 16, hipMemcpyDeviceToHost));
   return THM_OK;
 }
 // test hook: the device copy of the k-mer table as the kernels read it, `bytes` = 4^kt entries of two coordinates
@@ -675,7 +684,7 @@ int32_t thm_debug_calib_gather(thm_aligner* a, int32_t pattern, uint64_t n_threa
   HIPCHK(a, hipSetDevice(a->device));
   const uint64_t span = a->dix->lut.cap & ~255ull;
   if (span < 4096) return fail(a, THM_ERR_INVALID_ARG, "k-mer table too small for the calibration gather");
-  HIPCHK(a, launch_calib_gather(a->dix->lut.as<uint8_t>(), span, n_threads, pattern, a->d_cursors.as<unsigned long long>() + 4, a->stream));
+  HIPCHK(a, launch_calib_gather(a->dix->lut.as<uint8_t>(), span, n_threads, pattern, a->d_cursors + 4, a->stream));
   HIPCHK(a, hipStreamSynchronize(a->stream));
   if (bytes_requested) *bytes_requested = n_threads * (pattern == 0 ? 8 : (pattern == 1 ? 4 : 16));
   return THM_OK;

@@ -12,11 +12,11 @@
 #include "launch.h"
 #include "thermite_internal.h"
 
-// Ownership: a DBuf, an HBuf, an Event and a Stream each free what they hold when they are destroyed, and none of them
-// can be copied, so `delete` of the struct that holds them (thm_aligner, thm_index::DevCopy) is the whole clean-up and a
+// Ownership: a DBuf, an HBuf (and their typed forms DArr<T>, HArr<T>), an Event and a Stream each free what they hold when
+// they are destroyed, and none of them can be copied, so `delete` of the struct that holds them (thm_aligner, thm_index::DevCopy) is the whole clean-up and a
 // new member needs no entry anywhere.
 
-// grow-only device buffer
+// grow-only device buffer of bytes: for what holds more than one element type (a DArr otherwise)
 struct DBuf {
   void* p = nullptr;
   size_t cap = 0;
@@ -43,17 +43,16 @@ struct DBuf {
   }
 };
 
-// a fixed part of another DBuf (the control block's words): same accessors, nothing to grow or free
+// a fixed part of another DBuf (the control block's words) of one element type: stands where a T* is wanted, nothing
+// to grow or free
+template <class T>
 struct DView {
-  void* p = nullptr;
-  size_t cap = 0;
-  template <class T>
-  T* as() const {
-    return (T*)p;
-  }
+  T* p = nullptr;
+  size_t cap = 0;  // bytes
+  operator T*() const { return p; }
 };
 
-// grow-only pinned host buffer (results land here: D2H at full PCIe rate, no value-initialisation)
+// grow-only pinned host buffer of bytes (results land here: D2H at full PCIe rate, no value-initialisation)
 struct HBuf {
   void* p = nullptr;
   size_t cap = 0;
@@ -79,8 +78,37 @@ struct HBuf {
     return (T*)p;
   }
 };
+
+// A DBuf / an HBuf of one element type: sized in elements, stands where a T* is wanted.  `slack_bytes` is what a kernel may
+// read or write behind the last element (the comments at the members say which); it is asked for as it is written, so
+// that ensure(count, slack) requests exactly what ensure(count * sizeof(T) + slack) of the byte buffer does.
+template <class T, class Bytes>
+struct ArrOf {
+  Bytes b;
+  hipError_t ensure(size_t count, size_t slack_bytes = 0) { return b.ensure(count * sizeof(T) + slack_bytes); }
+  void release() { b.release(); }
+  T* get() const { return (T*)b.p; }
+  operator T*() const { return get(); }
+  size_t cap() const { return b.cap; }  // bytes
+};
+template <class T>
+using DArr = ArrOf<T, DBuf>;
+template <class T>
+using HArr = ArrOf<T, HBuf>;
 static_assert(!std::is_copy_constructible_v<DBuf> && !std::is_copy_assignable_v<DBuf>, "one owner per device allocation");
 static_assert(!std::is_copy_constructible_v<HBuf> && !std::is_copy_assignable_v<HBuf>, "one owner per pinned allocation");
+static_assert(!std::is_copy_constructible_v<DArr<int>> && !std::is_copy_assignable_v<DArr<int>>, "one owner per device allocation");
+static_assert(!std::is_copy_constructible_v<HArr<int>> && !std::is_copy_assignable_v<HArr<int>>, "one owner per pinned allocation");
+
+// Two sets of pinned results used alternately, so that the view a fetch returned stays valid while the next batch is
+// uploaded, run and fetched: next() is the set that does not back the previous view.
+template <class Set>
+struct Alternating {
+  Set set[2];
+  int cur = 0;
+  Set& next() { return set[cur ^= 1]; }
+  Set& current() { return set[cur]; }
+};
 
 // an event of the aligner's: made by the first ensure(), passed to the HIP calls as the hipEvent_t it holds
 struct Event {
@@ -134,13 +162,19 @@ struct Stream {
 
 struct thm_index::DevCopy {
   int device = -1;
-  DBuf text, sa, lut, refs, name_rank, ref_recs, ref_bin, txs, exons, exon_txoff, tx_seq, exon_grid_off, exon_grid, gene_grid_off, gene_grid;
+  DArr<uint8_t> text, tx_seq;
+  DArr<thm_ref> refs;
+  DArr<thm_tx> txs;
+  DArr<thm_exon> exons;
+  DArr<uint64_t> exon_txoff;
+  DArr<uint32_t> name_rank, ref_bin, exon_grid_off, gene_grid_off;
+  DBuf sa, lut, ref_recs, exon_grid, gene_grid;  // of the coordinate type of the valid view
   bool wide = false;                     // which of the two views is valid (thermite_internal.h, "Coordinate width")
   // lut_direct.h: the pass that runs once behind the upload put text positions into the single-suffix entries of `lut`
   // (THM_LUT_DIRECT=0, or a 32-bit table over 2^31 symbols or more: plain); how many entries it rewrote
   bool lut_direct = false;
   uint64_t lut_tagged = 0;
-  DBuf lut_cnt;                          // the pass's counter (one u64)
+  DArr<unsigned long long> lut_cnt;      // the pass's counter (one u64)
   thm::DeviceIndexT<uint32_t> view;
   thm::DeviceIndexT<uint64_t> view64;
 };
@@ -154,6 +188,20 @@ inline void free_dev_copy(thm_index::DevCopy* d) {
   (void)hipSetDevice(cur);
 }
 
+namespace thm {
+namespace inf {
+struct Member;
+}
+namespace gz {
+struct State;
+struct Run;
+struct End;
+struct Summary;
+}  // namespace gz
+}  // namespace thm
+
+// ---- the aligner's state, a struct per stage, each named after the host file that works on it ----
+
 // The opt-in problem-parallel path of the extend stage (pipeline_tpr.hip; kernels_tpr.hip: thread-per-read control kernel
 // + wave-per-request DP kernels, in rounds, ahead of the wave-per-read kernels, which take what is left): everything only
 // that path uses.  THM_TPR=1 or thm_debug_set_flags turn it on; THM_TPR_ROUNDS = 1..8.
@@ -164,9 +212,200 @@ struct TprState {
   Stream stream3;  // the wave-per-read and team kernels run beside the rounds
   Stream stream4;  // the thread-per-problem DP kernel of a round runs beside the wave-per-problem one
   Event ev_join3, ev_dpt_fork, ev_dpt_join;  // untimed, made by thm_aligner_create
-  DBuf t_memos, t_recs, t_dpops, t_qlist, t_act[2], t_ctl, t_bail, t_queue2, t_trace, t_ttrace, t_hdr, t_sums;
+  DArr<thm::ReadMemo> t_memos;
+  DArr<thm::DpRec> t_recs;
+  DArr<uint32_t> t_qlist, t_act[2];
+  DArr<unsigned long long> t_bail;
+  DArr<unsigned int> t_queue2;
+  DArr<thm::HitHdr> t_hdr;
+  DArr<thm::HitSum> t_sums;
+  DBuf t_ctl;    // u64 cursors and statistics, then the rounds' u32 work words
+  DBuf t_trace;  // sized in bytes per wave
   bool use_tpr = false;  // (until the path is the faster one on the headline workload)
   int tpr_rounds = 8;
+};
+
+// pipeline.hip: the batch on the device
+struct ReadsState {
+  DArr<uint8_t> bases, san;   // raw reads; upper-cased + sanitised copy (made by every run)
+  DArr<uint64_t> offsets;
+  DArr<int32_t> status;       // per-read status, zeroed by every run
+};
+
+// pipeline.hip: the seed stage
+struct SeedState {
+  DBuf smems, ms_lo, ms_hi;  // of the index's coordinate type
+  DArr<uint64_t> off, hits, cand_off;
+  DArr<uint32_t> cnt;
+  // the pipeline's own scan scratch: plan_pack_kernel reads the tile offsets launch_scan_tiles_sums_u64 leaves in it
+  DArr<uint64_t> scan_tmp;
+  DArr<uint16_t> ms_end, fill_keys;
+  DArr<unsigned long long> work_reads, work_long, work_cells, heavy, slow, team;
+  DArr<uint8_t> sel_scratch;
+  DArr<uint32_t> fill_perm;
+  DArr<unsigned int> fill_hist;
+  uint64_t smem_cap = 0;
+};
+
+// pipeline.hip: the extend stage and the compact stage's lists
+struct ExtendState {
+  DArr<uint64_t> heavy;  // compact stage: lists of reads with many alignments ...
+  DArr<uint32_t> rel;    // ... and the op offsets of their alignments
+  DArr<thm::Cand> cands;
+  DArr<uint32_t> order, nalns;
+  DArr<uint8_t> ops, slow;
+  DArr<uint64_t> opbytes, aln_off, ops_off;
+  DBuf trace;  // sized in bytes (the plan's slices)
+  DBuf recs;   // ReadRecT of the index's coordinate type
+  // wcnt (the waves' counter rows) is zero from end to end between runs: launch_counters_reduce zeroes what it read, so
+  // only a new allocation is zeroed by the host.  The capacity that is known clean (0 while a run's launches are being
+  // enqueued: an enqueue that fails half way leaves rows nobody reduced)
+  DArr<unsigned long long> wcnt;
+  size_t wcnt_clean_cap = 0;
+  DArr<unsigned long long> finstats;  // the finisher's per-workgroup statistics
+  uint64_t cand_cap = 0, cand_ops_cap = 0;
+};
+
+// host results of the read-level path (thm_batch_fetch)
+struct BatchHost {
+  HArr<uint64_t> off;
+  HArr<thm_aln> alns;
+  HArr<uint8_t> ops;
+  HArr<int32_t> stat;
+};
+// pipeline.hip: the compacted outputs and where thm_batch_fetch lands them
+struct OutputState {
+  DArr<thm_aln> alns;
+  DArr<uint8_t> ops;
+  DArr<thm_mem> mems;
+  // alns_cap, ops_cap: cand_cap and cand_ops_cap as the last enqueued run had them, which is what a fetch checks the
+  // batch against (thm_debug_set_pool_caps zeroes those two for the next run while this one's views are still being fetched)
+  uint64_t alns_cap = 0, ops_cap = 0;
+  Alternating<BatchHost> host;
+};
+
+// per-hit entry point (seed_hits.hip): device buffers
+struct SeedHitState {
+  DArr<uint8_t> bases, san, ops, slow;
+  DArr<uint64_t> off;
+  DArr<thm_mem> hits;
+  DArr<uint32_t> read, bw, list;
+  DArr<int32_t> xd, status;
+  DArr<thm_aln> out;
+  DArr<unsigned long long> ctl;
+  DBuf trace;  // sized in bytes per wave
+};
+
+// CIGAR entry points (cigar.hip): per-stream sums and word counts, their scan, digests and words on the device; the
+// uploaded streams of thm_cigar_encode_batch; two pinned host sets of thm_batch_fetch_cigars, used alternately and
+// apart from OutputState::host, so that neither fetch invalidates the other's view
+struct CigarHost {
+  HArr<uint64_t> off;
+  HArr<thm_aln> alns;
+  HArr<thm_aln_digest> dig;
+  HArr<uint32_t> words;
+  HArr<int32_t> stat;
+};
+struct CigarState {
+  DArr<thm::CigarSum> sums;
+  DArr<uint64_t> nwords, woff, in_off;
+  DArr<unsigned int> flags;
+  DArr<thm_aln_digest> dig;
+  DArr<uint32_t> words;
+  DArr<uint8_t> in_ops;
+  Alternating<CigarHost> host;
+  Event ev[4];  // made by the first call
+  std::vector<thm_aln_digest> h_dig;
+  std::vector<uint32_t> h_words;
+};
+
+// BAM records on the device (bam.hip): names and qualities of the batch (thm_batch_upload_reads), the index's name
+// tables (uploaded by the first thm_batch_fetch_bam), work arrays of the passes, the records, and two pinned host
+// sets of their own, used alternately
+struct BytesHost {  // (also the set of BgzfState)
+  HArr<uint8_t> data;
+  HArr<uint64_t> off;
+  HArr<int32_t> stat;
+};
+struct BamState {
+  DArr<uint8_t> names, quals;
+  DArr<uint64_t> name_off;
+  bool reads_named = false, reads_have_quals = false;  // thm_batch_upload clears reads_named
+  DArr<uint8_t> tx_pool, gid_pool, gname_pool;
+  DArr<uint32_t> tx_off, gid_off, gname_off, tx_gene;
+  DArr<int32_t> ref_sq;
+  bool tables = false;
+  DArr<uint64_t> cnt, first, len, off, read_off;
+  DArr<uint32_t> qn, rec_read;
+  DArr<uint8_t> out;
+  DArr<unsigned int> err;
+  Alternating<BytesHost> host;
+  int stage = -1;  // emit through LDS and dword stores (1) or byte stores (0); -1: not read from THM_BAM_EMIT yet
+  Event ev[4];  // made by the first call
+};
+
+// BGZF members on the device (bgzf.hip): per-position scratch of the workgroups, the members in their slots, their
+// sizes and the scan, the members behind one another; the bytes thm_debug_bgzf_device uploads; two pinned host sets
+// of their own, used alternately
+struct BgzfState {
+  DArr<uint32_t> match;
+  DArr<uint8_t> slots, out, dbg_in;
+  DArr<uint64_t> sizes, off;
+  Alternating<BytesHost> host;
+  Event ev[2];  // made by the first call
+};
+
+// FASTQ blocks parsed on the device (fastq.hip): the block's bytes, newline counts per chunk and their scan, the line
+// starts, the records' lengths and the flag word; the offsets come back into h_off for the length classes.  The
+// blocks that went either way since the aligner was created (thm_debug_fastq_device_blocks).  One pinned set behind
+// thm_batch_fetch_reads.
+struct FastqState {
+  DBuf raw;  // the block as bytes; the device inflaters build it here (gz::Job::out, InflateParams::out)
+  DArr<uint64_t> cnt, base, lines, name_len, seq_len;
+  DArr<unsigned int> flag;
+  HArr<uint64_t> h_off;
+  uint64_t on_device = 0, on_host = 0;
+  Event ev[6];  // made by the first call
+  struct {
+    HArr<uint8_t> bases, quals, names;
+    HArr<uint64_t> off, name_off;
+  } back;  // thm_batch_fetch_reads
+};
+
+// BGZF members inflated on the device (inflate.hip): the members' bytes, the host's table of them and their status
+// words (the table and the statuses in pinned memory too); the inflated block is built in fq.raw.  Two tail buffers,
+// used alternately; the block on the host where the host inflated or parsed it.  Counts for
+// thm_debug_fastq_bgzf_blocks: inflates on device / on host, parses on device / on host.
+struct InflateState {
+  DArr<uint8_t> in;
+  DArr<thm::inf::Member> tab;
+  DArr<uint32_t> status;
+  HArr<thm::inf::Member> h_tab;
+  HArr<uint32_t> h_status;
+  HArr<uint8_t> h_last;
+  Alternating<HArr<uint8_t>> tail;
+  std::vector<uint8_t> block;
+  uint64_t counts[4] = {0, 0, 0, 0};
+  Event ev[2];  // made by the first call
+};
+
+// plain gzip inflated on the device (gzip.hip; the arrays of gz::Job, gzip_device.h): the compressed bytes, both
+// states, candidates, runs, member ends, symbol regions, windows and what the chain derives; summary and outgoing
+// state in pinned memory too.  The inflated block is built in fq.raw and the tail buffers are fz.tail.  Counts for
+// thm_debug_fastq_gzip_blocks, as fz.counts.
+struct GzipState {
+  DArr<uint8_t> in, windows;
+  DArr<thm::gz::State> state;
+  DArr<uint64_t> cand, run_off, end_abs;
+  DArr<thm::gz::Run> runs;
+  DArr<thm::gz::End> ends;
+  DArr<uint16_t> syms;
+  DArr<uint32_t> run_list, end_crc, end_isize, member_crc;
+  DArr<thm::gz::Summary> sum;
+  HArr<thm::gz::Summary> h_sum;
+  HArr<thm::gz::State> h_state;
+  uint64_t counts[4] = {0, 0, 0, 0};
+  Event ev[2];  // made by the first call
 };
 
 struct thm_aligner {
@@ -186,22 +425,25 @@ struct thm_aligner {
   thm_align_opts run_opts;
   std::string err;
 
-  DBuf d_counters;
+  DArr<unsigned long long> d_counters;  // three rows of THM_N_COUNTERS: the counters, their snapshot, the profile clocks
   // Control block: every word a run of the read-level pipeline wants zeroed when it starts, side by side, so that the
   // run's first kernel zeroes them in one go (launch.h, RunResetParams).  The views below are its parts.
   DBuf d_ctl;
   static constexpr size_t CTL_WORK_COUNTS = 0, CTL_CURSORS = 128, CTL_FAULT = 192, CTL_QUEUE = 256,
                           CTL_QUEUE_EXT = CTL_QUEUE + thm::QUEUE_BYTES, CTL_BYTES = CTL_QUEUE_EXT + thm::QUEUE_BYTES;
   static_assert(CTL_BYTES % 16 == 0 && thm::QUEUE_BYTES % 16 == 0, "the block is zeroed 16 bytes at a time");
-  DView d_queue;      // work counters of the seed stage's selection kernel and of the operator-level calls
-  DView d_queue_ext;  // ... of the extend stage: its own words, so that one reset serves both stages of a run
-  DView d_fault, d_cursors;  // cursors: [0] smem pool head, [1] op pool head (u64 each)
-  DView s_work_counts;       // list lengths of the seed stage and of the plan kernel (16 u64)
+  DView<unsigned int> d_queue;      // work counters of the seed stage's selection kernel and of the operator-level calls
+  DView<unsigned int> d_queue_ext;  // ... of the extend stage: its own words, so that one reset serves both stages of a run
+  DView<int> d_fault;
+  DView<unsigned long long> d_cursors;      // cursors: [0] smem pool head, [1] op pool head (u64 each)
+  DView<unsigned long long> s_work_counts;  // list lengths of the seed stage and of the plan kernel (16 u64)
   DBuf b0, b1, b2, b3, b4, b5, b6, b7, b8;       // operator-level scratch
+  // scratch of the exclusive scans of the stages behind the pipeline (cigar, bam, bgzf, fastq: scan_u64 below), which
+  // run on `stream` one after the other
+  DArr<uint64_t> stage_scan_tmp;
 
   // ---- read-level pipeline ----
-  DBuf r_bases, r_offsets, r_san;  // raw reads, offsets, upper-cased + sanitised copy (made by every run)
-  DBuf r_status;                   // per-read status (i32), zeroed by every run
+  ReadsState reads;
   uint64_t n_reads = 0, n_bases = 0;
   uint32_t max_read_len = 0;
   // lengths present in the batch, ascending, with their read counts (thm_batch_upload): the length classes of a
@@ -209,25 +451,11 @@ struct thm_aligner {
   std::vector<std::pair<uint32_t, uint64_t>> len_hist;
   uint64_t n_over = 0;  // reads longer than MAX_READ_LEN (per-read status THM_ERR_UNSUPPORTED)
   bool uploaded = false;
-  // seeds
-  DBuf s_smems, s_off, s_cnt, s_hits, s_cand_off, scan_tmp, s_ms_end, s_ms_lo, s_ms_hi, s_work_reads, s_work_long, s_work_cells,
-      s_sel_scratch, s_heavy, s_slow, s_team, s_fill_keys, s_fill_perm, s_fill_hist;
-  uint64_t smem_cap = 0;
-  // extension
-  DBuf e_heavy, e_rel;  // compact stage: lists of reads with many alignments, op offsets of their alignments
-  DBuf e_cands, e_order, e_ops, e_nalns, e_opbytes, e_aln_off, e_ops_off, e_trace, e_slow, e_recs, e_wcnt;
-  // e_wcnt (the waves' counter rows) is zero from end to end between runs: launch_counters_reduce zeroes what it read, so
-  // only a new allocation is zeroed by the host.  The capacity that is known clean (0 while a run's launches are being
-  // enqueued: an enqueue that fails half way leaves rows nobody reduced)
-  size_t wcnt_clean_cap = 0;
+  SeedState seed;
+  ExtendState ext;
   uint64_t n_slow_host = 0;     // reads of the slow class in the last enqueue (host count)
   uint32_t fast_max_len = 0, slow_max_len = 0;
-  uint64_t cand_cap = 0, cand_ops_cap = 0;
-  // compacted outputs
-  DBuf o_alns, o_ops, o_mems;
-  // out_alns_cap, out_ops_cap: cand_cap and cand_ops_cap as the last enqueued run had them, which is what a fetch checks the
-  // batch against (thm_debug_set_pool_caps zeroes those two for the next run while this one's views are still being fetched)
-  uint64_t out_alns_cap = 0, out_ops_cap = 0;
+  OutputState out;
   // test hook (thm_debug_set_pool_caps): initial pool sizes instead of the heuristics, to force the grow-and-replay path
   uint64_t dbg_smem_cap = 0, dbg_cand_cap = 0, dbg_ops_cap = 0;
   uint32_t dbg_band_clip = 0;  // test hook (thm_debug_set_band_clip): pretend the fast class holds bands up to this only (0: off)
@@ -237,23 +465,18 @@ struct thm_aligner {
   // ... bit 6: a probe into a single-suffix bucket reads sa[lo] although the table entry holds the text position
   bool dbg_seed_nodirect = false;
   // The finisher (kernels_finish.hip): classes it takes (thm_debug_set_flags bits 12..15; fin::CLASS_E | fin::CLASS_S), the
-  // read-only op run at the front of e_ops (where it was written and for which read length, 0: none; while it exists every
-  // run starts the pool's cursor behind it), the classes and workgroups of the last enqueue, its per-workgroup statistics
+  // read-only op run at the front of ext.ops (where it was written and for which read length, 0: none; while it exists every
+  // run starts the pool's cursor behind it), the classes and workgroups of the last enqueue (its statistics: ext.finstats)
   uint32_t fin_classes = 3;
   const void* ops_run_ptr = nullptr;
   size_t ops_run_cap = 0;
   uint32_t ops_run_half = 0;
   uint32_t fin_run_classes = 0, fin_blocks = 0;
-  DBuf e_finstats;
   uint32_t n_replays = 0;  // pool-overflow replays since the aligner was created
   bool ran = false, synced = false;
   Event ev[6];  // made by thm_aligner_create
   float timings[THM_N_TIMINGS] = {0};
 
-  // host results of the read-level path: two pinned sets used alternately, so that the view
-  // thm_batch_fetch returned stays valid while the next batch is uploaded, run and fetched
-  HBuf r_off[2], r_alns[2], r_ops[2], r_stat[2];
-  int r_cur = 0;
   // host results of the operator- and seed-level calls
   std::vector<uint64_t> h_off;
   std::vector<thm_aln> h_alns;
@@ -261,67 +484,18 @@ struct thm_aligner {
   std::vector<thm_mem> h_mems;
   std::vector<thm_swg_aln> h_swg;
   std::vector<thm_lr_aln> h_lr;
-  // per-hit entry point (seed_hits.hip): device buffers and the host result its view points into
-  DBuf sh_bases, sh_san, sh_off, sh_hits, sh_read, sh_bw, sh_xd, sh_list, sh_out, sh_status, sh_ops, sh_ctl, sh_trace, sh_slow;
+  // per-hit entry point: the host result its view points into
+  SeedHitState sh;
   std::vector<thm_aln> h_hit_alns;
   std::vector<int32_t> h_hit_status;
   std::vector<uint8_t> h_hit_ops;
-  // CIGAR entry points (cigar.hip): per-stream sums and word counts, their scan, digests and words on the device; the
-  // uploaded streams of thm_cigar_encode_batch; two pinned host sets of thm_batch_fetch_cigars, used alternately and
-  // apart from r_off .. r_stat, so that neither fetch invalidates the other's view
-  DBuf c_sums, c_nwords, c_woff, c_scan_tmp, c_flags, c_dig, c_words, c_in_ops, c_in_off;
-  HBuf ch_off[2], ch_alns[2], ch_dig[2], ch_words[2], ch_stat[2];
-  int c_cur = 0;
-  Event ev_cig[4];  // made by the first call
-  std::vector<thm_aln_digest> h_cig_dig;
-  std::vector<uint32_t> h_cig_words;
-  // BAM records on the device (bam.hip): names and qualities of the batch (thm_batch_upload_reads), the index's name
-  // tables (uploaded by the first thm_batch_fetch_bam), work arrays of the passes, the records, and two pinned host
-  // sets of their own, used alternately
-  DBuf bn_names, bn_name_off, bn_quals;
-  bool reads_named = false, reads_have_quals = false;  // thm_batch_upload clears reads_named
-  DBuf bt_tx_pool, bt_tx_off, bt_gid_pool, bt_gid_off, bt_gname_pool, bt_gname_off, bt_tx_gene, bt_ref_sq;
-  bool bam_tables = false;
-  DBuf bm_cnt, bm_first, bm_qn, bm_rec_read, bm_len, bm_off, bm_out, bm_read_off, bm_err, bm_scan_tmp;
-  HBuf bh_data[2], bh_off[2], bh_stat[2];
-  int b_cur = 0;
-  int bam_stage = -1;  // emit through LDS and dword stores (1) or byte stores (0); -1: not read from THM_BAM_EMIT yet
-  Event ev_bam[4];  // made by the first call
-  // BGZF members on the device (bgzf.hip): per-position scratch of the workgroups, the members in their slots, their
-  // sizes and the scan, the members behind one another; the bytes thm_debug_bgzf_device uploads; two pinned host sets
-  // of their own, used alternately
-  DBuf bz_match, bz_slots, bz_sizes, bz_off, bz_out, bz_scan_tmp, bz_dbg_in;
-  HBuf zh_data[2], zh_off[2], zh_stat[2];
-  int z_cur = 0;
-  Event ev_bgzf[2];  // made by the first call
-  // FASTQ blocks parsed on the device (fastq.hip): the block's bytes, newline counts per chunk and their scan, the line
-  // starts, the records' lengths and the flag word; the offsets come back into fq_h_off for the length classes.  The
-  // blocks that went either way since the aligner was created (thm_debug_fastq_device_blocks).  One pinned set behind
-  // thm_batch_fetch_reads.
-  DBuf fq_raw, fq_cnt, fq_base, fq_lines, fq_name_len, fq_seq_len, fq_flag, fq_scan_tmp;
-  HBuf fq_h_off;
-  uint64_t fq_on_device = 0, fq_on_host = 0;
-  Event ev_fq[6];  // made by the first call
-  HBuf fr_bases, fr_off, fr_quals, fr_names, fr_name_off;
-  // BGZF members inflated on the device (inflate.hip): the members' bytes, the host's table of them and their status
-  // words (the table and the statuses in pinned memory too); the inflated block is built in fq_raw.  Two tail buffers,
-  // used alternately; the block on the host where the host inflated or parsed it.  Counts for
-  // thm_debug_fastq_bgzf_blocks: inflates on device / on host, parses on device / on host.
-  DBuf fz_in, fz_tab, fz_status;
-  HBuf fz_h_tab, fz_h_status, fz_tail[2], fz_h_last;
-  int fz_cur = 0;
-  std::vector<uint8_t> fz_block;
-  uint64_t fz_counts[4] = {0, 0, 0, 0};
-  Event ev_fz[2];  // made by the first call
-  // plain gzip inflated on the device (gzip.hip; the arrays of gz::Job, gzip_device.h): the compressed bytes, both
-  // states, candidates, runs, member ends, symbol regions, windows and what the chain derives; summary and outgoing
-  // state in pinned memory too.  The inflated block is built in fq_raw and the tail buffers are fz_tail.  Counts for
-  // thm_debug_fastq_gzip_blocks, as fz_counts.
-  DBuf gz_in, gz_state, gz_cand, gz_runs, gz_ends, gz_syms, gz_windows, gz_run_list, gz_run_off, gz_end_abs, gz_end_crc, gz_end_isize,
-      gz_member_crc, gz_sum;
-  HBuf gz_h_sum, gz_h_state;
-  uint64_t gz_counts[4] = {0, 0, 0, 0};
-  Event ev_gz[2];  // made by the first call
+  // ---- the stages behind the pipeline ----
+  CigarState cig;
+  BamState bam;
+  BgzfState bgzf;
+  FastqState fq;
+  InflateState fz;
+  GzipState gz;
 };
 
 inline int fail(thm_aligner* a, int code, const char* fmt, ...) {
@@ -343,22 +517,41 @@ inline int fail(thm_aligner* a, int code, const char* fmt, ...) {
                   #call, hipGetErrorString(e_), __FILE__, __LINE__);                                \
   } while (0)
 
-// cigar.hip: count -> scan -> emit over the streams of `p`; results in c_dig / c_words (synchronises the stream once)
+// ---- the exclusive scan of counts every stage runs: counts -> offsets, the total behind them in out[n]
+// `scratch` with room for a scan of n entries (a caller that keeps a scratch of its own sizes it for its longest scan)
+inline hipError_t scan_reserve(DArr<uint64_t>& scratch, uint64_t n) { return scratch.ensure(thm::scan_tmp_entries(n + 1), 64); }
+// out[0 .. n] = exclusive scan of in[0, n) on `s`, through `scratch`, which grows as the scan needs
+inline int scan_u64(thm_aligner* a, DArr<uint64_t>& scratch, const uint64_t* in, uint64_t* out, uint64_t n, hipStream_t s) {
+  HIPCHK(a, scan_reserve(scratch, n));
+  HIPCHK(a, thm::launch_exclusive_scan_u64(in, out, n, scratch, s));
+  return THM_OK;
+}
+// ... and the total on its way into *h_total, which holds it once the caller has synchronised `s`
+template <class W>
+inline int scan_u64(thm_aligner* a, DArr<uint64_t>& scratch, const uint64_t* in, uint64_t* out, uint64_t n, hipStream_t s, W* h_total) {
+  static_assert(sizeof(W) == 8, "the total is a 64-bit word");
+  const int rc = scan_u64(a, scratch, in, out, n, s);
+  if (rc != THM_OK) return rc;
+  HIPCHK(a, hipMemcpyAsync(h_total, out + n, 8, hipMemcpyDeviceToHost, s));
+  return THM_OK;
+}
+
+// cigar.hip: count -> scan -> emit over the streams of `p`; results in cig.dig / cig.words (synchronises the stream once)
 int run_cigar_passes(thm_aligner* a, thm::CigarParams p, uint64_t n_digests, uint64_t* n_words, unsigned* any_flags);
-// bam.hip: everything of thm_batch_fetch_bam up to the copies -- after it the records of the run are in bm_out on the
-// device and the per-read byte offsets in bm_read_off (both fetches that hand records out start here; the messages name
+// bam.hip: everything of thm_batch_fetch_bam up to the copies -- after it the records of the run are in bam.out on the
+// device and the per-read byte offsets in bam.read_off (both fetches that hand records out start here; the messages name
 // thm_batch_fetch_bam whichever it is).  Of the timings only `timing`, the caller's own, is touched: zeroed once the
-// arguments have passed; ev_bam[0..3] are left recorded around the size and emit passes.
+// arguments have passed; bam.ev[0..3] are left recorded around the size and emit passes.
 struct BamOnDevice {
   uint64_t n_reads = 0, n_alns = 0, n_records = 0, n_bytes = 0;
   bool any_failed = false;  // as in BatchSizes
 };
 int bam_records_on_device(thm_aligner* a, uint32_t flags, int timing, BamOnDevice* r);
-// bam.hip: the index's name tables, tx -> gene (bt_tx_gene) and ref -> BAM refID (bt_ref_sq) on the device, once per aligner
+// bam.hip: the index's name tables, tx -> gene (bam.tx_gene) and ref -> BAM refID (bam.ref_sq) on the device, once per aligner
 // (the aligner's device is current).  THM_ERR_INVALID_ARG: an index without names.  quant.hip counts from the last two.
 int bam_tables_on_device(thm_aligner* a);
-// bgzf.hip: d_in[0, n) (device, 4-byte aligned) cut every 0xff00 bytes and deflated -> the members back to back in bz_out,
-// their offsets in bz_off[0 .. *n_blocks]; synchronises the stream once and sets THM_T_BGZF (bam_sort.hip deflates the
+// bgzf.hip: d_in[0, n) (device, 4-byte aligned) cut every 0xff00 bytes and deflated -> the members back to back in bgzf.out,
+// their offsets in bgzf.off[0 .. *n_blocks]; synchronises the stream once and sets THM_T_BGZF (bam_sort.hip deflates the
 // windows of the sorted stream through it)
 int bgzf_range_on_device(thm_aligner* a, const uint8_t* d_in, uint64_t n, uint64_t* n_blocks, uint64_t* n_bytes);
 // ---- pipeline.hip: the head and the tail of every fetch entry point (after thm_batch_sync; a new one calls all of them)
@@ -366,20 +559,20 @@ struct BatchSizes {
   uint64_t n_alns = 0, n_ops = 0;  // alignments and op bytes of the compacted batch, checked against the pools
   bool any_failed = false;         // a read of the batch may have failed: the statuses are worth copying
 };
-// One round trip (a single synchronisation of the stream): e_aln_off[n], e_ops_off[n] and the device's count of
+// One round trip (a single synchronisation of the stream): ext.aln_off[n], ext.ops_off[n] and the device's count of
 // out-of-contract reads.  With `h_off` the whole offsets array comes into it, (n + 2) words with the op bytes last; with
 // `d_extra` that device word comes into *extra.
-int fetch_batch_sizes(thm_aligner* a, HBuf* h_off, const uint64_t* d_extra, uint64_t* extra, BatchSizes* z);
-// r_status on its way into `h_stat` where any_failed says so; after the next synchronisation failed_reads fills the two
+int fetch_batch_sizes(thm_aligner* a, HArr<uint64_t>* h_off, const uint64_t* d_extra, uint64_t* extra, BatchSizes* z);
+// reads.status on its way into `h_stat` where any_failed says so; after the next synchronisation failed_reads fills the two
 // fields of a view from it: the count of reads that failed, and the statuses where there is one (else null)
-int enqueue_statuses(thm_aligner* a, bool any_failed, HBuf& h_stat);
-void failed_reads(const thm_aligner* a, bool any_failed, const HBuf& h_stat, uint64_t* n_failed, const int32_t** status);
+int enqueue_statuses(thm_aligner* a, bool any_failed, HArr<int32_t>& h_stat);
+void failed_reads(const thm_aligner* a, bool any_failed, const HArr<int32_t>& h_stat, uint64_t* n_failed, const int32_t** status);
 // the two op streams of every alignment in the compacted pool, for run_cigar_passes
 thm::CigarParams compacted_cigar_params(const thm_aligner* a, const BatchSizes& z);
 // pipeline.hip: what thm_batch_upload derives from the offsets of a batch -- n_reads, n_bases, max_read_len, the length
 // classes (len_hist) and n_over -- for every upload path; THM_ERR_INVALID_ARG for offsets that do not start at 0 or descend
 int batch_length_classes(thm_aligner* a, const uint64_t* offsets, uint64_t n_reads);
-// fastq.hip: the device FASTQ parse (count, starts, records, gather) of a block of n > 0 bytes that stands in fq_raw,
+// fastq.hip: the device FASTQ parse (count, starts, records, gather) of a block of n > 0 bytes that stands in fq.raw,
 // which the caller has sized to n + 64 -- put there by a copy (thm_batch_upload_fastq) or by the device inflater
 // (inflate.hip).  Three synchronisations of the stream, whichever it is.
 struct FastqBlock {
@@ -388,9 +581,9 @@ struct FastqBlock {
   bool whole = true;              // the batch is the whole block; false: its first 4 * (newlines / 4) lines
   const uint32_t* d_status = nullptr;  // status words of an inflate (device), checked at the first synchronisation
   uint64_t n_status = 0;
-  HBuf* tail = nullptr;  // where the bytes behind the batch go, in the copy-back the gather ends with (null: not wanted)
+  HArr<uint8_t>* tail = nullptr;  // where the bytes behind the batch go, in the copy-back the gather ends with (null: not wanted)
   // results
-  uint64_t bad_member = 0;  // FQ_NOT_INFLATED: the first member with a status other than 0 (the word is in fz_h_status)
+  uint64_t bad_member = 0;  // FQ_NOT_INFLATED: the first member with a status other than 0 (the word is in fz.h_status)
   uint64_t n_newlines = 0;
   uint64_t cut = 0;         // bytes of the batch (valid once the call returns 0 or 1)
   uint64_t n_reads = 0, n_bases = 0, n_name_bytes = 0;
@@ -402,7 +595,7 @@ enum { FQ_NOT_INFLATED = 2, FQ_NO_RECORD = 3 };  // beside 1 (parsed), 0 (declin
 struct FastqOutcome {
   uint64_t n_reads = 0, n_bases = 0, n_name_bytes = 0;
   uint64_t n_lines = 0;  // lines of the block that the batch consumed
-  const uint8_t* tail = nullptr;  // the block's bytes behind the batch (in the HBuf handed in)
+  const uint8_t* tail = nullptr;  // the block's bytes behind the batch (in the array handed in)
   uint64_t tail_len = 0;
   uint32_t parsed_on_device = 0;
   float parse_ms = 0;
@@ -417,30 +610,30 @@ struct FastqOutcome {
 namespace thm {
 int parse_resident(thm_aligner* a, FastqBlock& b);
 // fastq.hip, the finish the three entry points share.
-// A block that stands on the host: copied into fq_raw and parsed there (parse_resident's codes).  On 1 `o` holds the
+// A block that stands on the host: copied into fq.raw and parsed there (parse_resident's codes).  On 1 `o` holds the
 // counts and the cut, and the bytes behind it are in `tail` (null: the batch is the whole block).
-int parse_host_block(thm_aligner* a, const uint8_t* blk, uint64_t n, bool whole, HBuf* tail, FastqOutcome& o);
+int parse_host_block(thm_aligner* a, const uint8_t* blk, uint64_t n, bool whole, HArr<uint8_t>* tail, FastqOutcome& o);
 // The device parsed the batch: the aligner's batch state, and o.tail.
-void batch_parsed_on_device(thm_aligner* a, HBuf* tail, FastqOutcome& o);
+void batch_parsed_on_device(thm_aligner* a, HArr<uint8_t>* tail, FastqOutcome& o);
 // The host parser's batch of a block the device did not parse: the batch bytes -- all of the block for a last block or
 // with no `tail`, else up to fastq_host_cut -- through fastq_parse_block and thm_batch_upload_reads, the lines and the
 // tail into `o`; *on_host counts a batch that has bytes.  The parser's error goes into a->err and the global error.
 int host_parser_batch(thm_aligner* a, const uint8_t* blk, uint64_t n, const std::string& path, uint64_t first_line, bool last_block,
-                      HBuf* tail, uint64_t* on_host, FastqOutcome& o);
+                      HArr<uint8_t>* tail, uint64_t* on_host, FastqOutcome& o);
 }
 int reset_queue(thm_aligner* a);
 inline int grid_blocks(const thm_aligner* a, uint64_t n_items, int waves_per_block, int blocks_per_cu) {
   return thm::grid_blocks(a->n_cu, n_items, waves_per_block, blocks_per_cu);
 }
 // ---- the extend stage's launches (pipeline.hip, pipeline_tpr.hip) over one run's thm::ExtendPlan ----
-// where a launch's waves leave their counters: row `row` of e_wcnt (the plan's row_* offsets)
-inline unsigned long long* counter_rows(const thm_aligner* a, uint64_t row) { return a->e_wcnt.as<unsigned long long>() + row * THM_N_COUNTERS; }
+// where a launch's waves leave their counters: row `row` of ext.wcnt (the plan's row_* offsets)
+inline unsigned long long* counter_rows(const thm_aligner* a, uint64_t row) { return a->ext.wcnt + row * THM_N_COUNTERS; }
 // the team kernel's parameter block: `p` over the team list only, with the team's own counter rows and trace slices
 template <class C>
 thm::ExtendParamsT<C> team_params(const thm_aligner* a, const thm::ExtendPlan& plan, thm::ExtendParamsT<C> p) {
   p.list_only = 1;
   p.wave_counters = counter_rows(a, plan.row_team);
-  p.trace_scratch = a->e_trace.as<unsigned long long>() + plan.trace_team_off / 8;
+  p.trace_scratch = a->ext.trace.as<unsigned long long>() + plan.trace_team_off / 8;
   return p;
 }
 // pipeline_tpr.hip: the problem-parallel path's launches (plan.tpr), in place of the main and team launches of the default

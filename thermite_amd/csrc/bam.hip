@@ -9,13 +9,14 @@
 
 #include "aligner_internal.h"
 #include "io_internal.h"
+#include "launch_io.h"
 
 using namespace thm;
 
 namespace {
 
 // strings back to back with u32 offsets [n + 1]
-int upload_pool(thm_aligner* a, const std::vector<std::string>& v, DBuf& pool, DBuf& off) {
+int upload_pool(thm_aligner* a, const std::vector<std::string>& v, DArr<uint8_t>& pool, DArr<uint32_t>& off) {
   std::vector<uint32_t> o(v.size() + 1, 0);
   std::string all;
   for (size_t i = 0; i < v.size(); i++) {
@@ -23,10 +24,10 @@ int upload_pool(thm_aligner* a, const std::vector<std::string>& v, DBuf& pool, D
     if (all.size() >= 0xFFFFFFFFull) return fail(a, THM_ERR_UNSUPPORTED, "name table of 4 GiB or more");
     o[i + 1] = (uint32_t)all.size();
   }
-  HIPCHK(a, pool.ensure(all.size() + 16));
-  HIPCHK(a, off.ensure(o.size() * 4));
-  if (!all.empty()) HIPCHK(a, hipMemcpy(pool.p, all.data(), all.size(), hipMemcpyHostToDevice));
-  HIPCHK(a, hipMemcpy(off.p, o.data(), o.size() * 4, hipMemcpyHostToDevice));
+  HIPCHK(a, pool.ensure(all.size(), 16));
+  HIPCHK(a, off.ensure(o.size()));
+  if (!all.empty()) HIPCHK(a, hipMemcpy(pool, all.data(), all.size(), hipMemcpyHostToDevice));
+  HIPCHK(a, hipMemcpy(off, o.data(), o.size() * 4, hipMemcpyHostToDevice));
   return THM_OK;
 }
 
@@ -34,14 +35,14 @@ int upload_pool(thm_aligner* a, const std::vector<std::string>& v, DBuf& pool, D
 
 // the index's name tables, once per aligner
 int bam_tables_on_device(thm_aligner* a) {
-  if (a->bam_tables) return THM_OK;
+  if (a->bam.tables) return THM_OK;
   const thm_index* ix = a->ix;
   if (ix->contig_names.empty() || ix->tx_ids.size() != ix->txs.size() || ix->gene_ids.size() != ix->genes.size() ||
       ix->gene_names.size() != ix->genes.size())
     return fail(a, THM_ERR_INVALID_ARG, "thm_batch_fetch_bam needs contig / transcript / gene names: thm_index_set_names or thm_index_create_from_files");
-  int rc = upload_pool(a, ix->tx_ids, a->bt_tx_pool, a->bt_tx_off);
-  if (rc == THM_OK) rc = upload_pool(a, ix->gene_ids, a->bt_gid_pool, a->bt_gid_off);
-  if (rc == THM_OK) rc = upload_pool(a, ix->gene_names, a->bt_gname_pool, a->bt_gname_off);
+  int rc = upload_pool(a, ix->tx_ids, a->bam.tx_pool, a->bam.tx_off);
+  if (rc == THM_OK) rc = upload_pool(a, ix->gene_ids, a->bam.gid_pool, a->bam.gid_off);
+  if (rc == THM_OK) rc = upload_pool(a, ix->gene_names, a->bam.gname_pool, a->bam.gname_off);
   if (rc != THM_OK) return rc;
   std::vector<uint32_t> tx_gene(ix->txs.size() + 1, 0);
   for (size_t t = 0; t < ix->txs.size(); t++) tx_gene[t] = ix->txs[t].gene_idx;
@@ -49,11 +50,11 @@ int bam_tables_on_device(thm_aligner* a) {
   std::vector<int32_t> ref_sq(ix->refs.size() + 1, -1);
   for (size_t r = 0; r < ix->refs.size(); r++)
     if (ix->refs[r].name_id < sq_of_name.size()) ref_sq[r] = sq_of_name[ix->refs[r].name_id];
-  HIPCHK(a, a->bt_tx_gene.ensure(tx_gene.size() * 4));
-  HIPCHK(a, a->bt_ref_sq.ensure(ref_sq.size() * 4));
-  HIPCHK(a, hipMemcpy(a->bt_tx_gene.p, tx_gene.data(), tx_gene.size() * 4, hipMemcpyHostToDevice));
-  HIPCHK(a, hipMemcpy(a->bt_ref_sq.p, ref_sq.data(), ref_sq.size() * 4, hipMemcpyHostToDevice));
-  a->bam_tables = true;
+  HIPCHK(a, a->bam.tx_gene.ensure(tx_gene.size()));
+  HIPCHK(a, a->bam.ref_sq.ensure(ref_sq.size()));
+  HIPCHK(a, hipMemcpy(a->bam.tx_gene, tx_gene.data(), tx_gene.size() * 4, hipMemcpyHostToDevice));
+  HIPCHK(a, hipMemcpy(a->bam.ref_sq, ref_sq.data(), ref_sq.size() * 4, hipMemcpyHostToDevice));
+  a->bam.tables = true;
   return THM_OK;
 }
 
@@ -69,33 +70,33 @@ extern "C" int32_t thm_batch_upload_reads(thm_aligner* a, const thm_read_batch* 
   if (rc != THM_OK) return rc;
   hipStream_t s = a->stream;
   const uint64_t nn = reads->name_off[n], nb = reads->offsets[n];
-  HIPCHK(a, a->bn_names.ensure(nn + 16));
-  HIPCHK(a, a->bn_name_off.ensure((n + 1) * 8));
-  if (nn) HIPCHK(a, hipMemcpyAsync(a->bn_names.p, reads->names, nn, hipMemcpyHostToDevice, s));
-  HIPCHK(a, hipMemcpyAsync(a->bn_name_off.p, reads->name_off, (n + 1) * 8, hipMemcpyHostToDevice, s));
-  a->reads_have_quals = reads->quals != nullptr;
+  HIPCHK(a, a->bam.names.ensure(nn, 16));
+  HIPCHK(a, a->bam.name_off.ensure(n + 1));
+  if (nn) HIPCHK(a, hipMemcpyAsync(a->bam.names, reads->names, nn, hipMemcpyHostToDevice, s));
+  HIPCHK(a, hipMemcpyAsync(a->bam.name_off, reads->name_off, (n + 1) * 8, hipMemcpyHostToDevice, s));
+  a->bam.reads_have_quals = reads->quals != nullptr;
   if (reads->quals) {
-    HIPCHK(a, a->bn_quals.ensure(nb + 16));
-    if (nb) HIPCHK(a, hipMemcpyAsync(a->bn_quals.p, reads->quals, nb, hipMemcpyHostToDevice, s));
+    HIPCHK(a, a->bam.quals.ensure(nb, 16));
+    if (nb) HIPCHK(a, hipMemcpyAsync(a->bam.quals, reads->quals, nb, hipMemcpyHostToDevice, s));
   }
   HIPCHK(a, hipStreamSynchronize(s));
-  a->reads_named = true;
+  a->bam.reads_named = true;
   return THM_OK;
 }
 
 int bam_records_on_device(thm_aligner* a, uint32_t flags, int timing, BamOnDevice* r) {
   if (flags & ~(uint32_t)THM_BAM_NO_ANNOTATION_TAGS) return fail(a, THM_ERR_INVALID_ARG, "thm_batch_fetch_bam: unknown flag bits 0x%x", flags);
-  if (!a->uploaded || !a->reads_named)
+  if (!a->uploaded || !a->bam.reads_named)
     return fail(a, THM_ERR_INVALID_ARG, "thm_batch_fetch_bam: the batch was not uploaded by thm_batch_upload_reads (no names)");
   int rc = thm_batch_sync(a);
   if (rc != THM_OK) return rc;
   HIPCHK(a, hipSetDevice(a->device));
   rc = bam_tables_on_device(a);
   if (rc != THM_OK) return rc;
-  HIPCHK(a, ensure_events(a->ev_bam));
-  if (a->bam_stage < 0) {  // THM_BAM_EMIT=bytes: the other form of the emit kernel (DESIGN.md section 4.9 has both times)
+  HIPCHK(a, ensure_events(a->bam.ev));
+  if (a->bam.stage < 0) {  // THM_BAM_EMIT=bytes: the other form of the emit kernel (DESIGN.md section 4.9 has both times)
     const char* e = getenv("THM_BAM_EMIT");
-    a->bam_stage = e && !strcmp(e, "bytes") ? 0 : 1;
+    a->bam.stage = e && !strcmp(e, "bytes") ? 0 : 1;
   }
   const uint64_t n = a->n_reads;
   hipStream_t s = a->stream;
@@ -108,39 +109,39 @@ int bam_records_on_device(thm_aligner* a, uint32_t flags, int timing, BamOnDevic
   p.n_refs = (uint32_t)ix->refs.size();
   p.n_txs = (uint32_t)ix->txs.size();
   p.n_genes = (uint32_t)ix->genes.size();
-  p.bases = a->r_bases.as<uint8_t>();
-  p.offsets = a->r_offsets.as<uint64_t>();
-  p.quals = a->reads_have_quals ? a->bn_quals.as<uint8_t>() : nullptr;
-  p.names = a->bn_names.as<uint8_t>();
-  p.name_off = a->bn_name_off.as<uint64_t>();
-  p.aln_off = a->e_aln_off.as<uint64_t>();
-  p.alns = a->o_alns.as<thm_aln>();
-  p.tx_pool = a->bt_tx_pool.as<uint8_t>();
-  p.tx_off = a->bt_tx_off.as<uint32_t>();
-  p.gid_pool = a->bt_gid_pool.as<uint8_t>();
-  p.gid_off = a->bt_gid_off.as<uint32_t>();
-  p.gname_pool = a->bt_gname_pool.as<uint8_t>();
-  p.gname_off = a->bt_gname_off.as<uint32_t>();
-  p.tx_gene = a->bt_tx_gene.as<uint32_t>();
-  p.ref_sq = a->bt_ref_sq.as<int32_t>();
+  p.bases = a->reads.bases;
+  p.offsets = a->reads.offsets;
+  p.quals = a->bam.reads_have_quals ? a->bam.quals : nullptr;
+  p.names = a->bam.names;
+  p.name_off = a->bam.name_off;
+  p.aln_off = a->ext.aln_off;
+  p.alns = a->out.alns;
+  p.tx_pool = a->bam.tx_pool;
+  p.tx_off = a->bam.tx_off;
+  p.gid_pool = a->bam.gid_pool;
+  p.gid_off = a->bam.gid_off;
+  p.gname_pool = a->bam.gname_pool;
+  p.gname_off = a->bam.gname_off;
+  p.tx_gene = a->bam.tx_gene;
+  p.ref_sq = a->bam.ref_sq;
   // ---- per read: records and QNAME length; their scan travels with the sizes thm_batch_fetch takes first
-  HIPCHK(a, a->bm_cnt.ensure((n + 1) * 8));
-  HIPCHK(a, a->bm_first.ensure((n + 2) * 8));
-  HIPCHK(a, a->bm_qn.ensure((n + 1) * 4));
-  HIPCHK(a, a->bm_read_off.ensure((n + 2) * 8));
-  HIPCHK(a, a->bm_err.ensure(64));
-  HIPCHK(a, a->bm_scan_tmp.ensure(scan_tmp_entries(n + 1) * 8 + 64));
-  p.rec_cnt = a->bm_cnt.as<uint64_t>();
-  p.rec_first = a->bm_first.as<uint64_t>();
-  p.qn = a->bm_qn.as<uint32_t>();
-  p.read_rec_off = a->bm_read_off.as<uint64_t>();
-  p.err = a->bm_err.as<unsigned int>();
-  HIPCHK(a, hipMemsetAsync(a->bm_err.p, 0, 64, s));
+  HIPCHK(a, a->bam.cnt.ensure(n + 1));
+  HIPCHK(a, a->bam.first.ensure(n + 2));
+  HIPCHK(a, a->bam.qn.ensure(n + 1));
+  HIPCHK(a, a->bam.read_off.ensure(n + 2));
+  HIPCHK(a, a->bam.err.ensure(16));
+  p.rec_cnt = a->bam.cnt;
+  p.rec_first = a->bam.first;
+  p.qn = a->bam.qn;
+  p.read_rec_off = a->bam.read_off;
+  p.err = a->bam.err;
+  HIPCHK(a, hipMemsetAsync(a->bam.err, 0, 64, s));
   HIPCHK(a, launch_bam_prep(p, s));
-  HIPCHK(a, launch_exclusive_scan_u64(a->bm_cnt.as<uint64_t>(), a->bm_first.as<uint64_t>(), n, a->bm_scan_tmp.as<uint64_t>(), s));
+  rc = scan_u64(a, a->stage_scan_tmp, a->bam.cnt, a->bam.first, n, s);
+  if (rc != THM_OK) return rc;
   BatchSizes z;
   uint64_t n_rec = 0;
-  rc = fetch_batch_sizes(a, nullptr, a->bm_first.as<uint64_t>() + n, &n_rec, &z);
+  rc = fetch_batch_sizes(a, nullptr, a->bam.first + n, &n_rec, &z);
   if (rc != THM_OK) return rc;
   const uint64_t n_alns = z.n_alns;
   if (n_rec > n_alns + n) return fail(a, THM_ERR_INTERNAL, "more BAM records than alignments and reads");
@@ -152,25 +153,25 @@ int bam_records_on_device(thm_aligner* a, uint32_t flags, int timing, BamOnDevic
   a->timings[THM_T_CIGAR] = t_cigar;
   if (rc != THM_OK) return rc;
   p.n_rec = n_rec;
-  p.digests = a->c_dig.as<thm_aln_digest>();
-  p.words = a->c_words.as<uint32_t>();
+  p.digests = a->cig.dig;
+  p.words = a->cig.words;
   p.n_words = n_words;
   // ---- size pass and its scan; one synchronisation sizes the output
-  HIPCHK(a, a->bm_rec_read.ensure((n_rec + 1) * 4));
-  HIPCHK(a, a->bm_len.ensure((n_rec + 1) * 8));
-  HIPCHK(a, a->bm_off.ensure((n_rec + 2) * 8));
-  HIPCHK(a, a->bm_scan_tmp.ensure(scan_tmp_entries(n_rec + 1) * 8 + 64));
-  p.rec_read = a->bm_rec_read.as<uint32_t>();
-  p.rec_len = a->bm_len.as<uint64_t>();
-  p.rec_off = a->bm_off.as<uint64_t>();
-  HIPCHK(a, hipEventRecord(a->ev_bam[0], s));
+  HIPCHK(a, a->bam.rec_read.ensure(n_rec + 1));
+  HIPCHK(a, a->bam.len.ensure(n_rec + 1));
+  HIPCHK(a, a->bam.off.ensure(n_rec + 2));
+  p.rec_read = a->bam.rec_read;
+  p.rec_len = a->bam.len;
+  p.rec_off = a->bam.off;
+  HIPCHK(a, hipEventRecord(a->bam.ev[0], s));
   HIPCHK(a, launch_bam_size(p, s));
-  HIPCHK(a, launch_exclusive_scan_u64(a->bm_len.as<uint64_t>(), a->bm_off.as<uint64_t>(), n_rec, a->bm_scan_tmp.as<uint64_t>(), s));
-  HIPCHK(a, hipEventRecord(a->ev_bam[1], s));
+  rc = scan_u64(a, a->stage_scan_tmp, a->bam.len, a->bam.off, n_rec, s);
+  if (rc != THM_OK) return rc;
+  HIPCHK(a, hipEventRecord(a->bam.ev[1], s));
   unsigned long long n_bytes = 0;
   unsigned err = 0;
-  HIPCHK(a, hipMemcpyAsync(&n_bytes, a->bm_off.as<uint64_t>() + n_rec, 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(a, hipMemcpyAsync(&err, a->bm_err.p, 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(a, hipMemcpyAsync(&n_bytes, a->bam.off + n_rec, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(a, hipMemcpyAsync(&err, a->bam.err, 4, hipMemcpyDeviceToHost, s));
   HIPCHK(a, hipStreamSynchronize(s));
   // what thm_writer_format_batch_cigars reports for the same batch
   if (any_flags & THM_DIGEST_MALFORMED) return fail(a, THM_ERR_INTERNAL, "malformed op stream in the compacted pool");
@@ -179,11 +180,11 @@ int bam_records_on_device(thm_aligner* a, uint32_t flags, int timing, BamOnDevic
   if (err & BAM_ERR_CIGAR_WORDS) return fail(a, THM_ERR_INTERNAL, "thm_writer_format_batch: malformed op stream");
   if (err & BAM_ERR_RANGE) return fail(a, THM_ERR_INTERNAL, "thm_writer_format_batch: alignment record out of range");
   // ---- emit and offsets
-  HIPCHK(a, a->bm_out.ensure(n_bytes + 16));
-  p.out = a->bm_out.as<uint8_t>();
-  HIPCHK(a, hipEventRecord(a->ev_bam[2], s));
-  HIPCHK(a, launch_bam_emit(p, a->bam_stage == 1, a->n_cu, s));
-  HIPCHK(a, hipEventRecord(a->ev_bam[3], s));
+  HIPCHK(a, a->bam.out.ensure(n_bytes, 16));
+  p.out = a->bam.out;
+  HIPCHK(a, hipEventRecord(a->bam.ev[2], s));
+  HIPCHK(a, launch_bam_emit(p, a->bam.stage == 1, a->n_cu, s));
+  HIPCHK(a, hipEventRecord(a->bam.ev[3], s));
   HIPCHK(a, launch_bam_offsets(p, s));
   r->n_reads = n;
   r->n_alns = n_alns;
@@ -204,24 +205,21 @@ int32_t thm_batch_fetch_bam(thm_aligner* a, uint32_t flags, thm_bam_view* out) {
   const uint64_t n = r.n_reads, n_rec = r.n_records, n_bytes = r.n_bytes;
   hipStream_t s = a->stream;
   // ---- the copies
-  const int k = a->b_cur ^= 1;  // the other set still backs the previous view
-  HBuf& h_data = a->bh_data[k];
-  HBuf& h_off = a->bh_off[k];
-  HBuf& h_stat = a->bh_stat[k];
-  HIPCHK(a, h_data.ensure(n_bytes));
-  HIPCHK(a, h_off.ensure((n + 1) * 8));
-  if (n_bytes) HIPCHK(a, hipMemcpyAsync(h_data.p, a->bm_out.p, n_bytes, hipMemcpyDeviceToHost, s));
-  HIPCHK(a, hipMemcpyAsync(h_off.p, a->bm_read_off.p, (n + 1) * 8, hipMemcpyDeviceToHost, s));
-  rc = enqueue_statuses(a, r.any_failed, h_stat);
+  BytesHost& h = a->bam.host.next();  // the other set still backs the previous view
+  HIPCHK(a, h.data.ensure(n_bytes));
+  HIPCHK(a, h.off.ensure(n + 1));
+  if (n_bytes) HIPCHK(a, hipMemcpyAsync(h.data, a->bam.out, n_bytes, hipMemcpyDeviceToHost, s));
+  HIPCHK(a, hipMemcpyAsync(h.off, a->bam.read_off, (n + 1) * 8, hipMemcpyDeviceToHost, s));
+  rc = enqueue_statuses(a, r.any_failed, h.stat);
   if (rc != THM_OK) return rc;
   HIPCHK(a, hipStreamSynchronize(s));
-  (void)elapsed_ms(a->ev_bam, &a->timings[THM_T_BAM]);
+  (void)elapsed_ms(a->bam.ev, &a->timings[THM_T_BAM]);
   out->n_reads = n;
   out->n_records = n_rec;
   out->n_bytes = n_bytes;
-  out->data = h_data.as<uint8_t>();
-  out->read_rec_off = h_off.as<uint64_t>();
-  failed_reads(a, r.any_failed, h_stat, &out->n_failed_reads, &out->read_status);
+  out->data = h.data;
+  out->read_rec_off = h.off;
+  failed_reads(a, r.any_failed, h.stat, &out->n_failed_reads, &out->read_status);
   return THM_OK;
 }
 

@@ -4,7 +4,6 @@
 // a staging buffer and deflated from there by the BGZF stage of bgzf.hip.  Only counts, statuses and finished members
 // come back to the host.  DESIGN.md section 4.15.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 
 #include <cstdlib>
 #include <cstring>
@@ -14,6 +13,7 @@
 #include "bam_sort_internal.h"
 #include "bgzf_device.h"
 #include "io_internal.h"
+#include "launch_io.h"
 
 using namespace thm;
 
@@ -28,15 +28,16 @@ constexpr uint64_t MAX_RECORDS = 0xFFFFFFFFull;
 
 namespace {
 
-// `b` with room for `want` bytes, its first `keep` bytes kept
-int grow(thm_aligner* a, DBuf& b, size_t keep, size_t want) {
-  if (want <= b.cap) return THM_OK;
-  DBuf n;
+// `b` with room for `want` elements, its first `keep` elements kept
+template <class T>
+int grow(thm_aligner* a, DArr<T>& b, size_t keep, size_t want) {
+  if (want * sizeof(T) <= b.cap()) return THM_OK;
+  DArr<T> n;
   HIPCHK(a, n.ensure(want));
-  if (keep) HIPCHK(a, hipMemcpyAsync(n.p, b.p, keep, hipMemcpyDeviceToDevice, a->stream));
+  if (keep) HIPCHK(a, hipMemcpyAsync(n, b, keep * sizeof(T), hipMemcpyDeviceToDevice, a->stream));
   HIPCHK(a, hipStreamSynchronize(a->stream));
-  std::swap(n.p, b.p);
-  std::swap(n.cap, b.cap);
+  std::swap(n.b.p, b.b.p);
+  std::swap(n.b.cap, b.b.cap);
   return THM_OK;
 }
 
@@ -55,9 +56,9 @@ int add_resident(thm_bam_sorter* s, const char* who, const uint8_t* d_data, cons
   if (total > s->rec_cap) {
     uint64_t cap = s->rec_cap ? s->rec_cap : 1u << 16;
     while (cap < total) cap *= 2;
-    int rc = grow(a, s->key, s->n_rec * 8, cap * 8);
-    if (rc == THM_OK) rc = grow(a, s->len, s->n_rec * 4, cap * 4);
-    if (rc == THM_OK) rc = grow(a, s->loc, s->n_rec * 8, cap * 8);
+    int rc = grow(a, s->key, s->n_rec, cap);
+    if (rc == THM_OK) rc = grow(a, s->len, s->n_rec, cap);
+    if (rc == THM_OK) rc = grow(a, s->loc, s->n_rec, cap);
     if (rc != THM_OK) return rc;
     s->rec_cap = cap;
   }
@@ -79,9 +80,9 @@ int add_resident(thm_bam_sorter* s, const char* who, const uint8_t* d_data, cons
   p.n = n;
   p.n_sq = s->n_sq;
   p.base = s->n_bytes;
-  p.key = s->key.as<uint64_t>() + s->n_rec;
-  p.len = s->len.as<uint32_t>() + s->n_rec;
-  p.loc = s->loc.as<uint64_t>() + s->n_rec;
+  p.key = s->key + s->n_rec;
+  p.len = s->len + s->n_rec;
+  p.loc = s->loc + s->n_rec;
   hipError_t e = hipEventRecord(s->ev[0], st);
   if (e == hipSuccess) e = launch_bam_sort_keys(p, st);
   if (e == hipSuccess) e = hipMemcpyAsync(seg.p, d_data, n_bytes, hipMemcpyDeviceToDevice, st);
@@ -145,7 +146,7 @@ int thm::bam_sorter_add(thm_bam_sorter* s, uint32_t bam_flags, thm_bam_sort_info
   if (rc != THM_OK) return rc;
   rc = enqueue_statuses(a, r.any_failed, s->h_stat);  // (first: what can fail after the batch is in must not)
   if (rc != THM_OK) return rc;
-  rc = add_resident(s, "thm_bam_sorter_add", a->bm_out.as<uint8_t>(), a->bm_off.as<uint64_t>(), r.n_records, r.n_bytes, &info->add_ms);
+  rc = add_resident(s, "thm_bam_sorter_add", a->bam.out, a->bam.off, r.n_records, r.n_bytes, &info->add_ms);
   if (rc != THM_OK) return rc;
   HIPCHK(a, hipStreamSynchronize(a->stream));
   info->n_reads = r.n_reads;
@@ -174,38 +175,37 @@ int32_t thm_bam_sorter_finish(thm_bam_sorter* s, float* sort_ms) {
   HIPCHK(a, hipSetDevice(a->device));
   hipStream_t st = a->stream;
   HIPCHK(a, ensure_events(s->ev));
-  DBuf key2, ord, ord2, tmp, scan_tmp;
-  HIPCHK(a, key2.ensure(n * 8));
-  HIPCHK(a, ord.ensure(n * 4));
-  HIPCHK(a, ord2.ensure(n * 4));
-  HIPCHK(a, s->s_off.ensure((n + 2) * 8));
-  HIPCHK(a, s->s_loc.ensure(n * 8));
-  HIPCHK(a, scan_tmp.ensure(scan_tmp_entries(n + 1) * 8 + 64));
-  hipcub::DoubleBuffer<uint64_t> dk(s->key.as<uint64_t>(), key2.as<uint64_t>());
-  hipcub::DoubleBuffer<uint32_t> dv(ord.as<uint32_t>(), ord2.as<uint32_t>());
+  // (everything of this call's own is freed when it returns)
+  DArr<uint64_t> key2, scan_tmp;
+  DArr<uint32_t> ord, ord2;
+  DBuf tmp;
+  HIPCHK(a, key2.ensure(n));
+  HIPCHK(a, ord.ensure(n));
+  HIPCHK(a, ord2.ensure(n));
+  HIPCHK(a, s->s_off.ensure(n + 2));
+  HIPCHK(a, s->s_loc.ensure(n));
+  HIPCHK(a, scan_reserve(scan_tmp, n));
   // rank n_sq, the unmapped one, must fit: bit_width(n_sq) bits of rank, not log2
   const int bits = (int)bsort::key_bits(s->n_sq);
-  size_t tmp_bytes = 0;
-  HIPCHK(a, hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, dk, dv, n, 0, bits, st));
-  HIPCHK(a, tmp.ensure(tmp_bytes + 16));
-  HIPCHK(a, hipEventRecord(s->ev[0], st));
-  HIPCHK(a, launch_bam_sort_iota(ord.as<uint32_t>(), n, st));
-  // least significant digit first, every pass stable: equal keys keep their ordinals' order
-  HIPCHK(a, hipcub::DeviceRadixSort::SortPairs(tmp.p, tmp_bytes, dk, dv, n, 0, bits, st));
+  uint64_t* s_key = nullptr;
+  uint32_t* s_ord = nullptr;
+  int rc = sort_pairs_u64_u32(a, tmp, s->key, key2, ord, ord2, n, bits, st, &s_key, &s_ord, s->ev[0]);
+  if (rc != THM_OK) return rc;
   // the sorted lengths go where the keys no longer are
-  uint64_t* s_len = dk.Alternate();
-  HIPCHK(a, launch_bam_sort_order(dv.Current(), s->len.as<uint32_t>(), s->loc.as<uint64_t>(), n, s_len, s->s_loc.as<uint64_t>(), st));
-  HIPCHK(a, launch_exclusive_scan_u64(s_len, s->s_off.as<uint64_t>(), n, scan_tmp.as<uint64_t>(), st));
+  uint64_t* s_len = s_key == s->key.get() ? key2.get() : s->key.get();
+  HIPCHK(a, launch_bam_sort_order(s_ord, s->len, s->loc, n, s_len, s->s_loc, st));
+  rc = scan_u64(a, scan_tmp, s_len, s->s_off, n, st);
+  if (rc != THM_OK) return rc;
   HIPCHK(a, hipEventRecord(s->ev[1], st));
   const uint32_t n_seg = (uint32_t)s->segs.size();
   std::vector<const uint8_t*> ptrs;
   for (const Segment& g : s->segs) ptrs.push_back((const uint8_t*)g.p);
-  HIPCHK(a, s->d_seg_start.ensure(n_seg * 8));
-  HIPCHK(a, s->d_seg_ptr.ensure(n_seg * sizeof(void*)));
-  HIPCHK(a, hipMemcpyAsync(s->d_seg_start.p, s->seg_start.data(), n_seg * 8, hipMemcpyHostToDevice, st));
-  HIPCHK(a, hipMemcpyAsync(s->d_seg_ptr.p, ptrs.data(), n_seg * sizeof(void*), hipMemcpyHostToDevice, st));
+  HIPCHK(a, s->d_seg_start.ensure(n_seg));
+  HIPCHK(a, s->d_seg_ptr.ensure(n_seg));
+  HIPCHK(a, hipMemcpyAsync(s->d_seg_start, s->seg_start.data(), n_seg * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(a, hipMemcpyAsync(s->d_seg_ptr, ptrs.data(), n_seg * sizeof(void*), hipMemcpyHostToDevice, st));
   unsigned long long total = 0;
-  HIPCHK(a, hipMemcpyAsync(&total, s->s_off.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(a, hipMemcpyAsync(&total, s->s_off + n, 8, hipMemcpyDeviceToHost, st));
   HIPCHK(a, hipStreamSynchronize(st));
   if (total != s->n_bytes) return fail(a, THM_ERR_INTERNAL, "thm_bam_sorter_finish: the sorted records are %llu bytes, the arena holds %llu", total, (unsigned long long)s->n_bytes);
   if (sort_ms) (void)elapsed_ms(s->ev[0], s->ev[1], sort_ms);
@@ -236,50 +236,48 @@ int32_t thm_bam_sorter_next(thm_bam_sorter* s, uint64_t max_raw_bytes, uint32_t 
   HIPCHK(a, hipSetDevice(a->device));
   hipStream_t st = a->stream;
   HIPCHK(a, ensure_events(s->ev));
-  HIPCHK(a, s->stage.ensure(n + 64));
+  HIPCHK(a, s->stage.ensure(n, 64));
   BamSortGatherParams p;
-  p.off = s->s_off.as<uint64_t>();
-  p.loc = s->s_loc.as<uint64_t>();
+  p.off = s->s_off;
+  p.loc = s->s_loc;
   p.n = s->n_rec;
-  p.seg_start = s->d_seg_start.as<uint64_t>();
-  p.seg = s->d_seg_ptr.as<const uint8_t*>();
+  p.seg_start = s->d_seg_start;
+  p.seg = s->d_seg_ptr;
   p.n_seg = (uint32_t)s->segs.size();
   p.w0 = w0;
   p.w1 = w0 + n;
-  p.out = s->stage.as<uint8_t>();
+  p.out = s->stage;
   HIPCHK(a, hipEventRecord(s->ev[2], st));
   HIPCHK(a, launch_bam_sort_gather(p, s->by_records, a->n_cu, st));
   HIPCHK(a, hipEventRecord(s->ev[3], st));
-  const int k = s->cur ^= 1;  // the other set still backs the previous view
-  HBuf& h_data = s->h_data[k];
+  SortHost& h = s->host.next();  // the other set still backs the previous view
   if (flags & THM_SORT_RAW) {
-    HIPCHK(a, h_data.ensure(n));
-    HIPCHK(a, hipMemcpyAsync(h_data.p, s->stage.p, n, hipMemcpyDeviceToHost, st));
+    HIPCHK(a, h.data.ensure(n));
+    HIPCHK(a, hipMemcpyAsync(h.data, s->stage, n, hipMemcpyDeviceToHost, st));
     HIPCHK(a, hipStreamSynchronize(st));
     out->n_bytes = n;
     s->raw_taken = true;
   } else {
     const float t_bgzf = a->timings[THM_T_BGZF];
     uint64_t nb = 0, n_bytes = 0;
-    const int rc = bgzf_range_on_device(a, s->stage.as<uint8_t>(), n, &nb, &n_bytes);
+    const int rc = bgzf_range_on_device(a, s->stage, n, &nb, &n_bytes);
     out->deflate_ms = a->timings[THM_T_BGZF];
     a->timings[THM_T_BGZF] = t_bgzf;
     if (rc != THM_OK) return rc;
-    HBuf& h_off = s->h_off[k];
-    HIPCHK(a, h_data.ensure(n_bytes));
-    HIPCHK(a, h_off.ensure((nb + 1) * 8));
-    HIPCHK(a, hipMemcpyAsync(h_data.p, a->bz_out.p, n_bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(a, hipMemcpyAsync(h_off.p, a->bz_off.p, (nb + 1) * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(a, h.data.ensure(n_bytes));
+    HIPCHK(a, h.off.ensure(nb + 1));
+    HIPCHK(a, hipMemcpyAsync(h.data, a->bgzf.out, n_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(a, hipMemcpyAsync(h.off, a->bgzf.off, (nb + 1) * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(a, hipStreamSynchronize(st));
     out->n_blocks = nb;
     out->n_bytes = n_bytes;
-    out->block_off = h_off.as<uint64_t>();
+    out->block_off = h.off;
     // the index needs every member's compressed size (8 bytes a member, 64 KiB of records each)
     for (uint64_t b = 0; b < nb; b++) s->member_bytes.push_back(out->block_off[b + 1] - out->block_off[b]);
   }
   (void)elapsed_ms(s->ev[2], s->ev[3], &out->gather_ms);
   out->n_raw_bytes = n;
-  out->data = h_data.as<uint8_t>();
+  out->data = h.data;
   s->cursor = w0 + n;
   return THM_OK;
 }
@@ -313,12 +311,12 @@ int32_t thm_debug_bam_sorter_add_records(thm_bam_sorter* s, const uint8_t* bytes
     off.push_back(at);
   }
   HIPCHK(a, hipSetDevice(a->device));
-  HIPCHK(a, s->dbg_in.ensure(n_bytes + 16));
-  HIPCHK(a, s->dbg_off.ensure(off.size() * 8));
-  if (n_bytes) HIPCHK(a, hipMemcpy(s->dbg_in.p, bytes, n_bytes, hipMemcpyHostToDevice));
-  HIPCHK(a, hipMemcpy(s->dbg_off.p, off.data(), off.size() * 8, hipMemcpyHostToDevice));
+  HIPCHK(a, s->dbg_in.ensure(n_bytes, 16));
+  HIPCHK(a, s->dbg_off.ensure(off.size()));
+  if (n_bytes) HIPCHK(a, hipMemcpy(s->dbg_in, bytes, n_bytes, hipMemcpyHostToDevice));
+  HIPCHK(a, hipMemcpy(s->dbg_off, off.data(), off.size() * 8, hipMemcpyHostToDevice));
   float ms = 0;
-  return add_resident(s, who, s->dbg_in.as<uint8_t>(), s->dbg_off.as<uint64_t>(), off.size() - 1, n_bytes, &ms);
+  return add_resident(s, who, s->dbg_in, s->dbg_off, off.size() - 1, n_bytes, &ms);
 }
 
 }  // extern "C"

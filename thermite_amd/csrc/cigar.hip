@@ -10,43 +10,42 @@
 
 using namespace thm;
 
-// count -> scan -> emit over `n_streams` streams of the pool `p.ops`; device results in c_dig / c_words, the number of
+// count -> scan -> emit over `n_streams` streams of the pool `p.ops`; device results in cig.dig / cig.words, the number of
 // words and the flags met through *n_words / *any_flags (synchronises the stream once between the passes: the word pool
 // is sized by the count)
 int run_cigar_passes(thm_aligner* a, CigarParams p, uint64_t n_digests, uint64_t* n_words, unsigned* any_flags) {
   hipStream_t s = a->stream;
-  HIPCHK(a, ensure_events(a->ev_cig));
+  HIPCHK(a, ensure_events(a->cig.ev));
   const uint64_t ns = p.n_streams;
   *n_words = 0;
   *any_flags = 0;
   a->timings[THM_T_CIGAR] = 0;
   if (ns == 0) return THM_OK;
-  HIPCHK(a, a->c_sums.ensure(ns * sizeof(CigarSum)));
-  HIPCHK(a, a->c_nwords.ensure((ns + 1) * 8));
-  HIPCHK(a, a->c_woff.ensure((ns + 2) * 8));
-  HIPCHK(a, a->c_scan_tmp.ensure(scan_tmp_entries(ns + 1) * 8 + 64));
-  HIPCHK(a, a->c_flags.ensure(64));
-  HIPCHK(a, a->c_dig.ensure(n_digests * sizeof(thm_aln_digest)));
-  p.sums = a->c_sums.as<CigarSum>();
-  p.n_words = a->c_nwords.as<uint64_t>();
-  p.word_off = a->c_woff.as<uint64_t>();
-  p.digests = a->c_dig.as<thm_aln_digest>();
-  p.any_flags = a->c_flags.as<unsigned int>();
+  HIPCHK(a, a->cig.sums.ensure(ns));
+  HIPCHK(a, a->cig.nwords.ensure(ns + 1));
+  HIPCHK(a, a->cig.woff.ensure(ns + 2));
+  HIPCHK(a, a->cig.flags.ensure(16));
+  HIPCHK(a, a->cig.dig.ensure(n_digests));
+  p.sums = a->cig.sums;
+  p.n_words = a->cig.nwords;
+  p.word_off = a->cig.woff;
+  p.digests = a->cig.dig;
+  p.any_flags = a->cig.flags;
   p.words = nullptr;
-  HIPCHK(a, hipEventRecord(a->ev_cig[0], s));
-  HIPCHK(a, hipMemsetAsync(a->c_flags.p, 0, 64, s));
+  HIPCHK(a, hipEventRecord(a->cig.ev[0], s));
+  HIPCHK(a, hipMemsetAsync(a->cig.flags, 0, 64, s));
   HIPCHK(a, launch_cigar_count(p, a->n_cu, s));
-  HIPCHK(a, launch_exclusive_scan_u64(a->c_nwords.as<uint64_t>(), a->c_woff.as<uint64_t>(), ns, a->c_scan_tmp.as<uint64_t>(), s));
-  HIPCHK(a, hipEventRecord(a->ev_cig[1], s));
+  if (const int rc = scan_u64(a, a->stage_scan_tmp, a->cig.nwords, a->cig.woff, ns, s); rc != THM_OK) return rc;
+  HIPCHK(a, hipEventRecord(a->cig.ev[1], s));
   unsigned long long total = 0;
-  HIPCHK(a, hipMemcpyAsync(&total, a->c_woff.as<uint64_t>() + ns, 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(a, hipMemcpyAsync(any_flags, a->c_flags.p, 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(a, hipMemcpyAsync(&total, a->cig.woff + ns, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(a, hipMemcpyAsync(any_flags, a->cig.flags, 4, hipMemcpyDeviceToHost, s));
   HIPCHK(a, hipStreamSynchronize(s));
-  HIPCHK(a, a->c_words.ensure(total * 4 + 16));
-  p.words = a->c_words.as<uint32_t>();
-  HIPCHK(a, hipEventRecord(a->ev_cig[2], s));
+  HIPCHK(a, a->cig.words.ensure(total, 16));
+  p.words = a->cig.words;
+  HIPCHK(a, hipEventRecord(a->cig.ev[2], s));
   HIPCHK(a, launch_cigar_emit(p, a->n_cu, s));
-  HIPCHK(a, hipEventRecord(a->ev_cig[3], s));
+  HIPCHK(a, hipEventRecord(a->cig.ev[3], s));
   *n_words = total;
   return THM_OK;
 }
@@ -61,40 +60,35 @@ int32_t thm_batch_fetch_cigars(thm_aligner* a, thm_cigar_view* out) {
   HIPCHK(a, hipSetDevice(a->device));
   const uint64_t n = a->n_reads;
   hipStream_t s = a->stream;
-  const int k = a->c_cur ^= 1;  // the other set still backs the previous view
-  HBuf& h_off = a->ch_off[k];
-  HBuf& h_alns = a->ch_alns[k];
-  HBuf& h_dig = a->ch_dig[k];
-  HBuf& h_words = a->ch_words[k];
-  HBuf& h_stat = a->ch_stat[k];
+  CigarHost& h = a->cig.host.next();  // the other set still backs the previous view
   BatchSizes z;  // offsets, the op-pool size behind them and the count of out-of-contract reads, as thm_batch_fetch takes them
-  rc = fetch_batch_sizes(a, &h_off, nullptr, nullptr, &z);
+  rc = fetch_batch_sizes(a, &h.off, nullptr, nullptr, &z);
   if (rc != THM_OK) return rc;
   const uint64_t n_alns = z.n_alns;
-  HIPCHK(a, h_alns.ensure(n_alns * sizeof(thm_aln)));
-  HIPCHK(a, h_dig.ensure(n_alns * sizeof(thm_aln_digest)));
-  if (n_alns) HIPCHK(a, hipMemcpyAsync(h_alns.p, a->o_alns.p, n_alns * sizeof(thm_aln), hipMemcpyDeviceToHost, s));
+  HIPCHK(a, h.alns.ensure(n_alns));
+  HIPCHK(a, h.dig.ensure(n_alns));
+  if (n_alns) HIPCHK(a, hipMemcpyAsync(h.alns, a->out.alns, n_alns * sizeof(thm_aln), hipMemcpyDeviceToHost, s));
   uint64_t n_words = 0;
   unsigned any_flags = 0;
   rc = run_cigar_passes(a, compacted_cigar_params(a, z), n_alns, &n_words, &any_flags);
   if (rc != THM_OK) return rc;
-  HIPCHK(a, h_words.ensure(n_words * 4));
-  if (n_alns) HIPCHK(a, hipMemcpyAsync(h_dig.p, a->c_dig.p, n_alns * sizeof(thm_aln_digest), hipMemcpyDeviceToHost, s));
-  if (n_words) HIPCHK(a, hipMemcpyAsync(h_words.p, a->c_words.p, n_words * 4, hipMemcpyDeviceToHost, s));
-  rc = enqueue_statuses(a, z.any_failed, h_stat);
+  HIPCHK(a, h.words.ensure(n_words));
+  if (n_alns) HIPCHK(a, hipMemcpyAsync(h.dig, a->cig.dig, n_alns * sizeof(thm_aln_digest), hipMemcpyDeviceToHost, s));
+  if (n_words) HIPCHK(a, hipMemcpyAsync(h.words, a->cig.words, n_words * 4, hipMemcpyDeviceToHost, s));
+  rc = enqueue_statuses(a, z.any_failed, h.stat);
   if (rc != THM_OK) return rc;
   HIPCHK(a, hipStreamSynchronize(s));
-  if (n_alns) (void)elapsed_ms(a->ev_cig, &a->timings[THM_T_CIGAR]);
+  if (n_alns) (void)elapsed_ms(a->cig.ev, &a->timings[THM_T_CIGAR]);
   // the extend kernels write well-formed streams: anything else is a fault of this library, not of the input
   if (any_flags & THM_DIGEST_MALFORMED) return fail(a, THM_ERR_INTERNAL, "malformed op stream in the compacted pool");
   out->n_reads = n;
   out->n_alns = n_alns;
   out->n_cigar_words = n_words;
-  out->read_aln_off = h_off.as<uint64_t>();
-  out->alns = h_alns.as<thm_aln>();
-  out->digests = h_dig.as<thm_aln_digest>();
-  out->cigar = h_words.as<uint32_t>();
-  failed_reads(a, z.any_failed, h_stat, &out->n_failed_reads, &out->read_status);
+  out->read_aln_off = h.off;
+  out->alns = h.alns;
+  out->digests = h.dig;
+  out->cigar = h.words;
+  failed_reads(a, z.any_failed, h.stat, &out->n_failed_reads, &out->read_status);
   return THM_OK;
 }
 
@@ -125,30 +119,30 @@ int32_t thm_cigar_encode_batch(thm_aligner* a, const uint8_t* ops, const uint64_
   const uint64_t o0 = off[0], pool = off[n] - o0;
   std::vector<uint64_t> rel(n + 1);
   for (uint64_t i = 0; i <= n; i++) rel[i] = off[i] - o0;
-  HIPCHK(a, a->c_in_ops.ensure(pool + 16));
-  HIPCHK(a, a->c_in_off.ensure((n + 1) * 8));
-  if (pool) HIPCHK(a, hipMemcpyAsync(a->c_in_ops.p, ops + o0, pool, hipMemcpyHostToDevice, s));
-  HIPCHK(a, hipMemcpyAsync(a->c_in_off.p, rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
+  HIPCHK(a, a->cig.in_ops.ensure(pool, 16));
+  HIPCHK(a, a->cig.in_off.ensure(n + 1));
+  if (pool) HIPCHK(a, hipMemcpyAsync(a->cig.in_ops, ops + o0, pool, hipMemcpyHostToDevice, s));
+  HIPCHK(a, hipMemcpyAsync(a->cig.in_off, rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
   CigarParams p;
   memset(&p, 0, sizeof p);
-  p.ops = a->c_in_ops.as<uint8_t>();
+  p.ops = a->cig.in_ops;
   p.ops_bytes = pool;
   p.n_streams = n;
-  p.off = a->c_in_off.as<uint64_t>();
+  p.off = a->cig.in_off;
   uint64_t n_words = 0;
   unsigned any_flags = 0;
   const int rc = run_cigar_passes(a, p, n, &n_words, &any_flags);  // (synchronises: `rel` has been read by then)
   if (rc != THM_OK) return rc;
-  a->h_cig_dig.resize(n);
-  a->h_cig_words.resize(n_words);
-  HIPCHK(a, hipMemcpyAsync(a->h_cig_dig.data(), a->c_dig.p, n * sizeof(thm_aln_digest), hipMemcpyDeviceToHost, s));
-  if (n_words) HIPCHK(a, hipMemcpyAsync(a->h_cig_words.data(), a->c_words.p, n_words * 4, hipMemcpyDeviceToHost, s));
+  a->cig.h_dig.resize(n);
+  a->cig.h_words.resize(n_words);
+  HIPCHK(a, hipMemcpyAsync(a->cig.h_dig.data(), a->cig.dig, n * sizeof(thm_aln_digest), hipMemcpyDeviceToHost, s));
+  if (n_words) HIPCHK(a, hipMemcpyAsync(a->cig.h_words.data(), a->cig.words, n_words * 4, hipMemcpyDeviceToHost, s));
   HIPCHK(a, hipStreamSynchronize(s));
-  (void)elapsed_ms(a->ev_cig, &a->timings[THM_T_CIGAR]);
+  (void)elapsed_ms(a->cig.ev, &a->timings[THM_T_CIGAR]);
   out->n_alns = n;
   out->n_cigar_words = n_words;
-  out->digests = a->h_cig_dig.data();
-  out->cigar = a->h_cig_words.data();
+  out->digests = a->cig.h_dig.data();
+  out->cigar = a->cig.h_words.data();
   return THM_OK;
 }
 

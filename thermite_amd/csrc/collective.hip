@@ -118,7 +118,7 @@ int32_t thm_counters_allreduce(thm_aligner* a, thm_comm* c) {
   Rccl& r = rccl();
   if (!r.ok) return no_rccl();
   HIPCHK(a, hipSetDevice(a->device));
-  const ncclResult_t e = r.AllReduce(a->d_counters.p, a->d_counters.p, THM_N_COUNTERS, ncclUint64, ncclSum, c->comm, a->stream);
+  const ncclResult_t e = r.AllReduce(a->d_counters, a->d_counters, THM_N_COUNTERS, ncclUint64, ncclSum, c->comm, a->stream);
   if (e != ncclSuccess) return nccl_fail(a, "ncclAllReduce", e);
   HIPCHK(a, hipStreamSynchronize(a->stream));
   return THM_OK;

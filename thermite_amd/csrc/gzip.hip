@@ -1,6 +1,6 @@
 // gzip.hip -- host side of thm_batch_upload_fastq_gzip (include/thermite_io.h): bytes of an
 // ordinary .fastq.gz go up compressed, wherever they begin and end.  kernels_gzip.hip searches block starts, decodes
-// every run into symbols, chains the runs, resolves the symbols into fq_raw behind the head the caller hands in and
+// every run into symbols, chains the runs, resolves the symbols into fq.raw behind the head the caller hands in and
 // checks the members (gzip_device.h has the rules); the device FASTQ parser (fastq.hip, parse_resident) runs on the
 // block where it stands.  The device's summary -- status, bytes out, bytes consumed -- and the outgoing state come down in
 // one synchronisation, because the parse cannot be sized before the inflate has ended; the parse brings its own three.
@@ -16,6 +16,7 @@
 #include "aligner_internal.h"
 #include "gzip_device.h"
 #include "io_internal.h"
+#include "launch_io.h"
 
 using namespace thm;
 
@@ -27,7 +28,7 @@ static_assert(sizeof(gz::State) == sizeof(thm_gzip_state) && offsetof(gz::State,
 namespace {
 
 // The inflate of bytes[0, n), n > 0, in chunks of `chunk` on the stream, and one synchronisation: *sum; with status 0
-// the bytes stand in fq_raw behind head_len and the outgoing state in gz_h_state.  fq_raw is sized here.
+// the bytes stand in fq.raw behind head_len and the outgoing state in gz.h_state.  fq.raw is sized here.
 int inflate_on_device(thm_aligner* a, const thm_gzip_state* st, const uint8_t* bytes, uint64_t n, uint32_t chunk, bool last_block,
                       uint64_t head_len, gz::Summary* sum) {
   hipStream_t s = a->stream;
@@ -36,46 +37,46 @@ int inflate_on_device(thm_aligner* a, const thm_gzip_state* st, const uint8_t* b
   j.n = n, j.chunk_bytes = chunk, j.n_chunks = (uint32_t)((n + chunk - 1) / chunk), j.last_block = last_block ? 1 : 0;
   const uint64_t nc = j.n_chunks, ne = nc * gz::ENDS_PER_CHUNK;
   j.out_cap = nc * gz::region_syms(j);
-  HIPCHK(a, ensure_events(a->ev_gz));
-  HIPCHK(a, a->fq_raw.ensure(head_len + j.out_cap + 64));
-  HIPCHK(a, a->gz_in.ensure(n + 64));
-  HIPCHK(a, a->gz_state.ensure(2 * sizeof(gz::State)));
-  HIPCHK(a, a->gz_cand.ensure(nc * 8));
-  HIPCHK(a, a->gz_runs.ensure(nc * sizeof(gz::Run)));
-  HIPCHK(a, a->gz_ends.ensure(ne * sizeof(gz::End)));
-  HIPCHK(a, a->gz_syms.ensure(j.out_cap * 2));
-  HIPCHK(a, a->gz_windows.ensure(nc * gz::WINDOW));
-  HIPCHK(a, a->gz_run_list.ensure(nc * 4));
-  HIPCHK(a, a->gz_run_off.ensure((nc + 1) * 8));
-  HIPCHK(a, a->gz_end_abs.ensure(ne * 8));
-  HIPCHK(a, a->gz_end_crc.ensure(ne * 4));
-  HIPCHK(a, a->gz_end_isize.ensure(ne * 4));
-  HIPCHK(a, a->gz_member_crc.ensure((ne + 1) * 4));
-  HIPCHK(a, a->gz_sum.ensure(sizeof(gz::Summary)));
-  HIPCHK(a, a->gz_h_sum.ensure(sizeof(gz::Summary)));
-  HIPCHK(a, a->gz_h_state.ensure(sizeof(gz::State)));
-  j.in = a->gz_in.as<uint8_t>();
-  j.st_in = a->gz_state.as<gz::State>();
-  j.st_out = a->gz_state.as<gz::State>() + 1;
-  j.cand = a->gz_cand.as<uint64_t>(), j.runs = a->gz_runs.as<gz::Run>(), j.ends = a->gz_ends.as<gz::End>();
-  j.syms = a->gz_syms.as<uint16_t>(), j.windows = a->gz_windows.as<uint8_t>();
-  j.run_list = a->gz_run_list.as<uint32_t>(), j.run_off = a->gz_run_off.as<uint64_t>();
-  j.end_abs = a->gz_end_abs.as<uint64_t>(), j.end_crc = a->gz_end_crc.as<uint32_t>(), j.end_isize = a->gz_end_isize.as<uint32_t>();
-  j.member_crc = a->gz_member_crc.as<uint32_t>();
-  j.out = a->fq_raw.as<uint8_t>() + head_len;
-  j.sum = a->gz_sum.as<gz::Summary>();
-  HIPCHK(a, hipMemcpyAsync(a->gz_in.p, bytes, n, hipMemcpyHostToDevice, s));
-  HIPCHK(a, hipMemcpyAsync(a->gz_state.p, st, sizeof(gz::State), hipMemcpyHostToDevice, s));
+  HIPCHK(a, ensure_events(a->gz.ev));
+  HIPCHK(a, a->fq.raw.ensure(head_len + j.out_cap + 64));
+  HIPCHK(a, a->gz.in.ensure(n, 64));
+  HIPCHK(a, a->gz.state.ensure(2));
+  HIPCHK(a, a->gz.cand.ensure(nc));
+  HIPCHK(a, a->gz.runs.ensure(nc));
+  HIPCHK(a, a->gz.ends.ensure(ne));
+  HIPCHK(a, a->gz.syms.ensure(j.out_cap));
+  HIPCHK(a, a->gz.windows.ensure(nc * gz::WINDOW));
+  HIPCHK(a, a->gz.run_list.ensure(nc));
+  HIPCHK(a, a->gz.run_off.ensure(nc + 1));
+  HIPCHK(a, a->gz.end_abs.ensure(ne));
+  HIPCHK(a, a->gz.end_crc.ensure(ne));
+  HIPCHK(a, a->gz.end_isize.ensure(ne));
+  HIPCHK(a, a->gz.member_crc.ensure(ne + 1));
+  HIPCHK(a, a->gz.sum.ensure(1));
+  HIPCHK(a, a->gz.h_sum.ensure(1));
+  HIPCHK(a, a->gz.h_state.ensure(1));
+  j.in = a->gz.in;
+  j.st_in = a->gz.state;
+  j.st_out = a->gz.state + 1;
+  j.cand = a->gz.cand, j.runs = a->gz.runs, j.ends = a->gz.ends;
+  j.syms = a->gz.syms, j.windows = a->gz.windows;
+  j.run_list = a->gz.run_list, j.run_off = a->gz.run_off;
+  j.end_abs = a->gz.end_abs, j.end_crc = a->gz.end_crc, j.end_isize = a->gz.end_isize;
+  j.member_crc = a->gz.member_crc;
+  j.out = a->fq.raw.as<uint8_t>() + head_len;
+  j.sum = a->gz.sum;
+  HIPCHK(a, hipMemcpyAsync(a->gz.in, bytes, n, hipMemcpyHostToDevice, s));
+  HIPCHK(a, hipMemcpyAsync(a->gz.state, st, sizeof(gz::State), hipMemcpyHostToDevice, s));
   HIPCHK(a, hipMemsetAsync(j.st_out, 0, sizeof(gz::State), s));
-  HIPCHK(a, hipMemsetAsync(a->gz_member_crc.p, 0, (ne + 1) * 4, s));
-  HIPCHK(a, hipMemsetAsync(a->gz_sum.p, 0xFF, sizeof(gz::Summary), s));  // (a status no kernel wrote is not 0)
-  HIPCHK(a, hipEventRecord(a->ev_gz[0], s));
+  HIPCHK(a, hipMemsetAsync(a->gz.member_crc, 0, (ne + 1) * 4, s));
+  HIPCHK(a, hipMemsetAsync(a->gz.sum, 0xFF, sizeof(gz::Summary), s));  // (a status no kernel wrote is not 0)
+  HIPCHK(a, hipEventRecord(a->gz.ev[0], s));
   HIPCHK(a, launch_gzip_inflate(j, s));
-  HIPCHK(a, hipEventRecord(a->ev_gz[1], s));
-  HIPCHK(a, hipMemcpyAsync(a->gz_h_sum.p, a->gz_sum.p, sizeof(gz::Summary), hipMemcpyDeviceToHost, s));
-  HIPCHK(a, hipMemcpyAsync(a->gz_h_state.p, j.st_out, sizeof(gz::State), hipMemcpyDeviceToHost, s));
+  HIPCHK(a, hipEventRecord(a->gz.ev[1], s));
+  HIPCHK(a, hipMemcpyAsync(a->gz.h_sum, a->gz.sum, sizeof(gz::Summary), hipMemcpyDeviceToHost, s));
+  HIPCHK(a, hipMemcpyAsync(a->gz.h_state, j.st_out, sizeof(gz::State), hipMemcpyDeviceToHost, s));
   HIPCHK(a, hipStreamSynchronize(s));
-  *sum = *a->gz_h_sum.as<gz::Summary>();
+  *sum = *a->gz.h_sum;
   if (sum->status == gz::OK && (sum->n_out > j.out_cap || sum->n_consumed > n))
     return fail(a, THM_ERR_INTERNAL, "device gzip inflate: a summary larger than its input");
   return THM_OK;
@@ -105,12 +106,12 @@ int32_t thm_batch_upload_fastq_gzip(thm_aligner* a, thm_gzip_state* st, const ui
   HIPCHK(a, hipSetDevice(a->device));
   hipStream_t s = a->stream;
   a->uploaded = a->ran = a->synced = false;
-  a->reads_named = false;
+  a->bam.reads_named = false;
   const std::string name = path ? path : "";
-  HBuf& tail = a->fz_tail[a->fz_cur ^= 1];  // (the other one may be this call's head)
+  HArr<uint8_t>& tail = a->fz.tail.next();  // (the other one may be this call's head)
   // the state this call leaves, handed over once nothing can fail any more
   std::unique_ptr<thm_gzip_state> next(new thm_gzip_state(*st));
-  // ---- the block into fq_raw: inflated there, or inflated here and copied
+  // ---- the block into fq.raw: inflated there, or inflated here and copied
   bool on_device = n != 0 && n <= gz::MAX_IN;
   if (n > gz::MAX_IN) info->decline_reason = gz::INPUT;
   uint64_t blk_n = head_len, consumed = 0;
@@ -129,15 +130,15 @@ int32_t thm_batch_upload_fastq_gzip(thm_aligner* a, thm_gzip_state* st, const ui
     } else {
       blk_n = head_len + sum.n_out;
       consumed = sum.n_consumed;
-      memcpy(next.get(), a->gz_h_state.p, sizeof(thm_gzip_state));
-      a->gz_counts[0]++;
+      memcpy(next.get(), a->gz.h_state, sizeof(thm_gzip_state));
+      a->gz.counts[0]++;
       info->inflated_on_device = 1;
-      (void)elapsed_ms(a->ev_gz[0], a->ev_gz[1], &info->inflate_ms);
+      (void)elapsed_ms(a->gz.ev[0], a->gz.ev[1], &info->inflate_ms);
       if (sum.n_out == 0) {  // nothing new: the block is the head, which the host has
-        a->fz_block.assign(head, head + head_len);
-        host_blk = a->fz_block.data();
+        a->fz.block.assign(head, head + head_len);
+        host_blk = a->fz.block.data();
       } else {
-        if (head_len) HIPCHK(a, hipMemcpyAsync(a->fq_raw.p, head, head_len, hipMemcpyHostToDevice, s));  // (in front of the inflated bytes)
+        if (head_len) HIPCHK(a, hipMemcpyAsync(a->fq.raw.p, head, head_len, hipMemcpyHostToDevice, s));  // (in front of the inflated bytes)
         FastqBlock b;
         b.n = blk_n;
         b.whole = last_block != 0;
@@ -147,33 +148,33 @@ int32_t thm_batch_upload_fastq_gzip(thm_aligner* a, thm_gzip_state* st, const ui
         if (d == 1) {
           o.take(b);
         } else {  // the parse is the host's: the inflated bytes come down, they are not inflated again
-          a->fz_block.resize(blk_n);
-          HIPCHK(a, hipMemcpyAsync(a->fz_block.data(), a->fq_raw.p, blk_n, hipMemcpyDeviceToHost, s));
+          a->fz.block.resize(blk_n);
+          HIPCHK(a, hipMemcpyAsync(a->fz.block.data(), a->fq.raw.p, blk_n, hipMemcpyDeviceToHost, s));
           HIPCHK(a, hipStreamSynchronize(s));
-          host_blk = a->fz_block.data();
+          host_blk = a->fz.block.data();
         }
       }
     }
   }
   if (!on_device) {
-    a->fz_block.assign(head, head + head_len);
-    const int rc = GzInflater::inflate_slice(next.get(), bytes, (size_t)n, name, last_block != 0, a->fz_block, &consumed, a->err);
+    a->fz.block.assign(head, head + head_len);
+    const int rc = GzInflater::inflate_slice(next.get(), bytes, (size_t)n, name, last_block != 0, a->fz.block, &consumed, a->err);
     if (rc != THM_OK) {
       set_global_error(a->err);
       return rc;
     }
-    if (n) a->gz_counts[1]++;
-    blk_n = a->fz_block.size();
-    host_blk = a->fz_block.data();
+    if (n) a->gz.counts[1]++;
+    blk_n = a->fz.block.size();
+    host_blk = a->fz.block.data();
     if (blk_n > head_len && (d = parse_host_block(a, host_blk, blk_n, last_block != 0, &tail, o)) < 0) return d;
   }
   info->n_inflated_bytes = blk_n - head_len;
   info->n_consumed_bytes = consumed;
   if (d == 1) {
     batch_parsed_on_device(a, &tail, o);
-    a->gz_counts[2]++;
+    a->gz.counts[2]++;
   } else {
-    const int rc = host_parser_batch(a, host_blk, blk_n, name, first_line, last_block != 0, &tail, &a->gz_counts[3], o);
+    const int rc = host_parser_batch(a, host_blk, blk_n, name, first_line, last_block != 0, &tail, &a->gz.counts[3], o);
     if (rc != THM_OK) return rc;
   }
   info->n_reads = o.n_reads, info->n_bases = o.n_bases, info->n_name_bytes = o.n_name_bytes;
@@ -206,8 +207,8 @@ int32_t thm_debug_gzip_inflate(thm_aligner* a, thm_gzip_state* st, const uint8_t
     return fail(a, THM_ERR_UNSUPPORTED, "thm_debug_gzip_inflate: declined with status %u at chunk %u", sum.status, sum.bad_chunk);
   if (sum.n_out > cap)
     return fail(a, THM_ERR_INVALID_ARG, "thm_debug_gzip_inflate: %llu bytes do not fit into %llu", (unsigned long long)sum.n_out, (unsigned long long)cap);
-  if (sum.n_out) HIPCHK(a, hipMemcpy(out, a->fq_raw.p, sum.n_out, hipMemcpyDeviceToHost));
-  memcpy(st, a->gz_h_state.p, sizeof(thm_gzip_state));
+  if (sum.n_out) HIPCHK(a, hipMemcpy(out, a->fq.raw.p, sum.n_out, hipMemcpyDeviceToHost));
+  memcpy(st, a->gz.h_state, sizeof(thm_gzip_state));
   *n_out = sum.n_out;
   *n_consumed = sum.n_consumed;
   return THM_OK;
@@ -217,7 +218,7 @@ int32_t thm_debug_gzip_inflate(thm_aligner* a, thm_gzip_state* st, const uint8_t
 // device, on the host, batches parsed on the device, parsed on the host (a batch without a record is neither)
 int32_t thm_debug_fastq_gzip_blocks(thm_aligner* a, uint64_t* counts) {
   if (!a || !counts) return THM_ERR_INVALID_ARG;
-  for (int k = 0; k < 4; k++) counts[k] = a->gz_counts[k];
+  for (int k = 0; k < 4; k++) counts[k] = a->gz.counts[k];
   return THM_OK;
 }
 

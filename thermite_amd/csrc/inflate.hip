@@ -1,6 +1,6 @@
 // inflate.hip -- host side of thm_batch_upload_fastq_bgzf (include/thermite_io.h): a block of
 // .fastq.gz input goes up compressed.  The host only walks the chain of BGZF members, header to header, into a table
-// (inflate_device.h); kernels_inflate.hip inflates every member to its place in fq_raw, behind the head the caller hands
+// (inflate_device.h); kernels_inflate.hip inflates every member to its place in fq.raw, behind the head the caller hands
 // in, and the device FASTQ parser (fastq.hip, parse_resident) runs on the block where it stands.  What the device does
 // not take -- a chain that is not BGZF throughout, a member that ends with a status word -- is inflated by GzInflater
 // (io_inflate.cpp) from memory, as a whole: the bytes, or the error and its message, are the host inflater's on every
@@ -15,6 +15,7 @@
 #include "fastq_cut.h"
 #include "inflate_device.h"
 #include "io_internal.h"
+#include "launch_io.h"
 
 using namespace thm;
 
@@ -36,30 +37,30 @@ bool walk_chain(const uint8_t* members, uint64_t n, uint64_t out_off, std::vecto
   return true;
 }
 
-// members and table up, the kernel on the stream: member k's bytes land at fq_raw + tab[k].out_off, its status word in
-// fz_status[k].  fq_raw must hold n_out bytes.  Nothing is synchronised.
+// members and table up, the kernel on the stream: member k's bytes land at fq.raw + tab[k].out_off, its status word in
+// fz.status[k].  fq.raw must hold n_out bytes.  Nothing is synchronised.
 int enqueue_inflate(thm_aligner* a, const uint8_t* members, uint64_t n, const std::vector<inf::Member>& tab, uint64_t n_out) {
   hipStream_t s = a->stream;
   const uint64_t nm = tab.size();
-  HIPCHK(a, ensure_events(a->ev_fz));
-  HIPCHK(a, a->fz_in.ensure(n + 64));
-  HIPCHK(a, a->fz_tab.ensure(nm * sizeof(inf::Member)));
-  HIPCHK(a, a->fz_status.ensure(nm * 4));
-  HIPCHK(a, a->fz_h_tab.ensure(nm * sizeof(inf::Member)));
-  memcpy(a->fz_h_tab.p, tab.data(), nm * sizeof(inf::Member));
-  HIPCHK(a, hipMemcpyAsync(a->fz_in.p, members, n, hipMemcpyHostToDevice, s));
-  HIPCHK(a, hipMemcpyAsync(a->fz_tab.p, a->fz_h_tab.p, nm * sizeof(inf::Member), hipMemcpyHostToDevice, s));
+  HIPCHK(a, ensure_events(a->fz.ev));
+  HIPCHK(a, a->fz.in.ensure(n, 64));
+  HIPCHK(a, a->fz.tab.ensure(nm));
+  HIPCHK(a, a->fz.status.ensure(nm));
+  HIPCHK(a, a->fz.h_tab.ensure(nm));
+  memcpy(a->fz.h_tab, tab.data(), nm * sizeof(inf::Member));
+  HIPCHK(a, hipMemcpyAsync(a->fz.in, members, n, hipMemcpyHostToDevice, s));
+  HIPCHK(a, hipMemcpyAsync(a->fz.tab, a->fz.h_tab, nm * sizeof(inf::Member), hipMemcpyHostToDevice, s));
   InflateParams p;
-  p.in = a->fz_in.as<uint8_t>();
+  p.in = a->fz.in;
   p.n_in = n;
-  p.members = a->fz_tab.as<inf::Member>();
+  p.members = a->fz.tab;
   p.n_members = nm;
-  p.out = a->fq_raw.as<uint8_t>();
+  p.out = a->fq.raw.as<uint8_t>();
   p.n_out = n_out;
-  p.status = a->fz_status.as<uint32_t>();
-  HIPCHK(a, hipEventRecord(a->ev_fz[0], s));
+  p.status = a->fz.status;
+  HIPCHK(a, hipEventRecord(a->fz.ev[0], s));
   HIPCHK(a, launch_bgzf_inflate(p, s));
-  HIPCHK(a, hipEventRecord(a->ev_fz[1], s));
+  HIPCHK(a, hipEventRecord(a->fz.ev[1], s));
   return THM_OK;
 }
 
@@ -87,7 +88,7 @@ int inflate_to(std::vector<uint8_t>& blk, const uint8_t* head, uint64_t head_len
   return THM_OK;
 }
 int inflate_on_host(thm_aligner* a, const uint8_t* head, uint64_t head_len, const uint8_t* members, uint64_t n, const std::string& path) {
-  const int rc = inflate_to(a->fz_block, head, head_len, members, n, path, a->err);
+  const int rc = inflate_to(a->fz.block, head, head_len, members, n, path, a->err);
   if (rc != THM_OK) set_global_error(a->err);
   return rc;
 }
@@ -112,10 +113,10 @@ int32_t thm_batch_upload_fastq_bgzf(thm_aligner* a, const uint8_t* head, uint64_
   HIPCHK(a, hipSetDevice(a->device));
   hipStream_t s = a->stream;
   a->uploaded = a->ran = a->synced = false;
-  a->reads_named = false;
+  a->bam.reads_named = false;
   const std::string name = path ? path : "";
-  HBuf& tail = a->fz_tail[a->fz_cur ^= 1];  // (the other one may be this call's head)
-  // ---- the block into fq_raw: inflated there, or inflated here and copied
+  HArr<uint8_t>& tail = a->fz.tail.next();  // (the other one may be this call's head)
+  // ---- the block into fq.raw: inflated there, or inflated here and copied
   std::vector<inf::Member> tab;
   uint64_t total = 0;
   bool on_device = n != 0 && walk_chain(members, n, head_len, tab, &total);
@@ -125,22 +126,22 @@ int32_t thm_batch_upload_fastq_bgzf(thm_aligner* a, const uint8_t* head, uint64_
   int d = FQ_NOT_INFLATED;
   FastqOutcome o;
   if (on_device) {
-    HIPCHK(a, a->fq_raw.ensure(blk_n + 64));
-    if (head_len) HIPCHK(a, hipMemcpyAsync(a->fq_raw.p, head, head_len, hipMemcpyHostToDevice, s));
+    HIPCHK(a, a->fq.raw.ensure(blk_n + 64));
+    if (head_len) HIPCHK(a, hipMemcpyAsync(a->fq.raw.p, head, head_len, hipMemcpyHostToDevice, s));
     int rc = enqueue_inflate(a, members, n, tab, blk_n);
     if (rc != THM_OK) return rc;
     if (blk_n == 0) {  // (members of no bytes, no head: only the statuses are of interest)
-      HIPCHK(a, a->fz_h_status.ensure(tab.size() * 4));
-      HIPCHK(a, hipMemcpyAsync(a->fz_h_status.p, a->fz_status.p, tab.size() * 4, hipMemcpyDeviceToHost, s));
+      HIPCHK(a, a->fz.h_status.ensure(tab.size()));
+      HIPCHK(a, hipMemcpyAsync(a->fz.h_status, a->fz.status, tab.size() * 4, hipMemcpyDeviceToHost, s));
       HIPCHK(a, hipStreamSynchronize(s));
       d = FQ_NO_RECORD;
       for (size_t k = 0; k < tab.size(); k++)
-        if (a->fz_h_status.as<uint32_t>()[k] != 0) d = FQ_NOT_INFLATED;
+        if (a->fz.h_status[k] != 0) d = FQ_NOT_INFLATED;
     } else {
       FastqBlock b;
       b.n = blk_n;
       b.whole = last_block != 0;
-      b.d_status = a->fz_status.as<uint32_t>();
+      b.d_status = a->fz.status;
       b.n_status = tab.size();
       b.tail = &tail;
       d = parse_resident(a, b);
@@ -150,30 +151,30 @@ int32_t thm_batch_upload_fastq_bgzf(thm_aligner* a, const uint8_t* head, uint64_
     on_device = d != FQ_NOT_INFLATED;
   }
   if (on_device) {
-    a->fz_counts[0]++;
+    a->fz.counts[0]++;
     info->inflated_on_device = 1;
-    (void)elapsed_ms(a->ev_fz[0], a->ev_fz[1], &info->inflate_ms);
+    (void)elapsed_ms(a->fz.ev[0], a->fz.ev[1], &info->inflate_ms);
     if (d != 1 && blk_n) {  // the parse is the host's: the inflated bytes come down, they are not inflated again
-      a->fz_block.resize(blk_n);
-      HIPCHK(a, hipMemcpyAsync(a->fz_block.data(), a->fq_raw.p, blk_n, hipMemcpyDeviceToHost, s));
+      a->fz.block.resize(blk_n);
+      HIPCHK(a, hipMemcpyAsync(a->fz.block.data(), a->fq.raw.p, blk_n, hipMemcpyDeviceToHost, s));
       HIPCHK(a, hipStreamSynchronize(s));
-      host_blk = a->fz_block.data();
+      host_blk = a->fz.block.data();
     }
   } else {
     const int rc = inflate_on_host(a, head, head_len, members, n, name);
     if (rc != THM_OK) return rc;
-    if (n) a->fz_counts[1]++;
-    blk_n = a->fz_block.size();
-    host_blk = a->fz_block.data();
+    if (n) a->fz.counts[1]++;
+    blk_n = a->fz.block.size();
+    host_blk = a->fz.block.data();
     d = FQ_NO_RECORD;
     if (blk_n && (d = parse_host_block(a, host_blk, blk_n, last_block != 0, &tail, o)) < 0) return d;
   }
   info->n_inflated_bytes = blk_n - head_len;
   if (d == 1) {
     batch_parsed_on_device(a, &tail, o);
-    a->fz_counts[2]++;
+    a->fz.counts[2]++;
   } else {
-    const int rc = host_parser_batch(a, host_blk, blk_n, name, first_line, last_block != 0, &tail, &a->fz_counts[3], o);
+    const int rc = host_parser_batch(a, host_blk, blk_n, name, first_line, last_block != 0, &tail, &a->fz.counts[3], o);
     if (rc != THM_OK) return rc;
   }
   info->n_reads = o.n_reads, info->n_bases = o.n_bases, info->n_name_bytes = o.n_name_bytes;
@@ -196,16 +197,16 @@ int32_t thm_debug_bgzf_inflate(thm_aligner* a, const uint8_t* members, uint64_t 
   if (!walk_chain(members, n, 0, tab, &total)) return fail(a, THM_ERR_UNSUPPORTED, "thm_debug_bgzf_inflate: the chain is not BGZF throughout");
   if (total > cap) return fail(a, THM_ERR_INVALID_ARG, "thm_debug_bgzf_inflate: %llu bytes do not fit into %llu", (unsigned long long)total, (unsigned long long)cap);
   if (tab.empty()) return THM_OK;
-  HIPCHK(a, a->fq_raw.ensure(total + 64));
+  HIPCHK(a, a->fq.raw.ensure(total + 64));
   const int rc = enqueue_inflate(a, members, n, tab, total);
   if (rc != THM_OK) return rc;
-  HIPCHK(a, a->fz_h_status.ensure(tab.size() * 4));
-  HIPCHK(a, hipMemcpyAsync(a->fz_h_status.p, a->fz_status.p, tab.size() * 4, hipMemcpyDeviceToHost, a->stream));
+  HIPCHK(a, a->fz.h_status.ensure(tab.size()));
+  HIPCHK(a, hipMemcpyAsync(a->fz.h_status, a->fz.status, tab.size() * 4, hipMemcpyDeviceToHost, a->stream));
   HIPCHK(a, hipStreamSynchronize(a->stream));
   for (size_t k = 0; k < tab.size(); k++)
-    if (const uint32_t st = a->fz_h_status.as<uint32_t>()[k])
+    if (const uint32_t st = a->fz.h_status[k])
       return fail(a, THM_ERR_UNSUPPORTED, "thm_debug_bgzf_inflate: member %llu declined with status %u", (unsigned long long)k, st);
-  if (total) HIPCHK(a, hipMemcpy(out, a->fq_raw.p, total, hipMemcpyDeviceToHost));
+  if (total) HIPCHK(a, hipMemcpy(out, a->fq.raw.p, total, hipMemcpyDeviceToHost));
   *n_out = total;
   return THM_OK;
 }
@@ -214,7 +215,7 @@ int32_t thm_debug_bgzf_inflate(thm_aligner* a, const uint8_t* members, uint64_t 
 // the device, inflated on the host, batches parsed on the device, parsed on the host (a batch without a record is neither)
 int32_t thm_debug_fastq_bgzf_blocks(thm_aligner* a, uint64_t* counts) {
   if (!a || !counts) return THM_ERR_INVALID_ARG;
-  for (int k = 0; k < 4; k++) counts[k] = a->fz_counts[k];
+  for (int k = 0; k < 4; k++) counts[k] = a->fz.counts[k];
   return THM_OK;
 }
 

@@ -18,7 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include "bam_sort_device.h"
-#include "launch.h"
+#include "launch_io.h"
 
 namespace thm {
 namespace dev {

@@ -16,7 +16,7 @@
 #include <hip/hip_runtime.h>
 
 #include "bgzf_device.h"
-#include "launch.h"
+#include "launch_io.h"
 
 namespace thm {
 namespace dev {

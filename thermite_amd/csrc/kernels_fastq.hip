@@ -9,7 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include "fastq_device.h"
-#include "launch.h"
+#include "launch_io.h"
 
 namespace thm {
 namespace dev {

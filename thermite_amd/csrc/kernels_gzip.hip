@@ -13,7 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include "gzip_device.h"
-#include "launch.h"
+#include "launch_io.h"
 
 namespace thm {
 namespace dev {

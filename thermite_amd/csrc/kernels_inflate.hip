@@ -8,7 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include "inflate_device.h"
-#include "launch.h"
+#include "launch_io.h"
 
 namespace thm {
 namespace dev {

@@ -21,7 +21,7 @@
 // Integer atomics only: no result depends on the order of arrival.
 #include <hip/hip_runtime.h>
 
-#include "launch.h"
+#include "launch_io.h"
 #include "quant_device.h"
 
 namespace thm {

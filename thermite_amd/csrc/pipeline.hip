@@ -63,20 +63,20 @@ template <class C>
 int enqueue_seed_t(thm_aligner* a, uint32_t min_seed_len, bool finish_scan) {
   const uint64_t n = a->n_reads;
   hipStream_t s = a->stream;
-  HIPCHK(a, a->s_off.ensure((n + 1) * 8));
-  HIPCHK(a, a->s_cnt.ensure((n + 1) * 4));
-  HIPCHK(a, a->s_hits.ensure((n + 1) * 8));
-  HIPCHK(a, a->s_cand_off.ensure((n + 2) * 8));
-  HIPCHK(a, a->scan_tmp.ensure(2 * scan_tmp_entries(n + 1) * 8 + 64));  // (twice: the two-array scan of the output offsets)
-  HIPCHK(a, a->r_status.ensure((n + 1) * 4 + 16));
+  HIPCHK(a, a->seed.off.ensure(n + 1));
+  HIPCHK(a, a->seed.cnt.ensure(n + 1));
+  HIPCHK(a, a->seed.hits.ensure(n + 1));
+  HIPCHK(a, a->seed.cand_off.ensure(n + 2));
+  HIPCHK(a, a->seed.scan_tmp.ensure(2 * scan_tmp_entries(n + 1), 64));  // (twice: the two-array scan of the output offsets)
+  HIPCHK(a, a->reads.status.ensure(n + 1, 16));
   // typical: 1-2 SMEMs per read; waves take the pool in 256-entry slices, hence the fixed slack
   const uint64_t smem_min = a->dbg_smem_cap ? a->dbg_smem_cap : n * 4 + (4u << 20);
-  if (a->smem_cap < smem_min) a->smem_cap = smem_min;
-  HIPCHK(a, a->s_smems.ensure(a->smem_cap * sizeof(SmemT<C>)));
-  if (!a->dbg_smem_cap) a->smem_cap = std::max<uint64_t>(a->smem_cap, a->s_smems.cap / sizeof(SmemT<C>));
+  if (a->seed.smem_cap < smem_min) a->seed.smem_cap = smem_min;
+  HIPCHK(a, a->seed.smems.ensure(a->seed.smem_cap * sizeof(SmemT<C>)));
+  if (!a->dbg_smem_cap) a->seed.smem_cap = std::max<uint64_t>(a->seed.smem_cap, a->seed.smems.cap / sizeof(SmemT<C>));
   // to_ascii_uppercase (src/aligner.rs:125) + sanitising, once per run for both kernels
   // (16 bytes in front: a left extension is read in whole 8-byte words that may begin a few bytes before the first read)
-  HIPCHK(a, a->r_san.ensure(a->n_bases + 256 + 16));
+  HIPCHK(a, a->reads.san.ensure(a->n_bases, 256 + 16));
   // The same launch starts the run: control block (list counts, cursors, fault words, the queue words of both
   // stages), per-read statuses and the 16 bytes in front zeroed, counters copied to their snapshot row (as they stood
   // before this attempt, so that a replay after a pool overflow does not count twice).
@@ -84,11 +84,11 @@ int enqueue_seed_t(thm_aligner* a, uint32_t min_seed_len, bool finish_scan) {
     RunResetParams rp;
     rp.ctl = a->d_ctl.as<uint4>();
     rp.ctl_vec4 = (uint32_t)(thm_aligner::CTL_BYTES / 16);
-    rp.status = a->r_status.as<uint4>();
+    rp.status = reinterpret_cast<uint4*>(a->reads.status.get());
     rp.status_vec4 = ((n + 1) * 4 + 15) / 16;
-    rp.san_head = a->r_san.as<uint4>();
-    rp.counters = a->d_counters.as<unsigned long long>();
-    HIPCHK(a, launch_sanitize_reset(a->r_bases.as<uint8_t>(), a->r_san.as<uint8_t>() + 16, a->n_bases, a->n_bases + 128, rp, s));
+    rp.san_head = reinterpret_cast<uint4*>(a->reads.san.get());
+    rp.counters = a->d_counters;
+    HIPCHK(a, launch_sanitize_reset(a->reads.bases, a->reads.san + 16, a->n_bases, a->n_bases + 128, rp, s));
   }
   // length classes of the seed stage (launch.h): short reads take the byte-per-position paths
   uint64_t n_long = 0;
@@ -104,45 +104,45 @@ int enqueue_seed_t(thm_aligner* a, uint32_t min_seed_len, bool finish_scan) {
   const uint64_t n_short = n - n_long;
   // ragged per-position rows (launch.h, ms_row)
   const uint64_t items = ms_row(a->n_bases, n) + 64;
-  HIPCHK(a, a->s_ms_end.ensure(items * 2 + 64));
-  HIPCHK(a, a->s_ms_lo.ensure(items * sizeof(C) + 64));
-  HIPCHK(a, a->s_ms_hi.ensure(items * sizeof(C) + 64));
+  HIPCHK(a, a->seed.ms_end.ensure(items, 64));
+  HIPCHK(a, a->seed.ms_lo.ensure(items * sizeof(C) + 64));
+  HIPCHK(a, a->seed.ms_hi.ensure(items * sizeof(C) + 64));
   auto cells_of = [&](uint32_t max_len) -> uint64_t {
     const uint32_t P = (max_len >= min_seed_len) ? max_len - min_seed_len + 1 : 1;
     return (P + 7) / 8;
   };
   const uint64_t cells = n_short * cells_of(max_short) + n_long * cells_of(max_long);
-  HIPCHK(a, a->s_work_reads.ensure((n + 1) * 8));
-  HIPCHK(a, a->s_work_long.ensure((n_long + 1) * 8));
-  HIPCHK(a, a->s_work_cells.ensure((std::max(cells, n) + 1) * 8));
+  HIPCHK(a, a->seed.work_reads.ensure(n + 1));
+  HIPCHK(a, a->seed.work_long.ensure(n_long + 1));
+  HIPCHK(a, a->seed.work_cells.ensure(std::max(cells, n) + 1));
   const int n_blocks = grid_blocks(a, n, 4, lds_blocks_per_cu(std::min(seed_select_lds_bytes(std::max(max_short, 1u)), SEED_SELECT_LDS_LIMIT), 8));
   SeedParamsT<C> sp;
   sp.ix = dev_view<C>(a);
-  sp.reads.bases = a->r_san.as<uint8_t>() + 16;
-  sp.reads.offsets = a->r_offsets.as<uint64_t>();
+  sp.reads.bases = a->reads.san + 16;
+  sp.reads.offsets = a->reads.offsets;
   sp.reads.n_reads = n;
   sp.min_seed_len = min_seed_len;
   sp.max_len_short = max_short;
   sp.max_len_long = max_long;
   sp.n_long = n_long;
-  sp.ms_end = a->s_ms_end.as<uint16_t>();
-  sp.ms_lo = a->s_ms_lo.as<C>();
-  sp.ms_hi = a->s_ms_hi.as<C>();
-  sp.work_short = a->s_work_reads.as<unsigned long long>();
-  sp.work_long = a->s_work_long.as<unsigned long long>();
-  sp.work_cells = a->s_work_cells.as<unsigned long long>();
-  sp.work_counts = a->s_work_counts.as<unsigned long long>();
+  sp.ms_end = a->seed.ms_end;
+  sp.ms_lo = a->seed.ms_lo.as<C>();
+  sp.ms_hi = a->seed.ms_hi.as<C>();
+  sp.work_short = a->seed.work_reads;
+  sp.work_long = a->seed.work_long;
+  sp.work_cells = a->seed.work_cells;
+  sp.work_counts = a->s_work_counts;
   sp.flags = (a->dbg_seed_noinfer ? 0u : SEED_INFER) | (a->dbg_seed_stats ? SEED_STATS : 0u) | (a->dbg_seed_nodirect ? SEED_NODIRECT : 0u);
-  sp.smems = a->s_smems.as<SmemT<C>>();
-  sp.smem_cap = a->smem_cap;
-  sp.cursor = a->d_cursors.as<unsigned long long>();
-  sp.read_smem_off = a->s_off.as<uint64_t>();
-  sp.read_smem_cnt = a->s_cnt.as<uint32_t>();
-  sp.read_hits = a->s_hits.as<uint64_t>();
-  sp.read_status = a->r_status.as<int32_t>();
-  sp.counters = a->d_counters.as<unsigned long long>();
-  sp.queue = a->d_queue.as<unsigned int>();
-  sp.fault = a->d_fault.as<int>();
+  sp.smems = a->seed.smems.as<SmemT<C>>();
+  sp.smem_cap = a->seed.smem_cap;
+  sp.cursor = a->d_cursors;
+  sp.read_smem_off = a->seed.off;
+  sp.read_smem_cnt = a->seed.cnt;
+  sp.read_hits = a->seed.hits;
+  sp.read_status = a->reads.status;
+  sp.counters = a->d_counters;
+  sp.queue = a->d_queue;
+  sp.fault = a->d_fault;
   sp.sel_scratch = nullptr;
   sp.sel_scratch_per_wave = 0;
   const uint32_t fill_mode = seed_fill_mode();
@@ -152,27 +152,27 @@ int enqueue_seed_t(thm_aligner* a, uint32_t min_seed_len, bool finish_scan) {
   sp.fill_hist = nullptr;
   if (fill_mode == 2) {
     const uint64_t slots = (std::max(cells, n) + 1) * 8;
-    HIPCHK(a, a->s_fill_keys.ensure(slots * 2));
-    HIPCHK(a, a->s_fill_perm.ensure(slots * 4));
-    HIPCHK(a, a->s_fill_hist.ensure((2 * (FILL_BUCKETS + 1) + 1) * 4));
-    HIPCHK(a, hipMemsetAsync(a->s_fill_hist.p, 0, (2 * (FILL_BUCKETS + 1) + 1) * 4, s));
-    sp.fill_keys = a->s_fill_keys.as<uint16_t>();
-    sp.fill_perm = a->s_fill_perm.as<uint32_t>();
-    sp.fill_hist = a->s_fill_hist.as<unsigned int>();
+    HIPCHK(a, a->seed.fill_keys.ensure(slots));
+    HIPCHK(a, a->seed.fill_perm.ensure(slots));
+    HIPCHK(a, a->seed.fill_hist.ensure(2 * (FILL_BUCKETS + 1) + 1));
+    HIPCHK(a, hipMemsetAsync(a->seed.fill_hist, 0, (2 * (FILL_BUCKETS + 1) + 1) * 4, s));
+    sp.fill_keys = a->seed.fill_keys;
+    sp.fill_perm = a->seed.fill_perm;
+    sp.fill_hist = a->seed.fill_hist;
   }
   if (n_long && seed_select_lds_bytes(max_long) > SEED_SELECT_LDS_LIMIT) {
     // reads of thousands of bases: the selection kernel's per-read lists go to global memory
     const int nb = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)n_blocks, (n_long + 3) / 4));
     sp.sel_scratch_per_wave = (seed_select_scratch_bytes(max_long) + 255) & ~255ull;
-    HIPCHK(a, a->s_sel_scratch.ensure((size_t)nb * 4 * sp.sel_scratch_per_wave + 256));
-    sp.sel_scratch = a->s_sel_scratch.as<uint8_t>();
+    HIPCHK(a, a->seed.sel_scratch.ensure((size_t)nb * 4 * sp.sel_scratch_per_wave, 256));
+    sp.sel_scratch = a->seed.sel_scratch;
   }
   HIPCHK(a, launch_seed(sp, n_blocks, s));
   // hit counts -> offsets of each read's slice (also the Mem offsets of thm_smems_batch)
   if (finish_scan)
-    HIPCHK(a, launch_exclusive_scan_u64(a->s_hits.as<uint64_t>(), a->s_cand_off.as<uint64_t>(), n, a->scan_tmp.as<uint64_t>(), s));
+    HIPCHK(a, launch_exclusive_scan_u64(a->seed.hits, a->seed.cand_off, n, a->seed.scan_tmp, s));
   else
-    HIPCHK(a, launch_scan_tiles_sums_u64(a->s_hits.as<uint64_t>(), a->s_cand_off.as<uint64_t>(), n, a->scan_tmp.as<uint64_t>(), s));
+    HIPCHK(a, launch_scan_tiles_sums_u64(a->seed.hits, a->seed.cand_off, n, a->seed.scan_tmp, s));
   return THM_OK;
 }
 
@@ -183,18 +183,18 @@ int enqueue_seed(thm_aligner* a, uint32_t min_seed_len, bool finish_scan) {
 // the extend stage's lists and the per-read records, one launch (kernels_seed.hip, plan_pack_kernel)
 template <class C>
 int enqueue_plan_pack_t(thm_aligner* a, const PlanParams& pp) {
-  HIPCHK(a, a->e_recs.ensure((a->n_reads + 1) * sizeof(ReadRecT<C>)));
+  HIPCHK(a, a->ext.recs.ensure((a->n_reads + 1) * sizeof(ReadRecT<C>)));
   PackParamsT<C> pk;
   pk.sa = dev_view<C>(a).sa;
-  pk.offsets = a->r_offsets.as<uint64_t>();
+  pk.offsets = a->reads.offsets;
   pk.n_reads = a->n_reads;
-  pk.smems = a->s_smems.as<SmemT<C>>();
-  pk.read_smem_off = a->s_off.as<uint64_t>();
-  pk.read_smem_cnt = a->s_cnt.as<uint32_t>();
-  pk.read_cand_off = a->s_cand_off.as<uint64_t>();
-  pk.tile_offs = a->scan_tmp.as<uint64_t>();
-  pk.fault_seed = a->d_fault.as<int>();
-  pk.recs = a->e_recs.as<ReadRecT<C>>();
+  pk.smems = a->seed.smems.as<SmemT<C>>();
+  pk.read_smem_off = a->seed.off;
+  pk.read_smem_cnt = a->seed.cnt;
+  pk.read_cand_off = a->seed.cand_off;
+  pk.tile_offs = a->seed.scan_tmp;
+  pk.fault_seed = a->d_fault;
+  pk.recs = a->ext.recs.as<ReadRecT<C>>();
   HIPCHK(a, launch_plan_pack(pp, pk, a->stream));
   return THM_OK;
 }
@@ -207,52 +207,52 @@ int enqueue_extend_t(thm_aligner* a, const ExtendPlan& plan) {
   hipStream_t s = a->stream;
   const int cpl = plan.cpl;
   a->fin_blocks = (uint32_t)plan.fin_blocks;
-  HIPCHK(a, a->e_trace.ensure(plan.trace_bytes + 64));
+  HIPCHK(a, a->ext.trace.ensure(plan.trace_bytes + 64));
   // The counter rows are zero from one run to the next (launch_counters_reduce zeroes what it read, and no launch writes
   // past its run's n_rows): only a new allocation is zeroed here -- or the rows of an enqueue that failed half way.
-  HIPCHK(a, a->e_wcnt.ensure(plan.n_rows * THM_N_COUNTERS * 8 + 64));
-  if (a->wcnt_clean_cap != a->e_wcnt.cap) HIPCHK(a, hipMemsetAsync(a->e_wcnt.p, 0, a->e_wcnt.cap, s));
-  a->wcnt_clean_cap = 0;
+  HIPCHK(a, a->ext.wcnt.ensure(plan.n_rows * THM_N_COUNTERS, 64));
+  if (a->ext.wcnt_clean_cap != a->ext.wcnt.cap()) HIPCHK(a, hipMemsetAsync(a->ext.wcnt, 0, a->ext.wcnt.cap(), s));
+  a->ext.wcnt_clean_cap = 0;
   // ---- fast class: the main kernel's parameter block; the other launches take copies of it ----
   ExtendParamsT<C> ep;
   ep.ix = dev_view<C>(a);
-  ep.reads.bases = a->r_san.as<uint8_t>() + 16;
-  ep.reads.offsets = a->r_offsets.as<uint64_t>();
+  ep.reads.bases = a->reads.san + 16;
+  ep.reads.offsets = a->reads.offsets;
   ep.reads.n_reads = n;
   ep.opts = a->run_opts;
-  ep.smems = a->s_smems.as<SmemT<C>>();
+  ep.smems = a->seed.smems.as<SmemT<C>>();
   // one record per read (offsets, SMEM run, candidate slice, first SMEM and its first occurrence): enqueue_plan_pack_t
-  ep.read_recs = a->e_recs.as<ReadRecT<C>>();
-  ep.heavy = a->s_heavy.as<unsigned long long>();
-  ep.heavy_count = a->s_work_counts.as<unsigned long long>() + 2;
-  ep.team = a->s_team.as<unsigned long long>();
-  ep.team_count = a->s_work_counts.as<unsigned long long>() + 7;
+  ep.read_recs = a->ext.recs.as<ReadRecT<C>>();
+  ep.heavy = a->seed.heavy;
+  ep.heavy_count = a->s_work_counts + 2;
+  ep.team = a->seed.team;
+  ep.team_count = a->s_work_counts + 7;
   ep.team_limit = 2u * (uint32_t)a->n_cu;
-  ep.cands = a->e_cands.as<Cand>();
-  ep.cand_cap = a->cand_cap;
-  ep.order = a->e_order.as<uint32_t>();
-  ep.cand_ops = a->e_ops.as<uint8_t>();
-  ep.cand_ops_cap = a->cand_ops_cap;
-  ep.ops_cursor = a->d_cursors.as<unsigned long long>() + 1;
-  ep.read_n_alns = a->e_nalns.as<uint32_t>();
-  ep.read_op_bytes = a->e_opbytes.as<uint64_t>();
-  ep.read_status = a->r_status.as<int32_t>();
-  ep.retry = a->s_slow.as<unsigned long long>();
-  ep.retry_count = a->s_work_counts.as<unsigned long long>() + 5;
-  ep.n_contract = a->s_work_counts.as<unsigned long long>() + 6;
-  ep.counters = a->d_counters.as<unsigned long long>();
+  ep.cands = a->ext.cands;
+  ep.cand_cap = a->ext.cand_cap;
+  ep.order = a->ext.order;
+  ep.cand_ops = a->ext.ops;
+  ep.cand_ops_cap = a->ext.cand_ops_cap;
+  ep.ops_cursor = a->d_cursors + 1;
+  ep.read_n_alns = a->ext.nalns;
+  ep.read_op_bytes = a->ext.opbytes;
+  ep.read_status = a->reads.status;
+  ep.retry = a->seed.slow;
+  ep.retry_count = a->s_work_counts + 5;
+  ep.n_contract = a->s_work_counts + 6;
+  ep.counters = a->d_counters;
   ep.wave_counters = counter_rows(a, plan.row_main);
-  ep.queue = a->d_queue_ext.as<unsigned int>();  // (not the seed stage's words: both sets were zeroed when the run began)
-  ep.fault = a->d_fault.as<int>() + 1;
-  ep.fault_seed = a->d_fault.as<int>();
-  ep.prof = a->d_counters.as<unsigned long long>() + 2 * THM_N_COUNTERS;
+  ep.queue = a->d_queue_ext;  // (not the seed stage's words: both sets were zeroed when the run began)
+  ep.fault = a->d_fault + 1;
+  ep.fault_seed = a->d_fault;
+  ep.prof = a->d_counters + 2 * THM_N_COUNTERS;
   ep.max_read_len = plan.fast_len;
   ep.max_bw = plan.fast_bw;
   if (a->dbg_band_clip) ep.max_bw = std::min<uint32_t>(ep.max_bw, a->dbg_band_clip - 1);  // test hook: reads beyond get THM_ERR_INTERNAL
   ep.mk_cap = FAST_MAX_YCLIPS;
   ep.list_only = 0;
   ep.skip_scan = 0;
-  ep.trace_scratch = a->e_trace.as<unsigned long long>() + plan.trace_main_off / 8;
+  ep.trace_scratch = a->ext.trace.as<unsigned long long>() + plan.trace_main_off / 8;
   ep.slow_scratch = nullptr;
   ep.slow_scratch_per_wave = 0;
   // ---- the finisher (kernels_finish.hip), in front of the wave-per-read kernel ----
@@ -260,20 +260,20 @@ int enqueue_extend_t(thm_aligner* a, const ExtendPlan& plan) {
   // are never the finisher's -- it was measured at 120 - 430 us instead: a team workgroup takes a whole CU's registers, and
   // the main kernel waited for the finisher all that time)
   if (plan.fin_blocks) {
-    HIPCHK(a, a->e_finstats.ensure((size_t)plan.fin_blocks * 4 * 8));
+    HIPCHK(a, a->ext.finstats.ensure((size_t)plan.fin_blocks * 4));
     FinishParamsT<C> fp;
     fp.ix = ep.ix;
     fp.reads = ep.reads;
     fp.opts = ep.opts;
     fp.smems = ep.smems;
-    fp.recs = a->e_recs.as<ReadRecT<C>>();
+    fp.recs = a->ext.recs.as<ReadRecT<C>>();
     fp.cands = ep.cands;
     fp.cand_cap = ep.cand_cap;
     fp.order = ep.order;
     fp.read_n_alns = ep.read_n_alns;
     fp.read_op_bytes = ep.read_op_bytes;
     fp.rows = counter_rows(a, plan.row_fin);
-    fp.stats = a->e_finstats.as<unsigned long long>();
+    fp.stats = a->ext.finstats;
     fp.fault_seed = ep.fault_seed;
     fp.max_read_len = ep.max_read_len;
     fp.max_bw = ep.max_bw;
@@ -303,22 +303,22 @@ int enqueue_extend_t(thm_aligner* a, const ExtendPlan& plan) {
   }
   // ---- slow class (and the fast kernel's retries) ----
   if (plan.slow) {
-    HIPCHK(a, a->e_slow.ensure((size_t)plan.slow_waves * plan.slow_per_wave + 256));
+    HIPCHK(a, a->ext.slow.ensure((size_t)plan.slow_waves * plan.slow_per_wave, 256));
     ep.wave_counters = counter_rows(a, plan.row_slow);
     ep.max_read_len = plan.slow_len;
     ep.max_bw = plan.slow_bw;
     ep.mk_cap = plan.mk_cap_slow;
     ep.list_only = 1;
-    ep.heavy = a->s_slow.as<unsigned long long>();
-    ep.heavy_count = a->s_work_counts.as<unsigned long long>() + 5;
+    ep.heavy = a->seed.slow;
+    ep.heavy_count = a->s_work_counts + 5;
     ep.team = nullptr;
     ep.team_count = nullptr;
-    ep.slow_scratch = a->e_slow.as<uint8_t>();
+    ep.slow_scratch = a->ext.slow;
     ep.slow_scratch_per_wave = plan.slow_per_wave;
     HIPCHK(a, launch_extend(ep, 0, (int)(plan.slow_waves / 4), s));
   }
-  HIPCHK(a, launch_counters_reduce(a->e_wcnt.as<unsigned long long>(), (uint32_t)plan.n_rows, a->d_counters.as<unsigned long long>(), s));
-  a->wcnt_clean_cap = a->e_wcnt.cap;
+  HIPCHK(a, launch_counters_reduce(a->ext.wcnt, (uint32_t)plan.n_rows, a->d_counters, s));
+  a->ext.wcnt_clean_cap = a->ext.wcnt.cap();
   return THM_OK;
 }
 
@@ -334,25 +334,25 @@ int enqueue_run(thm_aligner* a) {
   const uint64_t cand_min = a->dbg_cand_cap ? a->dbg_cand_cap : n * 3 + 1024;
   // op bytes: about 2 L per exonic alignment (genome + transcript op streams), 384 per read at least
   const uint64_t ops_min = a->dbg_ops_cap ? a->dbg_ops_cap : std::max<uint64_t>(n * 384, a->n_bases * 3) + 65536;
-  if (a->cand_cap < cand_min) a->cand_cap = cand_min;
-  if (a->cand_ops_cap < ops_min) a->cand_ops_cap = ops_min;
-  a->out_alns_cap = a->cand_cap;
-  a->out_ops_cap = a->cand_ops_cap;
-  HIPCHK(a, a->e_cands.ensure(a->cand_cap * sizeof(Cand)));
-  HIPCHK(a, a->e_order.ensure(a->cand_cap * 2 * 4));
-  HIPCHK(a, a->e_heavy.ensure((a->cand_cap / 2 + 16) * 2 * 8));
-  HIPCHK(a, a->e_rel.ensure(a->cand_cap * 4));
-  HIPCHK(a, a->e_ops.ensure(a->cand_ops_cap + 64));
-  HIPCHK(a, a->e_nalns.ensure((n + 1) * 4));
-  HIPCHK(a, a->e_opbytes.ensure((n + 1) * 8));
-  HIPCHK(a, a->e_aln_off.ensure((n + 2) * 8));
-  HIPCHK(a, a->e_ops_off.ensure((n + 2) * 8));
-  HIPCHK(a, a->o_alns.ensure(a->cand_cap * sizeof(thm_aln)));
+  if (a->ext.cand_cap < cand_min) a->ext.cand_cap = cand_min;
+  if (a->ext.cand_ops_cap < ops_min) a->ext.cand_ops_cap = ops_min;
+  a->out.alns_cap = a->ext.cand_cap;
+  a->out.ops_cap = a->ext.cand_ops_cap;
+  HIPCHK(a, a->ext.cands.ensure(a->ext.cand_cap));
+  HIPCHK(a, a->ext.order.ensure(a->ext.cand_cap * 2));
+  HIPCHK(a, a->ext.heavy.ensure((a->ext.cand_cap / 2 + 16) * 2));
+  HIPCHK(a, a->ext.rel.ensure(a->ext.cand_cap));
+  HIPCHK(a, a->ext.ops.ensure(a->ext.cand_ops_cap, 64));
+  HIPCHK(a, a->ext.nalns.ensure(n + 1));
+  HIPCHK(a, a->ext.opbytes.ensure(n + 1));
+  HIPCHK(a, a->ext.aln_off.ensure(n + 2));
+  HIPCHK(a, a->ext.ops_off.ensure(n + 2));
+  HIPCHK(a, a->out.alns.ensure(a->ext.cand_cap));
   // (a finished read's op bytes are not taken from the pool: 2 L at most per read on top of what the pool holds)
-  HIPCHK(a, a->o_ops.ensure(a->cand_ops_cap + 2 * a->n_bases + 64));
-  HIPCHK(a, a->s_heavy.ensure((n + 1) * 8));
-  HIPCHK(a, a->s_slow.ensure((n + 1) * 8));
-  HIPCHK(a, a->s_team.ensure((n + 1) * 8));
+  HIPCHK(a, a->out.ops.ensure(a->ext.cand_ops_cap + 2 * a->n_bases, 64));
+  HIPCHK(a, a->seed.heavy.ensure(n + 1));
+  HIPCHK(a, a->seed.slow.ensure(n + 1));
+  HIPCHK(a, a->seed.team.ensure(n + 1));
 
   // length classes for the run's options; lists for the extend stage
   const uint32_t mk_cap_slow = std::max<uint32_t>(a->ix->max_tx_exons, 1);
@@ -366,17 +366,17 @@ int enqueue_run(thm_aligner* a) {
   // it exists, EVERY run on this aligner starts the pool's cursor behind it -- also a run without the finisher (both classes
   // switched off, the problem-parallel path, a batch without a read of the fast class) -- so nothing ever writes there.  The
   // one run that cannot keep it, a pool (test hook) too small to hold it, forgets it: it is written again when next wanted.
-  const bool run_valid = a->ops_run_half > 0 && a->ops_run_ptr == a->e_ops.p && a->ops_run_cap == a->e_ops.cap;
+  const bool run_valid = a->ops_run_half > 0 && a->ops_run_ptr == a->ext.ops.get() && a->ops_run_cap == a->ext.ops.cap();
   if (!run_valid) a->ops_run_half = 0;
   const bool fin_wanted = !a->tpr.use_tpr && a->fin_classes && cls.fast_len > 0;
-  if (fin_wanted && a->ops_run_half < cls.fast_len && fin::run_bytes(cls.fast_len) <= a->cand_ops_cap) {
-    HIPCHK(a, hipMemsetAsync(a->e_ops.p, THM_OP_MATCH, fin::run_bytes(cls.fast_len), s));
-    HIPCHK(a, hipMemsetAsync(a->e_ops.as<uint8_t>() + cls.fast_len, THM_OP_SUBST, 1, s));
-    a->ops_run_ptr = a->e_ops.p;
-    a->ops_run_cap = a->e_ops.cap;
+  if (fin_wanted && a->ops_run_half < cls.fast_len && fin::run_bytes(cls.fast_len) <= a->ext.cand_ops_cap) {
+    HIPCHK(a, hipMemsetAsync(a->ext.ops, THM_OP_MATCH, fin::run_bytes(cls.fast_len), s));
+    HIPCHK(a, hipMemsetAsync(a->ext.ops + cls.fast_len, THM_OP_SUBST, 1, s));
+    a->ops_run_ptr = a->ext.ops.get();
+    a->ops_run_cap = a->ext.ops.cap();
     a->ops_run_half = cls.fast_len;
   }
-  if (a->ops_run_half && fin::run_bytes(a->ops_run_half) > a->cand_ops_cap) a->ops_run_half = 0;  // this run writes over it
+  if (a->ops_run_half && fin::run_bytes(a->ops_run_half) > a->ext.cand_ops_cap) a->ops_run_half = 0;  // this run writes over it
   const uint64_t ops_start = a->ops_run_half ? fin::run_bytes(a->ops_run_half) : 0;
   a->fin_run_classes = (fin_wanted && a->ops_run_half >= cls.fast_len) ? a->fin_classes : 0;
   // every launch of the extend stage: grids, scratch slices, counter rows (extend_plan.h)
@@ -393,23 +393,23 @@ int enqueue_run(thm_aligner* a) {
   pin.fin_classes = a->fin_run_classes;
   const ExtendPlan plan = plan_extend(pin);
   PlanParams pp;
-  pp.offsets = a->r_offsets.as<uint64_t>();
-  pp.read_hits = a->s_hits.as<uint64_t>();
+  pp.offsets = a->reads.offsets;
+  pp.read_hits = a->seed.hits;
   pp.n_reads = n;
   pp.fast_max_len = cls.fast_max;
   pp.slow_max_len = cls.slow_max;
-  pp.heavy = a->s_heavy.as<unsigned long long>();
-  pp.slow = a->s_slow.as<unsigned long long>();
-  pp.team = a->s_team.as<unsigned long long>();
+  pp.heavy = a->seed.heavy;
+  pp.slow = a->seed.slow;
+  pp.team = a->seed.team;
   pp.team_ok = plan.team_ok ? 1u : 0u;
-  pp.total_hits = a->s_cand_off.as<uint64_t>() + n;
+  pp.total_hits = a->seed.cand_off + n;
   pp.team_div = team_div_per_cu() * (uint32_t)std::max(a->n_cu, 1);
   pp.tpr_max_hits = plan.tpr_max_hits;
-  pp.counts = a->s_work_counts.as<unsigned long long>();
-  pp.read_status = a->r_status.as<int32_t>();
-  pp.read_n_alns = a->e_nalns.as<uint32_t>();
-  pp.read_op_bytes = a->e_opbytes.as<uint64_t>();
-  pp.ops_cursor = a->d_cursors.as<unsigned long long>() + 1;
+  pp.counts = a->s_work_counts;
+  pp.read_status = a->reads.status;
+  pp.read_n_alns = a->ext.nalns;
+  pp.read_op_bytes = a->ext.opbytes;
+  pp.ops_cursor = a->d_cursors + 1;
   pp.ops_start = ops_start;
   rc = a->dix->wide ? enqueue_plan_pack_t<uint64_t>(a, pp) : enqueue_plan_pack_t<uint32_t>(a, pp);
   if (rc != THM_OK) return rc;
@@ -419,29 +419,29 @@ int enqueue_run(thm_aligner* a) {
   if (rc != THM_OK) return rc;
   HIPCHK(a, hipEventRecord(a->ev[3], s));
 
-  HIPCHK(a, launch_exclusive_scan2(a->e_nalns.as<uint32_t>(), a->e_opbytes.as<uint64_t>(), a->e_aln_off.as<uint64_t>(),
-                                   a->e_ops_off.as<uint64_t>(), n, a->scan_tmp.as<uint64_t>(), s));
+  HIPCHK(a, launch_exclusive_scan2(a->ext.nalns, a->ext.opbytes, a->ext.aln_off,
+                                   a->ext.ops_off, n, a->seed.scan_tmp, s));
   CompactParams cp;
   cp.n_reads = n;
-  cp.read_cand_off = a->s_cand_off.as<uint64_t>();
-  cp.cands = a->e_cands.as<Cand>();
-  cp.order = a->e_order.as<uint32_t>();
-  cp.cand_ops = a->e_ops.as<uint8_t>();
-  cp.read_n_alns = a->e_nalns.as<uint32_t>();
-  cp.read_aln_off = a->e_aln_off.as<uint64_t>();
-  cp.read_ops_off = a->e_ops_off.as<uint64_t>();
-  cp.read_offsets = a->r_offsets.as<uint64_t>();
-  cp.alns = a->o_alns.as<thm_aln>();
-  cp.ops = a->o_ops.as<uint8_t>();
-  cp.fault = a->d_fault.as<int>();
-  cp.alns_cap = a->cand_cap;
-  cp.ops_cap = a->cand_ops_cap + 2 * a->n_bases;
+  cp.read_cand_off = a->seed.cand_off;
+  cp.cands = a->ext.cands;
+  cp.order = a->ext.order;
+  cp.cand_ops = a->ext.ops;
+  cp.read_n_alns = a->ext.nalns;
+  cp.read_aln_off = a->ext.aln_off;
+  cp.read_ops_off = a->ext.ops_off;
+  cp.read_offsets = a->reads.offsets;
+  cp.alns = a->out.alns;
+  cp.ops = a->out.ops;
+  cp.fault = a->d_fault;
+  cp.alns_cap = a->ext.cand_cap;
+  cp.ops_cap = a->ext.cand_ops_cap + 2 * a->n_bases;
   // (a heavy read has more than 8 alignments and a descriptor stands for 4 of them: cand_cap / 2 entries hold either list)
-  cp.heavy_cap = a->cand_cap / 2 + 16;
-  cp.heavy_cnt = a->d_cursors.as<unsigned long long>() + 2;  // zeroed with the cursors when the batch starts
-  cp.heavy_list = a->e_heavy.as<uint64_t>();
-  cp.heavy_desc = a->e_heavy.as<uint64_t>() + cp.heavy_cap;
-  cp.rel = a->e_rel.as<uint32_t>();
+  cp.heavy_cap = a->ext.cand_cap / 2 + 16;
+  cp.heavy_cnt = a->d_cursors + 2;  // zeroed with the cursors when the batch starts
+  cp.heavy_list = a->ext.heavy;
+  cp.heavy_desc = a->ext.heavy + cp.heavy_cap;
+  cp.rel = a->ext.rel;
   HIPCHK(a, launch_compact(cp, s));
   HIPCHK(a, hipEventRecord(a->ev[4], s));
   return THM_OK;
@@ -456,9 +456,9 @@ int read_status(thm_aligner* a, RunStatus* st) {
   hipStream_t s = a->stream;
   int f[2] = {0, 0};
   unsigned long long cur[2] = {0, 0};
-  HIPCHK(a, hipMemcpyAsync(f, a->d_fault.p, 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(a, hipMemcpyAsync(cur, a->d_cursors.p, 16, hipMemcpyDeviceToHost, s));
-  HIPCHK(a, hipMemcpyAsync(&st->total_hits, a->s_cand_off.as<uint64_t>() + a->n_reads, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(a, hipMemcpyAsync(f, a->d_fault, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(a, hipMemcpyAsync(cur, a->d_cursors, 16, hipMemcpyDeviceToHost, s));
+  HIPCHK(a, hipMemcpyAsync(&st->total_hits, a->seed.cand_off + a->n_reads, 8, hipMemcpyDeviceToHost, s));
   HIPCHK(a, hipStreamSynchronize(s));
   st->fault_seed = f[0];
   st->fault_ext = f[1];
@@ -472,11 +472,11 @@ int expand_mems_t(thm_aligner* a, uint64_t n) {
   ExpandParamsT<C> xp;
   xp.ix = dev_view<C>(a);
   xp.n_reads = n;
-  xp.smems = a->s_smems.as<SmemT<C>>();
-  xp.read_smem_off = a->s_off.as<uint64_t>();
-  xp.read_smem_cnt = a->s_cnt.as<uint32_t>();
-  xp.read_mem_off = a->s_cand_off.as<uint64_t>();
-  xp.mems = a->o_mems.as<thm_mem>();
+  xp.smems = a->seed.smems.as<SmemT<C>>();
+  xp.read_smem_off = a->seed.off;
+  xp.read_smem_cnt = a->seed.cnt;
+  xp.read_mem_off = a->seed.cand_off;
+  xp.mems = a->out.mems;
   HIPCHK(a, launch_expand(xp, a->stream));
   return THM_OK;
 }
@@ -523,27 +523,27 @@ int batch_length_classes(thm_aligner* a, const uint64_t* offsets, uint64_t n_rea
   return THM_OK;
 }
 
-int fetch_batch_sizes(thm_aligner* a, HBuf* h_off, const uint64_t* d_extra, uint64_t* extra, BatchSizes* z) {
+int fetch_batch_sizes(thm_aligner* a, HArr<uint64_t>* h_off, const uint64_t* d_extra, uint64_t* extra, BatchSizes* z) {
   const uint64_t n = a->n_reads;
   hipStream_t s = a->stream;
   uint64_t w[2] = {0, 0}, n_contract = 0;
   uint64_t* sizes = w;  // alignments, op bytes
   if (h_off) {
-    HIPCHK(a, h_off->ensure((n + 2) * 8));
-    sizes = h_off->as<uint64_t>() + n;
-    HIPCHK(a, hipMemcpyAsync(h_off->p, a->e_aln_off.p, (n + 1) * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(a, h_off->ensure(n + 2));
+    sizes = *h_off + n;
+    HIPCHK(a, hipMemcpyAsync(*h_off, a->ext.aln_off, (n + 1) * 8, hipMemcpyDeviceToHost, s));
   } else {
-    HIPCHK(a, hipMemcpyAsync(&sizes[0], a->e_aln_off.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(a, hipMemcpyAsync(&sizes[0], a->ext.aln_off + n, 8, hipMemcpyDeviceToHost, s));
   }
-  HIPCHK(a, hipMemcpyAsync(&sizes[1], a->e_ops_off.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(a, hipMemcpyAsync(&sizes[1], a->ext.ops_off + n, 8, hipMemcpyDeviceToHost, s));
   if (d_extra) HIPCHK(a, hipMemcpyAsync(extra, d_extra, 8, hipMemcpyDeviceToHost, s));
   // per-read statuses travel only when a read can have failed: reads beyond the classes are known to the host,
   // out-of-contract reads are counted by the device (the word behind the list counters)
-  HIPCHK(a, hipMemcpyAsync(&n_contract, a->s_work_counts.as<uint64_t>() + 6, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(a, hipMemcpyAsync(&n_contract, a->s_work_counts + 6, 8, hipMemcpyDeviceToHost, s));
   HIPCHK(a, hipStreamSynchronize(s));
   z->n_alns = sizes[0];
   z->n_ops = sizes[1];
-  if (z->n_alns > a->out_alns_cap || z->n_ops > a->out_ops_cap) return fail(a, THM_ERR_INTERNAL, "compacted batch exceeds its pools");
+  if (z->n_alns > a->out.alns_cap || z->n_ops > a->out.ops_cap) return fail(a, THM_ERR_INTERNAL, "compacted batch exceeds its pools");
   uint64_t n_beyond = a->n_over;
   for (const auto& lc : a->len_hist)
     if (lc.first > a->slow_max_len) n_beyond += lc.second;
@@ -551,18 +551,18 @@ int fetch_batch_sizes(thm_aligner* a, HBuf* h_off, const uint64_t* d_extra, uint
   return THM_OK;
 }
 
-int enqueue_statuses(thm_aligner* a, bool any_failed, HBuf& h_stat) {
+int enqueue_statuses(thm_aligner* a, bool any_failed, HArr<int32_t>& h_stat) {
   if (!any_failed) return THM_OK;
-  HIPCHK(a, h_stat.ensure((a->n_reads + 1) * 4));
-  HIPCHK(a, hipMemcpyAsync(h_stat.p, a->r_status.p, a->n_reads * 4, hipMemcpyDeviceToHost, a->stream));
+  HIPCHK(a, h_stat.ensure(a->n_reads + 1));
+  HIPCHK(a, hipMemcpyAsync(h_stat, a->reads.status, a->n_reads * 4, hipMemcpyDeviceToHost, a->stream));
   return THM_OK;
 }
 
-void failed_reads(const thm_aligner* a, bool any_failed, const HBuf& h_stat, uint64_t* n_failed, const int32_t** status) {
+void failed_reads(const thm_aligner* a, bool any_failed, const HArr<int32_t>& h_stat, uint64_t* n_failed, const int32_t** status) {
   *n_failed = 0;
   *status = nullptr;
   if (!any_failed) return;
-  const int32_t* st = h_stat.as<int32_t>();
+  const int32_t* st = h_stat;
   uint64_t bad = 0;
   for (uint64_t i = 0; i < a->n_reads; i++) bad += st[i] != THM_OK;
   *n_failed = bad;
@@ -572,10 +572,10 @@ void failed_reads(const thm_aligner* a, bool any_failed, const HBuf& h_stat, uin
 CigarParams compacted_cigar_params(const thm_aligner* a, const BatchSizes& z) {
   CigarParams p;
   memset(&p, 0, sizeof p);
-  p.ops = a->o_ops.as<uint8_t>();
+  p.ops = a->out.ops;
   p.ops_bytes = z.n_ops;
   p.n_streams = 2 * z.n_alns;
-  p.alns = a->o_alns.as<thm_aln>();
+  p.alns = a->out.alns;
   return p;
 }
 
@@ -585,13 +585,13 @@ int32_t thm_batch_upload(thm_aligner* a, const uint8_t* bases, const uint64_t* o
   if (!a || !offsets || (!bases && n_reads && offsets[n_reads] > 0)) return THM_ERR_INVALID_ARG;
   HIPCHK(a, hipSetDevice(a->device));
   a->uploaded = a->ran = a->synced = false;
-  a->reads_named = false;  // (thm_batch_upload_reads sets it)
+  a->bam.reads_named = false;  // (thm_batch_upload_reads sets it)
   const int rc = batch_length_classes(a, offsets, n_reads);
   if (rc != THM_OK) return rc;
-  HIPCHK(a, a->r_bases.ensure(a->n_bases + 64));
-  HIPCHK(a, a->r_offsets.ensure((n_reads + 1) * 8));
-  if (a->n_bases) HIPCHK(a, hipMemcpyAsync(a->r_bases.p, bases, a->n_bases, hipMemcpyHostToDevice, a->stream));
-  HIPCHK(a, hipMemcpyAsync(a->r_offsets.p, offsets, (n_reads + 1) * 8, hipMemcpyHostToDevice, a->stream));
+  HIPCHK(a, a->reads.bases.ensure(a->n_bases, 64));
+  HIPCHK(a, a->reads.offsets.ensure(n_reads + 1));
+  if (a->n_bases) HIPCHK(a, hipMemcpyAsync(a->reads.bases, bases, a->n_bases, hipMemcpyHostToDevice, a->stream));
+  HIPCHK(a, hipMemcpyAsync(a->reads.offsets, offsets, (n_reads + 1) * 8, hipMemcpyHostToDevice, a->stream));
   HIPCHK(a, hipStreamSynchronize(a->stream));
   a->uploaded = true;
   return THM_OK;
@@ -628,12 +628,12 @@ int32_t thm_batch_sync(thm_aligner* a) {
       return THM_OK;
     }
     // grow whatever overflowed and replay (counters of the failed attempt are discarded by the caller's reset)
-    if (st.fault_seed) a->smem_cap = std::max<uint64_t>(a->smem_cap * 2, st.smem_used + 1024);
-    if (st.total_hits > a->cand_cap) a->cand_cap = st.total_hits + st.total_hits / 8 + 1024;
-    if (st.ops_used > a->cand_ops_cap) a->cand_ops_cap = st.ops_used + st.ops_used / 2 + 65536;
-    if (a->cand_cap * sizeof(Cand) > (160ull << 30))
+    if (st.fault_seed) a->seed.smem_cap = std::max<uint64_t>(a->seed.smem_cap * 2, st.smem_used + 1024);
+    if (st.total_hits > a->ext.cand_cap) a->ext.cand_cap = st.total_hits + st.total_hits / 8 + 1024;
+    if (st.ops_used > a->ext.cand_ops_cap) a->ext.cand_ops_cap = st.ops_used + st.ops_used / 2 + 65536;
+    if (a->ext.cand_cap * sizeof(Cand) > (160ull << 30))
       return fail(a, THM_ERR_OOM, "batch has %llu seed hits: candidate pool would exceed 160 GiB", st.total_hits);
-    HIPCHK(a, hipMemcpyAsync(a->d_counters.p, a->d_counters.as<uint8_t>() + THM_N_COUNTERS * 8, THM_N_COUNTERS * 8,
+    HIPCHK(a, hipMemcpyAsync(a->d_counters, a->d_counters + THM_N_COUNTERS, THM_N_COUNTERS * 8,
                              hipMemcpyDeviceToDevice, a->stream));
     a->n_replays++;
     rc = enqueue_run(a);
@@ -649,29 +649,25 @@ int32_t thm_batch_fetch(thm_aligner* a, thm_batch_view* out) {
   if (rc != THM_OK) return rc;
   const uint64_t n = a->n_reads;
   hipStream_t s = a->stream;
-  const int k = a->r_cur ^= 1;  // the other set still backs the previous view
-  HBuf& h_off = a->r_off[k];
-  HBuf& h_alns = a->r_alns[k];
-  HBuf& h_ops = a->r_ops[k];
-  HBuf& h_stat = a->r_stat[k];
+  BatchHost& h = a->out.host.next();  // the other set still backs the previous view
   BatchSizes z;  // offsets, and behind them the op-pool size, in one round trip
-  rc = fetch_batch_sizes(a, &h_off, nullptr, nullptr, &z);
+  rc = fetch_batch_sizes(a, &h.off, nullptr, nullptr, &z);
   if (rc != THM_OK) return rc;
   const uint64_t n_alns = z.n_alns, n_ops = z.n_ops;
-  HIPCHK(a, h_alns.ensure(n_alns * sizeof(thm_aln)));
-  HIPCHK(a, h_ops.ensure(n_ops));
-  if (n_alns) HIPCHK(a, hipMemcpyAsync(h_alns.p, a->o_alns.p, n_alns * sizeof(thm_aln), hipMemcpyDeviceToHost, s));
-  if (n_ops) HIPCHK(a, hipMemcpyAsync(h_ops.p, a->o_ops.p, n_ops, hipMemcpyDeviceToHost, s));
-  rc = enqueue_statuses(a, z.any_failed, h_stat);
+  HIPCHK(a, h.alns.ensure(n_alns));
+  HIPCHK(a, h.ops.ensure(n_ops));
+  if (n_alns) HIPCHK(a, hipMemcpyAsync(h.alns, a->out.alns, n_alns * sizeof(thm_aln), hipMemcpyDeviceToHost, s));
+  if (n_ops) HIPCHK(a, hipMemcpyAsync(h.ops, a->out.ops, n_ops, hipMemcpyDeviceToHost, s));
+  rc = enqueue_statuses(a, z.any_failed, h.stat);
   if (rc != THM_OK) return rc;
   HIPCHK(a, hipStreamSynchronize(s));
   out->n_reads = n;
   out->n_alns = n_alns;
   out->n_op_bytes = n_ops;
-  out->read_aln_off = h_off.as<uint64_t>();
-  out->alns = h_alns.as<thm_aln>();
-  out->ops = h_ops.as<uint8_t>();
-  failed_reads(a, z.any_failed, h_stat, &out->n_failed_reads, &out->read_status);
+  out->read_aln_off = h.off;
+  out->alns = h.alns;
+  out->ops = h.ops;
+  failed_reads(a, z.any_failed, h.stat, &out->n_failed_reads, &out->read_status);
   return THM_OK;
 }
 
@@ -697,7 +693,7 @@ int32_t thm_smems_batch(thm_aligner* a, const uint8_t* bases, const uint64_t* of
   for (int attempt = 0;; attempt++) {
     // (the counters' snapshot is taken by the seed stage's first kernel; a replay starts from it)
     if (attempt > 0)
-      HIPCHK(a, hipMemcpyAsync(a->d_counters.p, a->d_counters.as<uint8_t>() + THM_N_COUNTERS * 8, THM_N_COUNTERS * 8,
+      HIPCHK(a, hipMemcpyAsync(a->d_counters, a->d_counters + THM_N_COUNTERS, THM_N_COUNTERS * 8,
                                hipMemcpyDeviceToDevice, s));
     rc = enqueue_seed(a, (uint32_t)min_seed_len, true);
     if (rc != THM_OK) return rc;
@@ -706,18 +702,18 @@ int32_t thm_smems_batch(thm_aligner* a, const uint8_t* bases, const uint64_t* of
     if (!st.fault_seed) break;
     if (attempt >= 6) return fail(a, THM_ERR_INTERNAL, "smem pool kept overflowing");
     a->n_replays++;
-    a->smem_cap = std::max<uint64_t>(a->smem_cap * 2, st.smem_used + 1024);
+    a->seed.smem_cap = std::max<uint64_t>(a->seed.smem_cap * 2, st.smem_used + 1024);
   }
   a->uploaded = false;  // the seed-only pass leaves no aligned batch behind
   const uint64_t n_mems = st.total_hits;
   if (n_mems * sizeof(thm_mem) > (64ull << 30)) return fail(a, THM_ERR_OOM, "%llu seed hits in one batch", st.total_hits);
-  HIPCHK(a, a->o_mems.ensure(n_mems * sizeof(thm_mem) + 64));
+  HIPCHK(a, a->out.mems.ensure(n_mems, 64));
   rc = a->dix->wide ? expand_mems_t<uint64_t>(a, n) : expand_mems_t<uint32_t>(a, n);
   if (rc != THM_OK) return rc;
   a->h_off.assign(n + 1, 0);
   a->h_mems.resize(n_mems);
-  HIPCHK(a, hipMemcpyAsync(a->h_off.data(), a->s_cand_off.p, (n + 1) * 8, hipMemcpyDeviceToHost, s));
-  if (n_mems) HIPCHK(a, hipMemcpyAsync(a->h_mems.data(), a->o_mems.p, n_mems * sizeof(thm_mem), hipMemcpyDeviceToHost, s));
+  HIPCHK(a, hipMemcpyAsync(a->h_off.data(), a->seed.cand_off, (n + 1) * 8, hipMemcpyDeviceToHost, s));
+  if (n_mems) HIPCHK(a, hipMemcpyAsync(a->h_mems.data(), a->out.mems, n_mems * sizeof(thm_mem), hipMemcpyDeviceToHost, s));
   HIPCHK(a, hipStreamSynchronize(s));
   out->n_reads = n;
   out->n_mems = n_mems;

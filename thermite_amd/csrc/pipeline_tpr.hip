@@ -19,27 +19,27 @@ int enqueue_tpr_rounds_t(thm_aligner* a, const ExtendPlan& plan, const ExtendPar
   hipStream_t s = a->stream;
   TprState& t = a->tpr;
   const uint64_t rec_cap = std::min<uint64_t>(4 * n + 65536, 64ull << 20);
-  HIPCHK(a, t.t_memos.ensure(n * sizeof(ReadMemo) + 64));
-  HIPCHK(a, t.t_recs.ensure(rec_cap * sizeof(DpRec) + 64));
-  HIPCHK(a, t.t_qlist.ensure((size_t)DP_NQ * rec_cap * 4 + 64));
-  HIPCHK(a, t.t_act[0].ensure(n * 4 + 64));
-  HIPCHK(a, t.t_act[1].ensure(n * 4 + 64));
-  HIPCHK(a, t.t_bail.ensure((n + 1) * 8));
-  HIPCHK(a, t.t_queue2.ensure(thm::QUEUE_BYTES));
-  HIPCHK(a, hipMemsetAsync(t.t_queue2.p, 0, thm::QUEUE_BYTES, s));
+  HIPCHK(a, t.t_memos.ensure(n, 64));
+  HIPCHK(a, t.t_recs.ensure(rec_cap, 64));
+  HIPCHK(a, t.t_qlist.ensure((size_t)DP_NQ * rec_cap, 64));
+  HIPCHK(a, t.t_act[0].ensure(n, 64));
+  HIPCHK(a, t.t_act[1].ensure(n, 64));
+  HIPCHK(a, t.t_bail.ensure(n + 1));
+  HIPCHK(a, t.t_queue2.ensure(thm::QUEUE_BYTES / sizeof(unsigned int)));  // (a multiple of 16: aligner_internal.h)
+  HIPCHK(a, hipMemsetAsync(t.t_queue2, 0, thm::QUEUE_BYTES, s));
   HIPCHK(a, t.t_ctl.ensure(TPRC_BYTES));
   HIPCHK(a, hipMemsetAsync(t.t_ctl.p, 0, TPRC_BYTES, s));
   unsigned long long* ctl = t.t_ctl.as<unsigned long long>();
   TprParamsT<C> tq;
-  tq.recs_rw = a->e_recs.as<ReadRecT<C>>();
-  tq.memos = t.t_memos.as<ReadMemo>();
-  tq.recs = t.t_recs.as<DpRec>();
+  tq.recs_rw = a->ext.recs.as<ReadRecT<C>>();
+  tq.memos = t.t_memos;
+  tq.recs = t.t_recs;
   tq.rec_cap = rec_cap;
   tq.rec_cursor = ctl + TPRC_REC_CUR;
-  tq.q_list = t.t_qlist.as<uint32_t>();
+  tq.q_list = t.t_qlist;
   tq.q_stride = rec_cap;
   tq.q_cur = ctl + TPRC_Q_CUR;
-  tq.bail = t.t_bail.as<unsigned long long>();
+  tq.bail = t.t_bail;
   tq.bail_count = ctl + TPRC_BAIL_CNT;
   tq.team = nullptr;  // (the team kernel is running already; a read of this path has fewer hits than it takes anyway)
   tq.team_count = nullptr;
@@ -66,10 +66,10 @@ int enqueue_tpr_rounds_t(thm_aligner* a, const ExtendPlan& plan, const ExtendPar
   }
   // hit summaries: everything about a hit that does not depend on the state align_read carries, all hits side by side
   {
-    const uint64_t slot_cap = a->cand_cap;
-    HIPCHK(a, t.t_hdr.ensure(slot_cap * sizeof(HitHdr) + 64));
-    HIPCHK(a, t.t_sums.ensure(slot_cap * sizeof(HitSum) + 64));
-    HIPCHK(a, hipMemsetAsync(t.t_hdr.p, 0xFF, slot_cap * sizeof(HitHdr), s));
+    const uint64_t slot_cap = a->ext.cand_cap;
+    HIPCHK(a, t.t_hdr.ensure(slot_cap, 64));
+    HIPCHK(a, t.t_sums.ensure(slot_cap, 64));
+    HIPCHK(a, hipMemsetAsync(t.t_hdr, 0xFF, slot_cap * sizeof(HitHdr), s));
     HitParamsT<C> hq;
     hq.ix = ep.ix;
     hq.reads = ep.reads;
@@ -78,14 +78,14 @@ int enqueue_tpr_rounds_t(thm_aligner* a, const ExtendPlan& plan, const ExtendPar
     hq.read_recs = ep.read_recs;
     hq.max_read_len = ep.max_read_len;
     hq.max_hits = TPR_MAX_HITS;
-    hq.hdr = t.t_hdr.as<HitHdr>();
-    hq.sums = t.t_sums.as<HitSum>();
-    hq.total_hits = a->s_cand_off.as<uint64_t>() + n;
+    hq.hdr = t.t_hdr;
+    hq.sums = t.t_sums;
+    hq.total_hits = a->seed.cand_off + n;
     hq.slot_cap = slot_cap;
-    hq.fault_seed = a->d_fault.as<int>();
+    hq.fault_seed = a->d_fault;
     HIPCHK(a, launch_hit_expand(hq, s));
     HIPCHK(a, launch_hit_summaries(hq, a->n_cu * 12, s));
-    tq.sums = t.t_sums.as<HitSum>();
+    tq.sums = t.t_sums;
   }
   // The reads with HEAVY_HITS hits and more (the lists of plan_kernel) are the wave-per-read / workgroup-per-read
   // kernels': they run BESIDE the rounds below, on their own streams.
@@ -102,14 +102,14 @@ int enqueue_tpr_rounds_t(thm_aligner* a, const ExtendPlan& plan, const ExtendPar
     HIPCHK(a, hipEventRecord(t.ev_join3, t.stream3));
   }
   // round 0's list: the reads of this path by descending hit count
-  HIPCHK(a, launch_tpr_order(a->e_recs.as<ReadRecT<C>>(), n, ep.max_read_len, TPR_MAX_HITS, ctl + TPRC_BINS, t.t_act[0].as<uint32_t>(), ctl + TPRC_N_ACT,
-                             a->d_fault.as<int>(), s));
+  HIPCHK(a, launch_tpr_order(a->ext.recs.as<ReadRecT<C>>(), n, ep.max_read_len, TPR_MAX_HITS, ctl + TPRC_BINS, t.t_act[0], ctl + TPRC_N_ACT,
+                             a->d_fault, s));
   const int n_rounds = t.tpr_rounds;  // rounds of requests a read may take (then: the wave-per-read kernel)
   for (int r = 0; r <= n_rounds; r++) {
     tq.round = (uint32_t)r;
-    tq.act_in = t.t_act[r & 1].as<uint32_t>();
+    tq.act_in = t.t_act[r & 1];
     tq.n_act_in = ctl + TPRC_N_ACT + r;
-    tq.act_out = t.t_act[(r + 1) & 1].as<uint32_t>();
+    tq.act_out = t.t_act[(r + 1) & 1];
     tq.n_act_out = ctl + TPRC_N_ACT + r + 1;
     tq.last_round = r == n_rounds ? 1u : 0u;
     HIPCHK(a, launch_extend_ctl(zp, tq, plan.ctl_blocks, s));
@@ -131,11 +131,11 @@ int enqueue_tpr_rounds_t(thm_aligner* a, const ExtendPlan& plan, const ExtendPar
   {
     ExtendParamsT<C> bp = ep;
     bp.skip_scan = 1;
-    bp.heavy = t.t_bail.as<unsigned long long>();
+    bp.heavy = t.t_bail;
     bp.heavy_count = ctl + TPRC_BAIL_CNT;
     bp.team = nullptr;
     bp.team_count = nullptr;
-    bp.queue = t.t_queue2.as<unsigned int>();
+    bp.queue = t.t_queue2;
     bp.wave_counters = counter_rows(a, plan.row_tpr_bail);
     HIPCHK(a, launch_extend(bp, plan.cpl, plan.bail_blocks, s));
   }

@@ -9,6 +9,7 @@
 #include <cstring>
 
 #include "aligner_internal.h"
+#include "launch_io.h"
 #include "quant_device.h"
 
 using namespace thm;
@@ -17,19 +18,26 @@ namespace {
 
 constexpr uint64_t MAX_ROWS = 0xFFFFFFFEull;  // a permutation entry is 32 bits, 0xFFFFFFFF the "not found" of the lookup
 
+// bytes held by some buffers
+template <class... B>
+size_t held(const B&... b) {
+  return (size_t(0) + ... + b.cap());
+}
+
 // junction rows on the device, an array per field
 struct RowBuf {
-  DBuf hi, lo, nu, nm, ov;
+  DArr<uint64_t> hi, lo, nu, nm;
+  DArr<uint32_t> ov;
   hipError_t ensure(uint64_t n) {
-    hipError_t e = hi.ensure(n * 8);
-    if (e == hipSuccess) e = lo.ensure(n * 8);
-    if (e == hipSuccess) e = nu.ensure(n * 8);
-    if (e == hipSuccess) e = nm.ensure(n * 8);
-    if (e == hipSuccess) e = ov.ensure(n * 4);
+    hipError_t e = hi.ensure(n);
+    if (e == hipSuccess) e = lo.ensure(n);
+    if (e == hipSuccess) e = nu.ensure(n);
+    if (e == hipSuccess) e = nm.ensure(n);
+    if (e == hipSuccess) e = ov.ensure(n);
     return e;
   }
-  QuantRows rows() const { return QuantRows{hi.as<uint64_t>(), lo.as<uint64_t>(), nu.as<uint64_t>(), nm.as<uint64_t>(), ov.as<uint32_t>()}; }
-  size_t bytes() const { return hi.cap + lo.cap + nu.cap + nm.cap + ov.cap; }
+  QuantRows rows() const { return QuantRows{hi, lo, nu, nm, ov}; }
+  size_t bytes() const { return hi.cap() + lo.cap() + nu.cap() + nm.cap() + ov.cap(); }
 };
 
 }  // namespace
@@ -37,27 +45,34 @@ struct RowBuf {
 struct thm_quant {
   thm_aligner* a = nullptr;
   uint32_t n_sq = 0;
-  std::vector<int32_t> h_ref_sq;  // what bt_ref_sq holds, for the checks of thm_quant_add_view
-  DBuf tx_forward;                // [n_txs] thm_tx::strand
-  DBuf genes;                     // [n_genes * 4] u64, the running gene table
+  std::vector<int32_t> h_ref_sq;  // what bam.ref_sq holds, for the checks of thm_quant_add_view
+  DArr<uint8_t> tx_forward;       // [n_txs] thm_tx::strand
+  DArr<unsigned long long> genes;  // [n_genes * 4], the running gene table
   RowBuf tab[2];                  // the running junction table, sorted, in tab[cur]; the other takes the next merge
   int cur = 0;
   uint64_t n_tab = 0;
   thm_quant_totals totals;
   // one batch's scratch
   RowBuf hits, red, cat;
-  DBuf hit_cnt, hit_off, multi, scan_tmp, d_tot, perm_a, perm_b, key_a, key_b, cub_tmp, flag, first, where, is_new, new_at;
-  DBuf v_off, v_alns, v_dig, v_words, v_stat;  // the view thm_quant_add_view uploads
-  DBuf d_rows;                                 // the table as records, for the fetch
-  HBuf h_out;
+  DArr<uint64_t> hit_cnt, hit_off, scan_tmp, key_a, key_b, flag, first, is_new, new_at;
+  DArr<uint8_t> multi;
+  DArr<uint32_t> perm_a, perm_b, where;
+  DBuf d_tot;    // the totals (unsigned long long) and behind them the `bad` word
+  DBuf cub_tmp;  // hipcub's scratch
+  // the view thm_quant_add_view uploads
+  DArr<uint64_t> v_off;
+  DArr<thm_aln> v_alns;
+  DArr<thm_aln_digest> v_dig;
+  DArr<uint32_t> v_words;
+  DArr<int32_t> v_stat;
+  DArr<thm_quant_junction> d_rows;  // the table as records, for the fetch
+  HBuf h_out;                       // the genes, and behind them the junctions
   Event ev[2], ev_fetch[2];
 
   uint64_t held_bytes() const {
-    size_t n = tx_forward.cap + genes.cap + tab[0].bytes() + tab[1].bytes() + hits.bytes() + red.bytes() + cat.bytes() + d_rows.cap;
-    for (const DBuf* b : {&hit_cnt, &hit_off, &multi, &scan_tmp, &d_tot, &perm_a, &perm_b, &key_a, &key_b, &cub_tmp, &flag, &first, &where,
-                          &is_new, &new_at, &v_off, &v_alns, &v_dig, &v_words, &v_stat})
-      n += b->cap;
-    return n;
+    return tab[0].bytes() + tab[1].bytes() + hits.bytes() + red.bytes() + cat.bytes() + d_tot.cap + cub_tmp.cap +
+           held(tx_forward, genes, d_rows, hit_cnt, hit_off, multi, scan_tmp, perm_a, perm_b, key_a, key_b, flag, first, where, is_new, new_at,
+                v_off, v_alns, v_dig, v_words, v_stat);
   }
 };
 
@@ -70,15 +85,15 @@ int sort_reduce(thm_quant* q, const QuantRows& in, uint64_t n, RowBuf& out, uint
   hipStream_t st = a->stream;
   *m = 0;
   if (n == 0) return THM_OK;
-  HIPCHK(a, q->perm_a.ensure(n * 4));
-  HIPCHK(a, q->perm_b.ensure(n * 4));
-  HIPCHK(a, q->key_a.ensure(n * 8));
-  HIPCHK(a, q->key_b.ensure(n * 8));
-  HIPCHK(a, q->flag.ensure((n + 1) * 8));
-  HIPCHK(a, q->first.ensure((n + 2) * 8));
-  HIPCHK(a, q->scan_tmp.ensure(scan_tmp_entries(n + 1) * 8 + 64));
-  uint32_t *pa = q->perm_a.as<uint32_t>(), *pb = q->perm_b.as<uint32_t>();
-  uint64_t *ka = q->key_a.as<uint64_t>(), *kb = q->key_b.as<uint64_t>();
+  HIPCHK(a, q->perm_a.ensure(n));
+  HIPCHK(a, q->perm_b.ensure(n));
+  HIPCHK(a, q->key_a.ensure(n));
+  HIPCHK(a, q->key_b.ensure(n));
+  HIPCHK(a, q->flag.ensure(n + 1));
+  HIPCHK(a, q->first.ensure(n + 2));
+  HIPCHK(a, scan_reserve(q->scan_tmp, n));
+  uint32_t *pa = q->perm_a, *pb = q->perm_b;
+  uint64_t *ka = q->key_a, *kb = q->key_b;
   const int hi_bits = quant::key_hi_bits(q->n_sq);
   size_t b1 = 0, b2 = 0;
   HIPCHK(a, hipcub::DeviceRadixSort::SortPairs(nullptr, b1, in.lo, kb, pa, pb, n, 0, quant::KEY_LO_BITS, st));
@@ -96,18 +111,17 @@ int sort_reduce(thm_quant* q, const QuantRows& in, uint64_t n, RowBuf& out, uint
   p.perm = pa;
   p.s_hi = kb;
   p.n = n;
-  p.flag = q->flag.as<uint64_t>();
-  p.first = q->first.as<uint64_t>();
+  p.flag = q->flag;
+  p.first = q->first;
   HIPCHK(a, launch_quant_heads(p, st));
-  HIPCHK(a, launch_exclusive_scan_u64(p.flag, q->first.as<uint64_t>(), n, q->scan_tmp.as<uint64_t>(), st));
   unsigned long long n_keys = 0;
-  HIPCHK(a, hipMemcpyAsync(&n_keys, q->first.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, st));
+  if (const int rc = scan_u64(a, q->scan_tmp, p.flag, q->first, n, st, &n_keys); rc != THM_OK) return rc;
   HIPCHK(a, hipStreamSynchronize(st));
   if (n_keys == 0 || n_keys > n) return fail(a, THM_ERR_INTERNAL, "thm_quant: %llu keys among %llu rows", n_keys, (unsigned long long)n);
   HIPCHK(a, out.ensure(n_keys));
-  HIPCHK(a, hipMemsetAsync(out.nu.p, 0, n_keys * 8, st));
-  HIPCHK(a, hipMemsetAsync(out.nm.p, 0, n_keys * 8, st));
-  HIPCHK(a, hipMemsetAsync(out.ov.p, 0, n_keys * 4, st));
+  HIPCHK(a, hipMemsetAsync(out.nu, 0, n_keys * 8, st));
+  HIPCHK(a, hipMemsetAsync(out.nm, 0, n_keys * 8, st));
+  HIPCHK(a, hipMemsetAsync(out.ov, 0, n_keys * 4, st));
   p.out = out.rows();
   HIPCHK(a, launch_quant_reduce(p, st));
   *m = n_keys;
@@ -120,23 +134,22 @@ int merge_rows(thm_quant* q, uint64_t n_red) {
   thm_aligner* a = q->a;
   hipStream_t st = a->stream;
   const uint64_t n_tab = q->n_tab;
-  HIPCHK(a, q->where.ensure(n_red * 4));
-  HIPCHK(a, q->is_new.ensure((n_red + 1) * 8));
-  HIPCHK(a, q->new_at.ensure((n_red + 2) * 8));
-  HIPCHK(a, q->scan_tmp.ensure(scan_tmp_entries(n_red + 1) * 8 + 64));
+  HIPCHK(a, q->where.ensure(n_red));
+  HIPCHK(a, q->is_new.ensure(n_red + 1));
+  HIPCHK(a, q->new_at.ensure(n_red + 2));
+  HIPCHK(a, scan_reserve(q->scan_tmp, n_red));
   QuantMergeParams p;
   memset(&p, 0, sizeof p);
   p.tab = q->tab[q->cur].rows();
   p.n_tab = n_tab;
   p.red = q->red.rows();
   p.n_red = n_red;
-  p.where = q->where.as<uint32_t>();
-  p.is_new = q->is_new.as<uint64_t>();
-  p.new_at = q->new_at.as<uint64_t>();
+  p.where = q->where;
+  p.is_new = q->is_new;
+  p.new_at = q->new_at;
   HIPCHK(a, launch_quant_lookup(p, st));
-  HIPCHK(a, launch_exclusive_scan_u64(p.is_new, q->new_at.as<uint64_t>(), n_red, q->scan_tmp.as<uint64_t>(), st));
   unsigned long long n_new = 0;
-  HIPCHK(a, hipMemcpyAsync(&n_new, q->new_at.as<uint64_t>() + n_red, 8, hipMemcpyDeviceToHost, st));
+  if (const int rc = scan_u64(a, q->scan_tmp, p.is_new, q->new_at, n_red, st, &n_new); rc != THM_OK) return rc;
   HIPCHK(a, hipStreamSynchronize(st));
   if (n_new > n_red) return fail(a, THM_ERR_INTERNAL, "thm_quant: %llu new keys among %llu rows", n_new, (unsigned long long)n_red);
   const uint64_t n_cat = n_tab + n_new;
@@ -147,11 +160,11 @@ int merge_rows(thm_quant* q, uint64_t n_red) {
   if (n_new == 0) return THM_OK;
   if (n_tab) {
     const RowBuf& t = q->tab[q->cur];
-    HIPCHK(a, hipMemcpyAsync(q->cat.hi.p, t.hi.p, n_tab * 8, hipMemcpyDeviceToDevice, st));
-    HIPCHK(a, hipMemcpyAsync(q->cat.lo.p, t.lo.p, n_tab * 8, hipMemcpyDeviceToDevice, st));
-    HIPCHK(a, hipMemcpyAsync(q->cat.nu.p, t.nu.p, n_tab * 8, hipMemcpyDeviceToDevice, st));
-    HIPCHK(a, hipMemcpyAsync(q->cat.nm.p, t.nm.p, n_tab * 8, hipMemcpyDeviceToDevice, st));
-    HIPCHK(a, hipMemcpyAsync(q->cat.ov.p, t.ov.p, n_tab * 4, hipMemcpyDeviceToDevice, st));
+    HIPCHK(a, hipMemcpyAsync(q->cat.hi, t.hi, n_tab * 8, hipMemcpyDeviceToDevice, st));
+    HIPCHK(a, hipMemcpyAsync(q->cat.lo, t.lo, n_tab * 8, hipMemcpyDeviceToDevice, st));
+    HIPCHK(a, hipMemcpyAsync(q->cat.nu, t.nu, n_tab * 8, hipMemcpyDeviceToDevice, st));
+    HIPCHK(a, hipMemcpyAsync(q->cat.nm, t.nm, n_tab * 8, hipMemcpyDeviceToDevice, st));
+    HIPCHK(a, hipMemcpyAsync(q->cat.ov, t.ov, n_tab * 4, hipMemcpyDeviceToDevice, st));
   }
   uint64_t m = 0;
   const int rc = sort_reduce(q, q->cat.rows(), n_cat, q->tab[q->cur ^ 1], &m);
@@ -172,19 +185,19 @@ int add_batch(thm_quant* q, const char* who, QuantBatch b, thm_quant_info* info)
   b.n_refs = (uint32_t)ix->refs.size();
   b.n_txs = (uint32_t)ix->txs.size();
   b.n_genes = (uint32_t)ix->genes.size();
-  b.tx_gene = a->bt_tx_gene.as<uint32_t>();
-  b.tx_forward = q->tx_forward.as<uint8_t>();
-  b.ref_sq = a->bt_ref_sq.as<int32_t>();
+  b.tx_gene = a->bam.tx_gene;
+  b.tx_forward = q->tx_forward;
+  b.ref_sq = a->bam.ref_sq;
   HIPCHK(a, ensure_events(q->ev));
-  HIPCHK(a, q->hit_cnt.ensure((n_alns + 1) * 8));
-  HIPCHK(a, q->hit_off.ensure((n_alns + 2) * 8));
-  HIPCHK(a, q->multi.ensure(n_alns + 16));
-  HIPCHK(a, q->scan_tmp.ensure(scan_tmp_entries(n_alns + 1) * 8 + 64));
+  HIPCHK(a, q->hit_cnt.ensure(n_alns + 1));
+  HIPCHK(a, q->hit_off.ensure(n_alns + 2));
+  HIPCHK(a, q->multi.ensure(n_alns, 16));
+  HIPCHK(a, scan_reserve(q->scan_tmp, n_alns));
   HIPCHK(a, q->d_tot.ensure((quant::N_TOTALS + 1) * 8));
   QuantCountParams cp;
   cp.b = b;
-  cp.hit_cnt = q->hit_cnt.as<uint64_t>();
-  cp.multi = q->multi.as<uint8_t>();
+  cp.hit_cnt = q->hit_cnt;
+  cp.multi = q->multi;
   cp.totals = q->d_tot.as<unsigned long long>();
   cp.bad = cp.totals + quant::N_TOTALS;
   HIPCHK(a, hipEventRecord(q->ev[0], st));
@@ -193,8 +206,7 @@ int add_batch(thm_quant* q, const char* who, QuantBatch b, thm_quant_info* info)
   HIPCHK(a, launch_quant_count(cp, a->n_cu, st));
   unsigned long long h_tot[quant::N_TOTALS + 1], n_hits = 0;
   if (n_alns) {
-    HIPCHK(a, launch_exclusive_scan_u64(cp.hit_cnt, q->hit_off.as<uint64_t>(), n_alns, q->scan_tmp.as<uint64_t>(), st));
-    HIPCHK(a, hipMemcpyAsync(&n_hits, q->hit_off.as<uint64_t>() + n_alns, 8, hipMemcpyDeviceToHost, st));
+    if (const int rc = scan_u64(a, q->scan_tmp, cp.hit_cnt, q->hit_off, n_alns, st, &n_hits); rc != THM_OK) return rc;
   }
   HIPCHK(a, hipMemcpyAsync(h_tot, cp.totals, sizeof h_tot, hipMemcpyDeviceToHost, st));
   HIPCHK(a, hipStreamSynchronize(st));
@@ -206,7 +218,7 @@ int add_batch(thm_quant* q, const char* who, QuantBatch b, thm_quant_info* info)
     HIPCHK(a, q->hits.ensure(n_hits));
     QuantExtractParams ep;
     ep.b = b;
-    ep.hit_off = q->hit_off.as<uint64_t>();
+    ep.hit_off = q->hit_off;
     ep.multi = cp.multi;
     ep.out = q->hits.rows();
     HIPCHK(a, launch_quant_extract(ep, st));
@@ -218,9 +230,9 @@ int add_batch(thm_quant* q, const char* who, QuantBatch b, thm_quant_info* info)
   QuantGenesParams gp;
   gp.b = b;
   gp.multi = cp.multi;
-  gp.genes = q->genes.as<unsigned long long>();
+  gp.genes = q->genes;
   // (the fetch's row buffer is sized here, before anything is counted: held_bytes is what the object holds with a fetch)
-  HIPCHK(a, q->d_rows.ensure(q->n_tab * sizeof(thm_quant_junction) + 16));
+  HIPCHK(a, q->d_rows.ensure(q->n_tab, 16));
   HIPCHK(a, launch_quant_genes(gp, a->n_cu, st));
   HIPCHK(a, hipEventRecord(q->ev[1], st));
   HIPCHK(a, hipStreamSynchronize(st));
@@ -300,10 +312,10 @@ int32_t thm_quant_create(thm_aligner* a, thm_quant** out) {
   std::vector<uint8_t> fwd(n_txs + 1, 0);
   for (size_t t = 0; t < n_txs; t++) fwd[t] = ix->txs[t].strand ? 1 : 0;
   hipError_t e = q->tx_forward.ensure(fwd.size());
-  if (e == hipSuccess) e = q->genes.ensure((n_genes * 4 + 1) * 8);
-  if (e == hipSuccess) e = hipMemcpy(q->tx_forward.p, fwd.data(), fwd.size(), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemset(q->genes.p, 0, (n_genes * 4 + 1) * 8);
-  if (e == hipSuccess && n_refs) e = hipMemcpy(q->h_ref_sq.data(), a->bt_ref_sq.p, n_refs * 4, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = q->genes.ensure(n_genes * 4 + 1);
+  if (e == hipSuccess) e = hipMemcpy(q->tx_forward, fwd.data(), fwd.size(), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(q->genes, 0, (n_genes * 4 + 1) * 8);
+  if (e == hipSuccess && n_refs) e = hipMemcpy(q->h_ref_sq.data(), a->bam.ref_sq, n_refs * 4, hipMemcpyDeviceToHost);
   if (e != hipSuccess) {
     delete q;
     return fail(a, e == hipErrorOutOfMemory ? THM_ERR_OOM : THM_ERR_HIP, "thm_quant_create: %s", hipGetErrorString(e));
@@ -348,11 +360,11 @@ int32_t thm_quant_add(thm_quant* q, thm_quant_info* info) {
   b.n_reads = a->n_reads;
   b.n_alns = z.n_alns;
   b.n_words = n_words;
-  b.aln_off = a->e_aln_off.as<uint64_t>();
-  b.alns = a->o_alns.as<thm_aln>();
-  b.digests = a->c_dig.as<thm_aln_digest>();
-  b.words = a->c_words.as<uint32_t>();
-  b.status = z.any_failed ? a->r_status.as<int32_t>() : nullptr;
+  b.aln_off = a->ext.aln_off;
+  b.alns = a->out.alns;
+  b.digests = a->cig.dig;
+  b.words = a->cig.words;
+  b.status = z.any_failed ? a->reads.status : nullptr;
   return add_batch(q, "thm_quant_add", b, info);
 }
 
@@ -366,17 +378,17 @@ int32_t thm_quant_add_view(thm_quant* q, const thm_cigar_view* v, thm_quant_info
   hipStream_t st = a->stream;
   const uint64_t n = v->n_reads, n_alns = v->n_alns, n_words = v->n_cigar_words;
   const uint64_t zero = 0;
-  HIPCHK(a, q->v_off.ensure((n + 1) * 8));
-  HIPCHK(a, q->v_alns.ensure((n_alns + 1) * sizeof(thm_aln)));
-  HIPCHK(a, q->v_dig.ensure((n_alns + 1) * sizeof(thm_aln_digest)));
-  HIPCHK(a, q->v_words.ensure((n_words + 4) * 4));
-  HIPCHK(a, hipMemcpyAsync(q->v_off.p, n ? v->read_aln_off : &zero, (n + 1) * 8, hipMemcpyHostToDevice, st));
-  if (n_alns) HIPCHK(a, hipMemcpyAsync(q->v_alns.p, v->alns, n_alns * sizeof(thm_aln), hipMemcpyHostToDevice, st));
-  if (n_alns) HIPCHK(a, hipMemcpyAsync(q->v_dig.p, v->digests, n_alns * sizeof(thm_aln_digest), hipMemcpyHostToDevice, st));
-  if (n_words) HIPCHK(a, hipMemcpyAsync(q->v_words.p, v->cigar, n_words * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(a, q->v_off.ensure(n + 1));
+  HIPCHK(a, q->v_alns.ensure(n_alns + 1));
+  HIPCHK(a, q->v_dig.ensure(n_alns + 1));
+  HIPCHK(a, q->v_words.ensure(n_words + 4));
+  HIPCHK(a, hipMemcpyAsync(q->v_off, n ? v->read_aln_off : &zero, (n + 1) * 8, hipMemcpyHostToDevice, st));
+  if (n_alns) HIPCHK(a, hipMemcpyAsync(q->v_alns, v->alns, n_alns * sizeof(thm_aln), hipMemcpyHostToDevice, st));
+  if (n_alns) HIPCHK(a, hipMemcpyAsync(q->v_dig, v->digests, n_alns * sizeof(thm_aln_digest), hipMemcpyHostToDevice, st));
+  if (n_words) HIPCHK(a, hipMemcpyAsync(q->v_words, v->cigar, n_words * 4, hipMemcpyHostToDevice, st));
   if (v->read_status && n) {
-    HIPCHK(a, q->v_stat.ensure(n * 4));
-    HIPCHK(a, hipMemcpyAsync(q->v_stat.p, v->read_status, n * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(a, q->v_stat.ensure(n));
+    HIPCHK(a, hipMemcpyAsync(q->v_stat, v->read_status, n * 4, hipMemcpyHostToDevice, st));
   }
   HIPCHK(a, hipStreamSynchronize(st));  // (`zero` and the caller's arrays have been read)
   QuantBatch b;
@@ -384,11 +396,11 @@ int32_t thm_quant_add_view(thm_quant* q, const thm_cigar_view* v, thm_quant_info
   b.n_reads = n;
   b.n_alns = n_alns;
   b.n_words = n_words;
-  b.aln_off = q->v_off.as<uint64_t>();
-  b.alns = q->v_alns.as<thm_aln>();
-  b.digests = q->v_dig.as<thm_aln_digest>();
-  b.words = q->v_words.as<uint32_t>();
-  b.status = v->read_status && n ? q->v_stat.as<int32_t>() : nullptr;
+  b.aln_off = q->v_off;
+  b.alns = q->v_alns;
+  b.digests = q->v_dig;
+  b.words = q->v_words;
+  b.status = v->read_status && n ? q->v_stat.get() : nullptr;
   return add_batch(q, "thm_quant_add_view", b, info);
 }
 
@@ -401,12 +413,12 @@ int32_t thm_quant_fetch(thm_quant* q, thm_quant_view* out) {
   const uint64_t n_genes = a->ix->genes.size(), n = q->n_tab;
   const size_t gene_bytes = n_genes * sizeof(thm_quant_gene), row_bytes = n * sizeof(thm_quant_junction);
   HIPCHK(a, ensure_events(q->ev_fetch));
-  HIPCHK(a, q->d_rows.ensure(row_bytes + 16));
+  HIPCHK(a, q->d_rows.ensure(n, 16));
   HIPCHK(a, q->h_out.ensure(gene_bytes + row_bytes + 16));
   HIPCHK(a, hipEventRecord(q->ev_fetch[0], st));
-  HIPCHK(a, launch_quant_rows(q->tab[q->cur].rows(), n, q->d_rows.as<thm_quant_junction>(), st));
-  if (gene_bytes) HIPCHK(a, hipMemcpyAsync(q->h_out.p, q->genes.p, gene_bytes, hipMemcpyDeviceToHost, st));
-  if (row_bytes) HIPCHK(a, hipMemcpyAsync(q->h_out.as<uint8_t>() + gene_bytes, q->d_rows.p, row_bytes, hipMemcpyDeviceToHost, st));
+  HIPCHK(a, launch_quant_rows(q->tab[q->cur].rows(), n, q->d_rows, st));
+  if (gene_bytes) HIPCHK(a, hipMemcpyAsync(q->h_out.p, q->genes, gene_bytes, hipMemcpyDeviceToHost, st));
+  if (row_bytes) HIPCHK(a, hipMemcpyAsync(q->h_out.as<uint8_t>() + gene_bytes, q->d_rows, row_bytes, hipMemcpyDeviceToHost, st));
   HIPCHK(a, hipEventRecord(q->ev_fetch[1], st));
   HIPCHK(a, hipStreamSynchronize(st));
   (void)elapsed_ms(q->ev_fetch[0], q->ev_fetch[1], &out->fetch_ms);
@@ -422,7 +434,7 @@ int32_t thm_quant_reset(thm_quant* q) {
   if (!q) return THM_ERR_INVALID_ARG;
   thm_aligner* a = q->a;
   HIPCHK(a, hipSetDevice(a->device));
-  HIPCHK(a, hipMemsetAsync(q->genes.p, 0, (a->ix->genes.size() * 4 + 1) * 8, a->stream));
+  HIPCHK(a, hipMemsetAsync(q->genes, 0, (a->ix->genes.size() * 4 + 1) * 8, a->stream));
   HIPCHK(a, hipStreamSynchronize(a->stream));
   q->n_tab = 0;
   memset(&q->totals, 0, sizeof q->totals);

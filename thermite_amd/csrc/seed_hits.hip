@@ -25,37 +25,37 @@ template <class C>
 int run_seed_hits(thm_aligner* a, const std::vector<Launch>& launches, uint64_t n_list_host, uint64_t pool_cap,
                   uint32_t mk_cap_slow) {
   hipStream_t s = a->stream;
-  unsigned long long* ctl = a->sh_ctl.as<unsigned long long>();  // [0] op pool cursor, [1] retry count (list length of the retry launch)
+  unsigned long long* ctl = a->sh.ctl;  // [0] op pool cursor, [1] retry count (list length of the retry launch)
   SeedHitParamsT<C> p;
   memset(&p, 0, sizeof p);
   if constexpr (sizeof(C) == 8)
     p.ix = a->dix->view64;
   else
     p.ix = a->dix->view;
-  p.reads.bases = a->sh_san.as<uint8_t>() + 16;
-  p.reads.offsets = a->sh_off.as<uint64_t>();
-  p.hits = a->sh_hits.as<thm_mem>();
-  p.hit_read = a->sh_read.as<uint32_t>();
-  p.bw = a->sh_bw.as<uint32_t>();
-  p.xd = a->sh_xd.as<int32_t>();
-  p.retry = a->sh_list.as<uint32_t>() + n_list_host;
+  p.reads.bases = a->sh.san + 16;
+  p.reads.offsets = a->sh.off;
+  p.hits = a->sh.hits;
+  p.hit_read = a->sh.read;
+  p.bw = a->sh.bw;
+  p.xd = a->sh.xd;
+  p.retry = a->sh.list + n_list_host;
   p.retry_count = ctl + 1;
-  p.out = a->sh_out.as<thm_aln>();
-  p.status = a->sh_status.as<int32_t>();
-  p.cand_ops = a->sh_ops.as<uint8_t>();
+  p.out = a->sh.out;
+  p.status = a->sh.status;
+  p.cand_ops = a->sh.ops;
   p.cand_ops_cap = pool_cap;
   p.ops_cursor = ctl;
-  p.counters = a->d_counters.as<unsigned long long>();
-  p.fault = a->d_fault.as<int>();
+  p.counters = a->d_counters;
+  p.fault = a->d_fault;
   HIPCHK(a, hipMemsetAsync(ctl, 0, 64, s));
   int rc = reset_queue(a);
   if (rc != THM_OK) return rc;
   unsigned q = 0;
   for (const Launch& l : launches) {
-    p.list = a->sh_list.as<uint32_t>() + l.list_off;
+    p.list = a->sh.list + l.list_off;
     p.n_list = l.n;
     p.n_list_dev = l.retries ? ctl + 1 : nullptr;
-    p.queue = a->d_queue.as<unsigned int>() + (q++) * EXT_QSTRIDE;
+    p.queue = a->d_queue + (q++) * EXT_QSTRIDE;
     p.max_read_len = l.max_len;
     p.max_bw = l.max_bw;
     p.mk_cap = l.cpl == 0 ? mk_cap_slow : (uint32_t)FAST_MAX_YCLIPS;
@@ -67,15 +67,15 @@ int run_seed_hits(thm_aligner* a, const std::vector<Launch>& launches, uint64_t 
       const uint64_t per_wave = slow_wave_bytes(l.max_len, l.max_bw, p.mk_cap);
       const uint64_t waves = slow_launch_waves(per_wave, a->n_cu, l.retries ? (uint64_t)a->n_cu * 8 : std::max<uint64_t>(l.n, 1));
       n_blocks = (int)(waves / 4);
-      HIPCHK(a, a->sh_slow.ensure((size_t)waves * per_wave + 256));
-      p.slow_scratch = a->sh_slow.as<uint8_t>();
+      HIPCHK(a, a->sh.slow.ensure((size_t)waves * per_wave, 256));
+      p.slow_scratch = a->sh.slow;
       p.slow_scratch_per_wave = per_wave;
     } else {
       const size_t lds = extend_lds_bytes(l.max_len, l.max_bw, l.cpl);
       n_blocks = grid_blocks(a, l.n, 4, lds_blocks_per_cu(lds, 4));
       const size_t trace_per_wave = extend_trace_scratch_bytes(l.max_len, l.max_bw, l.cpl);
-      HIPCHK(a, a->sh_trace.ensure((size_t)n_blocks * 4 * trace_per_wave + 64));
-      p.trace_scratch = a->sh_trace.as<unsigned long long>();
+      HIPCHK(a, a->sh.trace.ensure((size_t)n_blocks * 4 * trace_per_wave + 64));
+      p.trace_scratch = a->sh.trace.as<unsigned long long>();
     }
     HIPCHK(a, launch_seed_hits(p, l.cpl, n_blocks, s));
   }
@@ -196,51 +196,51 @@ int32_t thm_align_seed_hits_batch(thm_aligner* a, const uint8_t* bases, const ui
 
   // ---- upload ----
   hipStream_t s = a->stream;
-  HIPCHK(a, a->sh_bases.ensure(n_bases + 64));
-  HIPCHK(a, a->sh_san.ensure(n_bases + 256 + 16));
-  HIPCHK(a, a->sh_off.ensure((n_reads + 1) * 8));
-  HIPCHK(a, a->sh_hits.ensure(n_hits * sizeof(thm_mem)));
-  HIPCHK(a, a->sh_read.ensure(n_hits * 4));
-  HIPCHK(a, a->sh_bw.ensure(n_hits * 4));
-  HIPCHK(a, a->sh_xd.ensure(n_hits * 4));
-  HIPCHK(a, a->sh_list.ensure((n_list_host + n_hits) * 4 + 16));
-  HIPCHK(a, a->sh_out.ensure(n_hits * sizeof(thm_aln)));
-  HIPCHK(a, a->sh_status.ensure(n_hits * 4));
-  HIPCHK(a, a->sh_ctl.ensure(64));
-  if (n_bases) HIPCHK(a, hipMemcpyAsync(a->sh_bases.p, bases, n_bases, hipMemcpyHostToDevice, s));
-  HIPCHK(a, hipMemcpyAsync(a->sh_off.p, offsets, (n_reads + 1) * 8, hipMemcpyHostToDevice, s));
-  HIPCHK(a, hipMemcpyAsync(a->sh_hits.p, hits, n_hits * sizeof(thm_mem), hipMemcpyHostToDevice, s));
-  HIPCHK(a, hipMemcpyAsync(a->sh_read.p, hit_read.data(), n_hits * 4, hipMemcpyHostToDevice, s));
-  HIPCHK(a, hipMemcpyAsync(a->sh_bw.p, band_width, n_hits * 4, hipMemcpyHostToDevice, s));
-  HIPCHK(a, hipMemcpyAsync(a->sh_xd.p, x_drop, n_hits * 4, hipMemcpyHostToDevice, s));
-  if (n_list_host) HIPCHK(a, hipMemcpyAsync(a->sh_list.p, list.data(), n_list_host * 4, hipMemcpyHostToDevice, s));
-  HIPCHK(a, hipMemcpyAsync(a->sh_status.p, status.data(), n_hits * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(a, a->sh.bases.ensure(n_bases, 64));
+  HIPCHK(a, a->sh.san.ensure(n_bases, 256 + 16));
+  HIPCHK(a, a->sh.off.ensure(n_reads + 1));
+  HIPCHK(a, a->sh.hits.ensure(n_hits));
+  HIPCHK(a, a->sh.read.ensure(n_hits));
+  HIPCHK(a, a->sh.bw.ensure(n_hits));
+  HIPCHK(a, a->sh.xd.ensure(n_hits));
+  HIPCHK(a, a->sh.list.ensure(n_list_host + n_hits, 16));
+  HIPCHK(a, a->sh.out.ensure(n_hits));
+  HIPCHK(a, a->sh.status.ensure(n_hits));
+  HIPCHK(a, a->sh.ctl.ensure(8));
+  if (n_bases) HIPCHK(a, hipMemcpyAsync(a->sh.bases, bases, n_bases, hipMemcpyHostToDevice, s));
+  HIPCHK(a, hipMemcpyAsync(a->sh.off, offsets, (n_reads + 1) * 8, hipMemcpyHostToDevice, s));
+  HIPCHK(a, hipMemcpyAsync(a->sh.hits, hits, n_hits * sizeof(thm_mem), hipMemcpyHostToDevice, s));
+  HIPCHK(a, hipMemcpyAsync(a->sh.read, hit_read.data(), n_hits * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(a, hipMemcpyAsync(a->sh.bw, band_width, n_hits * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(a, hipMemcpyAsync(a->sh.xd, x_drop, n_hits * 4, hipMemcpyHostToDevice, s));
+  if (n_list_host) HIPCHK(a, hipMemcpyAsync(a->sh.list, list.data(), n_list_host * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(a, hipMemcpyAsync(a->sh.status, status.data(), n_hits * 4, hipMemcpyHostToDevice, s));
   // upper-cased, sanitised copy (sanitize_kernel, the normalisation thm_align_batch applies: src/aligner.rs:125)
-  HIPCHK(a, launch_sanitize(a->sh_bases.as<uint8_t>(), a->sh_san.as<uint8_t>() + 16, n_bases, n_bases + 128, s));
+  HIPCHK(a, launch_sanitize(a->sh.bases, a->sh.san + 16, n_bases, n_bases + 128, s));
 
   // ---- run; an op pool that overflows is grown and the run replayed (counters restored first) ----
   uint64_t pool_cap = 0;
   for (uint32_t h : list) pool_cap += 4ull * len_of(h) + 4ull * band_width[h] + 64;  // two paths of <= 2 (L + bw) ops, clips
   pool_cap += (uint64_t)a->n_cu * 64 * 4096;
-  HIPCHK(a, hipMemcpyAsync(a->d_counters.as<uint8_t>() + THM_N_COUNTERS * 8, a->d_counters.p, THM_N_COUNTERS * 8,
+  HIPCHK(a, hipMemcpyAsync(a->d_counters + THM_N_COUNTERS, a->d_counters, THM_N_COUNTERS * 8,
                            hipMemcpyDeviceToDevice, s));
   unsigned long long ctl[2] = {0, 0};
   int fault = 0;
   for (int attempt = 0;; attempt++) {
-    HIPCHK(a, a->sh_ops.ensure(pool_cap + 64));
+    HIPCHK(a, a->sh.ops.ensure(pool_cap, 64));
     int rc = a->dix->wide ? run_seed_hits<uint64_t>(a, launches, n_list_host, pool_cap, mk_cap_slow)
                           : run_seed_hits<uint32_t>(a, launches, n_list_host, pool_cap, mk_cap_slow);
     if (rc != THM_OK) return rc;
-    HIPCHK(a, hipMemcpyAsync(ctl, a->sh_ctl.p, sizeof ctl, hipMemcpyDeviceToHost, s));
-    HIPCHK(a, hipMemcpyAsync(&fault, a->d_fault.p, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(a, hipMemcpyAsync(ctl, a->sh.ctl, sizeof ctl, hipMemcpyDeviceToHost, s));
+    HIPCHK(a, hipMemcpyAsync(&fault, a->d_fault, 4, hipMemcpyDeviceToHost, s));
     HIPCHK(a, hipStreamSynchronize(s));
     if (fault & FAULT_INTERNAL) return fail(a, THM_ERR_INTERNAL, "seed_hit_kernel reported an internal inconsistency");
     if (!(fault & FAULT_OPS_POOL)) break;
     if (attempt >= 4) return fail(a, THM_ERR_INTERNAL, "op pool kept overflowing");
     pool_cap = std::max<uint64_t>(pool_cap * 2, ctl[0] + ctl[0] / 2 + 65536);
-    HIPCHK(a, hipMemcpyAsync(a->d_counters.p, a->d_counters.as<uint8_t>() + THM_N_COUNTERS * 8, THM_N_COUNTERS * 8,
+    HIPCHK(a, hipMemcpyAsync(a->d_counters, a->d_counters + THM_N_COUNTERS, THM_N_COUNTERS * 8,
                              hipMemcpyDeviceToDevice, s));
-    HIPCHK(a, hipMemcpyAsync(a->sh_status.p, status.data(), n_hits * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(a, hipMemcpyAsync(a->sh.status, status.data(), n_hits * 4, hipMemcpyHostToDevice, s));
   }
 
   // ---- fetch and lay out: records in hit order, op streams back to back (gx ops, then tx ops) ----
@@ -248,9 +248,9 @@ int32_t thm_align_seed_hits_batch(thm_aligner* a, const uint8_t* bases, const ui
   std::vector<thm_aln> raw(n_hits);
   std::vector<uint8_t> pool_h(used);
   a->h_hit_status.resize(n_hits);
-  HIPCHK(a, hipMemcpyAsync(raw.data(), a->sh_out.p, n_hits * sizeof(thm_aln), hipMemcpyDeviceToHost, s));
-  HIPCHK(a, hipMemcpyAsync(a->h_hit_status.data(), a->sh_status.p, n_hits * 4, hipMemcpyDeviceToHost, s));
-  if (used) HIPCHK(a, hipMemcpyAsync(pool_h.data(), a->sh_ops.p, used, hipMemcpyDeviceToHost, s));
+  HIPCHK(a, hipMemcpyAsync(raw.data(), a->sh.out, n_hits * sizeof(thm_aln), hipMemcpyDeviceToHost, s));
+  HIPCHK(a, hipMemcpyAsync(a->h_hit_status.data(), a->sh.status, n_hits * 4, hipMemcpyDeviceToHost, s));
+  if (used) HIPCHK(a, hipMemcpyAsync(pool_h.data(), a->sh.ops, used, hipMemcpyDeviceToHost, s));
   HIPCHK(a, hipStreamSynchronize(s));
   a->h_hit_alns.assign(n_hits, thm_aln());
   uint64_t n_failed = 0;
