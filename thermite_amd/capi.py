@@ -1238,7 +1238,7 @@ class Aligner:
         return n.value
 
     def debug_set_flags(self, tpr=None, rounds=0, seed_infer=None, seed_stats=None, seed_direct=None, finish_exact=None,
-                        finish_subst=None):
+                        finish_subst=None, seed_bounds=None):
         """test / tuning hook: tpr = False: every read takes the wave-per-read kernels, True: the problem-parallel path
         in front of them (None: keep); rounds = its request rounds (1..8, 0: keep); seed_infer = False: no seed probe
         is decided from its table entry and a neighbouring match (bit 2 of the word; True: bit 4, on again);
@@ -1246,13 +1246,16 @@ class Aligner:
         seed_direct = False: a probe into a single-suffix bucket reads the suffix array although its table entry holds
         the text position (bit 6; True: bit 7, the position is used again); finish_exact = False: the finisher in front
         of the extend kernel leaves whole-read exact matches (class E) to it (bit 12; True: bit 13, it takes them);
-        finish_subst: the same for reads with one substitution between two SMEMs (class S, bits 14 / 15).  None: keep."""
+        finish_subst: the same for reads with one substitution between two SMEMs (class S, bits 14 / 15);
+        seed_bounds = False: the seed stage probes every inner position of a grid cell whose two grid points do not
+        share a stored end, as it did before it used the bounds of the grid probes (bit 16; True: bit 17).  None: keep."""
         word = (0 if tpr is None else (2 if tpr else 1)) | (int(rounds) << 8)
         word |= 0 if seed_infer is None else (16 if seed_infer else 4)
         word |= 0 if seed_stats is None else (8 if seed_stats else 32)
         word |= 0 if seed_direct is None else (128 if seed_direct else 64)
         word |= 0 if finish_exact is None else (0x2000 if finish_exact else 0x1000)
         word |= 0 if finish_subst is None else (0x8000 if finish_subst else 0x4000)
+        word |= 0 if seed_bounds is None else (0x20000 if seed_bounds else 0x10000)
         self._chk(lib().thm_debug_set_flags(self.h, word))
 
     def debug_seed_stats(self):

@@ -573,6 +573,10 @@ int32_t thm_debug_set_flags(thm_aligner* a, uint32_t flags) {
   // table stays as it is; lut_direct.h), bit 7: it uses the position again
   if (flags & 64u) a->dbg_seed_nodirect = true;
   if (flags & 128u) a->dbg_seed_nodirect = false;
+  // bit 16: the cells phase of the seed stage decides an inner position only by the rule "both grid points have the same
+  // stored end" and leaves every other cell to the fill whole (seed_bounds.h off; for A/B runs), bit 17: bounds again
+  if (flags & 0x10000u) a->dbg_seed_nobounds = true;
+  if (flags & 0x20000u) a->dbg_seed_nobounds = false;
   // bit 12: the finisher (kernels_finish.hip) leaves class E (whole-read exact matches) to the extend kernel, bit 13: it
   // takes them again; bits 14 / 15: the same for class S (one substitution between two SMEMs).  Default: both on.
   if (flags & 0x1000u) a->fin_classes &= ~1u;

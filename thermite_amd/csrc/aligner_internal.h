@@ -464,6 +464,8 @@ struct thm_aligner {
   bool dbg_seed_noinfer = false, dbg_seed_stats = false;
   // ... bit 6: a probe into a single-suffix bucket reads sa[lo] although the table entry holds the text position
   bool dbg_seed_nodirect = false;
+  // (bits 16, 17): grid cells of the seed stage are listed whole, not cut down by the bounds of their grid probes (seed_bounds.h)
+  bool dbg_seed_nobounds = false;
   // The finisher (kernels_finish.hip): classes it takes (thm_debug_set_flags bits 12..15; fin::CLASS_E | fin::CLASS_S), the
   // read-only op run at the front of ext.ops (where it was written and for which read length, 0: none; while it exists every
   // run starts the pool's cursor behind it), the classes and workgroups of the last enqueue (its statistics: ext.finstats)

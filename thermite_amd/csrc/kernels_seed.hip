@@ -22,6 +22,7 @@
 
 #include "launch.h"
 #include "lut_direct.h"
+#include "seed_bounds.h"
 #include "swg_device.h"
 
 namespace thm {
@@ -115,6 +116,9 @@ __device__ __forceinline__ int lcp_cmp(const uint8_t* tp, const uint8_t* q, int 
 // hi = lo + 1: it is decoded right behind the load, everything below sees the plain interval, and step 2 goes from the
 // entry to the text without the dependent read of the suffix array (MS_DIRECT; `use_pos` false: the position is dropped
 // and sa[lo] read, MS_SA_ONE, as with a plain table).
+// out_d is MS[pos] exactly, also below k, except where the table path found an empty bucket: then out_lo == out_hi, out_d
+// is 0 and MS[pos] < kt is all that is known (seed_bounds.h goes through the paths one by one; probe_store makes the
+// bound on the match end from it).
 enum : int { MS_FULL = 0, MS_DECIDED = 1, MS_DIRECT = 2, MS_SA_ONE = 3 };
 template <class C>
 __device__ int ms_search(const DeviceIndexT<C>& ix, const uint8_t* rd, int L, int pos, int k, int known_end, bool use_pos, int& out_d,
@@ -313,7 +317,11 @@ __global__ void sanitize_reset_kernel(const uint8_t* in, uint8_t* out, uint64_t 
 //                      inside has that end too (and MS >= k), so nothing starts there and
 //                      the end is recorded without probing; other cells go on a work list.
 //   seed_fill_kernel   the inner positions of listed cells: the cells around a jump of E.
-// For reads of at most SHORT_READ_MAX bases the grid and cells steps are one launch (seed_grid_cells_kernel).
+// For reads of at most SHORT_READ_MAX bases the grid and cells steps are one launch (seed_grid_cells_kernel), and its
+// cells step uses all a grid probe knows, not only the stored end: the match end exactly, also where the match is
+// shorter than k, or an upper bound of it after an empty table bucket.  From the bounds of a cell's two grid points it
+// decides every inner position it can (seed_bounds.h) and lists the cell with a mask of the others (SEED_BOUNDS in
+// p.flags; off: the rule above, whole cells).
 // A probe behind position 0 is told the end of a match further left in its read (the match from position 0 for the
 // grid, the nearest grid point with a match for the fill): where that match covers the probe's kt-mer and the table
 // holds a single suffix for it, the probe is decided without reading the suffix array or the text (ms_search), and
@@ -322,6 +330,15 @@ __global__ void sanitize_reset_kernel(const uint8_t* in, uint8_t* out, uint64_t 
 // The work lists keep the probing launches dense (whole waves of real probes).  The per-position
 // arrays are ragged: the row of read r starts at slot ms_row(offsets[r], r) (launch.h).
 constexpr int PROBE_STRIDE = 8;
+static_assert(PROBE_STRIDE == sbd::STRIDE, "seed_bounds.h has the grid stride of the seed stage");
+
+// An entry of work_cells: read << 23 | cell << 7 | mask.  Bit j - 1 of the mask: inner position cell * 8 + j (1 <= j <= 7)
+// is to be probed.  16 bits of cell: a read of MAX_READ_LEN bases has at most 8 192 cells.
+constexpr int CELL_SHIFT = PROBE_STRIDE - 1, READ_SHIFT = CELL_SHIFT + 16;
+constexpr unsigned CELL_ALL = (1u << CELL_SHIFT) - 1u;  // every inner position
+__device__ __forceinline__ unsigned long long cell_item(uint64_t read, int cell, unsigned mask) {
+  return (read << READ_SHIFT) | ((unsigned long long)cell << CELL_SHIFT) | (unsigned long long)mask;
+}
 
 // append `value` to a list for every thread with `flag`: one atomic per 256-thread workgroup
 // (every thread must call it; the trailing barrier makes back-to-back calls safe)
@@ -388,16 +405,18 @@ __device__ __forceinline__ void seed_stats_end(const SeedParamsT<C>& p) {
 // end stored for pos - 1 is e as well and nothing starts at pos.  Without a hint the interval is always stored.
 // (seed_select_kernel loads ms_lo / ms_hi of a whole row into registers before it knows the starts: the words of
 // positions skipped here are stale or never written, inside the buffer, and must stay unused except at a start.)
-// Returns the stored end; `decided`: the table entry and the hint answered the probe.
+// Returns the stored end; `decided`: the table entry and the hint answered the probe; la <= E[pos] <= ub: what the probe
+// knows of the match end also where the match is shorter than k and the stored end 0 (seed_bounds.h).
 template <class C>
 __device__ __forceinline__ int probe_store(const SeedParamsT<C>& p, const uint8_t* rd, int L, int pos, uint64_t item0, int hint,
-                                           bool& decided) {
+                                           bool& decided, int& la, int& ub) {
   const int k = (int)p.min_seed_len;
   int d = 0;
   C lo = 0, hi = 0;
   const int how = ms_search(p.ix, rd, L, pos, k, hint, !(p.flags & SEED_NODIRECT), d, lo, hi);
   decided = how == MS_DECIDED;
   if (p.flags & SEED_STATS) seed_stats_note(how);
+  sbd::probe_bound(pos, d, !(lo < hi), (int)p.ix.kt, L, la, ub);
   const int e = (d >= k) ? pos + d : 0;
   const uint64_t item = item0 + (uint64_t)pos;
   p.ms_end[item] = (uint16_t)e;
@@ -499,7 +518,8 @@ __global__ __launch_bounds__(256) void seed_grid_kernel(SeedParamsT<C> p, const 
       const uint64_t item0 = ms_row(r0, read);
       const int hint = (p.flags & SEED_INFER) ? (int)p.ms_end[item0] : 0;  // the match from position 0
       bool decided;
-      (void)probe_store(p, p.reads.bases + r0, L, pos, item0, hint, decided);
+      int la, ub;
+      (void)probe_store(p, p.reads.bases + r0, L, pos, item0, hint, decided, la, ub);
     }
   }
   if (p.flags & SEED_STATS) seed_stats_end(p);
@@ -513,6 +533,7 @@ template <class C>
 __global__ __launch_bounds__(256) void seed_grid_cells_kernel(SeedParamsT<C> p, const unsigned long long* list,
                                                               const unsigned long long* count, uint32_t G) {
   __shared__ uint16_t s_end[256];
+  __shared__ uint16_t s_ub[256];             // SEED_BOUNDS: upper bound of the slot's match end (seed_bounds.h)
   const unsigned per = 256u / G;             // reads per workgroup
   const unsigned rl = threadIdx.x / G;       // read of the workgroup
   const int g = (int)(threadIdx.x - rl * G); // its slot
@@ -520,7 +541,7 @@ __global__ __launch_bounds__(256) void seed_grid_cells_kernel(SeedParamsT<C> p, 
   const bool live = rl < per && wi < *count;
   if (p.flags & SEED_STATS) seed_stats_begin();
   uint64_t read = 0, item0 = 0;
-  int npos = 0, e = 0;
+  int npos = 0, e = 0, la = 0, ub = 0;
   if (live) {
     read = list[wi];
     const uint64_t r0 = p.reads.offsets[read];
@@ -531,26 +552,37 @@ __global__ __launch_bounds__(256) void seed_grid_cells_kernel(SeedParamsT<C> p, 
     const int e0 = p.ms_end[item0];  // the match from position 0 (seed_first_kernel): slot 0's end, everybody's hint
     if (pos <= 0) {
       e = e0;
+      la = sbd::first_lower_bound(e0);  // (slot 0 is no cell's right end: its ub is never read)
     } else if (pos < npos && !(g + 1 != (int)G && pos == npos - 1)) {
       bool decided;
-      e = probe_store(p, p.reads.bases + r0, L, pos, item0, (p.flags & SEED_INFER) ? e0 : 0, decided);
+      e = probe_store(p, p.reads.bases + r0, L, pos, item0, (p.flags & SEED_INFER) ? e0 : 0, decided, la, ub);
     }
   }
   s_end[threadIdx.x] = (uint16_t)e;
+  s_ub[threadIdx.x] = (uint16_t)ub;
   __syncthreads();
-  bool todo = false;
+  unsigned mask = 0;  // inner positions of this thread's cell that are left to the fill (bit j: position a + j)
   if (live && g + 1 < (int)G) {  // cell g: positions a .. b, both probed (a by this thread, b by slot g + 1 or the last slot)
     const int a = g * PROBE_STRIDE, b = min(a + PROBE_STRIDE, npos - 1);
     if (b - a > 1) {  // the cell has inner positions
-      const int ea = e, eb = s_end[rl * G + (unsigned)(b == npos - 1 ? (int)G - 1 : g + 1)];
-      if (ea != 0 && ea == eb) {
-        for (int q = a + 1; q < b; q++) p.ms_end[item0 + (uint64_t)q] = (uint16_t)ea;  // same end: nothing starts here
+      const unsigned sb = rl * G + (unsigned)(b == npos - 1 ? (int)G - 1 : g + 1);
+      if (p.flags & SEED_BOUNDS) {
+        // seed_bounds.h: the leftmost inner positions may still hold a match of k or more, the others are decided here
+        const int k = (int)p.min_seed_len, ubb = s_ub[sb];
+        mask = sbd::cell_mask(a, b, la, ubb, k);
+        for (int q = a + 1; q < b; q++)
+          if (!((mask >> (q - a)) & 1u)) p.ms_end[item0 + (uint64_t)q] = (uint16_t)sbd::decided_end(q, la, ubb, k);
       } else {
-        todo = true;
+        const int ea = e, eb = s_end[sb];
+        if (ea != 0 && ea == eb) {
+          for (int q = a + 1; q < b; q++) p.ms_end[item0 + (uint64_t)q] = (uint16_t)ea;  // same end: nothing starts here
+        } else {
+          mask = ((1u << (b - a)) - 1u) & ~1u;
+        }
       }
     }
   }
-  block_append(todo, (read << 16) | (unsigned long long)g, p.work_cells, &p.work_counts[1]);
+  block_append(mask != 0, cell_item(read, g, mask >> 1), p.work_cells, &p.work_counts[1]);
   if (p.flags & SEED_STATS) seed_stats_end(p);
 }
 
@@ -579,7 +611,7 @@ __global__ __launch_bounds__(256) void seed_cells_kernel(SeedParamsT<C> p, const
       }
     }
   }
-  block_append(todo, (read << 16) | (unsigned long long)c, p.work_cells, &p.work_counts[1]);
+  block_append(todo, cell_item(read, c, CELL_ALL), p.work_cells, &p.work_counts[1]);  // (the long class lists whole cells)
 }
 
 // slot `tid` of the fill stage -> (read, position); false: nothing to probe there
@@ -588,8 +620,9 @@ __device__ __forceinline__ bool fill_item(const SeedParamsT<C>& p, uint64_t tid,
   const int j = (int)(tid % PROBE_STRIDE);
   if (j == 0) return false;  // the cell's left end is a grid position
   const unsigned long long w = p.work_cells[tid / PROBE_STRIDE];
-  read = w >> 16;
-  const int c = (int)(w & 0xffffu);
+  if (!((w >> (j - 1)) & 1ull)) return false;  // decided by the cells phase (seed_bounds.h)
+  read = w >> READ_SHIFT;
+  const int c = (int)((w >> CELL_SHIFT) & 0xffffu);
   r0 = p.reads.offsets[read];
   L = (int)(p.reads.offsets[read + 1] - r0);
   const int npos = L - (int)p.min_seed_len + 1;
@@ -622,18 +655,54 @@ __device__ __forceinline__ void fill_probe(const SeedParamsT<C>& p, uint64_t rea
   const uint64_t item0 = ms_row(r0, read);
   const int hint = (p.flags & SEED_INFER) ? fill_hint(p, item0, pos) : 0;
   bool decided;
-  (void)probe_store(p, p.reads.bases + r0, L, pos, item0, hint, decided);
+  int la, ub;
+  (void)probe_store(p, p.reads.bases + r0, L, pos, item0, hint, decided, la, ub);
 }
 
+// With seed_bounds.h a listed cell of the short class has two or three positions left to probe, not seven, and a thread
+// per slot of the cell would leave most lanes idle in a kernel that is bound by the probes in flight.  So a workgroup
+// takes 256 listed cells, one per thread, lays their masks end to end in LDS (prefix sum of the popcounts) and hands the
+// probes to consecutive threads: all its waves but the last of a pass are full.  work_cells stays one word per cell.
+// (The worst-case grid has one workgroup per 256 cells of the batch and makes one pass; the fixed grid strides.)
 template <class C>
 __global__ __launch_bounds__(256) void seed_fill_kernel(SeedParamsT<C> p) {
-  const uint64_t total = p.work_counts[1] * PROBE_STRIDE;
-  const uint64_t step = (uint64_t)gridDim.x * 256;  // (the worst-case grid covers every slot: one pass)
+  __shared__ unsigned long long s_item[256];
+  __shared__ uint16_t s_probe[256 * (PROBE_STRIDE - 1)];  // probes of the pass: cell of the workgroup << 3 | j
+  __shared__ unsigned s_wsum[4];
+  const uint64_t n_cells = p.work_counts[1];
+  const uint64_t step = (uint64_t)gridDim.x * 256;
+  const int lane = lane_id(), wv = (int)(threadIdx.x >> 6);
   if (p.flags & SEED_STATS) seed_stats_begin();
-  for (uint64_t tid = (uint64_t)blockIdx.x * 256 + threadIdx.x; tid < total; tid += step) {
-    uint64_t read, r0;
-    int pos, L;
-    if (fill_item(p, tid, read, pos, r0, L)) fill_probe(p, read, pos, r0, L);
+  for (uint64_t c0 = (uint64_t)blockIdx.x * 256; c0 < n_cells; c0 += step) {  // (uniform for the workgroup)
+    const unsigned long long w = (c0 + threadIdx.x < n_cells) ? p.work_cells[c0 + threadIdx.x] : 0ull;
+    s_item[threadIdx.x] = w;
+    const unsigned m = (unsigned)w & CELL_ALL;
+    const int cnt = __popc(m);
+    int inc = cnt;  // inclusive prefix sum within the wavefront
+    for (int o = 1; o < 64; o <<= 1) {
+      const int v = __shfl_up(inc, o);
+      if (lane >= o) inc += v;
+    }
+    if (lane == 63) s_wsum[wv] = (unsigned)inc;
+    __syncthreads();
+    unsigned at = (unsigned)(inc - cnt), total = 0;
+    for (int x = 0; x < 4; x++) {
+      const unsigned v = s_wsum[x];
+      if (x < wv) at += v;
+      total += v;
+    }
+    for (unsigned mm = m; mm; mm &= mm - 1u) s_probe[at++] = (uint16_t)((threadIdx.x << 3) | (unsigned)(__builtin_ctz(mm) + 1));
+    __syncthreads();
+    for (unsigned t = threadIdx.x; t < total; t += 256) {
+      const unsigned pr = s_probe[t];
+      const unsigned long long wc = s_item[pr >> 3];
+      const uint64_t read = wc >> READ_SHIFT;
+      const uint64_t r0 = p.reads.offsets[read];
+      const int L = (int)(p.reads.offsets[read + 1] - r0);
+      const int pos = (int)((wc >> CELL_SHIFT) & 0xffffu) * PROBE_STRIDE + (int)(pr & 7u);
+      if (pos < L - (int)p.min_seed_len) fill_probe(p, read, pos, r0, L);  // (a whole-cell mask runs past a short last cell)
+    }
+    __syncthreads();  // the next pass overwrites the lists
   }
   if (p.flags & SEED_STATS) seed_stats_end(p);
 }
@@ -1157,15 +1226,15 @@ static hipError_t launch_seed_t(const SeedParamsT<C>& p, int n_blocks, hipStream
     fill_cells += c.n * NC;
   }
   if (fill_cells) {
-    const dim3 worst = blocks(fill_cells * dev::PROBE_STRIDE);
-    const dim3 fixed(std::min<unsigned>(worst.x, 256u * 8u * 4u));  // (8 workgroups per CU, four times over)
+    const dim3 worst = blocks(fill_cells);  // seed_fill_kernel: a workgroup per 256 cells
+    const dim3 fixed(std::min<unsigned>(blocks(fill_cells * dev::PROBE_STRIDE).x, 256u * 8u * 4u));  // (8 workgroups per CU, four times over)
     if (p.fill_mode == 2 && fill_cells * dev::PROBE_STRIDE < (1ull << 32)) {
       hipLaunchKernelGGL(dev::seed_fill_keys_kernel<C>, fixed, dim3(256), 0, s, p);
       hipLaunchKernelGGL(dev::seed_fill_scan_kernel, dim3(1), dim3(1024), 0, s, p.fill_hist);
       hipLaunchKernelGGL(dev::seed_fill_scatter_kernel<C>, fixed, dim3(256), 0, s, p);
       hipLaunchKernelGGL(dev::seed_fill_bucketed_kernel<C>, fixed, dim3(256), 0, s, p);
     } else {
-      hipLaunchKernelGGL(dev::seed_fill_kernel<C>, p.fill_mode == 1 ? fixed : worst, dim3(256), 0, s, p);
+      hipLaunchKernelGGL(dev::seed_fill_kernel<C>, p.fill_mode == 1 ? dim3(std::min(fixed.x, worst.x)) : worst, dim3(256), 0, s, p);
     }
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }

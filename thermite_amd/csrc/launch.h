@@ -115,12 +115,12 @@ struct SeedParamsT {
   C* ms_hi;
   unsigned long long* work_short;   // [n_reads] short reads that need more than the probe at position 0
   unsigned long long* work_long;    // [n_long] long reads, the same
-  unsigned long long* work_cells;   // [cells] (read << 16 | cell) of grid cells to probe
+  unsigned long long* work_cells;   // [cells] grid cells with positions to probe: read << 23 | cell << 7 | mask of them
   unsigned long long* work_counts;  // [16] list lengths: 0 short, 1 cells, 2 heavy, 3 select overflow, 4 long, 5 slow; with
                                     // SEED_STATS 8 = probes decided from the table entry alone, 9 = probes run in full,
                                     // 10 = full probes that took the text position from the table entry, 11 = full
                                     // probes into a one-suffix bucket that read the suffix array; zeroed before launch
-  uint32_t flags;                   // SEED_INFER | SEED_STATS | SEED_NODIRECT
+  uint32_t flags;                   // SEED_INFER | SEED_STATS | SEED_NODIRECT | SEED_BOUNDS
   SmemT<C>* smems;             // pool
   uint64_t smem_cap;           // pool capacity (entries)
   unsigned long long* cursor;  // bump allocator head (entries), zeroed before launch
@@ -146,7 +146,10 @@ struct SeedParamsT {
 // SEED_STATS: the probing kernels count their probes into work_counts[8 .. 11] (thm_debug_set_flags bit 3; bit 5 ends it).
 // SEED_NODIRECT: a text position kept in a table entry (lut_direct.h) is decoded and then ignored: the probe reads sa[lo]
 // as it does with a plain table (thm_debug_set_flags bit 6; bit 7 clears it).
-constexpr uint32_t SEED_INFER = 1u, SEED_STATS = 2u, SEED_NODIRECT = 4u;
+// SEED_BOUNDS: the inner positions of a grid cell of the short class are decided from the bounds the two grid probes put
+// on the match end wherever those suffice, and only the others are probed (seed_bounds.h; thm_debug_set_flags bit 16
+// clears it, bit 17 sets it again).  Independent of SEED_INFER: neither changes which positions the other probes.
+constexpr uint32_t SEED_INFER = 1u, SEED_STATS = 2u, SEED_NODIRECT = 4u, SEED_BOUNDS = 8u;
 constexpr int FILL_KEY_BASES = 7;
 constexpr unsigned FILL_BUCKETS = 1u << (2 * FILL_KEY_BASES);  // + one bucket for k-mers with a byte outside ACGT
 size_t seed_select_lds_bytes(uint32_t max_read_len);         // per workgroup (4 waves)

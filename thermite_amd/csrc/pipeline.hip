@@ -132,7 +132,8 @@ int enqueue_seed_t(thm_aligner* a, uint32_t min_seed_len, bool finish_scan) {
   sp.work_long = a->seed.work_long;
   sp.work_cells = a->seed.work_cells;
   sp.work_counts = a->s_work_counts;
-  sp.flags = (a->dbg_seed_noinfer ? 0u : SEED_INFER) | (a->dbg_seed_stats ? SEED_STATS : 0u) | (a->dbg_seed_nodirect ? SEED_NODIRECT : 0u);
+  sp.flags = (a->dbg_seed_noinfer ? 0u : SEED_INFER) | (a->dbg_seed_stats ? SEED_STATS : 0u) | (a->dbg_seed_nodirect ? SEED_NODIRECT : 0u) |
+             (a->dbg_seed_nobounds ? 0u : SEED_BOUNDS);
   sp.smems = a->seed.smems.as<SmemT<C>>();
   sp.smem_cap = a->seed.smem_cap;
   sp.cursor = a->d_cursors;
