@@ -329,6 +329,106 @@ int32_t thm_quant_fetch(thm_quant* q, thm_quant_view* out);
 /* empties both tables and the totals */
 int32_t thm_quant_reset(thm_quant* q);
 
+/* ------------------------------------------------- per-base coverage tracks of a run, built on the device */
+
+/* What a depth counter reads back out of the run's SAM/BAM records (samtools depth, bedtools genomecov -bg -split):
+ * accumulated on the device over any number of batches from what is resident there after thm_batch_run; only finished
+ * runs of equal depth, or a window of depths, cross to the host.  These rules are the contract, each phrased as what a
+ * pass over the run's SAM records would compute.
+ *   Covered bases.  For an alignment at 0-based p = ystart, over the words (len << 4 | code) of its genome CIGAR: an M or
+ *     a D word covers [p, p + len) and advances p; an N word advances p and covers nothing; I and S words do neither.  A
+ *     block is a maximal stretch covered by consecutive M / D words (I and S words between them interrupt nothing, an N
+ *     word ends it): 3M2D4M is one block of 9, 3M4N4M two blocks.  A stretch of length 0 is no block.  Every alignment
+ *     record counts, secondary ones too, with weight 1 (no 1/NH).  An alignment whose digest has THM_DIGEST_LONG_RUN has
+ *     no words: it covers nothing and counts in n_long_run_alns.
+ *   Tracks, chosen at create by `flags`.  THM_COV_STRANDED: forward alignments (SAM flag 0x10 clear: thm_aln::strand == 1)
+ *     and reverse ones are kept apart.  THM_COV_MULTI: alignments with NH > 1 (NH as for thm_quant: the alignments of the
+ *     read) get tracks of their own; without it they cover nothing and count in n_skipped_multi.
+ *     n_strands = STRANDED ? 2 : 1; n_tracks = n_strands * (MULTI ? 2 : 1); track = cls * n_strands + strand_idx with
+ *     cls 0 = unique, 1 = multi and strand_idx 0 = forward, 1 = reverse (always 0 without STRANDED).
+ *   Depth.  depth[track][refID][x] = the number of blocks of that track's alignments that cover x, a 32-bit count: an add
+ *     that would bring the alignments counted by the object (totals.n_alns) over 2^32 - 1 is refused with
+ *     THM_ERR_INVALID_ARG, so no depth can wrap.
+ *   Runs: what a fetch returns for a track and a range of @SQ entries -- the maximal intervals of equal, non-zero depth.
+ *     A run never crosses a contig; runs ascend by refID, then start; two abutting blocks of equal depth make one run; a
+ *     run may end exactly at the contig's length.
+ *   Totals.  n_alns = the track n_alns summed + n_skipped_multi + n_long_run_alns (an alignment counts in one of them: a
+ *     multi-mapped one without a track in n_skipped_multi, whatever its digest says); per track n_alns (alignments that
+ *     went into it), n_blocks and n_bases (the summed block lengths).  Reads: n_reads, and n_failed_reads of them with a
+ *     status other than THM_OK. */
+typedef struct thm_coverage thm_coverage;
+
+#define THM_COV_STRANDED 1u
+#define THM_COV_MULTI 2u
+
+typedef struct thm_cov_run {
+  uint32_t ref_id;      /* BAM refID */
+  uint32_t depth;
+  uint64_t start, end;  /* 0-based, half open */
+} thm_cov_run; /* 24 bytes */
+
+typedef struct thm_cov_track_totals {
+  uint64_t n_alns, n_blocks, n_bases;
+} thm_cov_track_totals;
+
+typedef struct thm_cov_totals {
+  uint64_t n_reads, n_failed_reads, n_alns, n_skipped_multi, n_long_run_alns;
+  thm_cov_track_totals track[4]; /* [n_tracks] used */
+} thm_cov_totals; /* 136 bytes */
+
+typedef struct thm_cov_info {  /* what one add did */
+  thm_cov_totals batch;        /* this batch */
+  uint64_t held_bytes;         /* device memory the object holds: the difference arrays and the scratch of adds and fetches */
+  float add_ms;                /* device events, both kernels of the add */
+} thm_cov_info;
+
+typedef struct thm_cov_view {
+  uint32_t track, first_ref, n_refs;
+  uint32_t max_depth;          /* over the runs; 0 without runs */
+  uint64_t n_runs;
+  const thm_cov_run* runs;     /* [n_runs] */
+  uint64_t n_covered;          /* the sum of end - start over the runs */
+  uint64_t n_bases;            /* the sum of (end - start) * depth: over all contigs, the track's n_bases */
+  thm_cov_totals totals;       /* of the object so far */
+  float fetch_ms;              /* device events: the fetch kernels, scans and the copy */
+} thm_cov_view;
+
+typedef struct thm_cov_depth_view {
+  uint64_t n;
+  const uint32_t* depth;       /* [n] */
+  float depth_ms;
+} thm_cov_depth_view;
+
+/* A thm_coverage belongs to one aligner, like a thm_quant: it works on that aligner's device and stream and must be freed
+ * before it.  It holds n_tracks difference arrays of 4 bytes over every base of every @SQ contig, one more entry behind
+ * each contig (where a block that ends on the contig's last base is closed), and a table of 8 bytes per contig.
+ * THM_ERR_OOM: those bytes exceed max_bytes (0: no cap but the device's memory) or the allocation fails; the message names
+ * the bytes needed and the cap, and nothing is allocated before the cap is checked.  THM_ERR_INVALID_ARG: unknown bits in
+ * `flags`; with thm_batch_fetch_bam's message, an index without names. */
+int32_t thm_coverage_create(thm_aligner* a, uint32_t flags, uint64_t max_bytes, thm_coverage** out);
+void thm_coverage_free(thm_coverage* c);
+/* Stands where thm_batch_fetch stands after thm_batch_run, fails as thm_quant_add fails, runs the CIGAR passes itself
+ * (THM_T_CIGAR is put back) and disturbs no view, counter or timing.  The device validates every alignment in a pass of
+ * its own before any array is touched -- its ref has a refID, cigar_off + n_cigar lies inside the pool, the walk ends
+ * inside the contig -- so a call that fails has added nothing and no add can land outside the arrays.  Then every block
+ * costs two integer adds, whatever its length: batches in any cut and order give the same bytes.  Adding a run twice
+ * doubles every depth. */
+int32_t thm_coverage_add(thm_coverage* c, thm_cov_info* info);
+/* The same kernels over a caller-supplied view, uploaded by the call.  The host checks it first: what thm_quant_add_view
+ * checks of offsets, aln_type, tx_or_gene_idx, ref_id and the CIGAR range, and ystart + digest.ref_len <= the contig's
+ * length -- THM_ERR_INVALID_ARG with a message naming the alignment, as for a view the device's pass refuses (a digest
+ * whose ref_len is not that of its words), and nothing is added. */
+int32_t thm_coverage_add_view(thm_coverage* c, const thm_cigar_view* v, thm_cov_info* info);
+/* The runs of `track` on the @SQ entries [first_ref, first_ref + n_refs), built on the device: a snapshot at any time.
+ * They arrive in a pinned buffer of the object's own, valid until the next fetch, depth call, reset or free.
+ * THM_ERR_INVALID_ARG: no such track, or a range outside the @SQ entries. */
+int32_t thm_coverage_fetch(thm_coverage* c, uint32_t track, uint32_t first_ref, uint32_t n_refs, thm_cov_view* out);
+/* The depth of every base of [start, start + n) of one contig; valid as the runs are.  THM_ERR_INVALID_ARG: no such track
+ * or refID, n over 1 << 24, a window that leaves the contig. */
+int32_t thm_coverage_depth(thm_coverage* c, uint32_t track, uint32_t ref_id, uint64_t start, uint64_t n, thm_cov_depth_view* out);
+/* empties every track and the totals */
+int32_t thm_coverage_reset(thm_coverage* c);
+
 /* ------------------------------------------------- FASTQ blocks parsed on the device */
 
 typedef struct thm_fastq_upload_info {
@@ -550,7 +650,16 @@ typedef struct thm_run_stats {
  * end, strand, unique, multi, max_overhang, then one line per row, start and end the 1-based first and last base of the
  * intron, strand + or -; both tab-separated.  With several aligners their tables are merged on the host by key (counts
  * summed, overhang maximum), so the files do not depend on how the reads were dealt.  A failure to write one is THM_ERR_IO
- * with the path; to standard output the knob is refused with THM_ERR_INVALID_ARG.  thm_run_stats is unchanged. */
+ * with the path; to standard output the knob is refused with THM_ERR_INVALID_ARG.  thm_run_stats is unchanged.
+ * THM_COVERAGE=1, 2 or 3, in every format and mode, beside THM_QUANT or without it: every aligner keeps a thm_coverage and
+ * every batch is added to it after its run (thm_coverage_add); the output file is the unset run's byte for byte.
+ * THM_COVERAGE=1: the unique alignments, both strands together; =2: THM_COV_STRANDED; =3: THM_COV_STRANDED | THM_COV_MULTI.
+ * At the end every track is fetched contig by contig and written whole as <output_path>.cov.<track>.bedgraph, <track> one
+ * of unique, unique.fwd, unique.rev, multi, multi.fwd, multi.rev: lines "name<TAB>start<TAB>end<TAB>depth", 0-based and
+ * half open, contigs in @SQ order, no line of depth 0, no header.  With several aligners their run lists are merged on
+ * the host (depths summed, abutting stretches of equal depth fused), so the files do not depend on how the reads were
+ * dealt.  A failure to write one is THM_ERR_IO with the path; to standard output the knob is refused with
+ * THM_ERR_INVALID_ARG.  thm_run_stats is unchanged. */
 int32_t thm_align_files(thm_aligner* a, const char* const* fastq_paths, uint32_t n_paths, const char* output_path,
                         int32_t format, uint64_t batch_reads, uint32_t n_threads, thm_run_stats* stats);
 /* The same over several aligners -- one per GPU of the node, all over one index (the shape of ThermiteAligner: Clone +

@@ -197,6 +197,51 @@ class QuantView(C.Structure):
                 ("totals", QuantTotals), ("fetch_ms", C.c_float)]
 
 
+COV_STRANDED, COV_MULTI = 1, 2
+COV_TILE = 4096               # cov::TILE of thermite_amd/csrc/coverage_device.h: the positions a fetch works on at a time
+COV_MAX_DEPTH_WINDOW = 1 << 24
+COV_RUN_DT = np.dtype([("ref_id", "<u4"), ("depth", "<u4"), ("start", "<u8"), ("end", "<u8")])
+assert COV_RUN_DT.itemsize == 24
+COV_TOTAL_NAMES = ["n_reads", "n_failed_reads", "n_alns", "n_skipped_multi", "n_long_run_alns"]
+COV_TRACK_TOTAL_NAMES = ["n_alns", "n_blocks", "n_bases"]
+
+
+class CovTrackTotals(C.Structure):
+    """thm_cov_track_totals (include/thermite_io.h)"""
+
+    _fields_ = [(k, C.c_uint64) for k in COV_TRACK_TOTAL_NAMES]
+
+
+class CovTotals(C.Structure):
+    """thm_cov_totals (include/thermite_io.h)"""
+
+    _fields_ = [(k, C.c_uint64) for k in COV_TOTAL_NAMES] + [("track", CovTrackTotals * 4)]
+
+    def as_dict(self):
+        out = {k: int(getattr(self, k)) for k in COV_TOTAL_NAMES}
+        out["track"] = [{k: int(getattr(t, k)) for k in COV_TRACK_TOTAL_NAMES} for t in self.track]
+        return out
+
+
+class CovInfo(C.Structure):
+    """thm_cov_info (include/thermite_io.h)"""
+
+    _fields_ = [("batch", CovTotals), ("held_bytes", C.c_uint64), ("add_ms", C.c_float)]
+
+
+class CovView(C.Structure):
+    """thm_cov_view (include/thermite_io.h)"""
+
+    _fields_ = [("track", C.c_uint32), ("first_ref", C.c_uint32), ("n_refs", C.c_uint32), ("max_depth", C.c_uint32), ("n_runs", C.c_uint64),
+                ("runs", C.c_void_p), ("n_covered", C.c_uint64), ("n_bases", C.c_uint64), ("totals", CovTotals), ("fetch_ms", C.c_float)]
+
+
+class CovDepthView(C.Structure):
+    """thm_cov_depth_view (include/thermite_io.h)"""
+
+    _fields_ = [("n", C.c_uint64), ("depth", C.c_void_p), ("depth_ms", C.c_float)]
+
+
 class FastqUploadInfo(C.Structure):
     """thm_fastq_upload_info (include/thermite_io.h)"""
 
@@ -270,6 +315,8 @@ IO_ABI_SYMBOLS = [
     "thm_writer_header_sorted",
     "thm_bam_sorter_index",
     "thm_quant_create", "thm_quant_free", "thm_quant_add", "thm_quant_add_view", "thm_quant_fetch", "thm_quant_reset",
+    "thm_coverage_create", "thm_coverage_free", "thm_coverage_add", "thm_coverage_add_view", "thm_coverage_fetch", "thm_coverage_depth",
+    "thm_coverage_reset",
 ]
 ERR_IO, ERR_FORMAT = -8, -9
 FMT_PAF, FMT_SAM, FMT_BAM = 0, 1, 2
@@ -465,6 +512,20 @@ def lib():
     L.thm_quant_fetch.argtypes = [vp, vp]
     L.thm_quant_reset.restype = i32
     L.thm_quant_reset.argtypes = [vp]
+    L.thm_coverage_create.restype = i32
+    L.thm_coverage_create.argtypes = [vp, C.c_uint32, C.c_uint64, vp]
+    L.thm_coverage_free.restype = None
+    L.thm_coverage_free.argtypes = [vp]
+    L.thm_coverage_add.restype = i32
+    L.thm_coverage_add.argtypes = [vp, vp]
+    L.thm_coverage_add_view.restype = i32
+    L.thm_coverage_add_view.argtypes = [vp, vp, vp]
+    L.thm_coverage_fetch.restype = i32
+    L.thm_coverage_fetch.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]
+    L.thm_coverage_depth.restype = i32
+    L.thm_coverage_depth.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, vp]
+    L.thm_coverage_reset.restype = i32
+    L.thm_coverage_reset.argtypes = [vp]
     L.thm_debug_bam_sorter_add_records.restype = i32
     L.thm_debug_bam_sorter_add_records.argtypes = [vp, vp, u64]
     L.thm_debug_bam_sorter_gather.restype = i32
@@ -959,6 +1020,84 @@ class Quant:
     def close(self):
         if getattr(self, "h", None):
             lib().thm_quant_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+
+class CoverageResult:
+    """thm_cov_view copied out: the runs (COV_RUN_DT, ascending by ref_id, start), max_depth, n_covered, n_bases and the
+    object's totals as a dict"""
+
+    def __init__(self, view):
+        self.track, self.first_ref, self.n_refs = int(view.track), int(view.first_ref), int(view.n_refs)
+        self.runs = _copy(view.runs, view.n_runs, COV_RUN_DT)
+        self.max_depth, self.n_covered, self.n_bases = int(view.max_depth), int(view.n_covered), int(view.n_bases)
+        self.totals = view.totals.as_dict()
+        self.fetch_ms = view.fetch_ms
+
+
+class Coverage:
+    """thm_coverage: per-base coverage tracks of a run, accumulated on the aligner's device batch by batch.  Close it
+    before its aligner."""
+
+    def __init__(self, aligner, flags=0, max_bytes=0):
+        self.aligner = aligner
+        self.flags = flags
+        self.n_tracks = (2 if flags & COV_STRANDED else 1) * (2 if flags & COV_MULTI else 1)
+        h = C.c_void_p()
+        rc = lib().thm_coverage_create(aligner.h, flags, max_bytes, C.byref(h))
+        if rc != 0:
+            raise ThermiteError(rc, (lib().thm_last_error(aligner.h) or b"").decode())
+        self.h = h
+
+    @staticmethod
+    def _info(info):
+        out = info.batch.as_dict()
+        out.update(held_bytes=int(info.held_bytes), add_ms=info.add_ms)
+        return out
+
+    def add(self):
+        """thm_coverage_add, after Aligner.run -> the batch's totals, held_bytes and add_ms as a dict"""
+        info = CovInfo()
+        self.aligner._chk(lib().thm_coverage_add(self.h, C.byref(info)))
+        return self._info(info)
+
+    def add_view(self, offsets, alns, digests, cigar, status=None):
+        """thm_coverage_add_view: the same kernels over caller-made arrays (ALN_DT, DIGEST_DT, CIGAR words)"""
+        off = np.ascontiguousarray(offsets, dtype="<u8")
+        al = np.ascontiguousarray(alns, dtype=ALN_DT)
+        dg = np.ascontiguousarray(digests, dtype=DIGEST_DT)
+        cg = np.ascontiguousarray(cigar, dtype="<u4")
+        st = np.ascontiguousarray(status, dtype="<i4") if status is not None else None
+        n_reads = max(len(off) - 1, 0)
+        v = CigarView(n_reads, len(al), len(cg), _ptr(off) if len(off) else None, _ptr(al) if len(al) else None,
+                      _ptr(dg) if len(dg) else None, _ptr(cg) if len(cg) else None,
+                      int((st != 0).sum()) if st is not None else 0, _ptr(st) if st is not None and len(st) else None)
+        info = CovInfo()
+        self.aligner._chk(lib().thm_coverage_add_view(self.h, C.byref(v), C.byref(info)))
+        return self._info(info)
+
+    def fetch(self, track, first_ref, n_refs):
+        """thm_coverage_fetch: the runs of `track` on the @SQ entries [first_ref, first_ref + n_refs)"""
+        v = CovView()
+        self.aligner._chk(lib().thm_coverage_fetch(self.h, track, first_ref, n_refs, C.byref(v)))
+        return CoverageResult(v)
+
+    def depth(self, track, ref_id, start, n):
+        """thm_coverage_depth -> uint32[n]; the call's depth_ms is left in self.depth_ms"""
+        v = CovDepthView()
+        self.aligner._chk(lib().thm_coverage_depth(self.h, track, ref_id, start, n, C.byref(v)))
+        self.depth_ms = v.depth_ms
+        return _copy(v.depth, v.n, np.dtype("<u4"))
+
+    def reset(self):
+        self.aligner._chk(lib().thm_coverage_reset(self.h))
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().thm_coverage_free(self.h)
             self.h = None
 
     def __del__(self):

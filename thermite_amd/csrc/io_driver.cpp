@@ -567,6 +567,8 @@ struct Modes {
                               // (thm_batch_upload_fastq_gzip)
   bool quant = false;         // THM_QUANT=1, any format: every batch is added to its aligner's thm_quant behind its fetch, and
                               // <output_path>.genes.tsv / .junctions.tsv are written at the end
+  bool coverage = false;      // THM_COVERAGE=1..3, any format: every batch is added to its aligner's thm_coverage behind its fetch, and
+  uint32_t cov_flags = 0;     // <output_path>.cov.<track>.bedgraph are written at the end; =2: THM_COV_STRANDED, =3: ... | THM_COV_MULTI
   static Modes read(int32_t format) {
     auto is = [](const char* name, const char* v) {
       const char* e = getenv(name);
@@ -582,6 +584,8 @@ struct Modes {
     m.fastq_bgzf = m.fastq_gzip || (m.bam_device && is("THM_FASTQ_DEVICE", "2"));
     m.fastq_device = m.fastq_bgzf || (m.bam_device && is("THM_FASTQ_DEVICE", "1"));
     m.quant = is("THM_QUANT", "1");
+    m.coverage = is("THM_COVERAGE", "1") || is("THM_COVERAGE", "2") || is("THM_COVERAGE", "3");
+    m.cov_flags = is("THM_COVERAGE", "2") ? THM_COV_STRANDED : is("THM_COVERAGE", "3") ? (THM_COV_STRANDED | THM_COV_MULTI) : 0u;
     return m;
   }
 };
@@ -701,6 +705,7 @@ struct Run {
   Output& out;
   thm_bam_sorter* sorter;
   thm_quant* const* quants = nullptr;  // THM_QUANT=1: one per aligner
+  thm_coverage* const* coverages = nullptr;  // THM_COVERAGE: one per aligner
 
   Shared sh;
   thm_run_stats st;
@@ -1121,6 +1126,10 @@ void Run::gpu(uint32_t gi) {
         thm_quant_info qi;
         grc = sh.step([&] { return (int)thm_quant_add(quants[gi], &qi); });
       }
+      if (grc == THM_OK && coverages) {
+        thm_cov_info ci;
+        grc = sh.step([&] { return (int)thm_coverage_add(coverages[gi], &ci); });
+      }
       if (grc != THM_OK) {
         sh.set(grc, thm_last_error(a));
       } else {
@@ -1367,6 +1376,60 @@ int write_quant_tables(const thm_index* ix, thm_aligner* const* aligners, thm_qu
   return THM_OK;
 }
 
+// THM_COVERAGE: every track of every aligner, contig by contig, as <output_path>.cov.<track>.bedgraph.  The run lists of
+// several aligners are merged by a sweep over the change points of all of them with the depths summed, so that abutting
+// stretches of equal depth fuse: the files do not depend on how the reads were dealt.
+int write_coverage_tracks(const thm_index* ix, thm_aligner* const* aligners, thm_coverage* const* coverages, uint32_t n, uint32_t cov_flags,
+                          const std::string& output_path, std::string& err) {
+  std::vector<std::pair<std::string, uint64_t>> sq;
+  (void)thm::sq_of_name(ix, &sq);
+  const bool stranded = cov_flags & THM_COV_STRANDED, multi = cov_flags & THM_COV_MULTI;
+  std::vector<std::string> tracks;
+  for (const char* cls : {"unique", "multi"}) {
+    if (cls[0] == 'm' && !multi) continue;
+    if (stranded) {
+      tracks.push_back(std::string(cls) + ".fwd");
+      tracks.push_back(std::string(cls) + ".rev");
+    } else {
+      tracks.push_back(cls);
+    }
+  }
+  for (uint32_t k = 0; k < tracks.size(); k++) {
+    std::string text;
+    for (uint32_t s = 0; s < sq.size(); s++) {
+      std::map<uint64_t, int64_t> step;  // position -> change of the summed depth there
+      for (uint32_t i = 0; i < n; i++) {
+        thm_cov_view v;
+        const int rc = thm_coverage_fetch(coverages[i], k, s, 1, &v);
+        if (rc != THM_OK) {
+          err = thm_last_error(aligners[i]);
+          return rc;
+        }
+        for (uint64_t r = 0; r < v.n_runs; r++) {
+          step[v.runs[r].start] += (int64_t)v.runs[r].depth;
+          step[v.runs[r].end] -= (int64_t)v.runs[r].depth;
+        }
+      }
+      int64_t depth = 0;
+      uint64_t from = 0;
+      for (const auto& kv : step) {
+        if (kv.second == 0) continue;  // two runs abut with equal depths: no change point
+        if (depth) text += sq[s].first + "\t" + std::to_string(from) + "\t" + std::to_string(kv.first) + "\t" + std::to_string(depth) + "\n";
+        depth += kv.second;
+        from = kv.first;
+      }
+    }
+    const std::string path = output_path + ".cov." + tracks[k] + ".bedgraph";
+    Output o;
+    const bool ok = o.open(path.c_str()) && o.write_all(text.data(), text.size(), 0);
+    if (!o.close() || !ok) {
+      err = "cannot write " + path;
+      return THM_ERR_IO;
+    }
+  }
+  return THM_OK;
+}
+
 }  // namespace
 
 extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t n_aligners, const char* const* fastq_paths,
@@ -1389,6 +1452,10 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
   }
   if (m.quant && !strcmp(output_path, "-")) {
     thm::set_global_error("thm_align_files_multi: THM_QUANT=1 needs an output file (the tables are written beside it)");
+    return THM_ERR_INVALID_ARG;
+  }
+  if (m.coverage && !strcmp(output_path, "-")) {
+    thm::set_global_error("thm_align_files_multi: THM_COVERAGE needs an output file (the tracks are written beside it)");
     return THM_ERR_INVALID_ARG;
   }
   const thm_index* ix = thm_aligner_index(aligners[0]);
@@ -1427,6 +1494,17 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
       thm_writer_free(w);
       return rc;
     }
+  std::vector<thm_coverage*> coverages(m.coverage ? n_aligners : 0, nullptr);
+  for (size_t i = 0; i < coverages.size(); i++)
+    if ((rc = thm_coverage_create(aligners[i], m.cov_flags, 0, &coverages[i])) != THM_OK) {
+      thm::set_global_error(thm_last_error(aligners[i]));
+      for (thm_coverage* c : coverages) thm_coverage_free(c);
+      for (thm_quant* q : quants) thm_quant_free(q);
+      thm_bam_sorter_free(sorter);
+      (void)out.close();
+      thm_writer_free(w);
+      return rc;
+    }
   const auto t_start = Clock::now();
   thm_writer* w2 = nullptr;
   const bool have_w2 = thm_writer_create(ix, format, n_threads, &w2) == THM_OK;
@@ -1435,6 +1513,7 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
   if (!have_w2) run.sh.set(THM_ERR_OOM, "cannot create the second writer object");
   run.index_path = std::string(output_path) + ".bai";
   if (m.quant) run.quants = quants.data();
+  if (m.coverage) run.coverages = coverages.data();
   // ---- the stages: the cutter, the parsers, a thread per aligner; this thread formats
   std::thread cutter(&Run::cut, &run);
   std::vector<std::thread> parsers, gpus;
@@ -1453,6 +1532,12 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
     const int qrc = run.sh.step([&] { return write_quant_tables(ix, aligners, quants.data(), n_aligners, output_path, err); });
     if (qrc != THM_OK) run.sh.set(qrc, err);
   }
+  if (m.coverage && run.sh.rc == THM_OK) {
+    std::string err;
+    const int crc = run.sh.step([&] { return write_coverage_tracks(ix, aligners, coverages.data(), n_aligners, m.cov_flags, output_path, err); });
+    if (crc != THM_OK) run.sh.set(crc, err);
+  }
+  for (thm_coverage* c : coverages) thm_coverage_free(c);
   for (thm_quant* q : quants) thm_quant_free(q);
   thm_bam_sorter_free(sorter);
   if (!out.close()) run.sh.set(THM_ERR_IO, std::string("error closing ") + output_path);

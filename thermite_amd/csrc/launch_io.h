@@ -1,5 +1,5 @@
 // launch_io.h -- parameter blocks and launch wrappers of the kernels behind the file-level entry points (BAM, BGZF, BAM
-// sort, quant, BAI, FASTQ, inflate, gzip): what the alignment pipeline itself never sees.  The pipeline's are in launch.h.
+// sort, quant, coverage, BAI, FASTQ, inflate, gzip): what the alignment pipeline itself never sees.  The pipeline's are in launch.h.
 #ifndef THERMITE_LAUNCH_IO_H
 #define THERMITE_LAUNCH_IO_H
 
@@ -165,6 +165,71 @@ hipError_t launch_quant_reduce(const QuantReduceParams& p, hipStream_t s);
 hipError_t launch_quant_lookup(const QuantMergeParams& p, hipStream_t s);
 hipError_t launch_quant_update(const QuantMergeParams& p, hipStream_t s);
 hipError_t launch_quant_rows(const QuantRows& in, uint64_t n, thm_quant_junction* out, hipStream_t s);
+
+// ---- per-base coverage tracks of a run (kernels_coverage.hip, coverage_device.h; host side coverage.hip) ----
+// add:   count (per alignment: its track, the checks, its blocks and bases; per read: the read totals) ... the host
+//        reads the totals and the first bad alignment ... deposit (two integer adds per block).
+// fetch: tiles (per tile of the range: the sum of its entries and the number of non-zero ones) -> two scans -> points
+//        (per tile: a local scan plus the carry is the depth; (entry, depth) per change point) -> scan of the points with
+//        a depth -> runs (a thread per change point pairs it with its successor).
+// depth: tiles and the scan of the sums -> window (the local scan again, the depths of the window's entries).
+struct CovBatch {
+  uint64_t n_reads, n_alns, n_words;
+  const uint64_t* aln_off;        // [n_reads + 1]
+  const thm_aln* alns;            // [n_alns]
+  const thm_aln_digest* digests;  // [n_alns]
+  const uint32_t* words;          // [n_words]
+  const int32_t* status;          // [n_reads]; null: no read failed
+  uint32_t n_refs, n_sq, flags;   // flags: THM_COV_*
+  const int32_t* ref_sq;          // [n_refs] BAM refID, -1: none
+  const uint64_t* base;           // [n_sq + 1] first entry of every contig in a track (coverage_device.h)
+};
+struct CovCountParams {
+  CovBatch b;
+  uint8_t* track;              // [n_alns] the track an alignment deposits into, cov::NO_TRACK: none
+  unsigned long long* totals;  // [cov::N_TOTALS] zeroed by the caller
+  unsigned long long* bad;     // the first alignment that fails a check (atomic minimum; ~0: none)
+};
+struct CovDepositParams {
+  CovBatch b;
+  const uint8_t* track;
+  uint32_t* diff;              // [n_tracks * track_entries]
+  uint64_t track_entries;      // base[n_sq]
+};
+struct CovTileParams {
+  const uint32_t* diff;        // the first entry of the range
+  uint64_t n;                  // entries of the range
+  uint64_t* tile_sum;          // [n_tiles + 1] tiles: the 32-bit sum of the tile's entries
+  uint64_t* tile_cnt;          // [n_tiles + 1] tiles: its non-zero entries
+  const uint64_t* carry;       // [n_tiles + 1] scan of tile_sum (its low 32 bits are the depth in front of the tile)
+  const uint64_t* point_at;    // [n_tiles + 1] scan of tile_cnt
+  uint64_t g0;                 // the range's first entry in the track
+  uint64_t* point_entry;       // [n_points] points: the entry (in the track) of every change point
+  uint32_t* point_depth;       // [n_points]
+  uint64_t* point_live;        // [n_points + 1] 1 where the depth is not 0
+};
+struct CovRunParams {
+  const uint64_t* point_entry;
+  const uint32_t* point_depth;
+  const uint64_t* run_at;      // [n_points + 1] scan of point_live
+  uint64_t n_points;
+  const uint64_t* base;
+  uint32_t n_sq;
+  thm_cov_run* runs;           // [run_at[n_points]]
+  unsigned long long* stats;   // [3] zeroed: n_covered, n_bases, max_depth
+};
+struct CovWindowParams {
+  const uint32_t* diff;        // the contig's first entry
+  const uint64_t* carry;       // [n_tiles + 1] over the tiles of [0, start + n)
+  uint64_t start, n;           // the window
+  uint32_t* out;               // [n]
+};
+hipError_t launch_cov_count(const CovCountParams& p, int n_cu, hipStream_t s);
+hipError_t launch_cov_deposit(const CovDepositParams& p, hipStream_t s);
+hipError_t launch_cov_tiles(const CovTileParams& p, hipStream_t s);
+hipError_t launch_cov_points(const CovTileParams& p, hipStream_t s);
+hipError_t launch_cov_runs(const CovRunParams& p, hipStream_t s);
+hipError_t launch_cov_window(const CovWindowParams& p, hipStream_t s);
 
 // ---- BAI index of the sorted stream (kernels_bai.hip, bai_device.h; host side bai.hip) ----
 // fields (per sorted record: key = refID << 16 | bin, beg, end; per reference the mapped count and n_intv) -> run heads,

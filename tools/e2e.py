@@ -19,16 +19,24 @@ thm_bam_sorter_index, three calls.  The gzip files are not made.
 --quant[=ROUNDS]: only plain FASTQ -> BAM with THM_BAM_DEVICE=1, without and with THM_QUANT=1 alternately, ROUNDS rounds
 (default 3) in one session (the two .tsv files' sizes are reported); then one batch of 500 000 reads, of 91 and of 150
 bases, through thm_quant by hand: add_ms and fetch_ms beside THM_T_CIGAR and THM_T_COMPACT of the same run, five adds each.
+--coverage[=ROUNDS]: as --quant with THM_COVERAGE=3 (the bedGraph files' sizes are reported); then one batch of 500 000 reads,
+of 91 and of 150 bases, through thm_coverage by hand: add_ms of five adds and fetch_ms of every track beside THM_T_CIGAR
+and thm_quant_add's add_ms of the same run; then add_ms of 500 000 alignments of 50M at one position beside the same
+number spread over the contig (the contention of the deposit's atomics).
 --sha[=PART]: with any of the modes above, "sha256 <hash> <file> <bytes>" for every output file before it is removed (two
 builds of the library -- THM_LIB selects one -- are compared by these lines); with PART also, after every run that wrote a
 file whose name holds PART, "each <file> raw <hash> inflated <hash> size <bytes> batches <n>": does an output repeat from
 run to run, compressed and inflated?"""
 import hashlib, os, sys, time
-BAM_RUNS = FQ_ROUNDS = BGZF_ROUNDS = GZIP_ROUNDS = SORT_ROUNDS = QUANT_ROUNDS = 0
+BAM_RUNS = FQ_ROUNDS = BGZF_ROUNDS = GZIP_ROUNDS = SORT_ROUNDS = QUANT_ROUNDS = COV_ROUNDS = 0
 SHA, SHA_EACH = False, None
 for arg in list(sys.argv[1:]):
     if arg.startswith("--sha"):
         SHA, SHA_EACH = True, (arg.split("=")[1] if "=" in arg else None)
+        sys.argv.remove(arg)
+        continue
+    if arg.startswith("--coverage"):
+        COV_ROUNDS = int(arg.split("=")[1]) if "=" in arg else 3
         sys.argv.remove(arg)
         continue
     if arg.startswith("--quant"):
@@ -108,6 +116,69 @@ with open(big, "wb") as f:
         f.write(one)
     del one
 print("plain input: %d reads, %.1f MB" % (n * REP, os.path.getsize(big) / 1e6), flush=True)
+if COV_ROUNDS:
+    import glob
+    os.environ["THM_BAM_DEVICE"] = "1"
+    out = "/tmp/thm_e2e_out.bam"
+    st = capi.align_files(a, [big], out, capi.FMT_BAM, batch_reads=250000, n_threads=threads)   # warm-up: buffers grow
+    for k in range(COV_ROUNDS):
+        for tag, on in (("THM_BAM_DEVICE=1               ", False), ("THM_BAM_DEVICE=1 THM_COVERAGE=3", True)):
+            os.environ.pop("THM_COVERAGE", None)
+            if on:
+                os.environ["THM_COVERAGE"] = "3"
+            st = capi.align_files(a, [big], out, capi.FMT_BAM, batch_reads=250000, n_threads=threads)
+            files = ""
+            for f in sorted(glob.glob(out + ".cov.*.bedgraph")):
+                files += ", %s %d bytes" % (f[len(out) + 5:], os.path.getsize(f))
+                os.remove(f)
+            print("bam %s round %d: %.2f Mreads/s wall %.3fs | parse %.2fs gpu %.2fs format %.2fs write %.2fs | %d batches, %.0f MB out%s" % (
+                tag, k, st["n_reads"] / st["wall_s"] / 1e6, st["wall_s"], st["parse_s"], st["gpu_s"], st["format_s"], st["write_s"],
+                st["n_batches"], st["n_output_bytes"] / 1e6, files), flush=True)
+    os.environ.pop("THM_COVERAGE", None)
+    # one batch of 500 000 reads by hand
+    for L in (91, 150):
+        b, o, _ = synth.simulate_reads(t, 500000, L, sub_rate=0.01, indel_rate=0.001, stream=7)
+        c = capi.Coverage(a, capi.COV_STRANDED | capi.COV_MULTI)
+        q = capi.Quant(a)
+        a.upload(b, o)
+        a.run()
+        a.fetch_cigars(copy=False)
+        tm = a.timings()
+        adds = [c.add() for _ in range(5)]
+        q_adds = [q.add() for _ in range(5)]
+        fetches = [[c.fetch(k, 0, 1) for k in range(4)] for _ in range(3)]
+        depth_ms = []
+        for _ in range(3):
+            c.depth(0, 0, ref_len // 2, 1 << 20)
+            depth_ms.append(c.depth_ms)
+        tr = adds[0]["track"]
+        print("coverage %d bp: 500000 reads, %d alns, %d blocks, %d bases, held %.1f MB | add_ms %s | fetch_ms per track %s | runs per track %s, max depth %d | "
+              "depth_ms of 2^20 bases %s | thm_quant_add add_ms %s | THM_T_CIGAR %.3f THM_T_COMPACT %.3f THM_T_TOTAL %.3f" % (
+                  L, adds[0]["n_alns"], sum(x["n_blocks"] for x in tr), sum(x["n_bases"] for x in tr), adds[0]["held_bytes"] / 1e6,
+                  " ".join("%.3f" % x["add_ms"] for x in adds), " | ".join(" ".join("%.3f" % x.fetch_ms for x in f) for f in fetches),
+                  " ".join("%d" % len(x.runs) for x in fetches[0]), max(x.max_depth for x in fetches[0]),
+                  " ".join("%.3f" % x for x in depth_ms), " ".join("%.3f" % x["add_ms"] for x in q_adds), tm["cigar"], tm["compact"], tm["total"]), flush=True)
+        q.close()
+        c.close()
+    # the contention of the deposit: every alignment on one position, and the same number spread out
+    N = 500000
+    fwd_ref = int(np.nonzero(t["refs"]["strand"] == 1)[0][0])
+    rng = np.random.default_rng(11)
+    for tag, ystart in (("hot   ", np.full(N, ref_len // 3, np.uint64)), ("spread", rng.integers(0, ref_len - 100, N).astype(np.uint64))):
+        alns = np.zeros(N, capi.ALN_DT)
+        alns["ystart"], alns["ref_id"], alns["aln_type"], alns["tx_or_gene_idx"], alns["strand"] = ystart, fwd_ref, 2, 0xFFFFFFFF, 1
+        dig = np.zeros(N, capi.DIGEST_DT)
+        dig["cigar_off"], dig["n_cigar"], dig["ref_len"] = np.arange(N, dtype=np.uint64), 1, 50
+        words = np.full(N, 50 << 4, "<u4")
+        c = capi.Coverage(a, 0)
+        adds = [c.add_view(np.arange(N + 1, dtype="<u8"), alns, dig, words) for _ in range(5)]
+        res = c.fetch(0, 0, 1)
+        print("deposit %s: %d alignments of 50M, %d runs, max depth %d | add_ms %s | fetch_ms %.3f" % (
+            tag, N, len(res.runs), res.max_depth, " ".join("%.3f" % x["add_ms"] for x in adds), res.fetch_ms), flush=True)
+        c.close()
+    a.close()
+    drop(out)
+    sys.exit(0)
 if QUANT_ROUNDS:
     os.environ["THM_BAM_DEVICE"] = "1"
     out = "/tmp/thm_e2e_out.bam"
