@@ -33,6 +33,9 @@ def tables(key):
         t, info = beyond_team_reference()
         t["_info"] = info
         return t
+    if key == "contigs":
+        import contigs_common
+        return contigs_common.world()[0]
     raise KeyError(key)
 
 
@@ -93,6 +96,10 @@ def read_set(name, t):
         seqs = [seqs[i] for i in order]
         return dict(names=[b"b%d" % i for i in range(len(seqs))], seqs=seqs, quals=_quals(rng, seqs),
                     opts=dict(capi.CI_OPTS, multimap_score_range=6))
+    if name == "contigs":  # many contigs, names not in byte order: alignments of one read on several references, most references short
+        import contigs_common
+        seqs = contigs_common.read_set()["seqs"]
+        return dict(names=[b"g%d" % i for i in range(len(seqs))], seqs=seqs, quals=_quals(rng, seqs), opts=capi.CI_OPTS)
     raise KeyError(name)
 
 
@@ -118,7 +125,8 @@ def multi_reference(seed=0x62616D):
     return t
 
 
-REF_OF = dict(test_query="test_ref", chrm_ci="chrm", chrm_default="chrm", syn="syn", multi="multi", micro="micro", beyond="beyond")
+REF_OF = dict(test_query="test_ref", chrm_ci="chrm", chrm_default="chrm", syn="syn", multi="multi", micro="micro", beyond="beyond",
+              contigs="contigs")
 READ_SETS = list(REF_OF)
 
 

@@ -262,3 +262,37 @@ def assert_host_matches_oracle(w, opts, bases, off, out, half, per_read=96):
         assert (int(r1.counters[9]), int(r1.counters[12]), int(r1.counters[13])) == (int(o["calls"]), int(o["op_bytes"]), int(o["window_bytes"])), \
             ("counters of read", int(i), r1.counters[:14], o)
     return len(done)
+
+
+# ------------------------------------------------------------------ the finisher on the device
+def check_device(exe, w, opts, reads, tmp_path, pool_caps=None, expect=None):
+    """on the device (for tests marked gpu): check_align, then the three settings of the class switches with the finished / left
+    counts of the host program -> (class E finished, class E left, class S finished, class S left) with both classes on"""
+    import gpu_common as gc
+    bases, off = reads if isinstance(reads, tuple) else refdata.pack_reads(reads)
+    r = w.oix.align_batch(bases, off, opts, n_threads=8)
+    gc.check_align(w, bases, off, opts, pool_caps=pool_caps, ref=r)
+    counts = None
+    for classes in (CLASS_E | CLASS_S, CLASS_E, CLASS_S):
+        out, _ = run_host(exe, w, opts, bases, off, tmp_path, classes=classes, tag="c%d" % classes)
+        a = w.aligner(opts)
+        a.debug_set_flags(tpr=False, finish_exact=bool(classes & CLASS_E), finish_subst=bool(classes & CLASS_S))
+        if pool_caps:
+            a.debug_set_pool_caps(**pool_caps)
+        a.reset_counters()
+        g = a.align_batch(bases, off)
+        gc.assert_batch_equal(g, r)
+        gc.assert_counters_match(a.counters(), r.counters, classes)
+        got, want = a.debug_smem_finish_stats(), finished_counts(out)
+        assert got == want, (classes, got, want)
+        if classes == (CLASS_E | CLASS_S):
+            counts = want
+            done = int(out["what"].sum())
+            if expect == "all":
+                assert done == len(off) - 1
+                # finished reads add nothing to dp_cells and dp_cols: with every read finished both stay 0
+                assert a.counters()[10] == 0 and a.counters()[11] == 0, a.counters()[:14]
+            if expect == "none":
+                assert done == 0
+        a.close()
+    return counts

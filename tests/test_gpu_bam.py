@@ -150,7 +150,7 @@ def test_empty_batch_and_a_batch_without_alignments():
 
 
 # ------------------------------------------------------------------ annotation flag
-@pytest.mark.parametrize("name", ["multi", "syn", "micro", "test_query"])
+@pytest.mark.parametrize("name", ["multi", "syn", "micro", "test_query", "contigs"])
 def test_no_annotation_tags(name):
     w, rs, b, r, data, off = _set(name)
     stripped = bc.strip_annotation(data)

@@ -71,7 +71,7 @@ def _subset(rs, idx):
 
 
 # ------------------------------------------------------------------ 1. read sets
-@pytest.mark.parametrize("name,wide", [(n, False) for n in ("test_query", "syn", "multi", "micro")] + [("syn", True)],
+@pytest.mark.parametrize("name,wide", [(n, False) for n in ("test_query", "syn", "multi", "micro", "contigs")] + [("syn", True)],
                          ids=lambda v: {False: "c32", True: "c64"}.get(v, v) if isinstance(v, bool) else v)
 def test_read_sets_come_out_in_coordinate_order(name, wide):
     w, rs, b, r, data = _set(name, wide)

@@ -81,7 +81,7 @@ def test_encoder_edge_cases(name):
 
 
 # ------------------------------------------------------------------ 2. record streams
-@pytest.mark.parametrize("name,wide", [(n, False) for n in ("test_query", "syn", "micro", "multi", "beyond")] + [("syn", True)],
+@pytest.mark.parametrize("name,wide", [(n, False) for n in ("test_query", "syn", "micro", "multi", "beyond", "contigs")] + [("syn", True)],
                          ids=lambda v: {False: "c32", True: "c64"}.get(v, v) if isinstance(v, bool) else v)
 def test_members_inflate_to_the_bam_records(name, wide, tmp_path):
     w, rs, b = _set(name, wide)

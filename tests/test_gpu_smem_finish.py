@@ -34,35 +34,7 @@ def exe(tmp_path_factory):
     return sf.host_program(tmp_path_factory.mktemp("smem_finish_gpu"))
 
 
-def check(exe, w, opts, reads, tmp_path, pool_caps=None, expect=None):
-    """check_align, then the three settings of the class switches with the finished / left counts of the host program"""
-    bases, off = reads if isinstance(reads, tuple) else refdata.pack_reads(reads)
-    r = w.oix.align_batch(bases, off, opts, n_threads=8)
-    gc.check_align(w, bases, off, opts, pool_caps=pool_caps, ref=r)
-    counts = None
-    for classes in (sf.CLASS_E | sf.CLASS_S, sf.CLASS_E, sf.CLASS_S):
-        out, _ = sf.run_host(exe, w, opts, bases, off, tmp_path, classes=classes, tag="c%d" % classes)
-        a = w.aligner(opts)
-        a.debug_set_flags(tpr=False, finish_exact=bool(classes & sf.CLASS_E), finish_subst=bool(classes & sf.CLASS_S))
-        if pool_caps:
-            a.debug_set_pool_caps(**pool_caps)
-        a.reset_counters()
-        g = a.align_batch(bases, off)
-        gc.assert_batch_equal(g, r)
-        gc.assert_counters_match(a.counters(), r.counters, classes)
-        got, want = a.debug_smem_finish_stats(), sf.finished_counts(out)
-        assert got == want, (classes, got, want)
-        if classes == (sf.CLASS_E | sf.CLASS_S):
-            counts = want
-            done = int(out["what"].sum())
-            if expect == "all":
-                assert done == len(off) - 1
-                # finished reads add nothing to dp_cells and dp_cols: with every read finished both stay 0
-                assert a.counters()[10] == 0 and a.counters()[11] == 0, a.counters()[:14]
-            if expect == "none":
-                assert done == 0
-        a.close()
-    return counts
+check = sf.check_device
 
 
 def test_exact_reads(exe, tmp_path):
