@@ -429,6 +429,104 @@ int32_t thm_coverage_depth(thm_coverage* c, uint32_t track, uint32_t ref_id, uin
 /* empties every track and the totals */
 int32_t thm_coverage_reset(thm_coverage* c);
 
+/* ------------------------------------------------- per-base allele counts of a run, built on the device */
+
+/* What a pileup reads back out of the run's SAM records and the FASTA (samtools mpileup without a quality filter, counted
+ * per base): accumulated on the device over any number of batches from what is resident there after thm_batch_run -- the
+ * raw reads, the alignments, the genome CIGAR words and the index's text, whose forward copy of a contig is its sequence.
+ * Only rows of sites cross to the host.  These rules are the contract, each phrased as what a pass over the run's SAM
+ * records and the FASTA would compute.
+ *   Alignments used.  Every alignment record counts, secondary ones too, with weight 1.  The alignments of a read with
+ *     NH > 1 (NH as for thm_quant: the alignments of the read) are left out and count in n_skipped_multi, whatever their
+ *     digests say; with THM_PILE_MULTI they count like the others, into the same counts.  An alignment whose digest has
+ *     THM_DIGEST_LONG_RUN has no words: it contributes nothing and counts in n_long_run_alns.  The others are the
+ *     n_used_alns: n_alns = n_skipped_multi + n_long_run_alns + n_used_alns.
+ *   SEQ is what SAM prints: the read for thm_aln::strand == 1, otherwise its reverse complement.  kind(c) of a byte:
+ *     upper-cased, A C G T are 0..3 and anything else is 4 (N); the complement of kind 4 is kind 4.
+ *   Walk.  From 0-based p = ystart and q = 0 over the words (len << 4 | code) of the genome CIGAR: an M word lets position
+ *     p + i observe kind(SEQ[q + i]) for i < len, then p and q advance; a D word lets each of [p, p + len) observe one
+ *     `del`, p advances; an N word advances p; an S word advances q; an I word is one `ins` (the word, not its bases)
+ *     observed at x = p - 1 if p > ystart, else at x = ystart -- which may be an intron base directly behind an N word --
+ *     and q advances.  An alignment that consumes no reference base observes nothing.  M + I + S over the words is the
+ *     read's length.
+ *   Depth.  depth[x] = the number of used alignments whose M or D words cover x (the blocks of thm_coverage), a 32-bit
+ *     count: an add that would bring totals.n_alns over 2^32 - 1 is refused with THM_ERR_INVALID_ARG.
+ *   Counts at x.  cnt[0..4] = the M observations of each kind, del and ins as in the walk; depth[x] == cnt[0] + ... +
+ *     cnt[4] + del.  An event is an observation whose kind differs from kind(the text's byte at x), or any del or ins;
+ *     alt[x] = the events at x.  The reference allele's count is never stored: it is depth minus the rest.  The cap on
+ *     n_alns bounds depth, cnt and del below 2^32; ins, of which one alignment can bring several to one position, stays at
+ *     2^32 - 1 once it has reached it.
+ *   Totals.  n_blocks: the blocks of the used alignments; n_m_bases: their M bases; n_mismatches: the events of kinds
+ *     0..4; n_del_bases; n_ins (I words) and n_ins_bases (their summed lengths).  Reads: n_reads, and n_failed_reads of
+ *     them with a status other than THM_OK. */
+typedef struct thm_pileup thm_pileup;
+
+#define THM_PILE_MULTI 1u
+
+typedef struct thm_pile_site {
+  uint32_t ref_id;             /* BAM refID */
+  uint8_t ref_base, pad_[3];   /* the text's byte at pos */
+  uint64_t pos;                /* 0-based */
+  uint32_t depth, cnt[5], del, ins;
+} thm_pile_site; /* 48 bytes */
+
+typedef struct thm_pile_totals {
+  uint64_t n_reads, n_failed_reads, n_alns, n_skipped_multi, n_long_run_alns, n_used_alns, n_blocks;
+  uint64_t n_m_bases, n_mismatches, n_del_bases, n_ins, n_ins_bases;
+} thm_pile_totals; /* 96 bytes */
+
+typedef struct thm_pile_info { /* what one add did */
+  thm_pile_totals batch;       /* this batch */
+  uint64_t n_events;           /* rows of the event table so far: distinct (position, kind) with an event */
+  uint64_t held_bytes;         /* device memory the object holds: the difference array, the table and every scratch */
+  float add_ms;                /* device events, every pass of the add */
+} thm_pile_info;
+
+typedef struct thm_pile_view {
+  uint32_t first_ref, n_refs;  /* the range asked for (a window: its refID and 1) */
+  uint32_t min_alt, pad_;      /* 0 for a window */
+  uint64_t n_sites;
+  const thm_pile_site* sites;  /* [n_sites] ascending by ref_id, pos */
+  uint64_t n_events;           /* rows of the event table inside the range (a window: inside the window) */
+  thm_pile_totals totals;      /* of the object so far */
+  float fetch_ms;              /* device events: the kernels, scans and the copy */
+} thm_pile_view;
+
+/* A thm_pileup belongs to one aligner, like a thm_coverage: it works on that aligner's device and stream and must be
+ * freed before it.  It holds one difference array in thm_coverage's layout -- 4 bytes over every base of every @SQ
+ * contig, one more entry behind each contig -- two tables of 8 bytes per contig, and the sorted event table of 12 bytes
+ * per row.  max_bytes (0: no cap but the device's memory) bounds the arrays plus the table; the scratch of adds and
+ * fetches is not counted against it (held_bytes reports everything).  THM_ERR_OOM: the arrays alone exceed max_bytes, or
+ * the allocation fails; the message names the bytes needed and the cap, and nothing is allocated before the cap is
+ * checked.  THM_ERR_INVALID_ARG: unknown bits in `flags`; with thm_batch_fetch_bam's message, an index without names. */
+int32_t thm_pileup_create(thm_aligner* a, uint32_t flags, uint64_t max_bytes, thm_pileup** out);
+void thm_pileup_free(thm_pileup* p);
+/* Stands where thm_batch_fetch stands after thm_batch_run, fails as thm_coverage_add fails, runs the CIGAR passes itself
+ * (THM_T_CIGAR is put back) and disturbs no view, counter or timing.  The device validates every alignment in a pass of
+ * its own before anything is touched -- its ref has a refID, cigar_off + n_cigar lies inside the pool, the walk ends
+ * inside the contig, M + I + S is the read's length -- then extracts the events, sorts and reduces them by (position,
+ * kind) and merges them into the table; the deposit into the difference array and the swap to the merged table come
+ * last, so a call that fails has added nothing.  THM_ERR_OOM: the arrays plus the merged table would exceed max_bytes;
+ * the message names the bytes needed and the cap.  Batches in any cut and order give the same rows; adding a run twice
+ * doubles every count. */
+int32_t thm_pileup_add(thm_pileup* p, thm_pile_info* info);
+/* The same kernels over a caller-supplied view and the bytes of its reads (read r is bases[base_off[r], base_off[r + 1])),
+ * uploaded by the call.  The host checks first what thm_coverage_add_view checks, that base_off starts at 0 and ascends,
+ * and that M + I + S of every alignment with words is its read's length: THM_ERR_INVALID_ARG with a message naming the
+ * alignment (or the read), as for a view the device's pass refuses, and nothing is added. */
+int32_t thm_pileup_add_view(thm_pileup* p, const thm_cigar_view* v, const uint8_t* bases, const uint64_t* base_off,
+                            thm_pile_info* info);
+/* One row per position of the @SQ entries [first_ref, first_ref + n_refs) with alt >= min_alt, built on the device: a
+ * snapshot at any time.  The rows arrive in a pinned buffer of the object's own, valid until the next fetch, window,
+ * reset or free.  THM_ERR_INVALID_ARG: min_alt == 0, or a range outside the @SQ entries. */
+int32_t thm_pileup_fetch(thm_pileup* p, uint32_t first_ref, uint32_t n_refs, uint32_t min_alt, thm_pile_view* out);
+/* One row for every position of [start, start + n) of one contig, those without events or depth included: what a
+ * genotyper of known sites asks for; valid as the fetch's rows are.  THM_ERR_INVALID_ARG: no such refID, n over 1 << 20,
+ * a window that leaves the contig. */
+int32_t thm_pileup_window(thm_pileup* p, uint32_t ref_id, uint64_t start, uint64_t n, thm_pile_view* out);
+/* empties the difference array, the table and the totals */
+int32_t thm_pileup_reset(thm_pileup* p);
+
 /* ------------------------------------------------- FASTQ blocks parsed on the device */
 
 typedef struct thm_fastq_upload_info {
@@ -659,7 +757,15 @@ typedef struct thm_run_stats {
  * half open, contigs in @SQ order, no line of depth 0, no header.  With several aligners their run lists are merged on
  * the host (depths summed, abutting stretches of equal depth fused), so the files do not depend on how the reads were
  * dealt.  A failure to write one is THM_ERR_IO with the path; to standard output the knob is refused with
- * THM_ERR_INVALID_ARG.  thm_run_stats is unchanged. */
+ * THM_ERR_INVALID_ARG.  thm_run_stats is unchanged.
+ * THM_PILEUP=1 or 2, in every format and mode, beside THM_QUANT / THM_COVERAGE or alone: the aligner keeps a thm_pileup and
+ * every batch is added to it after its run (thm_pileup_add); the output file is the unset run's byte for byte.
+ * THM_PILEUP=1: the unique alignments; =2: THM_PILE_MULTI; any other value but 0, or a THM_PILEUP_MIN_ALT that is no number of
+ * 1 or more, is refused with THM_ERR_INVALID_ARG.  At the end the sites with alt >= THM_PILEUP_MIN_ALT (default
+ * 2, at least 1) are fetched and written as <output_path>.pileup.tsv: the header line "#contig pos ref depth A C G T N
+ * del ins", then one line per site, tab-separated, pos 1-based, contigs in @SQ order.  A failure to write it is
+ * THM_ERR_IO with the path; to standard output, and with more than one aligner (merging needs the depth of one device at
+ * the sites of another, which is not done), the knob is refused with THM_ERR_INVALID_ARG. */
 int32_t thm_align_files(thm_aligner* a, const char* const* fastq_paths, uint32_t n_paths, const char* output_path,
                         int32_t format, uint64_t batch_reads, uint32_t n_threads, thm_run_stats* stats);
 /* The same over several aligners -- one per GPU of the node, all over one index (the shape of ThermiteAligner: Clone +

@@ -242,6 +242,39 @@ class CovDepthView(C.Structure):
     _fields_ = [("n", C.c_uint64), ("depth", C.c_void_p), ("depth_ms", C.c_float)]
 
 
+PILE_MULTI = 1
+PILE_CHUNK = 8                # pile::CHUNK of thermite_amd/csrc/pileup_device.h: the SEQ bytes a lane compares at a time ...
+PILE_GROUP = 16               # ... and pile::GROUP, the lanes that walk one alignment
+PILE_MAX_WINDOW = 1 << 20
+PILE_SITE_DT = np.dtype([("ref_id", "<u4"), ("ref_base", "u1"), ("pad_", "u1", (3,)), ("pos", "<u8"), ("depth", "<u4"), ("cnt", "<u4", (5,)),
+                         ("del", "<u4"), ("ins", "<u4")])
+assert PILE_SITE_DT.itemsize == 48
+PILE_TOTAL_NAMES = ["n_reads", "n_failed_reads", "n_alns", "n_skipped_multi", "n_long_run_alns", "n_used_alns", "n_blocks", "n_m_bases",
+                    "n_mismatches", "n_del_bases", "n_ins", "n_ins_bases"]
+
+
+class PileTotals(C.Structure):
+    """thm_pile_totals (include/thermite_io.h)"""
+
+    _fields_ = [(k, C.c_uint64) for k in PILE_TOTAL_NAMES]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k in PILE_TOTAL_NAMES}
+
+
+class PileInfo(C.Structure):
+    """thm_pile_info (include/thermite_io.h)"""
+
+    _fields_ = [("batch", PileTotals), ("n_events", C.c_uint64), ("held_bytes", C.c_uint64), ("add_ms", C.c_float)]
+
+
+class PileView(C.Structure):
+    """thm_pile_view (include/thermite_io.h)"""
+
+    _fields_ = [("first_ref", C.c_uint32), ("n_refs", C.c_uint32), ("min_alt", C.c_uint32), ("pad_", C.c_uint32), ("n_sites", C.c_uint64),
+                ("sites", C.c_void_p), ("n_events", C.c_uint64), ("totals", PileTotals), ("fetch_ms", C.c_float)]
+
+
 class FastqUploadInfo(C.Structure):
     """thm_fastq_upload_info (include/thermite_io.h)"""
 
@@ -317,6 +350,7 @@ IO_ABI_SYMBOLS = [
     "thm_quant_create", "thm_quant_free", "thm_quant_add", "thm_quant_add_view", "thm_quant_fetch", "thm_quant_reset",
     "thm_coverage_create", "thm_coverage_free", "thm_coverage_add", "thm_coverage_add_view", "thm_coverage_fetch", "thm_coverage_depth",
     "thm_coverage_reset",
+    "thm_pileup_create", "thm_pileup_free", "thm_pileup_add", "thm_pileup_add_view", "thm_pileup_fetch", "thm_pileup_window", "thm_pileup_reset",
 ]
 ERR_IO, ERR_FORMAT = -8, -9
 FMT_PAF, FMT_SAM, FMT_BAM = 0, 1, 2
@@ -526,6 +560,20 @@ def lib():
     L.thm_coverage_depth.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, vp]
     L.thm_coverage_reset.restype = i32
     L.thm_coverage_reset.argtypes = [vp]
+    L.thm_pileup_create.restype = i32
+    L.thm_pileup_create.argtypes = [vp, C.c_uint32, C.c_uint64, vp]
+    L.thm_pileup_free.restype = None
+    L.thm_pileup_free.argtypes = [vp]
+    L.thm_pileup_add.restype = i32
+    L.thm_pileup_add.argtypes = [vp, vp]
+    L.thm_pileup_add_view.restype = i32
+    L.thm_pileup_add_view.argtypes = [vp, vp, vp, vp, vp]
+    L.thm_pileup_fetch.restype = i32
+    L.thm_pileup_fetch.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]
+    L.thm_pileup_window.restype = i32
+    L.thm_pileup_window.argtypes = [vp, C.c_uint32, C.c_uint64, C.c_uint64, vp]
+    L.thm_pileup_reset.restype = i32
+    L.thm_pileup_reset.argtypes = [vp]
     L.thm_debug_bam_sorter_add_records.restype = i32
     L.thm_debug_bam_sorter_add_records.argtypes = [vp, vp, u64]
     L.thm_debug_bam_sorter_gather.restype = i32
@@ -1098,6 +1146,83 @@ class Coverage:
     def close(self):
         if getattr(self, "h", None):
             lib().thm_coverage_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+
+class PileupResult:
+    """thm_pile_view copied out: the sites (PILE_SITE_DT, ascending by ref_id, pos), n_events and the object's totals as a dict"""
+
+    def __init__(self, view):
+        self.first_ref, self.n_refs, self.min_alt = int(view.first_ref), int(view.n_refs), int(view.min_alt)
+        self.sites = _copy(view.sites, view.n_sites, PILE_SITE_DT)
+        self.n_events = int(view.n_events)
+        self.totals = view.totals.as_dict()
+        self.fetch_ms = view.fetch_ms
+
+
+class Pileup:
+    """thm_pileup: per-base allele counts of a run, accumulated on the aligner's device batch by batch.  Close it before
+    its aligner."""
+
+    def __init__(self, aligner, flags=0, max_bytes=0):
+        self.aligner = aligner
+        self.flags = flags
+        h = C.c_void_p()
+        rc = lib().thm_pileup_create(aligner.h, flags, max_bytes, C.byref(h))
+        if rc != 0:
+            raise ThermiteError(rc, (lib().thm_last_error(aligner.h) or b"").decode())
+        self.h = h
+
+    @staticmethod
+    def _info(info):
+        out = info.batch.as_dict()
+        out.update(n_events=int(info.n_events), held_bytes=int(info.held_bytes), add_ms=info.add_ms)
+        return out
+
+    def add(self):
+        """thm_pileup_add, after Aligner.run -> the batch's totals, n_events, held_bytes and add_ms as a dict"""
+        info = PileInfo()
+        self.aligner._chk(lib().thm_pileup_add(self.h, C.byref(info)))
+        return self._info(info)
+
+    def add_view(self, offsets, alns, digests, cigar, bases, base_off, status=None):
+        """thm_pileup_add_view: the same kernels over caller-made arrays (ALN_DT, DIGEST_DT, CIGAR words) and the reads' bytes"""
+        off = np.ascontiguousarray(offsets, dtype="<u8")
+        al = np.ascontiguousarray(alns, dtype=ALN_DT)
+        dg = np.ascontiguousarray(digests, dtype=DIGEST_DT)
+        cg = np.ascontiguousarray(cigar, dtype="<u4")
+        bs = np.ascontiguousarray(bases, dtype=np.uint8)
+        bo = np.ascontiguousarray(base_off, dtype="<u8")
+        st = np.ascontiguousarray(status, dtype="<i4") if status is not None else None
+        n_reads = max(len(off) - 1, 0)
+        v = CigarView(n_reads, len(al), len(cg), _ptr(off) if len(off) else None, _ptr(al) if len(al) else None,
+                      _ptr(dg) if len(dg) else None, _ptr(cg) if len(cg) else None,
+                      int((st != 0).sum()) if st is not None else 0, _ptr(st) if st is not None and len(st) else None)
+        info = PileInfo()
+        self.aligner._chk(lib().thm_pileup_add_view(self.h, C.byref(v), _ptr(bs) if len(bs) else None, _ptr(bo) if len(bo) else None, C.byref(info)))
+        return self._info(info)
+
+    def fetch(self, first_ref, n_refs, min_alt=1):
+        """thm_pileup_fetch: the sites of the @SQ entries [first_ref, first_ref + n_refs) with min_alt events or more"""
+        v = PileView()
+        self.aligner._chk(lib().thm_pileup_fetch(self.h, first_ref, n_refs, min_alt, C.byref(v)))
+        return PileupResult(v)
+
+    def window(self, ref_id, start, n):
+        """thm_pileup_window: a row for every position of [start, start + n) of one contig"""
+        v = PileView()
+        self.aligner._chk(lib().thm_pileup_window(self.h, ref_id, start, n, C.byref(v)))
+        return PileupResult(v)
+
+    def reset(self):
+        self.aligner._chk(lib().thm_pileup_reset(self.h))
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().thm_pileup_free(self.h)
             self.h = None
 
     def __del__(self):

@@ -569,6 +569,10 @@ struct Modes {
                               // <output_path>.genes.tsv / .junctions.tsv are written at the end
   bool coverage = false;      // THM_COVERAGE=1..3, any format: every batch is added to its aligner's thm_coverage behind its fetch, and
   uint32_t cov_flags = 0;     // <output_path>.cov.<track>.bedgraph are written at the end; =2: THM_COV_STRANDED, =3: ... | THM_COV_MULTI
+  bool pileup = false;        // THM_PILEUP=1|2, any format, one aligner: every batch is added to a thm_pileup behind its fetch, and
+  uint32_t pile_flags = 0;    // <output_path>.pileup.tsv is written at the end; =2: THM_PILE_MULTI
+  uint32_t pile_min_alt = 2;  // THM_PILEUP_MIN_ALT: the events a site needs for a line (at least 1)
+  bool pile_bad = false;      // THM_PILEUP is set to something else, or THM_PILEUP_MIN_ALT is no number of 1 or more: the run is refused
   static Modes read(int32_t format) {
     auto is = [](const char* name, const char* v) {
       const char* e = getenv(name);
@@ -586,6 +590,17 @@ struct Modes {
     m.quant = is("THM_QUANT", "1");
     m.coverage = is("THM_COVERAGE", "1") || is("THM_COVERAGE", "2") || is("THM_COVERAGE", "3");
     m.cov_flags = is("THM_COVERAGE", "2") ? THM_COV_STRANDED : is("THM_COVERAGE", "3") ? (THM_COV_STRANDED | THM_COV_MULTI) : 0u;
+    m.pileup = is("THM_PILEUP", "1") || is("THM_PILEUP", "2");
+    m.pile_flags = is("THM_PILEUP", "2") ? THM_PILE_MULTI : 0u;
+    if (const char* e = getenv("THM_PILEUP")) m.pile_bad = *e && strcmp(e, "0") && !m.pileup;
+    if (const char* e = getenv("THM_PILEUP_MIN_ALT")) {
+      char* end = nullptr;
+      const long v = strtol(e, &end, 10);
+      if (end == e || *end || v < 1 || v > 0x7FFFFFFFl)
+        m.pile_bad = true;
+      else
+        m.pile_min_alt = (uint32_t)v;
+    }
     return m;
   }
 };
@@ -706,6 +721,7 @@ struct Run {
   thm_bam_sorter* sorter;
   thm_quant* const* quants = nullptr;  // THM_QUANT=1: one per aligner
   thm_coverage* const* coverages = nullptr;  // THM_COVERAGE: one per aligner
+  thm_pileup* pileup = nullptr;              // THM_PILEUP: the one aligner's
 
   Shared sh;
   thm_run_stats st;
@@ -1130,6 +1146,10 @@ void Run::gpu(uint32_t gi) {
         thm_cov_info ci;
         grc = sh.step([&] { return (int)thm_coverage_add(coverages[gi], &ci); });
       }
+      if (grc == THM_OK && pileup) {
+        thm_pile_info pi;
+        grc = sh.step([&] { return (int)thm_pileup_add(pileup, &pi); });
+      }
       if (grc != THM_OK) {
         sh.set(grc, thm_last_error(a));
       } else {
@@ -1430,6 +1450,33 @@ int write_coverage_tracks(const thm_index* ix, thm_aligner* const* aligners, thm
   return THM_OK;
 }
 
+// THM_PILEUP: the sites of all contigs with min_alt events or more as <output_path>.pileup.tsv
+int write_pileup_sites(const thm_index* ix, thm_aligner* a, thm_pileup* pileup, uint32_t min_alt, const std::string& output_path, std::string& err) {
+  std::vector<std::pair<std::string, uint64_t>> sq;
+  (void)thm::sq_of_name(ix, &sq);
+  thm_pile_view v;
+  const int rc = thm_pileup_fetch(pileup, 0, (uint32_t)sq.size(), min_alt, &v);
+  if (rc != THM_OK) {
+    err = thm_last_error(a);
+    return rc;
+  }
+  std::string text = "#contig\tpos\tref\tdepth\tA\tC\tG\tT\tN\tdel\tins\n";
+  for (uint64_t i = 0; i < v.n_sites; i++) {
+    const thm_pile_site& s = v.sites[i];
+    text += sq[s.ref_id].first + "\t" + std::to_string(s.pos + 1) + "\t" + (char)s.ref_base + "\t" + std::to_string(s.depth);
+    for (int k = 0; k < 5; k++) text += "\t" + std::to_string(s.cnt[k]);
+    text += "\t" + std::to_string(s.del) + "\t" + std::to_string(s.ins) + "\n";
+  }
+  const std::string path = output_path + ".pileup.tsv";
+  Output o;
+  const bool ok = o.open(path.c_str()) && o.write_all(text.data(), text.size(), 0);
+  if (!o.close() || !ok) {
+    err = "cannot write " + path;
+    return THM_ERR_IO;
+  }
+  return THM_OK;
+}
+
 }  // namespace
 
 extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t n_aligners, const char* const* fastq_paths,
@@ -1456,6 +1503,18 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
   }
   if (m.coverage && !strcmp(output_path, "-")) {
     thm::set_global_error("thm_align_files_multi: THM_COVERAGE needs an output file (the tracks are written beside it)");
+    return THM_ERR_INVALID_ARG;
+  }
+  if (m.pile_bad) {
+    thm::set_global_error("thm_align_files_multi: THM_PILEUP must be 1 or 2 (or 0, or unset) and THM_PILEUP_MIN_ALT a number of 1 or more");
+    return THM_ERR_INVALID_ARG;
+  }
+  if (m.pileup && !strcmp(output_path, "-")) {
+    thm::set_global_error("thm_align_files_multi: THM_PILEUP needs an output file (the sites are written beside it)");
+    return THM_ERR_INVALID_ARG;
+  }
+  if (m.pileup && n_aligners > 1) {
+    thm::set_global_error("thm_align_files_multi: THM_PILEUP takes one aligner (merging across devices is not done)");
     return THM_ERR_INVALID_ARG;
   }
   const thm_index* ix = thm_aligner_index(aligners[0]);
@@ -1505,6 +1564,16 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
       thm_writer_free(w);
       return rc;
     }
+  thm_pileup* pileup = nullptr;
+  if (m.pileup && (rc = thm_pileup_create(aligners[0], m.pile_flags, 0, &pileup)) != THM_OK) {
+    thm::set_global_error(thm_last_error(aligners[0]));
+    for (thm_coverage* c : coverages) thm_coverage_free(c);
+    for (thm_quant* q : quants) thm_quant_free(q);
+    thm_bam_sorter_free(sorter);
+    (void)out.close();
+    thm_writer_free(w);
+    return rc;
+  }
   const auto t_start = Clock::now();
   thm_writer* w2 = nullptr;
   const bool have_w2 = thm_writer_create(ix, format, n_threads, &w2) == THM_OK;
@@ -1514,6 +1583,7 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
   run.index_path = std::string(output_path) + ".bai";
   if (m.quant) run.quants = quants.data();
   if (m.coverage) run.coverages = coverages.data();
+  run.pileup = pileup;
   // ---- the stages: the cutter, the parsers, a thread per aligner; this thread formats
   std::thread cutter(&Run::cut, &run);
   std::vector<std::thread> parsers, gpus;
@@ -1537,6 +1607,12 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
     const int crc = run.sh.step([&] { return write_coverage_tracks(ix, aligners, coverages.data(), n_aligners, m.cov_flags, output_path, err); });
     if (crc != THM_OK) run.sh.set(crc, err);
   }
+  if (m.pileup && run.sh.rc == THM_OK) {
+    std::string err;
+    const int prc = run.sh.step([&] { return write_pileup_sites(ix, aligners[0], pileup, m.pile_min_alt, output_path, err); });
+    if (prc != THM_OK) run.sh.set(prc, err);
+  }
+  thm_pileup_free(pileup);
   for (thm_coverage* c : coverages) thm_coverage_free(c);
   for (thm_quant* q : quants) thm_quant_free(q);
   thm_bam_sorter_free(sorter);

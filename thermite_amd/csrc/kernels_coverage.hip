@@ -18,34 +18,13 @@
 #include <hip/hip_runtime.h>
 
 #include "coverage_device.h"
+#include "coverage_tile.h"
 #include "launch_io.h"
 
 namespace thm {
 namespace dev {
 
 using ull = unsigned long long;
-constexpr uint32_t COV_LDS = cov::TILE + cov::TILE / cov::PER_THREAD;  // a word of padding per thread: stride 17, no bank conflict
-static_assert(cov::TILE_THREADS == 256 && cov::PER_THREAD == 16, "the kernels are written for 256 threads of 16 entries");
-
-__device__ inline uint64_t cov_wave_sum_u64(uint64_t v) {
-  for (int d = 32; d >= 1; d >>= 1) {
-    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, d), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), d);
-    v += (uint64_t)hi << 32 | lo;
-  }
-  return v;
-}
-__device__ inline uint32_t cov_wave_sum_u32(uint32_t v) {
-  for (int d = 32; d >= 1; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d);
-  return v;
-}
-__device__ inline uint32_t cov_wave_max_u32(uint32_t v) {
-  for (int d = 32; d >= 1; d >>= 1) {
-    const uint32_t o = (uint32_t)__shfl_xor((int)v, d);
-    v = o > v ? o : v;
-  }
-  return v;
-}
-
 __global__ __launch_bounds__(256) void cov_count_kernel(const CovCountParams p) {
   __shared__ ull sh_tot[cov::N_TOTALS];
   const CovBatch& b = p.b;
@@ -137,39 +116,6 @@ __global__ __launch_bounds__(256) void cov_tiles_kernel(const CovTileParams p) {
     p.tile_sum[blockIdx.x] = (uint32_t)(sh[0] + sh[1] + sh[2] + sh[3]);
     p.tile_cnt[blockIdx.x] = sh[4] + sh[5] + sh[6] + sh[7];
   }
-}
-
-// Tile `tile` of diff[0, n) into LDS, the thread's own PER_THREAD consecutive entries into v[], and the exclusive scans
-// over the workgroup of their sum and of the number of non-zero ones.  The tile stays in `lds` (entry i at i + i / 16).
-__device__ inline void cov_tile_scan(const uint32_t* diff, uint64_t n, uint64_t tile, uint32_t* lds, uint32_t* sh, uint32_t (&v)[cov::PER_THREAD],
-                                     uint32_t* sum_before, uint32_t* cnt_before) {
-  const uint64_t t0 = tile * cov::TILE;
-  for (uint32_t k = 0; k < cov::PER_THREAD; k++) {
-    const uint32_t i = k * 256u + threadIdx.x;
-    const uint64_t x = t0 + i;
-    lds[i + (i >> 4)] = x < n ? diff[x] : 0u;
-  }
-  __syncthreads();
-  uint32_t sum = 0, cnt = 0;
-  for (uint32_t j = 0; j < cov::PER_THREAD; j++) {
-    v[j] = lds[threadIdx.x * (cov::PER_THREAD + 1) + j];
-    sum += v[j];
-    cnt += v[j] ? 1u : 0u;
-  }
-  // inclusive over the wavefront, then the wavefronts in front
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  uint32_t isum = sum, icnt = cnt;
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t s2 = (uint32_t)__shfl_up((int)isum, d), c2 = (uint32_t)__shfl_up((int)icnt, d);
-    if (lane >= (uint32_t)d) isum += s2, icnt += c2;
-  }
-  if (lane == 63) sh[wave] = isum, sh[4 + wave] = icnt;
-  __syncthreads();
-  uint32_t ws = 0, wc = 0;
-  for (uint32_t w = 0; w < 4; w++)
-    if (w < wave) ws += sh[w], wc += sh[4 + w];
-  *sum_before = ws + isum - sum;
-  *cnt_before = wc + icnt - cnt;
 }
 
 __global__ __launch_bounds__(256) void cov_points_kernel(const CovTileParams p) {

@@ -231,6 +231,103 @@ hipError_t launch_cov_points(const CovTileParams& p, hipStream_t s);
 hipError_t launch_cov_runs(const CovRunParams& p, hipStream_t s);
 hipError_t launch_cov_window(const CovWindowParams& p, hipStream_t s);
 
+// ---- per-base allele counts of a run (kernels_pileup.hip, pileup_device.h; host side pileup.hip) ----
+// add:    count (a group of lanes per alignment: its read, whether it is used, the checks, its blocks, bases and events;
+//         per read: the read totals) -> scan of the event counts ... the host reads the totals and the first bad
+//         alignment ... extract (the group again: a key per event) -> sort of the keys -> heads, scan, runs (by key: key
+//         and count) -> lookup of the reduced rows in the running table, scan of the new ones ... the host checks the cap
+//         ... update (found rows in place, new rows behind the table's) -> sort of table + new rows -> deposit (two
+//         integer adds per block into the difference array).
+// fetch:  bounds (the range's rows) -> keep (the rows that begin a position with enough events) -> scan; coverage's tiles
+//         and their scan -> sites (per tile with rows: the depths through LDS, a row per kept position).
+// window: bounds, tiles and their scan -> window (per tile of the window: the depths, a row per position).
+struct PileBatch {
+  uint64_t n_reads, n_alns, n_words;
+  const uint64_t* aln_off;        // [n_reads + 1]
+  const thm_aln* alns;            // [n_alns]
+  const thm_aln_digest* digests;  // [n_alns]
+  const uint32_t* words;          // [n_words]
+  const int32_t* status;          // [n_reads]; null: no read failed
+  const uint8_t* bases;           // the raw reads: read r is bases[base_off[r], base_off[r + 1])
+  const uint64_t* base_off;       // [n_reads + 1]
+  uint32_t n_refs, n_sq, flags;   // flags: THM_PILE_*
+  const int32_t* ref_sq;          // [n_refs] BAM refID, -1: none
+  const uint64_t* base;           // [n_sq + 1] first entry of every contig in the layout (coverage_device.h)
+  const uint64_t* tstart;         // [n_sq] first byte of every contig's forward copy in the text
+  const uint8_t* text;
+};
+struct PileCountParams {
+  PileBatch b;
+  uint64_t* ev_cnt;            // [n_alns + 1] events of every alignment, for the scan
+  uint64_t* aln_read;          // [n_alns] its read
+  uint8_t* used;               // [n_alns] 1: it is walked and deposited
+  unsigned long long* totals;  // [pile::N_TOTALS] zeroed by the caller
+  unsigned long long* bad;     // the first alignment that fails a check (atomic minimum; ~0: none)
+};
+struct PileExtractParams {
+  PileBatch b;
+  const uint64_t* ev_off;      // [n_alns + 1] scan of ev_cnt
+  const uint64_t* aln_read;
+  const uint8_t* used;
+  uint64_t* keys;              // [ev_off[n_alns]]
+  uint32_t* diff;              // deposit: the difference array
+};
+struct PileReduceParams {
+  const uint64_t* skey;        // [n] sorted keys
+  uint64_t n;
+  uint64_t* flag;              // [n + 1] heads: 1 where a key begins
+  const uint64_t* first;       // [n + 1] its scan
+  uint64_t* head_at;           // [n_keys + 1] runs: where every key begins in skey, and n behind them
+  uint64_t* red_key;           // [n_keys]
+  uint32_t* red_cnt;           // [n_keys]
+  uint64_t n_keys;
+};
+struct PileMergeParams {
+  const uint64_t* tab_key;     // [n_tab] the running table, sorted
+  uint64_t n_tab;
+  const uint64_t* red_key;     // [n_red] the batch's reduced rows
+  const uint32_t* red_cnt;
+  uint64_t n_red;
+  uint64_t* where;             // [n_red] row of the table with the same key, or ~0
+  uint64_t* is_new;            // [n_red + 1] for the scan
+  const uint64_t* new_at;      // [n_red + 1] its scan
+  uint64_t* dst_key;           // update: found rows add to dst_cnt[where], new rows go to row n_tab + new_at
+  uint32_t* dst_cnt;
+};
+struct PileFetchParams {
+  const uint64_t* keys;        // the table
+  const uint32_t* cnts;
+  uint64_t n_tab;
+  uint64_t e0, e1;             // the entries of the range (a window: of the window)
+  uint64_t* bounds;            // [2] bounds: the rows of the range, r0 and r1
+  uint64_t r0, r1;             // ... read back
+  uint32_t min_alt;
+  uint64_t* keep;              // [r1 - r0 + 1] keep: 1 where a row begins a position with alt >= min_alt
+  const uint64_t* site_at;     // [r1 - r0 + 1] its scan
+  uint64_t n_sites;
+  const uint32_t* diff;        // sites: the first entry of the range; window: of the contig
+  uint64_t n;                  // entries the tiles count from there
+  uint64_t g0;                 // that entry in the layout
+  const uint64_t* carry;       // [n_tiles + 1] scan of the tile sums
+  uint64_t start;              // window: its first position in the contig
+  const uint64_t* base;
+  const uint64_t* tstart;
+  const uint8_t* text;
+  uint32_t n_sq;
+  thm_pile_site* sites;        // [n_sites]
+};
+hipError_t launch_pile_count(const PileCountParams& p, int n_cu, hipStream_t s);
+hipError_t launch_pile_extract(const PileExtractParams& p, hipStream_t s);
+hipError_t launch_pile_deposit(const PileExtractParams& p, hipStream_t s);
+hipError_t launch_pile_heads(const PileReduceParams& p, hipStream_t s);
+hipError_t launch_pile_runs(const PileReduceParams& p, hipStream_t s);
+hipError_t launch_pile_lookup(const PileMergeParams& p, hipStream_t s);
+hipError_t launch_pile_update(const PileMergeParams& p, hipStream_t s);
+hipError_t launch_pile_bounds(const PileFetchParams& p, hipStream_t s);
+hipError_t launch_pile_keep(const PileFetchParams& p, hipStream_t s);
+hipError_t launch_pile_sites(const PileFetchParams& p, hipStream_t s);
+hipError_t launch_pile_window(const PileFetchParams& p, hipStream_t s);
+
 // ---- BAI index of the sorted stream (kernels_bai.hip, bai_device.h; host side bai.hip) ----
 // fields (per sorted record: key = refID << 16 | bin, beg, end; per reference the mapped count and n_intv) -> run heads,
 // scan, runs (the chunks before merging, raw offsets) -> sort of (key, ordinal) -> chunk and bin heads, two scans, chunks

@@ -23,16 +23,24 @@ bases, through thm_quant by hand: add_ms and fetch_ms beside THM_T_CIGAR and THM
 of 91 and of 150 bases, through thm_coverage by hand: add_ms of five adds and fetch_ms of every track beside THM_T_CIGAR
 and thm_quant_add's add_ms of the same run; then add_ms of 500 000 alignments of 50M at one position beside the same
 number spread over the contig (the contention of the deposit's atomics).
+--pileup[=ROUNDS]: as --quant with THM_PILEUP=1 (the .pileup.tsv's size is reported); then one batch of 500 000 reads, of 91
+and of 150 bases, through thm_pileup by hand: add_ms of five adds (the first builds the table, the others find every row in
+it), fetch_ms at min_alt 1 and 2, the ms of a window of 1 << 20 positions, n_events and the held bytes, beside
+thm_coverage_add's and thm_quant_add's add_ms of the same run -- the two adds this one is made of.
 --sha[=PART]: with any of the modes above, "sha256 <hash> <file> <bytes>" for every output file before it is removed (two
 builds of the library -- THM_LIB selects one -- are compared by these lines); with PART also, after every run that wrote a
 file whose name holds PART, "each <file> raw <hash> inflated <hash> size <bytes> batches <n>": does an output repeat from
 run to run, compressed and inflated?"""
 import hashlib, os, sys, time
-BAM_RUNS = FQ_ROUNDS = BGZF_ROUNDS = GZIP_ROUNDS = SORT_ROUNDS = QUANT_ROUNDS = COV_ROUNDS = 0
+BAM_RUNS = FQ_ROUNDS = BGZF_ROUNDS = GZIP_ROUNDS = SORT_ROUNDS = QUANT_ROUNDS = COV_ROUNDS = PILE_ROUNDS = 0
 SHA, SHA_EACH = False, None
 for arg in list(sys.argv[1:]):
     if arg.startswith("--sha"):
         SHA, SHA_EACH = True, (arg.split("=")[1] if "=" in arg else None)
+        sys.argv.remove(arg)
+        continue
+    if arg.startswith("--pileup"):
+        PILE_ROUNDS = int(arg.split("=")[1]) if "=" in arg else 3
         sys.argv.remove(arg)
         continue
     if arg.startswith("--coverage"):
@@ -116,6 +124,53 @@ with open(big, "wb") as f:
         f.write(one)
     del one
 print("plain input: %d reads, %.1f MB" % (n * REP, os.path.getsize(big) / 1e6), flush=True)
+if PILE_ROUNDS:
+    os.environ["THM_BAM_DEVICE"] = "1"
+    out = "/tmp/thm_e2e_out.bam"
+    st = capi.align_files(a, [big], out, capi.FMT_BAM, batch_reads=250000, n_threads=threads)   # warm-up: buffers grow
+    for k in range(PILE_ROUNDS):
+        for tag, on in (("THM_BAM_DEVICE=1             ", False), ("THM_BAM_DEVICE=1 THM_PILEUP=1", True)):
+            os.environ.pop("THM_PILEUP", None)
+            if on:
+                os.environ["THM_PILEUP"] = "1"
+            st = capi.align_files(a, [big], out, capi.FMT_BAM, batch_reads=250000, n_threads=threads)
+            tsv = ""
+            if on:
+                tsv = ", pileup.tsv %d bytes" % os.path.getsize(out + ".pileup.tsv")
+                os.remove(out + ".pileup.tsv")
+            print("bam %s round %d: %.2f Mreads/s wall %.3fs | parse %.2fs gpu %.2fs format %.2fs write %.2fs | %d batches, %.0f MB out%s" % (
+                tag, k, st["n_reads"] / st["wall_s"] / 1e6, st["wall_s"], st["parse_s"], st["gpu_s"], st["format_s"], st["write_s"],
+                st["n_batches"], st["n_output_bytes"] / 1e6, tsv), flush=True)
+    os.environ.pop("THM_PILEUP", None)
+    # one batch of 500 000 reads by hand
+    for L in (91, 150):
+        b, o, _ = synth.simulate_reads(t, 500000, L, sub_rate=0.01, indel_rate=0.001, stream=7)
+        p = capi.Pileup(a, 0)
+        c = capi.Coverage(a, 0)
+        q = capi.Quant(a)
+        a.upload(b, o)
+        a.run()
+        a.fetch_cigars(copy=False)
+        tm = a.timings()
+        adds = [p.add() for _ in range(5)]
+        c_adds = [c.add() for _ in range(5)]
+        q_adds = [q.add() for _ in range(5)]
+        fetches = [[p.fetch(0, 1, m) for m in (1, 2)] for _ in range(3)]
+        wins = [p.window(0, ref_len // 2, 1 << 20) for _ in range(3)]
+        print("pileup %d bp: 500000 reads, %d alns, %d used, %d M bases, %d mismatches, %d del bases, %d ins | n_events %d, held %.1f MB | add_ms %s | "
+              "fetch_ms min_alt 1, 2: %s | sites %d, %d | window_ms of 2^20 positions %s | thm_coverage_add add_ms %s | thm_quant_add add_ms %s | "
+              "THM_T_CIGAR %.3f THM_T_COMPACT %.3f THM_T_TOTAL %.3f" % (
+                  L, adds[0]["n_alns"], adds[0]["n_used_alns"], adds[0]["n_m_bases"], adds[0]["n_mismatches"], adds[0]["n_del_bases"], adds[0]["n_ins"],
+                  adds[-1]["n_events"], adds[-1]["held_bytes"] / 1e6, " ".join("%.3f" % x["add_ms"] for x in adds),
+                  " | ".join(" ".join("%.3f" % x.fetch_ms for x in f) for f in fetches), len(fetches[0][0].sites), len(fetches[0][1].sites),
+                  " ".join("%.3f" % x.fetch_ms for x in wins), " ".join("%.3f" % x["add_ms"] for x in c_adds),
+                  " ".join("%.3f" % x["add_ms"] for x in q_adds), tm["cigar"], tm["compact"], tm["total"]), flush=True)
+        q.close()
+        c.close()
+        p.close()
+    a.close()
+    drop(out)
+    sys.exit(0)
 if COV_ROUNDS:
     import glob
     os.environ["THM_BAM_DEVICE"] = "1"
