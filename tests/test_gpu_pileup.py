@@ -395,6 +395,16 @@ def test_file_driver_writes_the_sites(tmp_path):
     assert none is None
     sam = str(tmp_path / "sam_plain")
     bam_plain, _ = run("bam_plain", capi.FMT_BAM, THM_BAM_DEVICE=1)
+
+    def beside(tag, *patterns):
+        """what a run wrote beside its output: file name behind the tag -> bytes"""
+        return {f.name[len(tag):]: f.read_bytes() for pat in patterns for f in sorted(tmp_path.glob(tag + pat))}
+
+    # the tables and tracks of a run that keeps one summary only: what a run with all three on one aligner must write too
+    run("quant_alone", capi.FMT_BAM, THM_QUANT=1)
+    run("cov_alone", capi.FMT_BAM, THM_COVERAGE=1)
+    tables_alone, tracks_alone = beside("quant_alone", ".genes.tsv", ".junctions.tsv"), beside("cov_alone", ".cov.*.bedgraph")
+    assert sorted(tables_alone) == [".genes.tsv", ".junctions.tsv"] and tracks_alone and all(tracks_alone.values())
     for mode, flags in ((1, 0), (2, pc.MULTI)):
         for min_alt in (None, 1):
             # what the run's own SAM output holds, counted line by line; the expectation from the oracle says the same
@@ -404,8 +414,10 @@ def test_file_driver_writes_the_sites(tmp_path):
             got, tsv = run("pile%d_%s" % (mode, min_alt), capi.FMT_SAM, THM_PILEUP=mode, **extra)
             assert got == plain and tsv == want, (mode, min_alt)
             # a device-encoded BAM with the other tables beside: the same sites, the same file as without the knob
-            got, tsv = run("bam_pile%d_%s" % (mode, min_alt), capi.FMT_BAM, THM_BAM_DEVICE=1, THM_PILEUP=mode, THM_COVERAGE=1, THM_QUANT=1, **extra)
-            assert got == bam_plain and tsv == want and (tmp_path / ("bam_pile%d_%s.genes.tsv" % (mode, min_alt))).exists()
+            tag = "bam_pile%d_%s" % (mode, min_alt)
+            got, tsv = run(tag, capi.FMT_BAM, THM_BAM_DEVICE=1, THM_PILEUP=mode, THM_COVERAGE=1, THM_QUANT=1, **extra)
+            assert got == bam_plain and tsv == want and (tmp_path / (tag + ".genes.tsv")).exists()
+            assert beside(tag, ".genes.tsv", ".junctions.tsv") == tables_alone and beside(tag, ".cov.*.bedgraph") == tracks_alone, (mode, min_alt)
     # to standard output there is nowhere to put the table; two aligners' counts are not merged
     with _knobs(THM_PILEUP=1):
         e = _raises(lambda: capi.align_files(a, [fq], "-", capi.FMT_SAM, batch_reads=700, n_threads=4))

@@ -1018,60 +1018,82 @@ class QuantResult:
         self.fetch_ms = view.fetch_ms
 
 
-class Quant:
-    """thm_quant: gene and splice-junction count tables of a run, accumulated on the aligner's device batch by batch.
-    Close it before its aligner."""
+def _cigar_view(offsets, alns, digests, cigar, status):
+    """caller-made arrays (ALN_DT, DIGEST_DT, CIGAR words) -> the CigarView over them, and the arrays it points into:
+    they must stay alive while the view is used"""
+    off = np.ascontiguousarray(offsets, dtype="<u8")
+    al = np.ascontiguousarray(alns, dtype=ALN_DT)
+    dg = np.ascontiguousarray(digests, dtype=DIGEST_DT)
+    cg = np.ascontiguousarray(cigar, dtype="<u4")
+    st = np.ascontiguousarray(status, dtype="<i4") if status is not None else None
+    n_reads = max(len(off) - 1, 0)
+    v = CigarView(n_reads, len(al), len(cg), _ptr(off) if len(off) else None, _ptr(al) if len(al) else None,
+                  _ptr(dg) if len(dg) else None, _ptr(cg) if len(cg) else None,
+                  int((st != 0).sum()) if st is not None else 0, _ptr(st) if st is not None and len(st) else None)
+    return v, (off, al, dg, cg, st)
 
-    def __init__(self, aligner):
+
+class _RunSummary:
+    """What Quant, Coverage and Pileup share: the handle of an object that accumulates over the batches of its aligner.
+    A subclass names its C functions (_NAME: thm_<_NAME>_create, _add, _add_view, _reset, _free), its info struct (_INFO)
+    and the fields of that struct its add and add_view (through _add) return beside the batch's totals (_INFO_FIELDS)."""
+
+    _NAME = _INFO = None
+    _INFO_FIELDS = ()
+
+    def __init__(self, aligner, *create_args):
         self.aligner = aligner
         h = C.c_void_p()
-        rc = lib().thm_quant_create(aligner.h, C.byref(h))
+        rc = self._fn("create")(aligner.h, *create_args, C.byref(h))
         if rc != 0:
             raise ThermiteError(rc, (lib().thm_last_error(aligner.h) or b"").decode())
         self.h = h
 
-    @staticmethod
-    def _info(info):
+    @classmethod
+    def _fn(cls, what):
+        return getattr(lib(), "thm_%s_%s" % (cls._NAME, what))
+
+    def _add(self, what, *args):
+        info = self._INFO()
+        self.aligner._chk(self._fn(what)(self.h, *args, C.byref(info)))
         out = info.batch.as_dict()
-        out.update(n_junctions=int(info.n_junctions), held_bytes=int(info.held_bytes), add_ms=info.add_ms)
+        out.update({k: int(getattr(info, k)) for k in self._INFO_FIELDS}, held_bytes=int(info.held_bytes), add_ms=info.add_ms)
         return out
+
+    def reset(self):
+        self.aligner._chk(self._fn("reset")(self.h))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._fn("free")(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+
+class Quant(_RunSummary):
+    """thm_quant: gene and splice-junction count tables of a run, accumulated on the aligner's device batch by batch.
+    Close it before its aligner."""
+
+    _NAME, _INFO, _INFO_FIELDS = "quant", QuantInfo, ("n_junctions",)
+
+    def __init__(self, aligner):
+        super().__init__(aligner)
 
     def add(self):
         """thm_quant_add, after Aligner.run -> the batch's totals, n_junctions, held_bytes and add_ms as a dict"""
-        info = QuantInfo()
-        self.aligner._chk(lib().thm_quant_add(self.h, C.byref(info)))
-        return self._info(info)
+        return self._add("add")
 
     def add_view(self, offsets, alns, digests, cigar, status=None):
         """thm_quant_add_view: the same kernels over caller-made arrays (ALN_DT, DIGEST_DT, CIGAR words)"""
-        off = np.ascontiguousarray(offsets, dtype="<u8")
-        al = np.ascontiguousarray(alns, dtype=ALN_DT)
-        dg = np.ascontiguousarray(digests, dtype=DIGEST_DT)
-        cg = np.ascontiguousarray(cigar, dtype="<u4")
-        st = np.ascontiguousarray(status, dtype="<i4") if status is not None else None
-        n_reads = max(len(off) - 1, 0)
-        v = CigarView(n_reads, len(al), len(cg), _ptr(off) if len(off) else None, _ptr(al) if len(al) else None,
-                      _ptr(dg) if len(dg) else None, _ptr(cg) if len(cg) else None,
-                      int((st != 0).sum()) if st is not None else 0, _ptr(st) if st is not None and len(st) else None)
-        info = QuantInfo()
-        self.aligner._chk(lib().thm_quant_add_view(self.h, C.byref(v), C.byref(info)))
-        return self._info(info)
+        v, _alive = _cigar_view(offsets, alns, digests, cigar, status)
+        return self._add("add_view", C.byref(v))
 
     def fetch(self):
         v = QuantView()
         self.aligner._chk(lib().thm_quant_fetch(self.h, C.byref(v)))
         return QuantResult(v)
-
-    def reset(self):
-        self.aligner._chk(lib().thm_quant_reset(self.h))
-
-    def close(self):
-        if getattr(self, "h", None):
-            lib().thm_quant_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        self.close()
 
 
 class CoverageResult:
@@ -1086,46 +1108,25 @@ class CoverageResult:
         self.fetch_ms = view.fetch_ms
 
 
-class Coverage:
+class Coverage(_RunSummary):
     """thm_coverage: per-base coverage tracks of a run, accumulated on the aligner's device batch by batch.  Close it
     before its aligner."""
 
+    _NAME, _INFO = "coverage", CovInfo
+
     def __init__(self, aligner, flags=0, max_bytes=0):
-        self.aligner = aligner
         self.flags = flags
         self.n_tracks = (2 if flags & COV_STRANDED else 1) * (2 if flags & COV_MULTI else 1)
-        h = C.c_void_p()
-        rc = lib().thm_coverage_create(aligner.h, flags, max_bytes, C.byref(h))
-        if rc != 0:
-            raise ThermiteError(rc, (lib().thm_last_error(aligner.h) or b"").decode())
-        self.h = h
-
-    @staticmethod
-    def _info(info):
-        out = info.batch.as_dict()
-        out.update(held_bytes=int(info.held_bytes), add_ms=info.add_ms)
-        return out
+        super().__init__(aligner, flags, max_bytes)
 
     def add(self):
         """thm_coverage_add, after Aligner.run -> the batch's totals, held_bytes and add_ms as a dict"""
-        info = CovInfo()
-        self.aligner._chk(lib().thm_coverage_add(self.h, C.byref(info)))
-        return self._info(info)
+        return self._add("add")
 
     def add_view(self, offsets, alns, digests, cigar, status=None):
         """thm_coverage_add_view: the same kernels over caller-made arrays (ALN_DT, DIGEST_DT, CIGAR words)"""
-        off = np.ascontiguousarray(offsets, dtype="<u8")
-        al = np.ascontiguousarray(alns, dtype=ALN_DT)
-        dg = np.ascontiguousarray(digests, dtype=DIGEST_DT)
-        cg = np.ascontiguousarray(cigar, dtype="<u4")
-        st = np.ascontiguousarray(status, dtype="<i4") if status is not None else None
-        n_reads = max(len(off) - 1, 0)
-        v = CigarView(n_reads, len(al), len(cg), _ptr(off) if len(off) else None, _ptr(al) if len(al) else None,
-                      _ptr(dg) if len(dg) else None, _ptr(cg) if len(cg) else None,
-                      int((st != 0).sum()) if st is not None else 0, _ptr(st) if st is not None and len(st) else None)
-        info = CovInfo()
-        self.aligner._chk(lib().thm_coverage_add_view(self.h, C.byref(v), C.byref(info)))
-        return self._info(info)
+        v, _alive = _cigar_view(offsets, alns, digests, cigar, status)
+        return self._add("add_view", C.byref(v))
 
     def fetch(self, track, first_ref, n_refs):
         """thm_coverage_fetch: the runs of `track` on the @SQ entries [first_ref, first_ref + n_refs)"""
@@ -1140,17 +1141,6 @@ class Coverage:
         self.depth_ms = v.depth_ms
         return _copy(v.depth, v.n, np.dtype("<u4"))
 
-    def reset(self):
-        self.aligner._chk(lib().thm_coverage_reset(self.h))
-
-    def close(self):
-        if getattr(self, "h", None):
-            lib().thm_coverage_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        self.close()
-
 
 class PileupResult:
     """thm_pile_view copied out: the sites (PILE_SITE_DT, ascending by ref_id, pos), n_events and the object's totals as a dict"""
@@ -1163,47 +1153,26 @@ class PileupResult:
         self.fetch_ms = view.fetch_ms
 
 
-class Pileup:
+class Pileup(_RunSummary):
     """thm_pileup: per-base allele counts of a run, accumulated on the aligner's device batch by batch.  Close it before
     its aligner."""
 
-    def __init__(self, aligner, flags=0, max_bytes=0):
-        self.aligner = aligner
-        self.flags = flags
-        h = C.c_void_p()
-        rc = lib().thm_pileup_create(aligner.h, flags, max_bytes, C.byref(h))
-        if rc != 0:
-            raise ThermiteError(rc, (lib().thm_last_error(aligner.h) or b"").decode())
-        self.h = h
+    _NAME, _INFO, _INFO_FIELDS = "pileup", PileInfo, ("n_events",)
 
-    @staticmethod
-    def _info(info):
-        out = info.batch.as_dict()
-        out.update(n_events=int(info.n_events), held_bytes=int(info.held_bytes), add_ms=info.add_ms)
-        return out
+    def __init__(self, aligner, flags=0, max_bytes=0):
+        self.flags = flags
+        super().__init__(aligner, flags, max_bytes)
 
     def add(self):
         """thm_pileup_add, after Aligner.run -> the batch's totals, n_events, held_bytes and add_ms as a dict"""
-        info = PileInfo()
-        self.aligner._chk(lib().thm_pileup_add(self.h, C.byref(info)))
-        return self._info(info)
+        return self._add("add")
 
     def add_view(self, offsets, alns, digests, cigar, bases, base_off, status=None):
         """thm_pileup_add_view: the same kernels over caller-made arrays (ALN_DT, DIGEST_DT, CIGAR words) and the reads' bytes"""
-        off = np.ascontiguousarray(offsets, dtype="<u8")
-        al = np.ascontiguousarray(alns, dtype=ALN_DT)
-        dg = np.ascontiguousarray(digests, dtype=DIGEST_DT)
-        cg = np.ascontiguousarray(cigar, dtype="<u4")
+        v, _alive = _cigar_view(offsets, alns, digests, cigar, status)
         bs = np.ascontiguousarray(bases, dtype=np.uint8)
         bo = np.ascontiguousarray(base_off, dtype="<u8")
-        st = np.ascontiguousarray(status, dtype="<i4") if status is not None else None
-        n_reads = max(len(off) - 1, 0)
-        v = CigarView(n_reads, len(al), len(cg), _ptr(off) if len(off) else None, _ptr(al) if len(al) else None,
-                      _ptr(dg) if len(dg) else None, _ptr(cg) if len(cg) else None,
-                      int((st != 0).sum()) if st is not None else 0, _ptr(st) if st is not None and len(st) else None)
-        info = PileInfo()
-        self.aligner._chk(lib().thm_pileup_add_view(self.h, C.byref(v), _ptr(bs) if len(bs) else None, _ptr(bo) if len(bo) else None, C.byref(info)))
-        return self._info(info)
+        return self._add("add_view", C.byref(v), _ptr(bs) if len(bs) else None, _ptr(bo) if len(bo) else None)
 
     def fetch(self, first_ref, n_refs, min_alt=1):
         """thm_pileup_fetch: the sites of the @SQ entries [first_ref, first_ref + n_refs) with min_alt events or more"""
@@ -1216,17 +1185,6 @@ class Pileup:
         v = PileView()
         self.aligner._chk(lib().thm_pileup_window(self.h, ref_id, start, n, C.byref(v)))
         return PileupResult(v)
-
-    def reset(self):
-        self.aligner._chk(lib().thm_pileup_reset(self.h))
-
-    def close(self):
-        if getattr(self, "h", None):
-            lib().thm_pileup_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        self.close()
 
 
 def cigar_text(words):

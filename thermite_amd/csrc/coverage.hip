@@ -2,8 +2,14 @@
 // on the device over its batches from what is resident after thm_batch_run -- the compacted thm_aln records, the per-read
 // offsets, the CIGAR words and digests of the CIGAR passes, and the ref -> @SQ table of the BAM encoder.  A track is a
 // difference array over every base of every contig; only totals, finished runs of equal depth and windows of depths come
-// back to the host.  The kernels are kernels_coverage.hip, the per-item functions and the layout coverage_device.h;
-// DESIGN.md section 4.18.
+// back to the host.  The kernels are kernels_coverage.hip, the per-item functions and the layout coverage_device.h; the
+// batch, the view's upload and checks, the contig layout, the totals and the tile pass are run_summary.h's, shared with
+// quant.hip and pileup.hip.  DESIGN.md sections 4.18 and 4.20.
+//
+// Synchronisations of the stream.  add: thm_batch_sync's, one of fetch_batch_sizes, one of the CIGAR passes, one behind
+// the count pass, one behind the deposit.  add_view: one behind the upload, then the last two.  fetch: one behind the
+// tile scans (a range with entries), one behind the point scan (with change points), one at the end.  depth: one.
+// reset: one.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -12,39 +18,33 @@
 #include "coverage_device.h"
 #include "io_internal.h"
 #include "launch_io.h"
+#include "run_summary.h"
 
 using namespace thm;
 
 struct thm_coverage {
   thm_aligner* a = nullptr;
-  uint32_t flags = 0, n_tracks = 0, n_sq = 0;
-  std::vector<int32_t> h_ref_sq;  // what bam.ref_sq holds, for the checks of thm_coverage_add_view
-  std::vector<uint64_t> h_base;   // [n_sq + 1] first entry of every contig in a track
-  DArr<uint64_t> base;
-  DArr<uint32_t> diff;            // [n_tracks * h_base[n_sq]]
+  uint32_t flags = 0, n_tracks = 0;
+  SqLayout sq;          // the contigs of a track
+  DArr<uint32_t> diff;  // [n_tracks * sq.entries()]
   thm_cov_totals totals;
   // one batch's scratch
   DArr<uint8_t> track;
-  DBuf d_tot;  // the totals (unsigned long long) and behind them the `bad` word
-  // the view thm_coverage_add_view uploads
-  DArr<uint64_t> v_off;
-  DArr<thm_aln> v_alns;
-  DArr<thm_aln_digest> v_dig;
-  DArr<uint32_t> v_words;
-  DArr<int32_t> v_stat;
+  BatchTotals<cov::N_TOTALS> tot;
+  AlnView view;  // what thm_coverage_add_view uploads
   // a fetch's and a depth call's scratch and results
-  DArr<uint64_t> tile_sum, tile_cnt, carry, point_at, scan_tmp, point_entry, point_live, run_at;
+  TileScratch tiles;
+  DArr<uint64_t> point_entry, point_live, run_at;
   DArr<uint32_t> point_depth, d_depth;
   DArr<thm_cov_run> d_runs;
   DArr<unsigned long long> d_stats;
   HBuf h_out;
   Event ev[2], ev_fetch[2];
 
-  uint64_t track_entries() const { return h_base[n_sq]; }
+  uint64_t track_entries() const { return sq.entries(); }
   uint64_t held_bytes() const {
-    return base.cap() + diff.cap() + track.cap() + d_tot.cap + v_off.cap() + v_alns.cap() + v_dig.cap() + v_words.cap() + v_stat.cap() + tile_sum.cap() +
-           tile_cnt.cap() + carry.cap() + point_at.cap() + scan_tmp.cap() + point_entry.cap() + point_live.cap() + run_at.cap() + point_depth.cap() +
-           d_depth.cap() + d_runs.cap() + d_stats.cap();
+    return sq.base.cap() + diff.cap() + track.cap() + tot.d.cap + view.cap() + tiles.cap() + point_entry.cap() + point_live.cap() + run_at.cap() +
+           point_depth.cap() + d_depth.cap() + d_runs.cap() + d_stats.cap();
   }
 };
 
@@ -59,29 +59,26 @@ int add_batch(thm_coverage* c, const char* who, int refused, CovBatch b, thm_cov
   if (n_alns > 0xFFFFFFFFull - c->totals.n_alns)
     return fail(a, THM_ERR_INVALID_ARG, "%s: %llu alignments behind the %llu counted would be more than 2^32-1: a depth could wrap", who,
                 (unsigned long long)n_alns, (unsigned long long)c->totals.n_alns);
-  b.n_refs = (uint32_t)a->ix->refs.size();
-  b.n_sq = c->n_sq;
+  b.n_sq = c->sq.n_sq;
   b.flags = c->flags;
-  b.ref_sq = a->bam.ref_sq;
-  b.base = c->base;
+  b.base = c->sq.base;
   HIPCHK(a, ensure_events(c->ev));
   HIPCHK(a, c->track.ensure(n_alns, 16));
-  HIPCHK(a, c->d_tot.ensure((cov::N_TOTALS + 1) * 8));
+  HIPCHK(a, c->tot.reserve());
   CovCountParams cp;
   cp.b = b;
   cp.track = c->track;
-  cp.totals = c->d_tot.as<unsigned long long>();
-  cp.bad = cp.totals + cov::N_TOTALS;
+  cp.totals = c->tot.totals();
+  cp.bad = c->tot.bad();
   HIPCHK(a, hipEventRecord(c->ev[0], st));
-  HIPCHK(a, hipMemsetAsync(cp.totals, 0, cov::N_TOTALS * 8, st));
-  HIPCHK(a, hipMemsetAsync(cp.bad, 0xff, 8, st));
+  HIPCHK(a, c->tot.clear(st));
   HIPCHK(a, launch_cov_count(cp, a->n_cu, st));
-  unsigned long long h_tot[cov::N_TOTALS + 1];
-  HIPCHK(a, hipMemcpyAsync(h_tot, cp.totals, sizeof h_tot, hipMemcpyDeviceToHost, st));
+  HIPCHK(a, c->tot.fetch(st));
   HIPCHK(a, hipStreamSynchronize(st));
-  if (h_tot[cov::N_TOTALS] != ~0ull)
+  const unsigned long long* h_tot = c->tot.h;
+  if (c->tot.refused())
     return fail(a, refused, "%s: alignment %llu has a ref without an @SQ line, a CIGAR range outside the pool, or ends beyond its contig", who,
-                h_tot[cov::N_TOTALS]);
+                c->tot.first_bad());
   if (h_tot[cov::T_ALNS] != n_alns) return fail(a, THM_ERR_INTERNAL, "%s: %llu alignments counted of %llu", who, h_tot[cov::T_ALNS], (unsigned long long)n_alns);
   CovDepositParams dp;
   dp.b = b;
@@ -92,12 +89,7 @@ int add_batch(thm_coverage* c, const char* who, int refused, CovBatch b, thm_cov
   HIPCHK(a, hipEventRecord(c->ev[1], st));
   HIPCHK(a, hipStreamSynchronize(st));
   (void)elapsed_ms(c->ev[0], c->ev[1], &info->add_ms);
-  uint64_t* batch = (uint64_t*)&info->batch;
-  uint64_t* total = (uint64_t*)&c->totals;
-  for (int k = 0; k < cov::N_TOTALS; k++) {
-    batch[k] = h_tot[k];
-    total[k] += h_tot[k];
-  }
+  c->tot.accumulate(&info->batch, &c->totals);
   info->held_bytes = c->held_bytes();
   return THM_OK;
 }
@@ -106,58 +98,8 @@ int add_batch(thm_coverage* c, const char* who, int refused, CovBatch b, thm_cov
 int check_view(thm_coverage* c, const thm_cigar_view* v) {
   thm_aligner* a = c->a;
   const char* who = "thm_coverage_add_view";
-  const thm_index* ix = a->ix;
-  const uint64_t n = v->n_reads, n_alns = v->n_alns, n_words = v->n_cigar_words;
-  if ((n && !v->read_aln_off) || (n_alns && (!v->alns || !v->digests || !n)) || (n_words && !v->cigar))
-    return fail(a, THM_ERR_INVALID_ARG, "%s: null offsets, alignments, digests or words", who);
-  if (n) {
-    if (v->read_aln_off[0] != 0) return fail(a, THM_ERR_INVALID_ARG, "%s: read_aln_off[0] must be 0", who);
-    for (uint64_t r = 0; r < n; r++)
-      if (v->read_aln_off[r + 1] < v->read_aln_off[r]) return fail(a, THM_ERR_INVALID_ARG, "%s: the offsets descend at read %llu", who, (unsigned long long)r);
-    if (v->read_aln_off[n] != n_alns)
-      return fail(a, THM_ERR_INVALID_ARG, "%s: the offsets end at %llu, the view has %llu alignments", who, (unsigned long long)v->read_aln_off[n], (unsigned long long)n_alns);
-  }
-  for (uint64_t i = 0; i < n_alns; i++) {
-    const thm_aln& al = v->alns[i];
-    const thm_aln_digest& d = v->digests[i];
-    const unsigned long long at = i;
-    if (al.aln_type > THM_ALN_INTERGENIC) return fail(a, THM_ERR_INVALID_ARG, "%s: alignment %llu: aln_type %u is none", who, at, (unsigned)al.aln_type);
-    if (al.aln_type == THM_ALN_EXONIC && al.tx_or_gene_idx >= ix->txs.size())
-      return fail(a, THM_ERR_INVALID_ARG, "%s: alignment %llu: tx_or_gene_idx %u is outside the index's %zu transcripts", who, at, al.tx_or_gene_idx, ix->txs.size());
-    if (al.aln_type == THM_ALN_INTRONIC && al.tx_or_gene_idx >= ix->genes.size())
-      return fail(a, THM_ERR_INVALID_ARG, "%s: alignment %llu: tx_or_gene_idx %u is outside the index's %zu genes", who, at, al.tx_or_gene_idx, ix->genes.size());
-    if (al.ref_id >= c->h_ref_sq.size() || c->h_ref_sq[al.ref_id] < 0 || (uint32_t)c->h_ref_sq[al.ref_id] >= c->n_sq)
-      return fail(a, THM_ERR_INVALID_ARG, "%s: alignment %llu: ref_id %u has no @SQ line", who, at, al.ref_id);
-    if (d.cigar_off > n_words || d.n_cigar > n_words - d.cigar_off)
-      return fail(a, THM_ERR_INVALID_ARG, "%s: alignment %llu: CIGAR words [%llu, +%u) are outside the pool of %llu", who, at, (unsigned long long)d.cigar_off, d.n_cigar,
-                  (unsigned long long)n_words);
-    const uint32_t s = (uint32_t)c->h_ref_sq[al.ref_id];
-    const uint64_t len = c->h_base[s + 1] - c->h_base[s] - 1;
-    if (al.ystart > len || d.ref_len > len - al.ystart)
-      return fail(a, THM_ERR_INVALID_ARG, "%s: alignment %llu: position %llu + %llu lies beyond the %llu bases of its contig", who, at, (unsigned long long)al.ystart,
-                  (unsigned long long)d.ref_len, (unsigned long long)len);
-  }
-  return THM_OK;
-}
-
-// tile sums and counts of diff[0, n) (entries of one track from `first` on) and the scan of the sums
-int tile_pass(thm_coverage* c, CovTileParams& p, bool counts) {
-  thm_aligner* a = c->a;
-  hipStream_t st = a->stream;
-  const uint64_t nt = cov::n_tiles(p.n);
-  HIPCHK(a, c->tile_sum.ensure(nt + 1));
-  HIPCHK(a, c->tile_cnt.ensure(nt + 1));
-  HIPCHK(a, c->carry.ensure(nt + 2));
-  HIPCHK(a, c->point_at.ensure(nt + 2));
-  p.tile_sum = c->tile_sum;
-  p.tile_cnt = c->tile_cnt;
-  p.carry = c->carry;
-  p.point_at = c->point_at;
-  HIPCHK(a, launch_cov_tiles(p, st));
-  if (const int rc = scan_u64(a, c->scan_tmp, p.tile_sum, c->carry, nt, st); rc != THM_OK) return rc;
-  if (counts)
-    if (const int rc = scan_u64(a, c->scan_tmp, p.tile_cnt, c->point_at, nt, st); rc != THM_OK) return rc;
-  return THM_OK;
+  return check_cigar_view(a, who, v, c->sq.h_ref_sq,
+                          [&](uint64_t i, const thm_aln& al, const thm_aln_digest& d) { return c->sq.check_contig(a, who, i, al, d.ref_len); });
 }
 
 }  // namespace
@@ -179,27 +121,18 @@ int32_t thm_coverage_create(thm_aligner* a, uint32_t flags, uint64_t max_bytes, 
   c->a = a;
   c->flags = flags;
   c->n_tracks = cov::n_tracks(flags);
-  c->n_sq = (uint32_t)sq.size();
   memset(&c->totals, 0, sizeof c->totals);
-  c->h_base.assign(sq.size() + 1, 0);
-  for (size_t s = 0; s < sq.size(); s++) c->h_base[s + 1] = c->h_base[s] + sq[s].second + 1;
+  c->sq.lay_out(sq);
   const uint64_t entries = c->n_tracks * c->track_entries();
-  const unsigned long long need = entries * 4 + c->h_base.size() * 8;
+  const unsigned long long need = entries * 4 + c->sq.h_base.size() * 8;
   if (max_bytes && need > max_bytes) {
     delete c;
     return fail(a, THM_ERR_OOM, "thm_coverage_create: %u tracks over %zu contigs need %llu bytes, the cap is %llu", cov::n_tracks(flags), sq.size(), need,
                 (unsigned long long)max_bytes);
   }
-  const size_t n_refs = ix->refs.size();
-  c->h_ref_sq.assign(n_refs, -1);
-  // (allocated to the byte: the arrays are the object's size, not a buffer that grows)
-  hipError_t e = hipMalloc(&c->base.b.p, c->h_base.size() * 8);
-  if (e == hipSuccess) c->base.b.cap = c->h_base.size() * 8;
-  if (e == hipSuccess) e = hipMalloc(&c->diff.b.p, entries * 4 + 16);
-  if (e == hipSuccess) c->diff.b.cap = entries * 4 + 16;
-  if (e == hipSuccess) e = hipMemcpy(c->base, c->h_base.data(), c->h_base.size() * 8, hipMemcpyHostToDevice);
+  hipError_t e = c->sq.on_device(a);
+  if (e == hipSuccess) e = alloc_exact(c->diff, entries * 4 + 16);
   if (e == hipSuccess) e = hipMemset(c->diff, 0, entries * 4 + 16);
-  if (e == hipSuccess && n_refs) e = hipMemcpy(c->h_ref_sq.data(), a->bam.ref_sq, n_refs * 4, hipMemcpyDeviceToHost);
   if (e != hipSuccess) {
     delete c;
     return fail(a, e == hipErrorOutOfMemory ? THM_ERR_OOM : THM_ERR_HIP, "thm_coverage_create: %s (%llu bytes needed, the cap is %llu)", hipGetErrorString(e), need,
@@ -209,80 +142,23 @@ int32_t thm_coverage_create(thm_aligner* a, uint32_t flags, uint64_t max_bytes, 
   return THM_OK;
 }
 
-void thm_coverage_free(thm_coverage* c) {
-  if (!c) return;
-  int cur = 0;
-  (void)hipGetDevice(&cur);
-  (void)hipSetDevice(c->a->device);
-  (void)hipStreamSynchronize(c->a->stream);
-  delete c;
-  (void)hipSetDevice(cur);
-}
+void thm_coverage_free(thm_coverage* c) { free_summary(c); }
 
 int32_t thm_coverage_add(thm_coverage* c, thm_cov_info* info) {
   if (!c || !info) return THM_ERR_INVALID_ARG;
   memset(info, 0, sizeof(*info));
-  thm_aligner* a = c->a;
-  int rc = thm_batch_sync(a);
-  if (rc != THM_OK) return rc;
-  HIPCHK(a, hipSetDevice(a->device));
-  BatchSizes z;
-  rc = fetch_batch_sizes(a, nullptr, nullptr, nullptr, &z);
-  if (rc != THM_OK) return rc;
-  // the two CIGAR passes, as thm_batch_fetch_cigars runs them (THM_T_CIGAR belongs to that call)
-  uint64_t n_words = 0;
-  unsigned any_flags = 0;
-  const float t_cigar = a->timings[THM_T_CIGAR];
-  rc = run_cigar_passes(a, compacted_cigar_params(a, z), z.n_alns, &n_words, &any_flags);
-  a->timings[THM_T_CIGAR] = t_cigar;
-  if (rc != THM_OK) return rc;
-  if (any_flags & THM_DIGEST_MALFORMED) return fail(a, THM_ERR_INTERNAL, "malformed op stream in the compacted pool");
-  CovBatch b;
-  memset(&b, 0, sizeof b);
-  b.n_reads = a->n_reads;
-  b.n_alns = z.n_alns;
-  b.n_words = n_words;
-  b.aln_off = a->ext.aln_off;
-  b.alns = a->out.alns;
-  b.digests = a->cig.dig;
-  b.words = a->cig.words;
-  b.status = z.any_failed ? a->reads.status : nullptr;
+  CovBatch b{};
+  if (const int rc = resident_batch(c->a, &b); rc != THM_OK) return rc;
   return add_batch(c, "thm_coverage_add", THM_ERR_INTERNAL, b, info);
 }
 
 int32_t thm_coverage_add_view(thm_coverage* c, const thm_cigar_view* v, thm_cov_info* info) {
   if (!c || !v || !info) return THM_ERR_INVALID_ARG;
   memset(info, 0, sizeof(*info));
-  thm_aligner* a = c->a;
+  CovBatch b{};
   int rc = check_view(c, v);
+  if (rc == THM_OK) rc = c->view.upload(c->a, v, &b);
   if (rc != THM_OK) return rc;
-  HIPCHK(a, hipSetDevice(a->device));
-  hipStream_t st = a->stream;
-  const uint64_t n = v->n_reads, n_alns = v->n_alns, n_words = v->n_cigar_words;
-  const uint64_t zero = 0;
-  HIPCHK(a, c->v_off.ensure(n + 1));
-  HIPCHK(a, c->v_alns.ensure(n_alns + 1));
-  HIPCHK(a, c->v_dig.ensure(n_alns + 1));
-  HIPCHK(a, c->v_words.ensure(n_words + 4));
-  HIPCHK(a, hipMemcpyAsync(c->v_off, n ? v->read_aln_off : &zero, (n + 1) * 8, hipMemcpyHostToDevice, st));
-  if (n_alns) HIPCHK(a, hipMemcpyAsync(c->v_alns, v->alns, n_alns * sizeof(thm_aln), hipMemcpyHostToDevice, st));
-  if (n_alns) HIPCHK(a, hipMemcpyAsync(c->v_dig, v->digests, n_alns * sizeof(thm_aln_digest), hipMemcpyHostToDevice, st));
-  if (n_words) HIPCHK(a, hipMemcpyAsync(c->v_words, v->cigar, n_words * 4, hipMemcpyHostToDevice, st));
-  if (v->read_status && n) {
-    HIPCHK(a, c->v_stat.ensure(n));
-    HIPCHK(a, hipMemcpyAsync(c->v_stat, v->read_status, n * 4, hipMemcpyHostToDevice, st));
-  }
-  HIPCHK(a, hipStreamSynchronize(st));  // (`zero` and the caller's arrays have been read)
-  CovBatch b;
-  memset(&b, 0, sizeof b);
-  b.n_reads = n;
-  b.n_alns = n_alns;
-  b.n_words = n_words;
-  b.aln_off = c->v_off;
-  b.alns = c->v_alns;
-  b.digests = c->v_dig;
-  b.words = c->v_words;
-  b.status = v->read_status && n ? c->v_stat.get() : nullptr;
   return add_batch(c, "thm_coverage_add_view", THM_ERR_INVALID_ARG, b, info);
 }
 
@@ -291,13 +167,13 @@ int32_t thm_coverage_fetch(thm_coverage* c, uint32_t track, uint32_t first_ref, 
   memset(out, 0, sizeof(*out));
   thm_aligner* a = c->a;
   if (track >= c->n_tracks) return fail(a, THM_ERR_INVALID_ARG, "thm_coverage_fetch: track %u of %u", track, c->n_tracks);
-  if (first_ref > c->n_sq || n_refs > c->n_sq - first_ref)
-    return fail(a, THM_ERR_INVALID_ARG, "thm_coverage_fetch: @SQ entries [%u, +%u) of %u", first_ref, n_refs, c->n_sq);
+  if (first_ref > c->sq.n_sq || n_refs > c->sq.n_sq - first_ref)
+    return fail(a, THM_ERR_INVALID_ARG, "thm_coverage_fetch: @SQ entries [%u, +%u) of %u", first_ref, n_refs, c->sq.n_sq);
   HIPCHK(a, hipSetDevice(a->device));
   hipStream_t st = a->stream;
   HIPCHK(a, ensure_events(c->ev_fetch));
   HIPCHK(a, c->d_stats.ensure(4));
-  const uint64_t g0 = c->h_base[first_ref], g1 = c->h_base[first_ref + n_refs];
+  const uint64_t g0 = c->sq.h_base[first_ref], g1 = c->sq.h_base[first_ref + n_refs];
   CovTileParams tp;
   memset(&tp, 0, sizeof tp);
   tp.diff = c->diff + (uint64_t)track * c->track_entries() + g0;
@@ -308,8 +184,10 @@ int32_t thm_coverage_fetch(thm_coverage* c, uint32_t track, uint32_t first_ref, 
   HIPCHK(a, hipMemsetAsync(c->d_stats, 0, 3 * 8, st));
   unsigned long long n_points = 0, n_runs = 0, stats[3] = {0, 0, 0};
   if (nt) {
-    if (const int rc = tile_pass(c, tp, true); rc != THM_OK) return rc;
-    HIPCHK(a, hipMemcpyAsync(&n_points, c->point_at + nt, 8, hipMemcpyDeviceToHost, st));
+    if (const int rc = tile_pass(a, c->tiles, tp.diff, tp.n, true); rc != THM_OK) return rc;
+    tp.carry = c->tiles.carry;
+    tp.point_at = c->tiles.point_at;
+    HIPCHK(a, hipMemcpyAsync(&n_points, c->tiles.point_at + nt, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(a, hipStreamSynchronize(st));
     if (n_points > tp.n) return fail(a, THM_ERR_INTERNAL, "thm_coverage_fetch: %llu change points among %llu entries", n_points, (unsigned long long)tp.n);
   }
@@ -322,7 +200,7 @@ int32_t thm_coverage_fetch(thm_coverage* c, uint32_t track, uint32_t first_ref, 
     tp.point_depth = c->point_depth;
     tp.point_live = c->point_live;
     HIPCHK(a, launch_cov_points(tp, st));
-    if (const int rc = scan_u64(a, c->scan_tmp, tp.point_live, c->run_at, n_points, st, &n_runs); rc != THM_OK) return rc;
+    if (const int rc = scan_u64(a, c->tiles.scan_tmp, tp.point_live, c->run_at, n_points, st, &n_runs); rc != THM_OK) return rc;
     HIPCHK(a, hipStreamSynchronize(st));
     if (n_runs > n_points) return fail(a, THM_ERR_INTERNAL, "thm_coverage_fetch: %llu runs from %llu change points", n_runs, n_points);
   }
@@ -334,8 +212,8 @@ int32_t thm_coverage_fetch(thm_coverage* c, uint32_t track, uint32_t first_ref, 
     rp.point_depth = c->point_depth;
     rp.run_at = c->run_at;
     rp.n_points = n_points;
-    rp.base = c->base;
-    rp.n_sq = c->n_sq;
+    rp.base = c->sq.base;
+    rp.n_sq = c->sq.n_sq;
     rp.runs = c->d_runs;
     rp.stats = c->d_stats;
     HIPCHK(a, launch_cov_runs(rp, st));
@@ -362,8 +240,8 @@ int32_t thm_coverage_depth(thm_coverage* c, uint32_t track, uint32_t ref_id, uin
   memset(out, 0, sizeof(*out));
   thm_aligner* a = c->a;
   if (track >= c->n_tracks) return fail(a, THM_ERR_INVALID_ARG, "thm_coverage_depth: track %u of %u", track, c->n_tracks);
-  if (ref_id >= c->n_sq) return fail(a, THM_ERR_INVALID_ARG, "thm_coverage_depth: refID %u of %u", ref_id, c->n_sq);
-  const uint64_t len = c->h_base[ref_id + 1] - c->h_base[ref_id] - 1;
+  if (ref_id >= c->sq.n_sq) return fail(a, THM_ERR_INVALID_ARG, "thm_coverage_depth: refID %u of %u", ref_id, c->sq.n_sq);
+  const uint64_t len = c->sq.len(ref_id);
   if (n > cov::MAX_DEPTH_WINDOW || start > len || n > len - start)
     return fail(a, THM_ERR_INVALID_ARG, "thm_coverage_depth: the window [%llu, +%llu) must hold at most 2^24 bases and lie inside the %llu bases of refID %u",
                 (unsigned long long)start, (unsigned long long)n, (unsigned long long)len, ref_id);
@@ -374,15 +252,12 @@ int32_t thm_coverage_depth(thm_coverage* c, uint32_t track, uint32_t ref_id, uin
   HIPCHK(a, hipEventRecord(c->ev_fetch[0], st));
   if (n) {
     HIPCHK(a, c->d_depth.ensure(n));
-    CovTileParams tp;
-    memset(&tp, 0, sizeof tp);
-    tp.diff = c->diff + (uint64_t)track * c->track_entries() + c->h_base[ref_id];
-    tp.n = start + n;
-    tp.g0 = c->h_base[ref_id];
-    if (const int rc = tile_pass(c, tp, false); rc != THM_OK) return rc;
     CovWindowParams wp;
-    wp.diff = tp.diff;
-    wp.carry = c->carry;
+    wp.diff = c->diff + (uint64_t)track * c->track_entries() + c->sq.h_base[ref_id];
+    // (held_bytes is the same whether a fetch or a depth call came first: both size the scratch of the count scan)
+    HIPCHK(a, c->tiles.point_at.ensure(cov::n_tiles(start + n) + 2));
+    if (const int rc = tile_pass(a, c->tiles, wp.diff, start + n, false); rc != THM_OK) return rc;
+    wp.carry = c->tiles.carry;
     wp.start = start;
     wp.n = n;
     wp.out = c->d_depth;

@@ -79,20 +79,29 @@ struct NoBlock {
   COV_HD void operator()(uint64_t, uint64_t) const {}
 };
 
-// The device's checks of one alignment, before any array is touched: its ref has a refID below n_sq, its words lie inside
-// the pool, and the walk from ystart ends inside the contig.  *sq gets the refID; for an alignment with words *n_blocks
-// and *bases what the walk counted.
+// Where an alignment lies, before any array is touched: its ref has a refID below n_sq (-> *sq), its words lie inside the
+// pool, and it begins inside its contig.  Returns the contig's length, NOT_LOCATED where one of these fails.  The first
+// of the checks of every summary over this layout (check_aln below, pile::check_aln).
+constexpr uint64_t NOT_LOCATED = ~0ull;
+COV_HD uint64_t locate_aln(uint32_t ref_id, uint64_t ystart, uint64_t cigar_off, uint32_t n_cigar, uint64_t n_words, const int32_t* ref_sq, uint32_t n_refs,
+                           const uint64_t* base, uint32_t n_sq, uint32_t* sq) {
+  if (ref_id >= n_refs) return NOT_LOCATED;
+  const int32_t s = ref_sq[ref_id];
+  if (s < 0 || (uint32_t)s >= n_sq) return NOT_LOCATED;
+  *sq = (uint32_t)s;
+  if (cigar_off > n_words || (uint64_t)n_cigar > n_words - cigar_off) return NOT_LOCATED;
+  const uint64_t len = base[s + 1] - base[s] - 1;
+  return ystart > len ? NOT_LOCATED : len;
+}
+
+// The device's checks of one alignment, before any array is touched: locate_aln's, and the walk from ystart ends inside
+// the contig.  *sq gets the refID; for an alignment with words *n_blocks and *bases what the walk counted.
 COV_HD bool check_aln(uint32_t ref_id, uint64_t ystart, uint64_t cigar_off, uint32_t n_cigar, bool long_run, const uint32_t* words, uint64_t n_words,
                       const int32_t* ref_sq, uint32_t n_refs, const uint64_t* base, uint32_t n_sq, uint32_t* sq, uint32_t* n_blocks, uint64_t* bases) {
   *n_blocks = 0;
   *bases = 0;
-  if (ref_id >= n_refs) return false;
-  const int32_t s = ref_sq[ref_id];
-  if (s < 0 || (uint32_t)s >= n_sq) return false;
-  *sq = (uint32_t)s;
-  if (cigar_off > n_words || (uint64_t)n_cigar > n_words - cigar_off) return false;
-  const uint64_t len = base[s + 1] - base[s] - 1;
-  if (ystart > len) return false;
+  const uint64_t len = locate_aln(ref_id, ystart, cigar_off, n_cigar, n_words, ref_sq, n_refs, base, n_sq, sq);
+  if (len == NOT_LOCATED) return false;
   if (long_run) return true;
   uint64_t end = 0;
   *n_blocks = walk_blocks(words + cigar_off, n_cigar, ystart, NoBlock(), &end, bases);

@@ -1450,6 +1450,26 @@ int write_coverage_tracks(const thm_index* ix, thm_aligner* const* aligners, thm
   return THM_OK;
 }
 
+// The summaries a run was asked for, one quant and one coverage per aligner and the one aligner's pileup: they go when
+// their owner does (or at free()), the pileup first, then the coverages, then the quants, all before their aligners.
+struct Summaries {
+  std::vector<thm_quant*> quants;
+  std::vector<thm_coverage*> coverages;
+  thm_pileup* pileup = nullptr;
+  Summaries() = default;
+  Summaries(const Summaries&) = delete;
+  Summaries& operator=(const Summaries&) = delete;
+  ~Summaries() { free(); }
+  void free() {
+    thm_pileup_free(pileup);
+    for (thm_coverage* c : coverages) thm_coverage_free(c);
+    for (thm_quant* q : quants) thm_quant_free(q);
+    pileup = nullptr;
+    coverages.clear();
+    quants.clear();
+  }
+};
+
 // THM_PILEUP: the sites of all contigs with min_alt events or more as <output_path>.pileup.tsv
 int write_pileup_sites(const thm_index* ix, thm_aligner* a, thm_pileup* pileup, uint32_t min_alt, const std::string& output_path, std::string& err) {
   std::vector<std::pair<std::string, uint64_t>> sq;
@@ -1543,37 +1563,23 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
     thm_writer_free(w);
     return rc;
   }
-  std::vector<thm_quant*> quants(m.quant ? n_aligners : 0, nullptr);
-  for (size_t i = 0; i < quants.size(); i++)
-    if ((rc = thm_quant_create(aligners[i], &quants[i])) != THM_OK) {
-      thm::set_global_error(thm_last_error(aligners[i]));
-      for (thm_quant* q : quants) thm_quant_free(q);
-      thm_bam_sorter_free(sorter);
-      (void)out.close();
-      thm_writer_free(w);
-      return rc;
-    }
-  std::vector<thm_coverage*> coverages(m.coverage ? n_aligners : 0, nullptr);
-  for (size_t i = 0; i < coverages.size(); i++)
-    if ((rc = thm_coverage_create(aligners[i], m.cov_flags, 0, &coverages[i])) != THM_OK) {
-      thm::set_global_error(thm_last_error(aligners[i]));
-      for (thm_coverage* c : coverages) thm_coverage_free(c);
-      for (thm_quant* q : quants) thm_quant_free(q);
-      thm_bam_sorter_free(sorter);
-      (void)out.close();
-      thm_writer_free(w);
-      return rc;
-    }
-  thm_pileup* pileup = nullptr;
-  if (m.pileup && (rc = thm_pileup_create(aligners[0], m.pile_flags, 0, &pileup)) != THM_OK) {
-    thm::set_global_error(thm_last_error(aligners[0]));
-    for (thm_coverage* c : coverages) thm_coverage_free(c);
-    for (thm_quant* q : quants) thm_quant_free(q);
+  Summaries sums;  // (frees what has been created on every return below)
+  // a summary that `a` could not create: its message, and what stands so far goes
+  const auto not_created = [&](thm_aligner* a) {
+    thm::set_global_error(thm_last_error(a));
+    sums.free();
     thm_bam_sorter_free(sorter);
     (void)out.close();
     thm_writer_free(w);
     return rc;
-  }
+  };
+  sums.quants.assign(m.quant ? n_aligners : 0, nullptr);
+  for (size_t i = 0; i < sums.quants.size(); i++)
+    if ((rc = thm_quant_create(aligners[i], &sums.quants[i])) != THM_OK) return not_created(aligners[i]);
+  sums.coverages.assign(m.coverage ? n_aligners : 0, nullptr);
+  for (size_t i = 0; i < sums.coverages.size(); i++)
+    if ((rc = thm_coverage_create(aligners[i], m.cov_flags, 0, &sums.coverages[i])) != THM_OK) return not_created(aligners[i]);
+  if (m.pileup && (rc = thm_pileup_create(aligners[0], m.pile_flags, 0, &sums.pileup)) != THM_OK) return not_created(aligners[0]);
   const auto t_start = Clock::now();
   thm_writer* w2 = nullptr;
   const bool have_w2 = thm_writer_create(ix, format, n_threads, &w2) == THM_OK;
@@ -1581,9 +1587,9 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
   Run run(aligners, n_aligners, fastq_paths, n_paths, format, batch_reads, n_threads, n_parsers, m, w, w2 ? w2 : w, out, sorter);
   if (!have_w2) run.sh.set(THM_ERR_OOM, "cannot create the second writer object");
   run.index_path = std::string(output_path) + ".bai";
-  if (m.quant) run.quants = quants.data();
-  if (m.coverage) run.coverages = coverages.data();
-  run.pileup = pileup;
+  if (m.quant) run.quants = sums.quants.data();
+  if (m.coverage) run.coverages = sums.coverages.data();
+  run.pileup = sums.pileup;
   // ---- the stages: the cutter, the parsers, a thread per aligner; this thread formats
   std::thread cutter(&Run::cut, &run);
   std::vector<std::thread> parsers, gpus;
@@ -1599,22 +1605,20 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
   if (w2) thm_writer_free(w2);
   if (m.quant && run.sh.rc == THM_OK) {
     std::string err;
-    const int qrc = run.sh.step([&] { return write_quant_tables(ix, aligners, quants.data(), n_aligners, output_path, err); });
+    const int qrc = run.sh.step([&] { return write_quant_tables(ix, aligners, sums.quants.data(), n_aligners, output_path, err); });
     if (qrc != THM_OK) run.sh.set(qrc, err);
   }
   if (m.coverage && run.sh.rc == THM_OK) {
     std::string err;
-    const int crc = run.sh.step([&] { return write_coverage_tracks(ix, aligners, coverages.data(), n_aligners, m.cov_flags, output_path, err); });
+    const int crc = run.sh.step([&] { return write_coverage_tracks(ix, aligners, sums.coverages.data(), n_aligners, m.cov_flags, output_path, err); });
     if (crc != THM_OK) run.sh.set(crc, err);
   }
   if (m.pileup && run.sh.rc == THM_OK) {
     std::string err;
-    const int prc = run.sh.step([&] { return write_pileup_sites(ix, aligners[0], pileup, m.pile_min_alt, output_path, err); });
+    const int prc = run.sh.step([&] { return write_pileup_sites(ix, aligners[0], sums.pileup, m.pile_min_alt, output_path, err); });
     if (prc != THM_OK) run.sh.set(prc, err);
   }
-  thm_pileup_free(pileup);
-  for (thm_coverage* c : coverages) thm_coverage_free(c);
-  for (thm_quant* q : quants) thm_quant_free(q);
+  sums.free();  // (in front of the sorter and the writer, and inside wall_s, as they always were)
   thm_bam_sorter_free(sorter);
   if (!out.close()) run.sh.set(THM_ERR_IO, std::string("error closing ") + output_path);
   thm_writer_free(w);

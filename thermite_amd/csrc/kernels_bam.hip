@@ -413,8 +413,6 @@ __global__ __launch_bounds__(256) void bam_emit_kernel(const BamParams p) {
 
 }  // namespace dev
 
-static unsigned blocks256(uint64_t n) { return (unsigned)((n + 255) / 256); }
-
 hipError_t launch_bam_prep(const BamParams& p, hipStream_t s) {
   if (p.n_reads == 0) return hipSuccess;
   hipLaunchKernelGGL(dev::bam_prep_kernel, dim3(blocks256(p.n_reads)), dim3(256), 0, s, p);

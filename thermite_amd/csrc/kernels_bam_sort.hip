@@ -127,8 +127,6 @@ __global__ __launch_bounds__(256) void bam_sort_gather_records_kernel(const BamS
 
 }  // namespace dev
 
-static unsigned blocks256(uint64_t n) { return (unsigned)((n + 255) / 256); }
-
 hipError_t launch_bam_sort_keys(const BamSortKeysParams& p, hipStream_t s) {
   if (p.n == 0) return hipSuccess;
   hipLaunchKernelGGL(dev::bam_sort_keys_kernel, dim3(blocks256(p.n)), dim3(256), 0, s, p);

@@ -18,8 +18,8 @@
 #include <hip/hip_runtime.h>
 
 #include "coverage_device.h"
-#include "coverage_tile.h"
 #include "launch_io.h"
+#include "summary_tile.h"
 
 namespace thm {
 namespace dev {
@@ -64,25 +64,9 @@ __global__ __launch_bounds__(256) void cov_count_kernel(const CovCountParams p) 
     }
     p.track[a] = (uint8_t)track;
   }
-  for (uint64_t r = first; r < b.n_reads; r += stride) {
-    t[cov::T_READS]++;
-    if (b.status && b.status[r] != THM_OK) t[cov::T_FAILED]++;
-  }
-  for (int k = 0; k < cov::N_TOTALS; k++) {
-    const uint64_t s = cov_wave_sum_u64(t[k]);
-    if ((threadIdx.x & 63u) == 0 && s) atomicAdd(&sh_tot[k], (ull)s);
-  }
-  __syncthreads();
-  if (threadIdx.x < cov::N_TOTALS && sh_tot[threadIdx.x]) atomicAdd(&p.totals[threadIdx.x], sh_tot[threadIdx.x]);
+  read_totals(b, t[cov::T_READS], t[cov::T_FAILED]);
+  block_totals(t, sh_tot, p.totals);
 }
-
-struct BlockAdder {
-  uint32_t* dst;  // the contig's first entry in the alignment's track
-  __device__ void operator()(uint64_t s, uint64_t e) const {
-    (void)atomicAdd(dst + s, 1u);
-    (void)atomicAdd(dst + e, 0xFFFFFFFFu);
-  }
-};
 
 __global__ __launch_bounds__(256) void cov_deposit_kernel(const CovDepositParams p) {
   const uint64_t a = (uint64_t)blockIdx.x * 256u + threadIdx.x;
@@ -190,8 +174,6 @@ __global__ __launch_bounds__(256) void cov_window_kernel(const CovWindowParams p
 
 }  // namespace dev
 
-static unsigned cov_blocks(uint64_t n) { return (unsigned)((n + 255) / 256); }
-
 hipError_t launch_cov_count(const CovCountParams& p, int n_cu, hipStream_t s) {
   const uint64_t n = p.b.n_alns > p.b.n_reads ? p.b.n_alns : p.b.n_reads;
   if (n == 0) return hipSuccess;
@@ -202,7 +184,7 @@ hipError_t launch_cov_count(const CovCountParams& p, int n_cu, hipStream_t s) {
 }
 hipError_t launch_cov_deposit(const CovDepositParams& p, hipStream_t s) {
   if (p.b.n_alns == 0) return hipSuccess;
-  hipLaunchKernelGGL(dev::cov_deposit_kernel, dim3(cov_blocks(p.b.n_alns)), dim3(256), 0, s, p);
+  hipLaunchKernelGGL(dev::cov_deposit_kernel, dim3(blocks256(p.b.n_alns)), dim3(256), 0, s, p);
   return hipGetLastError();
 }
 hipError_t launch_cov_tiles(const CovTileParams& p, hipStream_t s) {
@@ -217,7 +199,7 @@ hipError_t launch_cov_points(const CovTileParams& p, hipStream_t s) {
 }
 hipError_t launch_cov_runs(const CovRunParams& p, hipStream_t s) {
   if (p.n_points == 0) return hipSuccess;
-  hipLaunchKernelGGL(dev::cov_runs_kernel, dim3(cov_blocks(p.n_points)), dim3(256), 0, s, p);
+  hipLaunchKernelGGL(dev::cov_runs_kernel, dim3(blocks256(p.n_points)), dim3(256), 0, s, p);
   return hipGetLastError();
 }
 hipError_t launch_cov_window(const CovWindowParams& p, hipStream_t s) {

@@ -21,9 +21,9 @@
 //   window   the same tile pass over the tiles of a window, a row per position, its table rows found inside the tile's
 #include <hip/hip_runtime.h>
 
-#include "coverage_tile.h"
 #include "launch_io.h"
 #include "pileup_device.h"
+#include "summary_tile.h"
 
 namespace thm {
 namespace dev {
@@ -162,17 +162,8 @@ __global__ __launch_bounds__(256) void pile_count_kernel(const PileCountParams p
       p.used[a] = used ? 1 : 0;
     }
   }
-  const uint64_t stride = (uint64_t)gridDim.x * 256u;
-  for (uint64_t r = (uint64_t)blockIdx.x * 256u + threadIdx.x; r < b.n_reads; r += stride) {
-    t[pile::T_READS]++;
-    if (b.status && b.status[r] != THM_OK) t[pile::T_FAILED]++;
-  }
-  for (int k = 0; k < pile::N_TOTALS; k++) {
-    const uint64_t s = cov_wave_sum_u64(t[k]);
-    if ((threadIdx.x & 63u) == 0 && s) atomicAdd(&sh_tot[k], (ull)s);
-  }
-  __syncthreads();
-  if (threadIdx.x < pile::N_TOTALS && sh_tot[threadIdx.x]) atomicAdd(&p.totals[threadIdx.x], sh_tot[threadIdx.x]);
+  read_totals(b, t[pile::T_READS], t[pile::T_FAILED]);
+  block_totals(t, sh_tot, p.totals);
 }
 
 __global__ __launch_bounds__(256) void pile_extract_kernel(const PileExtractParams p) {
@@ -185,21 +176,13 @@ __global__ __launch_bounds__(256) void pile_extract_kernel(const PileExtractPara
                         p.ev_off[a + 1]);
 }
 
-struct PileBlockAdder {
-  uint32_t* dst;  // the contig's first entry
-  __device__ void operator()(uint64_t s, uint64_t e) const {
-    (void)atomicAdd(dst + s, 1u);
-    (void)atomicAdd(dst + e, 0xFFFFFFFFu);
-  }
-};
-
 __global__ __launch_bounds__(256) void pile_deposit_kernel(const PileExtractParams p) {
   const uint64_t a = (uint64_t)blockIdx.x * 256u + threadIdx.x;
   if (a >= p.b.n_alns || !p.used[a]) return;
   const thm_aln& al = p.b.alns[a];
   const thm_aln_digest& d = p.b.digests[a];
   uint64_t end = 0;
-  (void)cov::walk_blocks(p.b.words + d.cigar_off, d.n_cigar, al.ystart, PileBlockAdder{p.diff + p.b.base[p.b.ref_sq[al.ref_id]]}, &end);
+  (void)cov::walk_blocks(p.b.words + d.cigar_off, d.n_cigar, al.ystart, BlockAdder{p.diff + p.b.base[p.b.ref_sq[al.ref_id]]}, &end);
 }
 
 __global__ __launch_bounds__(256) void pile_heads_kernel(const PileReduceParams p) {
@@ -290,8 +273,6 @@ __global__ __launch_bounds__(256) void pile_window_kernel(const PileFetchParams 
 
 }  // namespace dev
 
-static unsigned pile_blocks(uint64_t n, uint64_t per_block = 256) { return (unsigned)((n + per_block - 1) / per_block); }
-
 hipError_t launch_pile_count(const PileCountParams& p, int n_cu, hipStream_t s) {
   const uint64_t by_alns = (p.b.n_alns + dev::PILE_GROUPS - 1) / dev::PILE_GROUPS, by_reads = (p.b.n_reads + 255) / 256;
   const uint64_t need = by_alns > by_reads ? by_alns : by_reads;
@@ -303,34 +284,35 @@ hipError_t launch_pile_count(const PileCountParams& p, int n_cu, hipStream_t s) 
 }
 hipError_t launch_pile_extract(const PileExtractParams& p, hipStream_t s) {
   if (p.b.n_alns == 0) return hipSuccess;
-  hipLaunchKernelGGL(dev::pile_extract_kernel, dim3(pile_blocks(p.b.n_alns, dev::PILE_GROUPS)), dim3(256), 0, s, p);
+  // (a group of lanes per alignment: PILE_GROUPS alignments a workgroup)
+  hipLaunchKernelGGL(dev::pile_extract_kernel, dim3(blocks256(p.b.n_alns * pile::GROUP)), dim3(256), 0, s, p);
   return hipGetLastError();
 }
 hipError_t launch_pile_deposit(const PileExtractParams& p, hipStream_t s) {
   if (p.b.n_alns == 0) return hipSuccess;
-  hipLaunchKernelGGL(dev::pile_deposit_kernel, dim3(pile_blocks(p.b.n_alns)), dim3(256), 0, s, p);
+  hipLaunchKernelGGL(dev::pile_deposit_kernel, dim3(blocks256(p.b.n_alns)), dim3(256), 0, s, p);
   return hipGetLastError();
 }
 hipError_t launch_pile_heads(const PileReduceParams& p, hipStream_t s) {
   if (p.n == 0) return hipSuccess;
-  hipLaunchKernelGGL(dev::pile_heads_kernel, dim3(pile_blocks(p.n)), dim3(256), 0, s, p);
+  hipLaunchKernelGGL(dev::pile_heads_kernel, dim3(blocks256(p.n)), dim3(256), 0, s, p);
   return hipGetLastError();
 }
 hipError_t launch_pile_runs(const PileReduceParams& p, hipStream_t s) {
   if (p.n == 0) return hipSuccess;
-  hipLaunchKernelGGL(dev::pile_head_at_kernel, dim3(pile_blocks(p.n)), dim3(256), 0, s, p);
+  hipLaunchKernelGGL(dev::pile_head_at_kernel, dim3(blocks256(p.n)), dim3(256), 0, s, p);
   if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-  hipLaunchKernelGGL(dev::pile_runs_kernel, dim3(pile_blocks(p.n_keys)), dim3(256), 0, s, p);
+  hipLaunchKernelGGL(dev::pile_runs_kernel, dim3(blocks256(p.n_keys)), dim3(256), 0, s, p);
   return hipGetLastError();
 }
 hipError_t launch_pile_lookup(const PileMergeParams& p, hipStream_t s) {
   if (p.n_red == 0) return hipSuccess;
-  hipLaunchKernelGGL(dev::pile_lookup_kernel, dim3(pile_blocks(p.n_red)), dim3(256), 0, s, p);
+  hipLaunchKernelGGL(dev::pile_lookup_kernel, dim3(blocks256(p.n_red)), dim3(256), 0, s, p);
   return hipGetLastError();
 }
 hipError_t launch_pile_update(const PileMergeParams& p, hipStream_t s) {
   if (p.n_red == 0) return hipSuccess;
-  hipLaunchKernelGGL(dev::pile_update_kernel, dim3(pile_blocks(p.n_red)), dim3(256), 0, s, p);
+  hipLaunchKernelGGL(dev::pile_update_kernel, dim3(blocks256(p.n_red)), dim3(256), 0, s, p);
   return hipGetLastError();
 }
 hipError_t launch_pile_bounds(const PileFetchParams& p, hipStream_t s) {
@@ -339,7 +321,7 @@ hipError_t launch_pile_bounds(const PileFetchParams& p, hipStream_t s) {
 }
 hipError_t launch_pile_keep(const PileFetchParams& p, hipStream_t s) {
   if (p.r1 == p.r0) return hipSuccess;
-  hipLaunchKernelGGL(dev::pile_keep_kernel, dim3(pile_blocks(p.r1 - p.r0)), dim3(256), 0, s, p);
+  hipLaunchKernelGGL(dev::pile_keep_kernel, dim3(blocks256(p.r1 - p.r0)), dim3(256), 0, s, p);
   return hipGetLastError();
 }
 hipError_t launch_pile_sites(const PileFetchParams& p, hipStream_t s) {

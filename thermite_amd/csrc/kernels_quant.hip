@@ -23,6 +23,7 @@
 
 #include "launch_io.h"
 #include "quant_device.h"
+#include "summary_tile.h"
 
 namespace thm {
 namespace dev {
@@ -31,10 +32,6 @@ using ull = unsigned long long;
 constexpr uint32_t GENE_SLOTS = 2048;  // 16 KB of LDS: tags and counts
 constexpr uint32_t NOT_FOUND = 0xFFFFFFFFu;
 
-__device__ inline uint32_t wave_sum_u32(uint32_t v) {
-  for (int d = 32; d >= 1; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d);
-  return v;
-}
 __device__ inline uint64_t shfl_down_u64(uint64_t v, int d) {
   const uint32_t lo = (uint32_t)__shfl_down((int)(uint32_t)v, d), hi = (uint32_t)__shfl_down((int)(uint32_t)(v >> 32), d);
   return (uint64_t)hi << 32 | lo;
@@ -96,12 +93,7 @@ __global__ __launch_bounds__(256) void quant_count_kernel(const QuantCountParams
     else
       t[nh == 1 ? quant::T_UNIQUE_READS : quant::T_MULTI_READS]++;
   }
-  for (int k = 0; k < quant::N_TOTALS; k++) {
-    const uint32_t s = wave_sum_u32(t[k]);
-    if ((threadIdx.x & 63u) == 0 && s) atomicAdd(&sh_tot[k], (ull)s);
-  }
-  __syncthreads();
-  if (threadIdx.x < quant::N_TOTALS && sh_tot[threadIdx.x]) atomicAdd(&p.totals[threadIdx.x], sh_tot[threadIdx.x]);
+  block_totals(t, sh_tot, p.totals);
 }
 
 struct HitWriter {
@@ -253,7 +245,6 @@ __global__ __launch_bounds__(256) void quant_rows_kernel(const QuantRows in, uin
 
 }  // namespace dev
 
-static unsigned quant_blocks(uint64_t n) { return (unsigned)((n + 255) / 256); }
 // grid-stride kernels: enough workgroups to fill the device, few enough that each sums many items before its atomics
 static unsigned quant_grid(uint64_t n, int n_cu) {
   const uint64_t need = (n + 255) / 256, cap = (uint64_t)(n_cu > 0 ? n_cu : 256) * 8;
@@ -268,7 +259,7 @@ hipError_t launch_quant_count(const QuantCountParams& p, int n_cu, hipStream_t s
 }
 hipError_t launch_quant_extract(const QuantExtractParams& p, hipStream_t s) {
   if (p.b.n_alns == 0) return hipSuccess;
-  hipLaunchKernelGGL(dev::quant_extract_kernel, dim3(quant_blocks(p.b.n_alns)), dim3(256), 0, s, p);
+  hipLaunchKernelGGL(dev::quant_extract_kernel, dim3(blocks256(p.b.n_alns)), dim3(256), 0, s, p);
   return hipGetLastError();
 }
 hipError_t launch_quant_genes(const QuantGenesParams& p, int n_cu, hipStream_t s) {
@@ -278,32 +269,32 @@ hipError_t launch_quant_genes(const QuantGenesParams& p, int n_cu, hipStream_t s
 }
 hipError_t launch_quant_gather(const uint64_t* in, const uint32_t* perm, uint64_t n, uint64_t* out, hipStream_t s) {
   if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(dev::quant_gather_kernel, dim3(quant_blocks(n)), dim3(256), 0, s, in, perm, n, out);
+  hipLaunchKernelGGL(dev::quant_gather_kernel, dim3(blocks256(n)), dim3(256), 0, s, in, perm, n, out);
   return hipGetLastError();
 }
 hipError_t launch_quant_heads(const QuantReduceParams& p, hipStream_t s) {
   if (p.n == 0) return hipSuccess;
-  hipLaunchKernelGGL(dev::quant_heads_kernel, dim3(quant_blocks(p.n)), dim3(256), 0, s, p);
+  hipLaunchKernelGGL(dev::quant_heads_kernel, dim3(blocks256(p.n)), dim3(256), 0, s, p);
   return hipGetLastError();
 }
 hipError_t launch_quant_reduce(const QuantReduceParams& p, hipStream_t s) {
   if (p.n == 0) return hipSuccess;
-  hipLaunchKernelGGL(dev::quant_reduce_kernel, dim3(quant_blocks(p.n)), dim3(256), 0, s, p);
+  hipLaunchKernelGGL(dev::quant_reduce_kernel, dim3(blocks256(p.n)), dim3(256), 0, s, p);
   return hipGetLastError();
 }
 hipError_t launch_quant_lookup(const QuantMergeParams& p, hipStream_t s) {
   if (p.n_red == 0) return hipSuccess;
-  hipLaunchKernelGGL(dev::quant_lookup_kernel, dim3(quant_blocks(p.n_red)), dim3(256), 0, s, p);
+  hipLaunchKernelGGL(dev::quant_lookup_kernel, dim3(blocks256(p.n_red)), dim3(256), 0, s, p);
   return hipGetLastError();
 }
 hipError_t launch_quant_update(const QuantMergeParams& p, hipStream_t s) {
   if (p.n_red == 0) return hipSuccess;
-  hipLaunchKernelGGL(dev::quant_update_kernel, dim3(quant_blocks(p.n_red)), dim3(256), 0, s, p);
+  hipLaunchKernelGGL(dev::quant_update_kernel, dim3(blocks256(p.n_red)), dim3(256), 0, s, p);
   return hipGetLastError();
 }
 hipError_t launch_quant_rows(const QuantRows& in, uint64_t n, thm_quant_junction* out, hipStream_t s) {
   if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(dev::quant_rows_kernel, dim3(quant_blocks(n)), dim3(256), 0, s, in, n, out);
+  hipLaunchKernelGGL(dev::quant_rows_kernel, dim3(blocks256(n)), dim3(256), 0, s, in, n, out);
   return hipGetLastError();
 }
 

@@ -1,11 +1,14 @@
 // launch_io.h -- parameter blocks and launch wrappers of the kernels behind the file-level entry points (BAM, BGZF, BAM
-// sort, quant, coverage, BAI, FASTQ, inflate, gzip): what the alignment pipeline itself never sees.  The pipeline's are in launch.h.
+// sort, the run summaries, BAI, FASTQ, inflate, gzip): what the alignment pipeline itself never sees.  The pipeline's are in launch.h.
 #ifndef THERMITE_LAUNCH_IO_H
 #define THERMITE_LAUNCH_IO_H
 
 #include "launch.h"
 
 namespace thm {
+
+// workgroups of 256 threads for n items, a thread each
+inline unsigned blocks256(uint64_t n) { return (unsigned)((n + 255) / 256); }
 
 // ---- BAM records on the device (kernels_bam.hip; host side bam.hip) ----
 // prep (per read: record count, QNAME length) -> scan -> size (per record: its read, its bytes) -> scan -> emit (one
@@ -96,22 +99,30 @@ hipError_t launch_bam_sort_order(const uint32_t* ord, const uint32_t* len, const
 // by_records: the record-centric shape (a wavefront per record), else the output-centric one (16 bytes a lane)
 hipError_t launch_bam_sort_gather(const BamSortGatherParams& p, bool by_records, int n_cu, hipStream_t s);
 
-// ---- gene and junction count tables of a run (kernels_quant.hip, quant_device.h; host side quant.hip) ----
-// count (per alignment: checks, its hits; per read: the read totals) -> scan -> extract (a row per hit) -> sort by the
-// 128-bit key as two stable 64-bit passes over a permutation -> heads, scan, reduce (by key: sums and the maximum) ->
-// lookup of the reduced rows in the running table, scan of the new ones -> update (found rows in place, new rows behind
-// the table's) -> the same sort over table + new rows -> genes (last, so that a refused batch has added nothing).
-struct QuantBatch {
+// ---- what every summary of a run walks (quant, coverage, pileup below; host side run_summary.h) ----
+// The alignments of one batch on the device: the compacted records of the batch that is resident after thm_batch_run
+// with the digests and words of the CIGAR passes, or the arrays of a caller's thm_cigar_view.  The batch structs of the
+// three summaries begin with it and add their own tables; they go to the kernels by value.
+struct AlnBatch {
   uint64_t n_reads, n_alns, n_words;
   const uint64_t* aln_off;        // [n_reads + 1]
   const thm_aln* alns;            // [n_alns]
   const thm_aln_digest* digests;  // [n_alns]
   const uint32_t* words;          // [n_words]
   const int32_t* status;          // [n_reads]; null: no read failed
-  uint32_t n_refs, n_txs, n_genes;
+  uint32_t n_refs;
+  const int32_t* ref_sq;          // [n_refs] BAM refID, -1: none
+};
+
+// ---- gene and junction count tables of a run (kernels_quant.hip, quant_device.h; host side quant.hip) ----
+// count (per alignment: checks, its hits; per read: the read totals) -> scan -> extract (a row per hit) -> sort by the
+// 128-bit key as two stable 64-bit passes over a permutation -> heads, scan, reduce (by key: sums and the maximum) ->
+// lookup of the reduced rows in the running table, scan of the new ones -> update (found rows in place, new rows behind
+// the table's) -> the same sort over table + new rows -> genes (last, so that a refused batch has added nothing).
+struct QuantBatch : AlnBatch {
+  uint32_t n_txs, n_genes;
   const uint32_t* tx_gene;        // [n_txs]
   const uint8_t* tx_forward;      // [n_txs] thm_tx::strand
-  const int32_t* ref_sq;          // [n_refs] BAM refID, -1: none
 };
 // junction rows, one array per field: before the reduce a row is one hit (n_unique + n_multi == 1)
 struct QuantRows {
@@ -173,15 +184,8 @@ hipError_t launch_quant_rows(const QuantRows& in, uint64_t n, thm_quant_junction
 //        (per tile: a local scan plus the carry is the depth; (entry, depth) per change point) -> scan of the points with
 //        a depth -> runs (a thread per change point pairs it with its successor).
 // depth: tiles and the scan of the sums -> window (the local scan again, the depths of the window's entries).
-struct CovBatch {
-  uint64_t n_reads, n_alns, n_words;
-  const uint64_t* aln_off;        // [n_reads + 1]
-  const thm_aln* alns;            // [n_alns]
-  const thm_aln_digest* digests;  // [n_alns]
-  const uint32_t* words;          // [n_words]
-  const int32_t* status;          // [n_reads]; null: no read failed
-  uint32_t n_refs, n_sq, flags;   // flags: THM_COV_*
-  const int32_t* ref_sq;          // [n_refs] BAM refID, -1: none
+struct CovBatch : AlnBatch {
+  uint32_t n_sq, flags;           // flags: THM_COV_*
   const uint64_t* base;           // [n_sq + 1] first entry of every contig in a track (coverage_device.h)
 };
 struct CovCountParams {
@@ -241,17 +245,10 @@ hipError_t launch_cov_window(const CovWindowParams& p, hipStream_t s);
 // fetch:  bounds (the range's rows) -> keep (the rows that begin a position with enough events) -> scan; coverage's tiles
 //         and their scan -> sites (per tile with rows: the depths through LDS, a row per kept position).
 // window: bounds, tiles and their scan -> window (per tile of the window: the depths, a row per position).
-struct PileBatch {
-  uint64_t n_reads, n_alns, n_words;
-  const uint64_t* aln_off;        // [n_reads + 1]
-  const thm_aln* alns;            // [n_alns]
-  const thm_aln_digest* digests;  // [n_alns]
-  const uint32_t* words;          // [n_words]
-  const int32_t* status;          // [n_reads]; null: no read failed
+struct PileBatch : AlnBatch {
   const uint8_t* bases;           // the raw reads: read r is bases[base_off[r], base_off[r + 1])
   const uint64_t* base_off;       // [n_reads + 1]
-  uint32_t n_refs, n_sq, flags;   // flags: THM_PILE_*
-  const int32_t* ref_sq;          // [n_refs] BAM refID, -1: none
+  uint32_t n_sq, flags;           // flags: THM_PILE_*
   const uint64_t* base;           // [n_sq + 1] first entry of every contig in the layout (coverage_device.h)
   const uint64_t* tstart;         // [n_sq] first byte of every contig's forward copy in the text
   const uint8_t* text;

@@ -4,7 +4,14 @@
 // index's text.  The depth is a difference array as thm_coverage keeps one; the observations that differ from the
 // reference are a sorted table of (key, count), merged batch by batch as quant.hip merges its junction rows; only totals
 // and rows of sites come back to the host.  The kernels are kernels_pileup.hip, the per-item functions and the key
-// pileup_device.h; DESIGN.md section 4.19.
+// pileup_device.h; the batch, the view's upload and checks, the contig layout, the totals and the tile pass are
+// run_summary.h's, shared with quant.hip and coverage.hip.  DESIGN.md sections 4.19 and 4.20.
+//
+// Synchronisations of the stream.  add: thm_batch_sync's, one of fetch_batch_sizes, one of the CIGAR passes, one behind
+// the count pass, with events one in sort_reduce and with reduced rows one in merge_rows, one behind the deposit.
+// add_view: one behind the upload (the reads go up in front of it), then as add from the count pass on.  fetch: one in
+// row_bounds (a table with rows), one behind the scan of the kept rows (a range with rows), one at the end.  window: one
+// in row_bounds, one at the end.  reset: one.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -14,17 +21,17 @@
 #include "io_internal.h"
 #include "launch_io.h"
 #include "pileup_device.h"
+#include "run_summary.h"
 
 using namespace thm;
 
 struct thm_pileup {
   thm_aligner* a = nullptr;
-  uint32_t flags = 0, n_sq = 0;
+  uint32_t flags = 0;
   uint64_t max_bytes = 0, array_bytes = 0;
-  std::vector<int32_t> h_ref_sq;  // what bam.ref_sq holds, for the checks of thm_pileup_add_view
-  std::vector<uint64_t> h_base;   // [n_sq + 1] first entry of every contig in the layout
-  DArr<uint64_t> base, tstart;
-  DArr<uint32_t> diff;            // [h_base[n_sq]]
+  SqLayout sq;           // the contigs of the depth
+  DArr<uint64_t> tstart;
+  DArr<uint32_t> diff;   // [sq.entries()]
   // the running event table, sorted by key, in tab[cur]; the other takes the next merge
   DArr<uint64_t> tab_key[2];
   DArr<uint32_t> tab_cnt[2];
@@ -32,32 +39,30 @@ struct thm_pileup {
   uint64_t n_tab = 0;
   thm_pile_totals totals;
   // one batch's scratch
-  DArr<uint64_t> ev_cnt, ev_off, aln_read, scan_tmp, keys, skeys, flag, first, head_at, red_key, where, is_new, new_at, cat_key;
+  DArr<uint64_t> ev_cnt, ev_off, aln_read, keys, skeys, flag, first, head_at, red_key, where, is_new, new_at, cat_key;
   DArr<uint32_t> red_cnt, cat_cnt;
   DArr<uint8_t> used;
-  DBuf d_tot;    // the totals (unsigned long long) and behind them the `bad` word
+  BatchTotals<pile::N_TOTALS> tot;
   DBuf cub_tmp;  // hipcub's scratch
-  // the view thm_pileup_add_view uploads
-  DArr<uint64_t> v_off, v_base_off;
-  DArr<thm_aln> v_alns;
-  DArr<thm_aln_digest> v_dig;
-  DArr<uint32_t> v_words;
-  DArr<int32_t> v_stat;
+  // what thm_pileup_add_view uploads: the view, and the reads
+  AlnView view;
+  DArr<uint64_t> v_base_off;
   DArr<uint8_t> v_bases;
-  // a fetch's and a window's scratch and results
-  DArr<uint64_t> tile_sum, tile_cnt, carry, bounds, keep, site_at;
+  // a fetch's and a window's scratch and results; tiles.scan_tmp is every scan's of the object, tiles.point_at stays empty
+  TileScratch tiles;
+  DArr<uint64_t> bounds, keep, site_at;
   DArr<thm_pile_site> d_sites;
   HBuf h_out;
   Event ev[2], ev_fetch[2];
 
-  uint64_t entries() const { return h_base[n_sq]; }
+  uint64_t entries() const { return sq.entries(); }
   uint64_t held_bytes() const {
-    size_t n = d_tot.cap + cub_tmp.cap;
-    for (const DArr<uint64_t>* x : {&base, &tstart, &tab_key[0], &tab_key[1], &ev_cnt, &ev_off, &aln_read, &scan_tmp, &keys, &skeys, &flag, &first, &head_at, &red_key,
-                                    &where, &is_new, &new_at, &cat_key, &v_off, &v_base_off, &tile_sum, &tile_cnt, &carry, &bounds, &keep, &site_at})
+    size_t n = tot.d.cap + cub_tmp.cap + view.cap() + tiles.cap();
+    for (const DArr<uint64_t>* x : {&sq.base, &tstart, &tab_key[0], &tab_key[1], &ev_cnt, &ev_off, &aln_read, &keys, &skeys, &flag, &first, &head_at, &red_key, &where,
+                                    &is_new, &new_at, &cat_key, &v_base_off, &bounds, &keep, &site_at})
       n += x->cap();
-    for (const DArr<uint32_t>* x : {&diff, &tab_cnt[0], &tab_cnt[1], &red_cnt, &cat_cnt, &v_words}) n += x->cap();
-    return n + used.cap() + v_alns.cap() + v_dig.cap() + v_stat.cap() + v_bases.cap() + d_sites.cap();
+    for (const DArr<uint32_t>* x : {&diff, &tab_cnt[0], &tab_cnt[1], &red_cnt, &cat_cnt}) n += x->cap();
+    return n + used.cap() + v_bases.cap() + d_sites.cap();
   }
 };
 
@@ -91,7 +96,7 @@ int sort_reduce(thm_pileup* c, uint64_t n, uint64_t* m) {
   p.first = c->first;
   HIPCHK(a, launch_pile_heads(p, st));
   unsigned long long n_keys = 0;
-  if (const int rc = scan_u64(a, c->scan_tmp, p.flag, c->first, n, st, &n_keys); rc != THM_OK) return rc;
+  if (const int rc = scan_u64(a, c->tiles.scan_tmp, p.flag, c->first, n, st, &n_keys); rc != THM_OK) return rc;
   HIPCHK(a, hipStreamSynchronize(st));
   if (n_keys == 0 || n_keys > n) return fail(a, THM_ERR_INTERNAL, "thm_pileup: %llu keys among %llu events", n_keys, (unsigned long long)n);
   HIPCHK(a, c->head_at.ensure(n_keys + 1));
@@ -131,7 +136,7 @@ int merge_rows(thm_pileup* c, const char* who, uint64_t n_red, bool* swap, uint6
   p.new_at = c->new_at;
   HIPCHK(a, launch_pile_lookup(p, st));
   unsigned long long n_new = 0;
-  if (const int rc = scan_u64(a, c->scan_tmp, p.is_new, c->new_at, n_red, st, &n_new); rc != THM_OK) return rc;
+  if (const int rc = scan_u64(a, c->tiles.scan_tmp, p.is_new, c->new_at, n_red, st, &n_new); rc != THM_OK) return rc;
   HIPCHK(a, hipStreamSynchronize(st));
   if (n_new > n_red) return fail(a, THM_ERR_INTERNAL, "thm_pileup: %llu new keys among %llu rows", n_new, (unsigned long long)n_red);
   const uint64_t n_cat = n_tab + n_new;
@@ -185,11 +190,9 @@ int add_batch(thm_pileup* c, const char* who, int refused, PileBatch b, thm_pile
   if (n_alns > 0xFFFFFFFFull - c->totals.n_alns)
     return fail(a, THM_ERR_INVALID_ARG, "%s: %llu alignments behind the %llu counted would be more than 2^32-1: a depth could wrap", who,
                 (unsigned long long)n_alns, (unsigned long long)c->totals.n_alns);
-  b.n_refs = (uint32_t)a->ix->refs.size();
-  b.n_sq = c->n_sq;
+  b.n_sq = c->sq.n_sq;
   b.flags = c->flags;
-  b.ref_sq = a->bam.ref_sq;
-  b.base = c->base;
+  b.base = c->sq.base;
   b.tstart = c->tstart;
   b.text = text_of(a);
   HIPCHK(a, ensure_events(c->ev));
@@ -197,28 +200,28 @@ int add_batch(thm_pileup* c, const char* who, int refused, PileBatch b, thm_pile
   HIPCHK(a, c->ev_off.ensure(n_alns + 2));
   HIPCHK(a, c->aln_read.ensure(n_alns + 1));
   HIPCHK(a, c->used.ensure(n_alns, 16));
-  HIPCHK(a, c->d_tot.ensure((pile::N_TOTALS + 1) * 8));
+  HIPCHK(a, c->tot.reserve());
   PileCountParams cp;
   cp.b = b;
   cp.ev_cnt = c->ev_cnt;
   cp.aln_read = c->aln_read;
   cp.used = c->used;
-  cp.totals = c->d_tot.as<unsigned long long>();
-  cp.bad = cp.totals + pile::N_TOTALS;
+  cp.totals = c->tot.totals();
+  cp.bad = c->tot.bad();
   HIPCHK(a, hipEventRecord(c->ev[0], st));
-  HIPCHK(a, hipMemsetAsync(cp.totals, 0, pile::N_TOTALS * 8, st));
-  HIPCHK(a, hipMemsetAsync(cp.bad, 0xff, 8, st));
+  HIPCHK(a, c->tot.clear(st));
   HIPCHK(a, launch_pile_count(cp, a->n_cu, st));
-  unsigned long long h_tot[pile::N_TOTALS + 1], n_events = 0;
+  unsigned long long n_events = 0;
   if (n_alns) {
-    if (const int rc = scan_u64(a, c->scan_tmp, cp.ev_cnt, c->ev_off, n_alns, st, &n_events); rc != THM_OK) return rc;
+    if (const int rc = scan_u64(a, c->tiles.scan_tmp, cp.ev_cnt, c->ev_off, n_alns, st, &n_events); rc != THM_OK) return rc;
   }
-  HIPCHK(a, hipMemcpyAsync(h_tot, cp.totals, sizeof h_tot, hipMemcpyDeviceToHost, st));
+  HIPCHK(a, c->tot.fetch(st));
   HIPCHK(a, hipStreamSynchronize(st));
-  if (h_tot[pile::N_TOTALS] != ~0ull)
+  const unsigned long long* h_tot = c->tot.h;
+  if (c->tot.refused())
     return fail(a, refused,
                 "%s: alignment %llu has a ref without an @SQ line, a CIGAR range outside the pool, ends beyond its contig, or its M + I + S is not its read's length",
-                who, h_tot[pile::N_TOTALS]);
+                who, c->tot.first_bad());
   if (h_tot[pile::T_ALNS] != n_alns) return fail(a, THM_ERR_INTERNAL, "%s: %llu alignments counted of %llu", who, h_tot[pile::T_ALNS], (unsigned long long)n_alns);
   if (n_events != h_tot[pile::T_MISMATCHES] + h_tot[pile::T_DEL_BASES] + h_tot[pile::T_INS])
     return fail(a, THM_ERR_INTERNAL, "%s: %llu events scanned, %llu counted", who, n_events,
@@ -247,83 +250,35 @@ int add_batch(thm_pileup* c, const char* who, int refused, PileBatch b, thm_pile
   if (swap) c->cur ^= 1;
   c->n_tab = n_merged;
   (void)elapsed_ms(c->ev[0], c->ev[1], &info->add_ms);
-  uint64_t* batch = (uint64_t*)&info->batch;
-  uint64_t* total = (uint64_t*)&c->totals;
-  for (int k = 0; k < pile::N_TOTALS; k++) {
-    batch[k] = h_tot[k];
-    total[k] += h_tot[k];
-  }
+  c->tot.accumulate(&info->batch, &c->totals);
   info->n_events = c->n_tab;
   info->held_bytes = c->held_bytes();
   return THM_OK;
 }
 
-// the checks of thm_pileup_add_view, on the host before anything goes up
+// the checks of thm_pileup_add_view, on the host before anything goes up: the reads' offsets, then the view
 int check_view(thm_pileup* c, const thm_cigar_view* v, const uint8_t* bases, const uint64_t* base_off) {
   thm_aligner* a = c->a;
   const char* who = "thm_pileup_add_view";
-  const thm_index* ix = a->ix;
-  const uint64_t n = v->n_reads, n_alns = v->n_alns, n_words = v->n_cigar_words;
-  if ((n && (!v->read_aln_off || !base_off)) || (n_alns && (!v->alns || !v->digests || !n)) || (n_words && !v->cigar))
-    return fail(a, THM_ERR_INVALID_ARG, "%s: null offsets, alignments, digests or words", who);
+  const uint64_t n = v->n_reads;
   if (n) {
-    if (v->read_aln_off[0] != 0) return fail(a, THM_ERR_INVALID_ARG, "%s: read_aln_off[0] must be 0", who);
+    if (!base_off) return fail(a, THM_ERR_INVALID_ARG, "%s: null offsets, alignments, digests or words", who);
     if (base_off[0] != 0) return fail(a, THM_ERR_INVALID_ARG, "%s: base_off[0] must be 0", who);
-    for (uint64_t r = 0; r < n; r++) {
-      if (v->read_aln_off[r + 1] < v->read_aln_off[r]) return fail(a, THM_ERR_INVALID_ARG, "%s: the offsets descend at read %llu", who, (unsigned long long)r);
+    for (uint64_t r = 0; r < n; r++)
       if (base_off[r + 1] < base_off[r]) return fail(a, THM_ERR_INVALID_ARG, "%s: base_off descends at read %llu", who, (unsigned long long)r);
-    }
-    if (v->read_aln_off[n] != n_alns)
-      return fail(a, THM_ERR_INVALID_ARG, "%s: the offsets end at %llu, the view has %llu alignments", who, (unsigned long long)v->read_aln_off[n], (unsigned long long)n_alns);
     if (base_off[n] && !bases) return fail(a, THM_ERR_INVALID_ARG, "%s: null bases", who);
   }
-  uint64_t r = 0;
-  for (uint64_t i = 0; i < n_alns; i++) {
-    const thm_aln& al = v->alns[i];
-    const thm_aln_digest& d = v->digests[i];
-    const unsigned long long at = i;
+  uint64_t r = 0;  // the read of alignment i: the alignments come in the order of their reads
+  return check_cigar_view(a, who, v, c->sq.h_ref_sq, [&](uint64_t i, const thm_aln& al, const thm_aln_digest& d) {
     while (v->read_aln_off[r + 1] <= i) r++;
-    if (al.aln_type > THM_ALN_INTERGENIC) return fail(a, THM_ERR_INVALID_ARG, "%s: alignment %llu: aln_type %u is none", who, at, (unsigned)al.aln_type);
-    if (al.aln_type == THM_ALN_EXONIC && al.tx_or_gene_idx >= ix->txs.size())
-      return fail(a, THM_ERR_INVALID_ARG, "%s: alignment %llu: tx_or_gene_idx %u is outside the index's %zu transcripts", who, at, al.tx_or_gene_idx, ix->txs.size());
-    if (al.aln_type == THM_ALN_INTRONIC && al.tx_or_gene_idx >= ix->genes.size())
-      return fail(a, THM_ERR_INVALID_ARG, "%s: alignment %llu: tx_or_gene_idx %u is outside the index's %zu genes", who, at, al.tx_or_gene_idx, ix->genes.size());
-    if (al.ref_id >= c->h_ref_sq.size() || c->h_ref_sq[al.ref_id] < 0 || (uint32_t)c->h_ref_sq[al.ref_id] >= c->n_sq)
-      return fail(a, THM_ERR_INVALID_ARG, "%s: alignment %llu: ref_id %u has no @SQ line", who, at, al.ref_id);
-    if (d.cigar_off > n_words || d.n_cigar > n_words - d.cigar_off)
-      return fail(a, THM_ERR_INVALID_ARG, "%s: alignment %llu: CIGAR words [%llu, +%u) are outside the pool of %llu", who, at, (unsigned long long)d.cigar_off, d.n_cigar,
-                  (unsigned long long)n_words);
-    const uint32_t s = (uint32_t)c->h_ref_sq[al.ref_id];
-    const uint64_t len = c->h_base[s + 1] - c->h_base[s] - 1;
-    if (al.ystart > len || d.ref_len > len - al.ystart)
-      return fail(a, THM_ERR_INVALID_ARG, "%s: alignment %llu: position %llu + %llu lies beyond the %llu bases of its contig", who, at, (unsigned long long)al.ystart,
-                  (unsigned long long)d.ref_len, (unsigned long long)len);
-    if ((d.flags & THM_DIGEST_LONG_RUN) || d.n_cigar == 0) continue;
+    if (const int rc = c->sq.check_contig(a, who, i, al, d.ref_len); rc != THM_OK) return rc;
+    if ((d.flags & THM_DIGEST_LONG_RUN) || d.n_cigar == 0) return (int)THM_OK;
     const pile::Shape sh = pile::shape_of(v->cigar + d.cigar_off, d.n_cigar, al.ystart);
     if (sh.qlen != base_off[r + 1] - base_off[r])
-      return fail(a, THM_ERR_INVALID_ARG, "%s: alignment %llu: its M + I + S is %llu, read %llu has %llu bases", who, at, (unsigned long long)sh.qlen,
-                  (unsigned long long)r, (unsigned long long)(base_off[r + 1] - base_off[r]));
-  }
-  return THM_OK;
-}
-
-// tile sums of diff[0, n) (entries from a contig's first on) and their scan, with coverage's tile kernel, which reads
-// diff and n of its parameters and writes tile_sum and tile_cnt: the other fields stay zero
-int tile_pass(thm_pileup* c, const uint32_t* diff, uint64_t n) {
-  thm_aligner* a = c->a;
-  hipStream_t st = a->stream;
-  const uint64_t nt = cov::n_tiles(n);
-  HIPCHK(a, c->tile_sum.ensure(nt + 1));
-  HIPCHK(a, c->tile_cnt.ensure(nt + 1));
-  HIPCHK(a, c->carry.ensure(nt + 2));
-  CovTileParams tp;
-  memset(&tp, 0, sizeof tp);
-  tp.diff = diff;
-  tp.n = n;
-  tp.tile_sum = c->tile_sum;
-  tp.tile_cnt = c->tile_cnt;
-  HIPCHK(a, launch_cov_tiles(tp, st));
-  return scan_u64(a, c->scan_tmp, c->tile_sum, c->carry, nt, st);
+      return fail(a, THM_ERR_INVALID_ARG, "%s: alignment %llu: its M + I + S is %llu, read %llu has %llu bases", who, (unsigned long long)i,
+                  (unsigned long long)sh.qlen, (unsigned long long)r, (unsigned long long)(base_off[r + 1] - base_off[r]));
+    return (int)THM_OK;
+  });
 }
 
 // the rows of the entries [e0, e1) of the layout -> p.r0, p.r1; synchronises the stream
@@ -336,10 +291,10 @@ int row_bounds(thm_pileup* c, PileFetchParams& p, uint64_t e0, uint64_t e1) {
   p.n_tab = c->n_tab;
   p.e0 = e0;
   p.e1 = e1;
-  p.base = c->base;
+  p.base = c->sq.base;
   p.tstart = c->tstart;
   p.text = text_of(a);
-  p.n_sq = c->n_sq;
+  p.n_sq = c->sq.n_sq;
   if (c->n_tab == 0) return THM_OK;
   HIPCHK(a, c->bounds.ensure(2));
   p.bounds = c->bounds;
@@ -372,12 +327,10 @@ int32_t thm_pileup_create(thm_aligner* a, uint32_t flags, uint64_t max_bytes, th
   c->a = a;
   c->flags = flags;
   c->max_bytes = max_bytes;
-  c->n_sq = (uint32_t)sq.size();
   memset(&c->totals, 0, sizeof c->totals);
-  c->h_base.assign(sq.size() + 1, 0);
-  for (size_t s = 0; s < sq.size(); s++) c->h_base[s + 1] = c->h_base[s] + sq[s].second + 1;
+  c->sq.lay_out(sq);
   const uint64_t entries = c->entries();
-  const unsigned long long need = entries * 4 + c->h_base.size() * 8 + sq.size() * 8;
+  const unsigned long long need = entries * 4 + c->sq.h_base.size() * 8 + sq.size() * 8;
   c->array_bytes = need;
   if (max_bytes && need > max_bytes) {
     delete c;
@@ -396,19 +349,11 @@ int32_t thm_pileup_create(thm_aligner* a, uint32_t flags, uint64_t max_bytes, th
       delete c;
       return fail(a, THM_ERR_INVALID_ARG, "thm_pileup_create: the text holds no forward copy of contig %s", sq[s].first.c_str());
     }
-  const size_t n_refs = ix->refs.size();
-  c->h_ref_sq.assign(n_refs, -1);
-  // (allocated to the byte: the arrays are the object's size, not a buffer that grows)
-  hipError_t e = hipMalloc(&c->base.b.p, c->h_base.size() * 8);
-  if (e == hipSuccess) c->base.b.cap = c->h_base.size() * 8;
-  if (e == hipSuccess) e = hipMalloc(&c->tstart.b.p, tstart.size() * 8);
-  if (e == hipSuccess) c->tstart.b.cap = tstart.size() * 8;
-  if (e == hipSuccess) e = hipMalloc(&c->diff.b.p, entries * 4 + 16);
-  if (e == hipSuccess) c->diff.b.cap = entries * 4 + 16;
-  if (e == hipSuccess) e = hipMemcpy(c->base, c->h_base.data(), c->h_base.size() * 8, hipMemcpyHostToDevice);
+  hipError_t e = c->sq.on_device(a);
+  if (e == hipSuccess) e = alloc_exact(c->tstart, tstart.size() * 8);
+  if (e == hipSuccess) e = alloc_exact(c->diff, entries * 4 + 16);
   if (e == hipSuccess) e = hipMemcpy(c->tstart, tstart.data(), tstart.size() * 8, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemset(c->diff, 0, entries * 4 + 16);
-  if (e == hipSuccess && n_refs) e = hipMemcpy(c->h_ref_sq.data(), a->bam.ref_sq, n_refs * 4, hipMemcpyDeviceToHost);
   if (e != hipSuccess) {
     delete c;
     return fail(a, e == hipErrorOutOfMemory ? THM_ERR_OOM : THM_ERR_HIP, "thm_pileup_create: %s (%llu bytes needed, the cap is %llu)", hipGetErrorString(e), need,
@@ -418,44 +363,14 @@ int32_t thm_pileup_create(thm_aligner* a, uint32_t flags, uint64_t max_bytes, th
   return THM_OK;
 }
 
-void thm_pileup_free(thm_pileup* c) {
-  if (!c) return;
-  int cur = 0;
-  (void)hipGetDevice(&cur);
-  (void)hipSetDevice(c->a->device);
-  (void)hipStreamSynchronize(c->a->stream);
-  delete c;
-  (void)hipSetDevice(cur);
-}
+void thm_pileup_free(thm_pileup* c) { free_summary(c); }
 
 int32_t thm_pileup_add(thm_pileup* c, thm_pile_info* info) {
   if (!c || !info) return THM_ERR_INVALID_ARG;
   memset(info, 0, sizeof(*info));
   thm_aligner* a = c->a;
-  int rc = thm_batch_sync(a);
-  if (rc != THM_OK) return rc;
-  HIPCHK(a, hipSetDevice(a->device));
-  BatchSizes z;
-  rc = fetch_batch_sizes(a, nullptr, nullptr, nullptr, &z);
-  if (rc != THM_OK) return rc;
-  // the two CIGAR passes, as thm_batch_fetch_cigars runs them (THM_T_CIGAR belongs to that call)
-  uint64_t n_words = 0;
-  unsigned any_flags = 0;
-  const float t_cigar = a->timings[THM_T_CIGAR];
-  rc = run_cigar_passes(a, compacted_cigar_params(a, z), z.n_alns, &n_words, &any_flags);
-  a->timings[THM_T_CIGAR] = t_cigar;
-  if (rc != THM_OK) return rc;
-  if (any_flags & THM_DIGEST_MALFORMED) return fail(a, THM_ERR_INTERNAL, "malformed op stream in the compacted pool");
-  PileBatch b;
-  memset(&b, 0, sizeof b);
-  b.n_reads = a->n_reads;
-  b.n_alns = z.n_alns;
-  b.n_words = n_words;
-  b.aln_off = a->ext.aln_off;
-  b.alns = a->out.alns;
-  b.digests = a->cig.dig;
-  b.words = a->cig.words;
-  b.status = z.any_failed ? a->reads.status : nullptr;
+  PileBatch b{};
+  if (const int rc = resident_batch(a, &b); rc != THM_OK) return rc;
   b.bases = a->reads.bases;
   b.base_off = a->reads.offsets;
   return add_batch(c, "thm_pileup_add", THM_ERR_INTERNAL, b, info);
@@ -467,37 +382,18 @@ int32_t thm_pileup_add_view(thm_pileup* c, const thm_cigar_view* v, const uint8_
   thm_aligner* a = c->a;
   int rc = check_view(c, v, bases, base_off);
   if (rc != THM_OK) return rc;
-  HIPCHK(a, hipSetDevice(a->device));
-  hipStream_t st = a->stream;
-  const uint64_t n = v->n_reads, n_alns = v->n_alns, n_words = v->n_cigar_words, n_bases = n ? base_off[n] : 0;
+  const uint64_t n = v->n_reads, n_bases = n ? base_off[n] : 0;
   const uint64_t zero = 0;
-  HIPCHK(a, c->v_off.ensure(n + 1));
-  HIPCHK(a, c->v_base_off.ensure(n + 1));
-  HIPCHK(a, c->v_alns.ensure(n_alns + 1));
-  HIPCHK(a, c->v_dig.ensure(n_alns + 1));
-  HIPCHK(a, c->v_words.ensure(n_words + 4));
-  HIPCHK(a, c->v_bases.ensure(n_bases + 16));
-  HIPCHK(a, hipMemcpyAsync(c->v_off, n ? v->read_aln_off : &zero, (n + 1) * 8, hipMemcpyHostToDevice, st));
-  HIPCHK(a, hipMemcpyAsync(c->v_base_off, n ? base_off : &zero, (n + 1) * 8, hipMemcpyHostToDevice, st));
-  if (n_alns) HIPCHK(a, hipMemcpyAsync(c->v_alns, v->alns, n_alns * sizeof(thm_aln), hipMemcpyHostToDevice, st));
-  if (n_alns) HIPCHK(a, hipMemcpyAsync(c->v_dig, v->digests, n_alns * sizeof(thm_aln_digest), hipMemcpyHostToDevice, st));
-  if (n_words) HIPCHK(a, hipMemcpyAsync(c->v_words, v->cigar, n_words * 4, hipMemcpyHostToDevice, st));
-  if (n_bases) HIPCHK(a, hipMemcpyAsync(c->v_bases, bases, n_bases, hipMemcpyHostToDevice, st));
-  if (v->read_status && n) {
-    HIPCHK(a, c->v_stat.ensure(n));
-    HIPCHK(a, hipMemcpyAsync(c->v_stat, v->read_status, n * 4, hipMemcpyHostToDevice, st));
-  }
-  HIPCHK(a, hipStreamSynchronize(st));  // (`zero` and the caller's arrays have been read)
-  PileBatch b;
-  memset(&b, 0, sizeof b);
-  b.n_reads = n;
-  b.n_alns = n_alns;
-  b.n_words = n_words;
-  b.aln_off = c->v_off;
-  b.alns = c->v_alns;
-  b.digests = c->v_dig;
-  b.words = c->v_words;
-  b.status = v->read_status && n ? c->v_stat.get() : nullptr;
+  PileBatch b{};
+  rc = c->view.upload(a, v, &b, [&] {
+    hipStream_t st = a->stream;
+    HIPCHK(a, c->v_base_off.ensure(n + 1));
+    HIPCHK(a, c->v_bases.ensure(n_bases + 16));
+    HIPCHK(a, hipMemcpyAsync(c->v_base_off, n ? base_off : &zero, (n + 1) * 8, hipMemcpyHostToDevice, st));
+    if (n_bases) HIPCHK(a, hipMemcpyAsync(c->v_bases, bases, n_bases, hipMemcpyHostToDevice, st));
+    return (int)THM_OK;
+  });
+  if (rc != THM_OK) return rc;
   b.bases = c->v_bases;
   b.base_off = c->v_base_off;
   return add_batch(c, "thm_pileup_add_view", THM_ERR_INVALID_ARG, b, info);
@@ -508,12 +404,12 @@ int32_t thm_pileup_fetch(thm_pileup* c, uint32_t first_ref, uint32_t n_refs, uin
   memset(out, 0, sizeof(*out));
   thm_aligner* a = c->a;
   if (min_alt == 0) return fail(a, THM_ERR_INVALID_ARG, "thm_pileup_fetch: min_alt must be 1 or more (thm_pileup_window returns every position)");
-  if (first_ref > c->n_sq || n_refs > c->n_sq - first_ref)
-    return fail(a, THM_ERR_INVALID_ARG, "thm_pileup_fetch: @SQ entries [%u, +%u) of %u", first_ref, n_refs, c->n_sq);
+  if (first_ref > c->sq.n_sq || n_refs > c->sq.n_sq - first_ref)
+    return fail(a, THM_ERR_INVALID_ARG, "thm_pileup_fetch: @SQ entries [%u, +%u) of %u", first_ref, n_refs, c->sq.n_sq);
   HIPCHK(a, hipSetDevice(a->device));
   hipStream_t st = a->stream;
   HIPCHK(a, ensure_events(c->ev_fetch));
-  const uint64_t g0 = c->h_base[first_ref], g1 = c->h_base[first_ref + n_refs];
+  const uint64_t g0 = c->sq.h_base[first_ref], g1 = c->sq.h_base[first_ref + n_refs];
   HIPCHK(a, hipEventRecord(c->ev_fetch[0], st));
   PileFetchParams p;
   if (const int rc = row_bounds(c, p, g0, g1); rc != THM_OK) return rc;
@@ -526,19 +422,19 @@ int32_t thm_pileup_fetch(thm_pileup* c, uint32_t first_ref, uint32_t n_refs, uin
     p.keep = c->keep;
     p.site_at = c->site_at;
     HIPCHK(a, launch_pile_keep(p, st));
-    if (const int rc = scan_u64(a, c->scan_tmp, p.keep, c->site_at, n_rows, st, &n_sites); rc != THM_OK) return rc;
+    if (const int rc = scan_u64(a, c->tiles.scan_tmp, p.keep, c->site_at, n_rows, st, &n_sites); rc != THM_OK) return rc;
     HIPCHK(a, hipStreamSynchronize(st));
     if (n_sites > n_rows) return fail(a, THM_ERR_INTERNAL, "thm_pileup_fetch: %llu sites from %llu rows", n_sites, (unsigned long long)n_rows);
   }
   HIPCHK(a, c->h_out.ensure(n_sites * sizeof(thm_pile_site) + 16));
   if (n_sites) {
     HIPCHK(a, c->d_sites.ensure(n_sites));
-    if (const int rc = tile_pass(c, c->diff + g0, g1 - g0); rc != THM_OK) return rc;
+    if (const int rc = tile_pass(a, c->tiles, c->diff + g0, g1 - g0, false); rc != THM_OK) return rc;
     p.n_sites = n_sites;
     p.diff = c->diff + g0;
     p.n = g1 - g0;
     p.g0 = g0;
-    p.carry = c->carry;
+    p.carry = c->tiles.carry;
     p.sites = c->d_sites;
     HIPCHK(a, launch_pile_sites(p, st));
     HIPCHK(a, hipMemcpyAsync(c->h_out.p, c->d_sites, n_sites * sizeof(thm_pile_site), hipMemcpyDeviceToHost, st));
@@ -560,8 +456,8 @@ int32_t thm_pileup_window(thm_pileup* c, uint32_t ref_id, uint64_t start, uint64
   if (!c || !out) return THM_ERR_INVALID_ARG;
   memset(out, 0, sizeof(*out));
   thm_aligner* a = c->a;
-  if (ref_id >= c->n_sq) return fail(a, THM_ERR_INVALID_ARG, "thm_pileup_window: refID %u of %u", ref_id, c->n_sq);
-  const uint64_t g0 = c->h_base[ref_id], len = c->h_base[ref_id + 1] - g0 - 1;
+  if (ref_id >= c->sq.n_sq) return fail(a, THM_ERR_INVALID_ARG, "thm_pileup_window: refID %u of %u", ref_id, c->sq.n_sq);
+  const uint64_t g0 = c->sq.h_base[ref_id], len = c->sq.len(ref_id);
   if (n > pile::MAX_WINDOW || start > len || n > len - start)
     return fail(a, THM_ERR_INVALID_ARG, "thm_pileup_window: the window [%llu, +%llu) must hold at most 2^20 bases and lie inside the %llu bases of refID %u",
                 (unsigned long long)start, (unsigned long long)n, (unsigned long long)len, ref_id);
@@ -574,11 +470,11 @@ int32_t thm_pileup_window(thm_pileup* c, uint32_t ref_id, uint64_t start, uint64
   if (const int rc = row_bounds(c, p, g0 + start, g0 + start + n); rc != THM_OK) return rc;
   if (n) {
     HIPCHK(a, c->d_sites.ensure(n));
-    if (const int rc = tile_pass(c, c->diff + g0, start + n); rc != THM_OK) return rc;
+    if (const int rc = tile_pass(a, c->tiles, c->diff + g0, start + n, false); rc != THM_OK) return rc;
     p.diff = c->diff + g0;
     p.n = start + n;
     p.g0 = g0;
-    p.carry = c->carry;
+    p.carry = c->tiles.carry;
     p.start = start;
     p.sites = c->d_sites;
     HIPCHK(a, launch_pile_window(p, st));

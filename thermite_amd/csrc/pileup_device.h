@@ -76,19 +76,14 @@ COV_HD Shape shape_of(const uint32_t* words, uint32_t n, uint64_t ystart) {
 // the position an I word is observed at, the walk standing at p
 COV_HD uint64_t ins_pos(uint64_t p, uint64_t ystart) { return p > ystart ? p - 1 : ystart; }
 
-// The device's checks of one alignment, before anything is touched: cov::check_aln's -- the ref has a refID below n_sq,
-// the words lie inside the pool, the walk from ystart ends inside the contig -- and, for an alignment with words, that
-// they consume the read_len bytes of its read.  *sq gets the refID, *shape what the words add up to.
+// The device's checks of one alignment, before anything is touched: cov::locate_aln's, the walk from ystart ends inside
+// the contig, and, for an alignment with words, they consume the read_len bytes of its read.  *sq gets the refID, *shape
+// what the words add up to.
 COV_HD bool check_aln(uint32_t ref_id, uint64_t ystart, uint64_t cigar_off, uint32_t n_cigar, bool long_run, const uint32_t* words, uint64_t n_words,
                       const int32_t* ref_sq, uint32_t n_refs, const uint64_t* base, uint32_t n_sq, uint64_t read_len, uint32_t* sq, Shape* shape) {
   *shape = Shape{ystart, 0, 0, 0, 0, 0, 0};
-  if (ref_id >= n_refs) return false;
-  const int32_t s = ref_sq[ref_id];
-  if (s < 0 || (uint32_t)s >= n_sq) return false;
-  *sq = (uint32_t)s;
-  if (cigar_off > n_words || (uint64_t)n_cigar > n_words - cigar_off) return false;
-  const uint64_t len = base[s + 1] - base[s] - 1;
-  if (ystart > len) return false;
+  const uint64_t len = cov::locate_aln(ref_id, ystart, cigar_off, n_cigar, n_words, ref_sq, n_refs, base, n_sq, sq);
+  if (len == cov::NOT_LOCATED) return false;
   if (long_run || n_cigar == 0) return true;
   *shape = shape_of(words + cigar_off, n_cigar, ystart);
   return shape->end <= len && shape->qlen == read_len;

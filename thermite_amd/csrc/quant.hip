@@ -2,7 +2,12 @@
 // the device over its batches from what is resident after thm_batch_run -- the compacted thm_aln records, the per-read
 // offsets, the CIGAR words and digests of the CIGAR passes, and the tx -> gene and ref -> @SQ tables of the BAM encoder.
 // Only totals and the finished tables come back to the host.  The kernels are kernels_quant.hip, the per-alignment
-// functions quant_device.h; DESIGN.md section 4.17.
+// functions quant_device.h; the batch, the view's upload and checks and the totals are run_summary.h's, shared with
+// coverage.hip and pileup.hip.  DESIGN.md sections 4.17 and 4.20.
+//
+// Synchronisations of the stream.  add: thm_batch_sync's, one of fetch_batch_sizes, one of the CIGAR passes, one behind
+// the count pass, with hits one in sort_reduce, one in merge_rows and with new keys one more in its sort_reduce, one
+// behind the gene pass.  add_view: one behind the upload, then as add from the count pass on.  fetch: one.  reset: one.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -11,6 +16,7 @@
 #include "aligner_internal.h"
 #include "launch_io.h"
 #include "quant_device.h"
+#include "run_summary.h"
 
 using namespace thm;
 
@@ -57,22 +63,16 @@ struct thm_quant {
   DArr<uint64_t> hit_cnt, hit_off, scan_tmp, key_a, key_b, flag, first, is_new, new_at;
   DArr<uint8_t> multi;
   DArr<uint32_t> perm_a, perm_b, where;
-  DBuf d_tot;    // the totals (unsigned long long) and behind them the `bad` word
+  BatchTotals<quant::N_TOTALS> tot;
   DBuf cub_tmp;  // hipcub's scratch
-  // the view thm_quant_add_view uploads
-  DArr<uint64_t> v_off;
-  DArr<thm_aln> v_alns;
-  DArr<thm_aln_digest> v_dig;
-  DArr<uint32_t> v_words;
-  DArr<int32_t> v_stat;
+  AlnView view;  // what thm_quant_add_view uploads
   DArr<thm_quant_junction> d_rows;  // the table as records, for the fetch
   HBuf h_out;                       // the genes, and behind them the junctions
   Event ev[2], ev_fetch[2];
 
   uint64_t held_bytes() const {
-    return tab[0].bytes() + tab[1].bytes() + hits.bytes() + red.bytes() + cat.bytes() + d_tot.cap + cub_tmp.cap +
-           held(tx_forward, genes, d_rows, hit_cnt, hit_off, multi, scan_tmp, perm_a, perm_b, key_a, key_b, flag, first, where, is_new, new_at,
-                v_off, v_alns, v_dig, v_words, v_stat);
+    return tab[0].bytes() + tab[1].bytes() + hits.bytes() + red.bytes() + cat.bytes() + tot.d.cap + cub_tmp.cap +
+           held(tx_forward, genes, d_rows, hit_cnt, hit_off, multi, scan_tmp, perm_a, perm_b, key_a, key_b, flag, first, where, is_new, new_at, view);
   }
 };
 
@@ -182,36 +182,34 @@ int add_batch(thm_quant* q, const char* who, QuantBatch b, thm_quant_info* info)
   const thm_index* ix = a->ix;
   const uint64_t n_alns = b.n_alns;
   if (n_alns >= MAX_ROWS) return fail(a, THM_ERR_UNSUPPORTED, "%s: 2^32-2 alignments or more in one batch", who);
-  b.n_refs = (uint32_t)ix->refs.size();
   b.n_txs = (uint32_t)ix->txs.size();
   b.n_genes = (uint32_t)ix->genes.size();
   b.tx_gene = a->bam.tx_gene;
   b.tx_forward = q->tx_forward;
-  b.ref_sq = a->bam.ref_sq;
   HIPCHK(a, ensure_events(q->ev));
   HIPCHK(a, q->hit_cnt.ensure(n_alns + 1));
   HIPCHK(a, q->hit_off.ensure(n_alns + 2));
   HIPCHK(a, q->multi.ensure(n_alns, 16));
   HIPCHK(a, scan_reserve(q->scan_tmp, n_alns));
-  HIPCHK(a, q->d_tot.ensure((quant::N_TOTALS + 1) * 8));
+  HIPCHK(a, q->tot.reserve());
   QuantCountParams cp;
   cp.b = b;
   cp.hit_cnt = q->hit_cnt;
   cp.multi = q->multi;
-  cp.totals = q->d_tot.as<unsigned long long>();
-  cp.bad = cp.totals + quant::N_TOTALS;
+  cp.totals = q->tot.totals();
+  cp.bad = q->tot.bad();
   HIPCHK(a, hipEventRecord(q->ev[0], st));
-  HIPCHK(a, hipMemsetAsync(cp.totals, 0, quant::N_TOTALS * 8, st));
-  HIPCHK(a, hipMemsetAsync(cp.bad, 0xff, 8, st));
+  HIPCHK(a, q->tot.clear(st));
   HIPCHK(a, launch_quant_count(cp, a->n_cu, st));
-  unsigned long long h_tot[quant::N_TOTALS + 1], n_hits = 0;
+  unsigned long long n_hits = 0;
   if (n_alns) {
     if (const int rc = scan_u64(a, q->scan_tmp, cp.hit_cnt, q->hit_off, n_alns, st, &n_hits); rc != THM_OK) return rc;
   }
-  HIPCHK(a, hipMemcpyAsync(h_tot, cp.totals, sizeof h_tot, hipMemcpyDeviceToHost, st));
+  HIPCHK(a, q->tot.fetch(st));
   HIPCHK(a, hipStreamSynchronize(st));
-  if (h_tot[quant::N_TOTALS] != ~0ull)
-    return fail(a, THM_ERR_INTERNAL, "%s: alignment %llu has an index, a CIGAR range or an intron outside the index's tables", who, h_tot[quant::N_TOTALS]);
+  const unsigned long long* h_tot = q->tot.h;
+  if (q->tot.refused())
+    return fail(a, THM_ERR_INTERNAL, "%s: alignment %llu has an index, a CIGAR range or an intron outside the index's tables", who, q->tot.first_bad());
   if (n_hits != h_tot[quant::T_HITS]) return fail(a, THM_ERR_INTERNAL, "%s: %llu hits scanned, %llu counted", who, n_hits, h_tot[quant::T_HITS]);
   if (n_hits > MAX_ROWS) return fail(a, THM_ERR_UNSUPPORTED, "%s: more than 2^32-2 junction hits in one batch", who);
   if (n_hits) {
@@ -237,12 +235,7 @@ int add_batch(thm_quant* q, const char* who, QuantBatch b, thm_quant_info* info)
   HIPCHK(a, hipEventRecord(q->ev[1], st));
   HIPCHK(a, hipStreamSynchronize(st));
   (void)elapsed_ms(q->ev[0], q->ev[1], &info->add_ms);
-  uint64_t* batch = (uint64_t*)&info->batch;
-  uint64_t* total = (uint64_t*)&q->totals;
-  for (int k = 0; k < quant::N_TOTALS; k++) {
-    batch[k] = h_tot[k];
-    total[k] += h_tot[k];
-  }
+  q->tot.accumulate(&info->batch, &q->totals);
   info->n_junctions = q->n_tab;
   info->held_bytes = q->held_bytes();
   return THM_OK;
@@ -252,40 +245,17 @@ int add_batch(thm_quant* q, const char* who, QuantBatch b, thm_quant_info* info)
 int check_view(thm_quant* q, const thm_cigar_view* v) {
   thm_aligner* a = q->a;
   const char* who = "thm_quant_add_view";
-  const thm_index* ix = a->ix;
-  const uint64_t n = v->n_reads, n_alns = v->n_alns, n_words = v->n_cigar_words;
-  if ((n && !v->read_aln_off) || (n_alns && (!v->alns || !v->digests || !n)) || (n_words && !v->cigar))
-    return fail(a, THM_ERR_INVALID_ARG, "%s: null offsets, alignments, digests or words", who);
-  if (n) {
-    if (v->read_aln_off[0] != 0) return fail(a, THM_ERR_INVALID_ARG, "%s: read_aln_off[0] must be 0", who);
-    for (uint64_t r = 0; r < n; r++)
-      if (v->read_aln_off[r + 1] < v->read_aln_off[r]) return fail(a, THM_ERR_INVALID_ARG, "%s: the offsets descend at read %llu", who, (unsigned long long)r);
-    if (v->read_aln_off[n] != n_alns)
-      return fail(a, THM_ERR_INVALID_ARG, "%s: the offsets end at %llu, the view has %llu alignments", who, (unsigned long long)v->read_aln_off[n], (unsigned long long)n_alns);
-  }
-  for (uint64_t i = 0; i < n_alns; i++) {
-    const thm_aln& al = v->alns[i];
-    const thm_aln_digest& d = v->digests[i];
+  return check_cigar_view(a, who, v, q->h_ref_sq, [&](uint64_t i, const thm_aln& al, const thm_aln_digest& d) {
+    if (d.flags & THM_DIGEST_LONG_RUN) return (int)THM_OK;
     const unsigned long long at = i;
-    if (al.aln_type > THM_ALN_INTERGENIC) return fail(a, THM_ERR_INVALID_ARG, "%s: alignment %llu: aln_type %u is none", who, at, (unsigned)al.aln_type);
-    if (al.aln_type == THM_ALN_EXONIC && al.tx_or_gene_idx >= ix->txs.size())
-      return fail(a, THM_ERR_INVALID_ARG, "%s: alignment %llu: tx_or_gene_idx %u is outside the index's %zu transcripts", who, at, al.tx_or_gene_idx, ix->txs.size());
-    if (al.aln_type == THM_ALN_INTRONIC && al.tx_or_gene_idx >= ix->genes.size())
-      return fail(a, THM_ERR_INVALID_ARG, "%s: alignment %llu: tx_or_gene_idx %u is outside the index's %zu genes", who, at, al.tx_or_gene_idx, ix->genes.size());
-    if (al.ref_id >= q->h_ref_sq.size() || q->h_ref_sq[al.ref_id] < 0)
-      return fail(a, THM_ERR_INVALID_ARG, "%s: alignment %llu: ref_id %u has no @SQ line", who, at, al.ref_id);
-    if (d.cigar_off > n_words || d.n_cigar > n_words - d.cigar_off)
-      return fail(a, THM_ERR_INVALID_ARG, "%s: alignment %llu: CIGAR words [%llu, +%u) are outside the pool of %llu", who, at, (unsigned long long)d.cigar_off, d.n_cigar,
-                  (unsigned long long)n_words);
-    if (d.flags & THM_DIGEST_LONG_RUN) continue;
     uint64_t span = 0;
     const uint32_t n_hits = quant::count_hits(v->cigar + d.cigar_off, d.n_cigar, &span);
     if (al.ystart > 0xFFFFFFFFull || al.ystart + span > 0xFFFFFFFFull)
       return fail(a, THM_ERR_INVALID_ARG, "%s: alignment %llu: position %llu + %llu is 2^32 or more", who, at, (unsigned long long)al.ystart, (unsigned long long)span);
     if (n_hits && al.aln_type != THM_ALN_EXONIC)
       return fail(a, THM_ERR_INVALID_ARG, "%s: alignment %llu: an N word in an alignment that is not exonic has no strand", who, at);
-  }
-  return THM_OK;
+    return (int)THM_OK;
+  });
 }
 
 }  // namespace
@@ -327,80 +297,23 @@ int32_t thm_quant_create(thm_aligner* a, thm_quant** out) {
   return THM_OK;
 }
 
-void thm_quant_free(thm_quant* q) {
-  if (!q) return;
-  int cur = 0;
-  (void)hipGetDevice(&cur);
-  (void)hipSetDevice(q->a->device);
-  (void)hipStreamSynchronize(q->a->stream);
-  delete q;
-  (void)hipSetDevice(cur);
-}
+void thm_quant_free(thm_quant* q) { free_summary(q); }
 
 int32_t thm_quant_add(thm_quant* q, thm_quant_info* info) {
   if (!q || !info) return THM_ERR_INVALID_ARG;
   memset(info, 0, sizeof(*info));
-  thm_aligner* a = q->a;
-  int rc = thm_batch_sync(a);
-  if (rc != THM_OK) return rc;
-  HIPCHK(a, hipSetDevice(a->device));
-  BatchSizes z;
-  rc = fetch_batch_sizes(a, nullptr, nullptr, nullptr, &z);
-  if (rc != THM_OK) return rc;
-  // the two CIGAR passes, as thm_batch_fetch_cigars runs them (THM_T_CIGAR belongs to that call)
-  uint64_t n_words = 0;
-  unsigned any_flags = 0;
-  const float t_cigar = a->timings[THM_T_CIGAR];
-  rc = run_cigar_passes(a, compacted_cigar_params(a, z), z.n_alns, &n_words, &any_flags);
-  a->timings[THM_T_CIGAR] = t_cigar;
-  if (rc != THM_OK) return rc;
-  if (any_flags & THM_DIGEST_MALFORMED) return fail(a, THM_ERR_INTERNAL, "malformed op stream in the compacted pool");
-  QuantBatch b;
-  memset(&b, 0, sizeof b);
-  b.n_reads = a->n_reads;
-  b.n_alns = z.n_alns;
-  b.n_words = n_words;
-  b.aln_off = a->ext.aln_off;
-  b.alns = a->out.alns;
-  b.digests = a->cig.dig;
-  b.words = a->cig.words;
-  b.status = z.any_failed ? a->reads.status : nullptr;
+  QuantBatch b{};
+  if (const int rc = resident_batch(q->a, &b); rc != THM_OK) return rc;
   return add_batch(q, "thm_quant_add", b, info);
 }
 
 int32_t thm_quant_add_view(thm_quant* q, const thm_cigar_view* v, thm_quant_info* info) {
   if (!q || !v || !info) return THM_ERR_INVALID_ARG;
   memset(info, 0, sizeof(*info));
-  thm_aligner* a = q->a;
+  QuantBatch b{};
   int rc = check_view(q, v);
+  if (rc == THM_OK) rc = q->view.upload(q->a, v, &b);
   if (rc != THM_OK) return rc;
-  HIPCHK(a, hipSetDevice(a->device));
-  hipStream_t st = a->stream;
-  const uint64_t n = v->n_reads, n_alns = v->n_alns, n_words = v->n_cigar_words;
-  const uint64_t zero = 0;
-  HIPCHK(a, q->v_off.ensure(n + 1));
-  HIPCHK(a, q->v_alns.ensure(n_alns + 1));
-  HIPCHK(a, q->v_dig.ensure(n_alns + 1));
-  HIPCHK(a, q->v_words.ensure(n_words + 4));
-  HIPCHK(a, hipMemcpyAsync(q->v_off, n ? v->read_aln_off : &zero, (n + 1) * 8, hipMemcpyHostToDevice, st));
-  if (n_alns) HIPCHK(a, hipMemcpyAsync(q->v_alns, v->alns, n_alns * sizeof(thm_aln), hipMemcpyHostToDevice, st));
-  if (n_alns) HIPCHK(a, hipMemcpyAsync(q->v_dig, v->digests, n_alns * sizeof(thm_aln_digest), hipMemcpyHostToDevice, st));
-  if (n_words) HIPCHK(a, hipMemcpyAsync(q->v_words, v->cigar, n_words * 4, hipMemcpyHostToDevice, st));
-  if (v->read_status && n) {
-    HIPCHK(a, q->v_stat.ensure(n));
-    HIPCHK(a, hipMemcpyAsync(q->v_stat, v->read_status, n * 4, hipMemcpyHostToDevice, st));
-  }
-  HIPCHK(a, hipStreamSynchronize(st));  // (`zero` and the caller's arrays have been read)
-  QuantBatch b;
-  memset(&b, 0, sizeof b);
-  b.n_reads = n;
-  b.n_alns = n_alns;
-  b.n_words = n_words;
-  b.aln_off = q->v_off;
-  b.alns = q->v_alns;
-  b.digests = q->v_dig;
-  b.words = q->v_words;
-  b.status = v->read_status && n ? q->v_stat.get() : nullptr;
   return add_batch(q, "thm_quant_add_view", b, info);
 }
 

@@ -1,11 +1,14 @@
-// coverage_tile.h -- the device-only pieces that the kernels over a difference array in coverage_device.h's layout share
-// (kernels_coverage.hip, kernels_pileup.hip): the sums over a wavefront, and the pass that brings one tile of cov::TILE
-// entries through LDS and scans it over the workgroup.
-#ifndef THERMITE_COVERAGE_TILE_H
-#define THERMITE_COVERAGE_TILE_H
+// summary_tile.h -- the device-only pieces that the kernels of the run summaries share (kernels_quant.hip,
+// kernels_coverage.hip, kernels_pileup.hip): the sums over a wavefront, the way a count kernel's totals leave its
+// workgroup and the read totals in front of it; and, for the two over a difference array in coverage_device.h's layout,
+// the two adds a block deposits and the pass that brings one tile of cov::TILE entries through LDS and scans it over the
+// workgroup.
+#ifndef THERMITE_SUMMARY_TILE_H
+#define THERMITE_SUMMARY_TILE_H
 #include <hip/hip_runtime.h>
 
 #include "coverage_device.h"
+#include "launch_io.h"
 
 namespace thm {
 namespace dev {
@@ -31,6 +34,39 @@ __device__ inline uint32_t cov_wave_max_u32(uint32_t v) {
   }
   return v;
 }
+__device__ inline uint64_t wave_sum(uint64_t v) { return cov_wave_sum_u64(v); }
+__device__ inline uint32_t wave_sum(uint32_t v) { return cov_wave_sum_u32(v); }
+
+// The end of a count kernel of 256 threads: the N totals a thread has summed in registers (T: as wide as its kernel
+// needs them) are summed per wavefront by shuffles, per workgroup in sh_tot (zeroed behind a barrier by the kernel's
+// beginning), and reach global memory as one add per total and workgroup.
+template <int N, class T>
+__device__ inline void block_totals(const T (&t)[N], unsigned long long* sh_tot, unsigned long long* totals) {
+  for (int k = 0; k < N; k++) {
+    const T s = wave_sum(t[k]);
+    if ((threadIdx.x & 63u) == 0 && s) atomicAdd(&sh_tot[k], (unsigned long long)s);
+  }
+  __syncthreads();
+  if (threadIdx.x < N && sh_tot[threadIdx.x]) atomicAdd(&totals[threadIdx.x], sh_tot[threadIdx.x]);
+}
+
+// the read totals of a batch, grid-stride with one thread per read: the reads, and those that failed
+__device__ inline void read_totals(const AlnBatch& b, uint64_t& n_reads, uint64_t& n_failed) {
+  const uint64_t stride = (uint64_t)gridDim.x * 256u;
+  for (uint64_t r = (uint64_t)blockIdx.x * 256u + threadIdx.x; r < b.n_reads; r += stride) {
+    n_reads++;
+    if (b.status && b.status[r] != THM_OK) n_failed++;
+  }
+}
+
+// what the deposit kernels hand to cov::walk_blocks: a block [s, e) is two integer adds (mod 2^32) without a return value
+struct BlockAdder {
+  uint32_t* dst;  // the contig's first entry (in the alignment's track)
+  __device__ void operator()(uint64_t s, uint64_t e) const {
+    (void)atomicAdd(dst + s, 1u);
+    (void)atomicAdd(dst + e, 0xFFFFFFFFu);
+  }
+};
 
 // Tile `tile` of diff[0, n) into LDS, the thread's own PER_THREAD consecutive entries into v[], and the exclusive scans
 // over the workgroup of their sum and of the number of non-zero ones.  The tile stays in `lds` (entry i at i + i / 16).
