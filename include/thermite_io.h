@@ -527,6 +527,108 @@ int32_t thm_pileup_window(thm_pileup* p, uint32_t ref_id, uint64_t start, uint64
 /* empties the difference array, the table and the totals */
 int32_t thm_pileup_reset(thm_pileup* p);
 
+/* ------------------------------------------------- cell-by-gene UMI count matrix of a run, built on the device */
+
+/* What a single-cell pipeline computes from the run's BAM by parsing every QNAME and sorting by (barcode, gene, UMI): the
+ * distinct molecules per cell and gene, accumulated on the device over any number of batches from what is resident there
+ * after thm_batch_run -- the alignments with their annotation, the per-read offsets (NH) and the read names.  Only rows
+ * of cells and matrix entries cross to the host.  These rules are the contract.
+ *   Where barcode and UMI come from (the convention of `umi_tools extract`).  QNAME is the read's name up to its first
+ *     space, the BAM layer's rule; a name without a space is all QNAME.  The QNAME carries a tag exactly when its last
+ *     cb_len + umi_len + 2 bytes are '_', cb_len bases, '_', umi_len bases, every base one of upper-case A C G T.
+ *     Anything else -- an N, lower case, a shorter QNAME, another separator -- means the read has no tag; what follows the
+ *     first space is never looked at; the prefix in front of the tag may be empty.  cb_len and umi_len are fixed at create,
+ *     each 1..16.  A sequence packs into 32 bits, 2 bits a base, A=0 C=1 G=2 T=3, the first base most significant (a
+ *     sequence of L bases fills the low 2 L bits), so integer order is lexicographic order.
+ *   Which reads count.  A read is counted exactly when its status is THM_OK, it has a tag, NH == 1 (NH as for thm_quant:
+ *     the alignments of the read), and its one alignment is exonic -- its gene is txs[tx_or_gene_idx].gene_idx -- or, only
+ *     with THM_CELLS_INTRONIC, intronic -- its gene is tx_or_gene_idx.  Every other read falls into exactly one total,
+ *     tested in this order: n_failed_reads (status), n_unmapped_reads (NH == 0), n_multi_reads (NH > 1),
+ *     n_intergenic_reads, n_intronic_skipped_reads (intronic without the flag), n_untagged_reads.  n_reads is the sum of
+ *     these six and n_counted_reads.  Strand relative to the gene is not considered, as in thm_quant; CIGAR words are not
+ *     needed, and an alignment with THM_DIGEST_LONG_RUN counts like any other.
+ *   Molecules.  A molecule is a distinct (barcode, gene, UMI); the object keeps one row of 16 bytes per molecule with a
+ *     32-bit count of its reads: an add that would bring totals.n_reads over 2^32 - 1 is refused with
+ *     THM_ERR_INVALID_ARG.  Batches in any cut and order give the same bytes from a fetch; adding the same run twice
+ *     doubles every n_reads and changes no n_umis. */
+typedef struct thm_cells thm_cells;
+
+#define THM_CELLS_INTRONIC 1u
+#define THM_CELLS_MAX_LEN 16u
+
+typedef struct thm_cell {
+  uint64_t n_reads;            /* counted reads of the cell */
+  uint32_t barcode;            /* packed */
+  uint32_t n_umis;             /* distinct molecules over all genes */
+  uint32_t n_genes;            /* genes with a molecule: the cell's entries */
+  uint32_t pad_;
+} thm_cell; /* 24 bytes */
+
+typedef struct thm_cell_entry {
+  uint32_t cell;               /* index into cells[] */
+  uint32_t gene;               /* index into the index's genes */
+  uint32_t n_umis;             /* distinct UMIs of (cell, gene): the matrix's value */
+  uint32_t n_reads;            /* their reads */
+} thm_cell_entry; /* 16 bytes */
+
+typedef struct thm_cells_totals {
+  uint64_t n_reads, n_failed_reads, n_unmapped_reads, n_multi_reads, n_intergenic_reads, n_intronic_skipped_reads;
+  uint64_t n_untagged_reads, n_counted_reads;
+} thm_cells_totals; /* 64 bytes */
+
+typedef struct thm_cells_info { /* what one add did */
+  thm_cells_totals batch;      /* this batch */
+  uint64_t n_molecules;        /* rows the object holds: the sorted table's distinct molecules plus n_pending */
+  uint64_t n_pending;          /* rows of batches not yet merged into the table (a molecule of the table, or of two such
+                                  batches, has a row in each): 0 when this add merged, and after every fetch */
+  uint64_t held_bytes;         /* device memory the object holds: the table, the pending rows and every scratch */
+  float add_ms;                /* device events, every pass of the add */
+} thm_cells_info;
+
+typedef struct thm_cells_view {
+  uint32_t cb_len, umi_len;
+  uint32_t min_umis, pad_;
+  uint64_t n_cells;
+  const thm_cell* cells;          /* [n_cells] ascending by barcode */
+  uint64_t n_entries;
+  const thm_cell_entry* entries;  /* [n_entries] ascending by (cell, gene) */
+  uint64_t n_molecules, n_barcodes;  /* distinct molecules and barcodes of the whole object */
+  uint64_t n_cells_below;         /* barcodes with fewer than min_umis molecules: n_barcodes - n_cells */
+  thm_cells_totals totals;        /* of the object so far */
+  float fetch_ms;                 /* device events: the merge of pending rows, the kernels, scans and the copies */
+} thm_cells_view;
+
+/* A thm_cells belongs to one aligner, like a thm_quant: it works on that aligner's device and stream and must be freed
+ * before it.  max_bytes (0: no cap but the device's memory) bounds the rows the object keeps, 16 bytes each, the sorted
+ * table's and the pending ones; the scratch of adds and fetches is not counted against it (held_bytes reports
+ * everything).  THM_ERR_INVALID_ARG: unknown bits in `flags`; cb_len or umi_len outside 1..16; with
+ * thm_batch_fetch_bam's message, an index without names.  THM_ERR_UNSUPPORTED: 2^30 genes or more. */
+int32_t thm_cells_create(thm_aligner* a, uint32_t flags, uint32_t cb_len, uint32_t umi_len, uint64_t max_bytes, thm_cells** out);
+void thm_cells_free(thm_cells* c);
+/* Stands where thm_batch_fetch stands after thm_batch_run, fails as thm_quant_add fails, runs the CIGAR passes itself
+ * (THM_T_CIGAR is put back) and disturbs no view, counter or timing.  The batch must have its names on the device
+ * (thm_batch_upload_reads or a thm_batch_upload_fastq*): otherwise THM_ERR_INVALID_ARG with thm_batch_fetch_bam's message
+ * for that.  One pass classifies every read and composes the keys of the counted ones (no byte of the names outside the
+ * batch's pool is read); these are compacted, sorted over the bits in use and reduced by key.  The reduced rows wait as
+ * pending rows behind those of earlier batches; once there are as many of them as the table has rows, and at every
+ * fetch, table and pending rows are sorted and reduced together into the new table, so the cost of an add does not grow
+ * with the table at every call.  The totals, the pending count and the swap to a merged table come last: a call that
+ * fails has added nothing.  THM_ERR_OOM: the rows held would exceed max_bytes even after a merge; the message names the
+ * bytes needed and the cap. */
+int32_t thm_cells_add(thm_cells* c, thm_cells_info* info);
+/* The same kernels over a caller-supplied view and the names of its reads (read r's is names[name_off[r], name_off[r + 1])),
+ * uploaded by the call.  The host checks first what thm_quant_add_view checks of the view's arrays, and that name_off
+ * starts at 0 and does not descend: THM_ERR_INVALID_ARG with a message naming the alignment or the read, and nothing is
+ * added. */
+int32_t thm_cells_add_view(thm_cells* c, const thm_cigar_view* v, const uint8_t* names, const uint64_t* name_off,
+                           thm_cells_info* info);
+/* The cells with min_umis molecules or more and their matrix entries, built on the device: a snapshot at any time, which
+ * changes nothing that a later fetch returns.  Both arrays arrive in a pinned buffer of the object's own, valid until
+ * the next fetch, reset or free.  THM_ERR_INVALID_ARG: min_umis == 0. */
+int32_t thm_cells_fetch(thm_cells* c, uint32_t min_umis, thm_cells_view* out);
+/* empties the table, the pending rows and the totals */
+int32_t thm_cells_reset(thm_cells* c);
+
 /* ------------------------------------------------- FASTQ blocks parsed on the device */
 
 typedef struct thm_fastq_upload_info {
@@ -765,7 +867,20 @@ typedef struct thm_run_stats {
  * 2, at least 1) are fetched and written as <output_path>.pileup.tsv: the header line "#contig pos ref depth A C G T N
  * del ins", then one line per site, tab-separated, pos 1-based, contigs in @SQ order.  A failure to write it is
  * THM_ERR_IO with the path; to standard output, and with more than one aligner (merging needs the depth of one device at
- * the sites of another, which is not done), the knob is refused with THM_ERR_INVALID_ARG. */
+ * the sites of another, which is not done), the knob is refused with THM_ERR_INVALID_ARG.
+ * THM_CELLS=1 or 2, in every format and mode, beside the other summaries or alone: the aligner keeps a thm_cells and every
+ * batch is added to it after its run (thm_cells_add); every batch goes up with its names (thm_batch_upload_reads where
+ * the host formats SAM or PAF), and the output file is the unset run's byte for byte.  THM_CELLS=1: exonic reads only;
+ * =2: THM_CELLS_INTRONIC.  THM_CELLS_CB_LEN (default 16) and THM_CELLS_UMI_LEN (default 12) are the tag's lengths, each
+ * 1..16; THM_CELLS_MIN_UMIS (default 1, at least 1) is the fetch's min_umis.  Any other THM_CELLS but 0, or one of the
+ * three that is no such number, is refused with THM_ERR_INVALID_ARG.  At the end three files are written whole:
+ * <output_path>.cells.mtx -- the line "%%MatrixMarket matrix coordinate integer general", the line "n_genes n_cells
+ * n_entries", then one line "gene+1 cell+1 n_umis" per entry in the entries' order --, <output_path>.cells.barcodes.tsv
+ * -- the unpacked barcode of every cell, a line each -- and <output_path>.cells.features.tsv -- gene_id, gene_name and
+ * "Gene Expression", tab-separated, a line per gene in index order.  A failure to write one is THM_ERR_IO with the path;
+ * to standard output, and with more than one aligner (the tables of two devices hold reduced counts: their distinct
+ * molecules are those of the union of their rows, which is not formed), the knob is refused with THM_ERR_INVALID_ARG.
+ * thm_run_stats is unchanged. */
 int32_t thm_align_files(thm_aligner* a, const char* const* fastq_paths, uint32_t n_paths, const char* output_path,
                         int32_t format, uint64_t batch_reads, uint32_t n_threads, thm_run_stats* stats);
 /* The same over several aligners -- one per GPU of the node, all over one index (the shape of ThermiteAligner: Clone +

@@ -275,6 +275,38 @@ class PileView(C.Structure):
                 ("sites", C.c_void_p), ("n_events", C.c_uint64), ("totals", PileTotals), ("fetch_ms", C.c_float)]
 
 
+CELLS_INTRONIC = 1
+CELLS_MAX_LEN = 16
+CELL_DT = np.dtype([("n_reads", "<u8"), ("barcode", "<u4"), ("n_umis", "<u4"), ("n_genes", "<u4"), ("pad_", "<u4")])
+CELL_ENTRY_DT = np.dtype([("cell", "<u4"), ("gene", "<u4"), ("n_umis", "<u4"), ("n_reads", "<u4")])
+assert CELL_DT.itemsize == 24 and CELL_ENTRY_DT.itemsize == 16
+CELLS_TOTAL_NAMES = ["n_reads", "n_failed_reads", "n_unmapped_reads", "n_multi_reads", "n_intergenic_reads", "n_intronic_skipped_reads",
+                     "n_untagged_reads", "n_counted_reads"]
+
+
+class CellsTotals(C.Structure):
+    """thm_cells_totals (include/thermite_io.h)"""
+
+    _fields_ = [(k, C.c_uint64) for k in CELLS_TOTAL_NAMES]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k in CELLS_TOTAL_NAMES}
+
+
+class CellsInfo(C.Structure):
+    """thm_cells_info (include/thermite_io.h)"""
+
+    _fields_ = [("batch", CellsTotals), ("n_molecules", C.c_uint64), ("n_pending", C.c_uint64), ("held_bytes", C.c_uint64), ("add_ms", C.c_float)]
+
+
+class CellsView(C.Structure):
+    """thm_cells_view (include/thermite_io.h)"""
+
+    _fields_ = [("cb_len", C.c_uint32), ("umi_len", C.c_uint32), ("min_umis", C.c_uint32), ("pad_", C.c_uint32), ("n_cells", C.c_uint64),
+                ("cells", C.c_void_p), ("n_entries", C.c_uint64), ("entries", C.c_void_p), ("n_molecules", C.c_uint64), ("n_barcodes", C.c_uint64),
+                ("n_cells_below", C.c_uint64), ("totals", CellsTotals), ("fetch_ms", C.c_float)]
+
+
 class FastqUploadInfo(C.Structure):
     """thm_fastq_upload_info (include/thermite_io.h)"""
 
@@ -351,6 +383,7 @@ IO_ABI_SYMBOLS = [
     "thm_coverage_create", "thm_coverage_free", "thm_coverage_add", "thm_coverage_add_view", "thm_coverage_fetch", "thm_coverage_depth",
     "thm_coverage_reset",
     "thm_pileup_create", "thm_pileup_free", "thm_pileup_add", "thm_pileup_add_view", "thm_pileup_fetch", "thm_pileup_window", "thm_pileup_reset",
+    "thm_cells_create", "thm_cells_free", "thm_cells_add", "thm_cells_add_view", "thm_cells_fetch", "thm_cells_reset",
 ]
 ERR_IO, ERR_FORMAT = -8, -9
 FMT_PAF, FMT_SAM, FMT_BAM = 0, 1, 2
@@ -574,6 +607,18 @@ def lib():
     L.thm_pileup_window.argtypes = [vp, C.c_uint32, C.c_uint64, C.c_uint64, vp]
     L.thm_pileup_reset.restype = i32
     L.thm_pileup_reset.argtypes = [vp]
+    L.thm_cells_create.restype = i32
+    L.thm_cells_create.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, vp]
+    L.thm_cells_free.restype = None
+    L.thm_cells_free.argtypes = [vp]
+    L.thm_cells_add.restype = i32
+    L.thm_cells_add.argtypes = [vp, vp]
+    L.thm_cells_add_view.restype = i32
+    L.thm_cells_add_view.argtypes = [vp, vp, vp, vp, vp]
+    L.thm_cells_fetch.restype = i32
+    L.thm_cells_fetch.argtypes = [vp, C.c_uint32, vp]
+    L.thm_cells_reset.restype = i32
+    L.thm_cells_reset.argtypes = [vp]
     L.thm_debug_bam_sorter_add_records.restype = i32
     L.thm_debug_bam_sorter_add_records.argtypes = [vp, vp, u64]
     L.thm_debug_bam_sorter_gather.restype = i32
@@ -1185,6 +1230,48 @@ class Pileup(_RunSummary):
         v = PileView()
         self.aligner._chk(lib().thm_pileup_window(self.h, ref_id, start, n, C.byref(v)))
         return PileupResult(v)
+
+
+class CellsResult:
+    """thm_cells_view copied out: the cells (CELL_DT, ascending by barcode), the entries (CELL_ENTRY_DT, ascending by cell,
+    gene), the object's counts and its totals as a dict"""
+
+    def __init__(self, view):
+        self.cb_len, self.umi_len, self.min_umis = int(view.cb_len), int(view.umi_len), int(view.min_umis)
+        self.cells = _copy(view.cells, view.n_cells, CELL_DT)
+        self.entries = _copy(view.entries, view.n_entries, CELL_ENTRY_DT)
+        self.n_molecules, self.n_barcodes, self.n_cells_below = int(view.n_molecules), int(view.n_barcodes), int(view.n_cells_below)
+        self.totals = view.totals.as_dict()
+        self.fetch_ms = view.fetch_ms
+
+
+class Cells(_RunSummary):
+    """thm_cells: the cell-by-gene matrix of distinct molecules of a run, accumulated on the aligner's device batch by
+    batch from the (barcode, UMI) tags of the read names.  Close it before its aligner."""
+
+    _NAME, _INFO, _INFO_FIELDS = "cells", CellsInfo, ("n_molecules", "n_pending")
+
+    def __init__(self, aligner, flags=0, cb_len=16, umi_len=12, max_bytes=0):
+        self.flags, self.cb_len, self.umi_len = flags, cb_len, umi_len
+        super().__init__(aligner, flags, cb_len, umi_len, max_bytes)
+
+    def add(self):
+        """thm_cells_add, after Aligner.run of a batch with names -> the batch's totals, n_molecules, n_pending, held_bytes
+        and add_ms as a dict"""
+        return self._add("add")
+
+    def add_view(self, offsets, alns, digests, cigar, names, name_off, status=None):
+        """thm_cells_add_view: the same kernels over caller-made arrays (ALN_DT, DIGEST_DT, CIGAR words) and the reads' names"""
+        v, _alive = _cigar_view(offsets, alns, digests, cigar, status)
+        nm = _u8(names)
+        no = np.ascontiguousarray(name_off, dtype="<u8")
+        return self._add("add_view", C.byref(v), _ptr(nm) if len(nm) else None, _ptr(no) if len(no) else None)
+
+    def fetch(self, min_umis=1):
+        """thm_cells_fetch: the cells with min_umis distinct molecules or more, and their (cell, gene) entries"""
+        v = CellsView()
+        self.aligner._chk(lib().thm_cells_fetch(self.h, min_umis, C.byref(v)))
+        return CellsResult(v)
 
 
 def cigar_text(words):

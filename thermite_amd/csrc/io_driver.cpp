@@ -41,6 +41,7 @@
 #include <utility>
 #include <vector>
 
+#include "cells_device.h"
 #include "fastq_cut.h"
 #include "inflate_device.h"
 #include "io_internal.h"
@@ -573,6 +574,11 @@ struct Modes {
   uint32_t pile_flags = 0;    // <output_path>.pileup.tsv is written at the end; =2: THM_PILE_MULTI
   uint32_t pile_min_alt = 2;  // THM_PILEUP_MIN_ALT: the events a site needs for a line (at least 1)
   bool pile_bad = false;      // THM_PILEUP is set to something else, or THM_PILEUP_MIN_ALT is no number of 1 or more: the run is refused
+  bool cells = false;         // THM_CELLS=1|2, any format, one aligner: every batch goes up with its names and is added to a thm_cells
+  uint32_t cells_flags = 0;   // behind its fetch; <output_path>.cells.mtx / .barcodes.tsv / .features.tsv are written at the end; =2: THM_CELLS_INTRONIC
+  uint32_t cells_cb_len = 16, cells_umi_len = 12;  // THM_CELLS_CB_LEN, THM_CELLS_UMI_LEN: the tag's lengths, each 1..16
+  uint32_t cells_min_umis = 1;                     // THM_CELLS_MIN_UMIS: the molecules a barcode needs to be a cell (at least 1)
+  bool cells_bad = false;     // THM_CELLS is set to something else, or one of the three is no such number: the run is refused
   static Modes read(int32_t format) {
     auto is = [](const char* name, const char* v) {
       const char* e = getenv(name);
@@ -601,6 +607,22 @@ struct Modes {
       else
         m.pile_min_alt = (uint32_t)v;
     }
+    m.cells = is("THM_CELLS", "1") || is("THM_CELLS", "2");
+    m.cells_flags = is("THM_CELLS", "2") ? THM_CELLS_INTRONIC : 0u;
+    if (const char* e = getenv("THM_CELLS")) m.cells_bad = *e && strcmp(e, "0") && !m.cells;
+    const auto number = [&](const char* name, long most, uint32_t* out) {
+      const char* e = getenv(name);
+      if (!e) return;
+      char* end = nullptr;
+      const long v = strtol(e, &end, 10);
+      if (end == e || *end || v < 1 || v > most)
+        m.cells_bad = true;
+      else
+        *out = (uint32_t)v;
+    };
+    number("THM_CELLS_CB_LEN", (long)THM_CELLS_MAX_LEN, &m.cells_cb_len);
+    number("THM_CELLS_UMI_LEN", (long)THM_CELLS_MAX_LEN, &m.cells_umi_len);
+    number("THM_CELLS_MIN_UMIS", 0x7FFFFFFFl, &m.cells_min_umis);
     return m;
   }
 };
@@ -722,6 +744,7 @@ struct Run {
   thm_quant* const* quants = nullptr;  // THM_QUANT=1: one per aligner
   thm_coverage* const* coverages = nullptr;  // THM_COVERAGE: one per aligner
   thm_pileup* pileup = nullptr;              // THM_PILEUP: the one aligner's
+  thm_cells* cells = nullptr;                // THM_CELLS: the one aligner's
 
   Shared sh;
   thm_run_stats st;
@@ -1127,7 +1150,7 @@ void Run::gpu(uint32_t gi) {
     if (have) {
       const thm_read_batch rb = s->reads.view();
       int grc = sh.step([&] {
-        int g2 = raw_up ? up_rc : m.bam_device ? thm_batch_upload_reads(a, &rb) : thm_batch_upload(a, rb.bases, rb.offsets, rb.n_reads);
+        int g2 = raw_up ? up_rc : (m.bam_device || m.cells) ? thm_batch_upload_reads(a, &rb) : thm_batch_upload(a, rb.bases, rb.offsets, rb.n_reads);
         if (g2 == THM_OK) g2 = thm_batch_run(a);
         if (g2 == THM_OK) g2 = thm_batch_sync(a);
         return g2;
@@ -1149,6 +1172,10 @@ void Run::gpu(uint32_t gi) {
       if (grc == THM_OK && pileup) {
         thm_pile_info pi;
         grc = sh.step([&] { return (int)thm_pileup_add(pileup, &pi); });
+      }
+      if (grc == THM_OK && cells) {
+        thm_cells_info ci;
+        grc = sh.step([&] { return (int)thm_cells_add(cells, &ci); });
       }
       if (grc != THM_OK) {
         sh.set(grc, thm_last_error(a));
@@ -1450,17 +1477,21 @@ int write_coverage_tracks(const thm_index* ix, thm_aligner* const* aligners, thm
   return THM_OK;
 }
 
-// The summaries a run was asked for, one quant and one coverage per aligner and the one aligner's pileup: they go when
-// their owner does (or at free()), the pileup first, then the coverages, then the quants, all before their aligners.
+// The summaries a run was asked for, one quant and one coverage per aligner and the one aligner's pileup and cells: they
+// go when their owner does (or at free()), the cells first, then the pileup, the coverages, the quants, all before their
+// aligners.
 struct Summaries {
   std::vector<thm_quant*> quants;
   std::vector<thm_coverage*> coverages;
   thm_pileup* pileup = nullptr;
+  thm_cells* cells = nullptr;
   Summaries() = default;
   Summaries(const Summaries&) = delete;
   Summaries& operator=(const Summaries&) = delete;
   ~Summaries() { free(); }
   void free() {
+    thm_cells_free(cells);
+    cells = nullptr;
     thm_pileup_free(pileup);
     for (thm_coverage* c : coverages) thm_coverage_free(c);
     for (thm_quant* q : quants) thm_quant_free(q);
@@ -1493,6 +1524,46 @@ int write_pileup_sites(const thm_index* ix, thm_aligner* a, thm_pileup* pileup, 
   if (!o.close() || !ok) {
     err = "cannot write " + path;
     return THM_ERR_IO;
+  }
+  return THM_OK;
+}
+
+// THM_CELLS: the cells with min_umis molecules or more as <output_path>.cells.mtx, .cells.barcodes.tsv and
+// .cells.features.tsv
+int write_cells_matrix(const thm_index* ix, thm_aligner* a, thm_cells* cells, uint32_t min_umis, const std::string& output_path, std::string& err) {
+  thm_cells_view v;
+  const int rc = thm_cells_fetch(cells, min_umis, &v);
+  if (rc != THM_OK) {
+    err = thm_last_error(a);
+    return rc;
+  }
+  std::string mtx = "%%MatrixMarket matrix coordinate integer general\n";
+  mtx += std::to_string(ix->genes.size()) + " " + std::to_string(v.n_cells) + " " + std::to_string(v.n_entries) + "\n";
+  for (uint64_t i = 0; i < v.n_entries; i++) {
+    const thm_cell_entry& e = v.entries[i];
+    mtx += std::to_string(e.gene + 1) + " " + std::to_string(e.cell + 1) + " " + std::to_string(e.n_umis) + "\n";
+  }
+  std::string barcodes;
+  for (uint64_t i = 0; i < v.n_cells; i++) {
+    char text[THM_CELLS_MAX_LEN];
+    thm::cells::unpack_bases(v.cells[i].barcode, v.cb_len, text);
+    barcodes.append(text, v.cb_len);
+    barcodes += "\n";
+  }
+  std::string features;
+  for (size_t g = 0; g < ix->genes.size(); g++) {
+    const char *id = thm_index_gene_id(ix, (uint32_t)g), *name = thm_index_gene_name(ix, (uint32_t)g);
+    features += std::string(id ? id : "") + "\t" + (name ? name : "") + "\tGene Expression\n";
+  }
+  const std::pair<const char*, const std::string*> files[3] = {{".cells.mtx", &mtx}, {".cells.barcodes.tsv", &barcodes}, {".cells.features.tsv", &features}};
+  for (const auto& f : files) {
+    const std::string path = output_path + f.first;
+    Output o;
+    const bool ok = o.open(path.c_str()) && o.write_all(f.second->data(), f.second->size(), 0);
+    if (!o.close() || !ok) {
+      err = "cannot write " + path;
+      return THM_ERR_IO;
+    }
   }
   return THM_OK;
 }
@@ -1535,6 +1606,22 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
   }
   if (m.pileup && n_aligners > 1) {
     thm::set_global_error("thm_align_files_multi: THM_PILEUP takes one aligner (merging across devices is not done)");
+    return THM_ERR_INVALID_ARG;
+  }
+  if (m.cells_bad) {
+    thm::set_global_error(
+        "thm_align_files_multi: THM_CELLS must be 1 or 2 (or 0, or unset), THM_CELLS_CB_LEN and THM_CELLS_UMI_LEN numbers of 1..16 and THM_CELLS_MIN_UMIS a number of 1 or "
+        "more");
+    return THM_ERR_INVALID_ARG;
+  }
+  if (m.cells && !strcmp(output_path, "-")) {
+    thm::set_global_error("thm_align_files_multi: THM_CELLS needs an output file (the matrix is written beside it)");
+    return THM_ERR_INVALID_ARG;
+  }
+  if (m.cells && n_aligners > 1) {
+    thm::set_global_error(
+        "thm_align_files_multi: THM_CELLS takes one aligner (the tables of two devices hold reduced counts: their distinct molecules are those of the union of their rows, "
+        "which is not formed)");
     return THM_ERR_INVALID_ARG;
   }
   const thm_index* ix = thm_aligner_index(aligners[0]);
@@ -1580,6 +1667,7 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
   for (size_t i = 0; i < sums.coverages.size(); i++)
     if ((rc = thm_coverage_create(aligners[i], m.cov_flags, 0, &sums.coverages[i])) != THM_OK) return not_created(aligners[i]);
   if (m.pileup && (rc = thm_pileup_create(aligners[0], m.pile_flags, 0, &sums.pileup)) != THM_OK) return not_created(aligners[0]);
+  if (m.cells && (rc = thm_cells_create(aligners[0], m.cells_flags, m.cells_cb_len, m.cells_umi_len, 0, &sums.cells)) != THM_OK) return not_created(aligners[0]);
   const auto t_start = Clock::now();
   thm_writer* w2 = nullptr;
   const bool have_w2 = thm_writer_create(ix, format, n_threads, &w2) == THM_OK;
@@ -1590,6 +1678,7 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
   if (m.quant) run.quants = sums.quants.data();
   if (m.coverage) run.coverages = sums.coverages.data();
   run.pileup = sums.pileup;
+  run.cells = sums.cells;
   // ---- the stages: the cutter, the parsers, a thread per aligner; this thread formats
   std::thread cutter(&Run::cut, &run);
   std::vector<std::thread> parsers, gpus;
@@ -1617,6 +1706,11 @@ extern "C" int32_t thm_align_files_multi(thm_aligner* const* aligners, uint32_t 
     std::string err;
     const int prc = run.sh.step([&] { return write_pileup_sites(ix, aligners[0], sums.pileup, m.pile_min_alt, output_path, err); });
     if (prc != THM_OK) run.sh.set(prc, err);
+  }
+  if (m.cells && run.sh.rc == THM_OK) {
+    std::string err;
+    const int crc = run.sh.step([&] { return write_cells_matrix(ix, aligners[0], sums.cells, m.cells_min_umis, output_path, err); });
+    if (crc != THM_OK) run.sh.set(crc, err);
   }
   sums.free();  // (in front of the sorter and the writer, and inside wall_s, as they always were)
   thm_bam_sorter_free(sorter);

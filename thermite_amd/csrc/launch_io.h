@@ -99,10 +99,10 @@ hipError_t launch_bam_sort_order(const uint32_t* ord, const uint32_t* len, const
 // by_records: the record-centric shape (a wavefront per record), else the output-centric one (16 bytes a lane)
 hipError_t launch_bam_sort_gather(const BamSortGatherParams& p, bool by_records, int n_cu, hipStream_t s);
 
-// ---- what every summary of a run walks (quant, coverage, pileup below; host side run_summary.h) ----
+// ---- what every summary of a run walks (quant, coverage, pileup, cells below; host side run_summary.h) ----
 // The alignments of one batch on the device: the compacted records of the batch that is resident after thm_batch_run
 // with the digests and words of the CIGAR passes, or the arrays of a caller's thm_cigar_view.  The batch structs of the
-// three summaries begin with it and add their own tables; they go to the kernels by value.
+// summaries begin with it and add their own tables; they go to the kernels by value.
 struct AlnBatch {
   uint64_t n_reads, n_alns, n_words;
   const uint64_t* aln_off;        // [n_reads + 1]
@@ -324,6 +324,69 @@ hipError_t launch_pile_bounds(const PileFetchParams& p, hipStream_t s);
 hipError_t launch_pile_keep(const PileFetchParams& p, hipStream_t s);
 hipError_t launch_pile_sites(const PileFetchParams& p, hipStream_t s);
 hipError_t launch_pile_window(const PileFetchParams& p, hipStream_t s);
+
+// ---- cell-by-gene UMI count matrix of a run (kernels_cells.hip, cells_device.h; host side cells.hip) ----
+// add:   classify (a thread per read: its class, the tag of its name, its key and a flag; the totals) -> scan of the
+//        flags ... the host reads the totals and the first bad alignment ... compact (the counted reads' keys) -> sort,
+//        low word then high word, over the bits in use -> heads, scan, head_at, reduce (a row per molecule with its reads)
+//        -> the rows go behind the pending ones, or table + pending + rows through the same sort and reduce.
+// fetch: (pending rows merged as in add) levels (per row: begins a barcode, begins a (barcode, gene), its reads) -> three
+//        scans -> starts (where every barcode and entry begins) -> barcodes (kept or not, its entries) -> two scans ->
+//        cells, entries (the rows of the kept ones at their new numbers).
+struct CellsBatch : AlnBatch {
+  const uint8_t* names;           // read r's name is names[name_off[r], name_off[r + 1])
+  const uint64_t* name_off;       // [n_reads + 1]
+  uint32_t n_txs, n_genes;
+  const uint32_t* tx_gene;        // [n_txs]
+  uint32_t flags;                 // THM_CELLS_*
+  uint32_t cb_len, umi_len;
+};
+struct CellsClassifyParams {
+  CellsBatch b;
+  uint64_t* counted;           // [n_reads + 1] 1: the read is counted, for the scan
+  uint64_t *hc, *lo;           // [n_reads] the key of a counted read, its count 1
+  unsigned long long* totals;  // [cells::N_TOTALS] zeroed by the caller
+  unsigned long long* bad;     // the first alignment with a type or an index out of range (atomic minimum; ~0: none)
+};
+struct CellsCompactParams {
+  uint64_t n_reads;
+  const uint64_t* counted;     // [n_reads]
+  const uint64_t* at;          // [n_reads + 1] its scan
+  const uint64_t *hc, *lo;     // [n_reads]
+  uint64_t *out_hc, *out_lo;   // [at[n_reads]]
+};
+struct CellsReduceParams {
+  const uint64_t *hc, *lo;     // [n] sorted rows
+  uint64_t n;
+  uint64_t* flag;              // [n + 1] heads: 1 where a molecule begins
+  const uint64_t* first;       // [n + 1] its scan
+  uint64_t* head_at;           // [n_keys + 1] head_at: where every molecule begins, and n behind them
+  uint64_t n_keys;
+  uint32_t unit;               // 1: every row's count is 1 (a batch's reads): a molecule's count is its run's length
+  uint64_t *out_hc, *out_lo;   // [n_keys] reduce
+};
+struct CellsFetchParams {
+  const uint64_t *hc, *lo;     // [n] the table
+  uint64_t n;
+  uint32_t umi_len, min_umis;
+  uint64_t *bflag, *eflag, *cnt;               // [n + 1] levels
+  const uint64_t *b_at, *e_at, *pre;           // [n + 1] their scans
+  uint64_t n_barcodes, n_all_entries;          // b_at[n], e_at[n]
+  uint64_t *bc_start, *ent_start;              // [n_barcodes + 1], [n_all_entries + 1] starts
+  uint64_t *keep, *kept_entries;               // [n_barcodes + 1] barcodes
+  const uint64_t *cell_at, *ent_at;            // [n_barcodes + 1] their scans
+  thm_cell* cells;                             // [cell_at[n_barcodes]]
+  thm_cell_entry* entries;                     // [ent_at[n_barcodes]]
+};
+hipError_t launch_cells_classify(const CellsClassifyParams& p, int n_cu, hipStream_t s);
+hipError_t launch_cells_compact(const CellsCompactParams& p, hipStream_t s);
+hipError_t launch_cells_heads(const CellsReduceParams& p, hipStream_t s);
+hipError_t launch_cells_head_at(const CellsReduceParams& p, hipStream_t s);
+hipError_t launch_cells_reduce(const CellsReduceParams& p, hipStream_t s);
+hipError_t launch_cells_levels(const CellsFetchParams& p, hipStream_t s);
+hipError_t launch_cells_starts(const CellsFetchParams& p, hipStream_t s);
+hipError_t launch_cells_barcodes(const CellsFetchParams& p, hipStream_t s);
+hipError_t launch_cells_rows(const CellsFetchParams& p, hipStream_t s);
 
 // ---- BAI index of the sorted stream (kernels_bai.hip, bai_device.h; host side bai.hip) ----
 // fields (per sorted record: key = refID << 16 | bin, beg, end; per reference the mapped count and n_intv) -> run heads,

@@ -1,4 +1,4 @@
-// run_summary.h -- the host side that the summaries of a run share (quant.hip, coverage.hip, pileup.hip): each walks the
+// run_summary.h -- the host side that the summaries of a run share (quant.hip, coverage.hip, pileup.hip, cells.hip): each walks the
 // alignments of a batch -- the one resident after thm_batch_run, or a caller's thm_cigar_view -- and accumulates something
 // on the aligner's device.  Here are the description of that batch (thm::AlnBatch, launch_io.h) from either source, the
 // host's checks of a view, the totals of a batch with the first refused alignment behind them, the contig layout and the
